@@ -644,6 +644,15 @@ osr_status osr_rpn_gather_cols(const osr_rpn_levels* lv, const osr_pyramid* feat
 osr_status osr_rpn_scatter_cols_add(const osr_rpn_levels* lv, int32_t n, const int32_t* row_map, const float* y,
                                     void* const* grads, int32_t grad_dtype, void* stream);
 
+/* The same two with the gradient row width as a parameter (1..64): the stock RPN head's backward lists the rows of its
+ * (rows, 5A) gradient (osr_std_rpn_losses_bwd) -- lv is then the PIXEL level table (num_anchors 1). osr_rpn_sparse_rows(...) =
+ * osr_rpn_sparse_rows_ex(..., width 5, ...), osr_rpn_gather_cols likewise; d_rows_listed is (cap, width). */
+osr_status osr_rpn_sparse_rows_ex(const float* d_rows, int64_t rows, int32_t width, int32_t cap, int32_t* row_ids, int32_t* row_map,
+                                  int32_t* count2, void* workspace, int64_t workspace_bytes, void* stream);
+osr_status osr_rpn_gather_cols_ex(const osr_rpn_levels* lv, const osr_pyramid* feats, int32_t feat_dtype, int32_t n,
+                                  const int32_t* row_ids, int32_t cap, const float* d_rows, int32_t width, void* cols,
+                                  float* d_rows_listed, void* stream);
+
 /* Gradient of osr_roi_box_losses_fwd w.r.t. the (m,5) predictor output {4 deltas, IoU logit}. workspace 16 bytes. */
 osr_status osr_roi_box_losses_bwd(const float* pred5, const float* proposal_boxes, const float* gt_boxes,
                                   const int64_t* gt_classes, const float* gt_iou, int64_t m, int32_t num_classes,
@@ -672,6 +681,49 @@ osr_status osr_pln_loss_bwd_ex(const float* emb, int64_t m, int32_t d, const flo
                                float iou_thr, float alpha, float beta, float loss_weight, float loss_scale, float* d_emb,
                                float* d_protos, int32_t accumulate_protos, void* workspace, int64_t workspace_bytes,
                                void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * Training step of the stock detectron2 heads (Base-RCNN-FPN.yaml: RPN + StandardRPNHead, StandardROIHeads +
+ * FastRCNNOutputLayers; csrc/osr_std_train.hip). Deterministic two-stage reductions as above.
+ * --------------------------------------------------------------------------------------------------------- */
+/* [d2] RPN.losses. pred_logits (rows*A) / pred_deltas (rows*A, 4): level-major as the head's GEMMs write them (levels->offset
+ * counts anchors); labels (n,R) int8 in {-1,0,1} and matched_boxes (n,R,4): image-major, as osr_rpn_match_anchors /
+ * osr_subsample_labels / osr_rpn_anchor_targets write them. loss_rpn_cls = sum_{label>=0} BCEWithLogits(logit, label) *
+ * cls_weight / (batch_size_per_image * n); loss_rpn_loc = sum_{label=1} smooth_l1(delta - get_deltas(anchor, gt; b2b_weights),
+ * beta) * loc_weight / (batch_size_per_image * n). out4 = {loss_rpn_cls, loss_rpn_loc, num_pos, num_neg}. workspace 4 KiB. */
+osr_status osr_std_rpn_losses_fwd(const osr_rpn_levels* levels, const float* cell_anchors, int32_t n, const float* pred_logits,
+                                  const float* pred_deltas, const int8_t* labels, const float* matched_boxes,
+                                  const float b2b_weights[4], float smooth_l1_beta, float cls_weight, float loc_weight,
+                                  int32_t batch_size_per_image, float* out4, void* workspace, int64_t workspace_bytes,
+                                  void* stream);
+/* Its gradient, times loss_scale, as ONE (rows, 5A) fp32 buffer over the pixel rows: columns [0, A) the logits, [A, 5A) the
+ * deltas (anchor a at A + 4a). Every element is written; only sampled anchors are non-zero. */
+osr_status osr_std_rpn_losses_bwd(const osr_rpn_levels* levels, const float* cell_anchors, int32_t n, const float* pred_logits,
+                                  const float* pred_deltas, const int8_t* labels, const float* matched_boxes,
+                                  const float b2b_weights[4], float smooth_l1_beta, float cls_weight, float loc_weight,
+                                  int32_t batch_size_per_image, float loss_scale, float* d_rows, void* stream);
+/* [d2] FastRCNNOutputLayers.losses over m sampled rows (gt_classes: 0..K-1 foreground, K background, -1 padding -- skipped and
+ * not counted). logits (m, K+1); pred_deltas rows of delta_stride floats: the 4 deltas at column 0 (cls_agnostic) or at 4c for
+ * GT class c. loss_cls = mean cross entropy * cls_weight; loss_box_reg = sum_fg smooth_l1(delta - get_deltas(proposal, gt;
+ * reg_weights), beta) * box_weight / max(rows, 1). out7 = {loss_cls, loss_box_reg, rows, correct, foreground, foreground
+ * correct, foreground predicted as background} (argmax: first maximum). workspace 7 KiB. */
+osr_status osr_fastrcnn_losses_fwd(const float* logits, const float* pred_deltas, int32_t delta_stride, int32_t cls_agnostic,
+                                   const float* proposal_boxes, const float* gt_boxes, const int64_t* gt_classes, int64_t m,
+                                   int32_t num_classes, const float reg_weights[4], float smooth_l1_beta, float cls_weight,
+                                   float box_weight, float* out7, void* workspace, int64_t workspace_bytes, void* stream);
+/* Its gradient times loss_scale: d_logits (m, K+1), d_deltas (m, delta_stride); every element written. workspace 16 bytes. */
+osr_status osr_fastrcnn_losses_bwd(const float* logits, const float* pred_deltas, int32_t delta_stride, int32_t cls_agnostic,
+                                   const float* proposal_boxes, const float* gt_boxes, const int64_t* gt_classes, int64_t m,
+                                   int32_t num_classes, const float reg_weights[4], float smooth_l1_beta, float cls_weight,
+                                   float box_weight, float loss_scale, float* d_logits, float* d_deltas, void* workspace,
+                                   int64_t workspace_bytes, void* stream);
+/* StandardRPNHead tail backward: t (rows,256) fp32 hidden state after the 3x3 conv's ReLU, w_tail (width,256) = [W_obj; W_delta],
+ * d_rows (rows, width). dt (rows,256) fp16/bf16 = (d_rows . w_tail) masked by t > 0; dw_tail (width,256) = d_rows^T . t;
+ * db_tail (width) = column sums of d_rows. width = 5A, A = 1..8. */
+int64_t osr_std_rpn_tail_bwd_workspace_bytes(void);
+osr_status osr_std_rpn_tail_bwd(const float* t, int64_t rows, const float* w_tail, int32_t width, const float* d_rows, void* dt,
+                                int32_t dt_dtype, float* dw_tail, float* db_tail, void* workspace, int64_t workspace_bytes,
+                                void* stream);
 
 /* RoIAlign backward: d feature pyramid (fp32 NHWC per level, zero-initialised by the caller; `dfeat->data` are written)
  * += scatter of dout (m,P,P,c) with the forward's geometry; fp32 atomic adds. */

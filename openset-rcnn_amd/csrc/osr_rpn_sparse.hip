@@ -23,24 +23,35 @@
 #define RS_BLOCKS 1024
 #define RS_THREADS 256
 
-__device__ __forceinline__ bool rs_row_nonzero(const float* __restrict__ d5, long long r) {
-    const float* g = d5 + r * 5;
-    return g[0] != 0.f || g[1] != 0.f || g[2] != 0.f || g[3] != 0.f || g[4] != 0.f;  // (NaN counts: it must reach the overflow check)
+// W > 0: the row width at compile time (5: the CF-RPN head); W == 0: `width` at run time (the _ex entry points)
+template <int W>
+__device__ __forceinline__ bool rs_row_nonzero(const float* __restrict__ d5, long long r, int width) {
+    if (W == 5) {
+        const float* g = d5 + r * 5;
+        return g[0] != 0.f || g[1] != 0.f || g[2] != 0.f || g[3] != 0.f || g[4] != 0.f;  // (NaN counts: it must reach the overflow check)
+    }
+    const int wd = W > 0 ? W : width;
+    const float* g = d5 + r * wd;
+    bool any = false;
+    for (int q = 0; q < wd; ++q) any |= g[q] != 0.f;
+    return any;
 }
 
 // rows [b * per, (b + 1) * per) belong to workgroup b, walked 256 at a time in ascending order
-__global__ __launch_bounds__(RS_THREADS) void rs_count_kernel(const float* __restrict__ d5, long long rows, long long per, int* __restrict__ block_counts) {
+template <int W>
+__global__ __launch_bounds__(RS_THREADS) void rs_count_kernel(const float* __restrict__ d5, long long rows, long long per, int width, int* __restrict__ block_counts) {
     __shared__ int s_c[RS_THREADS / 64];
     const long long r0 = (long long)blockIdx.x * per, r1 = r0 + per < rows ? r0 + per : rows;
     int cnt = 0;
-    for (long long r = r0 + threadIdx.x; r < r1; r += RS_THREADS) cnt += rs_row_nonzero(d5, r) ? 1 : 0;
+    for (long long r = r0 + threadIdx.x; r < r1; r += RS_THREADS) cnt += rs_row_nonzero<W>(d5, r, width) ? 1 : 0;
     cnt = (int)osr_wave_sum((float)cnt);  // (< 2^24: exact)
     if ((threadIdx.x & 63) == 0) s_c[threadIdx.x >> 6] = cnt;
     __syncthreads();
     if (threadIdx.x == 0) block_counts[blockIdx.x] = s_c[0] + s_c[1] + s_c[2] + s_c[3];
 }
 
-__global__ __launch_bounds__(RS_THREADS) void rs_fill_kernel(const float* __restrict__ d5, long long rows, long long per, const int* __restrict__ block_counts,
+template <int W>
+__global__ __launch_bounds__(RS_THREADS) void rs_fill_kernel(const float* __restrict__ d5, long long rows, long long per, int width, const int* __restrict__ block_counts,
                                                             int cap, int* __restrict__ row_ids, int* __restrict__ row_map, int* __restrict__ count2) {
     __shared__ int s_w[RS_THREADS / 64], s_pre[RS_THREADS / 64], s_tot[RS_THREADS / 64];
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
@@ -62,7 +73,7 @@ __global__ __launch_bounds__(RS_THREADS) void rs_fill_kernel(const float* __rest
     const long long r0 = (long long)blockIdx.x * per, r1 = r0 + per < rows ? r0 + per : rows;
     for (long long rb = r0; rb < r1; rb += RS_THREADS) {
         const long long r = rb + threadIdx.x;
-        const bool hit = r < r1 && rs_row_nonzero(d5, r);
+        const bool hit = r < r1 && rs_row_nonzero<W>(d5, r, width);
         const unsigned long long bal = __ballot(hit);
         __syncthreads();  // (s_w of the previous turn has been read)
         if (lane == 0) s_w[wid] = __popcll(bal);
@@ -81,19 +92,33 @@ __global__ __launch_bounds__(RS_THREADS) void rs_fill_kernel(const float* __rest
 
 extern "C" int64_t osr_rpn_sparse_rows_workspace_bytes(void) { return (int64_t)RS_BLOCKS * 4; }
 
-extern "C" osr_status osr_rpn_sparse_rows(const float* d_out5, int64_t rows, int32_t cap, int32_t* row_ids, int32_t* row_map, int32_t* count2,
-                                          void* workspace, int64_t workspace_bytes, void* stream) {
-    OSR_REQUIRE(d_out5 && row_ids && row_map && count2 && workspace, OSR_ERR_INVALID_ARG, "osr_rpn_sparse_rows: null pointer");
-    OSR_REQUIRE(rows >= 1 && rows < (1ll << 31) && cap >= 1, OSR_ERR_INVALID_ARG, "osr_rpn_sparse_rows: bad rows / cap");
+static osr_status rs_sparse_rows(const float* d_rows, int64_t rows, int32_t width, int32_t cap, int32_t* row_ids, int32_t* row_map, int32_t* count2,
+                                 void* workspace, int64_t workspace_bytes, void* stream) {
+    OSR_REQUIRE(d_rows && row_ids && row_map && count2 && workspace, OSR_ERR_INVALID_ARG, "osr_rpn_sparse_rows: null pointer");
+    OSR_REQUIRE(rows >= 1 && rows < (1ll << 31) && cap >= 1 && width >= 1 && width <= 64, OSR_ERR_INVALID_ARG, "osr_rpn_sparse_rows: bad rows / cap / width");
     OSR_REQUIRE(workspace_bytes >= osr_rpn_sparse_rows_workspace_bytes(), OSR_ERR_WORKSPACE, "osr_rpn_sparse_rows: workspace too small");
     hipStream_t st = (hipStream_t)stream;
     long long per = (rows + RS_BLOCKS - 1) / RS_BLOCKS;
     per = (per + RS_THREADS - 1) / RS_THREADS * RS_THREADS;
-    hipLaunchKernelGGL(rs_count_kernel, dim3(RS_BLOCKS), dim3(RS_THREADS), 0, st, d_out5, (long long)rows, per, (int*)workspace);
+    if (width == 5) hipLaunchKernelGGL(rs_count_kernel<5>, dim3(RS_BLOCKS), dim3(RS_THREADS), 0, st, d_rows, (long long)rows, per, width, (int*)workspace);
+    else hipLaunchKernelGGL(rs_count_kernel<0>, dim3(RS_BLOCKS), dim3(RS_THREADS), 0, st, d_rows, (long long)rows, per, width, (int*)workspace);
     OSR_CHECK_LAUNCH("osr_rpn_sparse_rows(count)");
-    hipLaunchKernelGGL(rs_fill_kernel, dim3(RS_BLOCKS), dim3(RS_THREADS), 0, st, d_out5, (long long)rows, per, (const int*)workspace, cap, row_ids, row_map, count2);
+    if (width == 5)
+        hipLaunchKernelGGL(rs_fill_kernel<5>, dim3(RS_BLOCKS), dim3(RS_THREADS), 0, st, d_rows, (long long)rows, per, width, (const int*)workspace, cap, row_ids, row_map, count2);
+    else
+        hipLaunchKernelGGL(rs_fill_kernel<0>, dim3(RS_BLOCKS), dim3(RS_THREADS), 0, st, d_rows, (long long)rows, per, width, (const int*)workspace, cap, row_ids, row_map, count2);
     OSR_CHECK_LAUNCH("osr_rpn_sparse_rows(fill)");
     return OSR_OK;
+}
+
+extern "C" osr_status osr_rpn_sparse_rows(const float* d_out5, int64_t rows, int32_t cap, int32_t* row_ids, int32_t* row_map, int32_t* count2,
+                                          void* workspace, int64_t workspace_bytes, void* stream) {
+    return rs_sparse_rows(d_out5, rows, 5, cap, row_ids, row_map, count2, workspace, workspace_bytes, stream);
+}
+
+extern "C" osr_status osr_rpn_sparse_rows_ex(const float* d_rows, int64_t rows, int32_t width, int32_t cap, int32_t* row_ids, int32_t* row_map,
+                                             int32_t* count2, void* workspace, int64_t workspace_bytes, void* stream) {
+    return rs_sparse_rows(d_rows, rows, width, cap, row_ids, row_map, count2, workspace, workspace_bytes, stream);
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -118,7 +143,7 @@ __device__ __forceinline__ void rs_decode(const RsGeom& g, long long r, int& l, 
 }
 
 // one wave per (list slot, tap): 64 lanes x 8 bytes = the 256 channels of one pixel
-__global__ __launch_bounds__(256) void rs_gather_kernel(RsGeom g, const int* __restrict__ row_ids, int cap, const float* __restrict__ d5,
+__global__ __launch_bounds__(256) void rs_gather_kernel(RsGeom g, const int* __restrict__ row_ids, int cap, const float* __restrict__ d5, int width,
                                                         uint2* __restrict__ cols, float* __restrict__ d5c) {
     const int lane = threadIdx.x & 63;
     const long long gw = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -134,16 +159,16 @@ __global__ __launch_bounds__(256) void rs_gather_kernel(RsGeom g, const int* __r
             v = reinterpret_cast<const uint2*>(g.feat[l])[(((long long)img * g.h[l] + yy) * g.w[l] + xx) * 64 + lane];
     }
     cols[gw * 64 + lane] = v;
-    if (tap == 0 && lane < 5) d5c[(long long)j * 5 + lane] = rid >= 0 ? d5[(long long)rid * 5 + lane] : 0.f;
+    if (tap == 0 && lane < width) d5c[(long long)j * width + lane] = rid >= 0 ? d5[(long long)rid * width + lane] : 0.f;
 }
 
-extern "C" osr_status osr_rpn_gather_cols(const osr_rpn_levels* lv, const osr_pyramid* feats, int32_t feat_dtype, int32_t n, const int32_t* row_ids,
-                                          int32_t cap, const float* d_out5, void* cols, float* d_out5_rows, void* stream) {
+static osr_status rs_gather_cols(const osr_rpn_levels* lv, const osr_pyramid* feats, int32_t feat_dtype, int32_t n, const int32_t* row_ids,
+                                 int32_t cap, const float* d_out5, int32_t width, void* cols, float* d_out5_rows, void* stream) {
     OSR_REQUIRE(lv && feats && row_ids && d_out5 && cols && d_out5_rows, OSR_ERR_INVALID_ARG, "osr_rpn_gather_cols: null pointer");
     OSR_REQUIRE(feat_dtype == OSR_F16 || feat_dtype == OSR_BF16, OSR_ERR_UNSUPPORTED, "osr_rpn_gather_cols: 2-byte features only");
     OSR_REQUIRE(lv->num_levels >= 1 && lv->num_levels <= OSR_MAX_LEVELS && lv->num_anchors == 1 && feats->num_levels == lv->num_levels && feats->c == 256,
                 OSR_ERR_UNSUPPORTED, "osr_rpn_gather_cols: one anchor per location, 256 channels, the same levels in both descriptions");
-    OSR_REQUIRE(n >= 1 && cap >= 1, OSR_ERR_INVALID_ARG, "osr_rpn_gather_cols: bad n / cap");
+    OSR_REQUIRE(n >= 1 && cap >= 1 && width >= 1 && width <= 64, OSR_ERR_INVALID_ARG, "osr_rpn_gather_cols: bad n / cap / width");
     RsGeom g{};
     g.nl = lv->num_levels; g.n = n;
     for (int l = 0; l < g.nl; ++l) {
@@ -154,9 +179,19 @@ extern "C" osr_status osr_rpn_gather_cols(const osr_rpn_levels* lv, const osr_py
     }
     g.off[g.nl] = g.off[g.nl - 1] + (long long)n * g.h[g.nl - 1] * g.w[g.nl - 1];
     const long long waves = (long long)cap * 9;
-    hipLaunchKernelGGL(rs_gather_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, (hipStream_t)stream, g, row_ids, cap, d_out5, (uint2*)cols, d_out5_rows);
+    hipLaunchKernelGGL(rs_gather_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, (hipStream_t)stream, g, row_ids, cap, d_out5, width, (uint2*)cols, d_out5_rows);
     OSR_CHECK_LAUNCH("osr_rpn_gather_cols");
     return OSR_OK;
+}
+
+extern "C" osr_status osr_rpn_gather_cols(const osr_rpn_levels* lv, const osr_pyramid* feats, int32_t feat_dtype, int32_t n, const int32_t* row_ids,
+                                          int32_t cap, const float* d_out5, void* cols, float* d_out5_rows, void* stream) {
+    return rs_gather_cols(lv, feats, feat_dtype, n, row_ids, cap, d_out5, 5, cols, d_out5_rows, stream);
+}
+
+extern "C" osr_status osr_rpn_gather_cols_ex(const osr_rpn_levels* lv, const osr_pyramid* feats, int32_t feat_dtype, int32_t n, const int32_t* row_ids,
+                                             int32_t cap, const float* d_rows, int32_t width, void* cols, float* d_rows_listed, void* stream) {
+    return rs_gather_cols(lv, feats, feat_dtype, n, row_ids, cap, d_rows, width, cols, d_rows_listed, stream);
 }
 
 // ------------------------------------------------------------------------------------------------------

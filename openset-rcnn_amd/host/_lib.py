@@ -165,6 +165,15 @@ PROTOTYPES = {
     "osr_roi_box_losses_bwd": (I32, [P, P, P, P, P, I64, I32, P, F32, F32, F32, P, P, I64, P]),
     "osr_roi_box_losses_bwd_ex": (I32, [P, P, P, P, P, I64, I32, P, F32, F32, F32, P, P, P, I64, P]),
     "osr_softmax_ce_loss_bwd": (I32, [P, I64, I32, P, I32, F32, F32, P, P, I64, P]),
+    # stock heads (csrc/osr_std_train.hip) and the width-generalised sparse RPN backward
+    "osr_std_rpn_losses_fwd": (I32, [P, P, I32, P, P, P, P, P, F32, F32, F32, I32, P, P, I64, P]),
+    "osr_std_rpn_losses_bwd": (I32, [P, P, I32, P, P, P, P, P, F32, F32, F32, I32, F32, P, P]),
+    "osr_fastrcnn_losses_fwd": (I32, [P, P, I32, I32, P, P, P, I64, I32, P, F32, F32, F32, P, P, I64, P]),
+    "osr_fastrcnn_losses_bwd": (I32, [P, P, I32, I32, P, P, P, I64, I32, P, F32, F32, F32, F32, P, P, P, I64, P]),
+    "osr_std_rpn_tail_bwd_workspace_bytes": (I64, []),
+    "osr_std_rpn_tail_bwd": (I32, [P, I64, P, I32, P, P, I32, P, P, P, I64, P]),
+    "osr_rpn_sparse_rows_ex": (I32, [P, I64, I32, I32, P, P, P, P, I64, P]),
+    "osr_rpn_gather_cols_ex": (I32, [P, P, I32, I32, P, I32, P, I32, P, P, P]),
     "osr_pln_loss_bwd_workspace_bytes": (I64, [I64]),
     "osr_pln_loss_bwd": (I32, [P, I64, I32, P, I32, P, P, F32, F32, F32, F32, F32, P, P, I32, P, I64, P]),
     "osr_pln_loss_bwd_ex": (I32, [P, I64, I32, P, I32, I32, I32, P, P, F32, F32, F32, F32, F32, P, P, I32, P, I64, P]),

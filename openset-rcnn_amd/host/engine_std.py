@@ -13,12 +13,15 @@ from typing import Dict, Optional
 import torch
 
 from . import ops
-from .engine import OpensetRCNNEngine
+from .engine import OpensetRCNNEngine, loss_types_of
 from .weights import pack_fc1_weight
 
 STD_DEFAULT_CFG = dict(
     anchor_ratios=(0.5, 1.0, 2.0), post_nms_topk_test=1000, rpn_nms_thresh=0.7, rpn_bbox_reg_weights=(1.0, 1.0, 1.0, 1.0),
     std_num_classes=80, score_thresh_test=0.05, std_nms_thresh_test=0.5, std_detections_per_image=100, cls_agnostic_bbox_reg=False,
+    # training ([d2] defaults; Base-RCNN-FPN.yaml:17-18 sets the two top-k values)
+    post_nms_topk_train=1000, rpn_cls_weight=1.0, std_cls_loss_weight=1.0,
+    loss_types=dict(rpn_box=("smooth_l1", 0.0), roi_box=("smooth_l1", 0.0)),
 )
 
 
@@ -79,7 +82,7 @@ class StandardRCNNEngine(OpensetRCNNEngine):
         return self._lv_cache[key]
 
     # ---- [d2] RPN.forward (inference) -------------------------------------------------------------------------------------------
-    def _rpn(self, feats, image_hw, keep=None, topk=None):
+    def _rpn(self, feats, image_hw, keep=None, topk=None, post_topk=None):
         c = self.cfg
         fl = [feats[k] for k in ("p2", "p3", "p4", "p5", "p6")]
         n = fl[0].shape[0]
@@ -101,13 +104,14 @@ class StandardRCNNEngine(OpensetRCNNEngine):
         sel = ops.rpn_select(self._levels(shapes, n), self.cell_anchors, logits, deltas, n, image_hw, k, c["min_box_size"],
                              b2b_weights=c["rpn_bbox_reg_weights"])
         # [d2] find_top_rpn_proposals: batched NMS with the level as category, then the first POST_NMS_TOPK of the keep list
-        post = c["post_nms_topk_test"]
+        post = c["post_nms_topk_test"] if post_topk is None else post_topk
         pk, pcnt = ops.nms_topk(sel["boxes"], sel["scores"], sel["level"], None, n, sel["cap"], sel["counts"], c["rpn_nms_thresh"], post)
         boxes = ops.gather_rows(sel["boxes"].view(-1, 4), sel["cap"], pk, pcnt)
         scores = ops.gather_rows(sel["scores"].view(-1), sel["cap"], pk, pcnt).view(n, post)
         ar = torch.arange(post, device=self.device, dtype=torch.int32)[None, :]
         bidx = torch.where(ar < pcnt[:, None], torch.arange(n, device=self.device, dtype=torch.int32)[:, None], torch.full((1, 1), -1, device=self.device, dtype=torch.int32))
-        out = dict(boxes=boxes, scores=scores, counts=pcnt, batch_idx=bidx.reshape(-1).contiguous(), cap=post, pre=sel, keep_idx=pk)
+        out = dict(boxes=boxes, scores=scores, counts=pcnt, batch_idx=bidx.reshape(-1).contiguous(), cap=post, pre=sel, keep_idx=pk,
+                   status_flags=sel["status_flags"], levels=self._levels(shapes, n), pred_logits=logits, pred_deltas=deltas)
         if keep is not None:
             keep.update(rpn_t=t_all, rpn_logits=logits, rpn_deltas=deltas, rpn_shapes=shapes, rpn_pre=sel, rpn_keep=pk)
         return out
@@ -136,3 +140,67 @@ class StandardRCNNEngine(OpensetRCNNEngine):
         if keep is not None:
             keep.update(pooled=pooled, h1=h1, box_feats=box_feats, logits=logits, deltas=deltas, cands=cands, det_keep=dk, det_count=dcnt)
         return ob, osc, ocl, dcnt
+
+    # ---- [d2] RPN.label_and_sample_anchors + RPN.losses (training) ---------------------------------------------------------------
+    def rpn_targets_forward(self, lv, n: int, gt_boxes: torch.Tensor, gt_count: torch.Tensor, keys: Dict[str, torch.Tensor],
+                            keep: Optional[dict] = None) -> dict:
+        """Matcher(RPN.IOU_THRESHOLDS, [0, -1, 1], allow_low_quality_matches) -- one label set: the objectness thresholds of the shared
+        kernel are set to the regression ones and its second output is dropped --, subsample_labels(BATCH_SIZE_PER_IMAGE,
+        POSITIVE_FRACTION) with the keys 'rpn_reg', and the matched GT box of every anchor. A function of the ground truth only."""
+        c = self.cfg
+        thr = c["rpn_iou_thresholds"]
+        midx, miou, lab, _ = ops.rpn_match_anchors(lv, self.cell_anchors, n, gt_boxes, gt_count, thr, thr)
+        if keep is not None:
+            keep.update(matched_idx=midx, matched_iou=miou, labels_pre=lab.clone())
+        ops.subsample_labels_(lab, keys["rpn_reg"], c["rpn_batch_size"], c["rpn_positive_fraction"])
+        mboxes, _ = ops.rpn_anchor_targets(lv, self.cell_anchors, n, gt_boxes, gt_count, midx, lab)
+        return dict(labels=lab, matched_boxes=mboxes)
+
+    def rpn_losses_forward(self, sel: dict, n: int, gt_boxes: torch.Tensor, gt_count: torch.Tensor, keys: Dict[str, torch.Tensor],
+                           keep: Optional[dict] = None, targets: Optional[dict] = None):
+        """-> (4 floats: loss_rpn_cls, loss_rpn_loc, num_pos, num_neg; the targets the backward reads)."""
+        c = self.cfg
+        check_std_supported(c)
+        tg = targets if targets is not None else self.rpn_targets_forward(sel["levels"], n, gt_boxes, gt_count, keys, keep)
+        rpn = ops.std_rpn_losses_fwd(sel["levels"], self.cell_anchors, n, sel["pred_logits"], sel["pred_deltas"], tg["labels"], tg["matched_boxes"],
+                                     c["rpn_bbox_reg_weights"], std_loss_beta(c, "rpn_box"), c["rpn_cls_weight"], c["rpn_loc_weight"], c["rpn_batch_size"])
+        return rpn, dict(tg)
+
+    # ---- [d2] StandardROIHeads.label_and_sample_proposals + FastRCNNOutputLayers.losses (training) ---------------------------------
+    def roi_losses_forward(self, feats: Dict[str, torch.Tensor], prop_boxes, prop_scores, prop_counts, gt_boxes, gt_classes, gt_count,
+                           keys_roi: torch.Tensor):
+        """Proposals (detached) + GT appended, Matcher([IOU_THRESHOLDS[0]], [0, 1]), background = NUM_CLASSES, BATCH_SIZE_PER_IMAGE /
+        POSITIVE_FRACTION sampling, box head, cls_score / bbox_pred, the two losses. Returns (dict: loss_cls, loss_box_reg,
+        roi_counts (n,3), stats (7); state dict with what the backward reads)."""
+        c = self.cfg
+        check_std_supported(c)
+        k = c["std_num_classes"]
+        smp = ops.roi_match_and_sample(prop_boxes, prop_scores, prop_counts, gt_boxes, gt_classes, gt_count, keys_roi,
+                                       k, c["roi_batch_size"], c["roi_positive_fraction"], c["roi_iou_threshold"])
+        boxes = smp["boxes"].view(-1, 4)
+        pooled = self.pool_rois(feats, boxes, smp["batch_idx"])
+        h1 = self._linear(pooled, self.fc1_w, self.fc1_b, True, name="roi_heads.box_head.fc1")
+        box_feats = self._linear(h1, self.fc2_w, self.fc2_b, True, torch.float32, name="roi_heads.box_head.fc2")
+        logits = ops.gemm_f32(box_feats, self.cls_w, self.cls_b)
+        deltas = ops.gemm_f32(box_feats, self.box_w, self.box_b)
+        cls = smp["gt_classes"].view(-1)
+        st = ops.fastrcnn_losses_fwd(logits, deltas, boxes, smp["gt_boxes"].view(-1, 4), cls, k, self.box_w.shape[0] == 4, c["bbox_reg_weights"],
+                                     std_loss_beta(c, "roi_box"), c["std_cls_loss_weight"], c["box_reg_weight"])
+        state = dict(smp=smp, boxes=boxes, pooled=self.pooled_bin_major(pooled), h1=h1, box_feats=box_feats, logits=logits, deltas=deltas, cls=cls)
+        return dict(loss_cls=st[0], loss_box_reg=st[1], roi_counts=smp["counts"], stats=st), state
+
+
+def std_loss_beta(cfg: dict, key: str) -> float:
+    return float(loss_types_of(cfg)[key][1])
+
+
+def check_std_supported(cfg: dict) -> None:
+    """The stock heads train with BBOX_REG_LOSS_TYPE "smooth_l1" (the [d2] default Base-RCNN-FPN.yaml keeps) for the RPN and the box
+    head; giou / diou / ciou are refused here, at model build time (modeling.RPN / StandardROIHeads call this), not at the first
+    iteration."""
+    lt = loss_types_of(cfg)
+    for key, name in (("rpn_box", "MODEL.RPN.BBOX_REG_LOSS_TYPE"), ("roi_box", "MODEL.ROI_BOX_HEAD.BBOX_REG_LOSS_TYPE")):
+        if lt[key][0] != "smooth_l1":
+            raise NotImplementedError(f"{name} '{lt[key][0]}': the stock RPN / StandardROIHeads train with \"smooth_l1\" only on the HIP path")
+        if lt[key][1] < 0.0:
+            raise ValueError(f"{name}: negative SMOOTH_L1_BETA")

@@ -26,7 +26,7 @@ from torch import nn
 from . import ops, parallel
 from .config import CfgNode
 from .engine import DEFAULT_CFG, OpensetRCNNEngine
-from .engine_std import StandardRCNNEngine
+from .engine_std import StandardRCNNEngine, check_std_supported
 from .structures import Boxes, ImageList, Instances, ShapeSpec
 from .weights import R50_BLOCKS, R50_MID, fold_frozen_bn
 
@@ -84,7 +84,8 @@ def pad_ground_truth(instances: List["Instances"]):
 
 
 class _ExplicitBackward(torch.autograd.Function):
-    """Stands for the whole training step in torch's autograd: forward hands out the six loss values the HIP kernels computed,
+    """Stands for the whole training step in torch's autograd: forward hands out the loss values the HIP kernels computed (six for
+    Openset R-CNN, four for the stock heads),
     backward runs OpensetRCNNTrainer._backward (the explicit sequence of data-gradient / weight-gradient launches) when
     `losses.backward()` reaches it. The gradients land in the trainer's flat fp32 buffer, where the optimizer mirror reads them."""
 
@@ -99,7 +100,7 @@ class _ExplicitBackward(torch.autograd.Function):
             raise RuntimeError("the HIP backward of this iteration has already run (its saved activations are released)")
         vals = [float(g) if g is not None else 0.0 for g in grads]  # one small D2H read; train.py:138 syncs on the losses anyway
         if min(vals) != max(vals) or vals[0] <= 0.0:
-            raise NotImplementedError(f"the HIP backward differentiates a uniformly weighted sum of the six losses (train.py:136); got d total / d loss = {vals}")
+            raise NotImplementedError(f"the HIP backward differentiates a uniformly weighted sum of the {len(vals)} losses (train.py:136); got d total / d loss = {vals}")
         ctx.trainer._backward(ctx.saved, ctx.n, grad_scale=vals[0])
         ctx.trainer.grads_ready = True
         ctx.saved = None
@@ -388,7 +389,9 @@ class RPN(nn.Module):
     """[d2] RPN (PROPOSAL_GENERATOR.NAME default, Base-RCNN-FPN.yaml:9-21), inference branch: anchors with the yaml's aspect
     ratios, StandardRPNHead, Box2BoxTransform(RPN.BBOX_REG_WEIGHTS) decode, per-level top PRE_NMS_TOPK, NMS at RPN.NMS_THRESH per
     level, first POST_NMS_TOPK. forward(images, features, gt_instances=None) -> (list[Instances{proposal_boxes,
-    objectness_logits}], {}). Training of the stock RPN (BCE objectness + smooth-L1 deltas) is not on the Openset hot path."""
+    objectness_logits}], {}). Training (gt_instances given): [d2] label_and_sample_anchors + losses -- loss_rpn_cls (BCE objectness),
+    loss_rpn_loc (smooth-L1 deltas) as VALUES (the gradients come from the model-level call, see the module docstring) -- and the
+    training proposals (PRE_NMS_TOPK_TRAIN per level, POST_NMS_TOPK_TRAIN per image)."""
 
     def __init__(self, cfg: CfgNode, input_shape: Dict[str, ShapeSpec]):
         super().__init__()
@@ -396,22 +399,40 @@ class RPN(nn.Module):
         shapes = [input_shape[f] for f in self.in_features]
         self.rpn_head = RPN_HEAD_REGISTRY.get(cfg.MODEL.RPN.HEAD_NAME)(cfg, shapes)
         self.rpn_head._eng_cfg = engine_cfg_from(cfg)
+        check_std_supported(self.rpn_head._eng_cfg)  # (an unsupported loss type is refused when the model is built)
+        self.sampler_generator = torch.Generator().manual_seed(max(int(cfg.SEED), 0))  # uniform keys replacing torch.randperm (H6)
 
     def forward(self, images: ImageList, features: Dict[str, torch.Tensor], gt_instances: Optional[List[Instances]] = None):
-        if self.training:
-            raise NotImplementedError("the stock RPN's training branch is outside the Openset hot path (SURVEY.md 8a): train ClsFreeRPN configs")
         eng = self.rpn_head.engine()
         feats = {k: _to_nhwc(features[k], eng.dtype) for k in self.in_features}
-        hw = torch.tensor(images.image_sizes, dtype=torch.int32, device=feats[self.in_features[0]].device)
-        sel = eng._rpn(feats, hw)
-        counts = sel["counts"].cpu().tolist()
+        dev = feats[self.in_features[0]].device
+        hw = torch.tensor(images.image_sizes, dtype=torch.int32, device=dev)
+        losses = {}
+        if self.training:
+            assert gt_instances is not None, "RPN requires gt_instances in training!"
+            c, n = eng.cfg, len(gt_instances)
+            sel = eng._rpn(feats, hw, topk=c["pre_nms_topk_train"], post_topk=c["post_nms_topk_train"])
+            gt, _, gcnt = pad_ground_truth(gt_instances)
+            keys = {"rpn_reg": torch.rand((n, sel["pred_logits"].numel() // n), generator=self.sampler_generator).to(dev)}
+            with torch.no_grad():
+                rpn, _ = eng.rpn_losses_forward(sel, n, gt.to(dev), gcnt.to(dev), keys)
+            losses = {"loss_rpn_cls": rpn[0], "loss_rpn_loc": rpn[1]}
+        else:
+            sel = eng._rpn(feats, hw)
+        host = torch.cat((sel["counts"], sel["status_flags"])).cpu().tolist()
+        counts = host[:-1]
+        if self.training and host[-1] != 0:  # [d2] find_top_rpn_proposals raises in training (at test time the kernel drops the rows)
+            raise FloatingPointError("Predicted boxes or scores contain Inf/NaN. Training has diverged.")
+        if self.training:
+            pos, neg = [float(v) for v in rpn[2:4].tolist()]
+            self.storage = {"rpn/num_pos_anchors": pos / n, "rpn/num_neg_anchors": neg / n}
         out = []
         for i, size in enumerate(images.image_sizes):
             r = Instances(size)
             r.proposal_boxes = Boxes(sel["boxes"][i, : counts[i]])
             r.objectness_logits = sel["scores"][i, : counts[i]]
             out.append(r)
-        return out, {}
+        return out, losses
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -496,7 +517,7 @@ def engine_cfg_from(cfg: CfgNode) -> dict:
         anchor_ratios=tuple(float(r) for r in cfg.MODEL.ANCHOR_GENERATOR.ASPECT_RATIOS[0]), post_nms_topk_test=cfg.MODEL.RPN.POST_NMS_TOPK_TEST,
         rpn_nms_thresh=cfg.MODEL.RPN.NMS_THRESH, rpn_bbox_reg_weights=tuple(cfg.MODEL.RPN.BBOX_REG_WEIGHTS), std_num_classes=rh.NUM_CLASSES,
         score_thresh_test=rh.SCORE_THRESH_TEST, std_nms_thresh_test=rh.NMS_THRESH_TEST, std_detections_per_image=cfg.TEST.DETECTIONS_PER_IMAGE,
-        cls_agnostic_bbox_reg=bool(bh.CLS_AGNOSTIC_BBOX_REG),
+        cls_agnostic_bbox_reg=bool(bh.CLS_AGNOSTIC_BBOX_REG), post_nms_topk_train=cfg.MODEL.RPN.POST_NMS_TOPK_TRAIN, rpn_cls_weight=rpn.LOSS_WEIGHT,
         # checked by engine.check_supported_losses when a loss is first computed (inference never needs them)
         loss_types=dict(rpn_box=(rpn.BBOX_REG_LOSS_TYPE, float(rpn.SMOOTH_L1_BETA)), rpn_ctr=(rpn.CTR_REG_LOSS_TYPE, float(rpn.CTR_SMOOTH_L1_BETA)),
                         roi_box=(bh.BBOX_REG_LOSS_TYPE, float(bh.SMOOTH_L1_BETA)), roi_iou=(bh.IOU_REG_LOSS_TYPE, float(bh.IOU_SMOOTH_L1_BETA))),
@@ -613,7 +634,8 @@ class StandardROIHeads(_EngineOwner):
     """[d2] StandardROIHeads (Base-RCNN-FPN.yaml:22-28), box branch, inference: ROIPooler(7x7, ROIAlignV2) -> FastRCNNConvFCHead ->
     FastRCNNOutputLayers.inference (softmax, Box2BoxTransform(10,10,5,5), SCORE_THRESH_TEST, per-class NMS_THRESH_TEST,
     TEST.DETECTIONS_PER_IMAGE). forward(images, features, proposals, targets=None) -> (list[Instances{pred_boxes, scores,
-    pred_classes}], {})."""
+    pred_classes}], {}). Training (targets given): label_and_sample_proposals + the box branch's loss_cls / loss_box_reg VALUES and the
+    sampled proposals (gradients: the model-level call, see the module docstring)."""
     _prefix = "roi_heads."
     _engine_cls = StandardRCNNEngine
 
@@ -628,11 +650,39 @@ class StandardROIHeads(_EngineOwner):
         self.box_predictor = FastRCNNOutputLayers(cfg, self.box_head.output_shape)
         self._eng_cfg = engine_cfg_from(cfg)
         self._eng_cfg["pooler_scales"] = tuple(1.0 / input_shape[k].stride for k in self.in_features)
+        check_std_supported(self._eng_cfg)  # (an unsupported loss type is refused when the model is built)
+        self.sampler_generator = torch.Generator().manual_seed(max(int(cfg.SEED), 0))  # uniform keys replacing torch.randperm (H6)
+
+    def _forward_train(self, features: Dict[str, torch.Tensor], proposals: List[Instances], targets: List[Instances]):
+        """[d2] label_and_sample_proposals + FastRCNNOutputLayers.losses: the sampled proposals (gt_classes / gt_boxes attached) and the
+        loss values."""
+        eng = self.engine()
+        boxes, scores, _, counts, cap = OpensetROIHeads._pack_proposals(proposals)
+        n, dev = len(proposals), boxes.device
+        gt, gcls, gcnt = pad_ground_truth(targets)
+        keys = torch.rand((n, cap + gt.shape[1]), generator=self.sampler_generator).to(dev)
+        feats = {k: _to_nhwc(features[k], eng.dtype) for k in self.in_features}
+        with torch.no_grad():
+            losses, st = eng.roi_losses_forward(feats, boxes, scores, counts, gt.to(dev), gcls.to(dev), gcnt.to(dev), keys)
+        smp = st["smp"]
+        host = smp["counts"].cpu()
+        self.storage = {"roi_head/num_fg_samples": float(host[:, 1].sum()) / n, "roi_head/num_bg_samples": float(host[:, 2].sum()) / n}
+        out = []
+        for i, p in enumerate(proposals):
+            k = int(host[i, 0])
+            r = Instances(p.image_size)
+            r.proposal_boxes = Boxes(smp["boxes"][i, :k])
+            r.objectness_logits = smp["logits"][i, :k]
+            r.gt_classes = smp["gt_classes"][i, :k]
+            r.gt_boxes = Boxes(smp["gt_boxes"][i, :k])
+            out.append(r)
+        return out, {"loss_cls": losses["loss_cls"], "loss_box_reg": losses["loss_box_reg"]}
 
     def forward(self, images: ImageList, features: Dict[str, torch.Tensor], proposals: List[Instances], targets=None):
         del images
         if self.training:
-            raise NotImplementedError("the stock ROI heads' training branch is outside the Openset hot path (SURVEY.md 8a): train OpensetROIHeads configs")
+            assert targets, "'targets' argument is required during training"
+            return self._forward_train(features, proposals, targets)
         eng = self.engine()
         n = len(proposals)
         boxes, scores, bidx, counts, cap = OpensetROIHeads._pack_proposals(proposals)
@@ -746,6 +796,7 @@ class GeneralizedRCNN(_EngineOwner):
         owns fp32 master copies of this model's trainable parameters (res3+ weights un-folded from their FrozenBN, FPN, heads);
         `load_trainer_state(trainer)` writes them back into the module for evaluation / checkpointing."""
         from .train import OpensetRCNNTrainer
+        from .train_std import StandardRCNNTrainer
         if self.device.type != "cuda":
             raise ops.OsrError("the model must be on the GPU (model.to('cuda')): the HIP path has no CPU fallback")
         sd = {k: v.detach().cpu() for k, v in self.state_dict().items()}
@@ -757,6 +808,9 @@ class GeneralizedRCNN(_EngineOwner):
                 bn[pre] = (sd[pre + ".weight"], scale)
         # class_map: the GraspNet id_map of the PLN / classifier losses (prototype_learning_network.py:80-95) -- without it the
         # trainer would treat dataset ids 0..NUM_KNOWN-1 as the known classes
+        if self._engine_cls is StandardRCNNEngine:  # the trainer by engine class: Base-RCNN-FPN.yaml's stock heads
+            return StandardRCNNTrainer(fold_frozen_bn(sd), self._eng_cfg, self.kernel_dtype, str(self.device), lr=lr, momentum=momentum,
+                                       weight_decay=weight_decay, loss_scale=loss_scale, frozen_bn=bn)
         return OpensetRCNNTrainer(fold_frozen_bn(sd), self._eng_cfg, self.kernel_dtype, str(self.device), lr=lr, momentum=momentum,
                                   weight_decay=weight_decay, loss_scale=loss_scale, frozen_bn=bn, class_map=self._class_map)
 
@@ -804,8 +858,13 @@ class GeneralizedRCNN(_EngineOwner):
         shapes.append(((shapes[-1][0] - 1) // 2 + 1, (shapes[-1][1] - 1) // 2 + 1))
         r = sum(a * b for a, b in shapes)
         cap = sum(min(ecfg["pre_nms_topk_train"], a * b) for a, b in shapes)
-        keys = {k: torch.rand(shape, generator=generator).to(dev) for k, shape in
-                (("rpn_reg", (n, r)), ("rpn_obj", (n, r)), ("roi", (n, cap + gmax)))}
+        if self._engine_cls is StandardRCNNEngine:  # A anchors per location; the RoI heads sample from the POST_NMS_TOPK_TRAIN list
+            r *= len(ecfg["anchor_ratios"])
+            cap = ecfg["post_nms_topk_train"]
+        # (the stock RPN has one label set: no objectness keys)
+        kinds = (("rpn_reg", (n, r)), ("roi", (n, cap + gmax))) if self._engine_cls is StandardRCNNEngine else \
+            (("rpn_reg", (n, r)), ("rpn_obj", (n, r)), ("roi", (n, cap + gmax)))
+        keys = {k: torch.rand(shape, generator=generator).to(dev) for k, shape in kinds}
         hw = torch.tensor(sizes, dtype=torch.int32, device=dev)
         return batch, hw, hp, wp, gt.to(dev), gcls.to(dev), gcnt.to(dev), keys
 

@@ -1376,3 +1376,126 @@ def sgd_step_(param, grad, buf, lr: float, momentum: float, weight_decay: float,
     row_elems = param.numel() // param.shape[0] if row_scale is not None else 1
     check(lib.osr_sgd_step(_p(param), _p(grad), _p(buf), param.numel(), lr, momentum, weight_decay, grad_scale, _p(row_scale), row_elems,
                            _p(lowp), _DT[lowp.dtype] if lowp is not None else 0, _p(apply_flag), _stream()), "osr_sgd_step")
+
+
+# ----------------------------------------------------------------------------------------------------------
+# stock heads (Base-RCNN-FPN.yaml: RPN + StandardROIHeads): losses, their gradients, the RPN head's tail backward
+# ----------------------------------------------------------------------------------------------------------
+def _f4(vals) -> "C.Array":
+    return (C.c_float * 4)(*[float(v) for v in vals])
+
+
+def std_rpn_losses_fwd(lv: RpnLevels, cell_anchors, n: int, pred_logits, pred_deltas, labels, matched_boxes, b2b_weights=(1.0, 1.0, 1.0, 1.0),
+                       beta: float = 0.0, cls_weight: float = 1.0, loc_weight: float = 1.0, batch_size_per_image: int = 256) -> torch.Tensor:
+    """[d2] RPN.losses: pred_logits (rows*A,) / pred_deltas (rows*A, 4) level-major, labels (n,R) int8, matched_boxes (n,R,4).
+    Returns 4 floats: loss_rpn_cls, loss_rpn_loc, num_pos, num_neg."""
+    lib = _lib.load()
+    _need(pred_logits, torch.float32, "pred_logits"); _need(pred_deltas, torch.float32, "pred_deltas")
+    _need(labels, torch.int8, "labels"); _need(matched_boxes, torch.float32, "matched_boxes")
+    dev = pred_logits.device
+    out = torch.empty((4,), dtype=torch.float32, device=dev)
+    ws = torch.empty((256 * 4 * 4,), dtype=torch.uint8, device=dev)
+    check(lib.osr_std_rpn_losses_fwd(C.byref(lv), _p(cell_anchors), n, _p(pred_logits), _p(pred_deltas), _p(labels), _p(matched_boxes),
+                                     _f4(b2b_weights), beta, cls_weight, loc_weight, batch_size_per_image, _p(out), _p(ws), ws.numel(), _stream()),
+          "osr_std_rpn_losses_fwd")
+    return out
+
+
+def std_rpn_losses_bwd(lv: RpnLevels, cell_anchors, n: int, pred_logits, pred_deltas, labels, matched_boxes, b2b_weights=(1.0, 1.0, 1.0, 1.0),
+                       beta: float = 0.0, cls_weight: float = 1.0, loc_weight: float = 1.0, batch_size_per_image: int = 256,
+                       loss_scale: float = 1.0) -> torch.Tensor:
+    """Gradient of std_rpn_losses_fwd times loss_scale: (rows, 5A) fp32 over the pixel rows -- A logit columns, then 4A delta columns."""
+    lib = _lib.load()
+    _need(pred_logits, torch.float32, "pred_logits"); _need(pred_deltas, torch.float32, "pred_deltas")
+    _need(labels, torch.int8, "labels"); _need(matched_boxes, torch.float32, "matched_boxes")
+    a = lv.num_anchors
+    d = torch.empty((pred_logits.numel() // a, 5 * a), dtype=torch.float32, device=pred_logits.device)
+    check(lib.osr_std_rpn_losses_bwd(C.byref(lv), _p(cell_anchors), n, _p(pred_logits), _p(pred_deltas), _p(labels), _p(matched_boxes),
+                                     _f4(b2b_weights), beta, cls_weight, loc_weight, batch_size_per_image, loss_scale, _p(d), _stream()),
+          "osr_std_rpn_losses_bwd")
+    return d
+
+
+def fastrcnn_losses_fwd(logits, pred_deltas, proposal_boxes, gt_boxes, gt_classes, num_classes: int, cls_agnostic: bool,
+                        reg_weights=(10.0, 10.0, 5.0, 5.0), beta: float = 0.0, cls_weight: float = 1.0, box_weight: float = 1.0) -> torch.Tensor:
+    """[d2] FastRCNNOutputLayers.losses over the sampled rows (class -1 = padding). Returns 7 floats: loss_cls, loss_box_reg, rows,
+    correct, foreground, foreground correct, foreground predicted as background."""
+    lib = _lib.load()
+    _need(logits, torch.float32, "logits"); _need(proposal_boxes, torch.float32, "proposal_boxes"); _need(gt_boxes, torch.float32, "gt_boxes")
+    _need(gt_classes, torch.int64, "gt_classes"); _need(pred_deltas, torch.float32, "pred_deltas")
+    m = logits.shape[0]
+    out = torch.empty((7,), dtype=torch.float32, device=logits.device)
+    ws = torch.empty((256 * 7 * 4,), dtype=torch.uint8, device=logits.device)
+    check(lib.osr_fastrcnn_losses_fwd(_p(logits), _p(pred_deltas), pred_deltas.shape[1], int(cls_agnostic), _p(proposal_boxes), _p(gt_boxes),
+                                      _p(gt_classes), m, num_classes, _f4(reg_weights), beta, cls_weight, box_weight, _p(out), _p(ws), ws.numel(),
+                                      _stream()), "osr_fastrcnn_losses_fwd")
+    return out
+
+
+def fastrcnn_losses_bwd(logits, pred_deltas, proposal_boxes, gt_boxes, gt_classes, num_classes: int, cls_agnostic: bool,
+                        reg_weights=(10.0, 10.0, 5.0, 5.0), beta: float = 0.0, cls_weight: float = 1.0, box_weight: float = 1.0,
+                        loss_scale: float = 1.0):
+    """Gradient of fastrcnn_losses_fwd times loss_scale: (d_logits (m, K+1), d_deltas (m, 4 | 4K)), fp32."""
+    lib = _lib.load()
+    _need(logits, torch.float32, "logits"); _need(pred_deltas, torch.float32, "pred_deltas")
+    _need(proposal_boxes, torch.float32, "proposal_boxes"); _need(gt_boxes, torch.float32, "gt_boxes"); _need(gt_classes, torch.int64, "gt_classes")
+    m = logits.shape[0]
+    dl = torch.empty_like(logits)
+    dd = torch.empty_like(pred_deltas)
+    ws = torch.empty((16,), dtype=torch.uint8, device=logits.device)
+    check(lib.osr_fastrcnn_losses_bwd(_p(logits), _p(pred_deltas), pred_deltas.shape[1], int(cls_agnostic), _p(proposal_boxes), _p(gt_boxes),
+                                      _p(gt_classes), m, num_classes, _f4(reg_weights), beta, cls_weight, box_weight, loss_scale, _p(dl), _p(dd),
+                                      _p(ws), ws.numel(), _stream()), "osr_fastrcnn_losses_bwd")
+    return dl, dd
+
+
+def std_rpn_tail_bwd(t: torch.Tensor, w_tail: torch.Tensor, d_rows: torch.Tensor, dt_dtype: torch.dtype,
+                     dw: Optional[torch.Tensor] = None, db: Optional[torch.Tensor] = None):
+    """t (rows,256) fp32 (after the 3x3 conv's ReLU), w_tail (5A,256) = [W_obj; W_delta], d_rows (rows,5A) -> dt (rows,256) in dt_dtype
+    (masked by t > 0), dw_tail (5A,256), db_tail (5A) -- written into dw / db when given (e.g. the gradient buffer's views)."""
+    lib = _lib.load()
+    _need(t, torch.float32, "t"); _need(w_tail, torch.float32, "w_tail"); _need(d_rows, torch.float32, "d_rows")
+    rows, q = d_rows.shape
+    if t.shape != (rows, 256) or w_tail.shape != (q, 256):
+        raise OsrError("std_rpn_tail_bwd: t (rows,256), w_tail (width,256), d_rows (rows,width)")
+    dt = torch.empty((rows, 256), dtype=dt_dtype, device=t.device)
+    if dw is None:
+        dw = torch.empty((q, 256), dtype=torch.float32, device=t.device)
+    if db is None:
+        db = torch.empty((q,), dtype=torch.float32, device=t.device)
+    _need(dw, torch.float32, "dw"); _need(db, torch.float32, "db")
+    if dw.shape != (q, 256) or db.shape != (q,):
+        raise OsrError("std_rpn_tail_bwd: dw (width,256), db (width)")
+    wsb = lib.osr_std_rpn_tail_bwd_workspace_bytes()
+    ws = torch.empty((wsb,), dtype=torch.uint8, device=t.device)
+    check(lib.osr_std_rpn_tail_bwd(_p(t), rows, _p(w_tail), q, _p(d_rows), _p(dt), _DT[dt_dtype], _p(dw), _p(db), _p(ws), wsb, _stream()),
+          "osr_std_rpn_tail_bwd")
+    return dt, dw, db
+
+
+def rpn_sparse_rows_ex(d_rows: torch.Tensor, cap: int):
+    """rpn_sparse_rows for a gradient of any row width (d_rows (rows, width) fp32)."""
+    lib = _lib.load()
+    _need(d_rows, torch.float32, "d_rows")
+    rows, width = d_rows.shape
+    dev = d_rows.device
+    ids = torch.empty((cap,), dtype=torch.int32, device=dev)
+    rmap = torch.empty((rows,), dtype=torch.int32, device=dev)
+    cnt = torch.empty((2,), dtype=torch.int32, device=dev)
+    wsb = lib.osr_rpn_sparse_rows_workspace_bytes()
+    ws = torch.empty((wsb,), dtype=torch.uint8, device=dev)
+    check(lib.osr_rpn_sparse_rows_ex(_p(d_rows), rows, width, cap, _p(ids), _p(rmap), _p(cnt), _p(ws), wsb, _stream()), "osr_rpn_sparse_rows_ex")
+    return ids, rmap, cnt
+
+
+def rpn_gather_cols_ex(lv: RpnLevels, feats: List[torch.Tensor], n: int, row_ids: torch.Tensor, d_rows: torch.Tensor):
+    """rpn_gather_cols for a gradient of any row width: -> (cols (cap, 2304), d_rows of the listed rows (cap, width)). lv: pixel levels."""
+    lib = _lib.load()
+    _need(row_ids, torch.int32, "row_ids"); _need(d_rows, torch.float32, "d_rows")
+    py = _pyramid(feats, [1.0] * len(feats))
+    cap, width = row_ids.shape[0], d_rows.shape[1]
+    cols = torch.empty((cap, 9 * 256), dtype=feats[0].dtype, device=row_ids.device)
+    dl = torch.empty((cap, width), dtype=torch.float32, device=row_ids.device)
+    check(lib.osr_rpn_gather_cols_ex(C.byref(lv), C.byref(py), _DT[feats[0].dtype], n, _p(row_ids), cap, _p(d_rows), width, _p(cols), _p(dl),
+                                     _stream()), "osr_rpn_gather_cols_ex")
+    return cols, dl

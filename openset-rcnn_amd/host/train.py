@@ -121,7 +121,7 @@ class OpensetRCNNTrainer:
         is the un-folded weight (weight decay acts on it, the chain rule multiplies the kernel's gradient by the scale)."""
         self.frozen_bn = frozen_bn or {}
         self.row_scale: Dict[str, torch.Tensor] = {}
-        self.eng = OpensetRCNNEngine(params, cfg, dtype, device, class_map)
+        self.eng = self._make_engine(params, cfg, dtype, device, class_map)
         # the CF-RPN head's backward runs on the sampled anchors only and recomputes their hidden state (osr_rpn_sparse.hip); False:
         # the dense launches of rounds 1-3 (the fused head kernel then also writes the hidden state of every anchor: 0.7 GB)
         self.sparse_rpn_bwd = True
@@ -152,19 +152,7 @@ class OpensetRCNNTrainer:
             self._add_conv(f"backbone.fpn_lateral{lvl}", params, bias=True)
             self._add_conv(f"backbone.fpn_output{lvl}", params, bias=True)
         self._add_conv("proposal_generator.rpn_head.conv", params, bias=True)
-        self.master["rpn_tail.w"], self.master["rpn_tail.b"] = e.rpn_wtail, e.rpn_btail  # (5,256): 4 ltrb rows + centerness
-        e.rpn_wd, e.rpn_wc, e.rpn_bd, e.rpn_bc = e.rpn_wtail[:4], e.rpn_wtail[4:5], e.rpn_btail[:4], e.rpn_btail[4:5]  # views: one storage
-        self.master["fc1.w"] = pack_fc1_weight(params["roi_heads.box_head.fc1.weight"], 256, e.cfg["pooler_resolution"], torch.float32).to(dev)
-        self.lowp["fc1.w"] = e.fc1_w
-        self.master["fc1.b"] = e.fc1_b
-        self.master["fc2.w"] = f32(params["roi_heads.box_head.fc2.weight"])
-        self.lowp["fc2.w"] = e.fc2_w
-        self.master["fc2.b"] = e.fc2_b
-        self.master["pred.w"], self.master["pred.b"] = e.pred_w, e.pred_b
-        self.master["enc.w"], self.master["enc.b"] = e.enc_w, e.enc_b
-        self.master["dec.w"], self.master["dec.b"] = e.dec_w, e.dec_b
-        self.master["cls.w"], self.master["cls.b"] = e.cls_w, e.cls_b
-        self.master["protos"] = f32(params["roi_heads.dml.representatives"])
+        self._add_head_masters(params)
         # ---- one flat gradient buffer (the all-reduce operand), momentum buffers ----
         al = lambda x: (x + 3) // 4 * 4  # noqa: E731  every view starts 16-byte aligned (the kernels use 16-byte accesses)
         total = sum(al(t.numel()) for t in self.master.values())
@@ -210,6 +198,28 @@ class OpensetRCNNTrainer:
     @property
     def overflow_steps(self) -> int:
         return self.scaler.overflow_steps
+
+    @staticmethod
+    def _make_engine(params, cfg, dtype, device, class_map):
+        return OpensetRCNNEngine(params, cfg, dtype, device, class_map)
+
+    def _add_head_masters(self, params) -> None:
+        """The masters behind the RPN head's 3x3 conv: CF-RPN tail, box head, predictor, PLN, classifier (in this order: see __init__)."""
+        e, dev = self.eng, self.eng.device
+        f32 = lambda t: t.detach().float().contiguous().to(dev)  # noqa: E731
+        self.master["rpn_tail.w"], self.master["rpn_tail.b"] = e.rpn_wtail, e.rpn_btail  # (5,256): 4 ltrb rows + centerness
+        e.rpn_wd, e.rpn_wc, e.rpn_bd, e.rpn_bc = e.rpn_wtail[:4], e.rpn_wtail[4:5], e.rpn_btail[:4], e.rpn_btail[4:5]  # views: one storage
+        self.master["fc1.w"] = pack_fc1_weight(params["roi_heads.box_head.fc1.weight"], 256, e.cfg["pooler_resolution"], torch.float32).to(dev)
+        self.lowp["fc1.w"] = e.fc1_w
+        self.master["fc1.b"] = e.fc1_b
+        self.master["fc2.w"] = f32(params["roi_heads.box_head.fc2.weight"])
+        self.lowp["fc2.w"] = e.fc2_w
+        self.master["fc2.b"] = e.fc2_b
+        self.master["pred.w"], self.master["pred.b"] = e.pred_w, e.pred_b
+        self.master["enc.w"], self.master["enc.b"] = e.enc_w, e.enc_b
+        self.master["dec.w"], self.master["dec.b"] = e.dec_w, e.dec_b
+        self.master["cls.w"], self.master["cls.b"] = e.cls_w, e.cls_b
+        self.master["protos"] = f32(params["roi_heads.dml.representatives"])
 
     def _add_conv(self, name: str, params, bias: bool):
         e = self.eng
@@ -277,6 +287,11 @@ class OpensetRCNNTrainer:
             jobs.append(lambda: ops.pack_dgrad_weight(e.fc1_w, wd["fc1"].view(e.fc1_w.shape[1], e.fc1_w.shape[0])))
             jobs.append(lambda: ops.pack_dgrad_weight(e.fc2_w, wd["fc2"].view(e.fc2_w.shape[1], e.fc2_w.shape[0])))
             self._fan(jobs)
+        self._refresh_heads()
+
+    def _refresh_heads(self) -> None:
+        """The derived tensors of the heads: transposed fp32 heads, normalised prototypes."""
+        e = self.eng
         if not hasattr(self, "t_cls"):  # zero-padded transposes of the narrow fp32 heads: the padding rows are written once
             self.t_cls = torch.zeros((e.cls_w.shape[1], 32), dtype=torch.float32, device=e.device)    # (1024, 32): d rec = d logits(padded to 32) . W_cls
             self.t_pred = torch.zeros((e.pred_w.shape[1], 16), dtype=torch.float32, device=e.device)  # (1024, 16)
@@ -305,6 +320,37 @@ class OpensetRCNNTrainer:
             with torch.cuda.stream(self._side):
                 rpn_targets = e.rpn_targets_forward(lv, n, gt_boxes, gt_count, keys)
                 targets_ready = self._side.record_event()
+        out = self._forward_trunk(images, hp, wp, s)
+        # CF-RPN head (unfused: the hidden state t is kept), targets, losses
+        keep: dict = {}
+        e.rpn_keep_hidden = not self.sparse_rpn_bwd
+        sel = e._rpn(out, image_hw, keep, topk=c["pre_nms_topk_train"])
+        s["rpn_t"], s["rpn_shapes"], s["sel"] = keep["rpn_t"], keep["rpn_shapes"], sel
+        self._proposal_status = sel["status_flags"]  # read with this iteration's overflow verdict (DynamicLossScale.record)
+        assert list(keep["rpn_shapes"]) == list(shapes), "pyramid_shapes disagrees with the backbone"
+        if self.overlap_targets:
+            cur.wait_event(targets_ready)
+            if not torch.cuda.is_current_stream_capturing():
+                for t in rpn_targets.values():
+                    t.record_stream(cur)
+        else:
+            rpn_targets = None
+        rpn, rpn_state = e.rpn_losses_forward(sel, n, gt_boxes, gt_count, keys, targets=rpn_targets)
+        s.update(rpn_state)
+        # RoI heads on the sampled proposals
+        roi, roi_state = e.roi_losses_forward(out, sel["boxes"], sel["scores"], sel["counts"], gt_boxes, gt_classes, gt_count, keys["roi"])
+        s.update(roi_state)
+        losses = dict(loss_rpn_loc=rpn[0], loss_rpn_ctr=rpn[1], loss_box_reg=roi["loss_box_reg"], loss_iou=roi["loss_iou"],
+                      loss_dml=roi["loss_dml"], loss_cls=roi["loss_cls"])
+        # what event_scalars() reads (references only: nothing is computed or copied unless a logger asks)
+        self._last_forward = dict(n=n, rpn_counts=rpn[2:6], prop_counts=sel["counts"], roi_counts=roi["roi_counts"], logits=roi_state["logits"],
+                                  cls_k=roi_state["cls_k"], nck=roi_state["nck"], batch_idx=roi_state["smp"]["batch_idx"])
+        return losses, s
+
+    def _forward_trunk(self, images, hp, wp, s: dict) -> Dict[str, torch.Tensor]:
+        """Backbone + FPN with the activations the backward reads saved into s (blocks, res, lat, p); returns p2..p6."""
+        e = self.eng
+        cur = torch.cuda.current_stream(self.device)
         pref, self._prefetched = self._prefetched, None
         if pref is not None and pref[0] is images and pref[1] == (hp, wp) and pref[4] == images._version:
             # the frozen prefix of THIS batch was computed under the previous iteration's backward (step(next_images=...)): take it
@@ -347,31 +393,7 @@ class OpensetRCNNTrainer:
             out[f"p{lvl}"] = outs[i] if outs is not None else e._conv(lat[lvl], f"backbone.fpn_output{lvl}", 1, 1)
         out["p6"] = ops.subsample2(out["p5"])
         s["lat"], s["p"] = lat, out
-        # CF-RPN head (unfused: the hidden state t is kept), targets, losses
-        keep: dict = {}
-        e.rpn_keep_hidden = not self.sparse_rpn_bwd
-        sel = e._rpn(out, image_hw, keep, topk=c["pre_nms_topk_train"])
-        s["rpn_t"], s["rpn_shapes"], s["sel"] = keep["rpn_t"], keep["rpn_shapes"], sel
-        self._proposal_status = sel["status_flags"]  # read with this iteration's overflow verdict (DynamicLossScale.record)
-        assert list(keep["rpn_shapes"]) == list(shapes), "pyramid_shapes disagrees with the backbone"
-        if self.overlap_targets:
-            cur.wait_event(targets_ready)
-            if not torch.cuda.is_current_stream_capturing():
-                for t in rpn_targets.values():
-                    t.record_stream(cur)
-        else:
-            rpn_targets = None
-        rpn, rpn_state = e.rpn_losses_forward(sel, n, gt_boxes, gt_count, keys, targets=rpn_targets)
-        s.update(rpn_state)
-        # RoI heads on the sampled proposals
-        roi, roi_state = e.roi_losses_forward(out, sel["boxes"], sel["scores"], sel["counts"], gt_boxes, gt_classes, gt_count, keys["roi"])
-        s.update(roi_state)
-        losses = dict(loss_rpn_loc=rpn[0], loss_rpn_ctr=rpn[1], loss_box_reg=roi["loss_box_reg"], loss_iou=roi["loss_iou"],
-                      loss_dml=roi["loss_dml"], loss_cls=roi["loss_cls"])
-        # what event_scalars() reads (references only: nothing is computed or copied unless a logger asks)
-        self._last_forward = dict(n=n, rpn_counts=rpn[2:6], prop_counts=sel["counts"], roi_counts=roi["roi_counts"], logits=roi_state["logits"],
-                                  cls_k=roi_state["cls_k"], nck=roi_state["nck"], batch_idx=roi_state["smp"]["batch_idx"])
-        return losses, s
+        return out
 
     def event_scalars(self) -> Dict[str, float]:
         """The ten scalars the reference puts into detectron2's EventStorage during a training iteration, for the LAST forward of this
@@ -500,16 +522,41 @@ class OpensetRCNNTrainer:
             for t in reads:
                 t.record_stream(self._wside)
 
-    def _backward(self, s, n, grad_scale: float = 1.0, overlap: bool = True, prefetch=None):
-        """Gradients of grad_scale * (sum of the six losses), times the loss scale, into self.grad. overlap: start each gradient
-        bucket's all-reduce as soon as the backward has passed it (several ranks only; all_reduce_grads() then just waits)."""
-        e, c, g, S = self.eng, self.eng.cfg, self.grad, self.loss_scale * grad_scale
+    def _backward_begin(self, grad_scale: float, overlap: bool) -> float:
+        """What every backward does first; returns the factor its loss gradients carry (loss scale x grad_scale)."""
+        S = self.loss_scale * grad_scale
         self._scale_used = self.loss_scale  # the update divides out the scale THIS backward multiplied in, whatever a poll does in between
         self._overlap = overlap and parallel.is_dist()
         self.buckets.reset()
         if getattr(self, "_pack_done", None) is not None:  # the repack of the backward-data weights behind the previous update (_refresh_derived)
             torch.cuda.current_stream(self.device).wait_event(self._pack_done)
             self._pack_done = None
+        return S
+
+    def _on_side(self, fn):
+        """fn() on the weight-gradient stream behind the main stream's current point (main stream when side_wgrad is off)."""
+        if not self.side_wgrad:
+            return fn()
+        cur0 = torch.cuda.current_stream(self.device)
+        if self._wside is None:
+            self._wside = torch.cuda.Stream(device=self.device)
+        self._wside.wait_stream(cur0)
+        with torch.cuda.stream(self._wside):
+            return fn()
+
+    def _join_side(self, ready, tensors) -> None:
+        """The main stream waits for the event `ready` of _on_side's chain and adopts its tensors."""
+        if self.side_wgrad:
+            torch.cuda.current_stream(self.device).wait_event(ready)
+            if not torch.cuda.is_current_stream_capturing():
+                for t_ in tensors:
+                    t_.record_stream(torch.cuda.current_stream(self.device))
+
+    def _backward(self, s, n, grad_scale: float = 1.0, overlap: bool = True, prefetch=None):
+        """Gradients of grad_scale * (sum of the six losses), times the loss scale, into self.grad. overlap: start each gradient
+        bucket's all-reduce as soon as the backward has passed it (several ranks only; all_reduce_grads() then just waits)."""
+        e, c, g = self.eng, self.eng.cfg, self.grad
+        S = self._backward_begin(grad_scale, overlap)
         dt = self.dtype
         p = s["p"]
         # --- CF-RPN: losses -> tail -> weight gradient of the 3x3 conv (weights shared by the five levels). This chain depends on
@@ -560,15 +607,7 @@ class OpensetRCNNTrainer:
                 ops.conv2d_wgrad(p[k_], dtl_, 3, 3, 1, 1, dw=g[rn + ".w"], accumulate=li_ > 0)
                 ops.bias_grad(dtl_, g[rn + ".b"], accumulate=li_ > 0)
             return (dta,), ready
-        if self.side_wgrad:
-            cur0 = torch.cuda.current_stream(self.device)
-            if self._wside is None:
-                self._wside = torch.cuda.Stream(device=self.device)
-            self._wside.wait_stream(cur0)
-            with torch.cuda.stream(self._wside):
-                rpn_grad, rpn_ready = rpn_chain()
-        else:
-            rpn_grad, rpn_ready = rpn_chain()
+        rpn_grad, rpn_ready = self._on_side(rpn_chain)
         self._done("rpn_tail.w", "rpn_tail.b", rn + ".w", rn + ".b")
         # --- RoI-head losses -> predictor / PLN / classifier (fp32 heads) ---
         lt = loss_types_of(c)
@@ -586,6 +625,32 @@ class OpensetRCNNTrainer:
         d_bf = self._f32_linear_bwd(s["box_feats"], d_emb, self.t_enc, "enc")
         d_bf2 = self._f32_linear_bwd(s["box_feats"], d_pred, self.t_pred, "pred", dy_pad=16)
         d_bf = ops.add_cast(d_bf, d_bf2, torch.float32)
+        d_feat = self._box_head_bwd(s, d_bf, n)
+        # --- CF-RPN 3x3 conv: data gradient per level, joined with the RoI heads' feature gradient (the chain above it ran on the
+        #     second stream, see the top of this function) ---
+        self._join_side(rpn_ready, rpn_grad)
+        dP = {}
+        lvl_shapes = list(zip(("p2", "p3", "p4", "p5", "p6"), s["rpn_shapes"]))
+        roi_part = [(d_feat[li] if d_feat[li].dtype == dt else ops.add_cast(d_feat[li], None, dt)) for li in range(4)] + [None]
+        if self.sparse_rpn_bwd:
+            # col2im of the listed anchors' per-tap gradients straight into the RoI heads' feature gradient (p6 has none: into zeros)
+            rmap, y_rows = rpn_grad
+            h6, w6 = s["rpn_shapes"][4]
+            glist = roi_part[:4] + [torch.zeros((n, h6, w6, 256), dtype=dt, device=self.device)]
+            ops.rpn_scatter_cols_add_(sel["levels"], n, rmap, y_rows, glist)
+            dP = {k: gl for (k, _), gl in zip(lvl_shapes, glist)}
+        else:
+            (dt_all,), off = rpn_grad, 0
+            for li, (k, (h, w)) in enumerate(lvl_shapes):
+                rows = n * h * w
+                dP[k] = ops.conv2d_dgrad(dt_all[off:off + rows].view(n, h, w, 256), self.wd[rn], (h, w), 1, 1, add=roi_part[li])
+                off += rows
+        self._backward_trunk(s, dP, prefetch)
+
+    def _box_head_bwd(self, s, d_bf, n):
+        """d box features (m,1024) fp32 -> FC2, FC1 (data + weight gradients) -> RoIAlign backward: the feature gradient per level."""
+        c, g, dt = self.eng.cfg, self.grad, self.dtype
+        p = s["p"]
         ops.relu_mask_(d_bf, s["box_feats"])
         dy2 = ops.add_cast(d_bf, None, dt)                                                  # (m,1024) low precision
         m = dy2.shape[0]
@@ -604,29 +669,12 @@ class OpensetRCNNTrainer:
         d_feat = ops.roi_align_bwd(d_pooled.view(m, P, P, -1), shapes, n, c["pooler_scales"], s["boxes"], s["smp"]["batch_idx"], c["canonical_level"],
                                    c["canonical_size"], 2, rois_per_image=m // n if m % n == 0 else None,  # (the sampled list is (n, S))
                                    out_dtype=dt if d_pooled.dtype == dt else None)
-        # --- CF-RPN 3x3 conv: data gradient per level, joined with the RoI heads' feature gradient (the chain above it ran on the
-        #     second stream, see the top of this function) ---
-        if self.side_wgrad:
-            torch.cuda.current_stream(self.device).wait_event(rpn_ready)
-            if not torch.cuda.is_current_stream_capturing():
-                for t_ in rpn_grad:
-                    t_.record_stream(torch.cuda.current_stream(self.device))
-        dP = {}
-        lvl_shapes = list(zip(("p2", "p3", "p4", "p5", "p6"), s["rpn_shapes"]))
-        roi_part = [(d_feat[li] if d_feat[li].dtype == dt else ops.add_cast(d_feat[li], None, dt)) for li in range(4)] + [None]
-        if self.sparse_rpn_bwd:
-            # col2im of the listed anchors' per-tap gradients straight into the RoI heads' feature gradient (p6 has none: into zeros)
-            rmap, y_rows = rpn_grad
-            h6, w6 = s["rpn_shapes"][4]
-            glist = roi_part[:4] + [torch.zeros((n, h6, w6, 256), dtype=dt, device=self.device)]
-            ops.rpn_scatter_cols_add_(sel["levels"], n, rmap, y_rows, glist)
-            dP = {k: gl for (k, _), gl in zip(lvl_shapes, glist)}
-        else:
-            (dt_all,), off = rpn_grad, 0
-            for li, (k, (h, w)) in enumerate(lvl_shapes):
-                rows = n * h * w
-                dP[k] = ops.conv2d_dgrad(dt_all[off:off + rows].view(n, h, w, 256), self.wd[rn], (h, w), 1, 1, add=roi_part[li])
-                off += rows
+        return d_feat
+
+    def _backward_trunk(self, s, dP, prefetch) -> None:
+        """dP (p2..p6 gradients, the heads' shares summed) -> p6 -> FPN -> res5 .. res3, weight gradients, the join of the streams."""
+        g = self.grad
+        p = s["p"]
         h5, w5 = p["p5"].shape[1], p["p5"].shape[2]
         dP["p5"] = ops.pool_bwd(dP["p6"], (h5, w5), dP["p5"], 1)  # p6 = p5[::2, ::2]
         # --- FPN: output convs, top-down adds, laterals (finest level first: its gradient flows up to the coarser sums) ---
@@ -793,18 +841,7 @@ class OpensetRCNNTrainer:
     def export_state_dict(self) -> Dict[str, torch.Tensor]:
         """The trainable parameters under detectron2 names and layouts (un-folded conv weights), for load_state_dict /
         checkpointing ([d2] DetectionCheckpointer writes these keys under "model")."""
-        e = self.eng
-        out: Dict[str, torch.Tensor] = {}
-        for n in self.conv_names:
-            out[n + ".weight"] = self.master[n + ".w"].permute(0, 3, 1, 2).contiguous().cpu()
-            if n + ".b" in self.master:
-                out[n + ".bias"] = self.master[n + ".b"].cpu().clone()
-        pr = e.cfg["pooler_resolution"]
-        fc1 = self.master["fc1.w"]  # (out, ph, pw, c) flattened -> the reference's (out, c*ph*pw)
-        out["roi_heads.box_head.fc1.weight"] = fc1.view(fc1.shape[0], pr, pr, -1).permute(0, 3, 1, 2).reshape(fc1.shape[0], -1).contiguous().cpu()
-        out["roi_heads.box_head.fc1.bias"] = self.master["fc1.b"].cpu().clone()
-        out["roi_heads.box_head.fc2.weight"] = self.master["fc2.w"].cpu().clone()
-        out["roi_heads.box_head.fc2.bias"] = self.master["fc2.b"].cpu().clone()
+        out = self._export_trunk()
         t_w, t_b = self.master["rpn_tail.w"].cpu(), self.master["rpn_tail.b"].cpu()
         out["proposal_generator.rpn_head.anchor_deltas.weight"] = t_w[:4].reshape(4, -1, 1, 1).clone()
         out["proposal_generator.rpn_head.anchor_deltas.bias"] = t_b[:4].clone()
@@ -816,4 +853,19 @@ class OpensetRCNNTrainer:
         for short, long in (("enc", "roi_heads.dml.encoder"), ("dec", "roi_heads.dml.decoder"), ("cls", "roi_heads.softmaxcls.cls_score")):
             out[long + ".weight"], out[long + ".bias"] = self.master[short + ".w"].cpu().clone(), self.master[short + ".b"].cpu().clone()
         out["roi_heads.dml.representatives"] = self.master["protos"].cpu().clone()
+        return out
+
+    def _export_trunk(self) -> Dict[str, torch.Tensor]:
+        """Backbone / FPN / RPN 3x3 conv and box head FC1 / FC2 masters under detectron2 names and layouts."""
+        out: Dict[str, torch.Tensor] = {}
+        for n in self.conv_names:
+            out[n + ".weight"] = self.master[n + ".w"].permute(0, 3, 1, 2).contiguous().cpu()
+            if n + ".b" in self.master:
+                out[n + ".bias"] = self.master[n + ".b"].cpu().clone()
+        pr = self.eng.cfg["pooler_resolution"]
+        fc1 = self.master["fc1.w"]  # (out, ph, pw, c) flattened -> the reference's (out, c*ph*pw)
+        out["roi_heads.box_head.fc1.weight"] = fc1.view(fc1.shape[0], pr, pr, -1).permute(0, 3, 1, 2).reshape(fc1.shape[0], -1).contiguous().cpu()
+        out["roi_heads.box_head.fc1.bias"] = self.master["fc1.b"].cpu().clone()
+        out["roi_heads.box_head.fc2.weight"] = self.master["fc2.w"].cpu().clone()
+        out["roi_heads.box_head.fc2.bias"] = self.master["fc2.b"].cpu().clone()
         return out
