@@ -706,7 +706,8 @@ osr_status osr_std_rpn_losses_bwd(const osr_rpn_levels* levels, const float* cel
  * not counted). logits (m, K+1); pred_deltas rows of delta_stride floats: the 4 deltas at column 0 (cls_agnostic) or at 4c for
  * GT class c. loss_cls = mean cross entropy * cls_weight; loss_box_reg = sum_fg smooth_l1(delta - get_deltas(proposal, gt;
  * reg_weights), beta) * box_weight / max(rows, 1). out7 = {loss_cls, loss_box_reg, rows, correct, foreground, foreground
- * correct, foreground predicted as background} (argmax: first maximum). workspace 7 KiB. */
+ * correct, foreground predicted as background} (argmax: first maximum). workspace 7 KiB. m = 0 gives zeros; the row arrays may
+ * then be null. */
 osr_status osr_fastrcnn_losses_fwd(const float* logits, const float* pred_deltas, int32_t delta_stride, int32_t cls_agnostic,
                                    const float* proposal_boxes, const float* gt_boxes, const int64_t* gt_classes, int64_t m,
                                    int32_t num_classes, const float reg_weights[4], float smooth_l1_beta, float cls_weight,

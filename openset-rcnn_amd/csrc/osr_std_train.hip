@@ -253,7 +253,8 @@ __global__ __launch_bounds__(256) void fastrcnn_losses_kernel(StdRoi p, float* _
 
 static const char* std_roi_fill(StdRoi* p, const float* logits, const float* deltas, int32_t delta_stride, int32_t agnostic, const float* prop,
                                 const float* gtb, const int64_t* cls, int64_t m, int32_t K, const float* rw, float beta) {
-    if (!logits || !deltas || !prop || !gtb || !cls || !rw) return "null pointer";
+    // (an empty batch, m = 0, may come with null data pointers -- torch's empty tensors: no row is read)
+    if ((m > 0 && (!logits || !deltas || !prop || !gtb || !cls)) || !rw) return "null pointer";
     if (m < 0 || K < 1 || !(beta >= 0.f)) return "bad m / num_classes / beta";
     if (delta_stride < (agnostic ? 4 : 4 * K)) return "delta_stride below 4 (class-agnostic) / 4K (class-specific)";
     if ((((uintptr_t)prop | (uintptr_t)gtb) & 15) != 0) return "box arrays must be 16-byte aligned";
@@ -331,7 +332,7 @@ extern "C" osr_status osr_fastrcnn_losses_bwd(const float* logits, const float* 
     const char* bad = std_roi_fill(&p, logits, pred_deltas, delta_stride, cls_agnostic, proposal_boxes, gt_boxes, gt_classes, m, num_classes, reg_weights,
                                    smooth_l1_beta);
     OSR_REQUIRE(!bad, OSR_ERR_INVALID_ARG, "osr_fastrcnn_losses_bwd: %s", bad ? bad : "");
-    OSR_REQUIRE(d_logits && d_deltas && workspace, OSR_ERR_INVALID_ARG, "osr_fastrcnn_losses_bwd: null pointer");
+    OSR_REQUIRE((m == 0 || (d_logits && d_deltas)) && workspace, OSR_ERR_INVALID_ARG, "osr_fastrcnn_losses_bwd: null pointer");
     OSR_REQUIRE(workspace_bytes >= 16, OSR_ERR_WORKSPACE, "osr_fastrcnn_losses_bwd: workspace needs 16 bytes");
     if (m == 0) return OSR_OK;
     hipStream_t st = (hipStream_t)stream;

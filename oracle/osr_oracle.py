@@ -1089,6 +1089,12 @@ def fast_rcnn_output_inference(x: torch.Tensor, proposals: torch.Tensor, image_s
     Returns (boxes, scores, classes, (row, class) of every kept detection)."""
     logits = F.linear(x, p[prefix + ".cls_score.weight"], p[prefix + ".cls_score.bias"])
     deltas = F.linear(x, p[prefix + ".bbox_pred.weight"], p[prefix + ".bbox_pred.bias"])
+    return fast_rcnn_inference_from_outputs(logits, deltas, proposals, image_size, cfg)
+
+
+def fast_rcnn_inference_from_outputs(logits: torch.Tensor, deltas: torch.Tensor, proposals: torch.Tensor, image_size, cfg=BASE_RCNN_CFG):
+    """The second half of fast_rcnn_output_inference, fed the predictor's outputs directly: logits (R, K+1), deltas (R, K*4) or
+    (R, 4) (class-agnostic). Same returns."""
     probs = F.softmax(logits, dim=-1)
     boxes = b2b_apply_deltas_multi(deltas, proposals, cfg["bbox_reg_weights"])
     valid = torch.isfinite(boxes).all(dim=1) & torch.isfinite(probs).all(dim=1)
