@@ -738,7 +738,11 @@ osr_status osr_roi_align_bwd(const osr_pyramid* dfeat, int32_t n, const float* b
  * rows [b * rois_per_image, (b + 1) * rois_per_image) belong to image b (batch_idx == b) or are padding (batch_idx < 0);
  * m == n * rois_per_image, rois_per_image <= 1024, c <= 256. Otherwise OSR_ERR_UNSUPPORTED with nothing launched: zero dfeat and
  * call osr_roi_align_bwd. out_dtype: OSR_F32, or dout's dtype -- the fp32 sums are then rounded once on the way out (what a separate
- * cast of the fp32 pyramid would give), dfeat->data pointing at tensors of that type. Same reference lines as osr_roi_align_bwd. */
+ * cast of the fp32 pyramid would give), dfeat->data pointing at tensors of that type. Same reference lines as osr_roi_align_bwd.
+ * Non-finite dout: a bin's weights are not tested before they multiply, so an Inf or NaN in dout[r][by][bx][ch] reaches channel ch of
+ * every pixel that bin weighs (as in the reference) and may also turn into NaN (0 * Inf) elsewhere in the 8 x 8 tiles RoI r reaches,
+ * never outside them and never in another channel. It is never dropped: the training step's overflow check (osr_check_finite) relies
+ * on that. Rows with batch_idx < 0 are not read at all. */
 osr_status osr_roi_align_bwd_dense(const osr_pyramid* dfeat, int32_t n, const float* boxes, const int32_t* batch_idx, int64_t m,
                                    int32_t rois_per_image, int32_t pooled, int32_t canonical_level, int32_t canonical_size, int32_t min_level,
                                    const void* dout, int32_t dout_dtype, int32_t out_dtype, void* stream);
