@@ -178,6 +178,21 @@ osr_status osr_stem_maxpool_fwd(const void* xpad, int32_t n, int32_t hp, int32_t
 osr_status osr_stem_maxpool_fwd_raw(const void* src, int32_t src_is_u8, int32_t n, int32_t h, int32_t w, int32_t hp, int32_t wp,
                                     const float mean[3], const float std[3], const void* w_view, int32_t w_rows, const float* bias,
                                     void* out, int32_t dtype, void* stream);
+/* Backward of the stem for a trainable stem (MODEL.BACKBONE.FREEZE_AT 0; csrc/osr_stem_bwd.hip). The training forward keeps the
+ * stem output: osr_conv2d_fwd(stem view, ReLU) -> s, osr_maxpool3x3s2(s) -> pooled (same bits as osr_stem_maxpool_fwd).
+ * osr_stem_pool_bwd: the max pool's and the ReLU's backward, s (n, hs, ws, c), dpool (n, (hs-1)/2+1, (ws-1)/2+1, c) -> ds (n, hs, ws, c):
+ * ds[p] = sum of dpool over the windows whose first maximum is p (scan ky then kx, (v > max) || isnan(v): torch's max_pool2d
+ * indices), 0 where s[p] <= 0. A gather in a fixed order: no atomics, repeats bit-identical. c % 8 == 0, dtype f16 / bf16. */
+osr_status osr_stem_pool_bwd(const void* s, const void* dpool, int32_t n, int32_t hs, int32_t ws, int32_t c, void* ds, int32_t dtype,
+                             void* stream);
+/* osr_stem_wgrad: dw (64, 8, 1, 32) fp32 in the stem view's layout = sum over the n * hp/2 * wp/2 stem pixels of ds[p][co] times the
+ * pixel's patch of xpad (osr_preprocess' image; row ky of the view: 8 taps x 4 channels of image row 2 oy + ky). MFMA with fp32
+ * accumulation; the pixels are cut into a fixed number of ranges (a function of the pixel count only) whose partials go to the
+ * caller's workspace (osr_stem_wgrad_workspace_bytes) and are summed in range order: no float atomics, repeats bit-identical. The
+ * 8th row, the 8th tap and the 4th channel are written as exact zeros (accumulate: dw += the gradient). ds (n, hp/2, wp/2, 64). */
+int64_t osr_stem_wgrad_workspace_bytes(int32_t n, int32_t hp, int32_t wp);
+osr_status osr_stem_wgrad(const void* xpad, const void* ds, int32_t n, int32_t hp, int32_t wp, float* dw, int32_t accumulate, void* workspace,
+                          int64_t workspace_bytes, int32_t dtype, void* stream);
 /* [d2] F.max_pool2d(k=3,s=2,p=1) of the ResNet stem, NHWC contiguous. */
 osr_status osr_maxpool3x3s2(const void* in, int32_t n, int32_t hi, int32_t wi, int32_t c, void* out, int32_t dtype,
                             void* stream);

@@ -34,6 +34,7 @@ SOURCES = {
     "osr_std_train.hip": ["-ffp-contract=off"],
     "osr_multi_tensor.hip": [],  # (same contraction setting as osr_train_bwd.hip: the multi-tensor SGD must round like osr_sgd_step)
     "osr_conv_bwd.hip": [],
+    "osr_stem_bwd.hip": [],
     "osr_train_bwd.hip": [],
 }
 COMMON = ["-O3", f"--offload-arch={ARCH}", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"] + \

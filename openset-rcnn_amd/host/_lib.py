@@ -107,6 +107,9 @@ PROTOTYPES = {
     "osr_stem_maxpool_fwd": (I32, [P, I32, I32, I32, P, I32, P, P, I32, P]),
     "osr_stem_maxpool_fwd_raw": (I32, [P, I32, I32, I32, I32, I32, I32, C.POINTER(C.c_float), C.POINTER(C.c_float), P, I32, P, P, I32, P]),
     "osr_maxpool3x3s2": (I32, [P, I32, I32, I32, I32, P, I32, P]),
+    "osr_stem_pool_bwd": (I32, [P, P, I32, I32, I32, I32, P, I32, P]),
+    "osr_stem_wgrad_workspace_bytes": (I64, [I32, I32, I32]),
+    "osr_stem_wgrad": (I32, [P, P, I32, I32, I32, P, I32, P, I64, I32, P]),
     "osr_subsample2": (I32, [P, I32, I32, I32, I32, P, I32, P]),
     "osr_gemm_f32": (I32, [P, I64, P, P, P, I64, I32, I32, I32, I32, P]),
     "osr_gemm_f32_tn_workspace_bytes": (I64, [I32, I32, I32]),

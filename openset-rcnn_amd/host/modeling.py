@@ -491,6 +491,15 @@ class SoftMaxClassifier(nn.Module):
         nn.init.constant_(self.cls_score.bias, 0)
 
 
+def freeze_at_of(cfg: CfgNode) -> int:
+    """MODEL.BACKBONE.FREEZE_AT as [d2] ResNet.freeze reads it: >= 1 freezes the stem, >= k freezes stage res<k>; values above 5
+    freeze the whole bottom-up network (act as 5), negative values are refused."""
+    v = int(cfg.MODEL.BACKBONE.FREEZE_AT)
+    if v < 0:
+        raise ValueError(f"MODEL.BACKBONE.FREEZE_AT must be >= 0, got {v}")
+    return min(v, 5)
+
+
 def engine_cfg_from(cfg: CfgNode) -> dict:
     """yaml keys -> engine hyper-parameters."""
     rh, bh, rpn = cfg.MODEL.ROI_HEADS, cfg.MODEL.ROI_BOX_HEAD, cfg.MODEL.RPN
@@ -725,6 +734,7 @@ class GeneralizedRCNN(_EngineOwner):
         self.register_buffer("pixel_mean", torch.tensor(cfg.MODEL.PIXEL_MEAN).view(-1, 1, 1), False)
         self.register_buffer("pixel_std", torch.tensor(cfg.MODEL.PIXEL_STD).view(-1, 1, 1), False)
         self._eng_cfg = engine_cfg_from(cfg)
+        self._freeze_at = freeze_at_of(cfg)  # the trainer's (a negative value is refused here, when the model is built)
         self._class_map = class_id
         self._engine_cls = StandardRCNNEngine if isinstance(self.roi_heads, StandardROIHeads) else OpensetRCNNEngine
         if self._engine_cls is StandardRCNNEngine:
@@ -793,7 +803,8 @@ class GeneralizedRCNN(_EngineOwner):
     def make_trainer(self, lr: float = 0.005, momentum: float = 0.9, weight_decay: float = 1e-4, loss_scale: float = 1024.0):
         """The training loop body of train.py:132-148 as one object: `losses = trainer.step(...)` replaces
         `loss_dict = model(data); losses.backward(); optimizer.step()` (there is no autograd graph on the HIP path). The trainer
-        owns fp32 master copies of this model's trainable parameters (res3+ weights un-folded from their FrozenBN, FPN, heads);
+        owns fp32 master copies of this model's trainable parameters (the backbone stages MODEL.BACKBONE.FREEZE_AT leaves
+        trainable, un-folded from their FrozenBN; FPN; heads);
         `load_trainer_state(trainer)` writes them back into the module for evaluation / checkpointing."""
         from .train import OpensetRCNNTrainer
         from .train_std import StandardRCNNTrainer
@@ -810,9 +821,10 @@ class GeneralizedRCNN(_EngineOwner):
         # trainer would treat dataset ids 0..NUM_KNOWN-1 as the known classes
         if self._engine_cls is StandardRCNNEngine:  # the trainer by engine class: Base-RCNN-FPN.yaml's stock heads
             return StandardRCNNTrainer(fold_frozen_bn(sd), self._eng_cfg, self.kernel_dtype, str(self.device), lr=lr, momentum=momentum,
-                                       weight_decay=weight_decay, loss_scale=loss_scale, frozen_bn=bn)
+                                       weight_decay=weight_decay, loss_scale=loss_scale, freeze_at=self._freeze_at, frozen_bn=bn)
         return OpensetRCNNTrainer(fold_frozen_bn(sd), self._eng_cfg, self.kernel_dtype, str(self.device), lr=lr, momentum=momentum,
-                                  weight_decay=weight_decay, loss_scale=loss_scale, frozen_bn=bn, class_map=self._class_map)
+                                  weight_decay=weight_decay, loss_scale=loss_scale, freeze_at=self._freeze_at, frozen_bn=bn,
+                                  class_map=self._class_map)
 
     def load_trainer_state(self, trainer, keep_trainer: bool = False) -> None:
         sd = dict(self.state_dict())

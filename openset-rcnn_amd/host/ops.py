@@ -331,6 +331,44 @@ def maxpool3x3s2(x: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def stem_pool_bwd(s: torch.Tensor, dpool: torch.Tensor) -> torch.Tensor:
+    """Backward of ReLU -> max_pool2d(3, 2, 1) of the stem (osr_stem_pool_bwd): s the (n, hs, ws, c) stem output (post-ReLU), dpool
+    the pooled output's gradient -> ds (n, hs, ws, c), zero where s <= 0."""
+    lib = _lib.load()
+    _need(s, name="s"); _need(dpool, s.dtype, "dpool")
+    n, hs, ws, c = s.shape
+    if tuple(dpool.shape) != (n, (hs - 1) // 2 + 1, (ws - 1) // 2 + 1, c):
+        raise OsrError(f"dpool shape {tuple(dpool.shape)} does not match the stem output {tuple(s.shape)}")
+    ds = torch.empty_like(s)
+    check(lib.osr_stem_pool_bwd(_p(s), _p(dpool), n, hs, ws, c, _p(ds), _DT[s.dtype], _stream()), "osr_stem_pool_bwd")
+    return ds
+
+
+def stem_wgrad(xpad: torch.Tensor, ds: torch.Tensor, hp: int, wp: int, dw: Optional[torch.Tensor] = None, accumulate: bool = False) -> torch.Tensor:
+    """Weight gradient of the stem in the stem view's layout (64, 8, 1, 32), fp32 (osr_stem_wgrad): xpad = preprocess(...), ds the
+    stem output's gradient (n, hp/2, wp/2, 64). The 8th row, the 8th tap and the 4th channel come out exactly 0."""
+    lib = _lib.load()
+    _need(xpad, name="xpad"); _need(ds, xpad.dtype, "ds")
+    n = xpad.shape[0]
+    if tuple(xpad.shape) != (n, hp + 6, stem_padded_width(wp), 4) or tuple(ds.shape) != (n, hp // 2, wp // 2, 64):
+        raise OsrError(f"stem_wgrad: xpad {tuple(xpad.shape)} / ds {tuple(ds.shape)} do not match hp={hp}, wp={wp}")
+    if dw is None:
+        dw = torch.empty((64, 8, 1, 32), dtype=torch.float32, device=xpad.device)
+        accumulate = False
+    else:
+        _need(dw, torch.float32, "dw")
+        if tuple(dw.shape) != (64, 8, 1, 32):
+            raise OsrError(f"stem_wgrad: dw must be (64, 8, 1, 32), got {tuple(dw.shape)}")
+    wsb = int(lib.osr_stem_wgrad_workspace_bytes(n, hp, wp))
+    if wsb < 0:
+        check(wsb, "osr_stem_wgrad_workspace_bytes")
+    ws = torch.empty((wsb,), dtype=torch.uint8, device=xpad.device)
+    if FLOP_COUNT is not None:
+        FLOP_COUNT["wgrad"] += 2.0 * n * (hp // 2) * (wp // 2) * 64 * 147
+    check(lib.osr_stem_wgrad(_p(xpad), _p(ds), n, hp, wp, _p(dw), int(accumulate), _p(ws), wsb, _DT[xpad.dtype], _stream()), "osr_stem_wgrad")
+    return dw
+
+
 def subsample2(x: torch.Tensor) -> torch.Tensor:
     lib = _lib.load()
     _need(x, name="x")

@@ -1,7 +1,10 @@
 """One training step of Openset R-CNN on the HIP path: forward with saved activations, the six losses, backward through every
 trainable layer, SGD with momentum -- the loop body of the reference's trainer (train.py:132-148: `loss_dict = model(data);
-losses.backward(); optimizer.step()`) for META_ARCHITECTURE GeneralizedRCNN with [d2] defaults: FREEZE_AT 2 (stem and res2
-frozen), FrozenBN everywhere, SGD momentum 0.9, weight decay 1e-4 on weights and biases.
+losses.backward(); optimizer.step()`) for META_ARCHITECTURE GeneralizedRCNN with [d2] defaults: FrozenBN everywhere, SGD
+momentum 0.9, weight decay 1e-4 on weights and biases. MODEL.BACKBONE.FREEZE_AT decides which backbone stages train (`freeze_at`:
+0 = stem and res2..res5, 1 = res2..res5, 2 = res3..res5 -- [d2]'s default and the trainer's --, ..., 5 = none; the FPN laterals of
+frozen stages still train). A trainable stem keeps its output for the backward (osr_conv2d_fwd stem view + osr_maxpool3x3s2 instead
+of the fused osr_stem_maxpool_fwd_raw) and differentiates it with osr_stem_pool_bwd / osr_stem_wgrad (csrc/osr_stem_bwd.hip).
 
 What runs where: every convolution / FC forward, data gradient and weight gradient is an MFMA kernel launch (osr_conv2d_fwd /
 osr_conv2d_wgrad), targets, sampling, losses and their gradients, RoIAlign forward/backward, the CF-RPN tail and the update are
@@ -21,7 +24,7 @@ import torch
 
 from . import ops, parallel
 from .engine import OpensetRCNNEngine, loss_types_of
-from .weights import R50_BLOCKS, pack_conv_weight, pack_fc1_weight
+from .weights import R50_BLOCKS, pack_conv_weight, pack_fc1_weight, pack_stem_weight
 
 
 def warmup_multistep_lr(iteration: int, base_lr: float, steps: Tuple[int, ...], gamma: float = 0.1, warmup_iters: int = 1000,
@@ -119,6 +122,7 @@ class OpensetRCNNTrainer:
         """params: BN-folded parameters under detectron2 names (what the engine reads). frozen_bn (optional): for convs followed by
         FrozenBatchNorm, name -> (un-folded weight (cout,cin,kh,kw), per-channel scale gamma/sqrt(var+eps)): the trainable parameter
         is the un-folded weight (weight decay acts on it, the chain rule multiplies the kernel's gradient by the scale)."""
+        freeze_at = self._check_freeze_at(freeze_at)
         self.frozen_bn = frozen_bn or {}
         self.row_scale: Dict[str, torch.Tensor] = {}
         self.eng = self._make_engine(params, cfg, dtype, device, class_map)
@@ -138,6 +142,8 @@ class OpensetRCNNTrainer:
         self.master: Dict[str, torch.Tensor] = {}
         self.lowp: Dict[str, Optional[torch.Tensor]] = {}  # working copy the forward kernels read (None: the master itself is read)
         self.conv_names: List[str] = []
+        if freeze_at == 0:
+            self._add_stem(params)
         for si, nb in enumerate(R50_BLOCKS):
             if si + 2 <= freeze_at:
                 continue
@@ -165,7 +171,8 @@ class OpensetRCNNTrainer:
             off += al(t.numel())
         self.buckets = parallel.GradBuckets(self.grad_flat, layout, bucket_bytes)
         self.mom = {k: torch.zeros_like(t) for k, t in self.master.items()}
-        self.num_params = sum(t.numel() for t in self.master.values())
+        # (the stem master is the padded (64, 8, 1, 32) view: its 6 976 padding zeros are not parameters)
+        self.num_params = sum(t.numel() for t in self.master.values()) - (16384 - 9408 if self.STEM + ".w" in self.master else 0)
         # overflow guard: device flag read by every osr_sgd_step launch; its host half is self.scaler (DynamicLossScale)
         self._ok = torch.ones((1,), dtype=torch.int32, device=dev)
         self._cside: Optional[torch.cuda.Stream] = None  # stream the gradient buckets' collectives are issued from (see _done)
@@ -200,6 +207,14 @@ class OpensetRCNNTrainer:
         return self.scaler.overflow_steps
 
     @staticmethod
+    def _check_freeze_at(freeze_at: int) -> int:
+        """[d2] ResNet.freeze semantics: values above 5 act as 5 (the whole bottom-up network frozen), negative values are refused."""
+        v = int(freeze_at)
+        if v < 0:
+            raise ValueError(f"freeze_at must be >= 0, got {v}")
+        return min(v, 5)
+
+    @staticmethod
     def _make_engine(params, cfg, dtype, device, class_map):
         return OpensetRCNNEngine(params, cfg, dtype, device, class_map)
 
@@ -220,6 +235,24 @@ class OpensetRCNNTrainer:
         self.master["dec.w"], self.master["dec.b"] = e.dec_w, e.dec_b
         self.master["cls.w"], self.master["cls.b"] = e.cls_w, e.cls_b
         self.master["protos"] = f32(params["roi_heads.dml.representatives"])
+
+    STEM = "backbone.bottom_up.stem.conv1"
+
+    def _add_stem(self, params) -> None:
+        """FREEZE_AT 0: the stem's master in the layout of the stem view the forward kernels read, (64, 8, 1, 32) fp32 (weights.pack_stem_weight:
+        the 8th row, the 8th tap and the 4th channel zero). Their gradient is exactly zero (osr_stem_wgrad) and so is their weight decay,
+        so the update leaves them zero in the master, the momentum and the working view it refreshes. No backward-data weights: nothing is
+        below the stem."""
+        e, name = self.eng, self.STEM
+        if name in self.frozen_bn:
+            w_unfolded, scale = self.frozen_bn[name]
+            self.master[name + ".w"] = pack_stem_weight(w_unfolded, torch.float32).to(e.device)
+            self.row_scale[name + ".w"] = scale.detach().float().contiguous().to(e.device)
+        else:
+            self.master[name + ".w"] = pack_stem_weight(params[name + ".weight"], torch.float32).to(e.device)
+        lw = e.w[name + ".w"]
+        assert tuple(lw.shape) == (64, 8, 1, 32), "the engine's stem view must have its 8th row (pack_stem_weight)"
+        self.lowp[name + ".w"] = lw
 
     def _add_conv(self, name: str, params, bias: bool):
         e = self.eng
@@ -352,7 +385,14 @@ class OpensetRCNNTrainer:
         e = self.eng
         cur = torch.cuda.current_stream(self.device)
         pref, self._prefetched = self._prefetched, None
-        if pref is not None and pref[0] is images and pref[1] == (hp, wp) and pref[4] == images._version:
+        if self.freeze_at == 0:
+            # trainable stem: its output is kept for the backward (the fused stem + pool launch never writes it); same pooled bits
+            c = e.cfg
+            xpad = ops.preprocess(images, hp, wp, c["pixel_mean"], c["pixel_std"], self.dtype)
+            stem = ops.stem_conv(xpad, e.w[self.STEM + ".w"], e.w[self.STEM + ".b"], hp, wp, relu=True)
+            x, frozen_feats = ops.maxpool3x3s2(stem), {}
+            s["stem"] = dict(xpad=xpad, s=stem, hp=hp, wp=wp)
+        elif pref is not None and pref[0] is images and pref[1] == (hp, wp) and pref[4] == images._version:
             # the frozen prefix of THIS batch was computed under the previous iteration's backward (step(next_images=...)): take it
             x, frozen_feats = pref[2]
             cur.wait_event(pref[3])
@@ -450,7 +490,7 @@ class OpensetRCNNTrainer:
         touches) is enqueued on a stream of its own behind the main stream's CURRENT point -- called between the forward and the
         backward, it runs under the chain of small head / loss launches that leaves the GPU nearly idle there. The next step() that is
         handed the same tensor object picks the result up (and waits for it); any other batch recomputes. Same values either way."""
-        if self.freeze_at < 2 or self.device.type != "cuda":
+        if self.freeze_at < 1 or self.device.type != "cuda":  # (freeze_at 1: the prefix is the stem alone)
             return
         cur = torch.cuda.current_stream(self.device)
         if self._pre is None:
@@ -463,8 +503,8 @@ class OpensetRCNNTrainer:
             t.record_stream(cur)
         images.record_stream(self._pre)  # (the caching allocator must not hand the batch's memory out while the side stream reads it)
         # Keyed on the tensor OBJECT and its version counter: a loader that refills one device buffer in place hands the same object with
-        # a bumped version (recompute); next_images must not be written again before the step that consumes it. load_state_dict /
-        # set_freeze_at drop the prefetch (the prefix is a function of the frozen weights).
+        # a bumped version (recompute); next_images must not be written again before the step that consumes it. A new trainer
+        # (load_state_dict drops the model's) starts without a prefetch (the prefix is a function of the frozen weights).
         self._prefetched = (images, (hp, wp), (x, feats), done, images._version)
 
     # ---- backward -------------------------------------------------------------------------------------------------
@@ -733,6 +773,13 @@ class OpensetRCNNTrainer:
                 G = ops.conv2d_dgrad(G, self.wd[pre + ".shortcut"], (hx, wx), stride, 0, add=dx, post_mask=pm)
             else:
                 G = ops.conv2d_dgrad(d_o1, self.wd[pre + ".conv1"], (hx, wx), 1, 0, add=G, post_mask=pm)
+        if self.freeze_at == 0:
+            # G: the gradient of the pooled stem output (masked where it is <= 0 by the launch that formed it) -> max pool + ReLU
+            # backward -> the stem's weight gradient (csrc/osr_stem_bwd.hip)
+            st = s["stem"]
+            ds = ops.stem_pool_bwd(st["s"], G)
+            self._wg(lambda: ops.stem_wgrad(st["xpad"], ds, st["hp"], st["wp"], dw=g[self.STEM + ".w"]), ds, st["xpad"])
+            self._done(self.STEM + ".w")
         if prefetch is not None:  # behind the last data gradient: the main stream is done, the weight-gradient stream still has its backlog
             self._prefetch_frozen(*prefetch)
         if self.side_wgrad and self._wside is not None:  # join: the update (and any collective issued from here on) sees every weight gradient
@@ -858,6 +905,8 @@ class OpensetRCNNTrainer:
     def _export_trunk(self) -> Dict[str, torch.Tensor]:
         """Backbone / FPN / RPN 3x3 conv and box head FC1 / FC2 masters under detectron2 names and layouts."""
         out: Dict[str, torch.Tensor] = {}
+        if self.STEM + ".w" in self.master:  # stem view (64, 8, 1, 32) -> (64, 3, 7, 7)
+            out[self.STEM + ".weight"] = self.master[self.STEM + ".w"].view(64, 8, 8, 4)[:, :7, :7, :3].permute(0, 3, 1, 2).contiguous().cpu()
         for n in self.conv_names:
             out[n + ".weight"] = self.master[n + ".w"].permute(0, 3, 1, 2).contiguous().cpu()
             if n + ".b" in self.master:
