@@ -813,6 +813,44 @@ osr_status osr_sgd_step_multi(const osr_sgd_tensor* table, const int32_t* chunks
                               void* stream);
 osr_status osr_pack_dgrad_weight_multi(const osr_pack_tensor* table, const int32_t* chunks, int32_t num_chunks, void* stream);
 
+/* The solver options of [d2] build_optimizer beyond one SGD group (csrc/osr_solver.hip): per-parameter gradient clipping
+ * (SOLVER.CLIP_GRADIENTS, CLIP_TYPE "value" / "norm"), a learning-rate factor and weight decay per parameter group
+ * (BIAS_LR_FACTOR, WEIGHT_DECAY_BIAS) and Nesterov momentum. The table entries are SEGMENTS: one parameter each, a row-aligned
+ * element range of a master (param / grad / momentum / row_scale / lowp already offset to its first row). `chunks` as for
+ * osr_sgd_step_multi; the chunks of a segment are the contiguous run [chunk0, chunk0 + nchunks) of the list.
+ * Per element, with d = grad*grad_scale*row_scale:
+ *   clip_mode VALUE: d = clamp(d, -clip_value, clip_value); NORM: d *= c when c = clip_value / (||d||_norm_type + 1e-6) < 1,
+ *   the norm over the segment's elements (inf: max |d|);
+ *   d += weight_decay*param; buf = momentum*buf + d; d = nesterov ? d + momentum*buf : buf; param -= lr*lr_factor*d;
+ *   lowp (nullable) = (T)(param*row_scale).
+ * With clip_mode NONE, lr_factor 1, nesterov 0 the arithmetic is osr_sgd_step_multi's (same bits). */
+typedef enum { OSR_CLIP_NONE = 0, OSR_CLIP_VALUE = 1, OSR_CLIP_NORM = 2 } osr_clip_mode;
+typedef struct osr_sgd_segment {
+    float* param;
+    const float* grad;
+    float* momentum;
+    const float* row_scale; /* nullable: one value per row of row_elems elements, from the segment's first row */
+    void* lowp;             /* nullable: low-precision working copy, lowp_dtype */
+    int64_t n;              /* elements of the segment */
+    int64_t row_elems;      /* >= 1 */
+    int32_t lowp_dtype;
+    int32_t chunk0;         /* first chunk of this segment in `chunks` (and in the norm partials) */
+    int32_t nchunks;
+    float lr_factor;
+    float weight_decay;
+    int32_t nesterov;
+} osr_sgd_segment;
+/* Norm pass: partials[c] (double, one per chunk) = sum over chunk c of |grad*grad_scale*row_scale|^norm_type, or its max for
+ * norm_type = inf (1, 2 and inf special-cased; any other norm_type > 0 through powf). One read of every segment's gradient;
+ * finite_flag (nullable, device int32, preset to 1) is cleared when any of it is inf or NaN, as osr_check_finite would. No atomics. */
+osr_status osr_grad_norm_partials(const osr_sgd_segment* table, const int32_t* chunks, int32_t num_chunks, int32_t chunk_elems,
+                                  float grad_scale, float norm_type, double* partials, int32_t* finite_flag, void* stream);
+/* SGD over every segment, one launch; clip_mode NORM reads the partials of osr_grad_norm_partials (same table and chunks) and
+ * sums each segment's in a fixed order. apply_flag (nullable): when it reads 0 the launch changes nothing. */
+osr_status osr_sgd_step_multi_ex(const osr_sgd_segment* table, const int32_t* chunks, int32_t num_chunks, int32_t chunk_elems,
+                                 float lr, float momentum, float grad_scale, int32_t clip_mode, float clip_value, float norm_type,
+                                 const double* partials, const int32_t* apply_flag, void* stream);
+
 /* Overflow guard: *flag (device int32, preset to 1 by the caller) is cleared when any of the n floats of x is inf or NaN.
  * The reference trains in fp32 and has no such step (train.py:135-146); the fp16 gradients of this build do, and an
  * overflowed iteration must not reach the fp32 masters or a checkpoint. x 16-byte aligned. Asynchronous, no host sync. */

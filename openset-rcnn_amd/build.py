@@ -33,6 +33,7 @@ SOURCES = {
     "osr_rpn_sparse.hip": ["-ffp-contract=off"],
     "osr_std_train.hip": ["-ffp-contract=off"],
     "osr_multi_tensor.hip": [],  # (same contraction setting as osr_train_bwd.hip: the multi-tensor SGD must round like osr_sgd_step)
+    "osr_solver.hip": [],
     "osr_conv_bwd.hip": [],
     "osr_stem_bwd.hip": [],
     "osr_train_bwd.hip": [],

@@ -73,6 +73,16 @@ class SgdTensor(C.Structure):
                 ("n", C.c_int64), ("row_elems", C.c_int64), ("lowp_dtype", C.c_int32), ("reserved", C.c_int32)]
 
 
+class SgdSegment(C.Structure):
+    """include/osr.h osr_sgd_segment: one parameter (a row range of a master) of osr_sgd_step_multi_ex / osr_grad_norm_partials."""
+    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("momentum", C.c_void_p), ("row_scale", C.c_void_p), ("lowp", C.c_void_p),
+                ("n", C.c_int64), ("row_elems", C.c_int64), ("lowp_dtype", C.c_int32), ("chunk0", C.c_int32), ("nchunks", C.c_int32),
+                ("lr_factor", C.c_float), ("weight_decay", C.c_float), ("nesterov", C.c_int32)]
+
+
+OSR_CLIP_NONE, OSR_CLIP_VALUE, OSR_CLIP_NORM = 0, 1, 2
+
+
 class PackTensor(C.Structure):
     _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("cout", C.c_int32), ("kh", C.c_int32), ("kw", C.c_int32), ("cin", C.c_int32),
                 ("elem_bytes", C.c_int32), ("reserved", C.c_int32)]
@@ -190,6 +200,8 @@ PROTOTYPES = {
     "osr_pack_dgrad_weight": (I32, [P, P, I32, I32, I32, I32, I32, P]),
     "osr_sgd_step_multi": (I32, [P, P, I32, I32, F32, F32, F32, F32, P, P]),
     "osr_pack_dgrad_weight_multi": (I32, [P, P, I32, P]),
+    "osr_grad_norm_partials": (I32, [P, P, I32, I32, F32, F32, P, P, P]),
+    "osr_sgd_step_multi_ex": (I32, [P, P, I32, I32, F32, F32, F32, I32, F32, F32, P, P, P]),
 }
 
 _lib = None

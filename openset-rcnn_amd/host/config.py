@@ -69,6 +69,8 @@ class CfgNode(dict):
             return type(old)(new)
         if isinstance(old, float) and isinstance(new, int):
             return float(new)
+        if isinstance(old, float) and isinstance(new, str) and new.strip().lower() in ("inf", "+inf", ".inf"):
+            return float("inf")  # SOLVER.CLIP_GRADIENTS.NORM_TYPE inf (the max norm) from a command line
         raise ValueError(f"Type mismatch for config key {key}: {type(old).__name__} vs {type(new).__name__} ({new!r})")
 
     def _merge(self, other: dict, path: str):
@@ -171,7 +173,8 @@ def get_cfg() -> CfgNode:
     c.SOLVER = CN({"LR_SCHEDULER_NAME": "WarmupMultiStepLR", "MAX_ITER": 40000, "BASE_LR": 0.001, "MOMENTUM": 0.9, "NESTEROV": False,
                    "WEIGHT_DECAY": 0.0001, "WEIGHT_DECAY_NORM": 0.0, "GAMMA": 0.1, "STEPS": (30000,), "WARMUP_FACTOR": 1.0 / 1000,
                    "WARMUP_ITERS": 1000, "WARMUP_METHOD": "linear", "CHECKPOINT_PERIOD": 5000, "IMS_PER_BATCH": 16,
-                   "BIAS_LR_FACTOR": 1.0, "WEIGHT_DECAY_BIAS": 0.0001})
+                   "BIAS_LR_FACTOR": 1.0, "WEIGHT_DECAY_BIAS": 0.0001, "BASE_LR_END": 0.0})
+    c.SOLVER.CLIP_GRADIENTS = CN({"ENABLED": False, "CLIP_TYPE": "value", "CLIP_VALUE": 1.0, "NORM_TYPE": 2.0})
     c.TEST = CN({"EVAL_PERIOD": 0, "DETECTIONS_PER_IMAGE": 100})
     return c
 

@@ -1361,6 +1361,73 @@ def sgd_step_multi_(plan: MultiTensorPlan, lr: float, momentum: float, weight_de
                                  _p(apply_flag), _stream()), "osr_sgd_step_multi")
 
 
+CLIP_MODES = {None: _lib.OSR_CLIP_NONE, "value": _lib.OSR_CLIP_VALUE, "norm": _lib.OSR_CLIP_NORM}
+
+
+def sgd_segment_plan(entries, device) -> MultiTensorPlan:
+    """The table of osr_sgd_step_multi_ex / osr_grad_norm_partials. entries: [(param, grad, momentum_buf, row_scale | None, lowp | None,
+    row0, row1, lr_factor, weight_decay, nesterov)]: one parameter each, rows [row0, row1) of the leading dimension of a master (fp32
+    param / grad / buf of equal size). The plan also owns the norm partials (float64, one per chunk)."""
+    tab = (_lib.SgdSegment * len(entries))()
+    chunks: List[int] = []
+    keep = []
+    for ti, (pm, gr, buf, rs, lp, r0, r1, lr_factor, wd, nesterov) in enumerate(entries):
+        _need(pm, torch.float32, "param"); _need(gr, torch.float32, "grad"); _need(buf, torch.float32, "buf")
+        if gr.numel() != pm.numel() or buf.numel() != pm.numel() or (lp is not None and lp.numel() != pm.numel()):
+            raise OsrError("sgd_segment_plan: size mismatch")
+        rows = pm.shape[0]
+        if not 0 <= r0 < r1 <= rows:
+            raise OsrError(f"sgd_segment_plan: rows [{r0}, {r1}) outside a master of {rows} rows")
+        re = pm.numel() // rows
+        if rs is not None:
+            _need(rs, torch.float32, "row_scale")
+            if rs.numel() != rows:
+                raise OsrError("sgd_segment_plan: row_scale must hold one value per row")
+        if lp is not None:
+            _need(lp, name="lowp")
+        t = tab[ti]
+        off = r0 * re
+        t.param, t.grad, t.momentum = pm.data_ptr() + 4 * off, gr.data_ptr() + 4 * off, buf.data_ptr() + 4 * off
+        t.row_scale = rs.data_ptr() + 4 * r0 if rs is not None else None
+        t.lowp = lp.data_ptr() + lp.element_size() * off if lp is not None else None
+        t.n = (r1 - r0) * re
+        t.row_elems = re if rs is not None else 1
+        t.lowp_dtype = _DT[lp.dtype] if lp is not None else 0
+        t.chunk0 = len(chunks) // 2
+        t.nchunks = (t.n + SGD_CHUNK_ELEMS - 1) // SGD_CHUNK_ELEMS
+        t.lr_factor, t.weight_decay, t.nesterov = float(lr_factor), float(wd), int(bool(nesterov))
+        for c in range(t.nchunks):
+            chunks += [ti, c]
+        keep += [pm, gr, buf, rs, lp]
+    ch = torch.tensor(chunks, dtype=torch.int32).to(device)
+    plan = MultiTensorPlan(_upload_struct_array(tab, device), ch, len(chunks) // 2, keep, SGD_CHUNK_ELEMS)
+    plan.partials = torch.zeros((max(plan.num_chunks, 1),), dtype=torch.float64, device=device)
+    plan.segments = [(t.chunk0, t.nchunks) for t in tab]
+    return plan
+
+
+def grad_norm_partials_(plan: MultiTensorPlan, grad_scale: float, norm_type: float, finite_flag: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """osr_grad_norm_partials: plan.partials[c] = sum over chunk c of |grad*grad_scale*row_scale|^norm_type (max for inf); clears
+    finite_flag where a gradient of the plan is inf / NaN. Returns plan.partials."""
+    lib = _lib.load()
+    if finite_flag is not None:
+        _need(finite_flag, torch.int32, "finite_flag")
+    check(lib.osr_grad_norm_partials(_p(plan.table), _p(plan.chunks), plan.num_chunks, plan.chunk_elems, grad_scale, float(norm_type),
+                                     _p(plan.partials), _p(finite_flag), _stream()), "osr_grad_norm_partials")
+    return plan.partials
+
+
+def sgd_step_multi_ex_(plan: MultiTensorPlan, lr: float, momentum: float, grad_scale: float = 1.0, clip: Optional[str] = None,
+                       clip_value: float = 1.0, norm_type: float = 2.0, apply_flag: Optional[torch.Tensor] = None) -> None:
+    """osr_sgd_step_multi_ex over every segment of the plan, one launch. clip None / "value" / "norm" ("norm" reads the partials of
+    the grad_norm_partials_ call before it)."""
+    lib = _lib.load()
+    if clip not in CLIP_MODES:
+        raise ValueError(f"clip mode {clip!r}: None, 'value' or 'norm'")
+    check(lib.osr_sgd_step_multi_ex(_p(plan.table), _p(plan.chunks), plan.num_chunks, plan.chunk_elems, lr, momentum, grad_scale, CLIP_MODES[clip],
+                                    clip_value, float(norm_type), _p(plan.partials), _p(apply_flag), _stream()), "osr_sgd_step_multi_ex")
+
+
 def pack_dgrad_multi_plan(pairs, device) -> MultiTensorPlan:
     """pairs: [(w, out)] as pack_dgrad_weight takes them (w (cout,kh,kw,cin) or a 2-d (n,k) matrix; out of the same size and dtype)."""
     tab = (_lib.PackTensor * len(pairs))()

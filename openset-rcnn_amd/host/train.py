@@ -185,6 +185,10 @@ class OpensetRCNNTrainer:
         self.chain_forward = True  # res3 blocks: conv2 -> conv3 in one launch that also stores conv2's output (osr_conv2d_chain_fwd_ex)
         self.multi_tensor_update = True  # the update as two launches (ops.sgd_step_multi_, ops.pack_dgrad_weight_multi_); False: one launch per tensor
         self._sgd_plan = None
+        self._segment_plan = None
+        # [d2] solver options beyond one plain SGD group (solver.SolverOptions: clipping, bias group, Nesterov), set by HipSGD.step;
+        # None: the plain update (osr_check_finite + osr_sgd_step_multi)
+        self.solver_options = None
         self._pack_plan = None
         self._pre: Optional[torch.cuda.Stream] = None  # stream of the next batch's frozen prefix (_prefetch_frozen)
         self.backward_concurrency_hint = 2  # launch streams of the backward (data gradients + weight gradients): see step(); 24.0 -> 23.7 ms
@@ -798,8 +802,11 @@ class OpensetRCNNTrainer:
         flag is read back lazily by `poll_overflow()` -- no host sync here."""
         gs = 1.0 / (getattr(self, "_scale_used", self.loss_scale) * world)
         self._ok.fill_(1)
-        ops.check_finite_(self.grad_flat, self._ok)
-        self._apply_sgd(self.lr, self.momentum, self.weight_decay, gs)
+        if self.solver_options is None:
+            ops.check_finite_(self.grad_flat, self._ok)
+            self._apply_sgd(self.lr, self.momentum, self.weight_decay, gs)
+        else:
+            self._apply_sgd_ex(self.solver_options, gs)
         self.scaler.record(self._ok, getattr(self, "_proposal_status", None))
         self._proposal_status = None
 
@@ -825,6 +832,38 @@ class OpensetRCNNTrainer:
             # three streams of the trainer they run three abreast instead of one behind the other
             self._fan([lambda k=k, pm=pm: ops.sgd_step_(pm, self.grad[k], self.mom[k], lr, momentum, weight_decay, gs, self.row_scale.get(k),
                                                        self.lowp.get(k), self._ok) for k, pm in self.master.items()])
+        self._refresh_derived()
+
+    def _param_rows(self) -> Dict[str, List[int]]:
+        """Masters that hold several detectron2 parameters as contiguous row ranges: name -> row boundaries (see export_state_dict).
+        Every other master is one parameter."""
+        return {"rpn_tail.w": [0, 4, 5], "rpn_tail.b": [0, 4, 5],  # anchor_deltas, centerness
+                "pred.w": [0, 4, 5], "pred.b": [0, 4, 5]}          # bbox_pred, iou_pred
+
+    def _apply_sgd_ex(self, o, gs: float) -> None:
+        """The update with the [d2] solver options (solver.SolverOptions o): one segment per detectron2 parameter (bias masters in the
+        bias group), per-parameter clipping of the averaged gradient grad * gs * row_scale, Nesterov momentum. Norm clipping: the
+        norm pass also clears the overflow flag (osr_grad_norm_partials covers every master: the flat buffer's alignment padding is
+        never written). Runs after all_reduce_grads(), so every rank computes the same coefficients."""
+        wd_bias = self.weight_decay if o.weight_decay_bias is None else o.weight_decay_bias
+        key = (tuple(t.data_ptr() for k in self.master for t in (self.master[k], self.grad[k], self.mom[k]) + ((self.lowp[k],) if self.lowp.get(k) is not None else ())),
+               o.bias_lr_factor, wd_bias, self.weight_decay, o.nesterov)
+        if self._segment_plan is None or self._segment_plan[0] != key:
+            rows = self._param_rows()
+            entries = []
+            for k, pm in self.master.items():
+                bias = k.endswith(".b")
+                bounds = rows.get(k, [0, pm.shape[0]])
+                for r0, r1 in zip(bounds[:-1], bounds[1:]):
+                    entries.append((pm, self.grad[k], self.mom[k], self.row_scale.get(k), self.lowp.get(k), r0, r1,
+                                    o.bias_lr_factor if bias else 1.0, wd_bias if bias else self.weight_decay, o.nesterov))
+            self._segment_plan = (key, ops.sgd_segment_plan(entries, self.device))
+        plan = self._segment_plan[1]
+        if o.clip == "norm":
+            ops.grad_norm_partials_(plan, gs, o.norm_type, self._ok)
+        else:
+            ops.check_finite_(self.grad_flat, self._ok)
+        ops.sgd_step_multi_ex_(plan, self.lr, self.momentum, gs, o.clip, o.clip_value, o.norm_type, self._ok)
         self._refresh_derived()
 
     # several ranks: step k applies the verdicts of the updates up to k - 1 - MULTI_RANK_LAG, waited for -- the same set on every rank

@@ -61,6 +61,10 @@ class StandardRCNNTrainer(OpensetRCNNTrainer):
         self.master["cls.w"], self.master["cls.b"] = e.cls_w, e.cls_b
         self._pixel_lv: Dict[tuple, object] = {}
 
+    def _param_rows(self):
+        a = self.eng.num_anchors
+        return {"rpn_tail.w": [0, a, 5 * a], "rpn_tail.b": [0, a, 5 * a]}  # objectness_logits, anchor_deltas
+
     def _refresh_heads(self) -> None:
         e = self.eng
         if not hasattr(self, "t_cls"):  # zero-padded transposes of the fp32 output layers: the padding columns are written once
