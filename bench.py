@@ -10,9 +10,12 @@ The K timed steps are K such passes, each captured as one hipGraph; consecutive 
 starts while pass i is still in its RoI heads -- a serving loop with four batches in flight. All K passes have completed when the
 closing synchronize returns; ms_per_step = elapsed / K (the latency of one pass alone is what --passes-in-flight 1 reports).
 
-    python bench.py --gpus N --steps K --warmup W        (N>1: launched by torch.distributed.run, one rank/GPU)
+    python bench.py --gpus N --steps K --warmup W [--full]        (N>1: launched by torch.distributed.run, one rank/GPU)
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with these extra objects:
+Prints ONE JSON line on rank 0: the headline (metric, value, unit, higher_is_better, dtype, ms_per_step) and a `config` object that
+describes the run. A plain run does only what that line needs: set-up (weights, the calibration pass, the lanes' captures), the W
+warm-up and K timed steps, --dump-outputs, the line. With --full the same line also carries these objects, each measured after the
+timed steps (the --no-* options skip single legs of it):
   roofline     -- the dominant kernel family (MFMA implicit-GEMM conv/FC): algorithmic FLOPs per step divided by
                   the summed duration of its launches, measured with HIP events on the launch stream.
   roofline_hbm -- the HBM group of SURVEY.md 8d (RoIAlign + proposal selection + NMS): algorithmic bytes per step over
@@ -173,7 +176,7 @@ def measure_traffic(timeout_s: int = 150):
             for counter in ("FETCH_SIZE", "WRITE_SIZE"):
                 d = os.path.join(tmp, counter)
                 cmd = ["rocprofv3", "--pmc", counter, "--kernel-trace", "--output-format", "csv", "-d", d, "-o", "run", "--", sys.executable,
-                       os.path.abspath(__file__), "--steps", str(steps), "--warmup", str(warm), "--no-cpu-baseline", "--no-train-step", "--no-pmc",
+                       os.path.abspath(__file__), "--full", "--steps", str(steps), "--warmup", str(warm), "--no-cpu-baseline", "--no-train-step", "--no-pmc",
                        "--no-parity", "--no-pcie", "--streams", "1", "--no-graph"]
                 env = dict(os.environ, TMPDIR="/tmp")
                 # a session of its own: on a time-out the WHOLE group is killed (rocprofv3 and the profiled python under it) and
@@ -190,7 +193,7 @@ def measure_traffic(timeout_s: int = 150):
         conv = lambda c, f: sum(v[0] for k, v in out[c].items() if k.startswith("conv_igemm") or k.startswith("splitk_reduce") or k.startswith("bottleneck64") or k.startswith("stem_pool")) * 1024 * f / 1e9  # noqa: E731
         roi = lambda c, f: sum(v[0] for k, v in out[c].items() if k.startswith("roi_align")) * 1024 * f / 1e9  # noqa: E731
         return (round(conv("FETCH_SIZE", 2) + conv("WRITE_SIZE", 1), 2), round(roi("FETCH_SIZE", 2) + roi("WRITE_SIZE", 1), 2),
-                "measured in this run: two child passes of `bench.py --steps 2 --warmup 1 --streams 1 --no-graph` under rocprofv3 --pmc FETCH_SIZE "
+                "measured in this run: two child passes of `bench.py --full --steps 2 --warmup 1 --streams 1 --no-graph` under rocprofv3 --pmc FETCH_SIZE "
                 "(x2, gfx950) / --pmc WRITE_SIZE, separate passes")
     except Exception:  # noqa: BLE001  (profiler missing pieces, time-out, parse error: fall back to the committed profile)
         return None
@@ -752,6 +755,9 @@ def main(argv=None) -> int:
     ap.add_argument("--dtype", default="f16", choices=["f16"],
                     help="storage dtype of the benchmarked path. (bf16 kernels exist for the training step; as an inference storage type "
                          "bf16 reproduces a quarter of the fp32 detections, tests/test_e2e_parity.py, so it is not offered here)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also measure the rooflines, HBM traffic, single-pass, PCIe-inclusive, full-list, parity / fp32 and "
+                         "vendor-GEMM figures, the config-3 / config-4 train steps and the CPU baseline (the --no-* options skip single legs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-train-step", action="store_true", help="skip the config-3 train-step leg")
     ap.add_argument("--no-pmc", action="store_true", help="do not measure HBM traffic with rocprofv3 child passes (quote the committed profile)")
@@ -769,13 +775,15 @@ def main(argv=None) -> int:
     ap.add_argument("--lane-hint", type=int, default=1, help="1: pass the number of lanes to the conv tile model as its concurrency hint")
     ap.add_argument("--no-graph", dest="graph", action="store_false", help="launch eagerly instead of replaying a captured hipGraph")
     ap.add_argument("--no-chain", action="store_true", help="(A/B) run res3's conv2 and conv3 as separate launches instead of osr_conv2d_chain_fwd")
-    ap.add_argument("--stages", action="store_true", help="also print a per-stage breakdown to stderr")
-    ap.add_argument("--layers", action="store_true", help="also print every MFMA launch (time, TFLOP/s, GB/s) to stderr")
+    ap.add_argument("--stages", action="store_true", help="with --full: also print a per-stage breakdown to stderr")
+    ap.add_argument("--layers", action="store_true", help="with --full: also print every MFMA launch (time, TFLOP/s, GB/s) to stderr")
     ap.add_argument("--dump-outputs", metavar="DIR", help="write the detections of the last timed step (every rank, in rank order) as DIR/<name>.npy")
     argv = list(sys.argv[1:] if argv is None else argv)
     args = ap.parse_args(argv)
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if (args.stages or args.layers) and not args.full:
+        ap.error("--stages and --layers come from the attribution pass of --full")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return launch_ranks(args.gpus, argv)  # (before any GPU call: this process only relays the job)
@@ -905,6 +913,47 @@ def main(argv=None) -> int:
     n_det = int(out[3].sum().item())
     eng_unknown_id = eng.cfg["unknown_id"]
     n_unknown = int((out[2] == eng.cfg["unknown_id"]).logical_and(torch.arange(out[2].shape[1], device=out[2].device)[None, :] < out[3][:, None]).sum().item())
+    line = None
+    if rank == 0:
+        ms = elapsed / args.steps * 1e3
+        line = {
+            "metric": METRIC, "value": round(world * args.batch * args.steps / elapsed, 2), "unit": "images/sec",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms, 3),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
+            "config": {"workload": "VOC-COCO openset_rcnn_R50_FPN_128k.yaml, inference-only, 3x800x1333 uint8 BGR -> padded 800x1344, "
+                                   "1000 proposals/level (4273/img), 1000 dets/img, 50+50 final",
+                       "batch_per_gpu": args.batch, "global_batch": args.batch * world, "parallelism": f"dp{world} (images sharded, no collective)",
+                       "weights": "random-init (seed 0), FrozenBN folded; PLN encoder bias calibrated for a known/unknown mix at UNK_THR 0.23",
+                       "detections_last_step": n_det, "unknown_detections_last_step": n_unknown, "known_detections_last_step": n_det - n_unknown,
+                       "micro_batch_streams": args.streams, "hipgraph": bool(args.graph),
+                       "ranks": identity["ranks"], "gpu_uuids": identity["gpu_uuids"], "distinct_gpus": identity["distinct_gpus"],
+                       "device_names": identity["device_names"], "per_rank_images_per_sec": identity["per_rank_images_per_sec"],
+                       "per_rank_ms_per_step": identity["per_rank_ms_per_step"],
+                       "passes_in_flight": max(1, len(lanes)),
+                       "images_in_flight": args.batch * max(1, len(lanes)),
+                       "lane_memory_GB": round(lane_gb, 2) if lane_gb is not None else None,
+                       "value_note": "throughput with passes_in_flight batches of 16 resident (each lane: own images, buffers, stream); the one-batch-at-a-time "
+                                     "figure is `single_pass`; the fp16 path's agreement with fp32 is `parity` (both with --full)"},
+        }
+
+    def finish(rc: int) -> int:
+        """Rank 0 prints the line; --dump-outputs writes every rank's detections of the last timed step."""
+        if rank == 0:
+            print(json.dumps(line), file=out_stream, flush=True)
+        if snapshot is not None:
+            host = snapshot_to_host(snapshot, n_det, n_unknown, eng_unknown_id)
+            per_rank = [host]
+            if dist is not None:
+                per_rank = [None] * world if rank == 0 else None
+                dist.gather_object(host, per_rank, dst=0)
+            if rank == 0:
+                dump_outputs(args.dump_outputs, per_rank, params["roi_heads.dml.encoder.bias"])
+        if dist is not None:
+            dist.destroy_process_group()
+        return rc
+
+    if not args.full:
+        return finish(0)
 
     # ---- one pass at a time: the same K steps on lane 0 alone (its graph, its stream; 16 images in flight, as in config 2) ----
     single_pass = None
@@ -1039,33 +1088,11 @@ def main(argv=None) -> int:
         print(f"  MFMA kernels total {mfma_ms:.3f} ms, HBM group {hbm_ms:.3f} ms of {elapsed / args.steps * 1e3:.3f} ms/step", file=sys.stderr)
 
     if rank == 0:
-        ms = elapsed / args.steps * 1e3
-        line = {
-            "metric": METRIC, "value": round(world * args.batch * args.steps / elapsed, 2), "unit": "images/sec",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms, 3),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
-            "config": {"workload": "VOC-COCO openset_rcnn_R50_FPN_128k.yaml, inference-only, 3x800x1333 uint8 BGR -> padded 800x1344, "
-                                   "1000 proposals/level (4273/img), 1000 dets/img, 50+50 final",
-                       "batch_per_gpu": args.batch, "global_batch": args.batch * world, "parallelism": f"dp{world} (images sharded, no collective)",
-                       "weights": "random-init (seed 0), FrozenBN folded; PLN encoder bias calibrated for a known/unknown mix at UNK_THR 0.23",
-                       "detections_last_step": n_det, "unknown_detections_last_step": n_unknown, "known_detections_last_step": n_det - n_unknown,
-                       "micro_batch_streams": args.streams, "hipgraph": bool(args.graph),
-                       "ranks": identity["ranks"], "gpu_uuids": identity["gpu_uuids"], "distinct_gpus": identity["distinct_gpus"],
-                       "device_names": identity["device_names"], "per_rank_images_per_sec": identity["per_rank_images_per_sec"],
-                       "per_rank_ms_per_step": identity["per_rank_ms_per_step"],
-                       "passes_in_flight": max(1, len(lanes)),
-                       "images_in_flight": args.batch * max(1, len(lanes)),
-                       "lane_memory_GB": round(lane_gb, 2) if lane_gb is not None else None,
-                       "value_note": "throughput with passes_in_flight batches of 16 resident (each lane: own images, buffers, stream); the one-batch-at-a-time "
-                                     "figure is `single_pass`; the fp16 path's agreement with fp32 is `parity`"},
-            "roofline": roofline, "roofline_hbm": roofline_hbm,
-        }
+        line.update(roofline=roofline, roofline_hbm=roofline_hbm)
         if single_pass is not None:
             line["single_pass"] = single_pass
         if pcie is not None:
             line["pcie_inclusive"] = pcie
-    else:
-        line = None
 
     del eng, out
     if args.graph:
@@ -1128,21 +1155,9 @@ def main(argv=None) -> int:
         guard.cancel()
         if rank == 0:
             line["config4"] = c4
-    if rank == 0:
-        if not args.no_cpu_baseline:  # host-only: rank 0 times it whatever N is (the other ranks wait at the closing barrier)
-            line["cpu_baseline"] = cpu_baseline(params, args.cpu_batch, one_thread=world == 1)
-        print(json.dumps(line), file=out_stream, flush=True)
-    if snapshot is not None:
-        host = snapshot_to_host(snapshot, n_det, n_unknown, eng_unknown_id)
-        per_rank = [host]
-        if dist is not None:
-            per_rank = [None] * world if rank == 0 else None
-            dist.gather_object(host, per_rank, dst=0)
-        if rank == 0:
-            dump_outputs(args.dump_outputs, per_rank, params["roi_heads.dml.encoder.bias"])
-    if dist is not None:
-        dist.destroy_process_group()
-    return rc
+    if rank == 0 and not args.no_cpu_baseline:  # host-only: rank 0 times it whatever N is (the other ranks wait at the closing barrier)
+        line["cpu_baseline"] = cpu_baseline(params, args.cpu_batch, one_thread=world == 1)
+    return finish(rc)
 
 
 if __name__ == "__main__":

@@ -8,6 +8,6 @@ for round in 1 2; do
   for v in A B; do
     if [ $v = A ]; then F="$FA"; else F="$FB"; fi
     OSR_EXTRA_HIPCC_FLAGS="$F" python3 openset-rcnn_amd/build.py > /dev/null 2>&1
-    python3 bench.py $ARGS 2>/dev/null | python3 -c "import sys, json; d = json.loads(sys.stdin.readline()); print('$v [$F] round $round:', d['value'], 'img/s', d['ms_per_step'], 'ms/step; conv family', d['roofline']['kernel_ms_per_step'], 'ms')"
+    python3 bench.py --full $ARGS 2>/dev/null | python3 -c "import sys, json; d = json.loads(sys.stdin.readline()); print('$v [$F] round $round:', d['value'], 'img/s', d['ms_per_step'], 'ms/step; conv family', d['roofline']['kernel_ms_per_step'], 'ms')"
   done
 done

@@ -4,6 +4,6 @@
 ROUNDS=${ROUNDS:-2}; STEPS=${STEPS:-20}
 for round in $(seq 1 $ROUNDS); do
   for E in "$@"; do
-    env $E python3 bench.py --steps $STEPS --warmup 5 --no-cpu-baseline 2>/dev/null | python3 -c "import sys, json; d = json.loads(sys.stdin.readline()); print('[$E] round $round:', d['value'], 'img/s', d['ms_per_step'], 'ms/step; conv family', d['roofline']['kernel_ms_per_step'], 'ms')"
+    env $E python3 bench.py --full --steps $STEPS --warmup 5 --no-cpu-baseline 2>/dev/null | python3 -c "import sys, json; d = json.loads(sys.stdin.readline()); print('[$E] round $round:', d['value'], 'img/s', d['ms_per_step'], 'ms/step; conv family', d['roofline']['kernel_ms_per_step'], 'ms')"
   done
 done

@@ -1,9 +1,11 @@
 #!/bin/bash
 # Per-layer time of every conv / FC launch under each forced tile configuration (OSR_CONV_FORCE_TILE, diagnostic knob of
-# osr_conv_gemm64.hip), single stream, for the given batch sizes. Output: gpurun_out/tiles_b<batch>_f<cfg>.log
+# osr_conv_gemm64.hip), single stream, for the given batch sizes. Output: $OUT/tiles_b<batch>_f<cfg>.log (OUT default: tiles_logs)
+export OUT=${OUT:-tiles_logs}
+mkdir -p $OUT
 for B in ${BATCHES:-16 8}; do
   for F in ${CFGS:-0 1 2 3 4 5 6 7}; do
-    OSR_CONV_FORCE_TILE=$F python3 bench.py --batch $B --steps 3 --warmup 2 --no-cpu-baseline --streams 1 --no-graph --layers > /dev/null 2> gpurun_out/tiles_b${B}_f${F}.log
+    OSR_CONV_FORCE_TILE=$F python3 bench.py --batch $B --steps 3 --warmup 2 --no-cpu-baseline --streams 1 --no-graph --full --layers > /dev/null 2> $OUT/tiles_b${B}_f${F}.log
   done
 done
 python3 - <<'PY'
@@ -15,7 +17,7 @@ for B in os.environ.get("BATCHES", "16 8").split():
     order = []
     for F in cfgs:
         idx = 0
-        for line in open(f"gpurun_out/tiles_b{B}_f{F}.log"):
+        for line in open(os.path.join(os.environ["OUT"], f"tiles_b{B}_f{F}.log")):
             m = re.match(r"\s+(\S+)\s+([\d.]+) us", line)
             if m:
                 key = (idx, m.group(1)); idx += 1

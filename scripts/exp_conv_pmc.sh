@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 i=0
 for c in "$@"; do
   i=$((i+1))
-  rocprofv3 --kernel-trace --pmc $c -d /tmp/cv_$i -o cv --output-format csv -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-train-step --no-pmc --streams 1 --no-graph > /tmp/cv_$i.log 2>&1
+  rocprofv3 --kernel-trace --pmc $c -d /tmp/cv_$i -o cv --output-format csv -- python3 $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-train-step --no-pmc --streams 1 --no-graph > /tmp/cv_$i.log 2>&1
   python3 - "$i" <<'PY'
 import csv, glob, sys, collections, re
 tag = sys.argv[1]

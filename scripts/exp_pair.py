@@ -8,4 +8,4 @@ import bench
 from openset_rcnn_amd.host import engine
 if os.environ.get("PAIR", "1") == "0":
     engine.OpensetRCNNEngine._shortcut_conv1_one_launch = lambda self, x, pre, stride: None
-sys.exit(bench.main(["--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--no-parity", "--no-pcie", "--no-pmc", "--no-train-step", "--layers"]))
+sys.exit(bench.main(["--full", "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--no-parity", "--no-pcie", "--no-pmc", "--no-train-step", "--layers"]))

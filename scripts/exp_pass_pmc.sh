@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 i=0
 for c in "$@"; do
   i=$((i+1))
-  rocprofv3 --kernel-trace --pmc $c -d /tmp/pp_$i -o pp --output-format csv -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-train-step --no-pmc --no-parity --no-pcie --streams 1 --no-graph > /tmp/pp_$i.log 2>&1
+  rocprofv3 --kernel-trace --pmc $c -d /tmp/pp_$i -o pp --output-format csv -- python3 $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-train-step --no-pmc --no-parity --no-pcie --streams 1 --no-graph > /tmp/pp_$i.log 2>&1
 done
 python3 - "$i" <<'PY'
 import csv, glob, sys, collections, re

@@ -78,7 +78,7 @@ def main():
     conv = [v for k, v in kernels.items() if k.startswith("conv_igemm") or k.startswith("bottleneck64") or k.startswith("splitk_reduce") or k.startswith("stem_pool")]
     print(json.dumps(dict(
         note="scripts/profile_round.sh: rocprofv3 --kernel-trace --stats, then --pmc FETCH_SIZE, --pmc WRITE_SIZE and --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_INSTS_VALU_MFMA_MOPS_F16 in separate passes of "
-             "`bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-train-step --streams 1 --no-graph` (`steps` passes of the path each: 2 warm-up + 5 timed + the attribution passes + the 4-image calibration pass); FETCH_SIZE doubled per "
+             "`bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-train-step --streams 1 --no-graph` (`steps` passes of the path each: 2 warm-up + 5 timed + the attribution passes + the 4-image calibration pass); FETCH_SIZE doubled per "
              "MI355X_MICROARCH.md; GB per 16-image step; mfma_util = MFMA busy cycles / (GRBM_GUI_ACTIVE / 8 x 1024 SIMDs), clock_GHz = GRBM_GUI_ACTIVE / 8 / dispatch time of the counter pass",
         conv_family=dict(ms_per_step=round(sum(v["ms_per_step"] for v in conv), 3),
                          fetch_GB_per_step_x2corrected=round(sum(v["fetch_GB_per_step_x2corrected"] for v in conv), 3),

@@ -74,6 +74,14 @@ def test_dump_outputs_checks_the_snapshot_and_writes_every_rank(tmp_path):
         bench.snapshot_to_host(snap, 102, 1, 1000)
 
 
+def test_per_kernel_printouts_need_the_full_run():
+    """--stages / --layers print what the attribution pass of --full measures: a plain run refuses them before touching the GPU."""
+    for flag in ("--stages", "--layers"):
+        with pytest.raises(SystemExit) as e:
+            bench.main([flag])
+        assert e.value.code == 2  # argparse's usage error, not the no-GPU exit
+
+
 def test_bf16_is_not_offered_as_a_benchmark_dtype():
     with pytest.raises(SystemExit):
         bench.main(["--dtype", "bf16"])
@@ -140,12 +148,12 @@ def test_committed_two_rank_rehearsal_line_has_the_config4_object():
 
 @pytest.mark.gpu
 def test_two_rank_bench_rehearsal_prints_exactly_one_json_line(tmp_path):
-    """`bench.py --gpus 2` with two gloo ranks sharing this GPU: stdout is ONE line (c10d's banners go to stderr), and that line carries
-    the headline, the multi-rank train step and the config-4 leg with the all-reduce measured alone."""
+    """`bench.py --gpus 2 --full` with two gloo ranks sharing this GPU: stdout is ONE line (c10d's banners go to stderr), and that line
+    carries the headline, the multi-rank train step and the config-4 leg with the all-reduce measured alone."""
     import json
     import subprocess
     env = dict(os.environ, OSR_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--train-steps", "2", "--passes-in-flight", "1",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--train-steps", "2", "--passes-in-flight", "1",
            "--no-cpu-baseline", "--no-pmc", "--dump-outputs", str(tmp_path / "dump")]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
@@ -161,3 +169,26 @@ def test_two_rank_bench_rehearsal_prints_exactly_one_json_line(tmp_path):
     if out:
         with open(out, "w") as fh:
             fh.write(lines[0] + "\n")
+
+
+@pytest.mark.gpu
+def test_two_rank_plain_bench_prints_the_headline_alone(tmp_path):
+    """`bench.py --gpus 2` without --full (two gloo ranks sharing this GPU): one JSON line with the headline and its config, none of
+    the objects --full measures after the timed steps, and --dump-outputs still writes both ranks' detections."""
+    import json
+    import subprocess
+    env = dict(os.environ, OSR_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--passes-in-flight", "1",
+           "--dump-outputs", str(tmp_path / "dump")]
+    r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, r.stdout[:2000]
+    line = json.loads(lines[0])
+    assert line["n_gpus"] == 2 and line["config"]["ranks"] == 2 and line["steps"] == 2 and line["warmup"] == 1
+    assert line["value"] > 0 and line["ms_per_step"] > 0 and line["unit"] == "images/sec" and line["higher_is_better"] is True
+    extras = {"roofline", "roofline_hbm", "single_pass", "pcie_inclusive", "parity", "full_lists", "train_step", "config4", "cpu_baseline"}
+    assert not extras & set(line), sorted(extras & set(line))
+    import numpy as np
+    counts = np.load(tmp_path / "dump" / "counts.npy")
+    assert counts.shape == (32,) and counts[:16].sum() == line["config"]["detections_last_step"]
