@@ -596,9 +596,10 @@ osr_status osr_softmax_ce_loss_fwd(const float* logits, int64_t m, int32_t num_k
 
 /* ---------------------------------------------------------------------------------------------------------
  * Backward of osr_conv2d_fwd (training step, backward half). `p` describes the FORWARD layer.
- *  - data gradient: no entry point of its own -- dx = osr_conv2d_fwd(dy, flipped/transposed weights) with stride 1,
- *    pad' = k-1-pad (host/weights.py pack_dgrad_weight); a stride-2 1x1 layer writes every second pixel of a zeroed dx
- *    through the output strides; res_mode 3 applies the ReLU mask of the layer below, res_mode 1 adds a second gradient.
+ *  - data gradient: dx = osr_conv2d_fwd(dy, flipped/transposed weights) with stride 1, pad' = k-1-pad
+ *    (host/weights.py pack_dgrad_weight); a stride-2 1x1 layer writes every second pixel of a zeroed dx through the output
+ *    strides; res_mode 3 applies the ReLU mask of the layer below, res_mode 1 adds a second gradient. A stride-2 3x3 layer
+ *    (pad 1) has an entry of its own, osr_conv2d_dgrad_s2.
  *  - weight gradient: dw[cout][kh][kw][cin] (fp32, the packed forward layout) = sum over output pixels of
  *    dy[n,oh,ow,co] * x[n, oh*sh-ph+kh, ow*sw-pw+kw, ci]; x, dy fp16/bf16 (dy dense (n,ho,wo,cout)), fp32 accumulate,
  *    split over the pixel axis with partials in the workspace and a fixed-order reduction (bitwise reproducible).
@@ -610,6 +611,18 @@ osr_status osr_conv2d_wgrad(const osr_conv_params* p, const void* x, const void*
                             void* workspace, int64_t workspace_bytes, void* stream);
 osr_status osr_bias_grad(const void* dy, int32_t dtype, int64_t m, int32_t cout, float* db, int32_t accumulate,
                          void* workspace, int64_t workspace_bytes, void* stream);
+
+/* Data gradient of a 3x3 convolution with stride 2 and pad 1 (the first block of res3-res5 with MODEL.RESNETS.STRIDE_IN_1X1
+ * False: torchvision's layout), `p` describing the FORWARD layer (n, hi, wi, cin of x; ho, wo, cout of dy; kh = kw = 3,
+ * stride 2, pad 1; in_stride_* / out_stride_* the dense strides of dx / dy):
+ *     dx[n,ih,iw,ci] = sum dy[n,oh,ow,co] * w[co,kh,kw,ci] over 2*oh-1+kh = ih, 2*ow-1+kw = iw,
+ * computed per pixel-parity phase (1, 1x2, 2x1 and 2x2 taps) in one launch. w_dgrad = pack_dgrad_weight(w), (cin,3,3,cout).
+ * add (nullable, dx's shape, in_dtype) is summed in; mask (nullable, dx's shape, in_dtype) is a ReLU mask applied after the
+ * sum: dx = mask > 0 ? conv + add : 0. Every pixel of dx is written once (no zero fill needed). dy, w_dgrad, mask, add f16 /
+ * bf16 (in_dtype), dx in_dtype or f32 (out_dtype); cin % 16 == 0, cout % 64 == 0; fp32 accumulation, fixed order
+ * (bitwise reproducible). */
+osr_status osr_conv2d_dgrad_s2(const osr_conv_params* p, const void* dy, const void* w_dgrad, const void* mask,
+                               const void* add, void* dx, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * Training step, backward half: losses and per-row stages. Every gradient is d(sum of weighted losses)/d(tensor)

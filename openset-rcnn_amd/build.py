@@ -35,6 +35,7 @@ SOURCES = {
     "osr_multi_tensor.hip": [],  # (same contraction setting as osr_train_bwd.hip: the multi-tensor SGD must round like osr_sgd_step)
     "osr_solver.hip": [],
     "osr_conv_bwd.hip": [],
+    "osr_conv_dgrad_s2.hip": [],
     "osr_stem_bwd.hip": [],
     "osr_train_bwd.hip": [],
 }

@@ -166,6 +166,7 @@ PROTOTYPES = {
     # training step, backward half
     "osr_conv2d_wgrad_workspace_bytes": (I64, [P]),
     "osr_conv2d_wgrad": (I32, [P, P, P, P, I32, P, I64, P]),
+    "osr_conv2d_dgrad_s2": (I32, [P, P, P, P, P, P, P]),
     "osr_bias_grad": (I32, [P, I32, I64, I32, P, I32, P, I64, P]),
     "osr_rpn_losses_bwd": (I32, [P, P, I32, P, P, P, P, P, P, F32, F32, I32, F32, P, P]),
     "osr_rpn_losses_bwd_ex": (I32, [P, P, I32, P, P, P, P, P, P, F32, F32, I32, F32, P, P, P]),

@@ -6,10 +6,21 @@
     naming (conv1_w, res_conv1_bn_s, res2_0_branch2a_w, res2_0_branch2a_bn_b, ..., fc1000_w), BN already reduced to a
     scale/shift pair. [d2] loads it through name heuristics; the mapping is closed-form for R-50 and written out below.
 
+and the two forms of torchvision's ImageNet ResNet-50 (stride in the 3x3: build the model with MODEL.RESNETS.STRIDE_IN_1X1
+False) --
+
+  * the `.pkl` of detectron2's tools/convert-torchvision-to-d2.py: {"model": {name: ndarray}, "__author__": ...,
+    "matching_heuristics": True} with backbone names lacking the `backbone.bottom_up.` prefix (stem.conv1.weight,
+    res2.0.conv1.norm.running_var, res2.0.shortcut.weight, stem.fc.weight, ...);
+  * the raw `resnet50().state_dict()` saved as `.pth` (conv1 / bn1 / layer{1..4}.{b}.conv{1,2,3} / bn{1,2,3} / downsample.{0,1} / fc).
+
+Both carry real BatchNorm statistics (not pre-reduced like the MSRA blobs); `weights.fold_frozen_bn` folds them.
+
 Nothing here reads from the network: paths are local files. The result is a flat {d2 name: fp32 tensor} dict, ready for
 `model.load_state_dict` (host/modeling.py) or, after `weights.fold_frozen_bn`, for `OpensetRCNNEngine`."""
 from __future__ import annotations
 
+import logging
 import pickle
 import re
 from typing import Dict, Iterable, List, Tuple
@@ -55,34 +66,112 @@ def convert_msra_state(blobs: Dict[str, np.ndarray]) -> Dict[str, torch.Tensor]:
     return out
 
 
-def load_checkpoint(path: str) -> Dict[str, torch.Tensor]:
-    """Read a `.pth` or `.pkl` checkpoint into a flat {d2 name: tensor} dict (fp32, CPU)."""
+_TV_LEAF = {"weight", "bias", "running_mean", "running_var"}
+_BOTTOM_UP = "backbone.bottom_up."
+log = logging.getLogger(__name__)
+
+
+class CheckpointState(dict):
+    """load_checkpoint's result: {d2 name: tensor}, and `origin`, the format it came from ("d2", "msra" or "torchvision": a
+    torchvision ResNet, stride in the 3x3)."""
+
+    def __init__(self, items, origin: str):
+        super().__init__(items)
+        self.origin = origin
+
+
+def convert_d2_backbone_name(name: str) -> str:
+    """A backbone name of detectron2's converted torchvision `.pkl` (no `backbone.bottom_up.` prefix) -> this model's name
+    ("" for the classifier and the BatchNorm step counters, which the detector does not use)."""
+    if name.startswith("stem.fc.") or name.endswith(".num_batches_tracked"):
+        return ""
+    if re.fullmatch(r"stem\.conv1\.(weight|norm\.(weight|bias|running_mean|running_var))", name) or \
+            re.fullmatch(r"res[2-5]\.\d+\.(shortcut|conv1|conv2|conv3)\.(weight|norm\.(weight|bias|running_mean|running_var))", name):
+        return _BOTTOM_UP + name
+    raise KeyError(f"unrecognised detectron2 backbone name '{name}'")
+
+
+def convert_torchvision_name(name: str) -> str:
+    """One torchvision resnet50 state-dict name -> this model's name ("" for fc.* and num_batches_tracked)."""
+    if name.startswith("fc.") or name.endswith(".num_batches_tracked"):
+        return ""
+    if name == "conv1.weight":
+        return _BOTTOM_UP + "stem.conv1.weight"
+    m = re.fullmatch(r"bn1\.(\w+)", name)
+    if m and m.group(1) in _TV_LEAF:
+        return _BOTTOM_UP + "stem.conv1.norm." + m.group(1)
+    m = re.fullmatch(r"layer([1-4])\.(\d+)\.(conv[123]\.weight|bn[123]\.\w+|downsample\.[01]\.\w+)", name)
+    if m:
+        layer, blk, rest = m.groups()
+        pre = f"{_BOTTOM_UP}res{int(layer) + 1}.{blk}."
+        mm = re.fullmatch(r"conv([123])\.weight", rest)
+        if mm:
+            return pre + f"conv{mm.group(1)}.weight"
+        mm = re.fullmatch(r"bn([123])\.(\w+)", rest)
+        if mm and mm.group(2) in _TV_LEAF:
+            return pre + f"conv{mm.group(1)}.norm.{mm.group(2)}"
+        if rest == "downsample.0.weight":
+            return pre + "shortcut.weight"
+        mm = re.fullmatch(r"downsample\.1\.(\w+)", rest)
+        if mm and mm.group(1) in _TV_LEAF:
+            return pre + "shortcut.norm." + mm.group(1)
+    raise KeyError(f"unrecognised torchvision ResNet name '{name}'")
+
+
+def _is_d2_backbone(names) -> bool:
+    return "stem.conv1.weight" in names and any(re.match(r"res[2-5]\.\d+\.", k) for k in names)
+
+
+def _is_torchvision(names) -> bool:
+    return "conv1.weight" in names and "bn1.running_var" in names and any(k.startswith("layer1.0.") for k in names)
+
+
+def _converted(state: Dict[str, object], convert) -> Dict[str, torch.Tensor]:
+    out = {}
+    for k, v in state.items():
+        name = convert(k)
+        if name:
+            out[name] = (v if torch.is_tensor(v) else torch.as_tensor(np.asarray(v))).float()
+    return out
+
+
+def load_checkpoint(path: str) -> CheckpointState:
+    """Read a `.pth` or `.pkl` checkpoint into a flat {d2 name: tensor} dict (fp32, CPU). The format is told by its names:
+    a torchvision ResNet (raw or converted by detectron2's tools) is mapped to this model's names."""
     if path.endswith(".pkl"):
         with open(path, "rb") as f:
             data = pickle.load(f, encoding="latin1")
         if isinstance(data, dict) and "model" in data and "__author__" in data:  # already converted by detectron2's tools
             model = data["model"]
             if not data.get("matching_heuristics", False):
-                return {k: torch.as_tensor(np.asarray(v)).float() for k, v in model.items()}
+                return CheckpointState({k: torch.as_tensor(np.asarray(v)).float() for k, v in model.items()}, "d2")
+            if _is_d2_backbone(model):  # tools/convert-torchvision-to-d2.py
+                return CheckpointState(_converted(model, convert_d2_backbone_name), "torchvision")
             data = model
         if isinstance(data, dict) and "blobs" in data:
             data = data["blobs"]
-        return convert_msra_state({k: np.asarray(v) for k, v in data.items()})
+        return CheckpointState(convert_msra_state({k: np.asarray(v) for k, v in data.items()}), "msra")
     data = torch.load(path, map_location="cpu", weights_only=False)
     state = data["model"] if isinstance(data, dict) and "model" in data else data
+    if _is_torchvision(state):  # torch.save(torchvision.models.resnet50(...).state_dict())
+        return CheckpointState(_converted(state, convert_torchvision_name), "torchvision")
     out = {}
     for k, v in state.items():
         k = k[len("module."):] if k.startswith("module.") else k  # DDP-wrapped saves (train.py:201-205)
         out[k] = torch.as_tensor(np.asarray(v)) if not torch.is_tensor(v) else v
         if out[k].is_floating_point():
             out[k] = out[k].float()
-    return out
+    return CheckpointState(out, "d2")
 
 
 def load_into(model: torch.nn.Module, state: Dict[str, torch.Tensor], strict: bool = False) -> Tuple[List[str], List[str]]:
     """[d2] Checkpointer semantics: load matching names, report (missing, unexpected); shape mismatches raise. A backbone-only
     checkpoint (MSRA R-50) leaves FPN / RPN / RoI-head parameters at their initial values, as in the reference's training
-    start."""
+    start. A torchvision checkpoint loaded into a model built with MODEL.RESNETS.STRIDE_IN_1X1 True (the MSRA layout) is
+    loaded, with a warning: its weights were trained with the stride in the 3x3."""
+    if getattr(state, "origin", None) == "torchvision" and getattr(model, "_eng_cfg", {}).get("stride_in_1x1", True):
+        log.warning("loading a torchvision ResNet checkpoint into a model with MODEL.RESNETS.STRIDE_IN_1X1 True: torchvision puts "
+                    "the stride in the 3x3 convolution; set STRIDE_IN_1X1 False (detectron2's convert-torchvision-to-d2 recipe)")
     own = model.state_dict()
     for k, v in state.items():
         if k in own and tuple(own[k].shape) != tuple(v.shape):

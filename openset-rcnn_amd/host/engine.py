@@ -34,6 +34,8 @@ DEFAULT_CFG = dict(
     rpn_iou_thresholds=(0.3, 0.7), rpn_iou_thresholds_objectness=(0.1, 0.3), rpn_loc_weight=0.5, rpn_ctr_weight=0.5,
     roi_batch_size=512, roi_positive_fraction=0.25, roi_iou_threshold=0.5, box_reg_weight=0.5, iou_reg_weight=0.5,
     pln_alpha=0.1, pln_beta=0.9, pln_iou_threshold=0.5, pln_loss_weight=0.5, cls_loss_weight=0.9,
+    # MODEL.RESNETS.STRIDE_IN_1X1: True (MSRA R-50.pkl) puts a stage's stride in conv1 of its first block, False (torchvision) in conv2
+    stride_in_1x1=True,
 )
 
 
@@ -210,17 +212,19 @@ class OpensetRCNNEngine:
                     nbytes = x.numel() * x.element_size() + y.numel() * y.element_size() + sum(w[f"{pre}.{c}.w"].numel() for c in names) * x.element_size()
                     self.profile.append((pre + " (fused block)", flops, e0, e1, nbytes, flops))
                 return y
-        pair = self._shortcut_conv1_one_launch(x, pre, stride) if first and self.fuse_levels else None
+        s1, s2 = (stride, 1) if self.cfg["stride_in_1x1"] else (1, stride)  # the block's stride: in conv1 (MSRA) or in conv2 (torchvision)
+        # (the shortcut + conv1 launch needs both 1x1 layers at one stride)
+        pair = self._shortcut_conv1_one_launch(x, pre, stride) if first and self.fuse_levels and s1 == stride else None
         if pair is not None:
             sc, o = pair
         else:
             sc = self._conv(x, pre + ".shortcut", stride) if first else x
-            o = self._conv(x, pre + ".conv1", stride, relu=True)
+            o = self._conv(x, pre + ".conv1", s1, relu=True)
         if self.chain_res3 and w[pre + ".conv2.w"].shape[0] == 128 and w[pre + ".conv3.w"].shape[0] == 512:
             if self.profile is not None:
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record()
-            y = ops.conv2d_chain(o, w[pre + ".conv2.w"], w[pre + ".conv2.b"], w[pre + ".conv3.w"], w[pre + ".conv3.b"], sc, 1, 1)
+            y = ops.conv2d_chain(o, w[pre + ".conv2.w"], w[pre + ".conv2.b"], w[pre + ".conv3.w"], w[pre + ".conv3.b"], sc, s2, 1)
             if y is not None:
                 if self.profile is not None:
                     e1.record()
@@ -229,7 +233,7 @@ class OpensetRCNNEngine:
                     nbytes = (o.numel() + sc.numel() + y.numel() + w[pre + ".conv2.w"].numel() + w[pre + ".conv3.w"].numel()) * es
                     self.profile.append((pre + ".conv2+conv3 (chained)", flops, e0, e1, nbytes, flops))
                 return y
-        o = self._conv(o, pre + ".conv2", 1, 1, relu=True)
+        o = self._conv(o, pre + ".conv2", s2, 1, relu=True)
         return self._conv(o, pre + ".conv3", relu=True, residual=sc, res_mode=1)
 
     def _linear(self, x, w, b, relu, out_dtype=None, name="fc", row_seg=None, real_rows=None):
@@ -281,7 +285,7 @@ class OpensetRCNNEngine:
         for si, nb in enumerate(R50_BLOCKS):
             for b in range(nb):
                 pre = f"backbone.bottom_up.res{si + 2}.{b}"
-                stride = 2 if (b == 0 and si > 0) else 1  # MSRA: stride in the first 1x1
+                stride = 2 if (b == 0 and si > 0) else 1  # in conv1 or conv2 of the block: cfg stride_in_1x1
                 x = self._bottleneck(x, pre, b == 0, stride)
             feats[f"res{si + 2}"] = x
         out = {}
@@ -577,7 +581,8 @@ class OpensetRCNNEngine:
     # ---- training step, forward half ----------------------------------------------------------------------
     @staticmethod
     def pyramid_shapes(hp: int, wp: int):
-        """(h, w) of p2..p6 for a padded hp x wp batch: stem 7x7/2 pad 3, max pool 3x3/2 pad 1, stride-2 1x1 convs, p6 = p5 subsampled."""
+        """(h, w) of p2..p6 for a padded hp x wp batch: stem 7x7/2 pad 3, max pool 3x3/2 pad 1, one stride-2 layer
+        per stage res3-res5 (a 1x1 with pad 0 or a 3x3 with pad 1: both give (v - 1) // 2 + 1), p6 = p5 subsampled."""
         down = lambda v: (v - 1) // 2 + 1  # noqa: E731
         h, w = (hp + 6 - 7) // 2 + 1, (wp + 6 - 7) // 2 + 1
         shapes = []

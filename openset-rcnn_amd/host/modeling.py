@@ -214,8 +214,9 @@ class ResNetFPN(_EngineOwner):
     def __init__(self, cfg: CfgNode):
         super().__init__()
         assert cfg.MODEL.RESNETS.DEPTH == 50, "only R-50 is on the hot path (VOC-COCO / GraspNet yaml: DEPTH 50)"
-        assert cfg.MODEL.RESNETS.STRIDE_IN_1X1 and cfg.MODEL.RESNETS.NORM == "FrozenBN"
+        assert cfg.MODEL.RESNETS.NORM == "FrozenBN", "only FrozenBN is on the hot path"
         self.bottom_up = _BottomUp()
+        self._eng_cfg = {"stride_in_1x1": bool(cfg.MODEL.RESNETS.STRIDE_IN_1X1)}  # (a stand-alone backbone's engine)
         for lvl, c in zip((2, 3, 4, 5), (256, 512, 1024, 2048)):
             setattr(self, f"fpn_lateral{lvl}", _ConvBias(c, 256, 1, 0.7))
             setattr(self, f"fpn_output{lvl}", _ConvBias(256, 256, 3, 0.7))
@@ -511,6 +512,7 @@ def engine_cfg_from(cfg: CfgNode) -> dict:
         obj_score_thresh=rh.OBJ_SCORE_THRESH_TEST, nms_thresh_test=rh.NMS_THRESH_TEST, detections_per_image=cfg.TEST.DETECTIONS_PER_IMAGE,
         known_score_thresh=rh.KNOWN_SCORE_THRESH, known_nms_thresh=rh.KNOWN_NMS_THRESH, known_topk=rh.KNOWN_TOPK,
         unknown_score_thresh=rh.UNKNOWN_SCORE_THRESH, unknown_nms_thresh=rh.UNKNOWN_NMS_THRESH, unknown_topk=rh.UNKNOWN_TOPK,
+        stride_in_1x1=bool(cfg.MODEL.RESNETS.STRIDE_IN_1X1),
         num_classes=rh.NUM_CLASSES, num_known=rh.NUM_KNOWN_CLASSES, reps_per_class=cfg.MODEL.PLN.REPS_PER_CLASS, pln_distance=cfg.MODEL.PLN.DISTANCE_TYPE,
         # the reference hard-codes the unknown id: 80 with --opendet-benchmark, else 1000
         unknown_id=80 if cfg.OPENDET_BENCHMARK else 1000, unk_thr=cfg.MODEL.PLN.UNK_THR,

@@ -1012,7 +1012,9 @@ def conv2d_dgrad(dy: torch.Tensor, w_dgrad: torch.Tensor, x_hw: Tuple[int, int],
     mask: forward activation at dx's positions (n,hi,wi,cin) -> dx is zeroed where mask <= 0 (the ReLU below);
     add: a second gradient of dx's shape summed in (residual / shortcut branch). At most one of the two (they share the
     epilogue's auxiliary operand); post_mask: a forward activation of dx's shape applied as a ReLU mask AFTER the sum (the
-    join of a residual block: osr_conv2d_fwd_masked); stride 2 is supported for 1x1 layers (every second pixel of a zeroed dx).
+    join of a residual block: osr_conv2d_fwd_masked); stride 2 is supported for 1x1 layers (every second pixel of a zeroed dx)
+    and for 3x3 layers with pad 1 (osr_conv2d_dgrad_s2: every pixel written; mask / post_mask and add may then be combined,
+    the mask applying after the sum).
     strided_only (stride > 1): the caller reads dx only at the pixels the stride visits (as the `add` of a second strided launch
     does), so the other pixels are left unwritten instead of zero-filled."""
     lib = _lib.load()
@@ -1022,6 +1024,8 @@ def conv2d_dgrad(dy: torch.Tensor, w_dgrad: torch.Tensor, x_hw: Tuple[int, int],
     hi, wi = x_hw
     if cout2 != cout:
         raise OsrError(f"w_dgrad cout {cout2} != dy channels {cout}")
+    if stride == 2 and kh == 3 and kw == 3 and pad == 1:
+        return _conv2d_dgrad_s2(dy, w_dgrad, hi, wi, mask, add, out_dtype, post_mask)
     if mask is not None and add is not None:
         raise OsrError("conv2d_dgrad takes a mask or an addend, not both")
     aux, mode = (mask, 3) if mask is not None else ((add, 1) if add is not None else (None, 0))
@@ -1059,6 +1063,31 @@ def conv2d_dgrad(dy: torch.Tensor, w_dgrad: torch.Tensor, x_hw: Tuple[int, int],
     check(lib.osr_conv2d_fwd(C.byref(p), _p(dy), _p(w_dgrad), _p(zero_bias), _p(aux), _p(dx), _stream()), "osr_conv2d_fwd(dgrad)")
     if post_mask is not None:
         relu_mask_(dx, post_mask)
+    return dx
+
+
+def _conv2d_dgrad_s2(dy: torch.Tensor, w_dgrad: torch.Tensor, hi: int, wi: int, mask: Optional[torch.Tensor], add: Optional[torch.Tensor],
+                     out_dtype: Optional[torch.dtype], post_mask: Optional[torch.Tensor]) -> torch.Tensor:
+    """conv2d_dgrad of a 3x3 / stride 2 / pad 1 layer: osr_conv2d_dgrad_s2, dx = mask > 0 ? conv + add : 0 in one launch."""
+    lib = _lib.load()
+    n, ho, wo, cout = dy.shape
+    cin = w_dgrad.shape[0]
+    if (hi - 1) // 2 + 1 != ho or (wi - 1) // 2 + 1 != wo:
+        raise OsrError("x_hw inconsistent with dy and the stride")
+    if mask is not None and post_mask is not None:
+        raise OsrError("conv2d_dgrad: mask and post_mask are the same thing; pass one")
+    m = mask if mask is not None else post_mask
+    for t, name in ((m, "mask"), (add, "add")):
+        if t is not None:
+            _need(t, dy.dtype, name)
+            if tuple(t.shape) != (n, hi, wi, cin):
+                raise OsrError(f"{name} shape {tuple(t.shape)} != {(n, hi, wi, cin)}")
+    out_dtype = out_dtype or dy.dtype
+    if FLOP_COUNT is not None:
+        FLOP_COUNT["conv"] += 2.0 * n * hi * wi * cin * cout * 9 / 4
+    dx = torch.empty((n, hi, wi, cin), dtype=out_dtype, device=dy.device)
+    p = _conv_params(n, hi, wi, cin, ho, wo, cout, 3, 3, 2, 1, dy.dtype, out_dtype)
+    check(lib.osr_conv2d_dgrad_s2(C.byref(p), _p(dy), _p(w_dgrad), _p(m), _p(add), _p(dx), _stream()), "osr_conv2d_dgrad_s2")
     return dx
 
 

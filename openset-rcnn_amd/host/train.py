@@ -410,21 +410,23 @@ class OpensetRCNNTrainer:
                 stride = 2 if (b == 0 and si > 0) else 1
                 if si + 2 <= self.freeze_at:  # frozen stage: part of the prefix above (nothing of it is needed by the backward)
                     break
-                pair = e._shortcut_conv1_one_launch(x, pre, stride) if b == 0 and e.fuse_levels else None  # (one launch for the two readers of x)
+                s1, s2 = (stride, 1) if e.cfg["stride_in_1x1"] else (1, stride)  # the stride in conv1 (MSRA) or conv2 (torchvision): o1 at x's size
+                # (one launch for the two readers of x, when both 1x1 layers run at one stride)
+                pair = e._shortcut_conv1_one_launch(x, pre, stride) if b == 0 and e.fuse_levels and s1 == stride else None
                 if pair is not None:
                     sc, o1 = pair
                 else:
                     sc = e._conv(x, pre + ".shortcut", stride) if b == 0 else x
-                    o1 = e._conv(x, pre + ".conv1", stride, relu=True)
+                    o1 = e._conv(x, pre + ".conv1", s1, relu=True)
                 # res3: conv2 -> conv3 + shortcut as ONE launch that also stores conv2's output for the backward (bit-identical to the two)
-                ch = ops.conv2d_chain(o1, e.w[pre + ".conv2.w"], e.w[pre + ".conv2.b"], e.w[pre + ".conv3.w"], e.w[pre + ".conv3.b"], sc, 1, 1,
+                ch = ops.conv2d_chain(o1, e.w[pre + ".conv2.w"], e.w[pre + ".conv2.b"], e.w[pre + ".conv3.w"], e.w[pre + ".conv3.b"], sc, s2, 1,
                                       keep_mid=True) if (self.chain_forward and e.w[pre + ".conv2.w"].shape[0] == 128 and e.w[pre + ".conv3.w"].shape[0] == 512) else None
                 if ch is not None:
                     y, o2 = ch
                 else:
-                    o2 = e._conv(o1, pre + ".conv2", 1, 1, relu=True)
+                    o2 = e._conv(o1, pre + ".conv2", s2, 1, relu=True)
                     y = e._conv(o2, pre + ".conv3", relu=True, residual=sc, res_mode=1)
-                blocks.append(dict(pre=pre, x=x, o1=o1, o2=o2, y=y, stride=stride, first=b == 0, stage=si + 2))
+                blocks.append(dict(pre=pre, x=x, o1=o1, o2=o2, y=y, stride=stride, s1=s1, s2=s2, first=b == 0, stage=si + 2))
                 x = y
             feats[f"res{si + 2}"] = frozen_feats[f"res{si + 2}"] if si + 2 <= self.freeze_at else x
         s["blocks"], s["res"] = blocks, feats
@@ -746,6 +748,7 @@ class OpensetRCNNTrainer:
         for bi in range(len(s["blocks"]) - 1, -1, -1):
             blk = s["blocks"][bi]
             pre, x, o1, o2, y, stride = blk["pre"], blk["x"], blk["o1"], blk["o2"], blk["y"], blk["stride"]
+            s1, s2 = blk["s1"], blk["s2"]
             hy, wy = y.shape[1], y.shape[2]
             last_of_stage = blk is s["blocks"][-1] or pre.endswith(f".{R50_BLOCKS[blk['stage'] - 2] - 1}")
             if last_of_stage:  # the stage output also feeds its FPN lateral
@@ -756,10 +759,11 @@ class OpensetRCNNTrainer:
             on_main = pre in self.wgrad_on_main
             d_o2 = ops.conv2d_dgrad(G, self.wd[pre + ".conv3"], (hy, wy), 1, 0, mask=o2)
             self._wg(lambda o2=o2, G=G, pre=pre: ops.conv2d_wgrad(o2, G, 1, 1, dw=g[pre + ".conv3.w"]), G, main=on_main)
-            d_o1 = ops.conv2d_dgrad(d_o2, self.wd[pre + ".conv2"], (o1.shape[1], o1.shape[2]), 1, 1, mask=o1)
-            self._wg(lambda o1=o1, d_o2=d_o2, x=x, d_o1=d_o1, pre=pre, stride=stride: (
-                ops.conv2d_wgrad(o1, d_o2, 3, 3, 1, 1, dw=g[pre + ".conv2.w"]),
-                ops.conv2d_wgrad(x, d_o1, 1, 1, stride, 0, dw=g[pre + ".conv1.w"])), d_o2, d_o1, main=on_main)
+            # (s2 == 2: osr_conv2d_dgrad_s2, the stride-2 3x3 layer's own data gradient)
+            d_o1 = ops.conv2d_dgrad(d_o2, self.wd[pre + ".conv2"], (o1.shape[1], o1.shape[2]), s2, 1, mask=o1)
+            self._wg(lambda o1=o1, d_o2=d_o2, x=x, d_o1=d_o1, pre=pre, s1=s1, s2=s2: (
+                ops.conv2d_wgrad(o1, d_o2, 3, 3, s2, 1, dw=g[pre + ".conv2.w"]),
+                ops.conv2d_wgrad(x, d_o1, 1, 1, s1, 0, dw=g[pre + ".conv1.w"])), d_o2, d_o1, main=on_main)
             if blk["first"]:
                 self._wg(lambda x=x, G=G, pre=pre, stride=stride: ops.conv2d_wgrad(x, G, 1, 1, stride, 0, dw=g[pre + ".shortcut.w"]), G, main=on_main)
                 self._done(pre + ".shortcut.w")
@@ -771,7 +775,12 @@ class OpensetRCNNTrainer:
             # is the last of its stage, whose G is completed (and masked) by the lateral's launch at the top of the next turn
             below_last = bi > 0 and s["blocks"][bi - 1]["pre"].endswith(f".{R50_BLOCKS[s['blocks'][bi - 1]['stage'] - 2] - 1}")
             pm = None if below_last else x
-            if blk["first"]:
+            if blk["first"] and s1 != stride:
+                # stride in conv2: conv1's share is dense, the shortcut's covers the even pixels only. The strided launch goes first
+                # (into a zeroed dx), conv1's dense launch adds it and applies the mask: every pixel is summed and masked once
+                dsc = ops.conv2d_dgrad(G, self.wd[pre + ".shortcut"], (hx, wx), stride, 0)
+                G = ops.conv2d_dgrad(d_o1, self.wd[pre + ".conv1"], (hx, wx), 1, 0, add=dsc, post_mask=pm)
+            elif blk["first"]:
                 # (conv1's share is read back by the shortcut's launch at the strided pixels only: no zero fill of the others)
                 dx = ops.conv2d_dgrad(d_o1, self.wd[pre + ".conv1"], (hx, wx), stride, 0, strided_only=stride > 1)
                 G = ops.conv2d_dgrad(G, self.wd[pre + ".shortcut"], (hx, wx), stride, 0, add=dx, post_mask=pm)
