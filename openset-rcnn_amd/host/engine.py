@@ -19,6 +19,12 @@ import torch
 from . import ops
 from .weights import R50_BLOCKS, pack_conv_weight, pack_fc1_weight, pack_stem_weight
 
+BOTTOM_UP = "backbone.bottom_up"
+STEM = BOTTOM_UP + ".stem.conv1"
+RPN_CONV = "proposal_generator.rpn_head.conv"
+FPN_LEVELS = (2, 3, 4, 5)                    # resN -> fpn_lateralN / fpn_outputN -> pN
+PYRAMID = ("p2", "p3", "p4", "p5", "p6")     # what the RPN head reads; RoIAlign reads PYRAMID[:4]
+
 DEFAULT_CFG = dict(
     pixel_mean=(103.53, 116.28, 123.675), pixel_std=(1.0, 1.0, 1.0), size_divisibility=32,
     fpn_strides=(4, 8, 16, 32, 64), anchor_sizes=(32, 64, 128, 256, 512),
@@ -95,7 +101,7 @@ class OpensetRCNNEngine:
         if "backbone" in self.fp32_points:
             self._bb32 = OpensetRCNNEngine({k: v for k, v in params.items() if k.startswith("backbone.")}, cfg, torch.float32, device)
         c = self.cfg
-        self.has_backbone = "backbone.bottom_up.stem.conv1.weight" in params
+        self.has_backbone = STEM + ".weight" in params
         self.class_map = None if class_map is None else class_map.to(torch.int64).to(dev)
         # training-side id_map of the GraspNet configuration (prototype_learning_network.py:80-95, softmax_classifier.py:214-229):
         # dataset class id -> index in the sorted known list, background (NUM_CLASSES) -> NUM_KNOWN, anything else -> -1
@@ -134,7 +140,7 @@ class OpensetRCNNEngine:
             if not k.endswith(".weight") or v.dim() != 4 or (k.startswith("proposal_generator.rpn_head.") and not k.startswith("proposal_generator.rpn_head.conv.")):
                 continue
             pre = k[: -len(".weight")]
-            if pre == "backbone.bottom_up.stem.conv1":
+            if pre == STEM:
                 w[pre + ".w"] = pack_stem_weight(v, dtype).to(dev)
             else:
                 w[pre + ".w"] = pack_conv_weight(v, dtype).to(dev)
@@ -180,135 +186,138 @@ class OpensetRCNNEngine:
     # ---- backbone -------------------------------------------------------------------------------------------
     def _conv(self, x, name, stride=1, pad=0, relu=False, residual=None, res_mode=0, out=None, out_dtype=None):
         w = self.w[name + ".w"]
-        if self.profile is None:
-            return ops.conv2d(x, w, self.w[name + ".b"], stride, pad, relu, residual, res_mode, out_dtype, out)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        y = ops.conv2d(x, w, self.w[name + ".b"], stride, pad, relu, residual, res_mode, out_dtype, out)
-        e1.record()
-        rows = y.numel() // w.shape[0]
-        nbytes = x.numel() * x.element_size() + w.numel() * w.element_size() + y.numel() * y.element_size() + \
-            (residual.numel() * residual.element_size() if residual is not None else 0)
-        flops = 2.0 * rows * w.shape[0] * w.shape[1] * w.shape[2] * w.shape[3]
-        self.profile.append((name, flops, e0, e1, nbytes, flops))
-        return y
 
-    def _bottleneck(self, x, pre: str, first: bool, stride: int = 1):
+        def cost(y):
+            rows = y.numel() // w.shape[0]
+            nbytes = x.numel() * x.element_size() + w.numel() * w.element_size() + y.numel() * y.element_size() + \
+                (residual.numel() * residual.element_size() if residual is not None else 0)
+            flops = 2.0 * rows * w.shape[0] * w.shape[1] * w.shape[2] * w.shape[3]
+            return flops, nbytes, flops
+        return self._timed(name, lambda: ops.conv2d(x, w, self.w[name + ".b"], stride, pad, relu, residual, res_mode, out_dtype, out), cost)
+
+    def _bottleneck(self, x, pre: str, first: bool, stride: int = 1, save: Optional[list] = None, chain: Optional[bool] = None):
         """One [d2] BottleneckBlock (conv1 1x1 -> conv2 3x3 -> conv3 1x1 + shortcut, ReLU after each). res2's blocks run as one
-        fused launch when the engine allows it (the intermediates never reach HBM); everything else as separate launches."""
+        fused launch when the engine allows it (the intermediates never reach HBM); everything else as separate launches.
+        save (a list: the training forward): the block keeps what its backward reads -- no fused res2 launch (its intermediates
+        never reach memory), the chained launch also stores conv2's output -- and appends the record of it (_stages adds the
+        block's place in its stage). chain: the caller's switch for the chained launch in place of chain_res3."""
         w = self.w
-        if self.fuse_res2 and stride == 1 and w[pre + ".conv1.w"].shape[0] == 64:
-            if self.profile is not None:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-            y = ops.bottleneck(x, w[pre + ".conv1.w"], w[pre + ".conv1.b"], w[pre + ".conv2.w"], w[pre + ".conv2.b"], w[pre + ".conv3.w"],
-                               w[pre + ".conv3.b"], w[pre + ".shortcut.w"] if first else None, w[pre + ".shortcut.b"] if first else None)
+        if save is None and self.fuse_res2 and stride == 1 and w[pre + ".conv1.w"].shape[0] == 64:
+            names = ["conv1", "conv2", "conv3"] + (["shortcut"] if first else [])
+
+            def cost_fused(y):
+                px = y.numel() // y.shape[-1]
+                flops = sum(2.0 * px * w[f"{pre}.{c}.w"].numel() for c in names)
+                nbytes = x.numel() * x.element_size() + y.numel() * y.element_size() + sum(w[f"{pre}.{c}.w"].numel() for c in names) * x.element_size()
+                return flops, nbytes, flops
+            y = self._timed(pre + " (fused block)", lambda: ops.bottleneck(
+                x, w[pre + ".conv1.w"], w[pre + ".conv1.b"], w[pre + ".conv2.w"], w[pre + ".conv2.b"], w[pre + ".conv3.w"], w[pre + ".conv3.b"],
+                w[pre + ".shortcut.w"] if first else None, w[pre + ".shortcut.b"] if first else None), cost_fused)
             if y is not None:
-                if self.profile is not None:
-                    e1.record()
-                    names = ["conv1", "conv2", "conv3"] + (["shortcut"] if first else [])
-                    px = y.numel() // y.shape[-1]
-                    flops = sum(2.0 * px * w[f"{pre}.{c}.w"].numel() for c in names)
-                    nbytes = x.numel() * x.element_size() + y.numel() * y.element_size() + sum(w[f"{pre}.{c}.w"].numel() for c in names) * x.element_size()
-                    self.profile.append((pre + " (fused block)", flops, e0, e1, nbytes, flops))
                 return y
-        s1, s2 = (stride, 1) if self.cfg["stride_in_1x1"] else (1, stride)  # the block's stride: in conv1 (MSRA) or in conv2 (torchvision)
+        s1, s2 = (stride, 1) if self.cfg["stride_in_1x1"] else (1, stride)  # the block's stride: in conv1 (MSRA) or in conv2 (torchvision): o1 at x's size
         # (the shortcut + conv1 launch needs both 1x1 layers at one stride)
         pair = self._shortcut_conv1_one_launch(x, pre, stride) if first and self.fuse_levels and s1 == stride else None
         if pair is not None:
-            sc, o = pair
+            sc, o1 = pair
         else:
             sc = self._conv(x, pre + ".shortcut", stride) if first else x
-            o = self._conv(x, pre + ".conv1", s1, relu=True)
-        if self.chain_res3 and w[pre + ".conv2.w"].shape[0] == 128 and w[pre + ".conv3.w"].shape[0] == 512:
-            if self.profile is not None:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-            y = ops.conv2d_chain(o, w[pre + ".conv2.w"], w[pre + ".conv2.b"], w[pre + ".conv3.w"], w[pre + ".conv3.b"], sc, s2, 1)
-            if y is not None:
-                if self.profile is not None:
-                    e1.record()
-                    px, es = y.numel() // y.shape[-1], y.element_size()
-                    flops = 2.0 * px * (w[pre + ".conv2.w"].numel() + w[pre + ".conv3.w"].numel())
-                    nbytes = (o.numel() + sc.numel() + y.numel() + w[pre + ".conv2.w"].numel() + w[pre + ".conv3.w"].numel()) * es
-                    self.profile.append((pre + ".conv2+conv3 (chained)", flops, e0, e1, nbytes, flops))
-                return y
-        o = self._conv(o, pre + ".conv2", s2, 1, relu=True)
-        return self._conv(o, pre + ".conv3", relu=True, residual=sc, res_mode=1)
+            o1 = self._conv(x, pre + ".conv1", s1, relu=True)
+        y = o2 = None
+        # res3: conv2 -> conv3 + shortcut as ONE launch (with save it also stores conv2's output for the backward), bit-identical to the two
+        if (self.chain_res3 if chain is None else chain) and w[pre + ".conv2.w"].shape[0] == 128 and w[pre + ".conv3.w"].shape[0] == 512:
+            def cost_chain(r):
+                y_, mid = r if save is not None else (r, None)
+                px, es = y_.numel() // y_.shape[-1], y_.element_size()
+                flops = 2.0 * px * (w[pre + ".conv2.w"].numel() + w[pre + ".conv3.w"].numel())
+                nbytes = (o1.numel() + sc.numel() + y_.numel() + (mid.numel() if mid is not None else 0) + w[pre + ".conv2.w"].numel() + w[pre + ".conv3.w"].numel()) * es
+                return flops, nbytes, flops
+            r = self._timed(pre + ".conv2+conv3 (chained)", lambda: ops.conv2d_chain(
+                o1, w[pre + ".conv2.w"], w[pre + ".conv2.b"], w[pre + ".conv3.w"], w[pre + ".conv3.b"], sc, s2, 1, keep_mid=save is not None), cost_chain)
+            if r is not None:
+                y, o2 = r if save is not None else (r, None)
+        if y is None:
+            o2 = self._conv(o1, pre + ".conv2", s2, 1, relu=True)
+            y = self._conv(o2, pre + ".conv3", relu=True, residual=sc, res_mode=1)
+        if save is not None:
+            save.append(dict(pre=pre, x=x, o1=o1, o2=o2, y=y, stride=stride, s1=s1, s2=s2, first=first))
+        return y
 
     def _linear(self, x, w, b, relu, out_dtype=None, name="fc", row_seg=None, real_rows=None):
         """real_rows (profiling only): how many of x's rows carry data. The padding rows of the per-image proposal lists are not
         algorithmic work: FLOPs and bytes are credited for the real rows only, the nominal figure (all rows of the
         fixed-capacity list) is kept beside it."""
-        if self.profile is None:
-            return ops.linear(x, w, b, relu=relu, out_dtype=out_dtype, row_seg=row_seg)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        y = ops.linear(x, w, b, relu=relu, out_dtype=out_dtype, row_seg=row_seg)
-        e1.record()
-        # (real_rows may be a callable that reads a device count: it is resolved by resolve_profile() AFTER the pass, so that no host
-        # sync sits between the launches of the attribution pass -- a sync in front of a kernel makes it start on an idle, down-clocked GPU)
-        rows_of = (lambda: x.shape[0]) if real_rows is None else (real_rows if callable(real_rows) else (lambda: int(real_rows)))
-        kx, ky, es_x, es_y, wbytes, kn = x.shape[1], y.shape[1], x.element_size(), y.element_size(), w.numel() * w.element_size(), w.shape[0] * w.shape[1]
-        self.profile.append((name, lambda: 2.0 * rows_of() * kn, e0, e1, lambda: rows_of() * kx * es_x + wbytes + rows_of() * ky * es_y,
-                             2.0 * x.shape[0] * kn))
-        return y
+        def cost(y):
+            # (real_rows may be a callable that reads a device count: it is resolved by resolve_profile() AFTER the pass, so that no host
+            # sync sits between the launches of the attribution pass -- a sync in front of a kernel makes it start on an idle, down-clocked GPU)
+            rows_of = (lambda: x.shape[0]) if real_rows is None else (real_rows if callable(real_rows) else (lambda: int(real_rows)))
+            kx, ky, es_x, es_y, wbytes, kn = x.shape[1], y.shape[1], x.element_size(), y.element_size(), w.numel() * w.element_size(), w.shape[0] * w.shape[1]
+            return lambda: 2.0 * rows_of() * kn, lambda: rows_of() * kx * es_x + wbytes + rows_of() * ky * es_y, 2.0 * x.shape[0] * kn
+        return self._timed(name, lambda: ops.linear(x, w, b, relu=relu, out_dtype=out_dtype, row_seg=row_seg), cost)
 
-    def _backbone(self, images: torch.Tensor, hp: int, wp: int, keep: Optional[dict] = None, normalized: bool = False) -> Dict[str, torch.Tensor]:
+    def _stem(self, images, hp: int, wp: int, normalized: bool = False, keep_stem: bool = False):
+        """Preprocessing, the stem's 7x7 conv + ReLU and the 3x3/2 max pool -> (pooled output, padded batch, un-pooled stem output).
+        The last two are None when all of it ran as one launch; keep_stem asks for them (a trainable stem's backward, `keep`)."""
         c = self.cfg
-        if "backbone" in self.fp32_points:  # diagnostic: the fp32 kernels compute the pyramid, the heads get it in the storage dtype
-            return {k: v.to(self.dtype) for k, v in self._bb32._backbone(images, hp, wp, None, normalized).items()}
         mean, std = ((0.0, 0.0, 0.0), (1.0, 1.0, 1.0)) if normalized else (c["pixel_mean"], c["pixel_std"])
-        fused = self.fuse_stem and keep is None
-        xpad = None if fused else ops.preprocess(images, hp, wp, mean, std, self.dtype)
-        if self.profile is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-        sw, sb = self.w["backbone.bottom_up.stem.conv1.w"], self.w["backbone.bottom_up.stem.conv1.b"]
-        if fused:  # normalise + pad + conv1 + ReLU + max pool in one launch: neither the padded batch nor the stem output reaches HBM (keep wants the latter)
-            x = ops.stem_maxpool_raw(images, hp, wp, mean, std, sw, sb)
+        sw, sb = self.w[STEM + ".w"], self.w[STEM + ".b"]
+        if self.fuse_stem and not keep_stem:
+            # normalise + pad + conv1 + ReLU + max pool in one launch: neither the padded batch nor the stem output reaches HBM
             stem_px = images.shape[0] * (hp // 2) * (wp // 2) * 64
-            if self.profile is not None:
-                e1.record()
-                self.profile.append(("backbone.bottom_up.stem (preprocess + conv1 + max pool, fused)", 2.0 * stem_px * 147, e0, e1,
-                                     images.numel() * images.element_size() + x.numel() * 2, 2.0 * stem_px * 147))  # 7*7*3 real taps of every stem pixel
-        else:
-            x = ops.stem_conv(xpad, sw, sb, hp, wp, relu=True)
-            if self.profile is not None:
-                e1.record()
-                self.profile.append(("backbone.bottom_up.stem.conv1", 2.0 * x.numel() * 147, e0, e1,
-                                     xpad.numel() * 2 + x.numel() * 2, 2.0 * x.numel() * 147))  # 7*7*3 real taps
-            if keep is not None:
-                keep["stem"] = x
-            x = ops.maxpool3x3s2(x)
-        feats = {}
-        for si, nb in enumerate(R50_BLOCKS):
-            for b in range(nb):
-                pre = f"backbone.bottom_up.res{si + 2}.{b}"
-                stride = 2 if (b == 0 and si > 0) else 1  # in conv1 or conv2 of the block: cfg stride_in_1x1
-                x = self._bottleneck(x, pre, b == 0, stride)
-            feats[f"res{si + 2}"] = x
-        out = {}
+            x = self._timed(BOTTOM_UP + ".stem (preprocess + conv1 + max pool, fused)", lambda: ops.stem_maxpool_raw(images, hp, wp, mean, std, sw, sb),
+                            lambda x: (2.0 * stem_px * 147, images.numel() * images.element_size() + x.numel() * 2, 2.0 * stem_px * 147))  # 7*7*3 real taps of every stem pixel
+            return x, None, None
+        xpad = ops.preprocess(images, hp, wp, mean, std, self.dtype)
+        stem = self._timed(STEM, lambda: ops.stem_conv(xpad, sw, sb, hp, wp, relu=True),
+                           lambda x: (2.0 * x.numel() * 147, xpad.numel() * 2 + x.numel() * 2, 2.0 * x.numel() * 147))  # 7*7*3 real taps
+        return ops.maxpool3x3s2(stem), xpad, stem
 
-        # [d2] FPN.forward: the lateral 1x1 convs + top-down sums form a chain (p5 -> p2); the four 3x3 output convs only read its results, so
+    def _stages(self, x, first: int, last: int, save: Optional[list] = None, chain: Optional[bool] = None):
+        """The bottlenecks of res{first}..res{last} on x -> (output of the last one, {resN: output of stage N}). save, chain: see
+        _bottleneck; this walk is the one place that knows a block's geometry, and it completes each saved record with it."""
+        res = {}
+        for stage in range(first, last + 1):
+            nb = R50_BLOCKS[stage - 2]
+            for b in range(nb):
+                stride = 2 if (b == 0 and stage > 2) else 1  # in conv1 or conv2 of the block: cfg stride_in_1x1
+                x = self._bottleneck(x, f"{BOTTOM_UP}.res{stage}.{b}", b == 0, stride, save=save, chain=chain)
+                if save is not None:
+                    save[-1].update(stage=stage, last_of_stage=b == nb - 1)
+            res[f"res{stage}"] = x
+        return x, res
+
+    def _fpn(self, res: Dict[str, torch.Tensor], save: Optional[dict] = None) -> Dict[str, torch.Tensor]:
+        """[d2] FPN.forward + LastLevelMaxPool on res2..res5 -> p2..p6. save (the training forward): also keeps the top-down sums as save["lat"]."""
+        # The lateral 1x1 convs + top-down sums form a chain (p5 -> p2); the four 3x3 output convs only read its results, so
         # they run behind it as ONE launch over the four levels (ops.conv2d_levels: one partial last dispatch round instead of four, and the
         # p4 / p5 convs no longer leave most of the chip idle), bit-identical to the per-level launches
-        lat = {5: self._conv(feats["res5"], "backbone.fpn_lateral5")}
+        lat = {5: self._conv(res["res5"], "backbone.fpn_lateral5")}
         for lvl in (4, 3, 2):
-            lat[lvl] = self._conv(feats[f"res{lvl}"], f"backbone.fpn_lateral{lvl}", residual=lat[lvl + 1], res_mode=2)
-        outs = self._fpn_outputs_one_launch([lat[l] for l in (2, 3, 4, 5)]) if self.fuse_levels else None
-        for i, lvl in enumerate((2, 3, 4, 5)):
+            lat[lvl] = self._conv(res[f"res{lvl}"], f"backbone.fpn_lateral{lvl}", residual=lat[lvl + 1], res_mode=2)
+        outs = self._fpn_outputs_one_launch([lat[l] for l in FPN_LEVELS]) if self.fuse_levels else None
+        out = {}
+        for i, lvl in enumerate(FPN_LEVELS):
             out[f"p{lvl}"] = outs[i] if outs is not None else self._conv(lat[lvl], f"backbone.fpn_output{lvl}", 1, 1)
         out["p6"] = ops.subsample2(out["p5"])
-        if keep is not None:
-            keep.update(feats)
+        if save is not None:
+            save["lat"] = lat
         return out
+
+    def _backbone(self, images: torch.Tensor, hp: int, wp: int, keep: Optional[dict] = None, normalized: bool = False) -> Dict[str, torch.Tensor]:
+        if "backbone" in self.fp32_points:  # diagnostic: the fp32 kernels compute the pyramid, the heads get it in the storage dtype
+            return {k: v.to(self.dtype) for k, v in self._bb32._backbone(images, hp, wp, None, normalized).items()}
+        x, _, stem = self._stem(images, hp, wp, normalized, keep_stem=keep is not None)  # (keep wants the un-pooled stem output)
+        _, res = self._stages(x, 2, 5)
+        if keep is not None:
+            keep["stem"] = stem
+            keep.update(res)
+        return self._fpn(res)
 
     def pool_rois(self, feats: Dict[str, torch.Tensor], boxes: torch.Tensor, batch_idx: torch.Tensor, out_dtype=None, fill_padding: bool = True) -> torch.Tensor:
         """[d2] ROIPooler + torchvision roi_align on p2..p5 (osrcnn_roi_heads.py:306) -> (m, 49 * 256) rows in (ph, pw, c) order, the K
         order self.fc1_w is packed in."""
         c = self.cfg
-        fl = [feats[k] for k in ("p2", "p3", "p4", "p5")]
+        fl = [feats[k] for k in PYRAMID[:4]]
         pooled = ops.roi_align(fl, c["pooler_scales"], boxes, batch_idx, c["pooler_resolution"], out_dtype or self.dtype,
                                c["canonical_level"], c["canonical_size"], 2, fill_padding=fill_padding)
         return pooled.view(pooled.shape[0], -1)
@@ -322,60 +331,53 @@ class OpensetRCNNEngine:
         """A stage's first bottleneck reads its input twice ([d2] BottleneckBlock.forward: self.shortcut(x), self.conv1(x)): both 1x1 layers
         as ONE launch (ops.conv2d_pair, bit-identical to the two). Returns (shortcut output, relu(conv1 output)) or None."""
         w = self.w
-        if self.profile is None:
-            return ops.conv2d_pair(x, w[pre + ".shortcut.w"], w[pre + ".shortcut.b"], False, w[pre + ".conv1.w"], w[pre + ".conv1.b"], True, stride, 0)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        out = ops.conv2d_pair(x, w[pre + ".shortcut.w"], w[pre + ".shortcut.b"], False, w[pre + ".conv1.w"], w[pre + ".conv1.b"], True, stride, 0)
-        e1.record()
-        if out is not None:
+
+        def cost(out):
             px = out[0].numel() // out[0].shape[-1]
             flops = 2.0 * px * (w[pre + ".shortcut.w"].numel() + w[pre + ".conv1.w"].numel())
             nbytes = (x.numel() // (stride * stride) + out[0].numel() + out[1].numel() + w[pre + ".shortcut.w"].numel() + w[pre + ".conv1.w"].numel()) * x.element_size()
-            self.profile.append((pre + ".shortcut+conv1 (one launch)", flops, e0, e1, nbytes, flops))
-        return out
+            return flops, nbytes, flops
+        return self._timed(pre + ".shortcut+conv1 (one launch)", lambda: ops.conv2d_pair(
+            x, w[pre + ".shortcut.w"], w[pre + ".shortcut.b"], False, w[pre + ".conv1.w"], w[pre + ".conv1.b"], True, stride, 0), cost)
 
     def _fpn_outputs_one_launch(self, lats):
-        ws = [self.w[f"backbone.fpn_output{l}.w"] for l in (2, 3, 4, 5)]
-        bs = [self.w[f"backbone.fpn_output{l}.b"] for l in (2, 3, 4, 5)]
-        if self.profile is None:
-            return ops.conv2d_levels(lats, ws, bs)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        outs = ops.conv2d_levels(lats, ws, bs)
-        e1.record()
-        if outs is not None:
+        ws = [self.w[f"backbone.fpn_output{l}.w"] for l in FPN_LEVELS]
+        bs = [self.w[f"backbone.fpn_output{l}.b"] for l in FPN_LEVELS]
+
+        def cost(outs):
             flops = sum(2.0 * (x.numel() // x.shape[-1]) * w_.numel() for x, w_ in zip(lats, ws))
             nbytes = sum(x.numel() + o.numel() + w_.numel() for x, o, w_ in zip(lats, outs, ws)) * lats[0].element_size()
-            self.profile.append(("backbone.fpn_output2-5 (four levels, one launch)", flops, e0, e1, nbytes, flops))
-        return outs
+            return flops, nbytes, flops
+        return self._timed("backbone.fpn_output2-5 (four levels, one launch)", lambda: ops.conv2d_levels(lats, ws, bs), cost)
 
     def _rpn_levels_fused(self, fl, deltas, ctrs, hiddens):
-        w, b = self.w["proposal_generator.rpn_head.conv.w"], self.w["proposal_generator.rpn_head.conv.b"]
-        if self.profile is None:
-            return ops.cfrpn_head_fused_levels(fl, w, b, self.rpn_wtail, self.rpn_btail, deltas, ctrs, hiddens)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        ok = ops.cfrpn_head_fused_levels(fl, w, b, self.rpn_wtail, self.rpn_btail, deltas, ctrs, hiddens)
-        e1.record()
-        if ok:
+        w, b = self.w[RPN_CONV + ".w"], self.w[RPN_CONV + ".b"]
+
+        def cost(ok):
             rows = sum(d.shape[0] for d in deltas)
             flops = 2.0 * rows * 256 * (2304 + 5)
-            self.profile.append(("proposal_generator.rpn_head.conv+tail (p2-p6, one launch)", flops, e0, e1,
-                                 sum(f.numel() for f in fl) * 2 + w.numel() * 2 + rows * 20, flops))
-        return ok
+            return flops, sum(f.numel() for f in fl) * 2 + w.numel() * 2 + rows * 20, flops
+        return self._timed(RPN_CONV + "+tail (p2-p6, one launch)", lambda: ops.cfrpn_head_fused_levels(fl, w, b, self.rpn_wtail, self.rpn_btail, deltas, ctrs, hiddens), cost)
 
     def _rpn_level_fused(self, f, deltas, ctr, hidden=None):
-        w, b = self.w["proposal_generator.rpn_head.conv.w"], self.w["proposal_generator.rpn_head.conv.b"]
+        w, b, rows = self.w[RPN_CONV + ".w"], self.w[RPN_CONV + ".b"], deltas.shape[0]
+        return self._timed(RPN_CONV + "+tail", lambda: ops.cfrpn_head_fused(f, w, b, self.rpn_wtail, self.rpn_btail, deltas, ctr, hidden),
+                           lambda out: (2.0 * rows * 256 * (2304 + 5), f.numel() * 2 + w.numel() * 2 + rows * 20, 2.0 * rows * 256 * (2304 + 5)))
+
+    def _timed(self, name, fn, cost):
+        """Run fn(), one MFMA launch; with profile set, bracket it with HIP events on the launch stream and record (name, algorithmic
+        flops, e0, e1, bytes, nominal flops). cost(result) -> (flops, bytes, nominal): numbers, or callables that resolve_profile()
+        evaluates after the pass. A fused launch that declines the shape (fn() returns None / False) leaves no entry."""
         if self.profile is None:
-            return ops.cfrpn_head_fused(f, w, b, self.rpn_wtail, self.rpn_btail, deltas, ctr, hidden)
+            return fn()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        ops.cfrpn_head_fused(f, w, b, self.rpn_wtail, self.rpn_btail, deltas, ctr, hidden)
+        out = fn()
         e1.record()
-        rows = deltas.shape[0]
-        self.profile.append(("proposal_generator.rpn_head.conv+tail", 2.0 * rows * 256 * (2304 + 5), e0, e1,
-                             f.numel() * 2 + w.numel() * 2 + rows * 20, 2.0 * rows * 256 * (2304 + 5)))
+        if out is not None and out is not False:
+            flops, nbytes, nominal = cost(out)
+            self.profile.append((name, flops, e0, e1, nbytes, nominal))
+        return out
 
     def _hbm(self, name, fn, nbytes, info=None):
         """Run fn(); with profile_hbm set, bracket it with HIP events on the launch stream and record its ALGORITHMIC bytes
@@ -406,7 +408,7 @@ class OpensetRCNNEngine:
         return self._lv_cache[key]
 
     def _rpn(self, feats: Dict[str, torch.Tensor], image_hw: torch.Tensor, keep: Optional[dict] = None, topk: Optional[int] = None):
-        fl = [feats[k] for k in ("p2", "p3", "p4", "p5", "p6")]
+        fl = [feats[k] for k in PYRAMID]
         n = fl[0].shape[0]
         shapes = [(f.shape[1], f.shape[2]) for f in fl]
         rows = [n * h * w for h, w in shapes]
@@ -427,7 +429,7 @@ class OpensetRCNNEngine:
             t_all = torch.empty((sum(rows), 256), dtype=t_dt, device=self.device)
             off = 0
             for f, r in zip(fl, rows):
-                self._conv(f, "proposal_generator.rpn_head.conv", 1, 1, relu=True, out=t_all[off:off + r], out_dtype=t_dt)
+                self._conv(f, RPN_CONV, 1, 1, relu=True, out=t_all[off:off + r], out_dtype=t_dt)
                 off += r
             deltas, ctr = ops.cfrpn_head_tail(t_all, self.rpn_wd, self.rpn_bd, self.rpn_wc, self.rpn_bc)
         k = self.cfg["pre_nms_topk_test"] if topk is None else topk
@@ -444,7 +446,7 @@ class OpensetRCNNEngine:
         c = self.cfg
         n, cap = sel["boxes"].shape[0], sel["cap"]
         boxes = sel["boxes"].view(-1, 4)
-        fl = [feats[k] for k in ("p2", "p3", "p4", "p5")]
+        fl = [feats[k] for k in PYRAMID[:4]]
         es = fl[0].element_size()
         # algorithmic bytes: the pyramid once + the pooled rows of the REAL RoIs once + their boxes (the padding rows of
         # the fixed-capacity lists are zero-filled, not algorithmic output); `info` carries (real rows, nominal bytes)

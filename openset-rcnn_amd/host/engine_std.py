@@ -13,7 +13,7 @@ from typing import Dict, Optional
 import torch
 
 from . import ops
-from .engine import OpensetRCNNEngine, loss_types_of
+from .engine import PYRAMID, RPN_CONV, OpensetRCNNEngine, loss_types_of
 from .weights import pack_fc1_weight
 
 STD_DEFAULT_CFG = dict(
@@ -84,7 +84,7 @@ class StandardRCNNEngine(OpensetRCNNEngine):
     # ---- [d2] RPN.forward (inference) -------------------------------------------------------------------------------------------
     def _rpn(self, feats, image_hw, keep=None, topk=None, post_topk=None):
         c = self.cfg
-        fl = [feats[k] for k in ("p2", "p3", "p4", "p5", "p6")]
+        fl = [feats[k] for k in PYRAMID]
         n = fl[0].shape[0]
         shapes = [(f.shape[1], f.shape[2]) for f in fl]
         rows = [n * h * w for h, w in shapes]
@@ -95,7 +95,7 @@ class StandardRCNNEngine(OpensetRCNNEngine):
         t_all = torch.empty((sum(rows), 256), dtype=torch.float32, device=self.device)
         off = 0
         for f, r in zip(fl, rows):
-            self._conv(f, "proposal_generator.rpn_head.conv", 1, 1, relu=True, out=t_all[off:off + r], out_dtype=torch.float32)
+            self._conv(f, RPN_CONV, 1, 1, relu=True, out=t_all[off:off + r], out_dtype=torch.float32)
             off += r
         logits = ops.gemm_f32(t_all, self.rpn_wo, self.rpn_bo).view(-1)
         deltas = ops.gemm_f32(t_all, self.rpn_wd, self.rpn_bd).view(-1, 4)
@@ -121,7 +121,7 @@ class StandardRCNNEngine(OpensetRCNNEngine):
         c = self.cfg
         n, cap = sel["boxes"].shape[0], sel["cap"]
         boxes = sel["boxes"].view(-1, 4)
-        pooled = ops.roi_align([feats[k] for k in ("p2", "p3", "p4", "p5")], c["pooler_scales"], boxes, sel["batch_idx"], c["pooler_resolution"],
+        pooled = ops.roi_align([feats[k] for k in PYRAMID[:4]], c["pooler_scales"], boxes, sel["batch_idx"], c["pooler_resolution"],
                                self.dtype, c["canonical_level"], c["canonical_size"], 2)
         m = pooled.shape[0]
         h1 = self._linear(pooled.view(m, -1), self.fc1_w, self.fc1_b, True, name="roi_heads.box_head.fc1")

@@ -23,7 +23,7 @@ from typing import Dict, List, Optional, Tuple
 import torch
 
 from . import ops, parallel
-from .engine import OpensetRCNNEngine, loss_types_of
+from .engine import PYRAMID, RPN_CONV, STEM, OpensetRCNNEngine, loss_types_of
 from .weights import R50_BLOCKS, pack_conv_weight, pack_fc1_weight, pack_stem_weight
 
 
@@ -157,7 +157,7 @@ class OpensetRCNNTrainer:
         for lvl in (5, 4, 3, 2):
             self._add_conv(f"backbone.fpn_lateral{lvl}", params, bias=True)
             self._add_conv(f"backbone.fpn_output{lvl}", params, bias=True)
-        self._add_conv("proposal_generator.rpn_head.conv", params, bias=True)
+        self._add_conv(RPN_CONV, params, bias=True)
         self._add_head_masters(params)
         # ---- one flat gradient buffer (the all-reduce operand), momentum buffers ----
         al = lambda x: (x + 3) // 4 * 4  # noqa: E731  every view starts 16-byte aligned (the kernels use 16-byte accesses)
@@ -172,7 +172,7 @@ class OpensetRCNNTrainer:
         self.buckets = parallel.GradBuckets(self.grad_flat, layout, bucket_bytes)
         self.mom = {k: torch.zeros_like(t) for k, t in self.master.items()}
         # (the stem master is the padded (64, 8, 1, 32) view: its 6 976 padding zeros are not parameters)
-        self.num_params = sum(t.numel() for t in self.master.values()) - (16384 - 9408 if self.STEM + ".w" in self.master else 0)
+        self.num_params = sum(t.numel() for t in self.master.values()) - (16384 - 9408 if STEM + ".w" in self.master else 0)
         # overflow guard: device flag read by every osr_sgd_step launch; its host half is self.scaler (DynamicLossScale)
         self._ok = torch.ones((1,), dtype=torch.int32, device=dev)
         self._cside: Optional[torch.cuda.Stream] = None  # stream the gradient buckets' collectives are issued from (see _done)
@@ -240,14 +240,12 @@ class OpensetRCNNTrainer:
         self.master["cls.w"], self.master["cls.b"] = e.cls_w, e.cls_b
         self.master["protos"] = f32(params["roi_heads.dml.representatives"])
 
-    STEM = "backbone.bottom_up.stem.conv1"
-
     def _add_stem(self, params) -> None:
         """FREEZE_AT 0: the stem's master in the layout of the stem view the forward kernels read, (64, 8, 1, 32) fp32 (weights.pack_stem_weight:
         the 8th row, the 8th tap and the 4th channel zero). Their gradient is exactly zero (osr_stem_wgrad) and so is their weight decay,
         so the update leaves them zero in the master, the momentum and the working view it refreshes. No backward-data weights: nothing is
         below the stem."""
-        e, name = self.eng, self.STEM
+        e, name = self.eng, STEM
         if name in self.frozen_bn:
             w_unfolded, scale = self.frozen_bn[name]
             self.master[name + ".w"] = pack_stem_weight(w_unfolded, torch.float32).to(e.device)
@@ -342,7 +340,7 @@ class OpensetRCNNTrainer:
 
     # ---- forward with saved activations -------------------------------------------------------------------------
     def _forward(self, images, image_hw, hp, wp, gt_boxes, gt_classes, gt_count, keys):
-        e, c = self.eng, self.eng.cfg
+        e = self.eng
         n = images.shape[0]
         s: dict = {}
         # anchor labels / sampling / targets depend on the ground truth only: a few small-grid launches (one workgroup per image)
@@ -358,11 +356,10 @@ class OpensetRCNNTrainer:
                 rpn_targets = e.rpn_targets_forward(lv, n, gt_boxes, gt_count, keys)
                 targets_ready = self._side.record_event()
         out = self._forward_trunk(images, hp, wp, s)
-        # CF-RPN head (unfused: the hidden state t is kept), targets, losses
+        # RPN head, targets, losses
         keep: dict = {}
-        e.rpn_keep_hidden = not self.sparse_rpn_bwd
-        sel = e._rpn(out, image_hw, keep, topk=c["pre_nms_topk_train"])
-        s["rpn_t"], s["rpn_shapes"], s["sel"] = keep["rpn_t"], keep["rpn_shapes"], sel
+        sel = self._rpn_forward(out, image_hw, keep)
+        s.update({k: keep[k] for k in self.RPN_SAVED}, sel=sel)
         self._proposal_status = sel["status_flags"]  # read with this iteration's overflow verdict (DynamicLossScale.record)
         assert list(keep["rpn_shapes"]) == list(shapes), "pyramid_shapes disagrees with the backbone"
         if self.overlap_targets:
@@ -377,69 +374,47 @@ class OpensetRCNNTrainer:
         # RoI heads on the sampled proposals
         roi, roi_state = e.roi_losses_forward(out, sel["boxes"], sel["scores"], sel["counts"], gt_boxes, gt_classes, gt_count, keys["roi"])
         s.update(roi_state)
-        losses = dict(loss_rpn_loc=rpn[0], loss_rpn_ctr=rpn[1], loss_box_reg=roi["loss_box_reg"], loss_iou=roi["loss_iou"],
-                      loss_dml=roi["loss_dml"], loss_cls=roi["loss_cls"])
-        # what event_scalars() reads (references only: nothing is computed or copied unless a logger asks)
-        self._last_forward = dict(n=n, rpn_counts=rpn[2:6], prop_counts=sel["counts"], roi_counts=roi["roi_counts"], logits=roi_state["logits"],
-                                  cls_k=roi_state["cls_k"], nck=roi_state["nck"], batch_idx=roi_state["smp"]["batch_idx"])
+        # (_last_forward: what event_scalars() reads -- references only: nothing is computed or copied unless a logger asks)
+        losses, self._last_forward = self._loss_dict(n, rpn, roi, sel, roi_state)
         return losses, s
 
+    # what differs between the trainers in _forward (StandardRCNNTrainer replaces these three)
+    RPN_SAVED = ("rpn_t", "rpn_shapes")  # what of the RPN head's `keep` the backward reads
+
+    def _rpn_forward(self, feats, image_hw, keep: dict) -> dict:
+        """CF-RPN head + proposal selection (un-fused when the dense backward wants the hidden state t of every anchor)."""
+        self.eng.rpn_keep_hidden = not self.sparse_rpn_bwd
+        return self.eng._rpn(feats, image_hw, keep, topk=self.eng.cfg["pre_nms_topk_train"])
+
+    @staticmethod
+    def _loss_dict(n, rpn, roi, sel, roi_state):
+        """(the loss dict step() returns, _last_forward)"""
+        losses = dict(loss_rpn_loc=rpn[0], loss_rpn_ctr=rpn[1], loss_box_reg=roi["loss_box_reg"], loss_iou=roi["loss_iou"],
+                      loss_dml=roi["loss_dml"], loss_cls=roi["loss_cls"])
+        return losses, dict(n=n, rpn_counts=rpn[2:6], prop_counts=sel["counts"], roi_counts=roi["roi_counts"], logits=roi_state["logits"],
+                            cls_k=roi_state["cls_k"], nck=roi_state["nck"], batch_idx=roi_state["smp"]["batch_idx"])
+
     def _forward_trunk(self, images, hp, wp, s: dict) -> Dict[str, torch.Tensor]:
-        """Backbone + FPN with the activations the backward reads saved into s (blocks, res, lat, p); returns p2..p6."""
+        """Backbone + FPN with the activations the backward reads saved into s (blocks, res, lat, p); returns p2..p6. This is the
+        engine's own walk (_stem, _stages, _fpn) with `save`: which kernel a block gets is decided there, for inference and training."""
         e = self.eng
-        cur = torch.cuda.current_stream(self.device)
         pref, self._prefetched = self._prefetched, None
         if self.freeze_at == 0:
             # trainable stem: its output is kept for the backward (the fused stem + pool launch never writes it); same pooled bits
-            c = e.cfg
-            xpad = ops.preprocess(images, hp, wp, c["pixel_mean"], c["pixel_std"], self.dtype)
-            stem = ops.stem_conv(xpad, e.w[self.STEM + ".w"], e.w[self.STEM + ".b"], hp, wp, relu=True)
-            x, frozen_feats = ops.maxpool3x3s2(stem), {}
+            x, xpad, stem = e._stem(images, hp, wp, keep_stem=True)
+            frozen = {}
             s["stem"] = dict(xpad=xpad, s=stem, hp=hp, wp=wp)
         elif pref is not None and pref[0] is images and pref[1] == (hp, wp) and pref[4] == images._version:
             # the frozen prefix of THIS batch was computed under the previous iteration's backward (step(next_images=...)): take it
-            x, frozen_feats = pref[2]
-            cur.wait_event(pref[3])
+            x, frozen = pref[2]
+            torch.cuda.current_stream(self.device).wait_event(pref[3])
         else:
-            x, frozen_feats = self._frozen_prefix(images, hp, wp)
-        blocks = []
-        feats = {}
-        for si, nb in enumerate(R50_BLOCKS):
-            for b in range(nb):
-                pre = f"backbone.bottom_up.res{si + 2}.{b}"
-                stride = 2 if (b == 0 and si > 0) else 1
-                if si + 2 <= self.freeze_at:  # frozen stage: part of the prefix above (nothing of it is needed by the backward)
-                    break
-                s1, s2 = (stride, 1) if e.cfg["stride_in_1x1"] else (1, stride)  # the stride in conv1 (MSRA) or conv2 (torchvision): o1 at x's size
-                # (one launch for the two readers of x, when both 1x1 layers run at one stride)
-                pair = e._shortcut_conv1_one_launch(x, pre, stride) if b == 0 and e.fuse_levels and s1 == stride else None
-                if pair is not None:
-                    sc, o1 = pair
-                else:
-                    sc = e._conv(x, pre + ".shortcut", stride) if b == 0 else x
-                    o1 = e._conv(x, pre + ".conv1", s1, relu=True)
-                # res3: conv2 -> conv3 + shortcut as ONE launch that also stores conv2's output for the backward (bit-identical to the two)
-                ch = ops.conv2d_chain(o1, e.w[pre + ".conv2.w"], e.w[pre + ".conv2.b"], e.w[pre + ".conv3.w"], e.w[pre + ".conv3.b"], sc, s2, 1,
-                                      keep_mid=True) if (self.chain_forward and e.w[pre + ".conv2.w"].shape[0] == 128 and e.w[pre + ".conv3.w"].shape[0] == 512) else None
-                if ch is not None:
-                    y, o2 = ch
-                else:
-                    o2 = e._conv(o1, pre + ".conv2", s2, 1, relu=True)
-                    y = e._conv(o2, pre + ".conv3", relu=True, residual=sc, res_mode=1)
-                blocks.append(dict(pre=pre, x=x, o1=o1, o2=o2, y=y, stride=stride, s1=s1, s2=s2, first=b == 0, stage=si + 2))
-                x = y
-            feats[f"res{si + 2}"] = frozen_feats[f"res{si + 2}"] if si + 2 <= self.freeze_at else x
-        s["blocks"], s["res"] = blocks, feats
-        out = {}
-        lat = {5: e._conv(feats["res5"], "backbone.fpn_lateral5")}
-        for lvl in (4, 3, 2):
-            lat[lvl] = e._conv(feats[f"res{lvl}"], f"backbone.fpn_lateral{lvl}", residual=lat[lvl + 1], res_mode=2)
-        outs = e._fpn_outputs_one_launch([lat[l] for l in (2, 3, 4, 5)]) if e.fuse_levels else None  # (the four output convs as one launch: engine._backbone)
-        for i, lvl in enumerate((2, 3, 4, 5)):
-            out[f"p{lvl}"] = outs[i] if outs is not None else e._conv(lat[lvl], f"backbone.fpn_output{lvl}", 1, 1)
-        out["p6"] = ops.subsample2(out["p5"])
-        s["lat"], s["p"] = lat, out
-        return out
+            x, frozen = self._frozen_prefix(images, hp, wp)
+        blocks: List[dict] = []  # (nothing of a frozen stage is needed by the backward)
+        _, trained = e._stages(x, max(2, self.freeze_at + 1), 5, save=blocks, chain=self.chain_forward)
+        s["blocks"], s["res"] = blocks, {**frozen, **trained}
+        s["p"] = e._fpn(s["res"], save=s)
+        return s["p"]
 
     def event_scalars(self) -> Dict[str, float]:
         """The ten scalars the reference puts into detectron2's EventStorage during a training iteration, for the LAST forward of this
@@ -474,22 +449,10 @@ class OpensetRCNNTrainer:
 
     def _frozen_prefix(self, images, hp, wp):
         """Stem (+ preprocessing) and the frozen residual stages: what depends on the batch and on frozen weights only -- the output of
-        the last frozen stage (the stem's max pool output when only the stem is frozen)."""
-        e, c = self.eng, self.eng.cfg
-        if e.fuse_stem and self.freeze_at >= 1:  # (the stem is frozen: nothing of it is needed by the backward)
-            x = ops.stem_maxpool_raw(images, hp, wp, c["pixel_mean"], c["pixel_std"], e.w["backbone.bottom_up.stem.conv1.w"], e.w["backbone.bottom_up.stem.conv1.b"])
-        else:
-            xpad = ops.preprocess(images, hp, wp, c["pixel_mean"], c["pixel_std"], self.dtype)
-            x = ops.stem_conv(xpad, e.w["backbone.bottom_up.stem.conv1.w"], e.w["backbone.bottom_up.stem.conv1.b"], hp, wp, relu=True)
-            x = ops.maxpool3x3s2(x)
-        feats = {}
-        for si, nb in enumerate(R50_BLOCKS):
-            if si + 2 > self.freeze_at:
-                break
-            for b in range(nb):
-                x = e._bottleneck(x, f"backbone.bottom_up.res{si + 2}.{b}", b == 0, 2 if (b == 0 and si > 0) else 1)
-            feats[f"res{si + 2}"] = x
-        return x, feats
+        the last frozen stage (the stem's max pool output when only the stem is frozen). freeze_at >= 1: the stem is frozen, nothing of
+        it is needed by the backward, so the engine may run it as one launch."""
+        x, _, _ = self.eng._stem(images, hp, wp)
+        return self.eng._stages(x, 2, self.freeze_at)
 
     def _prefetch_frozen(self, images, hp, wp) -> None:
         """Software pipelining across iterations: the next batch's frozen prefix (a function of that batch and of weights no update
@@ -603,13 +566,12 @@ class OpensetRCNNTrainer:
         bucket's all-reduce as soon as the backward has passed it (several ranks only; all_reduce_grads() then just waits)."""
         e, c, g = self.eng, self.eng.cfg, self.grad
         S = self._backward_begin(grad_scale, overlap)
-        dt = self.dtype
         p = s["p"]
         # --- CF-RPN: losses -> tail -> weight gradient of the 3x3 conv (weights shared by the five levels). This chain depends on
         #     the forward only and meets the RoI heads' chain at the 3x3 conv's data gradient: it runs first, on the second stream,
         #     under the RoI heads' backward (whose RoIAlign scatter is bound by the atomic rate, not by the matrix cores) ---
         sel = s["sel"]
-        rn = "proposal_generator.rpn_head.conv"
+        rn = RPN_CONV
 
         def rpn_chain():
             lt_ = loss_types_of(c)
@@ -620,7 +582,6 @@ class OpensetRCNNTrainer:
                 # the loss touches the sampled anchors only: list the rows with a gradient, gather their im2col rows, and run the
                 # head's backward on that list (csrc/osr_rpn_sparse.hip) -- hidden state recomputed, weight gradient and per-tap data
                 # gradient as three small GEMMs; the dense launches spent 2 x 1.7 TFLOP on zeros
-                lvl_keys = ("p2", "p3", "p4", "p5", "p6")
                 cap = n * 2 * int(c["rpn_batch_size"])
                 ids, rmap, cnt2 = ops.rpn_sparse_rows(d5, cap)
                 # count2 = {listed, found}: rows beyond the cap are dropped by the list (the reference sampler bounds them by 2 x 256 per image;
@@ -630,23 +591,21 @@ class OpensetRCNNTrainer:
                 # in front of its bucket's all-reduce) and reaches the other ranks through the sum; _update() then sees a non-finite
                 # all-reduced buffer everywhere. (the flag used to gate this rank's update only; the peers applied theirs.)
                 rows_fit = (cnt2[1:2] <= min(cap, self.sparse_rows_cap or cap)).to(torch.int32)
-                cols, d5r = ops.rpn_gather_cols(sel["levels"], [p[k_] for k_ in lvl_keys], n, ids, d5)
+                cols, d5r = ops.rpn_gather_cols(sel["levels"], [p[k_] for k_ in PYRAMID], n, ids, d5)
                 w3 = e.w[rn + ".w"].view(256, 9 * 256)
                 t_rows = ops.linear(cols, w3, e.w[rn + ".b"], relu=True)
                 dt_rows, dw_tail, db_tail = ops.cfrpn_tail_bwd(t_rows, e.rpn_wtail, d5r)
                 g["rpn_tail.w"].copy_(dw_tail)
                 g["rpn_tail.b"].copy_(db_tail)
-                ops.conv2d_wgrad(cols.view(1, cap, 1, 9 * 256), dt_rows.view(1, cap, 1, 256), 1, 1, dw=g[rn + ".w"].view(256, 1, 1, 9 * 256))
-                ops.bias_grad(dt_rows, g[rn + ".b"])
-                parallel.poison_unless_(rows_fit, g[rn + ".b"].view(-1)[:1])
-                y_rows = ops.linear(dt_rows, w3.t().contiguous(), ops._zero_bias(9 * 256, self.device), out_dtype=torch.float32)
+                # (w3 is transposed inside every step here; StandardRCNNTrainer keeps a transposed copy refreshed with the parameters)
+                y_rows = self._sparse_rpn_conv_bwd(cols, dt_rows, rows_fit, lambda: w3.t().contiguous())
                 return (rmap, y_rows), torch.cuda.current_stream(self.device).record_event()
             dta, dw_tail, db_tail = ops.cfrpn_tail_bwd(s["rpn_t"], e.rpn_wtail, d5)
             g["rpn_tail.w"].copy_(dw_tail)
             g["rpn_tail.b"].copy_(db_tail)
             ready = torch.cuda.current_stream(self.device).record_event()
             off_ = 0
-            for li_, (k_, (h_, w_)) in enumerate(zip(("p2", "p3", "p4", "p5", "p6"), s["rpn_shapes"])):
+            for li_, (k_, (h_, w_)) in enumerate(zip(PYRAMID, s["rpn_shapes"])):
                 rows_ = n * h_ * w_
                 dtl_ = dta[off_:off_ + rows_].view(n, h_, w_, 256)
                 off_ += rows_
@@ -675,23 +634,40 @@ class OpensetRCNNTrainer:
         # --- CF-RPN 3x3 conv: data gradient per level, joined with the RoI heads' feature gradient (the chain above it ran on the
         #     second stream, see the top of this function) ---
         self._join_side(rpn_ready, rpn_grad)
-        dP = {}
-        lvl_shapes = list(zip(("p2", "p3", "p4", "p5", "p6"), s["rpn_shapes"]))
-        roi_part = [(d_feat[li] if d_feat[li].dtype == dt else ops.add_cast(d_feat[li], None, dt)) for li in range(4)] + [None]
         if self.sparse_rpn_bwd:
-            # col2im of the listed anchors' per-tap gradients straight into the RoI heads' feature gradient (p6 has none: into zeros)
-            rmap, y_rows = rpn_grad
-            h6, w6 = s["rpn_shapes"][4]
-            glist = roi_part[:4] + [torch.zeros((n, h6, w6, 256), dtype=dt, device=self.device)]
-            ops.rpn_scatter_cols_add_(sel["levels"], n, rmap, y_rows, glist)
-            dP = {k: gl for (k, _), gl in zip(lvl_shapes, glist)}
+            dP = self._sparse_rpn_scatter(sel["levels"], s, n, rpn_grad, d_feat)
         else:
-            (dt_all,), off = rpn_grad, 0
-            for li, (k, (h, w)) in enumerate(lvl_shapes):
+            dP, (dt_all,), off = {}, rpn_grad, 0
+            roi_part = self._roi_share(d_feat) + [None]
+            for li, (k, (h, w)) in enumerate(zip(PYRAMID, s["rpn_shapes"])):
                 rows = n * h * w
                 dP[k] = ops.conv2d_dgrad(dt_all[off:off + rows].view(n, h, w, 256), self.wd[rn], (h, w), 1, 1, add=roi_part[li])
                 off += rows
         self._backward_trunk(s, dP, prefetch)
+
+    def _sparse_rpn_conv_bwd(self, cols, dt_rows, rows_fit, w3_t) -> torch.Tensor:
+        """The RPN head's 3x3 conv on the listed rows, behind the tail's backward: cols (cap, 2304) the gathered im2col rows, dt_rows
+        (cap, 256) the hidden state's gradient -> weight gradient as a GEMM, bias gradient (poisoned unless the list fitted: rows_fit),
+        and the per-tap data gradient y_rows (cap, 2304) fp32. w3_t: the (2304, 256) transposed weight matrix, or a callable that makes
+        it (evaluated in front of the launch that reads it)."""
+        g, cap = self.grad, cols.shape[0]
+        ops.conv2d_wgrad(cols.view(1, cap, 1, 9 * 256), dt_rows.view(1, cap, 1, 256), 1, 1, dw=g[RPN_CONV + ".w"].view(256, 1, 1, 9 * 256))
+        ops.bias_grad(dt_rows, g[RPN_CONV + ".b"])
+        parallel.poison_unless_(rows_fit, g[RPN_CONV + ".b"].view(-1)[:1])
+        return ops.linear(dt_rows, w3_t() if callable(w3_t) else w3_t, ops._zero_bias(9 * 256, self.device), out_dtype=torch.float32)
+
+    def _roi_share(self, d_feat) -> List[torch.Tensor]:
+        """The RoI heads' feature gradient of p2..p5 in the storage type."""
+        return [(d if d.dtype == self.dtype else ops.add_cast(d, None, self.dtype)) for d in d_feat[:4]]
+
+    def _sparse_rpn_scatter(self, levels, s, n, rpn_grad, d_feat) -> Dict[str, torch.Tensor]:
+        """col2im of the listed anchors' per-tap gradients straight into the RoI heads' feature gradient (p6 has none: into zeros).
+        levels: the level table of the pixel rows the list indexes. Returns dP (p2..p6)."""
+        rmap, y_rows = rpn_grad
+        h6, w6 = s["rpn_shapes"][4]
+        glist = self._roi_share(d_feat) + [torch.zeros((n, h6, w6, 256), dtype=self.dtype, device=self.device)]
+        ops.rpn_scatter_cols_add_(levels, n, rmap, y_rows, glist)
+        return dict(zip(PYRAMID, glist))
 
     def _box_head_bwd(self, s, d_bf, n):
         """d box features (m,1024) fp32 -> FC2, FC1 (data + weight gradients) -> RoIAlign backward: the feature gradient per level."""
@@ -711,7 +687,7 @@ class OpensetRCNNTrainer:
                           ops.bias_grad(d_h1, g["fc1.b"])), d_h1)
         self._done("fc1.w", "fc1.b")
         P = c["pooler_resolution"]
-        shapes = [(p[k].shape[1], p[k].shape[2]) for k in ("p2", "p3", "p4", "p5")]
+        shapes = [(p[k].shape[1], p[k].shape[2]) for k in PYRAMID[:4]]
         d_feat = ops.roi_align_bwd(d_pooled.view(m, P, P, -1), shapes, n, c["pooler_scales"], s["boxes"], s["smp"]["batch_idx"], c["canonical_level"],
                                    c["canonical_size"], 2, rois_per_image=m // n if m % n == 0 else None,  # (the sampled list is (n, S))
                                    out_dtype=dt if d_pooled.dtype == dt else None)
@@ -750,8 +726,7 @@ class OpensetRCNNTrainer:
             pre, x, o1, o2, y, stride = blk["pre"], blk["x"], blk["o1"], blk["o2"], blk["y"], blk["stride"]
             s1, s2 = blk["s1"], blk["s2"]
             hy, wy = y.shape[1], y.shape[2]
-            last_of_stage = blk is s["blocks"][-1] or pre.endswith(f".{R50_BLOCKS[blk['stage'] - 2] - 1}")
-            if last_of_stage:  # the stage output also feeds its FPN lateral
+            if blk["last_of_stage"]:  # the stage output also feeds its FPN lateral
                 d_ls, ln = d_res[blk["stage"]]
                 G = ops.conv2d_dgrad(d_ls, self.wd[ln], (hy, wy), 1, 0, add=G, post_mask=y)
             # (the last blocks of the backward: the weight-gradient stream is behind the data-gradient chain by then and nothing waits for
@@ -773,8 +748,7 @@ class OpensetRCNNTrainer:
             hx, wx = x.shape[1], x.shape[2]
             # x is the output of the block below (post-ReLU): its mask goes into the launch that completes G -- unless that block
             # is the last of its stage, whose G is completed (and masked) by the lateral's launch at the top of the next turn
-            below_last = bi > 0 and s["blocks"][bi - 1]["pre"].endswith(f".{R50_BLOCKS[s['blocks'][bi - 1]['stage'] - 2] - 1}")
-            pm = None if below_last else x
+            pm = None if bi > 0 and s["blocks"][bi - 1]["last_of_stage"] else x
             if blk["first"] and s1 != stride:
                 # stride in conv2: conv1's share is dense, the shortcut's covers the even pixels only. The strided launch goes first
                 # (into a zeroed dx), conv1's dense launch adds it and applies the mask: every pixel is summed and masked once
@@ -791,8 +765,8 @@ class OpensetRCNNTrainer:
             # backward -> the stem's weight gradient (csrc/osr_stem_bwd.hip)
             st = s["stem"]
             ds = ops.stem_pool_bwd(st["s"], G)
-            self._wg(lambda: ops.stem_wgrad(st["xpad"], ds, st["hp"], st["wp"], dw=g[self.STEM + ".w"]), ds, st["xpad"])
-            self._done(self.STEM + ".w")
+            self._wg(lambda: ops.stem_wgrad(st["xpad"], ds, st["hp"], st["wp"], dw=g[STEM + ".w"]), ds, st["xpad"])
+            self._done(STEM + ".w")
         if prefetch is not None:  # behind the last data gradient: the main stream is done, the weight-gradient stream still has its backlog
             self._prefetch_frozen(*prefetch)
         if self.side_wgrad and self._wside is not None:  # join: the update (and any collective issued from here on) sees every weight gradient
@@ -953,8 +927,8 @@ class OpensetRCNNTrainer:
     def _export_trunk(self) -> Dict[str, torch.Tensor]:
         """Backbone / FPN / RPN 3x3 conv and box head FC1 / FC2 masters under detectron2 names and layouts."""
         out: Dict[str, torch.Tensor] = {}
-        if self.STEM + ".w" in self.master:  # stem view (64, 8, 1, 32) -> (64, 3, 7, 7)
-            out[self.STEM + ".weight"] = self.master[self.STEM + ".w"].view(64, 8, 8, 4)[:, :7, :7, :3].permute(0, 3, 1, 2).contiguous().cpu()
+        if STEM + ".w" in self.master:  # stem view (64, 8, 1, 32) -> (64, 3, 7, 7)
+            out[STEM + ".weight"] = self.master[STEM + ".w"].view(64, 8, 8, 4)[:, :7, :7, :3].permute(0, 3, 1, 2).contiguous().cpu()
         for n in self.conv_names:
             out[n + ".weight"] = self.master[n + ".w"].permute(0, 3, 1, 2).contiguous().cpu()
             if n + ".b" in self.master:

@@ -20,7 +20,8 @@ from typing import Dict
 
 import torch
 
-from . import ops, parallel
+from . import ops
+from .engine import PYRAMID, RPN_CONV
 from .engine_std import StandardRCNNEngine, check_std_supported, std_loss_beta
 from .train import OpensetRCNNTrainer
 from .weights import pack_fc1_weight
@@ -73,7 +74,7 @@ class StandardRCNNTrainer(OpensetRCNNTrainer):
         self.t_cls[:, : e.cls_w.shape[0]].copy_(e.cls_w.t())
         self.t_box[:, : e.box_w.shape[0]].copy_(e.box_w.t())
         # the RPN 3x3 conv's weight as the (2304, 256) matrix of its per-tap data gradient y = dt . W (a function of the parameters)
-        w3 = e.w["proposal_generator.rpn_head.conv.w"].view(256, 9 * 256)
+        w3 = e.w[RPN_CONV + ".w"].view(256, 9 * 256)
         if not hasattr(self, "w3_t"):
             self.w3_t = torch.empty((9 * 256, 256), dtype=w3.dtype, device=e.device)
         self.w3_t.copy_(w3.t())
@@ -86,40 +87,16 @@ class StandardRCNNTrainer(OpensetRCNNTrainer):
         return self._pixel_lv[key]
 
     # ---- forward -----------------------------------------------------------------------------------------------
-    def _forward(self, images, image_hw, hp, wp, gt_boxes, gt_classes, gt_count, keys):
-        e, c = self.eng, self.eng.cfg
-        n = images.shape[0]
-        s: dict = {}
-        cur = torch.cuda.current_stream(self.device)
-        shapes = e.pyramid_shapes(hp, wp)
-        lv = e._levels(shapes, n)
-        if self._side is None:
-            self._side = torch.cuda.Stream(device=self.device)
-        if self.overlap_targets:  # anchor labels / matched boxes depend on the ground truth only: beside the backbone
-            self._side.wait_stream(cur)
-            with torch.cuda.stream(self._side):
-                rpn_targets = e.rpn_targets_forward(lv, n, gt_boxes, gt_count, keys)
-                targets_ready = self._side.record_event()
-        out = self._forward_trunk(images, hp, wp, s)
-        keep: dict = {}
-        sel = e._rpn(out, image_hw, keep, topk=c["pre_nms_topk_train"], post_topk=c["post_nms_topk_train"])
-        s["rpn_shapes"], s["sel"] = keep["rpn_shapes"], sel
-        self._proposal_status = sel["status_flags"]  # read with this iteration's overflow verdict (DynamicLossScale.record)
-        assert list(keep["rpn_shapes"]) == list(shapes), "pyramid_shapes disagrees with the backbone"
-        if self.overlap_targets:
-            cur.wait_event(targets_ready)
-            if not torch.cuda.is_current_stream_capturing():
-                for t in rpn_targets.values():
-                    t.record_stream(cur)
-        else:
-            rpn_targets = None
-        rpn, rpn_state = e.rpn_losses_forward(sel, n, gt_boxes, gt_count, keys, targets=rpn_targets)
-        s.update(rpn_state)
-        roi, roi_state = e.roi_losses_forward(out, sel["boxes"], sel["scores"], sel["counts"], gt_boxes, gt_classes, gt_count, keys["roi"])
-        s.update(roi_state)
+    RPN_SAVED = ("rpn_shapes",)
+
+    def _rpn_forward(self, feats, image_hw, keep: dict) -> dict:
+        c = self.eng.cfg
+        return self.eng._rpn(feats, image_hw, keep, topk=c["pre_nms_topk_train"], post_topk=c["post_nms_topk_train"])
+
+    @staticmethod
+    def _loss_dict(n, rpn, roi, sel, roi_state):
         losses = dict(loss_rpn_cls=rpn[0], loss_rpn_loc=rpn[1], loss_cls=roi["loss_cls"], loss_box_reg=roi["loss_box_reg"])
-        self._last_forward = dict(n=n, rpn_counts=rpn[2:4], roi_counts=roi["roi_counts"], stats=roi["stats"])
-        return losses, s
+        return losses, dict(n=n, rpn_counts=rpn[2:4], roi_counts=roi["roi_counts"], stats=roi["stats"])
 
     def event_scalars(self) -> Dict[str, float]:
         """The scalars [d2] RPN / StandardROIHeads / FastRCNNOutputLayers put into EventStorage for the last forward: rpn/num_pos_anchors,
@@ -151,8 +128,7 @@ class StandardRCNNTrainer(OpensetRCNNTrainer):
         S = self._backward_begin(grad_scale, overlap)
         dt = self.dtype
         p, sel = s["p"], s["sel"]
-        rn = "proposal_generator.rpn_head.conv"
-        lvl_keys = ("p2", "p3", "p4", "p5", "p6")
+        rn = RPN_CONV
 
         def rpn_chain():
             d = ops.std_rpn_losses_bwd(sel["levels"], e.cell_anchors, n, sel["pred_logits"], sel["pred_deltas"], s["labels"], s["matched_boxes"],
@@ -164,14 +140,11 @@ class StandardRCNNTrainer(OpensetRCNNTrainer):
             ids, rmap, cnt2 = ops.rpn_sparse_rows_ex(d, cap)
             rows_fit = (cnt2[1:2] <= min(cap, self.sparse_rows_cap or cap)).to(torch.int32)
             plv = self._pixel_levels(s["rpn_shapes"], n)
-            cols, d_rows = ops.rpn_gather_cols_ex(plv, [p[k_] for k_ in lvl_keys], n, ids, d)
+            cols, d_rows = ops.rpn_gather_cols_ex(plv, [p[k_] for k_ in PYRAMID], n, ids, d)
             w3 = e.w[rn + ".w"].view(256, 9 * 256)
             t_rows = ops.linear(cols, w3, e.w[rn + ".b"], relu=True, out_dtype=torch.float32)
             dt_rows, _, _ = ops.std_rpn_tail_bwd(t_rows, e.rpn_wtail, d_rows, dt, dw=g["rpn_tail.w"], db=g["rpn_tail.b"])
-            ops.conv2d_wgrad(cols.view(1, cap, 1, 9 * 256), dt_rows.view(1, cap, 1, 256), 1, 1, dw=g[rn + ".w"].view(256, 1, 1, 9 * 256))
-            ops.bias_grad(dt_rows, g[rn + ".b"])
-            parallel.poison_unless_(rows_fit, g[rn + ".b"].view(-1)[:1])
-            y_rows = ops.linear(dt_rows, self.w3_t, ops._zero_bias(9 * 256, self.device), out_dtype=torch.float32)
+            y_rows = self._sparse_rpn_conv_bwd(cols, dt_rows, rows_fit, self.w3_t)
             return (rmap, y_rows), torch.cuda.current_stream(self.device).record_event()
 
         rpn_grad, rpn_ready = self._on_side(rpn_chain)
@@ -187,12 +160,7 @@ class StandardRCNNTrainer(OpensetRCNNTrainer):
         d_feat = self._box_head_bwd(s, d_bf, n)
         # --- RPN 3x3 conv: col2im of the listed anchors' per-tap gradients into the RoI heads' feature gradient (p6: into zeros) ---
         self._join_side(rpn_ready, rpn_grad)
-        rmap, y_rows = rpn_grad
-        h6, w6 = s["rpn_shapes"][4]
-        glist = [(d_feat[li] if d_feat[li].dtype == dt else ops.add_cast(d_feat[li], None, dt)) for li in range(4)]
-        glist.append(torch.zeros((n, h6, w6, 256), dtype=dt, device=self.device))
-        ops.rpn_scatter_cols_add_(self._pixel_levels(s["rpn_shapes"], n), n, rmap, y_rows, glist)
-        self._backward_trunk(s, dict(zip(lvl_keys, glist)), prefetch)
+        self._backward_trunk(s, self._sparse_rpn_scatter(self._pixel_levels(s["rpn_shapes"], n), s, n, rpn_grad, d_feat), prefetch)
 
     def export_state_dict(self) -> Dict[str, torch.Tensor]:
         """The trainable parameters under detectron2 names and layouts (StandardRPNHead, FastRCNNOutputLayers keys)."""
