@@ -213,6 +213,37 @@ osr_status osr_gemm_f32_tn(const float* a, int64_t lda, const float* b, int64_t 
                            int32_t n, int32_t k, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * Split-precision fully connected layer: FastRCNNConvFCHead fc1 / fc2 (osrcnn_roi_heads.py:308) with the reference's fp32
+ * operands, on the bf16 matrix instruction.   out = act(x * W^T + bias),  x (m, k) fp32, W (n, k) fp32, out (m, n) fp32.
+ * Every fp32 value is carried as two bf16 terms, v = v0 + v1 with v0 = bf16(v), v1 = bf16(v - v0), both rounded to nearest
+ * even (bf16 has fp32's exponent range: no scaling and no exponents), and the layer sums x0 w0 + x1 w0 + x0 w1 in fp32;
+ * the x1 w1 term is dropped. Error against the exact product: about 2^-16 per product before the cancellation of the sum
+ * (measured 4e-6 of the largest output at k = 12544: DESIGN.md section 4), inside the 1e-4 of the fp32 parity mode.
+ *   osr_split_rows_bf16  splits a (rows, cols) fp32 matrix into its two (rows, cols) bf16 planes hi, lo: the static operand
+ *                        W, once. host/weights.py split_fp32_rows is the same format in torch.
+ *   osr_linear_split_fwd takes W as those planes and splits the rows of x on their way to the matrix cores.
+ * k and n must be multiples of 64, anything else returns OSR_ERR_UNSUPPORTED with nothing launched; any m >= 1. ldx / ldo are
+ * row strides in elements (multiples of 4); all pointers 16-byte aligned. row_seg_counts / row_seg_rows describe padded
+ * per-image row lists exactly as in osr_conv_params: a 128-row tile without a data row is skipped and its output rows are left
+ * unwritten; every other row is computed. Rows are independent: what a padding row of x holds (uninitialised memory, NaN)
+ * reaches its own output row only. One workgroup sums the whole K axis of its tile in order (no atomics, no split-K): a launch
+ * is bitwise reproducible. Non-finite inputs: an Inf or NaN in a row of x makes that output row non-finite, one in a row of W
+ * that output column, and so does a finite value beyond bf16's largest (about 3.39e38), whose leading term rounds to Inf;
+ * which elements exactly become Inf and which NaN is not specified. ReLU keeps a NaN.
+ * --------------------------------------------------------------------------------------------------------- */
+typedef struct osr_linear_split_params {
+    int32_t m, n, k;
+    int32_t relu;
+    int64_t ldx, ldo;
+    const int32_t* row_seg_counts; /* optional (may be null), device memory */
+    int32_t row_seg_rows;
+    int32_t reserved;
+} osr_linear_split_params;
+osr_status osr_split_rows_bf16(const float* w, int32_t rows, int32_t cols, void* hi, void* lo, void* stream);
+osr_status osr_linear_split_fwd(const osr_linear_split_params* p, const float* x, const void* w_hi, const void* w_lo,
+                                const float* bias, float* out, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * CF-RPN head tail: ClsFreeRPNHead.forward after the 3x3 conv+ReLU (classification_free_rpn.py:159-161):
  * t/max(||t||_2,1e-12) over channels, 1x1 -> 4 ltrb deltas, 1x1 -> centerness, sigmoid.
  * t: (rows, c) channels-last hidden state; w_delta (4,c), w_ctr (1,c) fp32. Outputs fp32.

@@ -52,6 +52,12 @@ class BottleneckParams(C.Structure):
                 ("dtype", C.c_int32), ("has_proj", C.c_int32)]
 
 
+class LinearSplitParams(C.Structure):
+    """include/osr.h osr_linear_split_params."""
+    _fields_ = [("m", C.c_int32), ("n", C.c_int32), ("k", C.c_int32), ("relu", C.c_int32), ("ldx", C.c_int64), ("ldo", C.c_int64),
+                ("row_seg_counts", C.c_void_p), ("row_seg_rows", C.c_int32), ("reserved", C.c_int32)]
+
+
 class LossOptions(C.Structure):
     _fields_ = [("box_loss_type", C.c_int32), ("box_smooth_l1_beta", C.c_float), ("aux_smooth_l1_beta", C.c_float)]
 
@@ -124,6 +130,8 @@ PROTOTYPES = {
     "osr_gemm_f32": (I32, [P, I64, P, P, P, I64, I32, I32, I32, I32, P]),
     "osr_gemm_f32_tn_workspace_bytes": (I64, [I32, I32, I32]),
     "osr_gemm_f32_tn": (I32, [P, I64, P, I64, P, I64, I32, I32, I32, P, I64, P]),
+    "osr_split_rows_bf16": (I32, [P, I32, I32, P, P, P]),
+    "osr_linear_split_fwd": (I32, [C.POINTER(LinearSplitParams), P, P, P, P, P, P]),
     "osr_cfrpn_head_tail": (I32, [P, I32, I64, I32, P, P, P, P, P, P, P]),
     "osr_cfrpn_head_fwd": (I32, [C.POINTER(ConvParams), P, P, P, P, P, P, P, P]),
     "osr_cfrpn_head_fwd_ex": (I32, [C.POINTER(ConvParams), P, P, P, P, P, P, P, P, P]),

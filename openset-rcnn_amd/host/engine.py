@@ -17,7 +17,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import torch
 
 from . import ops
-from .weights import R50_BLOCKS, pack_conv_weight, pack_fc1_weight, pack_stem_weight
+from .weights import R50_BLOCKS, pack_conv_weight, pack_fc1_weight, pack_stem_weight, split_fp32_rows
 
 BOTTOM_UP = "backbone.bottom_up"
 STEM = BOTTOM_UP + ".stem.conv1"
@@ -81,14 +81,27 @@ class OpensetRCNNEngine:
     fp32 oracle to summation order (tests/test_e2e_parity.py)."""
 
     FP32_POINTS = ("backbone", "rpn_hidden", "pooled", "h1")
+    BOX_HEADS = ("storage", "split")
 
     def __init__(self, params: Dict[str, torch.Tensor], cfg: Optional[dict] = None, dtype: torch.dtype = torch.float16,
-                 device: str = "cuda", class_map: Optional[torch.Tensor] = None, fp32_points: Sequence[str] = ()):
+                 device: str = "cuda", class_map: Optional[torch.Tensor] = None, fp32_points: Sequence[str] = (), box_head: str = "storage"):
         """fp32_points (diagnostic; fast mode only): storage points of the fp16 path kept in fp32 instead, to measure what each one
         costs in agreement with the fp32 reference (tests/test_e2e_parity.py): "backbone" (stem .. FPN outputs computed by the
         fp32 kernels, the pyramid handed on in fp16), "rpn_hidden" (the CF-RPN hidden state: un-fused head, fp32 t), "pooled"
         (RoIAlign output and FC1 in fp32), "h1" (FC1 output and FC2 in fp32). The layers behind such a point run on the fp32
-        kernels (1/16 of the matrix rate): a measurement aid, not a product configuration."""
+        kernels (1/16 of the matrix rate): a measurement aid, not a product configuration.
+        box_head: how FC1 / FC2 of the box head multiply. "storage" (default): in the storage dtype, or as fp32_points says.
+        "split" (fp16 / bf16 engines): the reference's fp32 arithmetic from the RoIAlign output on at a usable rate -- RoIAlign
+        writes fp32 rows, FC1 and FC2 run on the split-precision kernel (ops.linear_split: fp32 rows and fp32 weights as two bf16
+        terms each, three bf16 MFMA products, fp32 sums; the terms are bf16 whatever the storage dtype is) and h1 stays fp32.
+        It replaces the "pooled" / "h1" points, so it is refused together with them and with dtype=float32 (ValueError)."""
+        if box_head not in self.BOX_HEADS:
+            raise ValueError(f"box_head must be one of {self.BOX_HEADS}, got {box_head!r}")
+        if box_head == "split" and dtype == torch.float32:
+            raise ValueError('box_head="split" is a mode of the fp16 / bf16 engines: dtype=float32 already computes the box head in fp32')
+        if box_head == "split" and set(fp32_points) & {"pooled", "h1"}:
+            raise ValueError('box_head="split" replaces the "pooled" / "h1" fp32 points: ask for one or the other')
+        self.box_head = box_head
         self.cfg = dict(DEFAULT_CFG)
         if cfg:
             self.cfg.update(cfg)
@@ -176,6 +189,10 @@ class OpensetRCNNEngine:
         self.fc1_b = params["roi_heads.box_head.fc1.bias"].float().to(dev)
         self.fc2_w = params["roi_heads.box_head.fc2.weight"].to(fc2_dt).contiguous().to(dev)
         self.fc2_b = params["roi_heads.box_head.fc2.bias"].float().to(dev)
+        if self.box_head == "split":  # the fp32 weights as two bf16 planes each, split once (FC1 in RoIAlign's K order)
+            w1 = pack_fc1_weight(params["roi_heads.box_head.fc1.weight"], 256, c["pooler_resolution"], torch.float32)
+            self.fc1_split = tuple(t.to(dev) for t in split_fp32_rows(w1)[:2])
+            self.fc2_split = tuple(t.to(dev) for t in split_fp32_rows(params["roi_heads.box_head.fc2.weight"])[:2])
         self.pred_w = torch.cat((f32("roi_heads.box_predictor.bbox_pred.weight"), f32("roi_heads.box_predictor.iou_pred.weight"))).contiguous()
         self.pred_b = torch.cat((f32("roi_heads.box_predictor.bbox_pred.bias"), f32("roi_heads.box_predictor.iou_pred.bias"))).contiguous()
         self.enc_w, self.enc_b = f32("roi_heads.dml.encoder.weight"), f32("roi_heads.dml.encoder.bias")
@@ -254,6 +271,15 @@ class OpensetRCNNEngine:
             kx, ky, es_x, es_y, wbytes, kn = x.shape[1], y.shape[1], x.element_size(), y.element_size(), w.numel() * w.element_size(), w.shape[0] * w.shape[1]
             return lambda: 2.0 * rows_of() * kn, lambda: rows_of() * kx * es_x + wbytes + rows_of() * ky * es_y, 2.0 * x.shape[0] * kn
         return self._timed(name, lambda: ops.linear(x, w, b, relu=relu, out_dtype=out_dtype, row_seg=row_seg), cost)
+
+    def _linear_split(self, x, w_split, b, relu, name="fc", row_seg=None, real_rows=None):
+        """_linear on the split-precision kernel: fp32 rows in, fp32 rows out. The credited FLOPs are the layer's (one product per
+        element pair), not the three bf16 products the kernel spends on each."""
+        def cost(y):
+            rows_of = (lambda: x.shape[0]) if real_rows is None else (real_rows if callable(real_rows) else (lambda: int(real_rows)))
+            kx, ky, kn = x.shape[1], y.shape[1], w_split[0].numel()
+            return lambda: 2.0 * rows_of() * kn, lambda: rows_of() * (kx + ky) * 4 + kn * 4, 2.0 * x.shape[0] * kn
+        return self._timed(name + " (split)", lambda: ops.linear_split(x, w_split, b, relu=relu, row_seg=row_seg), cost)
 
     def _stem(self, images, hp: int, wp: int, normalized: bool = False, keep_stem: bool = False):
         """Preprocessing, the stem's 7x7 conv + ReLU and the 3x3/2 max pool -> (pooled output, padded batch, un-pooled stem output).
@@ -458,7 +484,8 @@ class OpensetRCNNEngine:
                 _real.append(int(sel["counts"].sum()))
             return _real[0]
         row_b = c["pooler_resolution"] ** 2 * 256 * es + 20
-        pooled_dt = torch.float32 if "pooled" in self.fp32_points else self.dtype
+        split = self.box_head == "split"
+        pooled_dt = torch.float32 if split or "pooled" in self.fp32_points else self.dtype
         h1_dt = torch.float32 if self.fp32_points & {"pooled", "h1"} else None  # (the fp32 kernel writes fp32 only)
         # (the padding rows of the per-image lists are not zero-filled unless `keep` hands the pooled rows out: the box head skips the
         # tiles that hold only padding, computes row by row in the others, and nothing downstream reads a padding row)
@@ -469,10 +496,14 @@ class OpensetRCNNEngine:
         # each image's list is [its proposals ..., padding]: the FC tiles that hold only padding rows are skipped (their rows of h1 /
         # box_feats stay unwritten; nothing downstream reads past an image's count)
         seg = (sel["counts"], cap) if self.skip_padding_tiles and not self.fp32_points & {"pooled", "h1"} else None
-        h1 = self._linear(pooled, self.fc1_w, self.fc1_b, True, h1_dt, name="roi_heads.box_head.fc1", row_seg=seg, real_rows=real if profiling else None)
-        if "pooled" in self.fp32_points and "h1" not in self.fp32_points:
-            h1 = h1.to(self.dtype)  # (diagnostic configuration: FC1 ran in fp32, h1 is stored in the fast path's dtype again)
-        box_feats = self._linear(h1, self.fc2_w, self.fc2_b, True, torch.float32, name="roi_heads.box_head.fc2", row_seg=seg, real_rows=real if profiling else None)
+        if split:  # fp32 pooled rows -> fp32 h1 -> fp32 box features, both layers on the split-precision kernel
+            h1 = self._linear_split(pooled, self.fc1_split, self.fc1_b, True, name="roi_heads.box_head.fc1", row_seg=seg, real_rows=real if profiling else None)
+            box_feats = self._linear_split(h1, self.fc2_split, self.fc2_b, True, name="roi_heads.box_head.fc2", row_seg=seg, real_rows=real if profiling else None)
+        else:
+            h1 = self._linear(pooled, self.fc1_w, self.fc1_b, True, h1_dt, name="roi_heads.box_head.fc1", row_seg=seg, real_rows=real if profiling else None)
+            if "pooled" in self.fp32_points and "h1" not in self.fp32_points:
+                h1 = h1.to(self.dtype)  # (diagnostic configuration: FC1 ran in fp32, h1 is stored in the fast path's dtype again)
+            box_feats = self._linear(h1, self.fc2_w, self.fc2_b, True, torch.float32, name="roi_heads.box_head.fc2", row_seg=seg, real_rows=real if profiling else None)
         pt = ops.box_predictor_tail(box_feats, self.pred_w, self.pred_b, boxes, sel["scores"].view(-1), sel["batch_idx"], image_hw,
                                     c["bbox_reg_weights"], 0 if c["mean_type"] == "geometric" else 1, c["obj_score_thresh"])
         topk1 = c["detections_per_image"]

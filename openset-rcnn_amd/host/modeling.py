@@ -125,10 +125,16 @@ class _EngineOwner(nn.Module):
         self._eng_cfg: dict = {}
         self._class_map = None
         self.kernel_dtype = torch.float16
+        # how the box head's FC1 / FC2 multiply (OpensetRCNNEngine box_head): "storage", or "split" = fp32 operands as bf16 terms.
+        # An attribute, not a yaml key: the reference's config files load unchanged
+        self.box_head_precision = "storage"
 
     def engine(self) -> OpensetRCNNEngine:
         if self._shared is not None:
             return self._shared
+        want = self._box_head_precision()
+        if self._eng is not None and getattr(self._eng, "box_head", "storage") != want:
+            self._eng = None  # (box_head_precision was changed after the engine was packed)
         if self._eng is None:
             sd = {self._prefix + k: v.detach() for k, v in self.state_dict().items()}
             dev = next(iter(sd.values())).device
@@ -136,10 +142,15 @@ class _EngineOwner(nn.Module):
                 raise ops.OsrError("the model must be on the GPU (model.to('cuda')): the HIP path has no CPU fallback")
             sd = fold_frozen_bn({k: v.cpu() for k, v in sd.items()})
             if self._engine_cls is OpensetRCNNEngine:
-                self._eng = OpensetRCNNEngine(sd, self._eng_cfg, self.kernel_dtype, str(dev), self._class_map)
+                self._eng = OpensetRCNNEngine(sd, self._eng_cfg, self.kernel_dtype, str(dev), self._class_map, box_head=want)
             else:
+                if want != "storage":
+                    raise ValueError(f"box_head_precision {want!r}: the stock Faster R-CNN engine keeps its box head")
                 self._eng = self._engine_cls(sd, self._eng_cfg, self.kernel_dtype, str(dev))
         return self._eng
+
+    def _box_head_precision(self) -> str:
+        return self.box_head_precision
 
     def refresh(self):
         self._eng = None
@@ -748,6 +759,11 @@ class GeneralizedRCNN(_EngineOwner):
     @property
     def device(self):
         return self.pixel_mean.device
+
+    def _box_head_precision(self) -> str:
+        """The box head's own setting (model.roi_heads.box_head_precision) decides, the model's attribute otherwise."""
+        own = self.roi_heads.box_head_precision
+        return own if own != "storage" else self.box_head_precision
 
     def engine(self) -> OpensetRCNNEngine:
         eng = super().engine()

@@ -226,6 +226,54 @@ def linear(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, relu: bool
     return y.view(m, weight.shape[0])
 
 
+# set to a dict {"launches": 0, "flops": 0.0}: every osr_linear_split_fwd launch and its algorithmic FLOPs (2*m*k*n, one product per
+# element pair: the three bf16 products behind it are the kernel's business) are counted -- how a test or a script sees that a layer
+# ran on the split-precision kernel and on nothing else
+LINEAR_SPLIT_COUNT = None
+
+
+def split_rows_bf16(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """fp32 (rows, cols) on the GPU -> its two bf16 planes (osr_split_rows_bf16): the same bits as weights.split_fp32_rows."""
+    _need(w, torch.float32, "w")
+    if w.dim() != 2 or w.numel() == 0:
+        raise OsrError("split_rows_bf16: a non-empty 2-d matrix")
+    hi, lo = torch.empty_like(w, dtype=torch.bfloat16), torch.empty_like(w, dtype=torch.bfloat16)
+    check(_lib.load().osr_split_rows_bf16(_p(w), w.shape[0], w.shape[1], _p(hi), _p(lo), _stream()), "osr_split_rows_bf16")
+    return hi, lo
+
+
+def linear_split(x: torch.Tensor, w_split, bias: torch.Tensor, relu: bool = False, row_seg: Optional[Tuple[torch.Tensor, int]] = None,
+                 x_exp: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Fully connected layer at fp32 quality on the bf16 MFMA (osr_linear_split_fwd): x (m, k) fp32, w_split = (hi, lo[, None]) the
+    bf16 planes of the (n, k) fp32 weight (weights.split_fp32_rows / split_rows_bf16), bias fp32 -> fp32 (m, n). row_seg: see conv2d
+    (skipped tiles are 128 rows). x_exp: per-row exponents of an fp16-term split; the bf16 terms need none, so it must be None."""
+    if x_exp is not None:
+        raise OsrError("linear_split: the bf16 split carries no row exponents (x_exp must be None)")
+    hi, lo = w_split[0], w_split[1]
+    _need(x, torch.float32, "x"); _need(hi, torch.bfloat16, "w_split hi"); _need(lo, torch.bfloat16, "w_split lo"); _need(bias, torch.float32, "bias")
+    if x.dim() != 2 or hi.dim() != 2 or hi.shape != lo.shape or hi.shape[1] != x.shape[1] or bias.numel() != hi.shape[0] or x.shape[0] < 1:
+        raise OsrError(f"linear_split: x {tuple(x.shape)}, weight planes {tuple(hi.shape)} / {tuple(lo.shape)}, bias {tuple(bias.shape)}")
+    (m, k), n = x.shape, hi.shape[0]
+    if out is None:
+        out = torch.empty((m, n), dtype=torch.float32, device=x.device)
+    else:
+        _need(out, torch.float32, "out")
+        assert tuple(out.shape) == (m, n)
+    p = _lib.LinearSplitParams()
+    p.m, p.n, p.k, p.relu, p.ldx, p.ldo = m, n, k, int(relu), k, n
+    if row_seg is not None:
+        counts, seg_rows = row_seg
+        _need(counts, torch.int32, "row_seg counts")
+        if seg_rows < 1 or counts.numel() * seg_rows < m:
+            raise OsrError("row_seg does not cover the output rows")
+        p.row_seg_counts, p.row_seg_rows = counts.data_ptr(), int(seg_rows)
+    check(_lib.load().osr_linear_split_fwd(C.byref(p), _p(x), _p(hi), _p(lo), _p(bias), _p(out), _stream()), "osr_linear_split_fwd")
+    if LINEAR_SPLIT_COUNT is not None:
+        LINEAR_SPLIT_COUNT["launches"] += 1
+        LINEAR_SPLIT_COUNT["flops"] += 2.0 * m * k * n
+    return out
+
+
 def conv2d_chain(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, w3: torch.Tensor, b3: torch.Tensor, residual: torch.Tensor,
                  stride: int = 1, pad: int = 0, keep_mid: bool = False):
     """A bottleneck's conv2 -> conv3 in one launch (osr_conv2d_chain_fwd): relu(conv1x1(relu(conv(x, weight) + bias), w3) + b3 +

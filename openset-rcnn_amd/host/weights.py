@@ -103,6 +103,18 @@ def pack_fc1_weight(w: torch.Tensor, channels: int, pooled: int, dtype: torch.dt
     return w.view(o, channels, pooled, pooled).permute(0, 2, 3, 1).reshape(o, pooled * pooled * channels).contiguous().to(dtype)
 
 
+def split_fp32_rows(w: torch.Tensor):
+    """The operand format of the split-precision box head (ops.linear_split, include/osr.h osr_linear_split_fwd): an fp32 matrix as
+    two bf16 planes, w = hi + lo to 2^-17 of each element's magnitude, hi = bf16(w), lo = bf16(w - hi), both rounded to nearest
+    even (w - hi is exact in fp32). Returns (hi, lo, exp); exp is None: bf16 carries fp32's exponent range, so rows need no
+    power-of-two scaling and there is no exponent to clamp -- a row of zeros, a row at 1e-30 and a row at 1e30 split like any
+    other (a value beyond bf16's largest, about 3.39e38, would round hi to Inf)."""
+    w = w.detach().to(torch.float32).contiguous()
+    hi = w.to(torch.bfloat16)
+    lo = (w - hi.to(torch.float32)).to(torch.bfloat16)
+    return hi, lo, None
+
+
 def pack_dgrad_weight(w: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
     """(cout,cin,kh,kw) -> (cin,kh,kw,cout), spatially flipped: the backward-data pass of a stride-1 convolution is the
     forward convolution of dy with these weights and padding k-1-pad; for a 1x1 layer it is the transposed matrix."""
