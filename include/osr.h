@@ -243,6 +243,31 @@ osr_status osr_split_rows_bf16(const float* w, int32_t rows, int32_t cols, void*
 osr_status osr_linear_split_fwd(const osr_linear_split_params* p, const float* x, const void* w_hi, const void* w_lo,
                                 const float* bias, float* out, void* stream);
 
+/* The training half of the split-precision layer: the reference's fp32 backward of F.linear (FastRCNNConvFCHead fc1 / fc2) on the
+ * same three bf16 products. Shapes name the LAYER: dy (m, n), x (m, k), W (n, k), all fp32 row-major, ld* in elements (multiples
+ * of 4), pointers 16-byte aligned; n and k multiples of 64 or OSR_ERR_UNSUPPORTED with nothing launched; any m >= 1.
+ *   osr_split_rows_bf16_t  w (rows, cols) fp32 -> the bf16 planes hi, lo of its TRANSPOSE (cols, rows): the operand of the data
+ *                          gradient, refreshed from the fp32 master after an update (host/weights.py split_fp32_rows_t).
+ *   osr_linear_split_dgrad dx[r][k] = (sum_n dy[r][n] W[n][k]) where mask[r][k] > 0, exactly 0 elsewhere (mask: the saved forward
+ *                          output of the layer below, fp32, optional). dy is split on the fly; wt_hi / wt_lo are the (k, n) planes
+ *                          of osr_split_rows_bf16_t, so both operands are contiguous along the reduction. Rows are independent
+ *                          and row lists are handled as in osr_linear_split_fwd (all-padding 128-row tiles are skipped, their rows
+ *                          of dx left unwritten).
+ *   osr_linear_split_wgrad dW[n][k] = sum_r dy[r][n] x[r][k], dW fp32 in the forward layout. Both operands are split on the fly
+ *                          (dy0 x0 + dy1 x0 + dy0 x1). With row_seg_counts (device, one count per row_seg_rows rows, covering
+ *                          m) the rows at or beyond their segment's count contribute nothing whatever they hold (NaN included).
+ *                          When `workspace` holds osr_linear_split_wgrad_workspace_bytes(m, n, k) the row axis is cut over
+ *                          workgroups and the partial sums are added in cut order; without it one workgroup sums all rows of its
+ *                          tile. No atomics either way: a launch is bitwise reproducible. */
+osr_status osr_split_rows_bf16_t(const float* w, int32_t rows, int32_t cols, void* hi, void* lo, void* stream);
+osr_status osr_linear_split_dgrad(const float* dy, int64_t lddy, const void* wt_hi, const void* wt_lo, const float* mask,
+                                  int64_t ldmask, float* dx, int64_t lddx, int32_t m, int32_t n, int32_t k,
+                                  const int32_t* row_seg_counts, int32_t row_seg_rows, void* stream);
+int64_t osr_linear_split_wgrad_workspace_bytes(int32_t m, int32_t n, int32_t k);
+osr_status osr_linear_split_wgrad(const float* dy, int64_t lddy, const float* x, int64_t ldx, float* dw, int64_t lddw,
+                                  int32_t m, int32_t n, int32_t k, const int32_t* row_seg_counts, int32_t row_seg_rows,
+                                  void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---------------------------------------------------------------------------------------------------------
  * CF-RPN head tail: ClsFreeRPNHead.forward after the 3x3 conv+ReLU (classification_free_rpn.py:159-161):
  * t/max(||t||_2,1e-12) over channels, 1x1 -> 4 ltrb deltas, 1x1 -> centerness, sigmoid.

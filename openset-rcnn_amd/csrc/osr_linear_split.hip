@@ -1,5 +1,6 @@
 // Split-precision fully connected layer (include/osr.h: osr_linear_split_fwd, osr_split_rows_bf16): fp32 rows times fp32 weights
-// at fp32 quality on the bf16 matrix instruction.
+// at fp32 quality on the bf16 matrix instruction. The layer's data gradient (osr_linear_split_dgrad, osr_split_rows_bf16_t) is the same
+// kernel with another epilogue; its weight gradient is csrc/osr_linear_split_bwd.hip.
 //
 // FastRCNNConvFCHead fc1 / fc2 (osrcnn_roi_heads.py:308) with the reference's fp32 operands. Every fp32 value is the sum of
 // two bf16 terms to 2^-17 of its magnitude (bf16 has fp32's exponent range: no scaling, no exponents, no range cases):
@@ -44,8 +45,14 @@ struct LinearSplitArgs {
     long long ldx, ldo;
     int m, n, k, relu;
     int seg_rows, tiles_m, tiles_n, per_xcd;
+    const float* mask;  // DGRAD only (may be null): out is exactly 0 where mask <= 0
+    long long ldmask;
 };
 
+// DGRAD: the same contraction as the data gradient of the layer (osr_linear_split_dgrad): x = dy (m, n_layer), the weight planes those
+// of W^T (k_layer, n_layer), no bias, and the ReLU mask of the layer below in the epilogue. The K loop is the forward's, instruction for
+// instruction.
+template <bool DGRAD>
 __global__ __launch_bounds__(256) void linear_split_kernel(LinearSplitArgs a) {
     constexpr int TM = 2, TN = 2;                     // 32 x 32 accumulator tiles per wave
     constexpr int A_CH = LS_BM * 8 / 256;             // float4 chunks of x per thread per K step (8 per row)
@@ -223,13 +230,23 @@ __global__ __launch_bounds__(256) void linear_split_kernel(LinearSplitArgs a) {
                 const float4 v0 = *reinterpret_cast<const float4*>(slab + row * EPI_LD + cseg);
                 const float4 v1 = *reinterpret_cast<const float4*>(slab + row * EPI_LD + cseg + 4);
                 float v[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-                const float4 b0 = *reinterpret_cast<const float4*>(a.bias + co);
-                const float4 b1 = *reinterpret_cast<const float4*>(a.bias + co + 4);
-                v[0] += b0.x; v[1] += b0.y; v[2] += b0.z; v[3] += b0.w;
-                v[4] += b1.x; v[5] += b1.y; v[6] += b1.z; v[7] += b1.w;
-                if (a.relu) {
+                if constexpr (DGRAD) {
+                    if (a.mask) {  // the saved forward output of the layer below: its ReLU passed nothing where it is <= 0
+                        const float4 k0 = *reinterpret_cast<const float4*>(a.mask + (long long)m * a.ldmask + co);
+                        const float4 k1 = *reinterpret_cast<const float4*>(a.mask + (long long)m * a.ldmask + co + 4);
+                        const float k[8] = {k0.x, k0.y, k0.z, k0.w, k1.x, k1.y, k1.z, k1.w};
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) v[e] = v[e] > 0.f ? v[e] : (v[e] == v[e] ? 0.f : v[e]);  // (a NaN stays a NaN)
+                        for (int e = 0; e < 8; ++e) v[e] = k[e] > 0.f ? v[e] : 0.f;
+                    }
+                } else {
+                    const float4 b0 = *reinterpret_cast<const float4*>(a.bias + co);
+                    const float4 b1 = *reinterpret_cast<const float4*>(a.bias + co + 4);
+                    v[0] += b0.x; v[1] += b0.y; v[2] += b0.z; v[3] += b0.w;
+                    v[4] += b1.x; v[5] += b1.y; v[6] += b1.z; v[7] += b1.w;
+                    if (a.relu) {
+#pragma unroll
+                        for (int e = 0; e < 8; ++e) v[e] = v[e] > 0.f ? v[e] : (v[e] == v[e] ? 0.f : v[e]);  // (a NaN stays a NaN)
+                    }
                 }
                 float* o = a.out + (long long)m * a.ldo + co;
                 *reinterpret_cast<float4*>(o) = make_float4(v[0], v[1], v[2], v[3]);
@@ -260,6 +277,39 @@ extern "C" osr_status osr_split_rows_bf16(const float* w, int32_t rows, int32_t 
     return OSR_OK;
 }
 
+// w (rows, cols) fp32 -> the two bf16 planes of its transpose (cols, rows): 32 x 32 tiles through LDS, both sides coalesced
+__global__ __launch_bounds__(256) void split_rows_bf16_t_kernel(const float* __restrict__ w, bf16_t* __restrict__ hi, bf16_t* __restrict__ lo, int rows, int cols) {
+    __shared__ float tile[32][33];
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    const int r0 = blockIdx.y * 32, c0 = blockIdx.x * 32;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int r = r0 + ty + 8 * i, c = c0 + tx;
+        if (r < rows && c < cols) tile[ty + 8 * i][tx] = w[(long long)r * cols + c];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int c = c0 + ty + 8 * i, r = r0 + tx;
+        if (r < rows && c < cols) {
+            const float v = tile[tx][ty + 8 * i];
+            const bf16_t h = (bf16_t)v;
+            hi[(long long)c * rows + r] = h;
+            lo[(long long)c * rows + r] = (bf16_t)(v - (float)h);
+        }
+    }
+}
+
+extern "C" osr_status osr_split_rows_bf16_t(const float* w, int32_t rows, int32_t cols, void* hi, void* lo, void* stream) {
+    OSR_REQUIRE(w && hi && lo, OSR_ERR_INVALID_ARG, "osr_split_rows_bf16_t: null pointer");
+    OSR_REQUIRE(rows >= 1 && cols >= 1, OSR_ERR_INVALID_ARG, "osr_split_rows_bf16_t: bad shape");
+    OSR_REQUIRE((rows + 31) / 32 <= 65535, OSR_ERR_UNSUPPORTED, "osr_split_rows_bf16_t: too many rows");
+    hipLaunchKernelGGL(split_rows_bf16_t_kernel, dim3((unsigned)((cols + 31) / 32), (unsigned)((rows + 31) / 32)), dim3(256), 0, (hipStream_t)stream, w,
+                       (bf16_t*)hi, (bf16_t*)lo, rows, cols);
+    OSR_CHECK_LAUNCH("osr_split_rows_bf16_t");
+    return OSR_OK;
+}
+
 extern "C" osr_status osr_linear_split_fwd(const osr_linear_split_params* p, const float* x, const void* w_hi, const void* w_lo, const float* bias,
                                            float* out, void* stream) {
     OSR_REQUIRE(p && x && w_hi && w_lo && bias && out, OSR_ERR_INVALID_ARG, "osr_linear_split_fwd: null pointer");
@@ -273,7 +323,7 @@ extern "C" osr_status osr_linear_split_fwd(const osr_linear_split_params* p, con
     OSR_REQUIRE(p->m <= (1 << 30), OSR_ERR_UNSUPPORTED, "osr_linear_split_fwd: m too large");
     LinearSplitArgs a;
     a.x = x; a.w0 = (const bf16_t*)w_hi; a.w1 = (const bf16_t*)w_lo; a.bias = bias; a.out = out;
-    a.seg_counts = p->row_seg_counts; a.seg_rows = p->row_seg_rows;
+    a.seg_counts = p->row_seg_counts; a.seg_rows = p->row_seg_rows; a.mask = nullptr; a.ldmask = 0;
     a.ldx = p->ldx; a.ldo = p->ldo; a.m = p->m; a.n = p->n; a.k = p->k; a.relu = p->relu;
     a.tiles_m = (p->m + LS_BM - 1) / LS_BM;
     a.tiles_n = (p->n + LS_BN - 1) / LS_BN;
@@ -281,8 +331,38 @@ extern "C" osr_status osr_linear_split_fwd(const osr_linear_split_params* p, con
     OSR_REQUIRE(tiles <= (1ll << 30), OSR_ERR_UNSUPPORTED, "osr_linear_split_fwd: problem too large");
     a.per_xcd = (int)((tiles + LS_XCDS - 1) / LS_XCDS);
     static osr_dev_mask mask{0};
-    osr_once_per_device(mask, [] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(linear_split_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LS_LDS); });
-    hipLaunchKernelGGL(linear_split_kernel, dim3((unsigned)(a.per_xcd * LS_XCDS)), dim3(256), LS_LDS, (hipStream_t)stream, a);
+    osr_once_per_device(mask, [] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(linear_split_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, LS_LDS); });
+    hipLaunchKernelGGL(linear_split_kernel<false>, dim3((unsigned)(a.per_xcd * LS_XCDS)), dim3(256), LS_LDS, (hipStream_t)stream, a);
     OSR_CHECK_LAUNCH("osr_linear_split_fwd");
+    return OSR_OK;
+}
+
+// dx (m, k) = (dy (m, n) . W (n, k)) masked: the forward's contraction with dy as the rows and the planes of W^T (k, n) as the weight
+extern "C" osr_status osr_linear_split_dgrad(const float* dy, int64_t lddy, const void* wt_hi, const void* wt_lo, const float* mask, int64_t ldmask,
+                                             float* dx, int64_t lddx, int32_t m, int32_t n, int32_t k, const int32_t* row_seg_counts, int32_t row_seg_rows,
+                                             void* stream) {
+    OSR_REQUIRE(dy && wt_hi && wt_lo && dx, OSR_ERR_INVALID_ARG, "osr_linear_split_dgrad: null pointer");
+    OSR_REQUIRE(m >= 1 && n >= 1 && k >= 1, OSR_ERR_INVALID_ARG, "osr_linear_split_dgrad: bad shape");
+    OSR_REQUIRE(n % 64 == 0, OSR_ERR_UNSUPPORTED, "osr_linear_split_dgrad: n must be a multiple of 64, got %d", n);
+    OSR_REQUIRE(k % 64 == 0, OSR_ERR_UNSUPPORTED, "osr_linear_split_dgrad: k must be a multiple of 64, got %d", k);
+    OSR_REQUIRE(lddy >= n && lddy % 4 == 0 && lddx >= k && lddx % 4 == 0 && (!mask || (ldmask >= k && ldmask % 4 == 0)), OSR_ERR_INVALID_ARG,
+                "osr_linear_split_dgrad: bad leading dimensions");
+    OSR_REQUIRE(!row_seg_counts || row_seg_rows >= 1, OSR_ERR_INVALID_ARG, "osr_linear_split_dgrad: row_seg_rows must be positive with row_seg_counts");
+    OSR_REQUIRE((((uintptr_t)dy | (uintptr_t)wt_hi | (uintptr_t)wt_lo | (uintptr_t)mask | (uintptr_t)dx) & 15) == 0, OSR_ERR_INVALID_ARG,
+                "osr_linear_split_dgrad: pointers must be 16-byte aligned");
+    OSR_REQUIRE(m <= (1 << 30), OSR_ERR_UNSUPPORTED, "osr_linear_split_dgrad: m too large");
+    LinearSplitArgs a;
+    a.x = dy; a.w0 = (const bf16_t*)wt_hi; a.w1 = (const bf16_t*)wt_lo; a.bias = nullptr; a.out = dx;
+    a.seg_counts = row_seg_counts; a.seg_rows = row_seg_rows; a.mask = mask; a.ldmask = ldmask;
+    a.ldx = lddy; a.ldo = lddx; a.m = m; a.n = k; a.k = n; a.relu = 0;  // (the kernel's n is its output width, its k the reduction length)
+    a.tiles_m = (m + LS_BM - 1) / LS_BM;
+    a.tiles_n = (k + LS_BN - 1) / LS_BN;
+    const long long tiles = (long long)a.tiles_m * a.tiles_n;
+    OSR_REQUIRE(tiles <= (1ll << 30), OSR_ERR_UNSUPPORTED, "osr_linear_split_dgrad: problem too large");
+    a.per_xcd = (int)((tiles + LS_XCDS - 1) / LS_XCDS);
+    static osr_dev_mask once{0};
+    osr_once_per_device(once, [] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(linear_split_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, LS_LDS); });
+    hipLaunchKernelGGL(linear_split_kernel<true>, dim3((unsigned)(a.per_xcd * LS_XCDS)), dim3(256), LS_LDS, (hipStream_t)stream, a);
+    OSR_CHECK_LAUNCH("osr_linear_split_dgrad");
     return OSR_OK;
 }

@@ -664,10 +664,15 @@ class OpensetRCNNEngine:
         smp = ops.roi_match_and_sample(prop_boxes, prop_scores, prop_counts, gt_boxes, gt_classes, gt_count, keys_roi,
                                        c["num_classes"], c["roi_batch_size"], c["roi_positive_fraction"], c["roi_iou_threshold"])
         boxes = smp["boxes"].view(-1, 4)
-        pooled = self.pool_rois(feats, boxes, smp["batch_idx"])
+        if self.box_head == "split":  # fp32 pooled rows -> fp32 h1 -> fp32 box features on the split-precision kernel, as in forward()
+            pooled = self.pool_rois(feats, boxes, smp["batch_idx"], out_dtype=torch.float32)
+            h1 = self._linear_split(pooled, self.fc1_split, self.fc1_b, True, name="roi_heads.box_head.fc1")
+            box_feats = self._linear_split(h1, self.fc2_split, self.fc2_b, True, name="roi_heads.box_head.fc2")
+        else:
+            pooled = self.pool_rois(feats, boxes, smp["batch_idx"])
+            h1 = self._linear(pooled, self.fc1_w, self.fc1_b, True, name="roi_heads.box_head.fc1")
+            box_feats = self._linear(h1, self.fc2_w, self.fc2_b, True, torch.float32, name="roi_heads.box_head.fc2")
         m = pooled.shape[0]
-        h1 = self._linear(pooled, self.fc1_w, self.fc1_b, True, name="roi_heads.box_head.fc1")
-        box_feats = self._linear(h1, self.fc2_w, self.fc2_b, True, torch.float32, name="roi_heads.box_head.fc2")
         pred = ops.gemm_f32(box_feats, self.pred_w, self.pred_b)  # (m,5): 4 deltas + IoU logit
         cls, ious = smp["gt_classes"].view(-1), smp["ious"].view(-1)
         lt = loss_types_of(c)

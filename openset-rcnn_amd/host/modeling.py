@@ -839,10 +839,12 @@ class GeneralizedRCNN(_EngineOwner):
         # trainer would treat dataset ids 0..NUM_KNOWN-1 as the known classes
         if self._engine_cls is StandardRCNNEngine:  # the trainer by engine class: Base-RCNN-FPN.yaml's stock heads
             return StandardRCNNTrainer(fold_frozen_bn(sd), self._eng_cfg, self.kernel_dtype, str(self.device), lr=lr, momentum=momentum,
-                                       weight_decay=weight_decay, loss_scale=loss_scale, freeze_at=self._freeze_at, frozen_bn=bn)
+                                       weight_decay=weight_decay, loss_scale=loss_scale, freeze_at=self._freeze_at, frozen_bn=bn,
+                                       box_head=self._box_head_precision())  # ("split" is refused: ValueError, as engine() does)
+        # the trainer's box head multiplies as the model's engine does: a model evaluated with box_head_precision="split" trains that way
         return OpensetRCNNTrainer(fold_frozen_bn(sd), self._eng_cfg, self.kernel_dtype, str(self.device), lr=lr, momentum=momentum,
                                   weight_decay=weight_decay, loss_scale=loss_scale, freeze_at=self._freeze_at, frozen_bn=bn,
-                                  class_map=self._class_map)
+                                  class_map=self._class_map, box_head=self._box_head_precision())
 
     def load_trainer_state(self, trainer, keep_trainer: bool = False) -> None:
         sd = dict(self.state_dict())

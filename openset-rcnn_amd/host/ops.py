@@ -232,14 +232,103 @@ def linear(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, relu: bool
 LINEAR_SPLIT_COUNT = None
 
 
-def split_rows_bf16(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
-    """fp32 (rows, cols) on the GPU -> its two bf16 planes (osr_split_rows_bf16): the same bits as weights.split_fp32_rows."""
+def _split_planes(w: torch.Tensor, shape, out, name: str):
     _need(w, torch.float32, "w")
     if w.dim() != 2 or w.numel() == 0:
-        raise OsrError("split_rows_bf16: a non-empty 2-d matrix")
-    hi, lo = torch.empty_like(w, dtype=torch.bfloat16), torch.empty_like(w, dtype=torch.bfloat16)
+        raise OsrError(f"{name}: a non-empty 2-d matrix")
+    if out is None:
+        return torch.empty(shape, dtype=torch.bfloat16, device=w.device), torch.empty(shape, dtype=torch.bfloat16, device=w.device)
+    hi, lo = out[0], out[1]
+    _need(hi, torch.bfloat16, "out hi"); _need(lo, torch.bfloat16, "out lo")
+    if tuple(hi.shape) != tuple(shape) or tuple(lo.shape) != tuple(shape):
+        raise OsrError(f"{name}: the planes must be {tuple(shape)}")
+    return hi, lo
+
+
+def split_rows_bf16(w: torch.Tensor, out=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """fp32 (rows, cols) on the GPU -> its two bf16 planes (osr_split_rows_bf16): the same bits as weights.split_fp32_rows.
+    out: (hi, lo) to refill in place."""
+    hi, lo = _split_planes(w, tuple(w.shape), out, "split_rows_bf16")
     check(_lib.load().osr_split_rows_bf16(_p(w), w.shape[0], w.shape[1], _p(hi), _p(lo), _stream()), "osr_split_rows_bf16")
     return hi, lo
+
+
+def split_rows_bf16_t(w: torch.Tensor, out=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """fp32 (rows, cols) on the GPU -> the two bf16 planes (cols, rows) of its transpose (osr_split_rows_bf16_t): the weight operand of
+    linear_split_dgrad, the same bits as weights.split_fp32_rows_t. out: (hi, lo) to refill in place."""
+    hi, lo = _split_planes(w, tuple(w.shape[::-1]), out, "split_rows_bf16_t")
+    check(_lib.load().osr_split_rows_bf16_t(_p(w), w.shape[0], w.shape[1], _p(hi), _p(lo), _stream()), "osr_split_rows_bf16_t")
+    return hi, lo
+
+
+# as LINEAR_SPLIT_COUNT, for the two backward kernels: {"launches": 0, "flops": 0.0} counts every osr_linear_split_dgrad /
+# osr_linear_split_wgrad launch and its algorithmic FLOPs (2*m*n*k)
+LINEAR_SPLIT_DGRAD_COUNT = None
+LINEAR_SPLIT_WGRAD_COUNT = None
+
+
+def _row_seg_args(row_seg, m: int):
+    if row_seg is None:
+        return None, 0
+    counts, seg_rows = row_seg
+    _need(counts, torch.int32, "row_seg counts")
+    if seg_rows < 1 or counts.numel() * seg_rows < m:
+        raise OsrError("row_seg does not cover the rows")
+    return counts.data_ptr(), int(seg_rows)
+
+
+def linear_split_dgrad(dy: torch.Tensor, wt_split, mask: Optional[torch.Tensor] = None, row_seg: Optional[Tuple[torch.Tensor, int]] = None,
+                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Data gradient of linear_split at fp32 quality on the bf16 MFMA (osr_linear_split_dgrad): dy (m, n) fp32, wt_split = (hi, lo) the
+    (k, n) bf16 planes of the TRANSPOSED weight (split_rows_bf16_t / weights.split_fp32_rows_t) -> dx (m, k) fp32. mask (m, k) fp32: the
+    saved forward output of the layer below; dx is exactly 0 where it is <= 0. row_seg: as linear_split (rows of skipped tiles are left
+    unwritten)."""
+    hi, lo = wt_split[0], wt_split[1]
+    _need(dy, torch.float32, "dy"); _need(hi, torch.bfloat16, "wt_split hi"); _need(lo, torch.bfloat16, "wt_split lo")
+    if dy.dim() != 2 or hi.dim() != 2 or hi.shape != lo.shape or hi.shape[1] != dy.shape[1] or dy.shape[0] < 1:
+        raise OsrError(f"linear_split_dgrad: dy {tuple(dy.shape)}, transposed weight planes {tuple(hi.shape)} / {tuple(lo.shape)}")
+    (m, n), k = dy.shape, hi.shape[0]
+    if mask is not None:
+        _need(mask, torch.float32, "mask")
+        if tuple(mask.shape) != (m, k):
+            raise OsrError(f"linear_split_dgrad: mask {tuple(mask.shape)} for dx {(m, k)}")
+    if out is None:
+        out = torch.empty((m, k), dtype=torch.float32, device=dy.device)
+    else:
+        _need(out, torch.float32, "out")
+        assert tuple(out.shape) == (m, k)
+    seg_p, seg_rows = _row_seg_args(row_seg, m)
+    check(_lib.load().osr_linear_split_dgrad(_p(dy), n, _p(hi), _p(lo), _p(mask), k, _p(out), k, m, n, k, seg_p, seg_rows, _stream()),
+          "osr_linear_split_dgrad")
+    if LINEAR_SPLIT_DGRAD_COUNT is not None:
+        LINEAR_SPLIT_DGRAD_COUNT["launches"] += 1
+        LINEAR_SPLIT_DGRAD_COUNT["flops"] += 2.0 * m * k * n
+    return out
+
+
+def linear_split_wgrad(x: torch.Tensor, dy: torch.Tensor, dw: Optional[torch.Tensor] = None,
+                       row_seg: Optional[Tuple[torch.Tensor, int]] = None) -> torch.Tensor:
+    """Weight gradient of linear_split at fp32 quality on the bf16 MFMA (osr_linear_split_wgrad): x (m, k), dy (m, n) fp32 ->
+    dW (n, k) = dy^T x fp32, the forward weight's layout. row_seg = (counts, seg_rows): rows at or beyond their segment's count
+    (padding of the per-image lists) contribute nothing, whatever they hold."""
+    lib = _lib.load()
+    _need(x, torch.float32, "x"); _need(dy, torch.float32, "dy")
+    if x.dim() != 2 or dy.dim() != 2 or x.shape[0] != dy.shape[0] or x.shape[0] < 1:
+        raise OsrError(f"linear_split_wgrad: x {tuple(x.shape)}, dy {tuple(dy.shape)}")
+    (m, k), n = x.shape, dy.shape[1]
+    if dw is None:
+        dw = torch.empty((n, k), dtype=torch.float32, device=x.device)
+    else:
+        _need(dw, torch.float32, "dw")
+        assert tuple(dw.shape) == (n, k)
+    seg_p, seg_rows = _row_seg_args(row_seg, m)
+    nb = int(lib.osr_linear_split_wgrad_workspace_bytes(m, n, k))
+    ws = torch.empty((nb,), dtype=torch.uint8, device=x.device) if nb else None
+    check(lib.osr_linear_split_wgrad(_p(dy), n, _p(x), k, _p(dw), k, m, n, k, seg_p, seg_rows, _p(ws), nb, _stream()), "osr_linear_split_wgrad")
+    if LINEAR_SPLIT_WGRAD_COUNT is not None:
+        LINEAR_SPLIT_WGRAD_COUNT["launches"] += 1
+        LINEAR_SPLIT_WGRAD_COUNT["flops"] += 2.0 * m * k * n
+    return dw
 
 
 def linear_split(x: torch.Tensor, w_split, bias: torch.Tensor, relu: bool = False, row_seg: Optional[Tuple[torch.Tensor, int]] = None,

@@ -118,14 +118,28 @@ class OpensetRCNNTrainer:
     def __init__(self, params: Dict[str, torch.Tensor], cfg: Optional[dict] = None, dtype: torch.dtype = torch.float16, device: str = "cuda",
                  lr: float = 0.005, momentum: float = 0.9, weight_decay: float = 1e-4, loss_scale: float = 1024.0, freeze_at: int = 2,
                  frozen_bn: Optional[Dict[str, Tuple[torch.Tensor, torch.Tensor]]] = None, class_map: Optional[torch.Tensor] = None,
-                 bucket_bytes: int = 25 << 20, scale_growth_interval: int = 2000):
+                 bucket_bytes: int = 25 << 20, scale_growth_interval: int = 2000, box_head: str = "storage"):
         """params: BN-folded parameters under detectron2 names (what the engine reads). frozen_bn (optional): for convs followed by
         FrozenBatchNorm, name -> (un-folded weight (cout,cin,kh,kw), per-channel scale gamma/sqrt(var+eps)): the trainable parameter
-        is the un-folded weight (weight decay acts on it, the chain rule multiplies the kernel's gradient by the scale)."""
+        is the un-folded weight (weight decay acts on it, the chain rule multiplies the kernel's gradient by the scale).
+        box_head: how FC1 / FC2 of the box head multiply, forward and backward. "storage" (default): on operands of the storage
+        dtype. "split": the reference's fp32 operands from the RoIAlign output on (OpensetRCNNEngine box_head="split") -- pooled, h1 and
+        box_feats are saved in fp32, the two layers' forward, data gradients and weight gradients run on the split-precision kernels
+        (ops.linear_split, linear_split_dgrad, linear_split_wgrad: three bf16 MFMA products per term, fp32 sums), fc1.w / fc2.w have
+        no low-precision copy: their fp32 masters are re-split into the kernels' bf16 planes after every update."""
         freeze_at = self._check_freeze_at(freeze_at)
+        if box_head not in OpensetRCNNEngine.BOX_HEADS:
+            raise ValueError(f"box_head must be one of {OpensetRCNNEngine.BOX_HEADS}, got {box_head!r}")
+        if box_head != "storage" and not self.SPLIT_BOX_HEAD:
+            raise ValueError(f"box_head_precision {box_head!r}: the stock Faster R-CNN engine keeps its box head")
+        self.box_head = box_head
+        # (tests / diagnostics) set to a dict: _box_head_bwd leaves the gradient it was given (d_bf, a copy) and the one it hands to
+        # RoIAlign's backward (d_pooled) in it
+        self.box_head_probe: Optional[dict] = None
         self.frozen_bn = frozen_bn or {}
         self.row_scale: Dict[str, torch.Tensor] = {}
-        self.eng = self._make_engine(params, cfg, dtype, device, class_map)
+        self.eng = self._make_engine(params, cfg, dtype, device, class_map) if box_head == "storage" else \
+            self._make_engine(params, cfg, dtype, device, class_map, box_head=box_head)
         # the CF-RPN head's backward runs on the sampled anchors only and recomputes their hidden state (osr_rpn_sparse.hip); False:
         # the dense launches of rounds 1-3 (the fused head kernel then also writes the hidden state of every anchor: 0.7 GB)
         self.sparse_rpn_bwd = True
@@ -218,9 +232,11 @@ class OpensetRCNNTrainer:
             raise ValueError(f"freeze_at must be >= 0, got {v}")
         return min(v, 5)
 
+    SPLIT_BOX_HEAD = True  # whether this trainer has the box_head="split" mode (the stock heads' trainer does not)
+
     @staticmethod
-    def _make_engine(params, cfg, dtype, device, class_map):
-        return OpensetRCNNEngine(params, cfg, dtype, device, class_map)
+    def _make_engine(params, cfg, dtype, device, class_map, box_head: str = "storage"):
+        return OpensetRCNNEngine(params, cfg, dtype, device, class_map, box_head=box_head)
 
     def _add_head_masters(self, params) -> None:
         """The masters behind the RPN head's 3x3 conv: CF-RPN tail, box head, predictor, PLN, classifier (in this order: see __init__)."""
@@ -229,11 +245,13 @@ class OpensetRCNNTrainer:
         self.master["rpn_tail.w"], self.master["rpn_tail.b"] = e.rpn_wtail, e.rpn_btail  # (5,256): 4 ltrb rows + centerness
         e.rpn_wd, e.rpn_wc, e.rpn_bd, e.rpn_bc = e.rpn_wtail[:4], e.rpn_wtail[4:5], e.rpn_btail[:4], e.rpn_btail[4:5]  # views: one storage
         self.master["fc1.w"] = pack_fc1_weight(params["roi_heads.box_head.fc1.weight"], 256, e.cfg["pooler_resolution"], torch.float32).to(dev)
-        self.lowp["fc1.w"] = e.fc1_w
         self.master["fc1.b"] = e.fc1_b
         self.master["fc2.w"] = f32(params["roi_heads.box_head.fc2.weight"])
-        self.lowp["fc2.w"] = e.fc2_w
         self.master["fc2.b"] = e.fc2_b
+        if self.box_head != "split":  # (split: no low-precision copy -- the kernels read the masters' bf16 planes, see _resplit_box_head)
+            self.lowp["fc1.w"], self.lowp["fc2.w"] = e.fc1_w, e.fc2_w
+        else:
+            e.fc1_w = e.fc2_w = None  # (nothing refreshes the engine's storage-dtype copies in this mode, and nothing reads them)
         self.master["pred.w"], self.master["pred.b"] = e.pred_w, e.pred_b
         self.master["enc.w"], self.master["enc.b"] = e.enc_w, e.enc_b
         self.master["dec.w"], self.master["dec.b"] = e.dec_w, e.dec_b
@@ -295,14 +313,23 @@ class OpensetRCNNTrainer:
         normalised prototypes."""
         e = self.eng
         wd = getattr(self, "wd", None)
+        split = self.box_head == "split"
+        if split and wd is not None:
+            # the forward planes are read by the NEXT FORWARD: they are re-split on the main stream, behind the update
+            ops.split_rows_bf16(self.master["fc1.w"], out=e.fc1_split)
+            ops.split_rows_bf16(self.master["fc2.w"], out=e.fc2_split)
         if wd is None:  # first call: allocate the buffers (on the main stream); they are refilled in place every step (osr_pack_dgrad_weight)
             wd = {n: ops.pack_dgrad_weight(e.w[n + ".w"]) for n in self.conv_names}
-            wd["fc1"] = ops.pack_dgrad_weight(e.fc1_w).view(e.fc1_w.shape[1], 1, 1, e.fc1_w.shape[0])
-            wd["fc2"] = ops.pack_dgrad_weight(e.fc2_w).view(e.fc2_w.shape[1], 1, 1, e.fc2_w.shape[0])
+            if split:  # the data gradients' operand: the bf16 planes of the transposed fp32 masters
+                self.wt_split = {"fc1": ops.split_rows_bf16_t(self.master["fc1.w"]), "fc2": ops.split_rows_bf16_t(self.master["fc2.w"])}
+            else:
+                wd["fc1"] = ops.pack_dgrad_weight(e.fc1_w).view(e.fc1_w.shape[1], 1, 1, e.fc1_w.shape[0])
+                wd["fc2"] = ops.pack_dgrad_weight(e.fc2_w).view(e.fc2_w.shape[1], 1, 1, e.fc2_w.shape[0])
             self.wd = wd
         elif self.multi_tensor_update:
             pairs = [(e.w[n + ".w"], wd[n]) for n in self.conv_names]
-            pairs += [(e.fc1_w, wd["fc1"].view(e.fc1_w.shape[1], e.fc1_w.shape[0])), (e.fc2_w, wd["fc2"].view(e.fc2_w.shape[1], e.fc2_w.shape[0]))]
+            if not split:
+                pairs += [(e.fc1_w, wd["fc1"].view(e.fc1_w.shape[1], e.fc1_w.shape[0])), (e.fc2_w, wd["fc2"].view(e.fc2_w.shape[1], e.fc2_w.shape[0]))]
             sig = tuple(t.data_ptr() for pr in pairs for t in pr)
             if self._pack_plan is None or self._pack_plan[0] != sig:
                 self._pack_plan = (sig, ops.pack_dgrad_multi_plan(pairs, self.device))
@@ -313,16 +340,29 @@ class OpensetRCNNTrainer:
                 self._wside.wait_stream(torch.cuda.current_stream(self.device))
                 with torch.cuda.stream(self._wside):
                     ops.pack_dgrad_weight_multi_(self._pack_plan[1])
+                    if split:
+                        self._resplit_transposed()
                     self._pack_done = self._wside.record_event()
             else:
                 ops.pack_dgrad_weight_multi_(self._pack_plan[1])
+                if split:
+                    self._resplit_transposed()
                 self._pack_done = None
         else:
             jobs = [lambda n=n: ops.pack_dgrad_weight(e.w[n + ".w"], wd[n]) for n in self.conv_names]
-            jobs.append(lambda: ops.pack_dgrad_weight(e.fc1_w, wd["fc1"].view(e.fc1_w.shape[1], e.fc1_w.shape[0])))
-            jobs.append(lambda: ops.pack_dgrad_weight(e.fc2_w, wd["fc2"].view(e.fc2_w.shape[1], e.fc2_w.shape[0])))
+            if split:
+                jobs.append(self._resplit_transposed)
+            else:
+                jobs.append(lambda: ops.pack_dgrad_weight(e.fc1_w, wd["fc1"].view(e.fc1_w.shape[1], e.fc1_w.shape[0])))
+                jobs.append(lambda: ops.pack_dgrad_weight(e.fc2_w, wd["fc2"].view(e.fc2_w.shape[1], e.fc2_w.shape[0])))
             self._fan(jobs)
         self._refresh_heads()
+
+    def _resplit_transposed(self) -> None:
+        """box_head="split": the transposed bf16 planes of fc1.w / fc2.w (what the NEXT BACKWARD's data gradients read) from the
+        updated fp32 masters, in place."""
+        ops.split_rows_bf16_t(self.master["fc1.w"], out=self.wt_split["fc1"])
+        ops.split_rows_bf16_t(self.master["fc2.w"], out=self.wt_split["fc2"])
 
     def _refresh_heads(self) -> None:
         """The derived tensors of the heads: transposed fp32 heads, normalised prototypes."""
@@ -673,19 +713,34 @@ class OpensetRCNNTrainer:
         """d box features (m,1024) fp32 -> FC2, FC1 (data + weight gradients) -> RoIAlign backward: the feature gradient per level."""
         c, g, dt = self.eng.cfg, self.grad, self.dtype
         p = s["p"]
+        if self.box_head_probe is not None:
+            self.box_head_probe["d_bf"] = d_bf.clone()
         ops.relu_mask_(d_bf, s["box_feats"])
-        dy2 = ops.add_cast(d_bf, None, dt)                                                  # (m,1024) low precision
-        m = dy2.shape[0]
-        # --- box head: FC2, FC1 on the MFMA kernels ---
-        d_h1 = ops.conv2d_dgrad(dy2.view(1, m, 1, -1), self.wd["fc2"], (m, 1), mask=s["h1"].view(1, m, 1, -1)).view(m, -1)
-        self._wg(lambda: (ops.conv2d_wgrad(s["h1"].view(1, m, 1, -1), dy2.view(1, m, 1, -1), 1, 1, dw=g["fc2.w"].view(-1, 1, 1, g["fc2.w"].shape[1])),
-                          ops.bias_grad(dy2, g["fc2.b"])), dy2)
-        self._done("fc2.w", "fc2.b")
-        pooled2 = s["pooled"].view(1, m, 1, -1)
-        d_pooled = ops.conv2d_dgrad(d_h1.view(1, m, 1, -1), self.wd["fc1"], (m, 1))
-        self._wg(lambda: (ops.conv2d_wgrad(pooled2, d_h1.view(1, m, 1, -1), 1, 1, dw=g["fc1.w"].view(-1, 1, 1, g["fc1.w"].shape[1])),
-                          ops.bias_grad(d_h1, g["fc1.b"])), d_h1)
-        self._done("fc1.w", "fc1.b")
+        m = d_bf.shape[0]
+        if self.box_head == "split":
+            # --- box head in fp32 operands: no cast of d_bf; FC2, FC1 on the split-precision kernels (the ReLU mask of h1 in the data
+            #     gradient's epilogue), weight / bias gradients from the fp32 rows on the second stream ---
+            d_h1 = ops.linear_split_dgrad(d_bf, self.wt_split["fc2"], mask=s["h1"])
+            self._wg(lambda: (ops.linear_split_wgrad(s["h1"], d_bf, dw=g["fc2.w"]), ops.bias_grad(d_bf, g["fc2.b"])), d_bf)
+            self._done("fc2.w", "fc2.b")
+            pooled2 = s["pooled"].view(m, -1)
+            d_pooled = ops.linear_split_dgrad(d_h1, self.wt_split["fc1"])  # fp32: RoIAlign's backward sums it in fp32, _roi_share casts
+            self._wg(lambda: (ops.linear_split_wgrad(pooled2, d_h1, dw=g["fc1.w"]), ops.bias_grad(d_h1, g["fc1.b"])), d_h1)
+            self._done("fc1.w", "fc1.b")
+        else:
+            dy2 = ops.add_cast(d_bf, None, dt)                                                  # (m,1024) low precision
+            # --- box head: FC2, FC1 on the MFMA kernels ---
+            d_h1 = ops.conv2d_dgrad(dy2.view(1, m, 1, -1), self.wd["fc2"], (m, 1), mask=s["h1"].view(1, m, 1, -1)).view(m, -1)
+            self._wg(lambda: (ops.conv2d_wgrad(s["h1"].view(1, m, 1, -1), dy2.view(1, m, 1, -1), 1, 1, dw=g["fc2.w"].view(-1, 1, 1, g["fc2.w"].shape[1])),
+                              ops.bias_grad(dy2, g["fc2.b"])), dy2)
+            self._done("fc2.w", "fc2.b")
+            pooled2 = s["pooled"].view(1, m, 1, -1)
+            d_pooled = ops.conv2d_dgrad(d_h1.view(1, m, 1, -1), self.wd["fc1"], (m, 1))
+            self._wg(lambda: (ops.conv2d_wgrad(pooled2, d_h1.view(1, m, 1, -1), 1, 1, dw=g["fc1.w"].view(-1, 1, 1, g["fc1.w"].shape[1])),
+                              ops.bias_grad(d_h1, g["fc1.b"])), d_h1)
+            self._done("fc1.w", "fc1.b")
+        if self.box_head_probe is not None:
+            self.box_head_probe["d_pooled"] = d_pooled
         P = c["pooler_resolution"]
         shapes = [(p[k].shape[1], p[k].shape[2]) for k in PYRAMID[:4]]
         d_feat = ops.roi_align_bwd(d_pooled.view(m, P, P, -1), shapes, n, c["pooler_scales"], s["boxes"], s["smp"]["batch_idx"], c["canonical_level"],

@@ -38,6 +38,8 @@ class StandardRCNNTrainer(OpensetRCNNTrainer):
     anchor_deltas] (5A,256) + (5A) (one storage the engine's two GEMMs read as views), fc1, fc2, "box" (bbox_pred), "cls" (cls_score)
     -- reverse order of gradient completion, as the base class lays them out."""
 
+    SPLIT_BOX_HEAD = False  # (box_head="split" is refused with the stock engine's ValueError)
+
     @staticmethod
     def _make_engine(params, cfg, dtype, device, class_map):
         eng = StandardRCNNEngine(params, cfg, dtype, device)

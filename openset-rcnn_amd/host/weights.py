@@ -115,6 +115,12 @@ def split_fp32_rows(w: torch.Tensor):
     return hi, lo, None
 
 
+def split_fp32_rows_t(w: torch.Tensor):
+    """split_fp32_rows of the transpose: (rows, cols) fp32 -> the planes (cols, rows) that the split-precision data gradient reads
+    (ops.linear_split_dgrad; ops.split_rows_bf16_t gives the same bits on the GPU). Returns (hi, lo, None)."""
+    return split_fp32_rows(w.detach().to(torch.float32).t().contiguous())
+
+
 def pack_dgrad_weight(w: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
     """(cout,cin,kh,kw) -> (cin,kh,kw,cout), spatially flipped: the backward-data pass of a stride-1 convolution is the
     forward convolution of dy with these weights and padding k-1-pad; for a 1x1 layer it is the transposed matrix."""
