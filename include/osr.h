@@ -269,6 +269,29 @@ osr_status osr_linear_split_wgrad(const float* dy, int64_t lddy, const float* x,
                                   void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * Split-precision convolution: the Conv2d / FrozenBatchNorm2d (folded) layers of build_resnet_fpn_backbone and
+ * ClsFreeRPNHead.conv (classification_free_rpn.py:158) with the reference's fp32 operands, on the bf16 matrix instruction.
+ * The implicit GEMM of osr_conv2d_fwd with the arithmetic of osr_linear_split_fwd: in, out and residual are fp32 NHWC
+ * (p->in_dtype and p->out_dtype must be OSR_F32), w_hi / w_lo are the two bf16 planes of the [cout][kh][kw][cin] fp32 weight
+ * (osr_split_rows_bf16 / host/weights.py split_fp32_rows on its (cout, kh*kw*cin) matrix). The activations are split on their
+ * way to the matrix cores, x0 = bf16(x), x1 = bf16(x - x0), and every K step sums x0 w1 + x1 w0 + x0 w0 into one fp32
+ * accumulator; the x1 w1 term is dropped. Strides, padding, pad_mode, relu and res_mode mean what they mean for osr_conv2d_fwd
+ * with fp32 operands; concurrency, workspace and row_seg_* are ignored.
+ * Shapes: cin a multiple of 32, cout of 64; 1x1 and 3x3 kernels (pad < kernel size) at stride 1 or 2 with pad_mode 0, or the stem's
+ * (kh = 8, kw = 1, cin = 32, stride 2, pad_mode 1) view of the pre-padded NHWC4 image osr_preprocess writes in fp32; any
+ * n*ho*wo >= 1. Anything else returns OSR_ERR_UNSUPPORTED with nothing launched. Strides are multiples of 4 elements and all
+ * pointers 16-byte aligned (OSR_ERR_INVALID_ARG otherwise).
+ * A tap outside the image contributes exactly zero. One workgroup sums the whole K axis of its output tile in order (no
+ * split-K, no atomics): a launch is bitwise reproducible and an output pixel's bits do not depend on the batch size. The
+ * library allocates nothing. Non-finite inputs: an Inf or NaN in an input pixel makes every output pixel that reads it
+ * non-finite, one in a weight row that output channel, and so does a finite value beyond bf16's largest (about 3.39e38),
+ * whose leading term rounds to Inf; which elements exactly become Inf and which NaN is not specified. ReLU maps a NaN to 0,
+ * as the fp32 kernel's does.
+ * --------------------------------------------------------------------------------------------------------- */
+osr_status osr_conv2d_split_fwd(const osr_conv_params* p, const float* in, const void* w_hi, const void* w_lo,
+                                const float* bias, const float* residual, float* out, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * CF-RPN head tail: ClsFreeRPNHead.forward after the 3x3 conv+ReLU (classification_free_rpn.py:159-161):
  * t/max(||t||_2,1e-12) over channels, 1x1 -> 4 ltrb deltas, 1x1 -> centerness, sigmoid.
  * t: (rows, c) channels-last hidden state; w_delta (4,c), w_ctr (1,c) fp32. Outputs fp32.

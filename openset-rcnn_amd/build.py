@@ -26,6 +26,7 @@ SOURCES = {
     "osr_conv_f32.hip": [],
     "osr_linear_split.hip": [],
     "osr_linear_split_bwd.hip": [],
+    "osr_conv_split.hip": [],
     "osr_bottleneck.hip": [],
     "osr_stem_pool.hip": [],
     "osr_rpn.hip": ["-ffp-contract=off"],

@@ -132,6 +132,7 @@ PROTOTYPES = {
     "osr_gemm_f32_tn": (I32, [P, I64, P, I64, P, I64, I32, I32, I32, P, I64, P]),
     "osr_split_rows_bf16": (I32, [P, I32, I32, P, P, P]),
     "osr_linear_split_fwd": (I32, [C.POINTER(LinearSplitParams), P, P, P, P, P, P]),
+    "osr_conv2d_split_fwd": (I32, [C.POINTER(ConvParams), P, P, P, P, P, P, P]),
     "osr_split_rows_bf16_t": (I32, [P, I32, I32, P, P, P]),
     "osr_linear_split_dgrad": (I32, [P, I64, P, P, P, I64, P, I64, I32, I32, I32, P, I32, P]),
     "osr_linear_split_wgrad_workspace_bytes": (I64, [I32, I32, I32]),

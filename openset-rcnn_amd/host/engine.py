@@ -17,7 +17,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import torch
 
 from . import ops
-from .weights import R50_BLOCKS, pack_conv_weight, pack_fc1_weight, pack_stem_weight, split_fp32_rows
+from .weights import R50_BLOCKS, pack_conv_weight, pack_fc1_weight, pack_stem_weight, split_conv_weight, split_fp32_rows, split_stem_weight
 
 BOTTOM_UP = "backbone.bottom_up"
 STEM = BOTTOM_UP + ".stem.conv1"
@@ -78,13 +78,16 @@ class OpensetRCNNEngine:
     """dtype: storage type of activations and MFMA operands. torch.float16 / torch.bfloat16 = the fast path (fp32 accumulation,
     fp32 heads from the box features on). torch.float32 = PARITY MODE: every tensor and every product in fp32 (osr_conv_f32.hip,
     1/16 of the fp16 matrix rate), the arithmetic the reference itself runs in -- boxes, scores and embeddings then agree with the
-    fp32 oracle to summation order (tests/test_e2e_parity.py)."""
+    fp32 oracle to summation order (tests/test_e2e_parity.py). torch.float32 with conv="split" = the SPLIT PARITY MODE: the same fp32
+    storage and the same 1e-4 contract with the convolutions and FC1 / FC2 on the bf16 matrix instruction (osr_conv_split.hip)."""
 
     FP32_POINTS = ("backbone", "rpn_hidden", "pooled", "h1")
     BOX_HEADS = ("storage", "split")
+    CONVS = ("storage", "split")
 
     def __init__(self, params: Dict[str, torch.Tensor], cfg: Optional[dict] = None, dtype: torch.dtype = torch.float16,
-                 device: str = "cuda", class_map: Optional[torch.Tensor] = None, fp32_points: Sequence[str] = (), box_head: str = "storage"):
+                 device: str = "cuda", class_map: Optional[torch.Tensor] = None, fp32_points: Sequence[str] = (), box_head: str = "storage",
+                 conv: str = "storage"):
         """fp32_points (diagnostic; fast mode only): storage points of the fp16 path kept in fp32 instead, to measure what each one
         costs in agreement with the fp32 reference (tests/test_e2e_parity.py): "backbone" (stem .. FPN outputs computed by the
         fp32 kernels, the pyramid handed on in fp16), "rpn_hidden" (the CF-RPN hidden state: un-fused head, fp32 t), "pooled"
@@ -94,14 +97,25 @@ class OpensetRCNNEngine:
         "split" (fp16 / bf16 engines): the reference's fp32 arithmetic from the RoIAlign output on at a usable rate -- RoIAlign
         writes fp32 rows, FC1 and FC2 run on the split-precision kernel (ops.linear_split: fp32 rows and fp32 weights as two bf16
         terms each, three bf16 MFMA products, fp32 sums; the terms are bf16 whatever the storage dtype is) and h1 stays fp32.
-        It replaces the "pooled" / "h1" points, so it is refused together with them and with dtype=float32 (ValueError)."""
+        It replaces the "pooled" / "h1" points, so it is refused together with them and with dtype=float32 (ValueError).
+        conv: how the convolutions multiply. "storage" (default): in the storage dtype. "split" (dtype=float32 only, ValueError
+        otherwise): fp32 storage as in the parity mode, with every backbone / FPN convolution, the stem and the CF-RPN head's 3x3 on
+        the split-precision kernel (ops.conv2d_split / ops.stem_conv_split: fp32 activations and fp32 weights as two bf16 terms each,
+        three bf16 MFMA products, fp32 sums) and FC1 / FC2 on ops.linear_split; these layers keep their weights as bf16 planes only.
+        Everything else is the parity mode's."""
         if box_head not in self.BOX_HEADS:
             raise ValueError(f"box_head must be one of {self.BOX_HEADS}, got {box_head!r}")
         if box_head == "split" and dtype == torch.float32:
             raise ValueError('box_head="split" is a mode of the fp16 / bf16 engines: dtype=float32 already computes the box head in fp32')
         if box_head == "split" and set(fp32_points) & {"pooled", "h1"}:
             raise ValueError('box_head="split" replaces the "pooled" / "h1" fp32 points: ask for one or the other')
+        if conv not in self.CONVS:
+            raise ValueError(f"conv must be one of {self.CONVS}, got {conv!r}")
+        if conv == "split" and dtype != torch.float32:
+            raise ValueError('conv="split" is a mode of the fp32 engine (dtype=float32): the fp16 / bf16 engines multiply in their storage dtype')
         self.box_head = box_head
+        self.conv = conv
+        self.split_head = box_head == "split" or conv == "split"  # FC1 / FC2 on ops.linear_split, fp32 rows in and out
         self.cfg = dict(DEFAULT_CFG)
         if cfg:
             self.cfg.update(cfg)
@@ -131,7 +145,7 @@ class OpensetRCNNEngine:
         self.profile_hbm = None  # set to a list to collect (name, algorithmic bytes, start event, end event, info) of the HBM-group kernels
         # the box head's FC layers skip the tiles that hold only padding rows of the per-image proposal lists (fp16 / bf16 kernels;
         # the fp32 parity kernel computes every row)
-        self.skip_padding_tiles = dtype != torch.float32
+        self.skip_padding_tiles = dtype != torch.float32 or conv == "split"
         # the three (four) convolutions of a res2 block run as ONE launch (osr_bottleneck_fwd): fp16 / bf16 storage only
         self.fuse_res2 = dtype != torch.float32
         # conv2 -> conv3 + shortcut of a res3 block run as ONE launch (osr_conv2d_chain_fwd: conv2's output stays in LDS)
@@ -146,14 +160,17 @@ class OpensetRCNNEngine:
 
     def _pack_convs(self, params) -> Dict[str, torch.Tensor]:
         """Every 4-d conv weight (backbone, FPN, RPN 3x3) repacked to [cout][kh][kw][cin] in the storage dtype + its fp32 bias; the
-        1x1 output convs of the RPN heads stay fp32 matrices (handled by _init_rpn)."""
+        1x1 output convs of the RPN heads stay fp32 matrices (handled by _init_rpn). conv="split": the weight is its pair of bf16 planes
+        (hi, lo) instead, and no fp32 copy is kept."""
         w: Dict[str, torch.Tensor] = {}
         dev, dtype = self.device, self.dtype
         for k, v in params.items():
             if not k.endswith(".weight") or v.dim() != 4 or (k.startswith("proposal_generator.rpn_head.") and not k.startswith("proposal_generator.rpn_head.conv.")):
                 continue
             pre = k[: -len(".weight")]
-            if pre == STEM:
+            if self.conv == "split":
+                w[pre + ".w"] = tuple(t.to(dev) for t in (split_stem_weight(v) if pre == STEM else split_conv_weight(v)))
+            elif pre == STEM:
                 w[pre + ".w"] = pack_stem_weight(v, dtype).to(dev)
             else:
                 w[pre + ".w"] = pack_conv_weight(v, dtype).to(dev)
@@ -185,11 +202,13 @@ class OpensetRCNNEngine:
             return
         fc1_dt = torch.float32 if "pooled" in self.fp32_points else dtype
         fc2_dt = torch.float32 if "h1" in self.fp32_points else dtype
-        self.fc1_w = pack_fc1_weight(params["roi_heads.box_head.fc1.weight"], 256, c["pooler_resolution"], fc1_dt).to(dev)
+        self.fc1_w = self.fc2_w = None
+        if self.conv != "split":  # (the split parity mode keeps FC1 / FC2 as bf16 planes only)
+            self.fc1_w = pack_fc1_weight(params["roi_heads.box_head.fc1.weight"], 256, c["pooler_resolution"], fc1_dt).to(dev)
+            self.fc2_w = params["roi_heads.box_head.fc2.weight"].to(fc2_dt).contiguous().to(dev)
         self.fc1_b = params["roi_heads.box_head.fc1.bias"].float().to(dev)
-        self.fc2_w = params["roi_heads.box_head.fc2.weight"].to(fc2_dt).contiguous().to(dev)
         self.fc2_b = params["roi_heads.box_head.fc2.bias"].float().to(dev)
-        if self.box_head == "split":  # the fp32 weights as two bf16 planes each, split once (FC1 in RoIAlign's K order)
+        if self.split_head:  # the fp32 weights as two bf16 planes each, split once (FC1 in RoIAlign's K order)
             w1 = pack_fc1_weight(params["roi_heads.box_head.fc1.weight"], 256, c["pooler_resolution"], torch.float32)
             self.fc1_split = tuple(t.to(dev) for t in split_fp32_rows(w1)[:2])
             self.fc2_split = tuple(t.to(dev) for t in split_fp32_rows(params["roi_heads.box_head.fc2.weight"])[:2])
@@ -203,6 +222,8 @@ class OpensetRCNNEngine:
     # ---- backbone -------------------------------------------------------------------------------------------
     def _conv(self, x, name, stride=1, pad=0, relu=False, residual=None, res_mode=0, out=None, out_dtype=None):
         w = self.w[name + ".w"]
+        if self.conv == "split":
+            return self._conv_split(x, name, w, stride, pad, relu, residual, res_mode, out)
 
         def cost(y):
             rows = y.numel() // w.shape[0]
@@ -211,6 +232,17 @@ class OpensetRCNNEngine:
             flops = 2.0 * rows * w.shape[0] * w.shape[1] * w.shape[2] * w.shape[3]
             return flops, nbytes, flops
         return self._timed(name, lambda: ops.conv2d(x, w, self.w[name + ".b"], stride, pad, relu, residual, res_mode, out_dtype, out), cost)
+
+    def _conv_split(self, x, name, w_split, stride, pad, relu, residual, res_mode, out):
+        """_conv on the split-precision kernel: fp32 in, fp32 out. The credited FLOPs are the layer's (one product per element pair),
+        not the three bf16 products the kernel spends on each; the weight bytes are the two bf16 planes."""
+        hi = w_split[0]
+
+        def cost(y):
+            flops = 2.0 * (y.numel() // hi.shape[0]) * hi.numel()
+            nbytes = (x.numel() + y.numel() + hi.numel() + (residual.numel() if residual is not None else 0)) * 4
+            return flops, nbytes, flops
+        return self._timed(name + " (split)", lambda: ops.conv2d_split(x, w_split, self.w[name + ".b"], stride, pad, relu, residual, res_mode, out), cost)
 
     def _bottleneck(self, x, pre: str, first: bool, stride: int = 1, save: Optional[list] = None, chain: Optional[bool] = None):
         """One [d2] BottleneckBlock (conv1 1x1 -> conv2 3x3 -> conv3 1x1 + shortcut, ReLU after each). res2's blocks run as one
@@ -294,6 +326,10 @@ class OpensetRCNNEngine:
                             lambda x: (2.0 * stem_px * 147, images.numel() * images.element_size() + x.numel() * 2, 2.0 * stem_px * 147))  # 7*7*3 real taps of every stem pixel
             return x, None, None
         xpad = ops.preprocess(images, hp, wp, mean, std, self.dtype)
+        if self.conv == "split":
+            stem = self._timed(STEM + " (split)", lambda: ops.stem_conv_split(xpad, sw, sb, hp, wp, relu=True),
+                               lambda x: (2.0 * x.numel() * 147, xpad.numel() * 4 + x.numel() * 4, 2.0 * x.numel() * 147))  # 7*7*3 real taps
+            return ops.maxpool3x3s2(stem), xpad, stem
         stem = self._timed(STEM, lambda: ops.stem_conv(xpad, sw, sb, hp, wp, relu=True),
                            lambda x: (2.0 * x.numel() * 147, xpad.numel() * 2 + x.numel() * 2, 2.0 * x.numel() * 147))  # 7*7*3 real taps
         return ops.maxpool3x3s2(stem), xpad, stem
@@ -484,7 +520,7 @@ class OpensetRCNNEngine:
                 _real.append(int(sel["counts"].sum()))
             return _real[0]
         row_b = c["pooler_resolution"] ** 2 * 256 * es + 20
-        split = self.box_head == "split"
+        split = self.split_head
         pooled_dt = torch.float32 if split or "pooled" in self.fp32_points else self.dtype
         h1_dt = torch.float32 if self.fp32_points & {"pooled", "h1"} else None  # (the fp32 kernel writes fp32 only)
         # (the padding rows of the per-image lists are not zero-filled unless `keep` hands the pooled rows out: the box head skips the
@@ -659,6 +695,8 @@ class OpensetRCNNEngine:
         """OpensetROIHeads.label_and_sample_proposals + _forward_box in training mode (osrcnn_roi_heads.py:137-230,282-318):
         proposals are fixed inputs (predict_proposals runs under no_grad, classification_free_rpn.py:575). Returns (losses of the
         four heads as a dict of GPU scalars + 'roi_counts', state dict with every activation the backward reads)."""
+        if self.conv == "split":
+            raise ValueError('conv="split" is an inference mode: the training forward needs conv="storage"')
         check_supported_losses(self.cfg)
         c = self.cfg
         smp = ops.roi_match_and_sample(prop_boxes, prop_scores, prop_counts, gt_boxes, gt_classes, gt_count, keys_roi,

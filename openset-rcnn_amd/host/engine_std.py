@@ -40,7 +40,10 @@ def cell_anchor_table(sizes, ratios) -> torch.Tensor:
 
 
 class StandardRCNNEngine(OpensetRCNNEngine):
-    def __init__(self, params: Dict[str, torch.Tensor], cfg: Optional[dict] = None, dtype: torch.dtype = torch.float16, device: str = "cuda"):
+    def __init__(self, params: Dict[str, torch.Tensor], cfg: Optional[dict] = None, dtype: torch.dtype = torch.float16, device: str = "cuda",
+                 conv: str = "storage"):
+        if conv != "storage":
+            raise ValueError(f"conv {conv!r}: the stock Faster R-CNN engine multiplies in its storage dtype (conv=\"storage\")")
         full = dict(STD_DEFAULT_CFG)
         if cfg:
             full.update(cfg)

@@ -128,6 +128,9 @@ class _EngineOwner(nn.Module):
         # how the box head's FC1 / FC2 multiply (OpensetRCNNEngine box_head): "storage", or "split" = fp32 operands as bf16 terms.
         # An attribute, not a yaml key: the reference's config files load unchanged
         self.box_head_precision = "storage"
+        # how the convolutions multiply (OpensetRCNNEngine conv): "storage", or "split" = the fp32 parity mode (kernel_dtype float32)
+        # on the bf16 matrix instruction. An attribute, not a yaml key, like box_head_precision
+        self.conv_precision = "storage"
 
     def engine(self) -> OpensetRCNNEngine:
         if self._shared is not None:
@@ -135,6 +138,11 @@ class _EngineOwner(nn.Module):
         want = self._box_head_precision()
         if self._eng is not None and getattr(self._eng, "box_head", "storage") != want:
             self._eng = None  # (box_head_precision was changed after the engine was packed)
+        conv = self.conv_precision
+        if self._eng is not None and getattr(self._eng, "conv", "storage") != conv:
+            self._eng = None  # (so was conv_precision)
+        if conv == "split" and self.kernel_dtype != torch.float32:
+            raise ValueError('conv_precision "split" needs kernel_dtype == torch.float32: it is a mode of the fp32 engine')
         if self._eng is None:
             sd = {self._prefix + k: v.detach() for k, v in self.state_dict().items()}
             dev = next(iter(sd.values())).device
@@ -142,11 +150,11 @@ class _EngineOwner(nn.Module):
                 raise ops.OsrError("the model must be on the GPU (model.to('cuda')): the HIP path has no CPU fallback")
             sd = fold_frozen_bn({k: v.cpu() for k, v in sd.items()})
             if self._engine_cls is OpensetRCNNEngine:
-                self._eng = OpensetRCNNEngine(sd, self._eng_cfg, self.kernel_dtype, str(dev), self._class_map, box_head=want)
+                self._eng = OpensetRCNNEngine(sd, self._eng_cfg, self.kernel_dtype, str(dev), self._class_map, box_head=want, conv=conv)
             else:
                 if want != "storage":
                     raise ValueError(f"box_head_precision {want!r}: the stock Faster R-CNN engine keeps its box head")
-                self._eng = self._engine_cls(sd, self._eng_cfg, self.kernel_dtype, str(dev))
+                self._eng = self._engine_cls(sd, self._eng_cfg, self.kernel_dtype, str(dev), conv=conv)  # ("split" is refused: ValueError)
         return self._eng
 
     def _box_head_precision(self) -> str:
@@ -826,6 +834,8 @@ class GeneralizedRCNN(_EngineOwner):
         `load_trainer_state(trainer)` writes them back into the module for evaluation / checkpointing."""
         from .train import OpensetRCNNTrainer
         from .train_std import StandardRCNNTrainer
+        if self.conv_precision != "storage":
+            raise ValueError(f"conv_precision {self.conv_precision!r}: the split-precision convolutions are an inference mode; set it back to \"storage\" to train")
         if self.device.type != "cuda":
             raise ops.OsrError("the model must be on the GPU (model.to('cuda')): the HIP path has no CPU fallback")
         sd = {k: v.detach().cpu() for k, v in self.state_dict().items()}

@@ -363,6 +363,89 @@ def linear_split(x: torch.Tensor, w_split, bias: torch.Tensor, relu: bool = Fals
     return out
 
 
+# as LINEAR_SPLIT_COUNT, for the split-precision convolution: {"launches": 0, "flops": 0.0} counts every osr_conv2d_split_fwd launch and
+# the layer's algorithmic FLOPs (2 * pixels * cout * kh*kw*cin; 147 real taps per output for the stem)
+CONV_SPLIT_COUNT = None
+
+
+def _conv_split_planes(w_split, name: str):
+    hi, lo = w_split[0], w_split[1]
+    _need(hi, torch.bfloat16, name + " hi"); _need(lo, torch.bfloat16, name + " lo")
+    if hi.dim() != 4 or hi.shape != lo.shape:
+        raise OsrError(f"{name}: two (cout,kh,kw,cin) bf16 planes, got {tuple(hi.shape)} / {tuple(lo.shape)}")
+    return hi, lo
+
+
+def conv2d_split(x: torch.Tensor, w_split, bias: torch.Tensor, stride: int = 1, pad: int = 0, relu: bool = False,
+                 residual: Optional[torch.Tensor] = None, res_mode: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """conv2d at fp32 quality on the bf16 MFMA (osr_conv2d_split_fwd): x (n,h,w,cin) fp32, w_split = (hi, lo) the bf16 planes of the
+    (cout,kh,kw,cin) fp32 weight (weights.split_conv_weight), bias fp32, residual fp32 -> fp32 (n,ho,wo,cout). stride, pad, relu,
+    residual and res_mode as conv2d. cin % 32 == 0, cout % 64 == 0, 1x1 / 3x3 at stride 1 / 2."""
+    lib = _lib.load()
+    _need(x, torch.float32, "x"); _need(bias, torch.float32, "bias")
+    hi, lo = _conv_split_planes(w_split, "w_split")
+    if x.dim() != 4:
+        raise OsrError(f"conv2d_split: x must be (n,h,w,cin), got {tuple(x.shape)}")
+    n, hi_, wi, cin = x.shape
+    cout, kh, kw, cin2 = hi.shape
+    if cin2 != cin:
+        raise OsrError(f"weight cin {cin2} != input cin {cin}")
+    ho = (hi_ + 2 * pad - kh) // stride + 1
+    wo = (wi + 2 * pad - kw) // stride + 1
+    if out is None:
+        out = torch.empty((n, ho, wo, cout), dtype=torch.float32, device=x.device)
+    else:
+        _need(out, torch.float32, "out")
+        if tuple(out.shape) not in ((n, ho, wo, cout), (n * ho * wo, cout)):
+            raise OsrError(f"conv2d_split: out {tuple(out.shape)} for a result of {(n, ho, wo, cout)} (or its {(n * ho * wo, cout)} rows)")
+    p = _new_conv_params()
+    p.n, p.hi, p.wi, p.cin, p.ho, p.wo, p.cout = n, hi_, wi, cin, ho, wo, cout
+    p.kh, p.kw, p.stride_h, p.stride_w, p.pad_h, p.pad_w = kh, kw, stride, stride, pad, pad
+    p.in_stride_n, p.in_stride_h, p.in_stride_w = hi_ * wi * cin, wi * cin, cin
+    p.out_stride_n, p.out_stride_h, p.out_stride_w = ho * wo * cout, wo * cout, cout
+    p.relu, p.res_mode, p.pad_mode = int(relu), int(res_mode), 0
+    p.in_dtype = p.out_dtype = _lib.OSR_F32
+    if res_mode:
+        _need(residual, torch.float32, "residual")
+        rn, rh, rw, rc = residual.shape
+        exp = (n, ho, wo, cout) if res_mode in (1, 3) else (n, (ho + 1) // 2, (wo + 1) // 2, cout)
+        if (rn, rh, rw, rc) != exp:
+            raise OsrError(f"residual shape {tuple(residual.shape)} != expected {exp} for res_mode {res_mode}")
+        p.res_stride_n, p.res_stride_h, p.res_stride_w = rh * rw * rc, rw * rc, rc
+    check(lib.osr_conv2d_split_fwd(C.byref(p), _p(x), _p(hi), _p(lo), _p(bias), _p(residual) if res_mode else None, _p(out), _stream()),
+          "osr_conv2d_split_fwd")
+    if CONV_SPLIT_COUNT is not None:
+        CONV_SPLIT_COUNT["launches"] += 1
+        CONV_SPLIT_COUNT["flops"] += 2.0 * n * ho * wo * cout * kh * kw * cin
+    return out
+
+
+def stem_conv_split(xpad: torch.Tensor, w_split, bias: torch.Tensor, hp: int, wp: int, relu: bool = True) -> torch.Tensor:
+    """stem_conv at fp32 quality on the bf16 MFMA: xpad the fp32 pre-padded NHWC4 image (preprocess(..., dtype=float32)), w_split the
+    bf16 planes of the (cout,8,1,32) stem view (weights.split_stem_weight) -> fp32 (n, hp/2, wp/2, cout)."""
+    lib = _lib.load()
+    _need(xpad, torch.float32, "xpad"); _need(bias, torch.float32, "bias")
+    hi, lo = _conv_split_planes(w_split, "w_split")
+    n, hd, wd, c4 = xpad.shape
+    assert c4 == 4 and hd == hp + 6 and wd == stem_padded_width(wp)
+    cout = hi.shape[0]
+    assert tuple(hi.shape[1:]) == (8, 1, 32)
+    ho, wo = hp // 2, wp // 2
+    out = torch.empty((n, ho, wo, cout), dtype=torch.float32, device=xpad.device)
+    p = _new_conv_params()
+    p.n, p.hi, p.wi, p.cin, p.ho, p.wo, p.cout = n, hd, wd, 32, ho, wo, cout
+    p.kh, p.kw, p.stride_h, p.stride_w, p.pad_h, p.pad_w = 8, 1, 2, 2, 0, 0
+    p.in_stride_n, p.in_stride_h, p.in_stride_w = hd * wd * 4, wd * 4, 4
+    p.out_stride_n, p.out_stride_h, p.out_stride_w = ho * wo * cout, wo * cout, cout
+    p.relu, p.res_mode, p.pad_mode = int(relu), 0, 1
+    p.in_dtype = p.out_dtype = _lib.OSR_F32
+    check(lib.osr_conv2d_split_fwd(C.byref(p), _p(xpad), _p(hi), _p(lo), _p(bias), None, _p(out), _stream()), "osr_conv2d_split_fwd(stem)")
+    if CONV_SPLIT_COUNT is not None:
+        CONV_SPLIT_COUNT["launches"] += 1
+        CONV_SPLIT_COUNT["flops"] += 2.0 * n * ho * wo * cout * 147  # 7*7*3 real taps
+    return out
+
+
 def conv2d_chain(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, w3: torch.Tensor, b3: torch.Tensor, residual: torch.Tensor,
                  stride: int = 1, pad: int = 0, keep_mid: bool = False):
     """A bottleneck's conv2 -> conv3 in one launch (osr_conv2d_chain_fwd): relu(conv1x1(relu(conv(x, weight) + bias), w3) + b3 +

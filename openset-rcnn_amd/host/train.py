@@ -118,7 +118,7 @@ class OpensetRCNNTrainer:
     def __init__(self, params: Dict[str, torch.Tensor], cfg: Optional[dict] = None, dtype: torch.dtype = torch.float16, device: str = "cuda",
                  lr: float = 0.005, momentum: float = 0.9, weight_decay: float = 1e-4, loss_scale: float = 1024.0, freeze_at: int = 2,
                  frozen_bn: Optional[Dict[str, Tuple[torch.Tensor, torch.Tensor]]] = None, class_map: Optional[torch.Tensor] = None,
-                 bucket_bytes: int = 25 << 20, scale_growth_interval: int = 2000, box_head: str = "storage"):
+                 bucket_bytes: int = 25 << 20, scale_growth_interval: int = 2000, box_head: str = "storage", conv: str = "storage"):
         """params: BN-folded parameters under detectron2 names (what the engine reads). frozen_bn (optional): for convs followed by
         FrozenBatchNorm, name -> (un-folded weight (cout,cin,kh,kw), per-channel scale gamma/sqrt(var+eps)): the trainable parameter
         is the un-folded weight (weight decay acts on it, the chain rule multiplies the kernel's gradient by the scale).
@@ -126,8 +126,11 @@ class OpensetRCNNTrainer:
         dtype. "split": the reference's fp32 operands from the RoIAlign output on (OpensetRCNNEngine box_head="split") -- pooled, h1 and
         box_feats are saved in fp32, the two layers' forward, data gradients and weight gradients run on the split-precision kernels
         (ops.linear_split, linear_split_dgrad, linear_split_wgrad: three bf16 MFMA products per term, fp32 sums), fc1.w / fc2.w have
-        no low-precision copy: their fp32 masters are re-split into the kernels' bf16 planes after every update."""
+        no low-precision copy: their fp32 masters are re-split into the kernels' bf16 planes after every update.
+        conv: "storage" only. The split-precision convolutions (OpensetRCNNEngine conv="split") have no backward: ValueError."""
         freeze_at = self._check_freeze_at(freeze_at)
+        if conv != "storage":
+            raise ValueError(f"conv_precision {conv!r}: the split-precision convolutions are an inference mode, training keeps conv=\"storage\"")
         if box_head not in OpensetRCNNEngine.BOX_HEADS:
             raise ValueError(f"box_head must be one of {OpensetRCNNEngine.BOX_HEADS}, got {box_head!r}")
         if box_head != "storage" and not self.SPLIT_BOX_HEAD:

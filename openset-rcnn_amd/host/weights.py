@@ -121,6 +121,24 @@ def split_fp32_rows_t(w: torch.Tensor):
     return split_fp32_rows(w.detach().to(torch.float32).t().contiguous())
 
 
+def _split_packed(packed: torch.Tensor):
+    hi, lo, _ = split_fp32_rows(packed.view(packed.shape[0], -1))
+    return hi.view(packed.shape), lo.view(packed.shape)
+
+
+def split_conv_weight(w: torch.Tensor):
+    """The weight operand of the split-precision convolution (ops.conv2d_split, include/osr.h osr_conv2d_split_fwd):
+    (cout,cin,kh,kw) -> pack_conv_weight in fp32 -> split_fp32_rows of its (cout, kh*kw*cin) rows. Returns (hi, lo), two bf16
+    tensors shaped (cout,kh,kw,cin)."""
+    return _split_packed(pack_conv_weight(w, torch.float32))
+
+
+def split_stem_weight(w: torch.Tensor):
+    """split_conv_weight for the stem: (64,3,7,7) -> pack_stem_weight in fp32 -> (hi, lo), bf16, shaped (64,8,1,32). The zero taps of
+    the view (8th tap, 4th channel, 8th row) are zero in both planes."""
+    return _split_packed(pack_stem_weight(w, torch.float32))
+
+
 def pack_dgrad_weight(w: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
     """(cout,cin,kh,kw) -> (cin,kh,kw,cout), spatially flipped: the backward-data pass of a stride-1 convolution is the
     forward convolution of dy with these weights and padding k-1-pad; for a 1x1 layer it is the transposed matrix."""
