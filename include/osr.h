@@ -440,6 +440,27 @@ osr_status osr_roi_align_fwd_ordered_ex(const osr_pyramid* feats, int32_t feat_d
                                         const int32_t* batch_idx, int64_t m, int32_t pooled, int32_t canonical_level,
                                         int32_t canonical_size, int32_t min_level, const int32_t* order,
                                         const int32_t* order_nvalid, int32_t flags, void* out, int32_t out_dtype, void* stream);
+/* Pooler options: the two ROI_BOX_HEAD keys beside the resolution that [d2] ROIPooler hands to roi_align.
+ * aligned: 1 = POOLER_TYPE "ROIAlignV2" (pixel centres at +0.5: box * scale - 0.5, no minimum size); 0 = "ROIAlign" (no offset, and the
+ *   RoI's width and height in level pixels are clamped to at least 1 before the bin size is taken).
+ * sampling_ratio: 0 = adaptive grid, ceil(roi / pooled) samples per bin and axis; S > 0 = a fixed S x S grid per bin, whose divisor is
+ *   S * S whether or not a sample is valid.
+ * A zero-area box pools to zeros under {1, 0} (its adaptive grid is 0 x 0) and to the bilinear value at its point under every other
+ * pair. NULL means {1, 0}, for which every _opt entry point computes bit for bit what the entry point without options computes (it
+ * runs the same kernel). Any other `aligned`, or a sampling_ratio outside 0 .. OSR_ROI_MAX_SAMPLING_RATIO (the sample loops are
+ * O(S) per table entry and S * S is the divisor): OSR_ERR_INVALID_ARG, nothing launched. Level assignment,
+ * the validity rule (a sample outside [-1, size] on an axis contributes nothing) and the edge clamps do not depend on the options. */
+#define OSR_ROI_MAX_SAMPLING_RATIO 64
+typedef struct osr_roi_options {
+    int32_t aligned;
+    int32_t sampling_ratio;
+} osr_roi_options;
+/* osr_roi_align_fwd_ordered_ex with pooler options. */
+osr_status osr_roi_align_fwd_ordered_opt(const osr_pyramid* feats, int32_t feat_dtype, int32_t n, const float* boxes,
+                                         const int32_t* batch_idx, int64_t m, int32_t pooled, int32_t canonical_level,
+                                         int32_t canonical_size, int32_t min_level, const int32_t* order,
+                                         const int32_t* order_nvalid, int32_t flags, const osr_roi_options* options, void* out,
+                                         int32_t out_dtype, void* stream);
 int64_t osr_roi_locality_order_workspace_bytes(int32_t n, int64_t m);
 osr_status osr_roi_locality_order(const osr_pyramid* feats, int32_t n, const float* boxes, const int32_t* batch_idx, int64_t m,
                                   int32_t canonical_level, int32_t canonical_size, int32_t min_level, int32_t* order,
@@ -839,6 +860,11 @@ osr_status osr_roi_align_bwd(const osr_pyramid* dfeat, int32_t n, const float* b
                              int32_t pooled, int32_t canonical_level, int32_t canonical_size, int32_t min_level,
                              const void* dout, int32_t dout_dtype, void* stream);
 
+/* osr_roi_align_bwd with pooler options (osr_roi_options above; NULL = {1, 0}). */
+osr_status osr_roi_align_bwd_opt(const osr_pyramid* dfeat, int32_t n, const float* boxes, const int32_t* batch_idx, int64_t m,
+                                 int32_t pooled, int32_t canonical_level, int32_t canonical_size, int32_t min_level,
+                                 const void* dout, int32_t dout_dtype, const osr_roi_options* options, void* stream);
+
 /* The same gradient in pixel-centric form: one workgroup per 8 x 8 pixel tile of a level GATHERS the contributions of the image's RoIs
  * -- no atomics, no zero-initialised output (every element of dfeat is written exactly once, zeros where no RoI reaches), bitwise
  * reproducible (fixed summation order: list order, bin row, bin column). The RoI list must be image-major with a fixed stride:
@@ -853,6 +879,11 @@ osr_status osr_roi_align_bwd(const osr_pyramid* dfeat, int32_t n, const float* b
 osr_status osr_roi_align_bwd_dense(const osr_pyramid* dfeat, int32_t n, const float* boxes, const int32_t* batch_idx, int64_t m,
                                    int32_t rois_per_image, int32_t pooled, int32_t canonical_level, int32_t canonical_size, int32_t min_level,
                                    const void* dout, int32_t dout_dtype, int32_t out_dtype, void* stream);
+/* osr_roi_align_bwd_dense with pooler options (NULL = {1, 0}); same envelope, same summation order. */
+osr_status osr_roi_align_bwd_dense_opt(const osr_pyramid* dfeat, int32_t n, const float* boxes, const int32_t* batch_idx, int64_t m,
+                                       int32_t rois_per_image, int32_t pooled, int32_t canonical_level, int32_t canonical_size,
+                                       int32_t min_level, const void* dout, int32_t dout_dtype, int32_t out_dtype,
+                                       const osr_roi_options* options, void* stream);
 
 /* g[i] = act[i] > 0 ? g[i] : 0, in place (gradient through a ReLU whose output is act). */
 osr_status osr_relu_mask(void* g, int32_t g_dtype, const void* act, int32_t act_dtype, int64_t n, void* stream);

@@ -1,7 +1,16 @@
 // RoIAlign over the FPN pyramid for gfx950 (include/osr.h: osr_roi_align_fwd).
 //
-// Replaces [d2] ROIPooler.forward + torchvision roi_align(aligned=True, sampling_ratio=0) at
-// /root/reference/openset_rcnn/modeling/roi_heads/osrcnn_roi_heads.py:108-113,306.
+// Replaces [d2] ROIPooler.forward + torchvision roi_align at
+// openset_rcnn/modeling/roi_heads/osrcnn_roi_heads.py:95-113,306.
+//
+// Pooler options (osr_roi_options; the _opt entry points): aligned = 1 (POOLER_TYPE "ROIAlignV2": offset 0.5, no minimum size) or
+// 0 ("ROIAlign": offset 0, the RoI at least one level pixel wide and high), sampling_ratio = 0 (adaptive ceil(roi / P) grid) or
+// S > 0 (fixed S x S grid per bin, divisor S * S). They enter each kernel in ra_geometry() alone: the per-axis weight tables, and
+// everything built on them, hold for any grid and either offset. Every kernel exists twice: <OPT = false> has the default pair
+// {1, 0} as literals and is the kernel the library has always run (same bits, same registers); <OPT = true> reads the options.
+// "No valid sample" shortcuts are taken from the tables, never from the box: a zero-area box has a 0 x 0 adaptive grid under the
+// default pair (a row of zeros) but a 1 x 1 grid with aligned = 0 and S x S coincident samples with S > 0. A fixed grid on wide
+// bins takes a gather of its own in the forward (ra_gather_roi); both backward kernels get the parameters only.
 //
 // Design (MI355X): one wave per RoI (4 per 256-thread workgroup, no workgroup barriers), NHWC features so that the
 // 256 channels of a pixel are one contiguous 512 B (fp16) line read by one wave-instruction (4 channels per lane).
@@ -54,6 +63,26 @@
 #endif
 #define RA_MAXD 16  // zero rows after the last step of S.wfull (the pair path's odd last step reads one row past; until round 6 the streams ran up to D steps past the footprint)
 
+// Pooler options (include/osr.h: osr_roi_options) as the kernels take them. The three kernels below exist twice: <OPT = false>
+// is the default pair (aligned, adaptive grid) with the offset 0.5, no clamp and the ceil(roi / P) grid as literals -- the code the
+// default has always run, bit for bit and register for register -- and <OPT = true> reads them from here.
+struct RaOpt {
+    float off;   // 0.5 (aligned: pixel centres at +0.5) or 0
+    int clamp1;  // 1: the RoI's width and height in level pixels are at least 1 (aligned = 0)
+    int sgrid;   // samples per bin and axis; 0: adaptive, ceil(roi / P)
+};
+
+static bool ra_opt_default(const osr_roi_options* o) { return !o || (o->aligned == 1 && o->sampling_ratio == 0); }
+static RaOpt ra_opt_of(const osr_roi_options* o) {
+    RaOpt r;
+    r.off = (!o || o->aligned) ? 0.5f : 0.f; r.clamp1 = (o && !o->aligned) ? 1 : 0; r.sgrid = o ? o->sampling_ratio : 0;
+    return r;
+}
+#define RA_REQUIRE_OPT(o, name)                                                                                                              \
+    OSR_REQUIRE(!(o) || (o)->aligned == 0 || (o)->aligned == 1, OSR_ERR_INVALID_ARG, name ": options: aligned must be 0 or 1, got %d", (o)->aligned); \
+    OSR_REQUIRE(!(o) || ((o)->sampling_ratio >= 0 && (o)->sampling_ratio <= OSR_ROI_MAX_SAMPLING_RATIO), OSR_ERR_INVALID_ARG,               \
+                name ": options: sampling_ratio must be 0 (adaptive) .. %d, got %d", OSR_ROI_MAX_SAMPLING_RATIO, (o)->sampling_ratio)
+
 struct RoiAlignArgs {
     const void* data[4];
     int h[4], w[4];
@@ -67,6 +96,7 @@ struct RoiAlignArgs {
     const int* order;  // processing order of the RoIs (a permutation of 0..m-1) or null: the result does not depend on it
     const int* order_nvalid;  // (with order) how many leading entries of it are real RoIs, the rest padding rows; null: unknown
     int no_pad_fill;   // 1: padding rows (batch index < 0) are left unwritten instead of zero-filled (osr_roi_align_fwd_ordered_ex)
+    RaOpt opt;         // pooler options; read by the <OPT = true> instantiation only
 };
 
 template <class T> struct Vec4;
@@ -189,6 +219,33 @@ __device__ __forceinline__ bool axis_sample(float start, int bin, float bin_size
     float f = v - (float)l;
     *lo = l; *hi = h; *wh = f; *wl = 1.f - f;
     return true;
+}
+
+// Start, size, bin size, sample grid and table width of one RoI on its level: the one place the pooler options enter a kernel.
+struct RaGeom {
+    float sw, sh, rw, rh, bw, bh;
+    int gh, gw;    // samples per bin along y / x
+    int tcols;     // columns of a bin's weight table that can be non-zero
+    float count;   // the divisor: gh * gw whether or not a sample is valid (at least 1)
+    bool neg;      // fixed grid on a box with x2 < x1 or y2 < y1: its samples run downwards, which the tables do not describe
+};
+template <bool OPT>
+__device__ __forceinline__ RaGeom ra_geometry(const RaOpt& o, float bx1, float by1, float bx2, float by2, float scale, int P) {
+    RaGeom g;
+    const float off = OPT ? o.off : 0.5f;
+    g.sw = bx1 * scale - off; g.sh = by1 * scale - off;
+    const float ew = bx2 * scale - off, eh = by2 * scale - off;
+    g.rw = ew - g.sw; g.rh = eh - g.sh;
+    if (OPT && o.clamp1) { g.rw = fmaxf(g.rw, 1.0f); g.rh = fmaxf(g.rh, 1.0f); }
+    g.bw = g.rw / (float)P; g.bh = g.rh / (float)P;
+    const int ch = (int)ceilf(g.rh / (float)P), cw = (int)ceilf(g.rw / (float)P);
+    const bool fixed = OPT && o.sgrid > 0;
+    g.gh = fixed ? o.sgrid : ch; g.gw = fixed ? o.sgrid : cw;
+    g.count = (float)max(g.gh * g.gw, 1);
+    // (a bin's samples span less than its width, i.e. at most ceil(width) + 2 pixels, whatever the grid)
+    g.tcols = min(RA_MAXC, max(OPT ? min(max(ch, cw), RA_MAXC) : max(ch, cw), 1) + 3);
+    g.neg = fixed && (g.bw < 0.f || g.bh < 0.f);
+    return g;
 }
 
 __device__ __forceinline__ void ra_wave_sync() {
@@ -476,6 +533,92 @@ __device__ __forceinline__ void ra_bin_row_tall(__amdgpu_buffer_rsrc_t rs, int v
     ra_store_bins<TO>(acc, inv_count, outrow, ostride, cok, P);
 }
 
+// Fixed S x S grid, wide bins (roi_align_kernel<.., OPT = true> only). The streamed paths above read every pixel of a bin's footprint;
+// with a fixed grid a bin of b x b pixels has weight on at most 2 S rows and 2 S columns of it (the two neighbours of each sample),
+// so from b of about 2 S on most of the stream multiplies zeros. This path loads just the 4 taps of every sample. The taps of an
+// axis -- (lo, hi, wl, wh) for each of the P S samples, laid over the bin's row of S.w, which this path does not otherwise use --
+// are wave-uniform: they are read into scalar registers and become the scalar offset of a buffer load, so a load costs no vector
+// address arithmetic. All 4 S^2 loads of a bin are issued before the first is used for S <= 2 (4 and 16 loads); for S = 3
+// the bin goes one sample row at a time (12 loads in flight), which keeps the fp32-feature instantiation inside its
+// registers. A sample outside [-1, size] has weights 0 on the border pixel nearest to it: that pixel is loaded and multiplies zeros
+// (a non-finite value there would turn into NaN, as a non-finite zero-weight pixel inside a streamed footprint does).
+// Summation order per bin: sample rows ascending, the two taps of a row, sample columns ascending.
+#ifndef RA_GATHER_MAXS
+#define RA_GATHER_MAXS 3  // largest S with a gather instantiation. S = 4 would fit the tables (4 S taps in a bin's RA_MAXC columns) but not the
+                          // registers: its 32 scalar taps push the 2-byte instantiations to 39 spilled registers (156 bytes of scratch
+                          // per lane); up to 3 the kernel has no scratch at the RA_MINW waves it is built for. Larger S: the paths below.
+#endif
+#ifndef RA_GATHER_BIN
+#define RA_GATHER_BIN 2.0f  // gather when the bin's shorter side is at least RA_GATHER_BIN * S pixels, else stream
+#endif
+static_assert(RA_GATHER_MAXS >= 2 && RA_GATHER_MAXS <= 3, "gather instantiations exist for S = 1, 2 and 3");
+static_assert(4 * RA_GATHER_MAXS <= RA_MAXC, "the taps of a bin are laid over its RA_MAXC table columns");
+template <int SG, class TI, class TO>
+__device__ __forceinline__ void ra_gather_roi(__amdgpu_buffer_rsrc_t rs, int lane, int sub, int C, int P, int W, const RaWaveLds& S,
+                                              float inv_count, TO* __restrict__ out) {
+    constexpr int NYG = SG <= 2 ? SG : 1;  // sample rows whose loads are in flight together
+    const int pix_b = C * (int)sizeof(TI), row_b = W * pix_b;
+    for (int ph = sub; ph < P; ph += RA_WPR) {
+        int yo[SG][2]; float wy[SG][2];
+#pragma unroll
+        for (int i = 0; i < SG; ++i)
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+                yo[i][t] = __builtin_amdgcn_readfirstlane(__float_as_int(S.w[0][ph][4 * i + t])) * row_b;
+                wy[i][t] = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(S.w[0][ph][4 * i + 2 + t])));
+            }
+        for (int pw = 0; pw < P; ++pw) {
+            int xo[SG][2]; float wx[SG][2];
+#pragma unroll
+            for (int i = 0; i < SG; ++i)
+#pragma unroll
+                for (int t = 0; t < 2; ++t) {
+                    xo[i][t] = __builtin_amdgcn_readfirstlane(__float_as_int(S.w[1][pw][4 * i + t])) * pix_b;
+                    wx[i][t] = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(S.w[1][pw][4 * i + 2 + t])));
+                }
+            for (int cb0 = 0; cb0 < C; cb0 += 256) {
+                const int c0 = cb0 + lane * 4;
+                const bool cok = c0 < C;
+                const int voff = (cok ? c0 : 0) * (int)sizeof(TI);
+                ra_f2 a0 = ra_f2{0.f, 0.f}, a1 = ra_f2{0.f, 0.f};
+#pragma unroll
+                for (int iy0 = 0; iy0 < SG; iy0 += NYG) {
+                    Buf4<TI> v[NYG][2][SG][2];
+#pragma unroll
+                    for (int iy = 0; iy < NYG; ++iy)
+#pragma unroll
+                        for (int ty = 0; ty < 2; ++ty)
+#pragma unroll
+                            for (int ix = 0; ix < SG; ++ix)
+#pragma unroll
+                                for (int tx = 0; tx < 2; ++tx) v[iy][ty][ix][tx].load(rs, voff, yo[iy0 + iy][ty] + xo[ix][tx]);
+#pragma unroll
+                    for (int iy = 0; iy < NYG; ++iy)
+#pragma unroll
+                        for (int ty = 0; ty < 2; ++ty) {
+                            ra_f2 r0 = ra_f2{0.f, 0.f}, r1 = ra_f2{0.f, 0.f};
+#pragma unroll
+                            for (int ix = 0; ix < SG; ++ix)
+#pragma unroll
+                                for (int tx = 0; tx < 2; ++tx) {
+                                    ra_f2 lo, hi;
+                                    v[iy][ty][ix][tx].get(lo, hi);
+                                    const ra_f2 wq = ra_f2{wx[ix][tx], wx[ix][tx]};
+                                    r0 = __builtin_elementwise_fma(wq, lo, r0);
+                                    r1 = __builtin_elementwise_fma(wq, hi, r1);
+                                }
+                            const ra_f2 wq = ra_f2{wy[iy0 + iy][ty], wy[iy0 + iy][ty]};
+                            a0 = __builtin_elementwise_fma(wq, r0, a0);
+                            a1 = __builtin_elementwise_fma(wq, r1, a1);
+                        }
+                }
+                const float tot[4] = {a0[0] * inv_count, a0[1] * inv_count, a1[0] * inv_count, a1[1] * inv_count};
+                if (cok) store4<TO>(out + (size_t)(ph * P + pw) * C + c0, tot);
+            }
+        }
+    }
+}
+
 // One wave per RoI (RA_WPB RoIs per workgroup, no workgroup barriers). The wave builds the per-axis weight tables in its
 // private LDS slice, picks the shorter side of the footprint as the streamed axis, and then, for each of the 7 bins of the
 // other axis, walks the footprint one pixel column (or row) at a time: the pixels of the step that fall into the bin are
@@ -488,7 +631,7 @@ __device__ __forceinline__ void ra_bin_row_tall(__amdgpu_buffer_rsrc_t rs, int v
                                    // path and 1583-1588 with round 5's kernel; the kernel alone 1.094-1.10 / 1.11-1.12 / 1.14-1.19 / 1.21-1.25 ms;
                                    // five waves keep 5 120 RoIs in flight against 32 MiB of L2: hit rate 0.64 instead of 0.73, +0.6 GB from HBM
 #endif
-template <class TI, class TO>
+template <class TI, class TO, bool OPT>
 __global__ __launch_bounds__(RA_THREADS, (sizeof(TI) == 4 ? 3 : RA_MINW)) void roi_align_kernel(RoiAlignArgs a) {  // (fp32 features: 16-byte pixel images, 3 waves)
     __shared__ RaWaveLds s_all[RA_WPB];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -542,18 +685,49 @@ __global__ __launch_bounds__(RA_THREADS, (sizeof(TI) == 4 ? 3 : RA_MINW)) void r
     const float scale = a.scale[lv];
     const TI* feat = reinterpret_cast<const TI*>(a.data[lv]) + (size_t)b * H * W * C;
 
-    const float sw = bx1 * scale - 0.5f, sh = by1 * scale - 0.5f;
-    const float ew = bx2 * scale - 0.5f, eh = by2 * scale - 0.5f;
-    const float rw = ew - sw, rh = eh - sh;
-    const float bw = rw / (float)P, bh = rh / (float)P;
-    const int gh = (int)ceilf(rh / (float)P), gw = (int)ceilf(rw / (float)P);
-    const float count = (float)max(gh * gw, 1);
+    const RaGeom geo = ra_geometry<OPT>(a.opt, bx1, by1, bx2, by2, scale, P);
+    const float sw = geo.sw, sh = geo.sh, bw = geo.bw, bh = geo.bh, count = geo.count;
+    const int gh = geo.gh, gw = geo.gw;
+
+    // ---- fixed grid on wide bins: only the 2 S rows and 2 S columns its samples touch carry weight, so gather those ----
+    if (OPT) {
+        const int SG = a.opt.sgrid;
+        const unsigned long long gl_bytes = (unsigned long long)H * W * C * sizeof(TI);
+        if (SG >= 1 && SG <= RA_GATHER_MAXS && !geo.neg && fminf(bw, bh) >= RA_GATHER_BIN * (float)SG && gl_bytes < (1ull << 31)) {
+            for (int e = gtid; e < 2 * P * SG; e += RA_WPR * 64) {  // the P S taps of each axis
+                const int axis = e / (P * SG), rem = e - axis * P * SG, bin = rem / SG, i = rem - bin * SG;
+                int lo = 0, hi = 0; float wl = 0.f, wh = 0.f;
+                const float start = axis ? sw : sh, bs = axis ? bw : bh;
+                const int size = axis ? W : H;
+                if (!axis_sample(start, bin, bs, i, SG, size, &lo, &hi, &wl, &wh)) {
+                    // outside [-1, size]: weights 0 on the border pixel next to the sample (the pixel is still loaded and multiplied,
+                    // like the zero-weight pixels inside a streamed footprint: keep it beside the RoI, not at pixel 0 of the level)
+                    const float v = start + bin * bs + ((float)i + .5f) * bs / (float)SG;
+                    lo = hi = v < 0.f ? 0 : size - 1; wl = wh = 0.f;
+                }
+                float* t = &S.w[axis][bin][4 * i];
+                t[0] = __int_as_float(lo); t[1] = __int_as_float(hi); t[2] = wl; t[3] = wh;
+            }
+            RA_SYNC();
+            const __amdgpu_buffer_rsrc_t grs = __builtin_amdgcn_make_buffer_rsrc(const_cast<TI*>(feat), 0, (int)gl_bytes, 0x00020000);
+            const float inv_count = 1.0f / count;
+            switch (SG) {
+                case 1: ra_gather_roi<1, TI, TO>(grs, lane, sub, C, P, W, S, inv_count, out); break;
+                case 2: ra_gather_roi<2, TI, TO>(grs, lane, sub, C, P, W, S, inv_count, out); break;
+#if RA_GATHER_MAXS >= 3
+                case 3: ra_gather_roi<3, TI, TO>(grs, lane, sub, C, P, W, S, inv_count, out); break;
+#endif
+                default: break;  // (not reached: SG <= RA_GATHER_MAXS)
+            }
+            return;
+        }
+    }
 
     // ---- per-axis weight tables: entry (axis, bin, col) sums the samples that touch its column ----
-    bool overflow = false;
-    // (a bin's samples span its width + 1 pixels, so only the first max(gh, gw) + 3 table columns can be non-zero and only
+    bool overflow = OPT && geo.neg;  // (samples that run downwards: the per-sample loop)
+    // (a bin's samples span its width + 1 pixels, so only the first ceil(width) + 3 table columns can be non-zero and only
     // those are ever read: build just them)
-    const int tcols = min(RA_MAXC, max(max(gh, gw), 1) + 3);
+    const int tcols = geo.tcols;
     for (int e = gtid; e < 2 * 7 * tcols; e += RA_WPR * 64) {
         const int axis = e / (7 * tcols), bin = (e / tcols) % 7, col = e % tcols;
         if (bin >= P) continue;
@@ -727,13 +901,13 @@ __global__ __launch_bounds__(RA_THREADS, (sizeof(TI) == 4 ? 3 : RA_MINW)) void r
     }
 }
 
-template <class TI>
+template <class TI, bool OPT>
 static osr_status launch_out(const RoiAlignArgs& a, int out_dtype, hipStream_t st) {
     dim3 grid((unsigned)((a.m + RA_WPB - 1) / RA_WPB)), block(RA_THREADS);
     switch (out_dtype) {
-        case OSR_F32: hipLaunchKernelGGL((roi_align_kernel<TI, float>), grid, block, 0, st, a); break;
-        case OSR_F16: hipLaunchKernelGGL((roi_align_kernel<TI, f16_t>), grid, block, 0, st, a); break;
-        default: hipLaunchKernelGGL((roi_align_kernel<TI, bf16_t>), grid, block, 0, st, a); break;
+        case OSR_F32: hipLaunchKernelGGL((roi_align_kernel<TI, float, OPT>), grid, block, 0, st, a); break;
+        case OSR_F16: hipLaunchKernelGGL((roi_align_kernel<TI, f16_t, OPT>), grid, block, 0, st, a); break;
+        default: hipLaunchKernelGGL((roi_align_kernel<TI, bf16_t, OPT>), grid, block, 0, st, a); break;
     }
     OSR_CHECK_LAUNCH("osr_roi_align_fwd");
     return OSR_OK;
@@ -742,8 +916,10 @@ static osr_status launch_out(const RoiAlignArgs& a, int out_dtype, hipStream_t s
 static osr_status roi_align_fwd_impl(const osr_pyramid* f, int32_t feat_dtype, int32_t n, const float* boxes,
                                      const int32_t* batch_idx, int64_t m, int32_t pooled, int32_t canonical_level,
                                      int32_t canonical_size, int32_t min_level, const int32_t* order,
-                                     const int32_t* order_nvalid, void* out, int32_t out_dtype, void* stream, int32_t flags = 0) {
+                                     const int32_t* order_nvalid, void* out, int32_t out_dtype, void* stream, int32_t flags = 0,
+                                     const osr_roi_options* opt = nullptr) {
     OSR_REQUIRE(f && boxes && batch_idx && out, OSR_ERR_INVALID_ARG, "osr_roi_align_fwd: null pointer");
+    RA_REQUIRE_OPT(opt, "osr_roi_align_fwd");
     OSR_REQUIRE(f->num_levels >= 1 && f->num_levels <= 4, OSR_ERR_INVALID_ARG, "osr_roi_align_fwd: 1..4 levels, got %d", f->num_levels);
     OSR_REQUIRE(pooled >= 1 && pooled <= 7, OSR_ERR_UNSUPPORTED, "osr_roi_align_fwd: pooled size 1..7, got %d", pooled);
     OSR_REQUIRE(f->c > 0 && f->c % 4 == 0, OSR_ERR_UNSUPPORTED, "osr_roi_align_fwd: channels must be a multiple of 4, got %d", f->c);
@@ -761,11 +937,19 @@ static osr_status roi_align_fwd_impl(const osr_pyramid* f, int32_t feat_dtype, i
     a.pooled = pooled; a.canonical_level = canonical_level; a.canonical_size = canonical_size; a.min_level = min_level;
     a.out = out; a.order = order; a.order_nvalid = order ? order_nvalid : nullptr;
     a.no_pad_fill = (flags & OSR_ROI_NO_PADDING_FILL) ? 1 : 0;
+    a.opt = ra_opt_of(opt);
     hipStream_t st = (hipStream_t)stream;
+    if (ra_opt_default(opt)) {
+        switch (feat_dtype) {
+            case OSR_F32: return launch_out<float, false>(a, out_dtype, st);
+            case OSR_F16: return launch_out<f16_t, false>(a, out_dtype, st);
+            default: return launch_out<bf16_t, false>(a, out_dtype, st);
+        }
+    }
     switch (feat_dtype) {
-        case OSR_F32: return launch_out<float>(a, out_dtype, st);
-        case OSR_F16: return launch_out<f16_t>(a, out_dtype, st);
-        default: return launch_out<bf16_t>(a, out_dtype, st);
+        case OSR_F32: return launch_out<float, true>(a, out_dtype, st);
+        case OSR_F16: return launch_out<f16_t, true>(a, out_dtype, st);
+        default: return launch_out<bf16_t, true>(a, out_dtype, st);
     }
 }
 
@@ -784,6 +968,16 @@ extern "C" osr_status osr_roi_align_fwd_ordered_ex(const osr_pyramid* f, int32_t
     OSR_REQUIRE((flags & ~OSR_ROI_NO_PADDING_FILL) == 0, OSR_ERR_INVALID_ARG, "osr_roi_align_fwd_ordered_ex: unknown flag bits 0x%x", flags);
     return roi_align_fwd_impl(f, feat_dtype, n, boxes, batch_idx, m, pooled, canonical_level, canonical_size, min_level, order, order_nvalid,
                               out, out_dtype, stream, flags);
+}
+
+extern "C" osr_status osr_roi_align_fwd_ordered_opt(const osr_pyramid* f, int32_t feat_dtype, int32_t n, const float* boxes,
+                                                    const int32_t* batch_idx, int64_t m, int32_t pooled, int32_t canonical_level,
+                                                    int32_t canonical_size, int32_t min_level, const int32_t* order,
+                                                    const int32_t* order_nvalid, int32_t flags, const osr_roi_options* options, void* out,
+                                                    int32_t out_dtype, void* stream) {
+    OSR_REQUIRE((flags & ~OSR_ROI_NO_PADDING_FILL) == 0, OSR_ERR_INVALID_ARG, "osr_roi_align_fwd_ordered_opt: unknown flag bits 0x%x", flags);
+    return roi_align_fwd_impl(f, feat_dtype, n, boxes, batch_idx, m, pooled, canonical_level, canonical_size, min_level, order, order_nvalid,
+                              out, out_dtype, stream, flags, options);
 }
 
 extern "C" osr_status osr_roi_align_fwd(const osr_pyramid* f, int32_t feat_dtype, int32_t n, const float* boxes,
@@ -941,6 +1135,7 @@ struct RoiAlignBwdArgs {
     long long m;
     int pooled, canonical_level, canonical_size, min_level;
     const void* dout;
+    RaOpt opt;
 };
 
 #define RA_BWD_WPB 2   // RoIs per workgroup of the backward kernel (20 KB of LDS per RoI)
@@ -958,7 +1153,7 @@ struct RaBwdLds {
     float tb[7][4][64];          // per lane: the row's gradient folded over y, for each x bin and each of the lane's 4 channels
 };
 
-template <class TG>
+template <class TG, bool OPT>
 __global__ __launch_bounds__(RA_BWD_WPB * 64) void roi_align_bwd_kernel(RoiAlignBwdArgs a) {
     __shared__ RaBwdLds s_all[RA_BWD_WPB];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -987,16 +1182,13 @@ __global__ __launch_bounds__(RA_BWD_WPB * 64) void roi_align_bwd_kernel(RoiAlign
     const int H = a.h[lv], W = a.w[lv];
     const float scale = a.scale[lv];
     float* feat = a.data[lv] + (size_t)b * H * W * C;
-    const float sw = bx1 * scale - 0.5f, sh = by1 * scale - 0.5f;
-    const float ew = bx2 * scale - 0.5f, eh = by2 * scale - 0.5f;
-    const float rw = ew - sw, rh = eh - sh;
-    const float bw = rw / (float)P, bh = rh / (float)P;
-    const int gh = (int)ceilf(rh / (float)P), gw = (int)ceilf(rw / (float)P);
-    const float count = (float)max(gh * gw, 1);
-    bool overflow = false;
-    // (a bin's samples span its width + 1 pixels, so only the first max(gh, gw) + 3 table columns can be non-zero and only
+    const RaGeom geo = ra_geometry<OPT>(a.opt, bx1, by1, bx2, by2, scale, P);
+    const float sw = geo.sw, sh = geo.sh, bw = geo.bw, bh = geo.bh, count = geo.count;
+    const int gh = geo.gh, gw = geo.gw;
+    bool overflow = OPT && geo.neg;  // (samples that run downwards: the per-sample loop)
+    // (a bin's samples span its width + 1 pixels, so only the first ceil(width) + 3 table columns can be non-zero and only
     // those are ever read: build just them)
-    const int tcols = min(RA_MAXC, max(max(gh, gw), 1) + 3);
+    const int tcols = geo.tcols;
     for (int e = lane; e < 2 * 7 * tcols; e += 64) {
         const int axis = e / (7 * tcols), bin = (e / tcols) % 7, col = e % tcols;
         if (bin >= P) continue;
@@ -1189,7 +1381,15 @@ __global__ __launch_bounds__(RA_BWD_WPB * 64) void roi_align_bwd_kernel(RoiAlign
 extern "C" osr_status osr_roi_align_bwd(const osr_pyramid* dfeat, int32_t n, const float* boxes, const int32_t* batch_idx, int64_t m,
                                         int32_t pooled, int32_t canonical_level, int32_t canonical_size, int32_t min_level, const void* dout,
                                         int32_t dout_dtype, void* stream) {
+    return osr_roi_align_bwd_opt(dfeat, n, boxes, batch_idx, m, pooled, canonical_level, canonical_size, min_level, dout, dout_dtype, nullptr,
+                                 stream);
+}
+
+extern "C" osr_status osr_roi_align_bwd_opt(const osr_pyramid* dfeat, int32_t n, const float* boxes, const int32_t* batch_idx, int64_t m,
+                                            int32_t pooled, int32_t canonical_level, int32_t canonical_size, int32_t min_level,
+                                            const void* dout, int32_t dout_dtype, const osr_roi_options* options, void* stream) {
     OSR_REQUIRE(dfeat && boxes && batch_idx && dout, OSR_ERR_INVALID_ARG, "osr_roi_align_bwd: null pointer");
+    RA_REQUIRE_OPT(options, "osr_roi_align_bwd");
     OSR_REQUIRE(dfeat->num_levels >= 1 && dfeat->num_levels <= 4, OSR_ERR_INVALID_ARG, "osr_roi_align_bwd: 1..4 levels, got %d", dfeat->num_levels);
     OSR_REQUIRE(pooled >= 1 && pooled <= 7, OSR_ERR_UNSUPPORTED, "osr_roi_align_bwd: pooled size 1..7, got %d", pooled);
     OSR_REQUIRE(dfeat->c > 0 && dfeat->c % 4 == 0, OSR_ERR_UNSUPPORTED, "osr_roi_align_bwd: channels must be a multiple of 4, got %d", dfeat->c);
@@ -1205,12 +1405,21 @@ extern "C" osr_status osr_roi_align_bwd(const osr_pyramid* dfeat, int32_t n, con
     a.num_levels = dfeat->num_levels; a.c = dfeat->c; a.boxes = boxes; a.batch_idx = batch_idx; a.m = m;
     a.pooled = pooled; a.canonical_level = canonical_level; a.canonical_size = canonical_size; a.min_level = min_level;
     a.dout = dout;
+    a.opt = ra_opt_of(options);
     hipStream_t st = (hipStream_t)stream;
     dim3 grid((unsigned)((m + RA_BWD_WPB - 1) / RA_BWD_WPB)), block(RA_BWD_WPB * 64);
-    switch (dout_dtype) {
-        case OSR_F32: hipLaunchKernelGGL(roi_align_bwd_kernel<float>, grid, block, 0, st, a); break;
-        case OSR_F16: hipLaunchKernelGGL(roi_align_bwd_kernel<f16_t>, grid, block, 0, st, a); break;
-        default: hipLaunchKernelGGL(roi_align_bwd_kernel<bf16_t>, grid, block, 0, st, a); break;
+    if (ra_opt_default(options)) {
+        switch (dout_dtype) {
+            case OSR_F32: hipLaunchKernelGGL((roi_align_bwd_kernel<float, false>), grid, block, 0, st, a); break;
+            case OSR_F16: hipLaunchKernelGGL((roi_align_bwd_kernel<f16_t, false>), grid, block, 0, st, a); break;
+            default: hipLaunchKernelGGL((roi_align_bwd_kernel<bf16_t, false>), grid, block, 0, st, a); break;
+        }
+    } else {
+        switch (dout_dtype) {
+            case OSR_F32: hipLaunchKernelGGL((roi_align_bwd_kernel<float, true>), grid, block, 0, st, a); break;
+            case OSR_F16: hipLaunchKernelGGL((roi_align_bwd_kernel<f16_t, true>), grid, block, 0, st, a); break;
+            default: hipLaunchKernelGGL((roi_align_bwd_kernel<bf16_t, true>), grid, block, 0, st, a); break;
+        }
     }
     OSR_CHECK_LAUNCH("osr_roi_align_bwd");
     return OSR_OK;
@@ -1240,9 +1449,10 @@ struct RoiBwdDenseArgs {
     const int* batch_idx;
     int pooled, canonical_level, canonical_size, min_level;
     const void* dout;
+    RaOpt opt;
 };
 
-template <class TG, class TO>
+template <class TG, class TO, bool OPT>
 #ifndef RD_MINW
 #define RD_MINW 4    // waves per SIMD the register allocation must allow (128 registers, no scratch)
 #endif
@@ -1277,7 +1487,11 @@ __global__ __launch_bounds__(256, RD_MINW) void roi_align_bwd_dense_kernel(RoiBw
             float lvf = floorf((float)a.canonical_level + log2f(sz / (float)a.canonical_size + 1e-8f));
             lvf = fminf(fmaxf(lvf, lmin), lmax);
             if ((int)lvf - a.min_level == lv) {
-                const float sw = bx1 * scale - 0.5f, sh = by1 * scale - 0.5f, ew = bx2 * scale - 0.5f, eh = by2 * scale - 0.5f;
+                float sw = bx1 * scale - 0.5f, sh = by1 * scale - 0.5f, ew = bx2 * scale - 0.5f, eh = by2 * scale - 0.5f;
+                if (OPT) {  // the end the samples are laid out to: start + the (clamped) size
+                    const RaGeom geo = ra_geometry<true>(a.opt, bx1, by1, bx2, by2, scale, P);
+                    sw = geo.sw; sh = geo.sh; ew = geo.sw + geo.rw; eh = geo.sh + geo.rh;
+                }
                 // samples lie in (start, end); a sample touches floor(v) and floor(v) + 1, and v in [-1, 0] is pulled to 0
                 const float ylo = floorf(fminf(sh, eh)) - 1.f, yhi = floorf(fmaxf(sh, eh)) + 2.f;
                 const float xlo = floorf(fminf(sw, ew)) - 1.f, xhi = floorf(fmaxf(sw, ew)) + 2.f;
@@ -1310,10 +1524,9 @@ __global__ __launch_bounds__(256, RD_MINW) void roi_align_bwd_dense_kernel(RoiBw
         const int buf = k & 1;
         const long long r = (long long)b * a.S + s_hits[k];
         const float bx1 = a.boxes[r * 4 + 0], by1 = a.boxes[r * 4 + 1], bx2 = a.boxes[r * 4 + 2], by2 = a.boxes[r * 4 + 3];
-        const float sw = bx1 * scale - 0.5f, sh = by1 * scale - 0.5f, ew = bx2 * scale - 0.5f, eh = by2 * scale - 0.5f;
-        const float rw = ew - sw, rh = eh - sh;
-        const float bw = rw / (float)P, bh = rh / (float)P;
-        const int gh = (int)ceilf(rh / (float)P), gw = (int)ceilf(rw / (float)P);
+        const RaGeom geo = ra_geometry<OPT>(a.opt, bx1, by1, bx2, by2, scale, P);
+        const float sw = geo.sw, sh = geo.sh, bw = geo.bw, bh = geo.bh;
+        const int gh = geo.gh, gw = geo.gw;
         if (tid < 2 * RD_T * 7) {
             const int axis = tid / (RD_T * 7), rem = tid - axis * RD_T * 7, pix = rem / 7, bin = rem - pix * 7;
             float wsum = 0.f;
@@ -1399,7 +1612,16 @@ __global__ __launch_bounds__(256, RD_MINW) void roi_align_bwd_dense_kernel(RoiBw
 extern "C" osr_status osr_roi_align_bwd_dense(const osr_pyramid* dfeat, int32_t n, const float* boxes, const int32_t* batch_idx, int64_t m,
                                               int32_t rois_per_image, int32_t pooled, int32_t canonical_level, int32_t canonical_size,
                                               int32_t min_level, const void* dout, int32_t dout_dtype, int32_t out_dtype, void* stream) {
+    return osr_roi_align_bwd_dense_opt(dfeat, n, boxes, batch_idx, m, rois_per_image, pooled, canonical_level, canonical_size, min_level, dout,
+                                       dout_dtype, out_dtype, nullptr, stream);
+}
+
+extern "C" osr_status osr_roi_align_bwd_dense_opt(const osr_pyramid* dfeat, int32_t n, const float* boxes, const int32_t* batch_idx, int64_t m,
+                                                  int32_t rois_per_image, int32_t pooled, int32_t canonical_level, int32_t canonical_size,
+                                                  int32_t min_level, const void* dout, int32_t dout_dtype, int32_t out_dtype,
+                                                  const osr_roi_options* options, void* stream) {
     OSR_REQUIRE(dfeat && boxes && batch_idx && dout, OSR_ERR_INVALID_ARG, "osr_roi_align_bwd_dense: null pointer");
+    RA_REQUIRE_OPT(options, "osr_roi_align_bwd_dense");
     OSR_REQUIRE(out_dtype == OSR_F32 || out_dtype == dout_dtype, OSR_ERR_UNSUPPORTED, "osr_roi_align_bwd_dense: out_dtype must be f32 or dout's dtype");
     OSR_REQUIRE(dfeat->num_levels >= 1 && dfeat->num_levels <= 4, OSR_ERR_INVALID_ARG, "osr_roi_align_bwd_dense: 1..4 levels, got %d", dfeat->num_levels);
     OSR_REQUIRE(pooled >= 1 && pooled <= 7, OSR_ERR_UNSUPPORTED, "osr_roi_align_bwd_dense: pooled size 1..7, got %d", pooled);
@@ -1427,17 +1649,21 @@ extern "C" osr_status osr_roi_align_bwd_dense(const osr_pyramid* dfeat, int32_t 
     hipStream_t st = (hipStream_t)stream;
     dim3 grid((unsigned)off), block(256);
     const bool lowp_out = out_dtype != OSR_F32;
-    switch (dout_dtype) {
-        case OSR_F32: hipLaunchKernelGGL((roi_align_bwd_dense_kernel<float, float>), grid, block, 0, st, a); break;
-        case OSR_F16:
-            if (lowp_out) hipLaunchKernelGGL((roi_align_bwd_dense_kernel<f16_t, f16_t>), grid, block, 0, st, a);
-            else hipLaunchKernelGGL((roi_align_bwd_dense_kernel<f16_t, float>), grid, block, 0, st, a);
-            break;
-        default:
-            if (lowp_out) hipLaunchKernelGGL((roi_align_bwd_dense_kernel<bf16_t, bf16_t>), grid, block, 0, st, a);
-            else hipLaunchKernelGGL((roi_align_bwd_dense_kernel<bf16_t, float>), grid, block, 0, st, a);
-            break;
+    a.opt = ra_opt_of(options);
+#define RD_LAUNCH(OPT)                                                                                                  \
+    switch (dout_dtype) {                                                                                               \
+        case OSR_F32: hipLaunchKernelGGL((roi_align_bwd_dense_kernel<float, float, OPT>), grid, block, 0, st, a); break; \
+        case OSR_F16:                                                                                                   \
+            if (lowp_out) hipLaunchKernelGGL((roi_align_bwd_dense_kernel<f16_t, f16_t, OPT>), grid, block, 0, st, a);    \
+            else hipLaunchKernelGGL((roi_align_bwd_dense_kernel<f16_t, float, OPT>), grid, block, 0, st, a);             \
+            break;                                                                                                      \
+        default:                                                                                                        \
+            if (lowp_out) hipLaunchKernelGGL((roi_align_bwd_dense_kernel<bf16_t, bf16_t, OPT>), grid, block, 0, st, a);  \
+            else hipLaunchKernelGGL((roi_align_bwd_dense_kernel<bf16_t, float, OPT>), grid, block, 0, st, a);            \
+            break;                                                                                                      \
     }
+    if (ra_opt_default(options)) { RD_LAUNCH(false) } else { RD_LAUNCH(true) }
+#undef RD_LAUNCH
     OSR_CHECK_LAUNCH("osr_roi_align_bwd_dense");
     return OSR_OK;
 }

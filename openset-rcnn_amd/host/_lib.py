@@ -94,6 +94,11 @@ class PackTensor(C.Structure):
                 ("elem_bytes", C.c_int32), ("reserved", C.c_int32)]
 
 
+class RoiOptions(C.Structure):
+    """include/osr.h osr_roi_options: the pooler's `aligned` and `sampling_ratio` (NULL = {1, 0})."""
+    _fields_ = [("aligned", C.c_int32), ("sampling_ratio", C.c_int32)]
+
+
 class Pyramid(C.Structure):
     _fields_ = [
         ("num_levels", C.c_int32), ("c", C.c_int32),
@@ -151,6 +156,7 @@ PROTOTYPES = {
     "osr_roi_align_fwd": (I32, [C.POINTER(Pyramid), I32, I32, P, P, I64, I32, I32, I32, I32, P, I32, P]),
     "osr_roi_align_fwd_ordered": (I32, [C.POINTER(Pyramid), I32, I32, P, P, I64, I32, I32, I32, I32, P, P, P, I32, P]),
     "osr_roi_align_fwd_ordered_ex": (I32, [C.POINTER(Pyramid), I32, I32, P, P, I64, I32, I32, I32, I32, P, P, I32, P, I32, P]),
+    "osr_roi_align_fwd_ordered_opt": (I32, [C.POINTER(Pyramid), I32, I32, P, P, I64, I32, I32, I32, I32, P, P, I32, C.POINTER(RoiOptions), P, I32, P]),
     "osr_roi_locality_order_workspace_bytes": (I64, [I32, I64]),
     "osr_roi_locality_order": (I32, [C.POINTER(Pyramid), I32, P, P, I64, I32, I32, I32, P, P, P, I64, P]),
     "osr_box_predictor_tail": (I32, [P, I64, I32, P, P, P, P, P, P, C.POINTER(C.c_float), I32, F32, P, P, P, P, P, P]),
@@ -206,6 +212,8 @@ PROTOTYPES = {
     "osr_pln_loss_bwd_ex": (I32, [P, I64, I32, P, I32, I32, I32, P, P, F32, F32, F32, F32, F32, P, P, I32, P, I64, P]),
     "osr_roi_align_bwd": (I32, [P, I32, P, P, I64, I32, I32, I32, I32, P, I32, P]),
     "osr_roi_align_bwd_dense": (I32, [P, I32, P, P, I64, I32, I32, I32, I32, I32, P, I32, I32, P]),
+    "osr_roi_align_bwd_opt": (I32, [P, I32, P, P, I64, I32, I32, I32, I32, P, I32, C.POINTER(RoiOptions), P]),
+    "osr_roi_align_bwd_dense_opt": (I32, [P, I32, P, P, I64, I32, I32, I32, I32, I32, P, I32, I32, C.POINTER(RoiOptions), P]),
     "osr_relu_mask": (I32, [P, I32, P, I32, I64, P]),
     "osr_add_cast": (I32, [P, P, P, I32, I64, P]),
     "osr_pool_bwd": (I32, [P, I32, I32, P, P, I32, I32, I32, I32, I32, I32, P]),

@@ -30,6 +30,8 @@ DEFAULT_CFG = dict(
     fpn_strides=(4, 8, 16, 32, 64), anchor_sizes=(32, 64, 128, 256, 512),
     pre_nms_topk_test=1000, min_box_size=0.0,
     pooler_resolution=7, pooler_scales=(0.25, 0.125, 0.0625, 0.03125), canonical_level=4, canonical_size=224,
+    # MODEL.ROI_BOX_HEAD.POOLER_TYPE "ROIAlignV2" (True) / "ROIAlign" (False) and POOLER_SAMPLING_RATIO (0 = adaptive grid)
+    pooler_aligned=True, pooler_sampling_ratio=0,
     bbox_reg_weights=(10.0, 10.0, 5.0, 5.0), mean_type="geometric",
     obj_score_thresh=0.05, nms_thresh_test=1.0, detections_per_image=1000,
     known_score_thresh=0.05, known_nms_thresh=0.5, known_topk=50,
@@ -119,6 +121,7 @@ class OpensetRCNNEngine:
         self.cfg = dict(DEFAULT_CFG)
         if cfg:
             self.cfg.update(cfg)
+        ops.check_pooler_options(self.cfg["pooler_aligned"], self.cfg["pooler_sampling_ratio"])  # (ValueError before anything is packed)
         self.dtype = dtype
         self.device = torch.device(device)
         dev = self.device
@@ -381,7 +384,8 @@ class OpensetRCNNEngine:
         c = self.cfg
         fl = [feats[k] for k in PYRAMID[:4]]
         pooled = ops.roi_align(fl, c["pooler_scales"], boxes, batch_idx, c["pooler_resolution"], out_dtype or self.dtype,
-                               c["canonical_level"], c["canonical_size"], 2, fill_padding=fill_padding)
+                               c["canonical_level"], c["canonical_size"], 2, fill_padding=fill_padding,
+                               aligned=c["pooler_aligned"], sampling_ratio=c["pooler_sampling_ratio"])
         return pooled.view(pooled.shape[0], -1)
 
     def pooled_bin_major(self, pooled: torch.Tensor) -> torch.Tensor:

@@ -125,7 +125,8 @@ class StandardRCNNEngine(OpensetRCNNEngine):
         n, cap = sel["boxes"].shape[0], sel["cap"]
         boxes = sel["boxes"].view(-1, 4)
         pooled = ops.roi_align([feats[k] for k in PYRAMID[:4]], c["pooler_scales"], boxes, sel["batch_idx"], c["pooler_resolution"],
-                               self.dtype, c["canonical_level"], c["canonical_size"], 2)
+                               self.dtype, c["canonical_level"], c["canonical_size"], 2, aligned=c["pooler_aligned"],
+                               sampling_ratio=c["pooler_sampling_ratio"])
         m = pooled.shape[0]
         h1 = self._linear(pooled.view(m, -1), self.fc1_w, self.fc1_b, True, name="roi_heads.box_head.fc1")
         box_feats = self._linear(h1, self.fc2_w, self.fc2_b, True, torch.float32, name="roi_heads.box_head.fc2")

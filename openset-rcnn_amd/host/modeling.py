@@ -520,10 +520,28 @@ def freeze_at_of(cfg: CfgNode) -> int:
     return min(v, 5)
 
 
+POOLER_TYPES = {"ROIAlignV2": True, "ROIAlign": False}  # MODEL.ROI_BOX_HEAD.POOLER_TYPE -> `aligned` of torchvision's roi_align
+
+
+def pooler_options_from(cfg: CfgNode) -> Tuple[bool, int]:
+    """MODEL.ROI_BOX_HEAD.POOLER_TYPE / POOLER_SAMPLING_RATIO as [d2] ROIPooler reads them -> (aligned, sampling_ratio) of the RoIAlign
+    kernels. "ROIPool" and "ROIAlignRotated" have no kernel and a negative ratio no meaning: ValueError when the model is built."""
+    bh = cfg.MODEL.ROI_BOX_HEAD
+    if bh.POOLER_TYPE not in POOLER_TYPES:
+        raise ValueError(f"MODEL.ROI_BOX_HEAD.POOLER_TYPE {bh.POOLER_TYPE!r}: one of {tuple(POOLER_TYPES)}")
+    ratio = bh.POOLER_SAMPLING_RATIO
+    if isinstance(ratio, bool) or not isinstance(ratio, int) or not 0 <= ratio <= ops.MAX_SAMPLING_RATIO:
+        raise ValueError(f"MODEL.ROI_BOX_HEAD.POOLER_SAMPLING_RATIO {ratio!r}: 0 (adaptive grid) or an integer S in 1 .. {ops.MAX_SAMPLING_RATIO} "
+                         "(S x S samples per bin)")
+    return POOLER_TYPES[bh.POOLER_TYPE], int(ratio)
+
+
 def engine_cfg_from(cfg: CfgNode) -> dict:
     """yaml keys -> engine hyper-parameters."""
     rh, bh, rpn = cfg.MODEL.ROI_HEADS, cfg.MODEL.ROI_BOX_HEAD, cfg.MODEL.RPN
+    aligned, sampling_ratio = pooler_options_from(cfg)
     return dict(
+        pooler_aligned=aligned, pooler_sampling_ratio=sampling_ratio,
         pixel_mean=tuple(cfg.MODEL.PIXEL_MEAN), pixel_std=tuple(cfg.MODEL.PIXEL_STD),
         anchor_sizes=tuple(float(s[0]) for s in cfg.MODEL.ANCHOR_GENERATOR.SIZES),
         pre_nms_topk_test=cfg.MODEL.RPN.PRE_NMS_TOPK_TEST, min_box_size=float(cfg.MODEL.PROPOSAL_GENERATOR.MIN_SIZE),
@@ -564,7 +582,6 @@ class OpensetROIHeads(_EngineOwner):
         super().__init__()
         self.in_features = self.box_in_features = list(cfg.MODEL.ROI_HEADS.IN_FEATURES)
         res = cfg.MODEL.ROI_BOX_HEAD.POOLER_RESOLUTION
-        assert cfg.MODEL.ROI_BOX_HEAD.POOLER_TYPE == "ROIAlignV2" and cfg.MODEL.ROI_BOX_HEAD.POOLER_SAMPLING_RATIO == 0
         self.pooler_scales = tuple(1.0 / input_shape[k].stride for k in self.in_features)
         ch = input_shape[self.in_features[0]].channels
         self.box_head = ROI_BOX_HEAD_REGISTRY.get(cfg.MODEL.ROI_BOX_HEAD.NAME)(cfg, ShapeSpec(channels=ch, height=res, width=res))
@@ -674,7 +691,6 @@ class StandardROIHeads(_EngineOwner):
         assert not cfg.MODEL.MASK_ON and not cfg.MODEL.KEYPOINT_ON, "box branch only (the Openset path has no mask / keypoint heads)"
         self.in_features = self.box_in_features = list(cfg.MODEL.ROI_HEADS.IN_FEATURES)
         res = cfg.MODEL.ROI_BOX_HEAD.POOLER_RESOLUTION
-        assert cfg.MODEL.ROI_BOX_HEAD.POOLER_TYPE == "ROIAlignV2" and cfg.MODEL.ROI_BOX_HEAD.POOLER_SAMPLING_RATIO == 0
         ch = input_shape[self.in_features[0]].channels
         self.box_head = ROI_BOX_HEAD_REGISTRY.get(cfg.MODEL.ROI_BOX_HEAD.NAME)(cfg, ShapeSpec(channels=ch, height=res, width=res))
         self.box_predictor = FastRCNNOutputLayers(cfg, self.box_head.output_shape)

@@ -900,13 +900,35 @@ def roi_locality_order(feats: List[torch.Tensor], scales: Sequence[float], boxes
     return order
 
 
+MAX_SAMPLING_RATIO = 64  # include/osr.h OSR_ROI_MAX_SAMPLING_RATIO
+
+
+def check_pooler_options(aligned, sampling_ratio) -> Tuple[bool, int]:
+    """The pooler options the RoIAlign kernels implement, as (aligned, sampling_ratio); ValueError for anything else."""
+    if not isinstance(aligned, (bool, int)) or aligned not in (0, 1):
+        raise ValueError(f"RoIAlign: aligned must be True (POOLER_TYPE 'ROIAlignV2') or False ('ROIAlign'), got {aligned!r}")
+    if isinstance(sampling_ratio, bool) or not isinstance(sampling_ratio, int) or not 0 <= sampling_ratio <= MAX_SAMPLING_RATIO:
+        raise ValueError(f"RoIAlign: sampling_ratio must be an integer 0 .. {MAX_SAMPLING_RATIO} (0 = adaptive grid, S > 0 = S x S samples per bin), "
+                         f"got {sampling_ratio!r}")
+    return bool(aligned), int(sampling_ratio)
+
+
+def _roi_options(aligned, sampling_ratio):
+    aligned, sampling_ratio = check_pooler_options(aligned, sampling_ratio)
+    return C.byref(_lib.RoiOptions(int(aligned), sampling_ratio))
+
+
 def roi_align(feats: List[torch.Tensor], scales: Sequence[float], boxes: torch.Tensor, batch_idx: torch.Tensor,
               pooled: int = 7, out_dtype: Optional[torch.dtype] = None, canonical_level: int = 4, canonical_size: int = 224,
-              min_level: int = 2, order: Optional[torch.Tensor] = None, fill_padding: bool = True) -> torch.Tensor:
+              min_level: int = 2, order: Optional[torch.Tensor] = None, fill_padding: bool = True, aligned: bool = True,
+              sampling_ratio: int = 0) -> torch.Tensor:
     """feats: NHWC per level; boxes (m,4) fp32; batch_idx (m) int32. Returns (m, pooled, pooled, c). order: processing order, (m,)
     int32 or (m + 1,) as roi_locality_order returns it (None: that order when ROI_LOCALITY_ORDER, else list order); the result
-    does not depend on it. fill_padding=False: the rows of padding entries (batch index -1) are left unwritten instead of zeroed."""
+    does not depend on it. fill_padding=False: the rows of padding entries (batch index -1) are left unwritten instead of zeroed.
+    aligned / sampling_ratio: torchvision roi_align's (include/osr.h osr_roi_options); the defaults are POOLER_TYPE "ROIAlignV2" with
+    the adaptive grid, aligned=False is "ROIAlign", sampling_ratio=S > 0 a fixed S x S grid per bin."""
     lib = _lib.load()
+    opt = _roi_options(aligned, sampling_ratio)
     _need(boxes, torch.float32, "boxes"); _need(batch_idx, torch.int32, "batch_idx")
     py = _pyramid(feats, scales)
     m = boxes.shape[0]
@@ -920,9 +942,9 @@ def roi_align(feats: List[torch.Tensor], scales: Sequence[float], boxes: torch.T
             nvalid = C.c_void_p(order.data_ptr() + 4 * m)
     out_dtype = out_dtype or feats[0].dtype
     out = torch.empty((m, pooled, pooled, py.c), dtype=out_dtype, device=boxes.device)
-    check(lib.osr_roi_align_fwd_ordered_ex(C.byref(py), _DT[feats[0].dtype], feats[0].shape[0], _p(boxes), _p(batch_idx), m, pooled,
-                                           canonical_level, canonical_size, min_level, _p(order), nvalid, 0 if fill_padding else 1, _p(out),
-                                           _DT[out_dtype], _stream()), "osr_roi_align_fwd")
+    check(lib.osr_roi_align_fwd_ordered_opt(C.byref(py), _DT[feats[0].dtype], feats[0].shape[0], _p(boxes), _p(batch_idx), m, pooled,
+                                            canonical_level, canonical_size, min_level, _p(order), nvalid, 0 if fill_padding else 1, opt,
+                                            _p(out), _DT[out_dtype], _stream()), "osr_roi_align_fwd")
     return out
 
 
@@ -1473,12 +1495,14 @@ def pln_loss_bwd(emb, protos_raw, gt_classes, ious, iou_thr: float, alpha: float
 
 def roi_align_bwd(dout: torch.Tensor, shapes: Sequence[Tuple[int, int]], n: int, scales: Sequence[float], boxes, batch_idx,
                   canonical_level: int = 4, canonical_size: int = 224, min_level: int = 2, rois_per_image: Optional[int] = None,
-                  out_dtype: Optional[torch.dtype] = None) -> List[torch.Tensor]:
+                  out_dtype: Optional[torch.dtype] = None, aligned: bool = True, sampling_ratio: int = 0) -> List[torch.Tensor]:
     """dout (m,P,P,c) -> list of (n,h,w,c) feature gradients, one per level: fp32, or out_dtype (= dout's dtype: the fp32 sums rounded
     once; the scatter path casts afterwards). rois_per_image: the list is image-major with this
     fixed stride (rows [b*S, (b+1)*S) are image b's or padding) -- the pixel-centric kernel then gathers (osr_roi_align_bwd_dense: no
-    atomics, no zero fill, reproducible bit for bit); otherwise the scatter kernel adds into a zeroed pyramid with fp32 atomics."""
+    atomics, no zero fill, reproducible bit for bit); otherwise the scatter kernel adds into a zeroed pyramid with fp32 atomics.
+    aligned / sampling_ratio: the forward's (roi_align)."""
     lib = _lib.load()
+    opt = _roi_options(aligned, sampling_ratio)
     _need(dout, name="dout"); _need(boxes, torch.float32, "boxes"); _need(batch_idx, torch.int32, "batch_idx")
     m, pooled, _, c = dout.shape
     dense = rois_per_image is not None and m == n * rois_per_image and rois_per_image <= 1024 and c <= 256
@@ -1492,16 +1516,16 @@ def roi_align_bwd(dout: torch.Tensor, shapes: Sequence[Tuple[int, int]], n: int,
     for i, (f, s) in enumerate(zip(outs, scales)):
         py.h[i], py.w[i], py.scale[i], py.data[i] = f.shape[1], f.shape[2], float(s), f.data_ptr()
     if dense:
-        st = lib.osr_roi_align_bwd_dense(C.byref(py), n, _p(boxes), _p(batch_idx), m, int(rois_per_image), pooled, canonical_level, canonical_size,
-                                         min_level, _p(dout), _DT[dout.dtype], _DT[odt], _stream())
+        st = lib.osr_roi_align_bwd_dense_opt(C.byref(py), n, _p(boxes), _p(batch_idx), m, int(rois_per_image), pooled, canonical_level,
+                                             canonical_size, min_level, _p(dout), _DT[dout.dtype], _DT[odt], opt, _stream())
         if st != _lib.ERR_UNSUPPORTED:
             check(st, "osr_roi_align_bwd_dense")
             return outs
         outs = [torch.zeros((n, h, w, c), dtype=torch.float32, device=dout.device) for h, w in shapes]
         for i, f in enumerate(outs):
             py.data[i] = f.data_ptr()
-    check(lib.osr_roi_align_bwd(C.byref(py), n, _p(boxes), _p(batch_idx), m, pooled, canonical_level, canonical_size, min_level, _p(dout),
-                                _DT[dout.dtype], _stream()), "osr_roi_align_bwd")
+    check(lib.osr_roi_align_bwd_opt(C.byref(py), n, _p(boxes), _p(batch_idx), m, pooled, canonical_level, canonical_size, min_level, _p(dout),
+                                    _DT[dout.dtype], opt, _stream()), "osr_roi_align_bwd")
     return outs if odt == torch.float32 else [add_cast(f, None, odt) for f in outs]
 
 

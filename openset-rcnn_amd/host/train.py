@@ -136,8 +136,8 @@ class OpensetRCNNTrainer:
         if box_head != "storage" and not self.SPLIT_BOX_HEAD:
             raise ValueError(f"box_head_precision {box_head!r}: the stock Faster R-CNN engine keeps its box head")
         self.box_head = box_head
-        # (tests / diagnostics) set to a dict: _box_head_bwd leaves the gradient it was given (d_bf, a copy) and the one it hands to
-        # RoIAlign's backward (d_pooled) in it
+        # (tests / diagnostics) set to a dict: _box_head_bwd leaves the gradient it was given (d_bf, a copy), the one it hands to
+        # RoIAlign's backward (d_pooled) and what that returns (d_feat, copies of the per-level feature gradients) in it
         self.box_head_probe: Optional[dict] = None
         self.frozen_bn = frozen_bn or {}
         self.row_scale: Dict[str, torch.Tensor] = {}
@@ -748,7 +748,10 @@ class OpensetRCNNTrainer:
         shapes = [(p[k].shape[1], p[k].shape[2]) for k in PYRAMID[:4]]
         d_feat = ops.roi_align_bwd(d_pooled.view(m, P, P, -1), shapes, n, c["pooler_scales"], s["boxes"], s["smp"]["batch_idx"], c["canonical_level"],
                                    c["canonical_size"], 2, rois_per_image=m // n if m % n == 0 else None,  # (the sampled list is (n, S))
-                                   out_dtype=dt if d_pooled.dtype == dt else None)
+                                   out_dtype=dt if d_pooled.dtype == dt else None, aligned=c["pooler_aligned"],
+                                   sampling_ratio=c["pooler_sampling_ratio"])
+        if self.box_head_probe is not None:
+            self.box_head_probe["d_feat"] = [d.clone() for d in d_feat]  # (the RPN's share is added into these tensors later)
         return d_feat
 
     def _backward_trunk(self, s, dP, prefetch) -> None:
