@@ -1,7 +1,6 @@
 // RoIAlign over the FPN pyramid for gfx950 (include/osr.h: osr_roi_align_fwd).
 //
-// Replaces [d2] ROIPooler.forward + torchvision roi_align at
-// openset_rcnn/modeling/roi_heads/osrcnn_roi_heads.py:95-113,306.
+// Replaces [d2] ROIPooler.forward + torchvision roi_align at openset_rcnn/modeling/roi_heads/osrcnn_roi_heads.py:95-113,306.
 //
 // Pooler options (osr_roi_options; the _opt entry points): aligned = 1 (POOLER_TYPE "ROIAlignV2": offset 0.5, no minimum size) or
 // 0 ("ROIAlign": offset 0, the RoI at least one level pixel wide and high), sampling_ratio = 0 (adaptive ceil(roi / P) grid) or
@@ -12,19 +11,25 @@
 // default pair (a row of zeros) but a 1 x 1 grid with aligned = 0 and S x S coincident samples with S > 0. A fixed grid on wide
 // bins takes a gather of its own in the forward (ra_gather_roi); both backward kernels get the parameters only.
 //
-// Design (MI355X): one wave per RoI (4 per 256-thread workgroup, no workgroup barriers), NHWC features so that the
-// 256 channels of a pixel are one contiguous 512 B (fp16) line read by one wave-instruction (4 channels per lane).
-// The adaptive ceil(roi/7) x ceil(roi/7) sample grid of a bin is a tensor product and bilinear weights are products,
-// so  sum_samples bilinear(f) = sum_y sum_x wy[y]*wx[x]*f[y][x]  with per-axis weight tables (built by the wave in
-// its private LDS slice). Fast path ("column sums"): for each bin row the wave streams the footprint columns left to
-// right, forms colsum[x] = sum_y wy[y] f[y][x] from up to 6 row loads (all loads of a column group are issued before
-// any is used), and adds wx * colsum into a 3-bin sliding window of register accumulators; a bin is stored as soon
-// as the stream has passed it. Every footprint pixel of a bin row is read once instead of 4 taps per sample.
-// The validity rule (y<-1||y>H||x<-1||x>W => sample contributes 0) and the edge clamps are per-axis, hence preserved
-// exactly; only the fp32 summation order differs from the reference loop (tolerance 1e-4, measured ~1e-6) and the
-// final division by the sample count is a multiplication by its reciprocal. RoIs outside the fast path's
-// preconditions (bins narrower than a pixel, >6 rows per bin row, >64 footprint columns) take the per-bin separable
-// loop, and table overflow (bins wider than 13 px) the per-sample 4-tap loop.
+// Design (MI355X): one wave per RoI (RA_WPB = 2 per workgroup, no workgroup barriers), NHWC features so that the 256 channels of
+// a pixel are one contiguous 512 B (fp16) line read by one wave instruction (4 channels per lane). The sample grid of a bin is a
+// tensor product and bilinear weights are products, so  sum_samples bilinear(f) = sum_y sum_x wy[y] * wx[x] * f[y][x]  with
+// per-axis weight tables, which the wave builds in its private LDS slice (RA_MAXC columns per bin).
+//  - Streamed path. The SHORTER side of the RoI's footprint is the streamed ("outer") axis. For each of the P bins of the other
+//    ("inner") axis the wave walks the footprint one pixel column (or row) at a time: the up to 6 pixels of the step inside the bin
+//    are reduced with the bin's inner weights (scalar registers) and the sum is added into SEVEN register accumulators, one per bin
+//    of the outer axis, with the step's row of a per-step weight table (zero outside a bin's footprint: nothing is assumed about how
+//    bins overlap). Loads run ahead behind counted waits, none past the last step (ra_stream); the seven bins are stored when the
+//    stream ends. Every footprint pixel of a bin row is read once instead of 4 taps per sample.
+//  - Tall bins. A bin deeper than 6 pixels along the inner axis (long boxes) reduces a step in chunks of 6 loads, weights from LDS.
+//  - Per-bin loop. A footprint longer than RA_FWD_MAXX = 96 pixels on both sides (the per-step table), or a level image of 2 GiB or
+//    more (the buffer resource's range), takes the separable loop over each bin's own footprint.
+//  - Per-sample loop. A bin whose samples span more than RA_MAXC = 32 pixels overflows its table: the RoI takes torchvision's 4-tap
+//    loop over every sample, as does a fixed grid on a box with x2 < x1 or y2 < y1.
+//  - Gather. A fixed S x S grid (S <= RA_GATHER_MAXS = 3) on bins at least RA_GATHER_BIN * S pixels wide loads only its samples' taps.
+// The validity rule (y < -1 || y > H || x < -1 || x > W => the sample contributes 0) and the edge clamps are per axis, hence preserved
+// exactly; only the fp32 summation order differs from the reference loop (tolerance 1e-4, measured ~1e-6), and the streamed and
+// gather paths multiply by the reciprocal of the sample count instead of dividing by it.
 #include "osr_common.h"
 #include <stdlib.h>
 
@@ -40,20 +45,6 @@
 #ifndef RA_FWD_MAXX
 #define RA_FWD_MAXX 96  // (forward) steps of the streamed (shorter) side of the footprint; beyond: the per-bin loop. This model's pyramid: <= 44
 #endif
-#ifndef RA_PAIR
-#define RA_PAIR 0   // 1: 2-byte features take two steps per wave instruction (16-byte loads, ra_bin_row_pair). Rounds 2-5 ran it: with the
-                    // dead prefetches of the old loops the kernel sat at the vector-memory instruction rate and halving the instructions paid.
-                    // With exact-length streams (ra_stream, round 6) the instruction count is 2.3x lower and the binding resource is
-                    // the L1-miss traffic (5.4 GB per pass from L2 at 0.6-0.7 of the L2 -> L1 ceiling) under memory latency: the
-                    // one-step form's 28 accumulator registers (against 56) let four or five waves per SIMD in instead of three, which is worth
-                    // more than the wider loads (same box: 1.20 ms round 5, 1.15 pair / 3 waves, 1.11 one-step / 4 waves, 1.08 / 5 waves; RA_MINW below)
-#endif
-#ifndef RA_PD1
-#define RA_PD1 6  // pipeline depth of the pair path by pixels per step (NY = 1..4)
-#define RA_PD2 4
-#define RA_PD3 2
-#define RA_PD4 2
-#endif
 #ifndef RA_SD1
 #define RA_SD1 8  // pipeline depth of the one-step-per-instruction path by pixels per step (NY = 1, 2, 3, 4-5, 6): with the
 #define RA_SD2 4  // (2 D - 1) NY loads of 8 bytes per lane a stream holds: 94 registers
@@ -61,7 +52,8 @@
 #define RA_SD4 2
 #define RA_SD6 2
 #endif
-#define RA_MAXD 16  // zero rows after the last step of S.wfull (the pair path's odd last step reads one row past; until round 6 the streams ran up to D steps past the footprint)
+#define RA_MAXD 16  // zero rows after the last step of S.wfull, at least a stream's pipeline depth (ra_bin_row). ra_stream stops at the last
+                    // step and reads none of them, but the LDS layout, and with it the generated code, depends on the value: it stays
 
 // Pooler options (include/osr.h: osr_roi_options) as the kernels take them. The three kernels below exist twice: <OPT = false>
 // is the default pair (aligned, adaptive grid) with the offset 0.5, no clamp and the ceil(roi / P) grid as literals -- the code the
@@ -83,10 +75,28 @@ static RaOpt ra_opt_of(const osr_roi_options* o) {
     OSR_REQUIRE(!(o) || ((o)->sampling_ratio >= 0 && (o)->sampling_ratio <= OSR_ROI_MAX_SAMPLING_RATIO), OSR_ERR_INVALID_ARG,               \
                 name ": options: sampling_ratio must be 0 (adaptive) .. %d, got %d", OSR_ROI_MAX_SAMPLING_RATIO, (o)->sampling_ratio)
 
-struct RoiAlignArgs {
-    const void* data[4];
+// The pyramid as every RoIAlign kernel takes it, at the head of its arguments: four level slots, those past num_levels repeating level 0.
+struct RaLevels {
+    void* data[4];  // features (forward, read only) or their gradient (backward)
     int h[4], w[4];
     float scale[4];
+};
+// What every entry point asks of the pyramid and the pooled size, and the fill of the four slots. dense: osr_roi_align_bwd_dense's
+// channel rule (a workgroup's four waves cover 256 channels) instead of the 4 channels per lane of the other two kernels.
+static osr_status ra_take_pyramid(const char* name, const osr_pyramid* f, int pooled, bool dense, RaLevels* a) {
+    OSR_REQUIRE(f->num_levels >= 1 && f->num_levels <= 4, OSR_ERR_INVALID_ARG, "%s: 1..4 levels, got %d", name, f->num_levels);
+    OSR_REQUIRE(pooled >= 1 && pooled <= 7, OSR_ERR_UNSUPPORTED, "%s: pooled size 1..7, got %d", name, pooled);
+    if (dense) OSR_REQUIRE(f->c > 0 && f->c <= 256, OSR_ERR_UNSUPPORTED, "%s: at most 256 channels, got %d", name, f->c);
+    else OSR_REQUIRE(f->c > 0 && f->c % 4 == 0, OSR_ERR_UNSUPPORTED, "%s: channels must be a multiple of 4, got %d", name, f->c);
+    for (int l = 0; l < 4; ++l) {
+        const int s = l < f->num_levels ? l : 0;
+        OSR_REQUIRE(f->data[s] && f->h[s] > 0 && f->w[s] > 0, OSR_ERR_INVALID_ARG, "%s: bad level %d", name, s);
+        a->data[l] = const_cast<void*>(f->data[s]); a->h[l] = f->h[s]; a->w[l] = f->w[s]; a->scale[l] = f->scale[s];
+    }
+    return OSR_OK;
+}
+
+struct RoiAlignArgs : RaLevels {
     int num_levels, c;
     const float* boxes;
     const int* batch_idx;
@@ -98,11 +108,6 @@ struct RoiAlignArgs {
     int no_pad_fill;   // 1: padding rows (batch index < 0) are left unwritten instead of zero-filled (osr_roi_align_fwd_ordered_ex)
     RaOpt opt;         // pooler options; read by the <OPT = true> instantiation only
 };
-
-template <class T> struct Vec4;
-template <> struct Vec4<float> { typedef float4 type; };
-template <> struct Vec4<f16_t> { typedef uint2 type; };
-template <> struct Vec4<bf16_t> { typedef uint2 type; };
 
 template <class T> __device__ __forceinline__ void load4(const T* p, float v[4]);
 template <> __device__ __forceinline__ void load4<float>(const float* p, float v[4]) {
@@ -134,78 +139,8 @@ template <> __device__ __forceinline__ void store4<bf16_t>(bf16_t* p, const floa
     *reinterpret_cast<b4*>(p) = t;
 }
 
-template <class T> __device__ __forceinline__ void load8(const T* p, float v[8]);
-template <> __device__ __forceinline__ void load8<float>(const float* p, float v[8]) { load4<float>(p, v); load4<float>(p + 4, v + 4); }
-template <> __device__ __forceinline__ void load8<f16_t>(const f16_t* p, float v[8]) {
-    typedef f16_t h8 __attribute__((ext_vector_type(8)));
-    h8 t = *reinterpret_cast<const h8*>(p);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) v[i] = (float)t[i];
-}
-template <> __device__ __forceinline__ void load8<bf16_t>(const bf16_t* p, float v[8]) {
-    uint4 t = *reinterpret_cast<const uint4*>(p);
-    v[0] = __uint_as_float(t.x << 16); v[1] = __uint_as_float(t.x & 0xffff0000u);
-    v[2] = __uint_as_float(t.y << 16); v[3] = __uint_as_float(t.y & 0xffff0000u);
-    v[4] = __uint_as_float(t.z << 16); v[5] = __uint_as_float(t.z & 0xffff0000u);
-    v[6] = __uint_as_float(t.w << 16); v[7] = __uint_as_float(t.w & 0xffff0000u);
-}
 // packed 8-channel register image of one load (kept packed while the loads of a column group are in flight)
 typedef unsigned int ra_u32x4 __attribute__((ext_vector_type(4)));
-typedef float ra_f32x8 __attribute__((ext_vector_type(8)));
-template <class T> struct Raw8;
-template <> struct Raw8<float> {
-    ra_f32x8 r;
-    __device__ __forceinline__ void load(const float* p) { r = *reinterpret_cast<const ra_f32x8*>(p); }
-    __device__ __forceinline__ void get(float v[8]) const { _Pragma("unroll") for (int i = 0; i < 8; ++i) v[i] = r[i]; }
-};
-template <> struct Raw8<f16_t> {
-    typedef f16_t h8 __attribute__((ext_vector_type(8)));
-    h8 r;
-    __device__ __forceinline__ void load(const f16_t* p) { r = *reinterpret_cast<const h8*>(p); }
-    __device__ __forceinline__ void get(float v[8]) const { _Pragma("unroll") for (int i = 0; i < 8; ++i) v[i] = (float)r[i]; }
-};
-template <> struct Raw8<bf16_t> {
-    ra_u32x4 r;
-    __device__ __forceinline__ void load(const bf16_t* p) { r = *reinterpret_cast<const ra_u32x4*>(p); }
-    __device__ __forceinline__ void get(float v[8]) const {
-        _Pragma("unroll") for (int i = 0; i < 4; ++i) { v[2 * i] = __uint_as_float(r[i] << 16); v[2 * i + 1] = __uint_as_float(r[i] & 0xffff0000u); }
-    }
-};
-// packed 4-channel register image of one 8-byte (fp16/bf16) or 16-byte (fp32) load
-template <class T> struct Raw4;
-template <> struct Raw4<float> {
-    typedef float f4 __attribute__((ext_vector_type(4)));
-    f4 r;
-    __device__ __forceinline__ void load(const float* p) { r = *reinterpret_cast<const f4*>(p); }
-    __device__ __forceinline__ void get(float v[4]) const { _Pragma("unroll") for (int i = 0; i < 4; ++i) v[i] = r[i]; }
-};
-template <> struct Raw4<f16_t> {
-    typedef f16_t h4 __attribute__((ext_vector_type(4)));
-    h4 r;
-    __device__ __forceinline__ void load(const f16_t* p) { r = *reinterpret_cast<const h4*>(p); }
-    __device__ __forceinline__ void get(float v[4]) const { _Pragma("unroll") for (int i = 0; i < 4; ++i) v[i] = (float)r[i]; }
-};
-template <> struct Raw4<bf16_t> {
-    typedef bf16_t b4 __attribute__((ext_vector_type(4)));
-    b4 r;
-    __device__ __forceinline__ void load(const bf16_t* p) { r = *reinterpret_cast<const b4*>(p); }
-    __device__ __forceinline__ void get(float v[4]) const { _Pragma("unroll") for (int i = 0; i < 4; ++i) v[i] = (float)r[i]; }
-};
-template <class T> __device__ __forceinline__ void store8(T* p, const float v[8]) { store4<T>(p, v); store4<T>(p + 4, v + 4); }
-template <> __device__ __forceinline__ void store8<f16_t>(f16_t* p, const float v[8]) {
-    typedef f16_t h8 __attribute__((ext_vector_type(8)));
-    h8 t;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) t[i] = (f16_t)v[i];
-    *reinterpret_cast<h8*>(p) = t;
-}
-template <> __device__ __forceinline__ void store8<bf16_t>(bf16_t* p, const float v[8]) {
-    typedef bf16_t b8 __attribute__((ext_vector_type(8)));
-    b8 t;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) t[i] = (bf16_t)v[i];
-    *reinterpret_cast<b8*>(p) = t;
-}
 
 // One sample coordinate of torchvision's pre_calc_for_bilinear_interpolate along one axis.
 // Returns false when the sample is outside [-1, size] (contributes nothing).
@@ -248,6 +183,16 @@ __device__ __forceinline__ RaGeom ra_geometry(const RaOpt& o, float bx1, float b
     return g;
 }
 
+// [d2] assign_boxes_to_levels, evaluated in fp32 exactly as written there: the level of a box, counted from min_level. The forward, the
+// locality order and both backward kernels take it from here, so a RoI's gradient lands in the map its features came from.
+__device__ __forceinline__ int ra_level_of(float bx1, float by1, float bx2, float by2, int canonical_level, int canonical_size, int min_level, int num_levels) {
+    float sz = sqrtf((bx2 - bx1) * (by2 - by1));
+    float lvf = floorf((float)canonical_level + log2f(sz / (float)canonical_size + 1e-8f));
+    float lmin = (float)min_level, lmax = (float)(min_level + num_levels - 1);
+    lvf = fminf(fmaxf(lvf, lmin), lmax);  // NaN (negative area) -> the first level via fmaxf
+    return (int)lvf - min_level;
+}
+
 __device__ __forceinline__ void ra_wave_sync() {
     __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): this wave's LDS writes have landed
     __builtin_amdgcn_wave_barrier();     // and the compiler keeps later LDS reads behind them
@@ -260,23 +205,10 @@ struct RaWaveLds {
                                                                      // bin's footprint, and in the RA_MAXD rows after the last step)
 };
 
-#ifndef RA_WPR
-#define RA_WPR 1  // waves per RoI: the bin rows (columns) of the inner axis are dealt over the waves of the workgroup, which share the
-                  // RoI's tables. 1 = a wave per RoI (RA_WPB RoIs per workgroup, no workgroup barriers).
-#endif
 #ifndef RA_WPB
-#define RA_WPB 2  // RoIs per workgroup when RA_WPR == 1 (2: -3 % against 4 once the small tables let five waves per SIMD in)
+#define RA_WPB 2  // RoIs (waves) per workgroup (2: -3 % against 4 once the small tables let five waves per SIMD in)
 #endif
-#if RA_WPR > 1
-#undef RA_WPB
-#define RA_WPB 1
-#define RA_SYNC() __syncthreads()
-#define RA_ANY(x) __syncthreads_or(x)
-#else
-#define RA_SYNC() ra_wave_sync()
-#define RA_ANY(x) __any(x)
-#endif
-#define RA_THREADS (RA_WPB * RA_WPR * 64)
+#define RA_THREADS (RA_WPB * 64)
 typedef float ra_f2 __attribute__((ext_vector_type(2)));
 typedef unsigned int ra_u2 __attribute__((ext_vector_type(2)));
 
@@ -397,105 +329,6 @@ __device__ __forceinline__ void ra_bin_row(__amdgpu_buffer_rsrc_t rs, int voff, 
     ra_store_bins<TO>(acc, inv_count, outrow, ostride, cok, P);
 }
 
-// 16-byte image of 8 channels of one pixel (2-byte feature types): 32 lanes cover a 256-channel pixel, so one wave instruction
-// loads TWO pixels. The vector memory path spends ~16 cycles on a wave instruction of up to 8 bytes per lane and ~21 on one of
-// 16 (measured, scripts/exp_ta_width.hip): at 8 bytes per lane the kernel was bound by exactly that (rocprofv3: TA busy 85 %).
-template <class T> struct Buf8;
-// acc + w * (fp16 half of a packed register), fp32: v_fma_mix_f32 converts inside the multiply-add (the compiler's own choice for
-// this pattern is v_cvt_f32_f16 + half a v_pk_fma_f32, 1.5 instructions per element instead of 1)
-template <int HI, bool FIRST> __device__ __forceinline__ float ra_mix(unsigned packed, float w, float c) {
-    float d;
-    if (FIRST) {
-        if (HI) asm("v_fma_mix_f32 %0, %1, %2, 0 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(d) : "v"(packed), "s"(w));
-        else asm("v_fma_mix_f32 %0, %1, %2, 0 op_sel_hi:[1,0,0]" : "=v"(d) : "v"(packed), "s"(w));
-    } else {
-        if (HI) asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(d) : "v"(packed), "s"(w), "v"(c));
-        else asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel_hi:[1,0,0]" : "=v"(d) : "v"(packed), "s"(w), "v"(c));
-    }
-    return d;
-}
-template <> struct Buf8<f16_t> {
-    ra_u32x4 r;
-    __device__ __forceinline__ void load(__amdgpu_buffer_rsrc_t rs, int vo, int so) { r = __builtin_amdgcn_raw_buffer_load_b128(rs, vo, so, 0); }
-    template <bool FIRST> __device__ __forceinline__ void fma_into(float w, float (&cs)[8]) const {  // cs += w * pixel (w: wave-uniform)
-        _Pragma("unroll") for (int i = 0; i < 4; ++i) {
-            cs[2 * i] = ra_mix<0, FIRST>(r[i], w, cs[2 * i]);
-            cs[2 * i + 1] = ra_mix<1, FIRST>(r[i], w, cs[2 * i + 1]);
-        }
-    }
-};
-template <> struct Buf8<bf16_t> {
-    ra_u32x4 r;
-    __device__ __forceinline__ void load(__amdgpu_buffer_rsrc_t rs, int vo, int so) { r = __builtin_amdgcn_raw_buffer_load_b128(rs, vo, so, 0); }
-    template <bool FIRST> __device__ __forceinline__ void fma_into(float w, float (&cs)[8]) const {
-        _Pragma("unroll") for (int i = 0; i < 4; ++i) {
-            cs[2 * i] = __builtin_fmaf(__uint_as_float(r[i] << 16), w, FIRST ? 0.f : cs[2 * i]);
-            cs[2 * i + 1] = __builtin_fmaf(__uint_as_float(r[i] & 0xffff0000u), w, FIRST ? 0.f : cs[2 * i + 1]);
-        }
-    }
-};
-template <> struct Buf8<float> {  // (never instantiated for a load: the pair path is for 2-byte features)
-    __device__ __forceinline__ void load(__amdgpu_buffer_rsrc_t, int, int) {}
-    template <bool FIRST> __device__ __forceinline__ void fma_into(float, float (&cs)[8]) const { _Pragma("unroll") for (int i = 0; i < 8; ++i) cs[i] = 0.f; }
-};
-
-// ra_bin_row for 2-byte features, two steps of the outer axis per wave instruction: lanes 0..31 take step 2s, lanes 32..63 step
-// 2s + 1 (voff carries the half's extra step), 8 channels per lane. Each half adds its step into its own 7 x 8 accumulators with
-// its own row of S.wfull; when the stream ends v_permlane32_swap brings the two halves of a pair of bins together (lanes 0..31
-// get the total of the even bin, lanes 32..63 of the odd one) and each half stores its bin: 4 store instructions per bin row.
-// The inner weighted sum is written per channel so that it compiles to v_fma_mix_f32 (fp16 operand, fp32 accumulate: one
-// instruction per element instead of a convert and half a packed multiply-add). Per bin the summation order is: even steps
-// ascending, odd steps ascending, then the two partial sums (fp32; the reference adds all samples in one ascending loop).
-template <int NY, class TI, class TO>
-__device__ __forceinline__ void ra_bin_row_pair(__amdgpu_buffer_rsrc_t rs, int voff, int base, int istride_b, int sstride_b, int ncol, const RaWaveLds& S,
-                                                int half, const float (&wy)[6], float inv_count, TO* __restrict__ outrow, size_t ostride, bool cok, int P) {
-    // wave steps in flight (D * NY loads of 16 bytes per lane in the rotation + (D - 1) * NY for the last steps: <= 60 registers)
-    constexpr int D = NY == 1 ? RA_PD1 : NY == 2 ? RA_PD2 : NY == 3 ? RA_PD3 : RA_PD4;
-    static_assert(2 * D + 1 <= RA_MAXD, "S.wfull is padded with RA_MAXD zero rows");
-    ra_f2 acc[7][4];
-#pragma unroll
-    for (int b = 0; b < 7; ++b)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) acc[b][q] = ra_f2{0.f, 0.f};
-    struct Grp { Buf8<TI> p[NY]; };
-    const int nws = (ncol + 1) >> 1, step2_b = 2 * sstride_b;
-    ra_stream<D, Grp>(
-        nws,
-        [&](Grp& g, int ws) {
-            const int so = base + ws * step2_b;
-#pragma unroll
-            for (int j = 0; j < NY; ++j) g.p[j].load(rs, voff, so + j * istride_b);
-        },
-        [&](Grp& g, int ws) {
-            float cs[8];
-            g.p[0].template fma_into<true>(wy[0], cs);
-#pragma unroll
-            for (int j = 1; j < NY; ++j) g.p[j].template fma_into<false>(wy[j], cs);
-            const float* wr = &S.wfull[2 * ws + half][0];
-            const float4 wa = *reinterpret_cast<const float4*>(wr), wb = *reinterpret_cast<const float4*>(wr + 4);
-            const float wv[7] = {wa.x, wa.y, wa.z, wa.w, wb.x, wb.y, wb.z};
-#pragma unroll
-            for (int b = 0; b < 7; ++b) {
-                const ra_f2 wq = ra_f2{wv[b], wv[b]};
-#pragma unroll
-                for (int q = 0; q < 4; ++q) acc[b][q] = __builtin_elementwise_fma(wq, ra_f2{cs[2 * q], cs[2 * q + 1]}, acc[b][q]);
-            }
-        });
-#pragma unroll
-    for (int k2 = 0; k2 < 4; ++k2) {
-        float tot[8];
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-#pragma unroll
-            for (int e = 0; e < 2; ++e) {
-                const unsigned x = __float_as_uint(acc[2 * k2][q][e]), y = 2 * k2 + 1 < 7 ? __float_as_uint(acc[(2 * k2 + 1) % 7][q][e]) : 0u;
-                const auto sw = __builtin_amdgcn_permlane32_swap(x, y, false, false);
-                tot[2 * q + e] = (__uint_as_float(sw[0]) + __uint_as_float(sw[1])) * inv_count;
-            }
-        const int bin = 2 * k2 + half;
-        if (cok && bin < P) store8<TO>(outrow + (size_t)bin * ostride, tot);
-    }
-}
 
 // The same bin row when its footprint is deeper than 6 pixels along the inner axis (long boxes: up to size / 7 + 2 per bin):
 // the weighted sum of a step runs over the pixels in chunks of 6 loads in flight, inner weights come from the LDS table.
@@ -554,11 +387,11 @@ __device__ __forceinline__ void ra_bin_row_tall(__amdgpu_buffer_rsrc_t rs, int v
 static_assert(RA_GATHER_MAXS >= 2 && RA_GATHER_MAXS <= 3, "gather instantiations exist for S = 1, 2 and 3");
 static_assert(4 * RA_GATHER_MAXS <= RA_MAXC, "the taps of a bin are laid over its RA_MAXC table columns");
 template <int SG, class TI, class TO>
-__device__ __forceinline__ void ra_gather_roi(__amdgpu_buffer_rsrc_t rs, int lane, int sub, int C, int P, int W, const RaWaveLds& S,
+__device__ __forceinline__ void ra_gather_roi(__amdgpu_buffer_rsrc_t rs, int lane, int C, int P, int W, const RaWaveLds& S,
                                               float inv_count, TO* __restrict__ out) {
     constexpr int NYG = SG <= 2 ? SG : 1;  // sample rows whose loads are in flight together
     const int pix_b = C * (int)sizeof(TI), row_b = W * pix_b;
-    for (int ph = sub; ph < P; ph += RA_WPR) {
+    for (int ph = 0; ph < P; ++ph) {
         int yo[SG][2]; float wy[SG][2];
 #pragma unroll
         for (int i = 0; i < SG; ++i)
@@ -619,25 +452,17 @@ __device__ __forceinline__ void ra_gather_roi(__amdgpu_buffer_rsrc_t rs, int lan
     }
 }
 
-// One wave per RoI (RA_WPB RoIs per workgroup, no workgroup barriers). The wave builds the per-axis weight tables in its
-// private LDS slice, picks the shorter side of the footprint as the streamed axis, and then, for each of the 7 bins of the
-// other axis, walks the footprint one pixel column (or row) at a time: the pixels of the step that fall into the bin are
-// reduced with the bin's weights (software pipelined, the next step's loads in flight) and the sum goes into a 3-bin
-// sliding window of register accumulators along the streamed axis.
+// One wave per RoI (RA_WPB RoIs per workgroup, no workgroup barriers); the head of this file describes the tables and the paths.
 #ifndef RA_MINW
-#define RA_MINW (RA_PAIR ? 3 : 4)  // waves per SIMD the register allocation must allow (pair path: 168 registers). One-step path: four, not the
-                                   // five its 94 registers would allow -- end to end (bench.py, four passes in flight, same box, two rounds:
-                                   // scripts/ab_bench6.sh) 1600-1606 img/s with four against 1602-1605 with five, 1585-1595 with the pair
-                                   // path and 1583-1588 with round 5's kernel; the kernel alone 1.094-1.10 / 1.11-1.12 / 1.14-1.19 / 1.21-1.25 ms;
-                                   // five waves keep 5 120 RoIs in flight against 32 MiB of L2: hit rate 0.64 instead of 0.73, +0.6 GB from HBM
+#define RA_MINW 4  // waves per SIMD the register allocation must allow. Four, not the five the 94 registers of a stream would allow: end to
+                   // end (bench.py, four passes in flight, same box, two rounds: scripts/ab_bench6.sh) 1600-1606 img/s with four against
+                   // 1602-1605 with five; five waves keep 5 120 RoIs in flight against 32 MiB of L2: hit rate 0.64 instead of 0.73, +0.6 GB from HBM
 #endif
 template <class TI, class TO, bool OPT>
 __global__ __launch_bounds__(RA_THREADS, (sizeof(TI) == 4 ? 3 : RA_MINW)) void roi_align_kernel(RoiAlignArgs a) {  // (fp32 features: 16-byte pixel images, 3 waves)
     __shared__ RaWaveLds s_all[RA_WPB];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-    // table builders of one RoI: the whole workgroup (RA_WPR > 1) or the RoI's wave; sub = this wave's share of the bin rows
-    const int grp = RA_WPR > 1 ? 0 : wid, sub = RA_WPR > 1 ? wid : 0, gtid = RA_WPR > 1 ? tid : lane;
     // XCD-aware order: workgroup b runs on XCD b % 8, and each XCD walks one CONTIGUOUS share of the list, so RoIs that are
     // neighbours in the list (a.order: in the image) are neighbours in time on one L2. When the list says where its padding rows
     // start (a.order_nvalid), every XCD gets an eighth of the real RoIs followed by its part of the padding, i.e. the same amount
@@ -647,7 +472,7 @@ __global__ __launch_bounds__(RA_THREADS, (sizeof(TI) == 4 ? 3 : RA_MINW)) void r
     {
         const int nwg = gridDim.x, bq = blockIdx.x, q = nwg >> 3, rr = nwg & 7, xcd = bq & 7, idx = bq >> 3;
         const int slot0 = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) * RA_WPB;  // first list slot of this XCD
-        const int pos = idx * RA_WPB + grp;                                                       // this RoI's slot inside the XCD's share
+        const int pos = idx * RA_WPB + wid;                                                       // this RoI's slot inside the XCD's share
         r = (long long)slot0 + pos;
         if (a.order_nvalid) {  // this XCD's slots [slot0, slot0 + cap) take the same fraction of the real RoIs as of all slots
             const long long cap = (long long)(xcd < rr ? q + 1 : q) * RA_WPB, total = (long long)nwg * RA_WPB;
@@ -659,28 +484,21 @@ __global__ __launch_bounds__(RA_THREADS, (sizeof(TI) == 4 ? 3 : RA_MINW)) void r
     }
     if (r >= a.m) return;
     if (a.order) r = a.order[r];
-    RaWaveLds& S = s_all[grp];
+    RaWaveLds& S = s_all[wid];
     const int P = a.pooled, C = a.c;
-    const int CE = C;  // element stride between two bins of a row
-#define RA_CBASE(c0) ((size_t)(c0))
     TO* out = reinterpret_cast<TO*>(a.out) + (size_t)r * P * P * C;
 
     const int b = a.batch_idx[r];
     if (b < 0) {  // padding row: zeros (or nothing: the caller never reads it)
         if (a.no_pad_fill) return;
-        for (int i = gtid * 4; i < P * P * C; i += RA_WPR * 64 * 4) {
+        for (int i = lane * 4; i < P * P * C; i += 64 * 4) {
             float z[4] = {0.f, 0.f, 0.f, 0.f};
             store4<TO>(out + i, z);
         }
         return;
     }
     const float bx1 = a.boxes[r * 4 + 0], by1 = a.boxes[r * 4 + 1], bx2 = a.boxes[r * 4 + 2], by2 = a.boxes[r * 4 + 3];
-    // [d2] assign_boxes_to_levels, evaluated in fp32 exactly as written there
-    float sz = sqrtf((bx2 - bx1) * (by2 - by1));
-    float lvf = floorf((float)a.canonical_level + log2f(sz / (float)a.canonical_size + 1e-8f));
-    float lmin = (float)a.min_level, lmax = (float)(a.min_level + a.num_levels - 1);
-    lvf = fminf(fmaxf(lvf, lmin), lmax);  // NaN (degenerate area) -> lmin via fmaxf
-    const int lv = __builtin_amdgcn_readfirstlane((int)lvf - a.min_level);
+    const int lv = __builtin_amdgcn_readfirstlane(ra_level_of(bx1, by1, bx2, by2, a.canonical_level, a.canonical_size, a.min_level, a.num_levels));
     const int H = a.h[lv], W = a.w[lv];
     const float scale = a.scale[lv];
     const TI* feat = reinterpret_cast<const TI*>(a.data[lv]) + (size_t)b * H * W * C;
@@ -694,7 +512,7 @@ __global__ __launch_bounds__(RA_THREADS, (sizeof(TI) == 4 ? 3 : RA_MINW)) void r
         const int SG = a.opt.sgrid;
         const unsigned long long gl_bytes = (unsigned long long)H * W * C * sizeof(TI);
         if (SG >= 1 && SG <= RA_GATHER_MAXS && !geo.neg && fminf(bw, bh) >= RA_GATHER_BIN * (float)SG && gl_bytes < (1ull << 31)) {
-            for (int e = gtid; e < 2 * P * SG; e += RA_WPR * 64) {  // the P S taps of each axis
+            for (int e = lane; e < 2 * P * SG; e += 64) {  // the P S taps of each axis
                 const int axis = e / (P * SG), rem = e - axis * P * SG, bin = rem / SG, i = rem - bin * SG;
                 int lo = 0, hi = 0; float wl = 0.f, wh = 0.f;
                 const float start = axis ? sw : sh, bs = axis ? bw : bh;
@@ -708,14 +526,14 @@ __global__ __launch_bounds__(RA_THREADS, (sizeof(TI) == 4 ? 3 : RA_MINW)) void r
                 float* t = &S.w[axis][bin][4 * i];
                 t[0] = __int_as_float(lo); t[1] = __int_as_float(hi); t[2] = wl; t[3] = wh;
             }
-            RA_SYNC();
+            ra_wave_sync();
             const __amdgpu_buffer_rsrc_t grs = __builtin_amdgcn_make_buffer_rsrc(const_cast<TI*>(feat), 0, (int)gl_bytes, 0x00020000);
             const float inv_count = 1.0f / count;
             switch (SG) {
-                case 1: ra_gather_roi<1, TI, TO>(grs, lane, sub, C, P, W, S, inv_count, out); break;
-                case 2: ra_gather_roi<2, TI, TO>(grs, lane, sub, C, P, W, S, inv_count, out); break;
+                case 1: ra_gather_roi<1, TI, TO>(grs, lane, C, P, W, S, inv_count, out); break;
+                case 2: ra_gather_roi<2, TI, TO>(grs, lane, C, P, W, S, inv_count, out); break;
 #if RA_GATHER_MAXS >= 3
-                case 3: ra_gather_roi<3, TI, TO>(grs, lane, sub, C, P, W, S, inv_count, out); break;
+                case 3: ra_gather_roi<3, TI, TO>(grs, lane, C, P, W, S, inv_count, out); break;
 #endif
                 default: break;  // (not reached: SG <= RA_GATHER_MAXS)
             }
@@ -728,7 +546,7 @@ __global__ __launch_bounds__(RA_THREADS, (sizeof(TI) == 4 ? 3 : RA_MINW)) void r
     // (a bin's samples span its width + 1 pixels, so only the first ceil(width) + 3 table columns can be non-zero and only
     // those are ever read: build just them)
     const int tcols = geo.tcols;
-    for (int e = gtid; e < 2 * 7 * tcols; e += RA_WPR * 64) {
+    for (int e = lane; e < 2 * 7 * tcols; e += 64) {
         const int axis = e / (7 * tcols), bin = (e / tcols) % 7, col = e % tcols;
         if (bin >= P) continue;
         const float start = axis ? sw : sh, bs = axis ? bw : bh;
@@ -751,10 +569,8 @@ __global__ __launch_bounds__(RA_THREADS, (sizeof(TI) == 4 ? 3 : RA_MINW)) void r
             overflow |= n > tcols;
         }
     }
-    const bool fallback = RA_ANY(overflow);
-#if RA_WPR == 1
+    const bool fallback = __any(overflow);
     ra_wave_sync();
-#endif
 
     // ---- streaming fast path. The footprint is walked along one axis (the "outer" axis, one step per pixel column or row);
     //      per step the pixels of the other ("inner") axis that fall into the current bin are reduced with the bin's weights,
@@ -788,16 +604,13 @@ __global__ __launch_bounds__(RA_THREADS, (sizeof(TI) == 4 ? 3 : RA_MINW)) void r
     }
     const unsigned long long lvl_bytes = (unsigned long long)H * W * C * sizeof(TI);  // one image of this level: the buffer resource's range
     // outer (streamed) axis: the shorter side when it fits the step table, else the other one
-#ifndef RA_AXIS_SELECT
-#define RA_AXIS_SELECT 1
-#endif
-    int oa = (!RA_AXIS_SELECT || ext_n[1] <= ext_n[0]) ? 1 : 0;
+    int oa = ext_n[1] <= ext_n[0] ? 1 : 0;
     if (!ax_ok[oa]) oa ^= 1;
 
     if (ax_ok[oa] && lvl_bytes < (1ull << 31)) {
         const int ia = oa ^ 1;
         const int os = ext_lo[oa], nstep = ext_n[oa];
-        for (int sl = gtid; sl < nstep + RA_MAXD; sl += RA_WPR * 64) {  // per-step table: the weight of this outer pixel in each bin
+        for (int sl = lane; sl < nstep + RA_MAXD; sl += 64) {  // per-step table: the weight of this outer pixel in each bin
             const int x = os + sl;
 #pragma unroll
             for (int bb = 0; bb < 8; ++bb) {
@@ -806,40 +619,24 @@ __global__ __launch_bounds__(RA_THREADS, (sizeof(TI) == 4 ? 3 : RA_MINW)) void r
                 S.wfull[sl][bb] = wv;
             }
         }
-        RA_SYNC();
+        ra_wave_sync();
         const float inv_count = 1.0f / count;
         const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<TI*>(feat), 0, (int)lvl_bytes, 0x00020000);
         // byte strides of one step along the inner / outer axis, and the element stride between two consecutive output bins of the outer axis
         const int rowstride_b = W * C * (int)sizeof(TI), pix_b = C * (int)sizeof(TI);
         const int istride_b = ia == 0 ? rowstride_b : pix_b, sstride_b = ia == 0 ? pix_b : rowstride_b;
-        const size_t ostride = oa == 1 ? (size_t)CE : (size_t)P * CE;
-        for (int pb = sub; pb < P; pb += RA_WPR) {  // bins along the inner axis
+        const size_t ostride = oa == 1 ? (size_t)C : (size_t)P * C;
+        for (int pb = 0; pb < P; ++pb) {  // bins along the inner axis
             const int i0 = __builtin_amdgcn_readfirstlane(S.lo[ia][pb]), ni = __builtin_amdgcn_readfirstlane(S.n[ia][pb]);
             float wi[6];  // wave-uniform inner weights (live in scalar registers)
 #pragma unroll
             for (int j = 0; j < 6; ++j) wi[j] = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(j < ni ? S.w[ia][pb][j] : 0.f)));
             const int base = i0 * istride_b + os * sstride_b;
-            if (RA_PAIR && sizeof(TI) == 2 && C % 8 == 0 && ni >= 1 && ni <= 4 && nstep > 0) {  // two steps per wave instruction, 8 channels per lane
-                const int half = lane >> 5;
-                for (int cb0 = 0; cb0 < C; cb0 += 256) {
-                    const int c0 = cb0 + (lane & 31) * 8;
-                    const bool cok = c0 < C;
-                    const int voff = (cok ? c0 : 0) * (int)sizeof(TI) + half * sstride_b;
-                    TO* outrow = out + (size_t)pb * (oa == 1 ? (size_t)P * CE : (size_t)CE) + RA_CBASE(c0);
-                    switch (ni) {
-                        case 1: ra_bin_row_pair<1, TI, TO>(rs, voff, base, istride_b, sstride_b, nstep, S, half, wi, inv_count, outrow, ostride, cok, P); break;
-                        case 2: ra_bin_row_pair<2, TI, TO>(rs, voff, base, istride_b, sstride_b, nstep, S, half, wi, inv_count, outrow, ostride, cok, P); break;
-                        case 3: ra_bin_row_pair<3, TI, TO>(rs, voff, base, istride_b, sstride_b, nstep, S, half, wi, inv_count, outrow, ostride, cok, P); break;
-                        default: ra_bin_row_pair<4, TI, TO>(rs, voff, base, istride_b, sstride_b, nstep, S, half, wi, inv_count, outrow, ostride, cok, P); break;
-                    }
-                }
-                continue;
-            }
             for (int cb0 = 0; cb0 < C; cb0 += 256) {
                 const int c0 = cb0 + lane * 4;
                 const bool cok = c0 < C;
                 const int voff = (cok ? c0 : 0) * (int)sizeof(TI);
-                TO* outrow = out + (size_t)pb * (oa == 1 ? (size_t)P * CE : (size_t)CE) + RA_CBASE(c0);
+                TO* outrow = out + (size_t)pb * (oa == 1 ? (size_t)P * C : (size_t)C) + c0;
                 switch (nstep > 0 ? (ni > 6 ? 7 : ni) : 0) {  // (no step: the pipelined loop would have nothing valid to prefetch)
                     case 1: ra_bin_row<1, TI, TO>(rs, voff, base, istride_b, sstride_b, nstep, S, wi, inv_count, outrow, ostride, cok, P); break;
                     case 2: ra_bin_row<2, TI, TO>(rs, voff, base, istride_b, sstride_b, nstep, S, wi, inv_count, outrow, ostride, cok, P); break;
@@ -859,7 +656,7 @@ __global__ __launch_bounds__(RA_THREADS, (sizeof(TI) == 4 ? 3 : RA_MINW)) void r
     }
 
     // ---- general paths: per-bin separable footprint, or (table overflow) the per-sample 4-tap loop ----
-    for (int ph = sub; ph < P; ph += RA_WPR) {
+    for (int ph = 0; ph < P; ++ph) {
         for (int c0 = lane * 4; c0 < C; c0 += 256) {
             for (int pw = 0; pw < P; ++pw) {
                 float acc[4] = {0.f, 0.f, 0.f, 0.f};
@@ -895,7 +692,7 @@ __global__ __launch_bounds__(RA_THREADS, (sizeof(TI) == 4 ? 3 : RA_MINW)) void r
                 }
 #pragma unroll
                 for (int k = 0; k < 4; ++k) acc[k] = acc[k] / count;
-                store4<TO>(out + (size_t)(ph * P + pw) * CE + RA_CBASE(c0), acc);
+                store4<TO>(out + (size_t)(ph * P + pw) * C + c0, acc);
             }
         }
     }
@@ -920,19 +717,12 @@ static osr_status roi_align_fwd_impl(const osr_pyramid* f, int32_t feat_dtype, i
                                      const osr_roi_options* opt = nullptr) {
     OSR_REQUIRE(f && boxes && batch_idx && out, OSR_ERR_INVALID_ARG, "osr_roi_align_fwd: null pointer");
     RA_REQUIRE_OPT(opt, "osr_roi_align_fwd");
-    OSR_REQUIRE(f->num_levels >= 1 && f->num_levels <= 4, OSR_ERR_INVALID_ARG, "osr_roi_align_fwd: 1..4 levels, got %d", f->num_levels);
-    OSR_REQUIRE(pooled >= 1 && pooled <= 7, OSR_ERR_UNSUPPORTED, "osr_roi_align_fwd: pooled size 1..7, got %d", pooled);
-    OSR_REQUIRE(f->c > 0 && f->c % 4 == 0, OSR_ERR_UNSUPPORTED, "osr_roi_align_fwd: channels must be a multiple of 4, got %d", f->c);
+    RoiAlignArgs a;
+    if (const osr_status e = ra_take_pyramid("osr_roi_align_fwd", f, pooled, false, &a)) return e;
     OSR_REQUIRE(osr_dtype_ok(feat_dtype) && osr_dtype_ok(out_dtype), OSR_ERR_INVALID_ARG, "osr_roi_align_fwd: bad dtype");
     OSR_REQUIRE(n >= 1 && m >= 0 && m < (1ll << 31), OSR_ERR_INVALID_ARG, "osr_roi_align_fwd: bad n/m");
     OSR_REQUIRE(canonical_size > 0, OSR_ERR_INVALID_ARG, "osr_roi_align_fwd: canonical_size must be > 0");
     if (m == 0) return OSR_OK;
-    RoiAlignArgs a;
-    for (int l = 0; l < 4; ++l) {
-        int s = l < f->num_levels ? l : 0;
-        OSR_REQUIRE(f->data[s] && f->h[s] > 0 && f->w[s] > 0, OSR_ERR_INVALID_ARG, "osr_roi_align_fwd: bad level %d", s);
-        a.data[l] = f->data[s]; a.h[l] = f->h[s]; a.w[l] = f->w[s]; a.scale[l] = f->scale[s];
-    }
     a.num_levels = f->num_levels; a.c = f->c; a.boxes = boxes; a.batch_idx = batch_idx; a.m = m;
     a.pooled = pooled; a.canonical_level = canonical_level; a.canonical_size = canonical_size; a.min_level = min_level;
     a.out = out; a.order = order; a.order_nvalid = order ? order_nvalid : nullptr;
@@ -1014,10 +804,7 @@ __device__ __forceinline__ int ra_bucket_of(const RoiOrderArgs& a, long long r) 
     const int b = a.batch_idx[r];
     if (b < 0 || b >= a.n) return a.n * RA_BUCKETS;
     const float4 bx = *reinterpret_cast<const float4*>(a.boxes + r * 4);
-    float sz = sqrtf((bx.z - bx.x) * (bx.w - bx.y));
-    float lvf = floorf((float)a.canonical_level + log2f(sz / (float)a.canonical_size + 1e-8f));
-    lvf = fminf(fmaxf(lvf, (float)a.min_level), (float)(a.min_level + a.num_levels - 1));
-    const int lv = (int)lvf - a.min_level;
+    const int lv = ra_level_of(bx.x, bx.y, bx.z, bx.w, a.canonical_level, a.canonical_size, a.min_level, a.num_levels);
     int base = 0;
     for (int l = 0; l < lv; ++l) base += ((a.h[l] + 31) >> 5) * ((a.w[l] + 31) >> 5);
     const int tnx = (a.w[lv] + 31) >> 5, tny = (a.h[lv] + 31) >> 5;
@@ -1125,10 +912,7 @@ extern "C" osr_status osr_roi_locality_order(const osr_pyramid* f, int32_t n, co
 // RoI, 4 channels per lane, fp32 atomic adds (several RoIs overlap on the same pixels; the summation order, and with it the
 // last bits of the result, therefore vary from run to run -- the reference's atomicAdd backward does the same).
 // ------------------------------------------------------------------------------------------------------
-struct RoiAlignBwdArgs {
-    float* data[4];
-    int h[4], w[4];
-    float scale[4];
+struct RoiAlignBwdArgs : RaLevels {  // (data: fp32)
     int num_levels, c;
     const float* boxes;
     const int* batch_idx;
@@ -1174,14 +958,10 @@ __global__ __launch_bounds__(RA_BWD_WPB * 64) void roi_align_bwd_kernel(RoiAlign
     const int b = a.batch_idx[r];
     if (b < 0) return;
     const float bx1 = a.boxes[r * 4 + 0], by1 = a.boxes[r * 4 + 1], bx2 = a.boxes[r * 4 + 2], by2 = a.boxes[r * 4 + 3];
-    float sz = sqrtf((bx2 - bx1) * (by2 - by1));
-    float lvf = floorf((float)a.canonical_level + log2f(sz / (float)a.canonical_size + 1e-8f));
-    float lmin = (float)a.min_level, lmax = (float)(a.min_level + a.num_levels - 1);
-    lvf = fminf(fmaxf(lvf, lmin), lmax);
-    const int lv = __builtin_amdgcn_readfirstlane((int)lvf - a.min_level);
+    const int lv = __builtin_amdgcn_readfirstlane(ra_level_of(bx1, by1, bx2, by2, a.canonical_level, a.canonical_size, a.min_level, a.num_levels));
     const int H = a.h[lv], W = a.w[lv];
     const float scale = a.scale[lv];
-    float* feat = a.data[lv] + (size_t)b * H * W * C;
+    float* feat = reinterpret_cast<float*>(a.data[lv]) + (size_t)b * H * W * C;
     const RaGeom geo = ra_geometry<OPT>(a.opt, bx1, by1, bx2, by2, scale, P);
     const float sw = geo.sw, sh = geo.sh, bw = geo.bw, bh = geo.bh, count = geo.count;
     const int gh = geo.gh, gw = geo.gw;
@@ -1390,18 +1170,11 @@ extern "C" osr_status osr_roi_align_bwd_opt(const osr_pyramid* dfeat, int32_t n,
                                             const void* dout, int32_t dout_dtype, const osr_roi_options* options, void* stream) {
     OSR_REQUIRE(dfeat && boxes && batch_idx && dout, OSR_ERR_INVALID_ARG, "osr_roi_align_bwd: null pointer");
     RA_REQUIRE_OPT(options, "osr_roi_align_bwd");
-    OSR_REQUIRE(dfeat->num_levels >= 1 && dfeat->num_levels <= 4, OSR_ERR_INVALID_ARG, "osr_roi_align_bwd: 1..4 levels, got %d", dfeat->num_levels);
-    OSR_REQUIRE(pooled >= 1 && pooled <= 7, OSR_ERR_UNSUPPORTED, "osr_roi_align_bwd: pooled size 1..7, got %d", pooled);
-    OSR_REQUIRE(dfeat->c > 0 && dfeat->c % 4 == 0, OSR_ERR_UNSUPPORTED, "osr_roi_align_bwd: channels must be a multiple of 4, got %d", dfeat->c);
+    RoiAlignBwdArgs a;
+    if (const osr_status e = ra_take_pyramid("osr_roi_align_bwd", dfeat, pooled, false, &a)) return e;
     OSR_REQUIRE(osr_dtype_ok(dout_dtype), OSR_ERR_INVALID_ARG, "osr_roi_align_bwd: bad dtype");
     OSR_REQUIRE(n >= 1 && m >= 0 && m < (1ll << 31) && canonical_size > 0, OSR_ERR_INVALID_ARG, "osr_roi_align_bwd: bad n / m / canonical_size");
     if (m == 0) return OSR_OK;
-    RoiAlignBwdArgs a;
-    for (int l = 0; l < 4; ++l) {
-        int s = l < dfeat->num_levels ? l : 0;
-        OSR_REQUIRE(dfeat->data[s] && dfeat->h[s] > 0 && dfeat->w[s] > 0, OSR_ERR_INVALID_ARG, "osr_roi_align_bwd: bad level %d", s);
-        a.data[l] = (float*)dfeat->data[s]; a.h[l] = dfeat->h[s]; a.w[l] = dfeat->w[s]; a.scale[l] = dfeat->scale[s];
-    }
     a.num_levels = dfeat->num_levels; a.c = dfeat->c; a.boxes = boxes; a.batch_idx = batch_idx; a.m = m;
     a.pooled = pooled; a.canonical_level = canonical_level; a.canonical_size = canonical_size; a.min_level = min_level;
     a.dout = dout;
@@ -1439,10 +1212,7 @@ extern "C" osr_status osr_roi_align_bwd_opt(const osr_pyramid* dfeat, int32_t n,
 // The RoI list must be image-major with a fixed stride (rows [b S, (b + 1) S) belong to image b; batch_idx < 0 = padding).
 // ------------------------------------------------------------------------------------------------------
 #define RD_T 8
-struct RoiBwdDenseArgs {
-    void* data[4];
-    int h[4], w[4];
-    float scale[4];
+struct RoiBwdDenseArgs : RaLevels {
     int tiles_x[4], tiles_y[4], tile_off[5];  // tile grid of one image per level; first workgroup of each level
     int num_levels, c, n, S;
     const float* boxes;
@@ -1475,7 +1245,6 @@ __global__ __launch_bounds__(256, RD_MINW) void roi_align_bwd_dense_kernel(RoiBw
     const int ty0 = (tt / a.tiles_x[lv]) * RD_T, tx0 = (tt % a.tiles_x[lv]) * RD_T;
     const int H = a.h[lv], W = a.w[lv], P = a.pooled, C = a.c;
     const float scale = a.scale[lv];
-    const float lmin = (float)a.min_level, lmax = (float)(a.min_level + a.num_levels - 1);
 
     // ---- 1. which of the image's RoIs reach this tile (list order is kept: the summation order is fixed) ----
     for (int j = tid; j < a.S; j += 256) {
@@ -1483,10 +1252,7 @@ __global__ __launch_bounds__(256, RD_MINW) void roi_align_bwd_dense_kernel(RoiBw
         bool hit = false;
         if (a.batch_idx[r] == b) {
             const float bx1 = a.boxes[r * 4 + 0], by1 = a.boxes[r * 4 + 1], bx2 = a.boxes[r * 4 + 2], by2 = a.boxes[r * 4 + 3];
-            const float sz = sqrtf((bx2 - bx1) * (by2 - by1));
-            float lvf = floorf((float)a.canonical_level + log2f(sz / (float)a.canonical_size + 1e-8f));
-            lvf = fminf(fmaxf(lvf, lmin), lmax);
-            if ((int)lvf - a.min_level == lv) {
+            if (ra_level_of(bx1, by1, bx2, by2, a.canonical_level, a.canonical_size, a.min_level, a.num_levels) == lv) {
                 float sw = bx1 * scale - 0.5f, sh = by1 * scale - 0.5f, ew = bx2 * scale - 0.5f, eh = by2 * scale - 0.5f;
                 if (OPT) {  // the end the samples are laid out to: start + the (clamped) size
                     const RaGeom geo = ra_geometry<true>(a.opt, bx1, by1, bx2, by2, scale, P);
@@ -1623,19 +1389,14 @@ extern "C" osr_status osr_roi_align_bwd_dense_opt(const osr_pyramid* dfeat, int3
     OSR_REQUIRE(dfeat && boxes && batch_idx && dout, OSR_ERR_INVALID_ARG, "osr_roi_align_bwd_dense: null pointer");
     RA_REQUIRE_OPT(options, "osr_roi_align_bwd_dense");
     OSR_REQUIRE(out_dtype == OSR_F32 || out_dtype == dout_dtype, OSR_ERR_UNSUPPORTED, "osr_roi_align_bwd_dense: out_dtype must be f32 or dout's dtype");
-    OSR_REQUIRE(dfeat->num_levels >= 1 && dfeat->num_levels <= 4, OSR_ERR_INVALID_ARG, "osr_roi_align_bwd_dense: 1..4 levels, got %d", dfeat->num_levels);
-    OSR_REQUIRE(pooled >= 1 && pooled <= 7, OSR_ERR_UNSUPPORTED, "osr_roi_align_bwd_dense: pooled size 1..7, got %d", pooled);
-    OSR_REQUIRE(dfeat->c > 0 && dfeat->c <= 256, OSR_ERR_UNSUPPORTED, "osr_roi_align_bwd_dense: at most 256 channels, got %d", dfeat->c);
+    RoiBwdDenseArgs a;
+    if (const osr_status e = ra_take_pyramid("osr_roi_align_bwd_dense", dfeat, pooled, true, &a)) return e;
     OSR_REQUIRE(osr_dtype_ok(dout_dtype), OSR_ERR_INVALID_ARG, "osr_roi_align_bwd_dense: bad dtype");
     OSR_REQUIRE(n >= 1 && m >= 0 && canonical_size > 0, OSR_ERR_INVALID_ARG, "osr_roi_align_bwd_dense: bad n / m / canonical_size");
     OSR_REQUIRE(rois_per_image >= 0 && rois_per_image <= 1024 && m == (int64_t)n * rois_per_image, OSR_ERR_UNSUPPORTED,
                 "osr_roi_align_bwd_dense: the RoI list must be image-major with a fixed stride <= 1024 (m = %lld, n = %d, stride %d)", (long long)m, n, rois_per_image);
-    RoiBwdDenseArgs a;
     long long off = 0;
     for (int l = 0; l < 4; ++l) {
-        const int s = l < dfeat->num_levels ? l : 0;
-        OSR_REQUIRE(dfeat->data[s] && dfeat->h[s] > 0 && dfeat->w[s] > 0, OSR_ERR_INVALID_ARG, "osr_roi_align_bwd_dense: bad level %d", s);
-        a.data[l] = (void*)dfeat->data[s]; a.h[l] = dfeat->h[s]; a.w[l] = dfeat->w[s]; a.scale[l] = dfeat->scale[s];
         a.tiles_x[l] = (a.w[l] + RD_T - 1) / RD_T; a.tiles_y[l] = (a.h[l] + RD_T - 1) / RD_T;
         a.tile_off[l] = (int)off;
         if (l < dfeat->num_levels) off += (long long)n * a.tiles_x[l] * a.tiles_y[l];

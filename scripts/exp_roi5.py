@@ -1,6 +1,6 @@
 """Experiment driver (not part of the product): forward RoIAlign on the bench's proposals, list order against the locality order
 (osr_roi_locality_order), timed kernel-only with HIP events; checks that the two outputs are bit-identical and prints the
-histogram of RoIs per level. Build variants (-DRA_WPR=1|7 ...) are compared by scripts/ab_roi.sh on one box."""
+histogram of RoIs per level."""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import __graft_entry__ as ge

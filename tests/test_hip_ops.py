@@ -412,6 +412,61 @@ def test_roi_align_linear_ramp_is_exact(ops):
             assert out[ph, pw].item() == pytest.approx(0.5 * cx - 0.25 * cy + 3.0, rel=1e-5)
 
 
+def _level_case():
+    """Fourteen boxes centred at (256, 256) of a 512 x 512 image and the level [d2] assign_boxes_to_levels gives each (include/osr.h:
+    floor(4 + log2(sqrt(area) / 224 + 1e-8)) clamped to [2, 5], counted from 2), in numpy float32. Twelve squares: sides 224 x
+    {1/4, 1/2, 1, 2} -- on a level boundary, where sqrt, the quotient and log2 are all exact -- and 5 % either side of each. Two
+    degenerate boxes, zero area and x2 < x1 (negative area, NaN side), which the rule puts on the first level."""
+    f32 = np.float32
+    sides = [224.0 * p * q for p in (0.25, 0.5, 1.0, 2.0) for q in (0.95, 1.0, 1.05)]
+    b = np.array([[256 - s / 2, 256 - s / 2, 256 + s / 2, 256 + s / 2] for s in sides] +
+                 [[256.0, 256.0, 256.0, 256.0], [300.0, 200.0, 200.0, 300.0]], dtype=f32)
+    with np.errstate(invalid="ignore"):
+        lv = np.floor(f32(4) + np.log2(np.sqrt((b[:, 2] - b[:, 0]) * (b[:, 3] - b[:, 1])) / f32(224) + f32(1e-8)))
+    assert lv.dtype == f32 and np.isnan(lv[13]) and not np.isnan(lv[:13]).any()
+    level = (np.fmin(np.fmax(lv, f32(2)), f32(5)).astype(np.int64) - 2).tolist()   # fmax: NaN -> 2
+    assert level == [0, 0, 0, 0, 1, 1, 1, 2, 2, 2, 3, 3, 0, 0]
+    return torch.from_numpy(b), level
+
+
+@pytest.mark.parametrize("aligned,sampling_ratio", [(True, 0), (False, 2)], ids=["default", "ROIAlign-S2"])
+def test_roi_align_forward_order_and_both_backwards_agree_on_the_level(ops, aligned, sampling_ratio):
+    """Level l of the pyramid holds the constant l + 1, so a pooled row names the level it was read from, and the gradient of one box
+    may be non-zero in one map only: the one the forward read. Every sample of the twelve squares lies inside its map, so each of a
+    box's P P C bins hands its whole upstream 1 down: the map's sum is P P C. The two degenerate boxes have no sample under the
+    default options (a 0 x 0 adaptive grid: zeros forward, no gradient in ANY map); with aligned=False and a fixed grid they are one
+    pixel wide with 2 x 2 samples per bin and must behave like the others, on level 0."""
+    P, C = 7, 4
+    shapes, scales = [(128, 128), (64, 64), (32, 32), (16, 16)], (0.25, 0.125, 0.0625, 0.03125)
+    feats = [torch.full((1, h, w, C), float(l + 1), device=DEV) for l, (h, w) in enumerate(shapes)]
+    boxes_cpu, level = _level_case()
+    m, boxes, bidx = len(level), boxes_cpu.to(DEV), torch.zeros(len(level), dtype=torch.int32, device=DEV)
+    has_samples = [i < 12 or not aligned for i in range(m)]
+
+    out = ops.roi_align(feats, scales, boxes, bidx, P, torch.float32, aligned=aligned, sampling_ratio=sampling_ratio).cpu()
+    for i in range(m):
+        want = float(level[i] + 1) if has_samples[i] else 0.0
+        print(f"box {i}: forward min {float(out[i].min()):.6f} max {float(out[i].max()):.6f}, expected {want}")
+        assert_close(out[i], torch.full((P, P, C), want), rtol=1e-4, name=f"forward, box {i}")
+
+    full = ops.roi_locality_order(feats, scales, boxes, bidx)
+    assert full.shape == (m + 1,) and int(full[m]) == m
+    assert torch.equal(torch.sort(full[:m].long()).values.cpu(), torch.arange(m))
+
+    dout = torch.ones(1, P, P, C, device=DEV)
+    sums = torch.stack([torch.stack([torch.stack([f.sum(), f.abs().max()]) for f in ops.roi_align_bwd(
+        dout, shapes, 1, scales, boxes[i:i + 1].contiguous(), bidx[i:i + 1].contiguous(), rois_per_image=rpi, aligned=aligned,
+        sampling_ratio=sampling_ratio)]) for i in range(m) for rpi in (None, 1)]).double().cpu().view(m, 2, 4, 2)
+    for i in range(m):
+        for k, form in enumerate(("scatter", "dense")):
+            print(f"box {i} {form}: sum / max |g| per level {sums[i, k].tolist()}")
+            for l in range(4):
+                if l == level[i] and has_samples[i]:
+                    assert abs(float(sums[i, k, l, 0]) - P * P * C) <= 1e-3 * P * P * C, f"box {i} {form}: level {l} sum {float(sums[i, k, l, 0])}"
+                else:
+                    assert float(sums[i, k, l, 1]) == 0.0, f"box {i} {form}: gradient in level {l}, expected level {level[i]}"
+
+
 def test_linear_split_k_tail_round(ops, osr):
     """Deep-K FC layers whose tile grid leaves a mostly empty last dispatch round are cut along K for that round (three launches:
     full rounds, ksplit partial-sum launches of the tail tiles, fixed-order reduction + epilogue). Same result as the single launch
