@@ -1222,9 +1222,19 @@ static bool conv64_plan_split(const Conv64Args& a, SplitPlan* sp) {
 
 template <class TO>
 __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restrict__ ws, int ksplit, long long split_stride, long long n4, int cout,
-                                                            const float* __restrict__ bias, int relu, TO* __restrict__ out) {
+                                                            const float* __restrict__ bias, int relu, TO* __restrict__ out,
+                                                            const int32_t* __restrict__ seg_counts, long long seg_rows, int bm, long long m_tail0, long long M) {
     // out[i] = act(sum_s ws[s][i] + bias[i % cout]), four elements per thread (cout % 8 == 0)
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
+        if (seg_counts) {  // segmented rows: the tail launch skipped the M tiles without a data row (same test), their slab rows hold nothing and their output rows stay unwritten
+            const long long m0 = (m_tail0 + i * 4 / cout) / bm * bm, mend = m0 + bm < M ? m0 + bm : M;
+            bool any = false;
+            for (long long sg = m0 / seg_rows; sg * seg_rows < mend; ++sg) {
+                const long long lo = m0 > sg * seg_rows ? m0 : sg * seg_rows, hi = sg * seg_rows + seg_counts[sg];
+                any |= (hi < mend ? hi : mend) > lo;
+            }
+            if (!any) continue;
+        }
         float4 v = *reinterpret_cast<const float4*>(ws + i * 4);
         for (int s = 1; s < ksplit; ++s) {
             const float4 u = *reinterpret_cast<const float4*>(ws + s * split_stride + i * 4);
@@ -1270,7 +1280,8 @@ static osr_status conv64_launch(Conv64Args& a, hipStream_t st) {
         long long blocks = (n4 + 255) / 256;
         if (blocks > 2048) blocks = 2048;
         hipLaunchKernelGGL(splitk_reduce_kernel<TO>, dim3((unsigned)blocks), dim3(256), 0, st, reinterpret_cast<const float*>(a.p.workspace), sp.ksplit,
-                           t.split_stride, n4, a.p.cout, a.bias, a.p.relu, reinterpret_cast<TO*>(a.out) + sp.m_tail0 * a.p.cout);
+                           t.split_stride, n4, a.p.cout, a.bias, a.p.relu, reinterpret_cast<TO*>(a.out) + sp.m_tail0 * a.p.cout,
+                           a.p.row_seg_counts, (long long)a.p.row_seg_rows, c->bm, sp.m_tail0, a.M);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) { osr_set_error("osr_conv2d_fwd(bk64, split-K tail): launch failed: %s", hipGetErrorString(e)); return OSR_ERR_LAUNCH; }
         return OSR_OK;
