@@ -416,6 +416,9 @@ typedef struct osr_pyramid {
     const void* data[OSR_MAX_LEVELS];
 } osr_pyramid;
 
+/* pooled: 1 .. OSR_ROI_MAX_POOLED_FWD for the four forward entry points (1..7: the box pooler's kernels; 8..14, the mask head's 14 x 14
+ * pooler: a per-sample kernel of its own, same options, same order independence); the backward entry points take 1..7. */
+#define OSR_ROI_MAX_POOLED_FWD 14
 osr_status osr_roi_align_fwd(const osr_pyramid* feats, int32_t feat_dtype, int32_t n, const float* boxes,
                              const int32_t* batch_idx, int64_t m, int32_t pooled, int32_t canonical_level,
                              int32_t canonical_size, int32_t min_level, void* out, int32_t out_dtype, void* stream);
@@ -567,6 +570,28 @@ osr_status osr_assemble_detections(const float* k_boxes, const float* k_scores, 
 osr_status osr_detector_postprocess(const float* boxes, const float* scores, const int64_t* classes, const int32_t* count,
                                     int32_t n, int32_t cap, const float* scale_xy, const int32_t* out_hw, float* out_boxes,
                                     float* out_scores, int64_t* out_classes, int32_t* out_count, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * Mask head tail ([d2] MaskRCNNConvUpsampleHead.deconv + ReLU + predictor, mask_rcnn_inference; csrc/osr_mask_head.hip).
+ * x: (r, s, s, cin) NHWC in `dtype` (the output of the mask_fcn convolutions). One launch computes
+ * ConvTranspose2d(cin -> cmid, 2 x 2, stride 2) + bias + ReLU, the 1 x 1 predictor row of each RoI's class and the sigmoid:
+ * probs (r, 2s, 2s) fp32. The (r, 2s, 2s, cmid) intermediate is never stored; it stays in fp32 up to the dot product.
+ * w_packed: the deconv weight in `dtype`, in MFMA fragment order (host/weights.py pack_deconv_weight): with t = 2 dy + dx and
+ *   E = 8 (f16 / bf16) or 4 (f32), element [t][n / 32][k / 2E][(k / E) % 2][n % 32][k % E] = weight[k][n][dy][dx].
+ * bias (cmid), pred_w (num_rows, cmid), pred_b (num_rows): fp32. num_rows == 1: class-agnostic, row 0 for every RoI with class >= 0
+ * (classes may be NULL: every RoI); otherwise row classes[i].
+ * rows_valid / seg_rows: as osr_pln_tail -- the RoIs are segments of seg_rows of which the first rows_valid[segment] exist (NULL:
+ * all exist). RoIs that do not exist, and RoIs whose class is negative or not a predictor row, are written as zeros.
+ * cin, cmid: multiples of 64, cin <= 448. r == 0: OSR_OK without a launch. Repeats are bit-identical. */
+osr_status osr_mask_upsample_predict(const void* x, int32_t dtype, int64_t r, int32_t s, int32_t cin, int32_t cmid,
+                                     const void* w_packed, const float* bias, const float* pred_w, const float* pred_b,
+                                     int32_t num_rows, const int64_t* classes, const int32_t* rows_valid, int32_t seg_rows,
+                                     float* probs, void* stream);
+/* [d2] paste_masks_in_image (_do_paste_mask, skip_empty=False) for ONE image: probs (r, m, m) fp32, boxes (r, 4) at the output
+ * resolution -> out (r, out_h, out_w) uint8, 1 where the bilinear sample (zeros outside the map) of mask i at
+ * u = (x + 0.5 - x0) / (x1 - x0) * m - 0.5, v likewise, is >= threshold, else 0. Every byte of out is written. r <= 65535. */
+osr_status osr_paste_masks(const float* probs, const float* boxes, int64_t r, int32_t m, int32_t out_h, int32_t out_w,
+                           float threshold, uint8_t* out, void* stream);
 
 /* =========================================================================================================
  * Training step, forward half: targets and losses. Gradients are not

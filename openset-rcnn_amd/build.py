@@ -32,6 +32,7 @@ SOURCES = {
     "osr_rpn.hip": ["-ffp-contract=off"],
     "osr_roi_align.hip": ["-ffp-contract=off"],
     "osr_det_tail.hip": ["-ffp-contract=off"],
+    "osr_mask_head.hip": [],
     "osr_train_fwd.hip": ["-ffp-contract=off"],
     "osr_rpn_sparse.hip": ["-ffp-contract=off"],
     "osr_std_train.hip": ["-ffp-contract=off"],

@@ -83,9 +83,10 @@ struct RaLevels {
 };
 // What every entry point asks of the pyramid and the pooled size, and the fill of the four slots. dense: osr_roi_align_bwd_dense's
 // channel rule (a workgroup's four waves cover 256 channels) instead of the 4 channels per lane of the other two kernels.
-static osr_status ra_take_pyramid(const char* name, const osr_pyramid* f, int pooled, bool dense, RaLevels* a) {
+// pmax: 7 for the backward entry points (their kernels hold 7 bins of state per axis), OSR_ROI_MAX_POOLED_FWD for the forward.
+static osr_status ra_take_pyramid(const char* name, const osr_pyramid* f, int pooled, bool dense, RaLevels* a, int pmax = 7) {
     OSR_REQUIRE(f->num_levels >= 1 && f->num_levels <= 4, OSR_ERR_INVALID_ARG, "%s: 1..4 levels, got %d", name, f->num_levels);
-    OSR_REQUIRE(pooled >= 1 && pooled <= 7, OSR_ERR_UNSUPPORTED, "%s: pooled size 1..7, got %d", name, pooled);
+    OSR_REQUIRE(pooled >= 1 && pooled <= pmax, OSR_ERR_UNSUPPORTED, "%s: pooled size 1..%d, got %d", name, pmax, pooled);
     if (dense) OSR_REQUIRE(f->c > 0 && f->c <= 256, OSR_ERR_UNSUPPORTED, "%s: at most 256 channels, got %d", name, f->c);
     else OSR_REQUIRE(f->c > 0 && f->c % 4 == 0, OSR_ERR_UNSUPPORTED, "%s: channels must be a multiple of 4, got %d", name, f->c);
     for (int l = 0; l < 4; ++l) {
@@ -698,6 +699,71 @@ __global__ __launch_bounds__(RA_THREADS, (sizeof(TI) == 4 ? 3 : RA_MINW)) void r
     }
 }
 
+// ---- pooled sizes 8 .. OSR_ROI_MAX_POOLED_FWD (the mask head's 14 x 14 pooler) ------------------------------------------------
+// The kernel above keeps seven bins of state per axis (tables, accumulators) and is left as it is. The larger grids are pooled for
+// TEST.DETECTIONS_PER_IMAGE RoIs per image, about 2 % of the box pooler's list, so they take torchvision's loop as written: one
+// workgroup per RoI, one thread per (bin, 4 channels), every sample of the bin with its four taps, in the reference's order. With
+// 256 channels a wave is one bin (uniform control flow, one 512-byte line per tap). Generic in the grid, the offset and the clamp
+// (ra_geometry<true> with the options of the call, {0.5, 0, adaptive} for the default pair); no LDS, no tables, no size limit.
+#define RA_BIG_THREADS 256
+template <class TI, class TO>
+__global__ __launch_bounds__(RA_BIG_THREADS) void roi_align_big_kernel(RoiAlignArgs a) {
+    long long r = blockIdx.x;
+    if (r >= a.m) return;
+    if (a.order) r = a.order[r];
+    const int P = a.pooled, C = a.c, cq = C >> 2, total = P * P * cq;
+    const int tid = threadIdx.x;
+    TO* out = reinterpret_cast<TO*>(a.out) + (size_t)r * P * P * C;
+    const int b = a.batch_idx[r];
+    if (b < 0) {  // padding row: zeros (or nothing: the caller never reads it)
+        if (a.no_pad_fill) return;
+        const float z[4] = {0.f, 0.f, 0.f, 0.f};
+        for (int e = tid; e < total; e += RA_BIG_THREADS) store4<TO>(out + (size_t)e * 4, z);
+        return;
+    }
+    const float bx1 = a.boxes[r * 4 + 0], by1 = a.boxes[r * 4 + 1], bx2 = a.boxes[r * 4 + 2], by2 = a.boxes[r * 4 + 3];
+    const int lv = ra_level_of(bx1, by1, bx2, by2, a.canonical_level, a.canonical_size, a.min_level, a.num_levels);
+    const int H = a.h[lv], W = a.w[lv];
+    const TI* feat = reinterpret_cast<const TI*>(a.data[lv]) + (size_t)b * H * W * C;
+    const RaGeom geo = ra_geometry<true>(a.opt, bx1, by1, bx2, by2, a.scale[lv], P);
+    for (int e = tid; e < total; e += RA_BIG_THREADS) {
+        const int bin = e / cq, c0 = (e - bin * cq) * 4;
+        const int ph = bin / P, pw = bin - ph * P;
+        float acc[4] = {0.f, 0.f, 0.f, 0.f};
+        for (int iy = 0; iy < geo.gh; ++iy) {
+            int yl, yh; float hy, ly;
+            if (!axis_sample(geo.sh, ph, geo.bh, iy, geo.gh, H, &yl, &yh, &hy, &ly)) continue;
+            for (int ix = 0; ix < geo.gw; ++ix) {
+                int xl, xh; float hx, lx;
+                if (!axis_sample(geo.sw, pw, geo.bw, ix, geo.gw, W, &xl, &xh, &hx, &lx)) continue;
+                float v1[4], v2[4], v3[4], v4[4];
+                load4<TI>(feat + ((size_t)yl * W + xl) * C + c0, v1);
+                load4<TI>(feat + ((size_t)yl * W + xh) * C + c0, v2);
+                load4<TI>(feat + ((size_t)yh * W + xl) * C + c0, v3);
+                load4<TI>(feat + ((size_t)yh * W + xh) * C + c0, v4);
+                const float w1 = hy * hx, w2 = hy * lx, w3 = ly * hx, w4 = ly * lx;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) acc[k] += w1 * v1[k] + w2 * v2[k] + w3 * v3[k] + w4 * v4[k];
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) acc[k] = acc[k] / geo.count;
+        store4<TO>(out + (size_t)bin * C + c0, acc);
+    }
+}
+
+template <class TI>
+static osr_status launch_big(const RoiAlignArgs& a, int out_dtype, hipStream_t st) {
+    dim3 grid((unsigned)a.m), block(RA_BIG_THREADS);
+    switch (out_dtype) {
+        case OSR_F32: hipLaunchKernelGGL((roi_align_big_kernel<TI, float>), grid, block, 0, st, a); break;
+        case OSR_F16: hipLaunchKernelGGL((roi_align_big_kernel<TI, f16_t>), grid, block, 0, st, a); break;
+        default: hipLaunchKernelGGL((roi_align_big_kernel<TI, bf16_t>), grid, block, 0, st, a); break;
+    }
+    OSR_CHECK_LAUNCH("osr_roi_align_fwd");
+    return OSR_OK;
+}
+
 template <class TI, bool OPT>
 static osr_status launch_out(const RoiAlignArgs& a, int out_dtype, hipStream_t st) {
     dim3 grid((unsigned)((a.m + RA_WPB - 1) / RA_WPB)), block(RA_THREADS);
@@ -718,7 +784,7 @@ static osr_status roi_align_fwd_impl(const osr_pyramid* f, int32_t feat_dtype, i
     OSR_REQUIRE(f && boxes && batch_idx && out, OSR_ERR_INVALID_ARG, "osr_roi_align_fwd: null pointer");
     RA_REQUIRE_OPT(opt, "osr_roi_align_fwd");
     RoiAlignArgs a;
-    if (const osr_status e = ra_take_pyramid("osr_roi_align_fwd", f, pooled, false, &a)) return e;
+    if (const osr_status e = ra_take_pyramid("osr_roi_align_fwd", f, pooled, false, &a, OSR_ROI_MAX_POOLED_FWD)) return e;
     OSR_REQUIRE(osr_dtype_ok(feat_dtype) && osr_dtype_ok(out_dtype), OSR_ERR_INVALID_ARG, "osr_roi_align_fwd: bad dtype");
     OSR_REQUIRE(n >= 1 && m >= 0 && m < (1ll << 31), OSR_ERR_INVALID_ARG, "osr_roi_align_fwd: bad n/m");
     OSR_REQUIRE(canonical_size > 0, OSR_ERR_INVALID_ARG, "osr_roi_align_fwd: canonical_size must be > 0");
@@ -729,6 +795,13 @@ static osr_status roi_align_fwd_impl(const osr_pyramid* f, int32_t feat_dtype, i
     a.no_pad_fill = (flags & OSR_ROI_NO_PADDING_FILL) ? 1 : 0;
     a.opt = ra_opt_of(opt);
     hipStream_t st = (hipStream_t)stream;
+    if (pooled > 7) {  // (the kernels below hold 7 bins of state per axis)
+        switch (feat_dtype) {
+            case OSR_F32: return launch_big<float>(a, out_dtype, st);
+            case OSR_F16: return launch_big<f16_t>(a, out_dtype, st);
+            default: return launch_big<bf16_t>(a, out_dtype, st);
+        }
+    }
     if (ra_opt_default(opt)) {
         switch (feat_dtype) {
             case OSR_F32: return launch_out<float, false>(a, out_dtype, st);

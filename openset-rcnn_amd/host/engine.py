@@ -170,6 +170,8 @@ class OpensetRCNNEngine:
         for k, v in params.items():
             if not k.endswith(".weight") or v.dim() != 4 or (k.startswith("proposal_generator.rpn_head.") and not k.startswith("proposal_generator.rpn_head.conv.")):
                 continue
+            if k.startswith("roi_heads.mask_head.") and not k.startswith("roi_heads.mask_head.mask_fcn"):
+                continue  # (deconv and predictor have layouts of their own: engine_std._init_mask_head)
             pre = k[: -len(".weight")]
             if self.conv == "split":
                 w[pre + ".w"] = tuple(t.to(dev) for t in (split_stem_weight(v) if pre == STEM else split_conv_weight(v)))
@@ -625,7 +627,7 @@ class OpensetRCNNEngine:
             cur.wait_event(done)
             outs.append(o)
             lo = hi
-        return tuple(torch.cat([o[k] for o in outs]) for k in range(4))
+        return tuple(torch.cat([o[k] for o in outs]) for k in range(len(outs[0])))  # (4; 5 with the stock engine's mask head)
 
     def capture(self, images, image_hw, hp, wp, nstreams: int = 1):
         """Capture one whole pass (all micro-batch streams, ~110 launches each) into a hipGraph. Returns (graph, outputs):
@@ -756,10 +758,13 @@ class OpensetRCNNEngine:
     @staticmethod
     def to_instances(result, n: int) -> List[dict]:
         """One D2H copy; list of {'pred_boxes','scores','pred_classes'} per image (the fields the evaluators read,
-        pascal_voc_evaluation.py:58-61)."""
-        ob, osc, ocl, on = [t.cpu() for t in result]
+        pascal_voc_evaluation.py:58-61). A fifth tensor (the stock engine's mask probabilities, (n, cap, M, M)) stays on the device
+        and is sliced into 'pred_masks' (k, 1, M, M), as [d2] mask_rcnn_inference attaches them."""
+        ob, osc, ocl, on = [t.cpu() for t in result[:4]]
         out = []
         for i in range(n):
             c = int(on[i])
             out.append(dict(pred_boxes=ob[i, :c], scores=osc[i, :c], pred_classes=ocl[i, :c]))
+            if len(result) > 4:
+                out[-1]["pred_masks"] = result[4][i, :c].unsqueeze(1)
         return out

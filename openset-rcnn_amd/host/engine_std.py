@@ -14,7 +14,7 @@ import torch
 
 from . import ops
 from .engine import PYRAMID, RPN_CONV, OpensetRCNNEngine, loss_types_of
-from .weights import pack_fc1_weight
+from .weights import pack_deconv_weight, pack_fc1_weight
 
 STD_DEFAULT_CFG = dict(
     anchor_ratios=(0.5, 1.0, 2.0), post_nms_topk_test=1000, rpn_nms_thresh=0.7, rpn_bbox_reg_weights=(1.0, 1.0, 1.0, 1.0),
@@ -22,6 +22,8 @@ STD_DEFAULT_CFG = dict(
     # training ([d2] defaults; Base-RCNN-FPN.yaml:17-18 sets the two top-k values)
     post_nms_topk_train=1000, rpn_cls_weight=1.0, std_cls_loss_weight=1.0,
     loss_types=dict(rpn_box=("smooth_l1", 0.0), roi_box=("smooth_l1", 0.0)),
+    # the mask branch (MODEL.MASK_ON; ROI_MASK_HEAD of Base-RCNN-FPN.yaml:29-33): built when the parameters carry a mask head
+    mask_pooler_resolution=14, mask_pooler_aligned=True, mask_pooler_sampling_ratio=0,
 )
 
 
@@ -67,6 +69,7 @@ class StandardRCNNEngine(OpensetRCNNEngine):
         dev, c, dtype = self.device, self.cfg, self.dtype
         f32 = lambda k: params[k].float().contiguous().to(dev)  # noqa: E731
         self.has_roi = "roi_heads.box_predictor.cls_score.weight" in params
+        self._init_mask_head(params)
         if not self.has_roi:
             return
         self.fc1_w = pack_fc1_weight(params["roi_heads.box_head.fc1.weight"], 256, c["pooler_resolution"], dtype).to(dev)
@@ -77,6 +80,47 @@ class StandardRCNNEngine(OpensetRCNNEngine):
         self.box_w, self.box_b = f32("roi_heads.box_predictor.bbox_pred.weight"), f32("roi_heads.box_predictor.bbox_pred.bias")
         k = c["std_num_classes"]
         assert self.cls_w.shape[0] == k + 1 and self.box_w.shape[0] in (4, 4 * k), "cls_score: K+1 rows; bbox_pred: 4 or 4K rows"
+
+    def _init_mask_head(self, params) -> None:
+        """[d2] MaskRCNNConvUpsampleHead: mask_fcn1..N (3x3, packed with the other convolutions by _pack_convs), deconv in the fused
+        kernel's fragment order, the 1x1 predictor as an fp32 (rows, CONV_DIM) matrix -- one row when CLS_AGNOSTIC_MASK."""
+        dev, c = self.device, self.cfg
+        pre = "roi_heads.mask_head."
+        self.has_mask = pre + "deconv.weight" in params
+        if not self.has_mask:
+            return
+        ops.check_pooler_options(c["mask_pooler_aligned"], c["mask_pooler_sampling_ratio"])
+        self.mask_num_conv = 0
+        while f"{pre}mask_fcn{self.mask_num_conv + 1}.weight" in params:
+            self.mask_num_conv += 1
+        self.mask_deconv_w = pack_deconv_weight(params[pre + "deconv.weight"], self.dtype).to(dev)
+        self.mask_deconv_b = params[pre + "deconv.bias"].float().contiguous().to(dev)
+        pw = params[pre + "predictor.weight"].float()
+        self.mask_pred_w = pw.reshape(pw.shape[0], -1).contiguous().to(dev)
+        self.mask_pred_b = params[pre + "predictor.bias"].float().contiguous().to(dev)
+        assert self.mask_pred_w.shape[0] in (1, c["std_num_classes"]), "mask predictor: 1 (CLS_AGNOSTIC_MASK) or NUM_CLASSES rows"
+
+    # ---- [d2] StandardROIHeads._forward_mask + mask_rcnn_inference (inference) ---------------------------------------------------
+    def _mask_head(self, feats, boxes, classes, counts):
+        """boxes (n, topk, 4) fp32, classes (n, topk) int64, counts (n,) int32: the padded detection lists (or any boxes: the head is
+        callable on its own). -> probs (n, topk, 2P, 2P) fp32, the sigmoid of each detection's class row (row 0 when class-agnostic);
+        the rows beyond an image's count, and rows with class -1, are zeros. No host sync: the capacities are fixed."""
+        c = self.cfg
+        if not self.has_mask:
+            raise ops.OsrError("this engine was built without a mask head (MODEL.MASK_ON False)")
+        n, topk = boxes.shape[0], boxes.shape[1]
+        res = c["mask_pooler_resolution"]
+        ar = torch.arange(topk, device=self.device, dtype=torch.int32)[None, :]
+        bidx = torch.where(ar < counts[:, None], torch.arange(n, device=self.device, dtype=torch.int32)[:, None],
+                           torch.full((1, 1), -1, device=self.device, dtype=torch.int32)).reshape(-1).contiguous()
+        x = ops.roi_align([feats[k] for k in PYRAMID[:4]], c["pooler_scales"], boxes.reshape(-1, 4).contiguous(), bidx, res, self.dtype,
+                          c["canonical_level"], c["canonical_size"], 2, aligned=c["mask_pooler_aligned"],
+                          sampling_ratio=c["mask_pooler_sampling_ratio"])
+        for i in range(self.mask_num_conv):
+            x = self._conv(x, f"roi_heads.mask_head.mask_fcn{i + 1}", 1, 1, relu=True)
+        probs = ops.mask_upsample_predict(x, self.mask_deconv_w, self.mask_deconv_b, self.mask_pred_w, self.mask_pred_b,
+                                          classes.reshape(-1).contiguous(), counts, topk)
+        return probs.view(n, topk, 2 * res, 2 * res)
 
     def _levels(self, shapes, n):
         key = (tuple(shapes), n)
@@ -143,6 +187,8 @@ class StandardRCNNEngine(OpensetRCNNEngine):
         ocl = torch.where(torch.arange(topk, device=self.device)[None, :] < dcnt[:, None], ocl, torch.full_like(ocl, -1))
         if keep is not None:
             keep.update(pooled=pooled, h1=h1, box_feats=box_feats, logits=logits, deltas=deltas, cands=cands, det_keep=dk, det_count=dcnt)
+        if self.has_mask:  # (a fifth output only when the engine has a mask head: MASK_ON False returns what it always has)
+            return ob, osc, ocl, dcnt, self._mask_head(feats, ob, ocl, dcnt)
         return ob, osc, ocl, dcnt
 
     # ---- [d2] RPN.label_and_sample_anchors + RPN.losses (training) ---------------------------------------------------------------

@@ -64,6 +64,7 @@ PROPOSAL_GENERATOR_REGISTRY = Registry("PROPOSAL_GENERATOR")
 RPN_HEAD_REGISTRY = Registry("RPN_HEAD")
 ROI_HEADS_REGISTRY = Registry("ROI_HEADS")
 ROI_BOX_HEAD_REGISTRY = Registry("ROI_BOX_HEAD")
+ROI_MASK_HEAD_REGISTRY = Registry("ROI_MASK_HEAD")
 
 
 
@@ -523,15 +524,16 @@ def freeze_at_of(cfg: CfgNode) -> int:
 POOLER_TYPES = {"ROIAlignV2": True, "ROIAlign": False}  # MODEL.ROI_BOX_HEAD.POOLER_TYPE -> `aligned` of torchvision's roi_align
 
 
-def pooler_options_from(cfg: CfgNode) -> Tuple[bool, int]:
-    """MODEL.ROI_BOX_HEAD.POOLER_TYPE / POOLER_SAMPLING_RATIO as [d2] ROIPooler reads them -> (aligned, sampling_ratio) of the RoIAlign
-    kernels. "ROIPool" and "ROIAlignRotated" have no kernel and a negative ratio no meaning: ValueError when the model is built."""
-    bh = cfg.MODEL.ROI_BOX_HEAD
+def pooler_options_from(cfg: CfgNode, head: str = "ROI_BOX_HEAD") -> Tuple[bool, int]:
+    """MODEL.<head>.POOLER_TYPE / POOLER_SAMPLING_RATIO (head: ROI_BOX_HEAD, or ROI_MASK_HEAD for the mask branch) as [d2] ROIPooler
+    reads them -> (aligned, sampling_ratio) of the RoIAlign kernels. "ROIPool" and "ROIAlignRotated" have no kernel and a negative ratio
+    no meaning: ValueError when the model is built."""
+    bh = cfg.MODEL[head]
     if bh.POOLER_TYPE not in POOLER_TYPES:
-        raise ValueError(f"MODEL.ROI_BOX_HEAD.POOLER_TYPE {bh.POOLER_TYPE!r}: one of {tuple(POOLER_TYPES)}")
+        raise ValueError(f"MODEL.{head}.POOLER_TYPE {bh.POOLER_TYPE!r}: one of {tuple(POOLER_TYPES)}")
     ratio = bh.POOLER_SAMPLING_RATIO
     if isinstance(ratio, bool) or not isinstance(ratio, int) or not 0 <= ratio <= ops.MAX_SAMPLING_RATIO:
-        raise ValueError(f"MODEL.ROI_BOX_HEAD.POOLER_SAMPLING_RATIO {ratio!r}: 0 (adaptive grid) or an integer S in 1 .. {ops.MAX_SAMPLING_RATIO} "
+        raise ValueError(f"MODEL.{head}.POOLER_SAMPLING_RATIO {ratio!r}: 0 (adaptive grid) or an integer S in 1 .. {ops.MAX_SAMPLING_RATIO} "
                          "(S x S samples per bin)")
     return POOLER_TYPES[bh.POOLER_TYPE], int(ratio)
 
@@ -662,6 +664,40 @@ class OpensetROIHeads(_EngineOwner):
         return out, {}
 
 
+@ROI_MASK_HEAD_REGISTRY.register()
+class MaskRCNNConvUpsampleHead(nn.Module):
+    """[d2] MaskRCNNConvUpsampleHead (Base-RCNN-FPN.yaml:29-33) with [d2]'s parameter names, so that model-zoo mask_rcnn checkpoints
+    load: mask_fcn1..NUM_CONV (3x3, CONV_DIM, ReLU), deconv (ConvTranspose2d 2x2 stride 2, ReLU), predictor (1x1 to one map when
+    CLS_AGNOSTIC_MASK, else NUM_CLASSES maps). Initialisers: c2_msra_fill for the convolutions, normal(std=0.001) for the predictor."""
+
+    def __init__(self, cfg: CfgNode, input_shape: ShapeSpec):
+        super().__init__()
+        mh = cfg.MODEL.ROI_MASK_HEAD
+        if mh.NORM != "":
+            raise ValueError(f"MODEL.ROI_MASK_HEAD.NORM {mh.NORM!r}: the mask head's convolutions have no normalisation on the HIP path (\"\")")
+        dim, cur = int(mh.CONV_DIM), input_shape.channels
+        if mh.NUM_CONV < 0 or dim % 64 or cur % 64 or (mh.NUM_CONV == 0 and cur > 448) or (mh.NUM_CONV > 0 and dim > 448):
+            raise ValueError(f"MODEL.ROI_MASK_HEAD: NUM_CONV >= 0 and CONV_DIM a multiple of 64, at most 448 (got {mh.NUM_CONV}, {dim})")
+        self.num_conv = int(mh.NUM_CONV)
+        for k in range(self.num_conv):
+            conv = nn.Conv2d(cur, dim, 3, padding=1)
+            nn.init.kaiming_normal_(conv.weight, mode="fan_out", nonlinearity="relu")
+            nn.init.constant_(conv.bias, 0)
+            self.add_module(f"mask_fcn{k + 1}", conv)
+            cur = dim
+        self.deconv = nn.ConvTranspose2d(cur, dim, 2, stride=2)
+        nn.init.kaiming_normal_(self.deconv.weight, mode="fan_out", nonlinearity="relu")
+        nn.init.constant_(self.deconv.bias, 0)
+        self.num_mask_classes = 1 if mh.CLS_AGNOSTIC_MASK else int(cfg.MODEL.ROI_HEADS.NUM_CLASSES)
+        self.predictor = nn.Conv2d(dim, self.num_mask_classes, 1)
+        nn.init.normal_(self.predictor.weight, std=0.001)
+        nn.init.constant_(self.predictor.bias, 0)
+
+
+MASK_LOSS_MESSAGE = ("MODEL.MASK_ON: training the mask branch needs ground-truth mask rasterisation and the mask loss "
+                     "(mask_rcnn_loss), which the HIP path does not have; the mask head runs at inference only")
+
+
 class FastRCNNOutputLayers(nn.Module):
     """[d2] FastRCNNOutputLayers: cls_score (K+1) and bbox_pred (4, or 4K when not class-agnostic); init std 0.01 / 0.001."""
 
@@ -688,7 +724,8 @@ class StandardROIHeads(_EngineOwner):
 
     def __init__(self, cfg: CfgNode, input_shape: Dict[str, ShapeSpec], class_id=None):
         super().__init__()
-        assert not cfg.MODEL.MASK_ON and not cfg.MODEL.KEYPOINT_ON, "box branch only (the Openset path has no mask / keypoint heads)"
+        if cfg.MODEL.KEYPOINT_ON:
+            raise ValueError("MODEL.KEYPOINT_ON: the HIP path has no keypoint head (box and mask branches only)")
         self.in_features = self.box_in_features = list(cfg.MODEL.ROI_HEADS.IN_FEATURES)
         res = cfg.MODEL.ROI_BOX_HEAD.POOLER_RESOLUTION
         ch = input_shape[self.in_features[0]].channels
@@ -698,10 +735,23 @@ class StandardROIHeads(_EngineOwner):
         self._eng_cfg["pooler_scales"] = tuple(1.0 / input_shape[k].stride for k in self.in_features)
         check_std_supported(self._eng_cfg)  # (an unsupported loss type is refused when the model is built)
         self.sampler_generator = torch.Generator().manual_seed(max(int(cfg.SEED), 0))  # uniform keys replacing torch.randperm (H6)
+        # [d2] StandardROIHeads._init_mask_head: the mask branch pools the same levels with its own resolution / type / ratio
+        self.mask_on = bool(cfg.MODEL.MASK_ON)
+        if self.mask_on:
+            mh = cfg.MODEL.ROI_MASK_HEAD
+            aligned, ratio = pooler_options_from(cfg, "ROI_MASK_HEAD")
+            mres = mh.POOLER_RESOLUTION
+            if isinstance(mres, bool) or not isinstance(mres, int) or not 1 <= mres <= ops.MAX_POOLED_FWD:
+                raise ValueError(f"MODEL.ROI_MASK_HEAD.POOLER_RESOLUTION {mres!r}: an integer 1 .. {ops.MAX_POOLED_FWD}")
+            self.mask_in_features = self.in_features
+            self.mask_head = ROI_MASK_HEAD_REGISTRY.get(mh.NAME)(cfg, ShapeSpec(channels=ch, height=mres, width=mres))
+            self._eng_cfg.update(mask_pooler_resolution=int(mres), mask_pooler_aligned=aligned, mask_pooler_sampling_ratio=ratio)
 
     def _forward_train(self, features: Dict[str, torch.Tensor], proposals: List[Instances], targets: List[Instances]):
         """[d2] label_and_sample_proposals + FastRCNNOutputLayers.losses: the sampled proposals (gt_classes / gt_boxes attached) and the
         loss values."""
+        if self.mask_on:
+            raise NotImplementedError(MASK_LOSS_MESSAGE)
         eng = self.engine()
         boxes, scores, _, counts, cap = OpensetROIHeads._pack_proposals(proposals)
         n, dev = len(proposals), boxes.device
@@ -738,22 +788,43 @@ class StandardROIHeads(_EngineOwner):
         res = OpensetRCNNEngine.to_instances(eng._roi_heads(feats, sel, hw), n)
         out = []
         for r, p in zip(res, proposals):
-            out.append(Instances(p.image_size, pred_boxes=Boxes(r["pred_boxes"]), scores=r["scores"], pred_classes=r["pred_classes"]))
+            out.append(_std_instances(p.image_size, r))
         return out, {}
+
+
+def _std_instances(image_size, r: dict) -> Instances:
+    """Instances of one image from OpensetRCNNEngine.to_instances' dict; pred_masks (k, 1, M, M) probabilities when the engine has a
+    mask head ([d2] mask_rcnn_inference)."""
+    inst = Instances(image_size, pred_boxes=Boxes(r["pred_boxes"]), scores=r["scores"], pred_classes=r["pred_classes"])
+    if "pred_masks" in r:
+        inst.pred_masks = r["pred_masks"]
+    return inst
 
 
 # ---------------------------------------------------------------------------------------------------------------
 # meta architecture
 # ---------------------------------------------------------------------------------------------------------------
-def detector_postprocess(results: Instances, output_height: int, output_width: int) -> Instances:
-    """[d2] rescale to the requested output resolution, clip, drop empty boxes."""
+MASK_THRESHOLD = 0.5  # [d2] detector_postprocess's mask_threshold
+
+
+def detector_postprocess(results: Instances, output_height: int, output_width: int, mask_threshold: float = MASK_THRESHOLD) -> Instances:
+    """[d2] rescale to the requested output resolution, clip, drop empty boxes; pred_masks (k, 1, M, M) probabilities on the GPU are
+    then pasted into (k, H, W) bool bitmasks at the output resolution (ops.paste_masks: [d2] paste_masks_in_image)."""
     sx, sy = output_width / results.image_size[1], output_height / results.image_size[0]
-    out = Instances((output_height, output_width), **results.get_fields())
+    fields = dict(results.get_fields())
+    masks = fields.pop("pred_masks", None)
+    out = Instances((output_height, output_width), **fields)
     b = out.pred_boxes.clone()
     b.scale(sx, sy)
     b.clip(out.image_size)
     out.pred_boxes = b
-    return out[b.nonempty()]
+    keep = b.nonempty()
+    out = out[keep]
+    if masks is not None:
+        probs = masks[keep.to(masks.device)][:, 0].float().contiguous()
+        boxes = out.pred_boxes.tensor.float().to(probs.device).contiguous()
+        out.pred_masks = ops.paste_masks(probs, boxes, output_height, output_width, mask_threshold).bool()
+    return out
 
 
 @META_ARCH_REGISTRY.register()
@@ -850,6 +921,8 @@ class GeneralizedRCNN(_EngineOwner):
         `load_trainer_state(trainer)` writes them back into the module for evaluation / checkpointing."""
         from .train import OpensetRCNNTrainer
         from .train_std import StandardRCNNTrainer
+        if getattr(self.roi_heads, "mask_on", False):
+            raise NotImplementedError(MASK_LOSS_MESSAGE)
         if self.conv_precision != "storage":
             raise ValueError(f"conv_precision {self.conv_precision!r}: the split-precision convolutions are an inference mode; set it back to \"storage\" to train")
         if self.device.type != "cuda":
@@ -947,6 +1020,12 @@ class GeneralizedRCNN(_EngineOwner):
         eng = self.engine()
         batch, sizes = self._stack_images([x["image"] for x in batched_inputs])
         res = eng.forward(batch, sizes)
+        if len(res) > 4:  # mask head: the masks follow their boxes through the per-image postprocess, which pastes them
+            insts = [_std_instances(s, r) for r, s in zip(OpensetRCNNEngine.to_instances(res, len(sizes)), sizes)]
+            if do_postprocess:
+                insts = [detector_postprocess(r, int(inp.get("height", s[0])), int(inp.get("width", s[1])))
+                         for r, inp, s in zip(insts, batched_inputs, sizes)]
+            return [{"instances": r} for r in insts]
         if do_postprocess:  # [d2] detector_postprocess on the device: rescale, clip, drop empties
             outs = [(int(inp.get("height", s[0])), int(inp.get("width", s[1]))) for inp, s in zip(batched_inputs, sizes)]
             scale = torch.tensor([[ow / s[1], oh / s[0]] for (oh, ow), s in zip(outs, sizes)], dtype=torch.float32, device=self.device)

@@ -901,6 +901,7 @@ def roi_locality_order(feats: List[torch.Tensor], scales: Sequence[float], boxes
 
 
 MAX_SAMPLING_RATIO = 64  # include/osr.h OSR_ROI_MAX_SAMPLING_RATIO
+MAX_POOLED_FWD = 14      # include/osr.h OSR_ROI_MAX_POOLED_FWD (the backward takes 1..7)
 
 
 def check_pooler_options(aligned, sampling_ratio) -> Tuple[bool, int]:
@@ -922,7 +923,7 @@ def roi_align(feats: List[torch.Tensor], scales: Sequence[float], boxes: torch.T
               pooled: int = 7, out_dtype: Optional[torch.dtype] = None, canonical_level: int = 4, canonical_size: int = 224,
               min_level: int = 2, order: Optional[torch.Tensor] = None, fill_padding: bool = True, aligned: bool = True,
               sampling_ratio: int = 0) -> torch.Tensor:
-    """feats: NHWC per level; boxes (m,4) fp32; batch_idx (m) int32. Returns (m, pooled, pooled, c). order: processing order, (m,)
+    """feats: NHWC per level; boxes (m,4) fp32; batch_idx (m) int32. Returns (m, pooled, pooled, c), pooled 1 .. MAX_POOLED_FWD. order: processing order, (m,)
     int32 or (m + 1,) as roi_locality_order returns it (None: that order when ROI_LOCALITY_ORDER, else list order); the result
     does not depend on it. fill_padding=False: the rows of padding entries (batch index -1) are left unwritten instead of zeroed.
     aligned / sampling_ratio: torchvision roi_align's (include/osr.h osr_roi_options); the defaults are POOLER_TYPE "ROIAlignV2" with
@@ -1073,6 +1074,53 @@ def detector_postprocess(boxes, scores, classes, count, scale_xy, out_hw):
     check(lib.osr_detector_postprocess(_p(boxes), _p(scores), _p(classes), _p(count), n, cap, _p(scale_xy), _p(out_hw), _p(ob), _p(os_), _p(oc),
                                        _p(on), _stream()), "osr_detector_postprocess")
     return ob, os_, oc, on
+
+
+def mask_upsample_predict(x: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor, pred_w: torch.Tensor, pred_b: torch.Tensor,
+                          classes: Optional[torch.Tensor] = None, rows_valid: Optional[torch.Tensor] = None, seg_rows: int = 0) -> torch.Tensor:
+    """[d2] MaskRCNNConvUpsampleHead's deconv (2 x 2, stride 2) + ReLU + 1 x 1 predictor and mask_rcnn_inference's sigmoid of each RoI's
+    class row, one launch. x (r, s, s, cin) NHWC; w_packed: weights.pack_deconv_weight in x's dtype; bias (cmid), pred_w (k, cmid),
+    pred_b (k) fp32; classes (r) int64 (may be None when k == 1: class-agnostic); rows_valid (segments) int32 with seg_rows RoIs per
+    segment: the RoIs beyond a segment's count, and those with class -1, come out as zeros. Returns probs (r, 2s, 2s) fp32."""
+    lib = _lib.load()
+    _need(x, name="x"); _need(w_packed, x.dtype, "w_packed")
+    for t, nme in ((bias, "bias"), (pred_w, "pred_w"), (pred_b, "pred_b")):
+        _need(t, torch.float32, nme)
+    r, s, s2, cin = x.shape
+    k, cmid = pred_w.shape
+    if s != s2 or bias.numel() != cmid or pred_b.numel() != k or w_packed.numel() != 4 * cin * cmid:
+        raise OsrError(f"mask_upsample_predict: x {tuple(x.shape)}, bias {tuple(bias.shape)}, pred_w {tuple(pred_w.shape)}, pred_b {tuple(pred_b.shape)}, "
+                       f"w_packed {tuple(w_packed.shape)} do not fit together")
+    if classes is not None:
+        _need(classes, torch.int64, "classes")
+        if classes.numel() != r:
+            raise OsrError(f"mask_upsample_predict: {classes.numel()} classes for {r} RoIs")
+    if rows_valid is not None:
+        _need(rows_valid, torch.int32, "rows_valid")
+        if seg_rows < 1 or rows_valid.numel() * seg_rows < r:
+            raise OsrError("mask_upsample_predict: rows_valid does not cover the RoIs")
+    probs = torch.empty((r, 2 * s, 2 * s), dtype=torch.float32, device=x.device)
+    check(lib.osr_mask_upsample_predict(_p(x), _DT[x.dtype], r, s, cin, cmid, _p(w_packed), _p(bias), _p(pred_w), _p(pred_b), k, _p(classes),
+                                        _p(rows_valid), int(seg_rows), _p(probs), _stream()), "osr_mask_upsample_predict")
+    return probs
+
+
+def paste_masks(probs: torch.Tensor, boxes: torch.Tensor, out_h: int, out_w: int, threshold: float = 0.5,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """[d2] paste_masks_in_image for one image: probs (r, m, m) fp32, boxes (r, 4) fp32 at the output resolution -> (r, out_h, out_w)
+    uint8, 0 or 1. Every byte of the result is written (out, if given, needs no fill)."""
+    lib = _lib.load()
+    _need(probs, torch.float32, "probs"); _need(boxes, torch.float32, "boxes")
+    r, m, m2 = probs.shape
+    if m != m2 or tuple(boxes.shape) != (r, 4):
+        raise OsrError(f"paste_masks: probs {tuple(probs.shape)} / boxes {tuple(boxes.shape)}")
+    if out is None:
+        out = torch.empty((r, out_h, out_w), dtype=torch.uint8, device=probs.device)
+    else:
+        _need(out, torch.uint8, "out")
+        assert tuple(out.shape) == (r, out_h, out_w)
+    check(lib.osr_paste_masks(_p(probs), _p(boxes), r, m, int(out_h), int(out_w), float(threshold), _p(out), _stream()), "osr_paste_masks")
+    return out
 
 
 # ----------------------------------------------------------------------------------------------------------

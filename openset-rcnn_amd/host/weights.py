@@ -103,6 +103,19 @@ def pack_fc1_weight(w: torch.Tensor, channels: int, pooled: int, dtype: torch.dt
     return w.view(o, channels, pooled, pooled).permute(0, 2, 3, 1).reshape(o, pooled * pooled * channels).contiguous().to(dtype)
 
 
+def pack_deconv_weight(w: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
+    """[d2] MaskRCNNConvUpsampleHead.deconv weight (cin, cmid, 2, 2) -> the B operand of ops.mask_upsample_predict (include/osr.h
+    osr_mask_upsample_predict): one (cmid, cin) matrix per tap t = 2 dy + dx, cut into the MFMA fragments a wave loads -- blocks of 32
+    output channels x 2E input channels, E = 8 (fp16 / bf16) or 4 (fp32), laid out [t][n / 32][k / 2E][(k / E) % 2][n % 32][k % E] so
+    that the 64 lanes of a wave read one contiguous block. cin and cmid must be multiples of 64."""
+    cin, cmid, kh, kw = w.shape
+    if (kh, kw) != (2, 2) or cin % 64 or cmid % 64:
+        raise ValueError(f"deconv weight {tuple(w.shape)}: (cin, cmid, 2, 2) with cin and cmid multiples of 64")
+    e = 4 if dtype == torch.float32 else 8
+    wt = w.detach().permute(2, 3, 1, 0).reshape(4, cmid // 32, 32, cin // (2 * e), 2, e)  # [t][n / 32][n % 32][k / 2E][half][k % E]
+    return wt.permute(0, 1, 3, 4, 2, 5).contiguous().to(dtype)
+
+
 def split_fp32_rows(w: torch.Tensor):
     """The operand format of the split-precision box head (ops.linear_split, include/osr.h osr_linear_split_fwd): an fp32 matrix as
     two bf16 planes, w = hi + lo to 2^-17 of each element's magnitude, hi = bf16(w), lo = bf16(w - hi), both rounded to nearest
