@@ -369,7 +369,8 @@ osr_status osr_cfrpn_head_fwd_ex(const osr_conv_params* p, const void* in, const
  * levels concatenated level-major (no NMS, no cross-level re-sort: the reference has both commented out).
  * Outputs are padded to cap = osr_rpn_select_capacity(): boxes (n,cap,4), scores (n,cap), src_index (n,cap)
  * (index into the image's concatenated anchor list), batch_idx (n*cap: image id, -1 for padding), counts (n).
- * status_flags[0] is set non-zero when any non-finite prediction was met (training raises on it).
+ * status_flags[0] is set non-zero when any non-finite prediction was met (training raises on it). A NaN score of
+ * either sign ranks above every number in the top-k (torch.sort's order), so it is met, dropped and flagged.
  * --------------------------------------------------------------------------------------------------------- */
 typedef struct osr_rpn_levels {
     int32_t num_levels;

@@ -111,6 +111,12 @@ __device__ __forceinline__ void bitonic_desc(unsigned long long* buf, int n) {
     }
 }
 
+// osr_float_key with every NaN mapped to the largest key. torch.sort(descending=True), which find_top_rpn_proposals selects with, puts
+// a NaN score first whatever its sign bit; osr_float_key orders a sign-set NaN (0xffc00000, an x86 host's inf - inf) below -inf, so
+// the anchor would never be selected, never reach the finite filter and never raise status_flags. NaNs tie with each other: lower
+// index first, like every other tie.
+__device__ __forceinline__ uint32_t sel_key(float f) { return f != f ? 0xffffffffu : osr_float_key(f); }
+
 // hist[digit] += 1 for the lanes with `on`, called by all 64 lanes of a wave. Two rounds of "the first pending lane's digit: every
 // lane that shares it is added by ONE atomic", then one atomic per lane that is still pending. Same histogram as 64 plain atomics.
 __device__ __forceinline__ void sel_hist_add(int* hist, int digit, bool on) {
@@ -174,8 +180,8 @@ __global__ __launch_bounds__(SEL_THREADS) void rpn_select_kernel(SelLevels lv, c
                 if (i < cnt) {
                     if (vec4) {
                         const float4 v = *reinterpret_cast<const float4*>(sc + i);
-                        key[0] = osr_float_key(v.x); key[1] = osr_float_key(v.y); key[2] = osr_float_key(v.z); key[3] = osr_float_key(v.w);
-                    } else key[0] = osr_float_key(sc[i]);
+                        key[0] = sel_key(v.x); key[1] = sel_key(v.y); key[2] = sel_key(v.z); key[3] = sel_key(v.w);
+                    } else key[0] = sel_key(sc[i]);
                 }
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
@@ -239,8 +245,8 @@ __global__ __launch_bounds__(SEL_THREADS) void rpn_select_kernel(SelLevels lv, c
         if (i < cnt) {
             if (vec4) {
                 const float4 v = *reinterpret_cast<const float4*>(sc + i);
-                key[0] = osr_float_key(v.x); key[1] = osr_float_key(v.y); key[2] = osr_float_key(v.z); key[3] = osr_float_key(v.w);
-            } else key[0] = osr_float_key(sc[i]);
+                key[0] = sel_key(v.x); key[1] = sel_key(v.y); key[2] = sel_key(v.z); key[3] = sel_key(v.w);
+            } else key[0] = sel_key(sc[i]);
 #pragma unroll
             for (int e = 0; e < 4; ++e)
                 if (e < per) { if (all) gt += 1; else { gt += key[e] > T; eq += key[e] == T; } }
