@@ -165,6 +165,16 @@ osr_status osr_resize_bilinear_u8(const uint8_t* in, int32_t h, int32_t w, int64
                                   int32_t ky, int32_t y_first, int32_t y_rows, int32_t nh, int32_t nw, uint8_t* tmp,
                                   int64_t tmp_bytes, uint8_t* out, void* stream);
 
+/* The same resampling of PLANAR images with an optional mirrored store: the "resize" and "resize + horizontal flip" of test-time
+ * augmentation ([d2] DatasetMapperTTA: ResizeShortestEdge(s, TEST.AUG.MAX_SIZE) [+ RandomFlip(prob=1.0)] applied to the model input
+ * image). in: (planes, h, w) uint8 -- planes = 3 for one image dict's "image", 3n for a stacked batch of n; out: (planes, nh, nw).
+ * Same tables, same two passes and 8-bit intermediate as osr_resize_bilinear_u8: on the transposed data the two give the same bits.
+ * mirror (0 / 1): the last pass stores column x at nw - 1 - x. tmp: planes * y_rows * nw bytes. */
+osr_status osr_resize_bilinear_u8_planar(const uint8_t* in, int32_t planes, int32_t h, int32_t w, const int32_t* xbounds,
+                                         const int32_t* xcoef, int32_t kx, const int32_t* ybounds, const int32_t* ycoef,
+                                         int32_t ky, int32_t y_first, int32_t y_rows, int32_t nh, int32_t nw, int32_t mirror,
+                                         uint8_t* tmp, int64_t tmp_bytes, uint8_t* out, void* stream);
+
 /* The whole ResNet stem in ONE launch (csrc/osr_stem_pool.hip): [d2] BasicStem.forward = conv1 (7x7, stride 2, pad 3, 3 -> 64,
  * FrozenBN folded) -> ReLU -> F.max_pool2d(3, 2, 1), built by build_resnet_fpn_backbone (/root/reference/configs/Base-RCNN-FPN.yaml:3-8).
  * xpad: osr_preprocess' (n, hp + 6, osr_stem_padded_width(wp), 4) image; w_view: the stem view (64, w_rows, 1, 32) of
@@ -593,6 +603,35 @@ osr_status osr_mask_upsample_predict(const void* x, int32_t dtype, int64_t r, in
  * u = (x + 0.5 - x0) / (x1 - x0) * m - 0.5, v likewise, is >= threshold, else 0. Every byte of out is written. r <= 65535. */
 osr_status osr_paste_masks(const float* probs, const float* boxes, int64_t r, int32_t m, int32_t out_h, int32_t out_w,
                            float threshold, uint8_t* out, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * Test-time augmentation glue ([d2] modeling/test_time_augmentation.py GeneralizedRCNNWithTTA; csrc/osr_tta.hip), over the padded
+ * detection lists (n, topk, .) + counts (n) of one engine pass. An augmentation of an input with image (hi, wi) and output resolution
+ * (ho, wo) is the transform list [resize (ho, wo) -> (hi, wi), only when the two differ], resize (hi, wi) -> (ha, wa), [hflip(wa)].
+ * sizes: (n, 4) int32 {hi, wi, ho, wo} per image. fp32 arithmetic per coordinate as [d2]'s numpy: a resize multiplies x by
+ * (float)((double)w' / w) and y by (float)((double)h' / h), a flip is (float)wa - x, the box is (min x, min y, max x, max y) of its
+ * corners after each step, nothing is fused across steps. boxes, sizes and the box outputs are 16-byte aligned.
+ *
+ * osr_tta_boxes_to_original (_inverse_augment_boxes + the per-row part of fast_rcnn_inference_single_image(.., 1e-8, ..)): the inverse
+ * list, then clip x to [0, wo] and y to [0, ho]. Writes rows [slot, slot + topk) of every image's candidate list of `cap` rows
+ * (cap >= slot + topk; A augmentations fill cap = A * topk): c_boxes (n, cap, 4), c_scores (n, cap), c_cls (n, cap) int32,
+ * c_cand (n, cap) int32 = the row exists && every mapped coordinate and the score are finite && score > 1e-8. Rows beyond an
+ * image's count: zeros, class -1, cand 0. Follow with osr_nms_topk(cls = c_cls, cand = c_cand, thr NMS_THRESH_TEST, topk
+ * DETECTIONS_PER_IMAGE) and osr_gather_rows.
+ * osr_tta_boxes_to_augmented (_rescale_detected_boxes): boxes in (ho, wo) space through the forward list, not clipped; rows beyond
+ * an image's count are zeros.
+ * osr_tta_reduce_masks (_reduce_pred_masks): maps (A, n, topk, m, m) fp32, flip (A) int32 0 / 1 in device memory -> out (n, topk, m, m):
+ * the maps of flipped augmentations mirrored along their last axis, summed in fp32 in augmentation order, divided by A; rows beyond
+ * an image's count are zeros. Repeats are bit-identical.
+ * --------------------------------------------------------------------------------------------------------- */
+osr_status osr_tta_boxes_to_original(const float* boxes, const float* scores, const int64_t* classes, const int32_t* counts,
+                                     const int32_t* sizes, int32_t n, int32_t topk, int32_t ha, int32_t wa, int32_t flip,
+                                     int32_t slot, int32_t cap, float* c_boxes, float* c_scores, int32_t* c_cls,
+                                     int32_t* c_cand, void* stream);
+osr_status osr_tta_boxes_to_augmented(const float* boxes, const int32_t* counts, const int32_t* sizes, int32_t n, int32_t topk,
+                                      int32_t ha, int32_t wa, int32_t flip, float* out, void* stream);
+osr_status osr_tta_reduce_masks(const float* maps, const int32_t* flip, int32_t num_aug, const int32_t* counts, int32_t n,
+                                int32_t topk, int32_t m, float* out, void* stream);
 
 /* =========================================================================================================
  * Training step, forward half: targets and losses. Gradients are not

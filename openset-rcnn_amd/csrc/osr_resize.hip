@@ -69,3 +69,62 @@ extern "C" osr_status osr_resize_bilinear_u8(const uint8_t* in, int32_t h, int32
     OSR_CHECK_LAUNCH("osr_resize_bilinear_u8");
     return OSR_OK;
 }
+
+// ---- planar input, optional mirrored store (osr_resize_bilinear_u8_planar): the resize (+ horizontal flip) of test-time augmentation,
+// whose source is a model input's (3, h, w) "image". Same tables, same two passes and the same 8-bit intermediate as above, one thread
+// per output sample of one plane; with `mirror` the vertical pass stores column x at nw - 1 - x (flip AFTER the resize, as [d2] applies
+// its transform list).
+// rows [y_first, y_first + rows) of every plane -> tmp (planes, rows, nw)
+__global__ __launch_bounds__(256) void resize_h_planar_kernel(const unsigned char* __restrict__ in, int planes, int h, int w, int y_first, int rows, int nw,
+                                                              const int* __restrict__ xbounds, const int* __restrict__ xcoef, int kx,
+                                                              unsigned char* __restrict__ tmp) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long long)planes * rows * nw) return;
+    const int xx = (int)(i % nw);
+    const long long pr = i / nw;
+    const int r = (int)(pr % rows), pl = (int)(pr / rows);
+    const int xmin = xbounds[2 * xx], xmax = xbounds[2 * xx + 1];
+    const unsigned char* p = in + ((long long)pl * h + (y_first + r)) * w + xmin;
+    const int* k = xcoef + (long long)xx * kx;
+    int s = 1 << (RS_PRECISION_BITS - 1);
+    for (int x = 0; x < xmax; ++x) s += (int)p[x] * k[x];
+    tmp[i] = rs_clip8(s);
+}
+
+// tmp (planes, rows, nw) -> out (planes, nh, nw)
+__global__ __launch_bounds__(256) void resize_v_planar_kernel(const unsigned char* __restrict__ tmp, int planes, int y_first, int rows, int nh, int nw,
+                                                              const int* __restrict__ ybounds, const int* __restrict__ ycoef, int ky, int mirror,
+                                                              unsigned char* __restrict__ out) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long long)planes * nh * nw) return;
+    const int xx = (int)(i % nw);
+    const long long py = i / nw;
+    const int yy = (int)(py % nh), pl = (int)(py / nh);
+    const int ymin = ybounds[2 * yy], ymax = ybounds[2 * yy + 1];
+    const int* k = ycoef + (long long)yy * ky;
+    const unsigned char* p = tmp + ((long long)pl * rows + (ymin - y_first)) * nw + xx;
+    int s = 1 << (RS_PRECISION_BITS - 1);
+    for (int y = 0; y < ymax; ++y) s += (int)p[(long long)y * nw] * k[y];
+    out[py * nw + (mirror ? nw - 1 - xx : xx)] = rs_clip8(s);
+}
+
+extern "C" osr_status osr_resize_bilinear_u8_planar(const uint8_t* in, int32_t planes, int32_t h, int32_t w, const int32_t* xbounds, const int32_t* xcoef,
+                                                    int32_t kx, const int32_t* ybounds, const int32_t* ycoef, int32_t ky, int32_t y_first,
+                                                    int32_t y_rows, int32_t nh, int32_t nw, int32_t mirror, uint8_t* tmp, int64_t tmp_bytes,
+                                                    uint8_t* out, void* stream) {
+    OSR_REQUIRE(in && xbounds && xcoef && ybounds && ycoef && tmp && out, OSR_ERR_INVALID_ARG, "osr_resize_bilinear_u8_planar: null pointer");
+    OSR_REQUIRE(planes >= 1 && h >= 1 && w >= 1 && nh >= 1 && nw >= 1 && kx >= 1 && ky >= 1, OSR_ERR_INVALID_ARG,
+                "osr_resize_bilinear_u8_planar: bad geometry");
+    OSR_REQUIRE(mirror == 0 || mirror == 1, OSR_ERR_INVALID_ARG, "osr_resize_bilinear_u8_planar: mirror must be 0 or 1");
+    OSR_REQUIRE(y_first >= 0 && y_rows >= 1 && y_first + y_rows <= h, OSR_ERR_INVALID_ARG,
+                "osr_resize_bilinear_u8_planar: the rows the vertical pass reads, [y_first, y_first + y_rows), must lie inside the image");
+    OSR_REQUIRE(tmp_bytes >= (int64_t)planes * y_rows * nw, OSR_ERR_INVALID_ARG, "osr_resize_bilinear_u8_planar: tmp needs planes * y_rows * nw bytes");
+    hipStream_t st = (hipStream_t)stream;
+    const long long n1 = (long long)planes * y_rows * nw, n2 = (long long)planes * nh * nw;
+    OSR_REQUIRE((n1 + 255) / 256 <= 0x7fffffffll && (n2 + 255) / 256 <= 0x7fffffffll, OSR_ERR_INVALID_ARG, "osr_resize_bilinear_u8_planar: too many samples");
+    hipLaunchKernelGGL(resize_h_planar_kernel, dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, st, in, planes, h, w, y_first, y_rows, nw, xbounds, xcoef, kx, tmp);
+    hipLaunchKernelGGL(resize_v_planar_kernel, dim3((unsigned)((n2 + 255) / 256)), dim3(256), 0, st, tmp, planes, y_first, y_rows, nh, nw, ybounds, ycoef, ky,
+                       mirror, out);
+    OSR_CHECK_LAUNCH("osr_resize_bilinear_u8_planar");
+    return OSR_OK;
+}

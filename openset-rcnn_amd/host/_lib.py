@@ -125,6 +125,7 @@ PROTOTYPES = {
     "osr_bottleneck_fwd": (I32, [C.POINTER(BottleneckParams), P, P, P, P, P, P, P, P, P, P, P]),
     "osr_resize_tmp_bytes": (I64, [I32, I32]),
     "osr_resize_bilinear_u8": (I32, [P, I32, I32, I64, P, P, I32, P, P, I32, I32, I32, I32, I32, P, I64, P, P]),
+    "osr_resize_bilinear_u8_planar": (I32, [P, I32, I32, I32, P, P, I32, P, P, I32, I32, I32, I32, I32, I32, P, I64, P, P]),
     "osr_stem_maxpool_fwd": (I32, [P, I32, I32, I32, P, I32, P, P, I32, P]),
     "osr_stem_maxpool_fwd_raw": (I32, [P, I32, I32, I32, I32, I32, I32, C.POINTER(C.c_float), C.POINTER(C.c_float), P, I32, P, P, I32, P]),
     "osr_maxpool3x3s2": (I32, [P, I32, I32, I32, I32, P, I32, P]),
@@ -171,6 +172,9 @@ PROTOTYPES = {
     "osr_detector_postprocess": (I32, [P, P, P, P, I32, I32, P, P, P, P, P, P, P]),
     "osr_mask_upsample_predict": (I32, [P, I32, I64, I32, I32, I32, P, P, P, P, I32, P, P, I32, P, P]),
     "osr_paste_masks": (I32, [P, P, I64, I32, I32, I32, F32, P, P]),
+    "osr_tta_boxes_to_original": (I32, [P, P, P, P, P, I32, I32, I32, I32, I32, I32, I32, P, P, P, P, P]),
+    "osr_tta_boxes_to_augmented": (I32, [P, P, P, I32, I32, I32, I32, I32, P, P]),
+    "osr_tta_reduce_masks": (I32, [P, P, I32, P, I32, I32, I32, P, P]),
     # training step, forward half
     "osr_rpn_match_anchors": (I32, [P, P, I32, P, P, I32, F32, F32, F32, F32, P, P, P, P, P, I64, P]),
     "osr_subsample_labels": (I32, [P, P, I32, I64, I32, F32, P, P, P]),

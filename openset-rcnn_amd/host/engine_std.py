@@ -164,7 +164,18 @@ class StandardRCNNEngine(OpensetRCNNEngine):
         return out
 
     # ---- [d2] StandardROIHeads._forward_box (inference) -----------------------------------------------------------------------
-    def _roi_heads(self, feats, sel, image_hw, keep=None):
+    def forward_device(self, images, image_hw, hp, wp, keep=None, mask: bool = True):
+        """mask=False: the pass without the mask branch -- the four box outputs, whether or not the engine has a mask head ([d2]
+        GeneralizedRCNNWithTTA._turn_off_roi_heads: the box stage of test-time augmentation). The engine's state is not touched."""
+        if mask:
+            return super().forward_device(images, image_hw, hp, wp, keep)
+        feats = self._backbone(images, hp, wp, keep)
+        sel = self._rpn(feats, image_hw, keep)
+        if keep is not None:
+            keep.update(feats=feats, sel=sel)
+        return self._roi_heads(feats, sel, image_hw, keep, mask=False)
+
+    def _roi_heads(self, feats, sel, image_hw, keep=None, mask: bool = True):
         c = self.cfg
         n, cap = sel["boxes"].shape[0], sel["cap"]
         boxes = sel["boxes"].view(-1, 4)
@@ -187,7 +198,7 @@ class StandardRCNNEngine(OpensetRCNNEngine):
         ocl = torch.where(torch.arange(topk, device=self.device)[None, :] < dcnt[:, None], ocl, torch.full_like(ocl, -1))
         if keep is not None:
             keep.update(pooled=pooled, h1=h1, box_feats=box_feats, logits=logits, deltas=deltas, cands=cands, det_keep=dk, det_count=dcnt)
-        if self.has_mask:  # (a fifth output only when the engine has a mask head: MASK_ON False returns what it always has)
+        if self.has_mask and mask:  # (a fifth output only when the engine has a mask head: MASK_ON False returns what it always has)
             return ob, osc, ocl, dcnt, self._mask_head(feats, ob, ocl, dcnt)
         return ob, osc, ocl, dcnt
 

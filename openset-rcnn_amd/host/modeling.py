@@ -792,6 +792,43 @@ class StandardROIHeads(_EngineOwner):
         return out, {}
 
 
+    def forward_with_given_boxes(self, features: Dict[str, torch.Tensor], instances: List[Instances]) -> List[Instances]:
+        """[d2] StandardROIHeads.forward_with_given_boxes: the mask branch on boxes the caller supplies. instances carry pred_boxes and
+        pred_classes; they come back with pred_masks (k, 1, M, M) probabilities added, every other field as given -- unchanged when the
+        model has no mask head. features: the NCHW pyramid of the backbone."""
+        assert not self.training, "forward_with_given_boxes is an inference entry"
+        for inst in instances:
+            if not (inst.has("pred_boxes") and inst.has("pred_classes")):
+                raise ValueError("forward_with_given_boxes: every Instances needs pred_boxes and pred_classes")
+        if not self.mask_on:
+            return instances
+        eng = self.engine()
+        feats = {k: _to_nhwc(features[k], eng.dtype) for k in self.in_features}
+        return self._attach_masks(eng, feats, instances)
+
+    @staticmethod
+    def _attach_masks(eng, feats: Dict[str, torch.Tensor], instances: List[Instances]) -> List[Instances]:
+        """The engine's mask head on the given boxes, over its NHWC pyramid. The lists are padded to the engine's detection capacity (or
+        the longest list, when longer), so a pass's own detections run through the very launches that made its masks."""
+        dev = eng.device
+        n = len(instances)
+        cap = max([int(eng.cfg["std_detections_per_image"])] + [len(i) for i in instances])
+        boxes = torch.zeros((n, cap, 4), dtype=torch.float32)
+        classes = torch.full((n, cap), -1, dtype=torch.int64)
+        for i, inst in enumerate(instances):
+            k = len(inst)
+            boxes[i, :k] = inst.pred_boxes.tensor.detach().float().cpu()
+            classes[i, :k] = inst.pred_classes.detach().to(torch.int64).cpu()
+        counts = torch.tensor([len(i) for i in instances], dtype=torch.int32)
+        probs = eng._mask_head(feats, boxes.to(dev), classes.to(dev), counts.to(dev))
+        out = []
+        for i, inst in enumerate(instances):
+            r = Instances(inst.image_size, **inst.get_fields())
+            r.pred_masks = probs[i, : len(inst)].unsqueeze(1)
+            out.append(r)
+        return out
+
+
 def _std_instances(image_size, r: dict) -> Instances:
     """Instances of one image from OpensetRCNNEngine.to_instances' dict; pred_masks (k, 1, M, M) probabilities when the engine has a
     mask head ([d2] mask_rcnn_inference)."""
@@ -1016,9 +1053,26 @@ class GeneralizedRCNN(_EngineOwner):
         return {k: v for k, v in out.items() if k.startswith("loss_")}
 
     @torch.no_grad()
-    def inference(self, batched_inputs: List[dict], do_postprocess: bool = True):
+    def inference(self, batched_inputs: List[dict], detected_instances: Optional[List[Instances]] = None, do_postprocess: bool = True):
+        """[d2] GeneralizedRCNN.inference. detected_instances (one Instances with pred_boxes / pred_classes per input, in the model
+        input's coordinates): the box branch is skipped, the instances are returned as given with pred_masks from the mask head on
+        those boxes (unchanged by a model without one) -- StandardROIHeads only."""
         eng = self.engine()
         batch, sizes = self._stack_images([x["image"] for x in batched_inputs])
+        if detected_instances is not None:
+            if not isinstance(self.roi_heads, StandardROIHeads):
+                raise ValueError("detected_instances: StandardROIHeads only (the Openset heads have no forward_with_given_boxes)")
+            if len(detected_instances) != len(batched_inputs):
+                raise ValueError(f"detected_instances: {len(detected_instances)} Instances for {len(batched_inputs)} inputs")
+            insts = list(detected_instances)
+            if self.roi_heads.mask_on:
+                d = eng.cfg["size_divisibility"]
+                hp, wp = (int(batch.shape[-2]) + d - 1) // d * d, (int(batch.shape[-1]) + d - 1) // d * d
+                insts = StandardROIHeads._attach_masks(eng, eng._backbone(batch, hp, wp), insts)
+            if do_postprocess:
+                insts = [detector_postprocess(r, int(inp.get("height", s[0])), int(inp.get("width", s[1])))
+                         for r, inp, s in zip(insts, batched_inputs, sizes)]
+            return [{"instances": r} for r in insts]
         res = eng.forward(batch, sizes)
         if len(res) > 4:  # mask head: the masks follow their boxes through the per-image postprocess, which pastes them
             insts = [_std_instances(s, r) for r, s in zip(OpensetRCNNEngine.to_instances(res, len(sizes)), sizes)]

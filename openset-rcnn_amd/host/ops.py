@@ -542,6 +542,35 @@ def resize_bilinear_u8(img: torch.Tensor, xbounds, xcoef, kx: int, ybounds, ycoe
     return out
 
 
+def resize_bilinear_u8_planar(img: torch.Tensor, xbounds, xcoef, kx: int, ybounds, ycoef, ky: int, y_first: int, y_rows: int, nh: int, nw: int,
+                              mirror: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """PIL Image.resize(BILINEAR) of planar uint8 CUDA images, (3, h, w) or a stacked (n, 3, h, w), with Pillow's coefficient tables
+    (host/data.py: pil_resample_coeffs) -> the same shape at (nh, nw); mirror: flipped along x after the resize
+    (osr_resize_bilinear_u8_planar)."""
+    lib = _lib.load()
+    _need(img, torch.uint8, "img")
+    for t, nm in ((xbounds, "xbounds"), (xcoef, "xcoef"), (ybounds, "ybounds"), (ycoef, "ycoef")):
+        _need(t, torch.int32, nm)
+    if img.dim() not in (3, 4):
+        raise OsrError("resize_bilinear_u8_planar: img must be (planes, h, w) or (n, planes, h, w)")
+    h, w = int(img.shape[-2]), int(img.shape[-1])
+    planes = img.numel() // max(h * w, 1)
+    if tuple(xbounds.shape) != (nw, 2) or tuple(ybounds.shape) != (nh, 2) or tuple(xcoef.shape) != (nw, kx) or tuple(ycoef.shape) != (nh, ky):
+        raise OsrError("resize_bilinear_u8_planar: table shapes do not match the sizes")
+    tmp_bytes = planes * y_rows * nw
+    tmp = torch.empty((tmp_bytes,), dtype=torch.uint8, device=img.device)
+    shape = tuple(img.shape[:-2]) + (nh, nw)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=img.device)
+    else:
+        _need(out, torch.uint8, "out")
+        if tuple(out.shape) != shape:
+            raise OsrError(f"resize_bilinear_u8_planar: out must be {shape}")
+    check(lib.osr_resize_bilinear_u8_planar(_p(img), planes, h, w, _p(xbounds), _p(xcoef), kx, _p(ybounds), _p(ycoef), ky, y_first, y_rows, nh, nw,
+                                            int(bool(mirror)), _p(tmp), tmp_bytes, _p(out), _stream()), "osr_resize_bilinear_u8_planar")
+    return out
+
+
 def maxpool3x3s2(x: torch.Tensor) -> torch.Tensor:
     lib = _lib.load()
     _need(x, name="x")
@@ -1120,6 +1149,55 @@ def paste_masks(probs: torch.Tensor, boxes: torch.Tensor, out_h: int, out_w: int
         _need(out, torch.uint8, "out")
         assert tuple(out.shape) == (r, out_h, out_w)
     check(lib.osr_paste_masks(_p(probs), _p(boxes), r, m, int(out_h), int(out_w), float(threshold), _p(out), _stream()), "osr_paste_masks")
+    return out
+
+
+# ---- test-time augmentation glue (csrc/osr_tta.hip; host/tta.py) ---------------------------------------------------------------
+def _tta_lists(boxes, counts, sizes, name):
+    _need(boxes, torch.float32, "boxes"); _need(counts, torch.int32, "counts"); _need(sizes, torch.int32, "sizes")
+    if boxes.dim() != 3 or boxes.shape[2] != 4 or counts.numel() != boxes.shape[0] or tuple(sizes.shape) != (boxes.shape[0], 4):
+        raise OsrError(f"{name}: boxes (n, topk, 4), counts (n), sizes (n, 4); got {tuple(boxes.shape)}, {tuple(counts.shape)}, {tuple(sizes.shape)}")
+    return int(boxes.shape[0]), int(boxes.shape[1])
+
+
+def tta_boxes_to_original(boxes, scores, classes, counts, sizes, ha: int, wa: int, flip: bool, slot: int, c_boxes, c_scores, c_cls, c_cand) -> None:
+    """One augmentation's padded detections (boxes (n, topk, 4), scores (n, topk), classes (n, topk) int64, counts (n)) mapped back to
+    each image's output resolution -- sizes (n, 4) int32 {hi, wi, ho, wo} -- and clipped, into rows [slot, slot + topk) of the
+    per-image candidate lists c_boxes (n, cap, 4), c_scores, c_cls int32, c_cand int32 (osr_tta_boxes_to_original)."""
+    lib = _lib.load()
+    n, topk = _tta_lists(boxes, counts, sizes, "tta_boxes_to_original")
+    _need(scores, torch.float32, "scores"); _need(classes, torch.int64, "classes")
+    _need(c_boxes, torch.float32, "c_boxes"); _need(c_scores, torch.float32, "c_scores"); _need(c_cls, torch.int32, "c_cls"); _need(c_cand, torch.int32, "c_cand")
+    cap = int(c_scores.shape[1]) if c_scores.dim() == 2 else -1
+    if tuple(scores.shape) != (n, topk) or tuple(classes.shape) != (n, topk) or tuple(c_boxes.shape) != (n, cap, 4) or \
+            tuple(c_scores.shape) != (n, cap) or tuple(c_cls.shape) != (n, cap) or tuple(c_cand.shape) != (n, cap):
+        raise OsrError("tta_boxes_to_original: scores / classes (n, topk); c_boxes (n, cap, 4), c_scores / c_cls / c_cand (n, cap)")
+    check(lib.osr_tta_boxes_to_original(_p(boxes), _p(scores), _p(classes), _p(counts), _p(sizes), n, topk, int(ha), int(wa), int(bool(flip)), int(slot),
+                                        cap, _p(c_boxes), _p(c_scores), _p(c_cls), _p(c_cand), _stream()), "osr_tta_boxes_to_original")
+
+
+def tta_boxes_to_augmented(boxes, counts, sizes, ha: int, wa: int, flip: bool) -> torch.Tensor:
+    """Merged padded boxes (n, topk, 4) at each image's output resolution -> the augmentation's (ha, wa) space, not clipped; rows
+    beyond an image's count are zeros (osr_tta_boxes_to_augmented)."""
+    lib = _lib.load()
+    n, topk = _tta_lists(boxes, counts, sizes, "tta_boxes_to_augmented")
+    out = torch.empty_like(boxes)
+    check(lib.osr_tta_boxes_to_augmented(_p(boxes), _p(counts), _p(sizes), n, topk, int(ha), int(wa), int(bool(flip)), _p(out), _stream()),
+          "osr_tta_boxes_to_augmented")
+    return out
+
+
+def tta_reduce_masks(maps, flip, counts) -> torch.Tensor:
+    """maps (A, n, topk, m, m) fp32, flip (A) int32 0 / 1, counts (n) int32 -> (n, topk, m, m): the mean over the augmentations of the
+    maps, those of flipped augmentations mirrored along x; fp32 sum in augmentation order, then / A; zeros beyond the counts
+    (osr_tta_reduce_masks)."""
+    lib = _lib.load()
+    _need(maps, torch.float32, "maps"); _need(flip, torch.int32, "flip"); _need(counts, torch.int32, "counts")
+    if maps.dim() != 5 or maps.shape[3] != maps.shape[4] or flip.numel() != maps.shape[0] or counts.numel() != maps.shape[1]:
+        raise OsrError(f"tta_reduce_masks: maps (A, n, topk, m, m), flip (A), counts (n); got {tuple(maps.shape)}, {tuple(flip.shape)}, {tuple(counts.shape)}")
+    a, n, topk, m, _ = (int(v) for v in maps.shape)
+    out = torch.empty((n, topk, m, m), dtype=torch.float32, device=maps.device)
+    check(lib.osr_tta_reduce_masks(_p(maps), _p(flip), a, _p(counts), n, topk, m, _p(out), _stream()), "osr_tta_reduce_masks")
     return out
 
 

@@ -114,15 +114,23 @@ def do_test(cfg, args, model, D, iteration: int = 0):
     from openset_rcnn_amd.host.data import DatasetMapper, build_detection_test_loader
     from openset_rcnn_amd.host.evaluation import inference_on_dataset
     results = OrderedDict()
-    for name in cfg.DATASETS.TEST:
-        folder = os.path.join(cfg.OUTPUT_DIR, "inference", name, str(iteration) if iteration else "Final")
-        evaluator = D.get_evaluator(cfg, name, folder)
+    runs = [(name, "inference", model) for name in cfg.DATASETS.TEST]
+    if cfg.TEST.AUG.ENABLED:
+        # [d2] tools/train_net.py test_with_TTA: every test set once more through the wrapper, reported as <name>_TTA. (The wrapper
+        # refuses the Openset heads with a ValueError; --resume_test re-scores the detections file kept under inference_TTA/.)
+        from openset_rcnn_amd.host.tta import GeneralizedRCNNWithTTA
+        tta = GeneralizedRCNNWithTTA(cfg, model) if model is not None else None
+        runs += [(name, "inference_TTA", tta) for name in cfg.DATASETS.TEST]
+    for dataset, sub, model in runs:
+        folder = os.path.join(cfg.OUTPUT_DIR, sub, dataset, str(iteration) if iteration else "Final")
+        evaluator = D.get_evaluator(cfg, dataset, folder)
+        name = dataset + "_TTA" if sub == "inference_TTA" else dataset
         if args.resume_test:
             if "resume" not in evaluator.evaluate.__code__.co_varnames:
                 raise NotImplementedError(f"--resume_test: the evaluator of {name} keeps no detections file (COCO-style datasets only, as in the reference)")
             res = evaluator.evaluate(resume=True)
         else:
-            dicts = D.DatasetCatalog[name]()
+            dicts = D.DatasetCatalog[dataset]()
             loader = build_detection_test_loader(dicts, DatasetMapper(cfg, is_train=False), batch_size=args.test_batch)
             # the loader already yields this rank's shard only: no second split inside inference_on_dataset
             res = inference_on_dataset(model, loader, evaluator, rank=0, world=1)
