@@ -13,7 +13,7 @@
 // prefetch of the next K slice behind the current slice's MFMAs, one barrier per K step. The epilogue goes
 // through a wave-private LDS slab so that bias + residual (+ FPN upsample-add) + ReLU + down-convert are applied
 // on 16-byte row segments and the store is coalesced along channels.
-#include "osr_common.h"
+#include "osr_conv64.h"
 #include <stdlib.h>
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -262,11 +262,6 @@ static osr_status conv_launch(const ConvArgs& a0, hipStream_t st) {
 
 osr_status osr_conv_f32_run(const osr_conv_params* p, const void* in, const void* weight, const float* bias, const void* residual, void* out,
                             hipStream_t st);
-int osr_conv64_eligible(const osr_conv_params* p, long long in_bytes, long long w_bytes);
-long long osr_conv64_split_workspace_bytes(const osr_conv_params* p);
-int osr_conv64_describe(const osr_conv_params* p, int has_workspace, char* buf, int n);
-osr_status osr_conv64_run(const osr_conv_params* p, const void* in, const void* weight, const float* bias, const void* residual, const void* mask,
-                          void* out, long long in_bytes, long long w_bytes, hipStream_t st);
 
 static bool force_bk32() {
 #ifdef OSR_EXPERIMENT  // diagnostic builds only: route every layer through the BK=32 kernel

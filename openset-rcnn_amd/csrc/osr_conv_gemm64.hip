@@ -10,8 +10,8 @@
 //  * one barrier per K step: [vmcnt(0)] -> barrier -> issue tile k+1 -> 16 MFMA (32x32x16) per wave on tile k.
 //  * workgroup -> tile mapping is XCD-aware (blocks b and b+8 share an XCD/L2): each XCD walks a contiguous run of
 //    tiles with the N tiles of one M tile adjacent, so the gathered A rows are fetched into one L2 once.
-#include "osr_common.h"
-#include <stdlib.h>
+#include "osr_conv64.h"
+#include "osr_conv64_plan.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 // Fixed design choices, each measured against its alternative on one box (profiles/README.md):
@@ -97,9 +97,9 @@ struct Conv64Args {
     const float* tail_b;
     float* tail_deltas;
     float* tail_ctr;
-    int tail_lds_off;      // byte offset of the tail weights in LDS
+    int tail_lds_off;      // byte offset of the tail weights in LDS (cfrpn_tail_lds)
     FastDiv div_howo, div_wo;  // row -> (image, oh, ow); M < 2^31
-    // Split-K of the last, partial dispatch round (deep-K 1x1 / FC layers; conv64_launch_split): a launch covers the linear tiles
+    // Split-K of the last, partial dispatch round (deep-K 1x1 / FC layers; conv64_plan, conv64_launch): a launch covers the linear tiles
     // [tile0, tile0 + ntile) only; with ksplit > 1 every one of them is taken by ksplit workgroups, each over its own range of K
     // slices, which write raw fp32 partial sums (no bias / ReLU) into slab s = out + s * split_stride floats.
     int tile0, ntile, ksplit;
@@ -1077,17 +1077,15 @@ static size_t conv64_lds_bytes(int bm, int bn, int two_stage, int nw = 4) {
     return stages > epi ? stages : epi;
 }
 
-// Tuning constants. A -DOSR_EXPERIMENT build (never shipped; scripts/ab_*.sh) reads them from the environment instead, so
-// that one box can compare settings; the product library has no environment dependence.
-#ifdef OSR_EXPERIMENT
-static int env_int(const char* name, int dflt) {
-    const char* e = getenv(name);
-    return e ? atoi(e) : dflt;
+// LDS of the fused CF-RPN tail (EPI == 1) on a bm x 256 tile: the parked (bm, 256 + 8) tile takes the front, over the K loop's `stages`
+// staging buffers; at *tail_off follow the tail's weight matrix / accumulator slab (C64_TAIL_LDS) and the exponents of the five tail rows.
+static size_t cfrpn_tail_lds(int bm, int stages, int* tail_off) {
+    const size_t t_bytes = (size_t)bm * (256 + 8) * 2, stage_bytes = (size_t)stages * (bm + 256) * 128;
+    *tail_off = (int)(t_bytes > stage_bytes ? t_bytes : stage_bytes);
+    return (size_t)*tail_off + C64_TAIL_LDS(bm) + 32;
 }
-#define OSR_KNOB(name, dflt) ([] { static const int v = env_int(name, dflt); return v; }())
-#else
-#define OSR_KNOB(name, dflt) (dflt)
-#endif
+
+// Launch knobs (OSR_KNOB and the planner's own knobs: osr_conv64_plan.h).
 #ifdef OSR_EXPERIMENT
 static int ph8_enabled() { return env_int("OSR_CONV_PH8", 1); }  // (read at every launch: one process can compare the two K loops, scripts/exp_ph8.py)
 #endif
@@ -1099,9 +1097,74 @@ static void allow_big_lds(K kernel) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
 }
 
-// Tile configurations of the plain conv / FC kernel.
-enum Conv64Tile { T128x128_1 = 1, T128x128_2, T256x256_2, T128x256_1, T256x128_1, T128x64_1, T128x64_2 };
-static int force_tile() { return OSR_KNOB("OSR_CONV_FORCE_TILE", 0); }  // diagnostic: one configuration for every layer it fits
+static osr_status conv64_check_launch(const char* who) {
+    OSR_CHECK_LAUNCH(who);
+    return OSR_OK;
+}
+
+// ---- the kernel argument ----------------------------------------------------------------------------------------------
+static void conv64_stamps(Conv64Args& a, bool dbg, bool p8) {  // (which stamp buffers a launch form writes: diagnostic build only)
+#ifdef C64_STAMPS
+    a.dbg = dbg ? g_c64_stamps : nullptr; a.p8 = p8 ? g_p8_stamps : nullptr;
+#endif
+}
+
+static bool conv64_stem_view(const osr_conv_params* p) { return p->pad_mode == 1 && p->cin == 32; }  // (osr_conv64_eligible admits only kw == 1, even kh)
+
+static bool conv64_dense_in(const osr_conv_params& p) {  // 1 x 1, stride 1, no padding over a dense input: GEMM row m is input row m
+    return p.kh == 1 && p.kw == 1 && p.stride_h == 1 && p.stride_w == 1 && p.pad_h == 0 && p.pad_w == 0 && p.in_stride_w == p.cin &&
+           p.in_stride_h == (long long)p.wi * p.cin && p.in_stride_n == (long long)p.hi * p.wi * p.cin;
+}
+
+// Everything a launch form does not decide for itself: ONE convolution p over the whole grid, no mask / residual / fused tail / chain /
+// groups / levels, no dense-row shortcut. An entry point then writes only the fields that make it different. (n, ho, wo of p are not
+// part of the multi-level ABI: whatever they hold, M and the two divisors are unused there, every workgroup takes its level's; the
+// divisor of 1 only keeps fastdiv_make away from a zero.)
+static Conv64Args conv64_args(const osr_conv_params* p, const void* in, const void* weight, const float* bias, void* out, long long in_bytes, long long w_bytes) {
+    Conv64Args a{};
+    a.p = *p; a.in = in; a.w = weight; a.bias = bias; a.out = out;
+    a.M = (long long)p->n * p->ho * p->wo;
+    a.K = p->kh * p->kw * p->cin;
+    a.div_howo = fastdiv_make(a.M > 0 ? (unsigned)(p->ho * p->wo) : 1u);
+    a.div_wo = fastdiv_make(a.M > 0 ? (unsigned)p->wo : 1u);
+    a.in_bytes = (unsigned)in_bytes; a.w_bytes = (unsigned)w_bytes;
+    a.stem = conv64_stem_view(p) ? 1 : 0;
+    a.tap_minor = (!a.stem && p->kh * p->kw > 1) ? tap_minor_default() : 0;
+    a.ksplit = 1;
+    conv64_stamps(a, true, true);
+    return a;
+}
+
+// ---- argument checks of the fused launch forms --------------------------------------------------------------------------
+// `who` is the entry point's name. The status is part of the contract: on OSR_ERR_UNSUPPORTED (outside a form's envelope) host/ops.py
+// falls back to separate launches, anything else it raises. Each entry point keeps its own order of checks and its own envelope.
+#define C64_CHECK(call) do { const osr_status s__ = (call); if (s__ != OSR_OK) return s__; } while (0)
+
+static osr_status conv64_check_geometry(const osr_conv_params* p, bool taps_ok, const char* who) {  // taps_ok: the form's bound on kh, kw
+    OSR_REQUIRE(p->n >= 1 && p->hi >= 1 && p->wi >= 1 && p->kh >= 1 && p->kw >= 1 && taps_ok && p->stride_h >= 1 && p->stride_w >= 1 && p->pad_h >= 0 &&
+                    p->pad_w >= 0, OSR_ERR_INVALID_ARG, "%s: bad geometry", who);
+    OSR_REQUIRE((p->hi + 2 * p->pad_h - p->kh) / p->stride_h + 1 == p->ho && (p->wi + 2 * p->pad_w - p->kw) / p->stride_w + 1 == p->wo, OSR_ERR_INVALID_ARG,
+                "%s: ho/wo inconsistent with hi/wi/kernel/stride/pad", who);
+    return OSR_OK;
+}
+static osr_status conv64_check_in_strides(const osr_conv_params* p, const char* who) {
+    OSR_REQUIRE(p->in_stride_w % 8 == 0 && p->in_stride_h % 8 == 0 && p->in_stride_n % 8 == 0 && p->in_stride_n > 0, OSR_ERR_INVALID_ARG,
+                "%s: input strides must be multiples of 8 elements", who);
+    return OSR_OK;
+}
+static osr_status conv64_check_aligned(uintptr_t any_of, const char* who) {  // any_of: the pointers, or-ed together
+    OSR_REQUIRE((any_of & 15) == 0, OSR_ERR_INVALID_ARG, "%s: pointers must be 16-byte aligned", who);
+    return OSR_OK;
+}
+static osr_status conv64_check_storage(const osr_conv_params* p, bool same_out, const char* who) {
+    OSR_REQUIRE(p->in_dtype == OSR_F16 || p->in_dtype == OSR_BF16, OSR_ERR_UNSUPPORTED, "%s: in_dtype must be f16/bf16", who);
+    OSR_REQUIRE(!same_out || p->out_dtype == p->in_dtype, OSR_ERR_UNSUPPORTED, "%s: out_dtype must equal in_dtype", who);
+    return OSR_OK;
+}
+// 32-bit row indices (fastdiv) and buffer offsets
+static bool conv64_rows_fit(long long rows) { return rows < (1ll << 31) - 1024; }
+static bool conv64_bytes_fit(long long bytes) { return bytes < (1ll << 31) - 4096; }
+#define C64_REQUIRE_FITS(cond, who) OSR_REQUIRE(cond, OSR_ERR_UNSUPPORTED, "%s: tensor too large for 32-bit buffer offsets", who)
 
 template <class TI, class TO, int BM, int BN, int WM, int WN, int TWO, int SPLIT = 0>
 static void conv64_launch_tile(Conv64Args& a, hipStream_t st) {
@@ -1109,115 +1172,13 @@ static void conv64_launch_tile(Conv64Args& a, hipStream_t st) {
     a.two_stage = TWO;
     a.tiles_m = (int)((a.M + BM - 1) / BM);
     a.tiles_n = (a.p.cout + BN - 1) / BN;
-    if (a.ntile <= 0) { a.tile0 = 0; a.ntile = a.tiles_m * a.tiles_n; a.ksplit = 1; }  // the whole grid in one launch
+    if (a.ntile <= 0) a.ntile = a.tiles_m * a.tiles_n;  // the whole grid in one launch
     const size_t lds = conv64_lds_bytes(BM, BN, TWO, NW);
     if (lds > 64 * 1024) {
         static osr_dev_mask attr{0};  // (one per instantiation of this function template)
         osr_once_per_device(attr, [] { allow_big_lds(conv_igemm64_kernel<TI, TO, BM, BN, WM, WN, 0, TWO, SPLIT>); });
     }
     hipLaunchKernelGGL((conv_igemm64_kernel<TI, TO, BM, BN, WM, WN, 0, TWO, SPLIT>), dim3((unsigned)a.ntile * (SPLIT ? a.ksplit : 1)), dim3(NW * 64), lds, st, a);
-}
-
-// Tile choice by a small cost model instead of per-layer thresholds. Measured on MI355X (scripts/ab_tiles.sh): with the
-// staging pieces interleaved into the MFMA stream every configuration saturates at the same ~4.45 TFLOP/s per CU once a CU
-// holds its full complement of workgroups, so what separates them is (i) how many dispatch rounds the grid needs at
-// `occ` workgroups per CU (VGPR / LDS limited) and how empty the last round is, and (ii) whether a K slice is bound by
-// the matrix pipe (r residents x w) or by the L2 -> LDS latency (single buffer: L + w, double buffer: max(L, r x w)).
-//   time = full_rounds x tile(occ) + tile(residents of the last partial round),  tile(r) = fixed + nk x slice(r)
-// The 256-wide tiles read the residual in the epilogue (no prefetch under the K loop), which measured 1.6x slower on the
-// HBM-bound residual layers: they are not offered to a residual layer with fewer than 18 K slices.
-#ifndef C64_BIG_CAP
-#define C64_BIG_CAP 5.2e6  // per-CU rate of the 256 x 256 tile under load, FLOP per us
-#endif
-struct TileCfg { int id, bm, bn, two, occ, pre_res; double cap; };  // cap: per-CU MFMA rate under load, FLOP per us
-static const TileCfg kTileCfgs[] = {
-    {T128x128_1, 128, 128, 0, 3, 1, 4.45e6}, {T128x128_2, 128, 128, 1, 2, 1, 4.45e6}, {T256x256_2, 256, 256, 1, 1, 0, C64_BIG_CAP},
-    {T128x256_1, 128, 256, 0, 2, 0, 4.45e6}, {T256x128_1, 256, 128, 0, 2, 0, 4.45e6}, {T128x64_1, 128, 64, 0, 4, 1, 4.45e6},
-    {T128x64_2, 128, 64, 1, 3, 1, 4.45e6},
-};
-
-static double conv64_tile_us(const TileCfg& c, int nk, int residents, bool res) {
-    const double kLat = 1.0;  // L2 -> LDS latency of one staged slice (us)
-    const double w = (double)c.bm * c.bn * 128.0 / c.cap;  // (the 256 x 256 tile measured 1.61 us per slice on fpn_output2: 5.2 TFLOP/s per CU)
-    const double busy = residents * w;
-    const double slice = c.two ? (busy > kLat + 0.1 ? busy : kLat + 0.1) : (busy > kLat + w ? busy : kLat + w);
-    const double fixed = 1.5 + (c.two ? kLat : 0.0) + (double)c.bm * c.bn / 16384.0 * 1.3 * (res ? 1.5 : 1.0);
-    return fixed + nk * slice;
-}
-
-// When the caller runs several streams side by side (osr_conv_params.concurrency >= 2: the engine's micro-batch streams) the
-// modelled time of the 256 x 256 tile is scaled by 0.8 (OSR_CONV_MODEL_BIG, percent): the empty part of a
-// one-workgroup-per-CU round is then filled by the other stream's launches, and the big tile
-// moves half the L2 -> LDS and LDS -> register bytes per FLOP of the 128 x 128 tile, which is what counts once both streams
-// compete for a CU (same-box end-to-end A/B with the per-configuration rates above: 1.00 -> 1169, 0.85 -> 1221, 0.75 -> 1219,
-// 0.65 -> 1208 img/s).
-static double model_big_scale() { return OSR_KNOB("OSR_CONV_MODEL_BIG", 80) / 100.0; }
-
-static int conv64_pick_tile(const Conv64Args& a) {
-    const int nk = a.K / 64, cout = a.p.cout;
-    const bool res = a.p.res_mode != 0;
-    const int f = force_tile();
-    if (f != 0) {
-        const bool fits = (f == T256x256_2 || f == T128x256_1) ? cout % 256 == 0 : f == T256x128_1 ? cout % 128 == 0 : true;
-        if (fits && !((f == T128x128_2 || f == T128x64_2 || f == T256x256_2) && nk < 2)) return f;
-    }
-    int best = T128x128_1;
-    double best_us = 1e30;
-    for (const TileCfg& c : kTileCfgs) {
-        if (c.bn == 256 && cout % 256 != 0) continue;
-        if (cout <= 64 && c.bn != 64) continue;          // narrow layers: no half-empty N tiles
-        // the 256-wide tiles read the residual in the epilogue, unprefetched: not for the short-K (HBM-bound) residual layers. From 18 K slices on
-        // (a 3 x 3 layer of >= 128 channels: the data gradients of fpn_output2/3 with their ReLU-mask / gradient-sum epilogues) the epilogue is
-        // a few per cent of the tile and the 256 x 256 8-phase loop wins (round 5: fpn_output2's dgrad 1.65 -> 1.2 ms)
-        if (res && !c.pre_res && nk < 18) continue;
-        if (c.two && nk < 2) continue;
-        const long long tiles = (a.M + c.bm - 1) / c.bm * ((cout + c.bn - 1) / c.bn), slots = 256ll * c.occ;
-        const long long full = tiles / slots, rem = tiles % slots;
-        double us = (double)full * conv64_tile_us(c, nk, c.occ, res);
-        if (rem) us += conv64_tile_us(c, nk, (int)((rem + 255) / 256), res);
-        if (c.id == T256x256_2 && a.p.concurrency >= 2) us *= model_big_scale();
-        if (us < best_us) { best_us = us; best = c.id; }
-    }
-    return best;
-}
-
-// ---- split-K of the tail round ---------------------------------------------------------------------------------------
-// A grid of T tiles on S = 256 x occ slots runs floor(T / S) full dispatch rounds and one round that is only (T mod S) / S full.
-// For a deep-K 1x1 / FC layer (FC1: 1072 tiles of 256 x 256 on 256 slots, 196 K slices: 4.19 rounds, the fifth one 19 % full)
-// the partial round is cut along K instead: its tiles go to a second launch in which ksplit workgroups share each tile's K loop
-// and write fp32 partial sums, and a small third launch adds them up and applies the epilogue. The partial sums are summed in
-// a fixed order: the result does not depend on timing.
-struct SplitPlan { int tile_id, tail_mtiles, ksplit; long long m_tail0, ws_bytes; };
-
-static bool conv64_plan_split(const Conv64Args& a, SplitPlan* sp) {
-    const osr_conv_params& p = a.p;
-    if (a.stem || p.res_mode != 0 || a.mask || p.stride_h != 1 || p.stride_w != 1 || p.cin % 64 != 0) return false;
-    if (p.out_stride_w != p.cout || p.out_stride_h != (long long)p.wo * p.cout || p.out_stride_n != (long long)p.ho * p.wo * p.cout) return false;  // dense output rows
-    const int nk = a.K / 64;
-    // the partial sums (tail rows x cout x 4 B x ksplit, written and read once) must be small beside the K loop: 48 slices for a 1 x 1 /
-    // FC layer, 32 for a KH x KW convolution (round 4: the 3 x 3 layers of res4 / FPN p4, 1050 tiles of 128 x 128 on 768 slots)
-    if (nk < (p.kh * p.kw > 1 ? 32 : 48)) return false;
-    const int id = conv64_pick_tile(a);
-    if (id != T256x256_2 && id != T128x128_1 && id != T128x256_1) return false;  // the tile shapes with a split-K tail instantiation
-    const TileCfg* c = nullptr;
-    for (const TileCfg& k : kTileCfgs) if (k.id == id) c = &k;
-    if (!c) return false;
-    const long long tiles_m = (a.M + c->bm - 1) / c->bm, tiles_n = (p.cout + c->bn - 1) / c->bn, tiles = tiles_m * tiles_n, slots = 256ll * c->occ;
-    const long long full = tiles / slots, rem = tiles % slots;
-    if (full < 1 || rem == 0 || rem * 2 > slots) return false;
-    // a K x K convolution needs at least two full rounds in front of the tail: with one (res4's 3 x 3 layers at batch 16, 1050 tiles on
-    // 768 slots) the two extra launches and the partial sums cost more than the half-empty round (measured 100 -> 115 us), with four
-    // (fpn_output3 on 256 x 256 tiles) the split takes 380 -> 321 us (scripts/exp_split3x3.py)
-    if (p.kh * p.kw > 1 && full < 2) return false;
-    const long long tail_mt = (rem + tiles_n - 1) / tiles_n;  // whole rows of M tiles
-    long long ks = slots / (tail_mt * tiles_n);
-    if (ks > 8) ks = 8;
-    if (ks > nk / 8) ks = nk / 8;
-    if (ks < 2) return false;
-    sp->tile_id = id; sp->tail_mtiles = (int)tail_mt; sp->ksplit = (int)ks;
-    sp->m_tail0 = (tiles_m - tail_mt) * c->bm;
-    sp->ws_bytes = ks * (a.M - sp->m_tail0) * p.cout * 4;
-    return true;
 }
 
 template <class TO>
@@ -1252,44 +1213,36 @@ template <class TI, class TO> static void conv64_dispatch_tile(int id, Conv64Arg
 
 template <class TI, class TO>
 static osr_status conv64_launch(Conv64Args& a, hipStream_t st) {
-    a.tail_lds_off = 0;
-    a.tile0 = 0; a.ntile = 0; a.ksplit = 1; a.split_stride = 0;
-    SplitPlan sp;
-    if (a.p.workspace && conv64_plan_split(a, &sp) && a.p.workspace_bytes >= sp.ws_bytes && (((uintptr_t)a.p.workspace) & 15) == 0) {
-        const TileCfg* c = nullptr;
-        for (const TileCfg& k : kTileCfgs) if (k.id == sp.tile_id) c = &k;
-        const int tiles_m = (int)((a.M + c->bm - 1) / c->bm), tiles_n = (a.p.cout + c->bn - 1) / c->bn;
-        // 1. the full rounds
-        Conv64Args m = a;
-        m.tile0 = 0; m.ntile = (tiles_m - sp.tail_mtiles) * tiles_n; m.ksplit = 1;
-        conv64_dispatch_tile<TI, TO>(sp.tile_id, m, st);
-        // 2. the tail tiles, ksplit workgroups each, raw fp32 partial sums into the workspace slabs (rows relative to m_tail0)
-        const long long tail_rows = a.M - sp.m_tail0;
-        Conv64Args t = a;
-        t.tile0 = m.ntile; t.ntile = sp.tail_mtiles * tiles_n; t.ksplit = sp.ksplit;
-        t.split_stride = tail_rows * a.p.cout;
-        t.out = reinterpret_cast<float*>(a.p.workspace) - sp.m_tail0 * a.p.cout;  // the epilogue adds row * cout: slab row 0 = output row m_tail0
-        t.p.relu = 0; t.p.out_dtype = OSR_F32;
-        switch (sp.tile_id) {
-            case T256x256_2: conv64_launch_tile<TI, float, 256, 256, 2, 4, 2, 1>(t, st); break;
-            case T128x256_1: conv64_launch_tile<TI, float, 128, 256, 2, 2, 0, 1>(t, st); break;
-            default: conv64_launch_tile<TI, float, 128, 128, 2, 2, 0, 1>(t, st); break;
-        }
-        // 3. fixed-order sum of the slabs + bias + ReLU + conversion
-        const long long n4 = tail_rows * a.p.cout / 4;
-        long long blocks = (n4 + 255) / 256;
-        if (blocks > 2048) blocks = 2048;
-        hipLaunchKernelGGL(splitk_reduce_kernel<TO>, dim3((unsigned)blocks), dim3(256), 0, st, reinterpret_cast<const float*>(a.p.workspace), sp.ksplit,
-                           t.split_stride, n4, a.p.cout, a.bias, a.p.relu, reinterpret_cast<TO*>(a.out) + sp.m_tail0 * a.p.cout,
-                           a.p.row_seg_counts, (long long)a.p.row_seg_rows, c->bm, sp.m_tail0, a.M);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) { osr_set_error("osr_conv2d_fwd(bk64, split-K tail): launch failed: %s", hipGetErrorString(e)); return OSR_ERR_LAUNCH; }
-        return OSR_OK;
+    const Conv64Plan pl = conv64_plan(a.p, a.M, a.K, a.stem, a.mask != nullptr, a.p.workspace != nullptr);
+    // the split plan only with a workspace that is large enough and 16-byte aligned
+    if (!pl.split || a.p.workspace_bytes < pl.ws_bytes || (((uintptr_t)a.p.workspace) & 15) != 0) {
+        conv64_dispatch_tile<TI, TO>(pl.tile.id, a, st);
+        return conv64_check_launch("osr_conv2d_fwd(bk64)");
     }
-    conv64_dispatch_tile<TI, TO>(conv64_pick_tile(a), a, st);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { osr_set_error("osr_conv2d_fwd(bk64): launch failed: %s", hipGetErrorString(e)); return OSR_ERR_LAUNCH; }
-    return OSR_OK;
+    // 1. the full rounds
+    Conv64Args m = a;
+    m.ntile = (int)((pl.tiles_m - pl.tail_mtiles) * pl.tiles_n);
+    conv64_dispatch_tile<TI, TO>(pl.tile.id, m, st);
+    // 2. the tail tiles, ksplit workgroups each, raw fp32 partial sums into the workspace slabs (rows relative to m_tail0)
+    const long long tail_rows = a.M - pl.m_tail0;
+    Conv64Args t = a;
+    t.tile0 = m.ntile; t.ntile = (int)(pl.tail_mtiles * pl.tiles_n); t.ksplit = pl.ksplit;
+    t.split_stride = tail_rows * a.p.cout;
+    t.out = reinterpret_cast<float*>(a.p.workspace) - pl.m_tail0 * a.p.cout;  // the epilogue adds row * cout: slab row 0 = output row m_tail0
+    t.p.relu = 0; t.p.out_dtype = OSR_F32;
+    switch (pl.tile.id) {
+        case T256x256_2: conv64_launch_tile<TI, float, 256, 256, 2, 4, 2, 1>(t, st); break;
+        case T128x256_1: conv64_launch_tile<TI, float, 128, 256, 2, 2, 0, 1>(t, st); break;
+        default: conv64_launch_tile<TI, float, 128, 128, 2, 2, 0, 1>(t, st); break;
+    }
+    // 3. fixed-order sum of the slabs + bias + ReLU + conversion
+    const long long n4 = tail_rows * a.p.cout / 4;
+    long long blocks = (n4 + 255) / 256;
+    if (blocks > 2048) blocks = 2048;
+    hipLaunchKernelGGL(splitk_reduce_kernel<TO>, dim3((unsigned)blocks), dim3(256), 0, st, reinterpret_cast<const float*>(a.p.workspace), pl.ksplit,
+                       t.split_stride, n4, a.p.cout, a.bias, a.p.relu, reinterpret_cast<TO*>(a.out) + pl.m_tail0 * a.p.cout,
+                       a.p.row_seg_counts, (long long)a.p.row_seg_rows, pl.tile.bm, pl.m_tail0, a.M);
+    return conv64_check_launch("osr_conv2d_fwd(bk64, split-K tail)");
 }
 
 template <class TI, class TO>
@@ -1314,116 +1267,43 @@ static void conv64_dispatch_tile(int id, Conv64Args& a, hipStream_t st) {
     }
 }
 
-// Host-side description of how osr_conv2d_fwd covers this layer (tests).
 int osr_conv64_describe(const osr_conv_params* p, int has_workspace, char* buf, int n) {
-    Conv64Args a;
-    a.p = *p; a.mask = nullptr;
-    a.M = (long long)p->n * p->ho * p->wo;
-    a.K = p->kh * p->kw * p->cin;
-    a.stem = (p->pad_mode == 1 && p->cin == 32) ? 1 : 0;
-    auto nm = [](int id) { for (const TileCfg& k : kTileCfgs) if (k.id == id) return k; return kTileCfgs[0]; };
-    SplitPlan sp;
-    if (has_workspace && conv64_plan_split(a, &sp)) {
-        const TileCfg c = nm(sp.tile_id);
-        return snprintf(buf, n, "%dx%d/%d rows [0,%lld) + split-K x%d tail rows [%lld,%lld) + reduce", c.bm, c.bn, c.two + 1, sp.m_tail0, sp.ksplit, sp.m_tail0, a.M);
-    }
-    const TileCfg c1 = nm(conv64_pick_tile(a));
-    return snprintf(buf, n, "%dx%d/%d rows [0,%lld)", c1.bm, c1.bn, c1.two + 1, a.M);
+    const long long M = (long long)p->n * p->ho * p->wo;
+    const Conv64Plan pl = conv64_plan(*p, M, p->kh * p->kw * p->cin, conv64_stem_view(p), false, has_workspace != 0);
+    const TileCfg& c = pl.tile;
+    if (pl.split)
+        return snprintf(buf, n, "%dx%d/%d rows [0,%lld) + split-K x%d tail rows [%lld,%lld) + reduce", c.bm, c.bn, c.two + 1, pl.m_tail0, pl.ksplit, pl.m_tail0, M);
+    return snprintf(buf, n, "%dx%d/%d rows [0,%lld)", c.bm, c.bn, c.two + 1, M);
 }
 
-// Bytes of workspace with which osr_conv2d_fwd cuts this layer's partial last dispatch round along K (0: not applicable).
 long long osr_conv64_split_workspace_bytes(const osr_conv_params* p) {
-    Conv64Args a;
-    a.p = *p; a.mask = nullptr;
-    a.M = (long long)p->n * p->ho * p->wo;
-    a.K = p->kh * p->kw * p->cin;
-    a.stem = (p->pad_mode == 1 && p->cin == 32) ? 1 : 0;
-    SplitPlan sp;
-    if (p->cin % 64 != 0 || a.M >= (1ll << 31) - 1024) return 0;
-    return conv64_plan_split(a, &sp) ? sp.ws_bytes : 0;
+    const long long M = (long long)p->n * p->ho * p->wo;
+    if (p->cin % 64 != 0 || !conv64_rows_fit(M)) return 0;
+    return conv64_plan(*p, M, p->kh * p->kw * p->cin, conv64_stem_view(p), false, true).ws_bytes;
 }
 
-template <class TI>
-static osr_status cfrpn_fused_launch(Conv64Args& a, hipStream_t st) {
-    a.tiles_n = 1;
-    a.tile0 = 0; a.ksplit = 1; a.split_stride = 0;
-    if ((a.M + 255) / 256 >= rpn_big_min_tiles() && a.K / 64 >= 8) {
-        a.two_stage = 1;
-        a.tiles_m = (int)((a.M + 255) / 256);
-        a.ntile = a.tiles_m;
-        const size_t t_bytes = (size_t)256 * (256 + 8) * 2, stages = (size_t)2 * (256 + 256) * 128;
-        a.tail_lds_off = (int)(t_bytes > stages ? t_bytes : stages);
-        const size_t lds = (size_t)a.tail_lds_off + C64_TAIL_LDS(256) + 32;
-        static osr_dev_mask attr8{0};
-        osr_once_per_device(attr8, [] {
-            allow_big_lds(conv_igemm64_kernel<TI, TI, 256, 256, 2, 4, 1, 2>);
-#ifdef OSR_EXPERIMENT
-            allow_big_lds(conv_igemm64_kernel<TI, TI, 256, 256, 2, 4, 1, 1>);
-#endif
-        });
-#ifdef OSR_EXPERIMENT
-        if (!ph8_enabled()) hipLaunchKernelGGL((conv_igemm64_kernel<TI, TI, 256, 256, 2, 4, 1, 1>), dim3((unsigned)a.tiles_m), dim3(512), lds, st, a);
-        else
-#endif
-        hipLaunchKernelGGL((conv_igemm64_kernel<TI, TI, 256, 256, 2, 4, 1, 2>), dim3((unsigned)a.tiles_m), dim3(512), lds, st, a);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) { osr_set_error("osr_cfrpn_head_fwd: launch failed: %s", hipGetErrorString(e)); return OSR_ERR_LAUNCH; }
-        return OSR_OK;
-    }
-    a.two_stage = 0;
-    a.tiles_m = (int)((a.M + 127) / 128);
-    a.ntile = a.tiles_m;
-    const size_t t_bytes = (size_t)128 * (256 + 8) * 2, stage = (size_t)(128 + 256) * 128;
-    a.tail_lds_off = (int)(t_bytes > stage ? t_bytes : stage);
-    const size_t lds = (size_t)a.tail_lds_off + C64_TAIL_LDS(128) + 32;
-    static osr_dev_mask attr{0};
-    osr_once_per_device(attr, [] { allow_big_lds(conv_igemm64_kernel<TI, TI, 128, 256, 2, 2, 1, 0>); });
-    hipLaunchKernelGGL((conv_igemm64_kernel<TI, TI, 128, 256, 2, 2, 1, 0>), dim3((unsigned)a.tiles_m), dim3(256), lds, st, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { osr_set_error("osr_cfrpn_head_fwd: launch failed: %s", hipGetErrorString(e)); return OSR_ERR_LAUNCH; }
-    return OSR_OK;
-}
-
-// Returns 1 when this fast path can take the problem (all arguments already validated by osr_conv2d_fwd).
 int osr_conv64_eligible(const osr_conv_params* p, long long in_bytes, long long w_bytes) {
     const bool stem = p->pad_mode == 1 && p->cin == 32 && p->kw == 1 && (p->kh % 2) == 0;
     if (!stem && p->cin % 64 != 0) return 0;
     if (!stem && p->kh * p->kw > 31) return 0;  // per-row tap validity mask: 31 bits
-    if ((long long)p->n * p->ho * p->wo >= (1ll << 31) - 1024) return 0;  // 32-bit row indices (fastdiv)
-    if (in_bytes <= 0 || w_bytes <= 0 || in_bytes >= (1ll << 31) - 4096 || w_bytes >= (1ll << 31) - 4096) return 0;
+    if (!conv64_rows_fit((long long)p->n * p->ho * p->wo)) return 0;
+    if (in_bytes <= 0 || w_bytes <= 0 || !conv64_bytes_fit(in_bytes) || !conv64_bytes_fit(w_bytes)) return 0;
     return 1;
 }
 
 osr_status osr_conv64_run(const osr_conv_params* p, const void* in, const void* weight, const float* bias, const void* residual, const void* mask,
                           void* out, long long in_bytes, long long w_bytes, hipStream_t st) {
-    Conv64Args a;
-    a.p = *p; a.in = in; a.w = weight; a.bias = bias; a.res = residual; a.mask = mask; a.out = out;
-    a.M = (long long)p->n * p->ho * p->wo;
-    a.K = p->kh * p->kw * p->cin;
-    a.div_howo = fastdiv_make((unsigned)(p->ho * p->wo));
-    a.div_wo = fastdiv_make((unsigned)p->wo);
-    a.in_bytes = (unsigned)in_bytes; a.w_bytes = (unsigned)w_bytes;
-    a.stem = (p->pad_mode == 1 && p->cin == 32) ? 1 : 0;
-    a.tap_minor = (!a.stem && p->kh * p->kw > 1) ? tap_minor_default() : 0;
-    {   // dense 1 x 1 layers (conv1 / conv3 of the bottlenecks, FC1 / FC2, their data gradients): see Conv64Args::pw_dense
-        const bool in_dense = p->in_stride_w == p->cin && p->in_stride_h == (long long)p->wi * p->cin && p->in_stride_n == (long long)p->hi * p->wi * p->cin;
-        const bool out_dense = p->out_stride_w == p->cout && p->out_stride_h == (long long)p->wo * p->cout && p->out_stride_n == (long long)p->ho * p->wo * p->cout;
-        const long long widest = p->cin > p->cout ? p->cin : p->cout;
-        const bool fits = a.M * widest < (1ll << 31), res_dense = (p->res_mode == 1 || p->res_mode == 3) && p->res_stride_w == p->out_stride_w &&
-                                                                    p->res_stride_h == p->out_stride_h && p->res_stride_n == p->out_stride_n;
-        a.pw_dense = 0;
-        if (fits && !a.stem) {
-            if (p->kh == 1 && p->kw == 1 && p->stride_h == 1 && p->stride_w == 1 && p->pad_h == 0 && p->pad_w == 0 && p->pad_mode == 0 && in_dense) a.pw_dense |= 1;
-            if (out_dense) a.pw_dense |= 2;
-            if (out_dense && res_dense) a.pw_dense |= 4;
-        }
+    Conv64Args a = conv64_args(p, in, weight, bias, out, in_bytes, w_bytes);
+    a.res = residual; a.mask = mask;
+    // dense 1 x 1 layers (conv1 / conv3 of the bottlenecks, FC1 / FC2, their data gradients): see Conv64Args::pw_dense
+    const long long widest = p->cin > p->cout ? p->cin : p->cout;
+    if (a.M * widest < (1ll << 31) && !a.stem) {
+        const bool out_dense = conv64_dense_out(*p), res_dense = (p->res_mode == 1 || p->res_mode == 3) && p->res_stride_w == p->out_stride_w &&
+                                                                   p->res_stride_h == p->out_stride_h && p->res_stride_n == p->out_stride_n;
+        if (p->pad_mode == 0 && conv64_dense_in(*p)) a.pw_dense |= 1;
+        if (out_dense) a.pw_dense |= 2;
+        if (out_dense && res_dense) a.pw_dense |= 4;
     }
-    a.tiles_m = a.tiles_n = 0;
-    a.tail_w = a.tail_b = nullptr; a.tail_deltas = a.tail_ctr = nullptr;
-    a.w3 = nullptr; a.bias3 = nullptr; a.cout3 = 0; a.w3_bytes = a.out_bytes = 0;
-#ifdef C64_STAMPS
-    a.dbg = g_c64_stamps; a.p8 = g_p8_stamps;
-#endif
     if (p->in_dtype == OSR_F16) {
         if (p->out_dtype == OSR_F16) return conv64_launch<f16_t, f16_t>(a, st);
         if (p->out_dtype == OSR_F32) return conv64_launch<f16_t, float>(a, st);
@@ -1435,49 +1315,57 @@ osr_status osr_conv64_run(const osr_conv_params* p, const void* in, const void* 
     return OSR_ERR_UNSUPPORTED;
 }
 
+// ---- the fused CF-RPN head (include/osr.h: osr_cfrpn_head_fwd, osr_cfrpn_head_fwd_levels) ------------------------------------------
+// One launch of the EPI == 1 kernel on tiles_m tiles of BM x 256 (a.M rows, or the levels' tiles: conv64_fill_levels).
+template <class TI, int BM, int WN, int TWO>
+static void cfrpn_launch_tile(Conv64Args& a, int tiles_m, hipStream_t st) {
+    a.two_stage = TWO ? 1 : 0;
+    a.tiles_m = a.ntile = tiles_m; a.tiles_n = 1;
+    const size_t lds = cfrpn_tail_lds(BM, TWO ? 2 : 1, &a.tail_lds_off);
+    static osr_dev_mask attr{0};  // (one per instantiation of this function template)
+    osr_once_per_device(attr, [] { allow_big_lds(conv_igemm64_kernel<TI, TI, BM, 256, 2, WN, 1, TWO>); });
+    hipLaunchKernelGGL((conv_igemm64_kernel<TI, TI, BM, 256, 2, WN, 1, TWO>), dim3((unsigned)tiles_m), dim3(2 * WN * 64), lds, st, a);
+}
+
+template <class TI>
+static osr_status cfrpn_fused_launch(Conv64Args& a, hipStream_t st) {
+    if ((a.M + 255) / 256 >= rpn_big_min_tiles() && a.K / 64 >= 8) {
+#ifdef OSR_EXPERIMENT
+        if (!ph8_enabled()) cfrpn_launch_tile<TI, 256, 4, 1>(a, (int)((a.M + 255) / 256), st);
+        else
+#endif
+        cfrpn_launch_tile<TI, 256, 4, 2>(a, (int)((a.M + 255) / 256), st);
+    } else {
+        cfrpn_launch_tile<TI, 128, 2, 0>(a, (int)((a.M + 127) / 128), st);
+    }
+    return conv64_check_launch("osr_cfrpn_head_fwd");
+}
+
 // Whole ClsFreeRPNHead.forward for one level (3x3 conv + ReLU + channel L2-normalise + two 1x1 convs + sigmoid) in one
 // launch; deltas/ctr are written at pixel index n*ho*wo + oh*wo + ow. Returns OSR_ERR_UNSUPPORTED when the shape is
 // outside the fused kernel's envelope (the caller then runs osr_conv2d_fwd + osr_cfrpn_head_tail).
 extern "C" osr_status osr_cfrpn_head_fwd_ex(const osr_conv_params* p, const void* in, const void* weight, const float* bias, const float* w_tail,
-                                            const float* b_tail, float* deltas, float* ctr, void* hidden_out, void* stream);
+                                            const float* b_tail, float* deltas, float* ctr, void* hidden_out, void* stream) {
+    const char* who = "osr_cfrpn_head_fwd";
+    OSR_REQUIRE(p && in && weight && bias && w_tail && b_tail && deltas && ctr, OSR_ERR_INVALID_ARG, "%s: null pointer", who);
+    OSR_REQUIRE((((uintptr_t)hidden_out) & 15) == 0, OSR_ERR_INVALID_ARG, "%s: hidden_out must be 16-byte aligned", who);
+    OSR_REQUIRE(p->cout == 256 && p->cin % 64 == 0 && p->pad_mode == 0 && p->res_mode == 0, OSR_ERR_UNSUPPORTED,
+                "%s: fused path needs cout == 256, cin %% 64 == 0, no residual", who);
+    C64_CHECK(conv64_check_storage(p, false, who));
+    C64_CHECK(conv64_check_geometry(p, p->kh <= 16 && p->kw <= 16, who));
+    C64_CHECK(conv64_check_in_strides(p, who));
+    C64_CHECK(conv64_check_aligned((uintptr_t)in | (uintptr_t)weight | (uintptr_t)bias | (uintptr_t)deltas, who));
+    const long long in_bytes = (long long)p->n * p->in_stride_n * 2, w_bytes = (long long)p->cout * p->kh * p->kw * p->cin * 2;
+    C64_REQUIRE_FITS(osr_conv64_eligible(p, in_bytes, w_bytes), who);
+    Conv64Args a = conv64_args(p, in, weight, bias, hidden_out, in_bytes, w_bytes);
+    a.tail_w = w_tail; a.tail_b = b_tail; a.tail_deltas = deltas; a.tail_ctr = ctr;
+    conv64_stamps(a, false, true);
+    hipStream_t st = (hipStream_t)stream;
+    return p->in_dtype == OSR_F16 ? cfrpn_fused_launch<f16_t>(a, st) : cfrpn_fused_launch<bf16_t>(a, st);
+}
 extern "C" osr_status osr_cfrpn_head_fwd(const osr_conv_params* p, const void* in, const void* weight, const float* bias,
                                          const float* w_tail, const float* b_tail, float* deltas, float* ctr, void* stream) {
     return osr_cfrpn_head_fwd_ex(p, in, weight, bias, w_tail, b_tail, deltas, ctr, nullptr, stream);
-}
-
-extern "C" osr_status osr_cfrpn_head_fwd_ex(const osr_conv_params* p, const void* in, const void* weight, const float* bias, const float* w_tail,
-                                            const float* b_tail, float* deltas, float* ctr, void* hidden_out, void* stream) {
-    OSR_REQUIRE(p && in && weight && bias && w_tail && b_tail && deltas && ctr, OSR_ERR_INVALID_ARG, "osr_cfrpn_head_fwd: null pointer");
-    OSR_REQUIRE((((uintptr_t)hidden_out) & 15) == 0, OSR_ERR_INVALID_ARG, "osr_cfrpn_head_fwd: hidden_out must be 16-byte aligned");
-    OSR_REQUIRE(p->cout == 256 && p->cin % 64 == 0 && p->pad_mode == 0 && p->res_mode == 0, OSR_ERR_UNSUPPORTED,
-                "osr_cfrpn_head_fwd: fused path needs cout == 256, cin %% 64 == 0, no residual");
-    OSR_REQUIRE(p->in_dtype == OSR_F16 || p->in_dtype == OSR_BF16, OSR_ERR_UNSUPPORTED, "osr_cfrpn_head_fwd: in_dtype must be f16/bf16");
-    OSR_REQUIRE(p->n >= 1 && p->hi >= 1 && p->wi >= 1 && p->kh >= 1 && p->kw >= 1 && p->kh <= 16 && p->kw <= 16 && p->stride_h >= 1 && p->stride_w >= 1 &&
-                    p->pad_h >= 0 && p->pad_w >= 0, OSR_ERR_INVALID_ARG, "osr_cfrpn_head_fwd: bad geometry");
-    OSR_REQUIRE((p->hi + 2 * p->pad_h - p->kh) / p->stride_h + 1 == p->ho && (p->wi + 2 * p->pad_w - p->kw) / p->stride_w + 1 == p->wo,
-                OSR_ERR_INVALID_ARG, "osr_cfrpn_head_fwd: ho/wo inconsistent with hi/wi/kernel/stride/pad");
-    OSR_REQUIRE(p->in_stride_w % 8 == 0 && p->in_stride_h % 8 == 0 && p->in_stride_n % 8 == 0 && p->in_stride_n > 0, OSR_ERR_INVALID_ARG,
-                "osr_cfrpn_head_fwd: input strides must be multiples of 8 elements");
-    OSR_REQUIRE((((uintptr_t)in | (uintptr_t)weight | (uintptr_t)bias | (uintptr_t)deltas) & 15) == 0, OSR_ERR_INVALID_ARG,
-                "osr_cfrpn_head_fwd: pointers must be 16-byte aligned");
-    const long long in_bytes = (long long)p->n * p->in_stride_n * 2, w_bytes = (long long)p->cout * p->kh * p->kw * p->cin * 2;
-    OSR_REQUIRE(osr_conv64_eligible(p, in_bytes, w_bytes), OSR_ERR_UNSUPPORTED, "osr_cfrpn_head_fwd: tensor too large for 32-bit buffer offsets");
-    Conv64Args a;
-    a.p = *p; a.in = in; a.w = weight; a.bias = bias; a.res = nullptr; a.mask = nullptr; a.out = hidden_out;
-    a.M = (long long)p->n * p->ho * p->wo;
-    a.K = p->kh * p->kw * p->cin;
-    a.div_howo = fastdiv_make((unsigned)(p->ho * p->wo));
-    a.div_wo = fastdiv_make((unsigned)p->wo);
-    a.in_bytes = (unsigned)in_bytes; a.w_bytes = (unsigned)w_bytes;
-    a.stem = 0;
-    a.tap_minor = p->kh * p->kw > 1 ? tap_minor_default() : 0;
-    a.tail_w = w_tail; a.tail_b = b_tail; a.tail_deltas = deltas; a.tail_ctr = ctr;
-    a.w3 = nullptr; a.bias3 = nullptr; a.cout3 = 0; a.w3_bytes = a.out_bytes = 0;
-#ifdef C64_STAMPS
-    a.dbg = nullptr; a.p8 = g_p8_stamps;
-#endif
-    hipStream_t st = (hipStream_t)stream;
-    return p->in_dtype == OSR_F16 ? cfrpn_fused_launch<f16_t>(a, st) : cfrpn_fused_launch<bf16_t>(a, st);
 }
 
 // ---- two convolutions of one input in one launch (include/osr.h: osr_conv2d_fwd_pair) ---------------------------------------------
@@ -1488,61 +1376,41 @@ extern "C" osr_status osr_cfrpn_head_fwd_ex(const osr_conv_params* p, const void
 // launch no longer leaves the chip half empty. Bit-identical to the two osr_conv2d_fwd launches on the 128 x 128 tile.
 extern "C" osr_status osr_conv2d_fwd_pair(const osr_conv_params* p, const void* in, const void* w_a, const float* bias_a, int32_t cout_a, int32_t relu_a,
                                           void* out_a, const void* w_b, const float* bias_b, int32_t cout_b, int32_t relu_b, void* out_b, void* stream) {
-    OSR_REQUIRE(p && in && w_a && bias_a && out_a && w_b && bias_b && out_b, OSR_ERR_INVALID_ARG, "osr_conv2d_fwd_pair: null pointer");
-    OSR_REQUIRE((p->in_dtype == OSR_F16 || p->in_dtype == OSR_BF16) && p->out_dtype == p->in_dtype, OSR_ERR_UNSUPPORTED, "osr_conv2d_fwd_pair: f16 / bf16 storage in and out");
-    OSR_REQUIRE(p->res_mode == 0 && p->pad_mode == 0 && !p->row_seg_counts, OSR_ERR_UNSUPPORTED, "osr_conv2d_fwd_pair: no residual / stem view / row segments");
+    const char* who = "osr_conv2d_fwd_pair";
+    OSR_REQUIRE(p && in && w_a && bias_a && out_a && w_b && bias_b && out_b, OSR_ERR_INVALID_ARG, "%s: null pointer", who);
+    OSR_REQUIRE((p->in_dtype == OSR_F16 || p->in_dtype == OSR_BF16) && p->out_dtype == p->in_dtype, OSR_ERR_UNSUPPORTED, "%s: f16 / bf16 storage in and out", who);
+    OSR_REQUIRE(p->res_mode == 0 && p->pad_mode == 0 && !p->row_seg_counts, OSR_ERR_UNSUPPORTED, "%s: no residual / stem view / row segments", who);
     OSR_REQUIRE(cout_a >= 128 && cout_b >= 128 && cout_a % 128 == 0 && cout_b % 128 == 0 && p->cin % 64 == 0, OSR_ERR_UNSUPPORTED,
-                "osr_conv2d_fwd_pair: both output widths multiples of 128, cin a multiple of 64");
-    OSR_REQUIRE(p->n >= 1 && p->hi >= 1 && p->wi >= 1 && p->kh >= 1 && p->kw >= 1 && p->kh * p->kw <= 31 && p->stride_h >= 1 && p->stride_w >= 1 && p->pad_h >= 0 && p->pad_w >= 0,
-                OSR_ERR_INVALID_ARG, "osr_conv2d_fwd_pair: bad geometry");
-    OSR_REQUIRE((p->hi + 2 * p->pad_h - p->kh) / p->stride_h + 1 == p->ho && (p->wi + 2 * p->pad_w - p->kw) / p->stride_w + 1 == p->wo, OSR_ERR_INVALID_ARG,
-                "osr_conv2d_fwd_pair: ho/wo inconsistent with hi/wi/kernel/stride/pad");
-    OSR_REQUIRE(p->in_stride_w % 8 == 0 && p->in_stride_h % 8 == 0 && p->in_stride_n % 8 == 0 && p->in_stride_n > 0, OSR_ERR_INVALID_ARG,
-                "osr_conv2d_fwd_pair: input strides must be multiples of 8 elements");
-    OSR_REQUIRE((((uintptr_t)in | (uintptr_t)w_a | (uintptr_t)w_b | (uintptr_t)bias_a | (uintptr_t)bias_b | (uintptr_t)out_a | (uintptr_t)out_b) & 15) == 0, OSR_ERR_INVALID_ARG,
-                "osr_conv2d_fwd_pair: pointers must be 16-byte aligned");
+                "%s: both output widths multiples of 128, cin a multiple of 64", who);
+    C64_CHECK(conv64_check_geometry(p, p->kh * p->kw <= 31, who));
+    C64_CHECK(conv64_check_in_strides(p, who));
+    C64_CHECK(conv64_check_aligned((uintptr_t)in | (uintptr_t)w_a | (uintptr_t)w_b | (uintptr_t)bias_a | (uintptr_t)bias_b | (uintptr_t)out_a | (uintptr_t)out_b, who));
     const long long M = (long long)p->n * p->ho * p->wo, K = (long long)p->kh * p->kw * p->cin, in_bytes = (long long)p->n * p->in_stride_n * 2;
     const long long wide = cout_a > cout_b ? cout_a : cout_b;
-    OSR_REQUIRE(M < (1ll << 31) - 1024 && in_bytes < (1ll << 31) - 4096 && wide * K * 2 < (1ll << 31) - 4096 && M * wide < (1ll << 31), OSR_ERR_UNSUPPORTED,
-                "osr_conv2d_fwd_pair: tensor too large for 32-bit offsets");
-    Conv64Args a;
-    a.p = *p; a.p.cout = cout_a + cout_b;
-    a.in = in; a.w = w_a; a.bias = bias_a; a.res = nullptr; a.mask = nullptr; a.out = out_a;
-    a.M = M; a.K = (int)K;
-    a.div_howo = fastdiv_make((unsigned)(p->ho * p->wo));
-    a.div_wo = fastdiv_make((unsigned)p->wo);
-    a.in_bytes = (unsigned)in_bytes; a.w_bytes = (unsigned)(cout_a * K * 2);
-    a.stem = 0; a.tap_minor = p->kh * p->kw > 1 ? tap_minor_default() : 0;
-    a.tail_w = a.tail_b = nullptr; a.tail_deltas = a.tail_ctr = nullptr; a.tail_lds_off = 0;
-    a.w3 = nullptr; a.bias3 = nullptr; a.cout3 = 0; a.w3_bytes = a.out_bytes = 0;
-#ifdef C64_STAMPS
-    a.dbg = g_c64_stamps; a.p8 = nullptr;
-#endif
-    const bool in_dense = p->in_stride_w == p->cin && p->in_stride_h == (long long)p->wi * p->cin && p->in_stride_n == (long long)p->hi * p->wi * p->cin;
-    a.pw_dense = 2 | ((p->kh == 1 && p->kw == 1 && p->stride_h == 1 && p->stride_w == 1 && p->pad_h == 0 && p->pad_w == 0 && in_dense) ? 1 : 0);  // both outputs are dense
+    OSR_REQUIRE(conv64_rows_fit(M) && conv64_bytes_fit(in_bytes) && conv64_bytes_fit(wide * K * 2) && M * wide < (1ll << 31), OSR_ERR_UNSUPPORTED,
+                "%s: tensor too large for 32-bit offsets", who);
+    Conv64Args a = conv64_args(p, in, w_a, bias_a, out_a, in_bytes, cout_a * K * 2);
+    a.p.cout = cout_a + cout_b;
+    a.pw_dense = 2 | (conv64_dense_in(*p) ? 1 : 0);  // both outputs are dense
+    conv64_stamps(a, true, false);
     a.ngroups = 2;
     const int couts[2] = {cout_a, cout_b}, relus[2] = {relu_a, relu_b};
     const void* ws[2] = {w_a, w_b}; const float* bs[2] = {bias_a, bias_b}; void* outs[2] = {out_a, out_b};
-    int tb = 0;
     for (int g = 0; g < 2; ++g) {
         Conv64Args::Group& G = a.cg[g];
         G.w = ws[g]; G.bias = bs[g]; G.out = outs[g]; G.cout = couts[g]; G.relu = relus[g] ? 1 : 0;
         G.out_stride_h = (long long)p->wo * couts[g]; G.out_stride_n = (long long)p->ho * G.out_stride_h;
         G.w_bytes = (unsigned)(couts[g] * K * 2);
-        G.tile_begin = tb;
-        tb += couts[g] / 128;
+        G.tile_begin = a.tiles_n;
+        a.tiles_n += couts[g] / 128;
     }
-    a.two_stage = 0;
     a.tiles_m = (int)((M + 127) / 128);
-    a.tiles_n = tb;
-    a.tile0 = 0; a.ntile = a.tiles_m * a.tiles_n; a.ksplit = 1; a.split_stride = 0;
+    a.ntile = a.tiles_m * a.tiles_n;
     hipStream_t st = (hipStream_t)stream;
     const size_t lds = conv64_lds_bytes(128, 128, 0, 4);
     if (p->in_dtype == OSR_F16) hipLaunchKernelGGL((conv_igemm64_kernel<f16_t, f16_t, 128, 128, 2, 2, 0, 0, 0>), dim3((unsigned)a.ntile), dim3(256), lds, st, a);
     else hipLaunchKernelGGL((conv_igemm64_kernel<bf16_t, bf16_t, 128, 128, 2, 2, 0, 0, 0>), dim3((unsigned)a.ntile), dim3(256), lds, st, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { osr_set_error("osr_conv2d_fwd_pair: launch failed: %s", hipGetErrorString(e)); return OSR_ERR_LAUNCH; }
-    return OSR_OK;
+    return conv64_check_launch(who);
 }
 
 // ---- multi-level launches (include/osr.h: osr_conv2d_fwd_levels, osr_cfrpn_head_fwd_levels) ------------------------------------
@@ -1565,7 +1433,7 @@ static osr_status conv64_fill_levels(Conv64Args& a, const osr_conv_params* p, in
         OSR_REQUIRE(head ? (v.deltas && v.ctr) : v.out != nullptr, OSR_ERR_INVALID_ARG, "%s: level %d: null output", who, l);
         OSR_REQUIRE((((uintptr_t)v.in | (uintptr_t)v.out | (uintptr_t)v.deltas) & 15) == 0, OSR_ERR_INVALID_ARG, "%s: level %d: pointers must be 16-byte aligned", who, l);
         const long long rows = (long long)v.n * v.hi * v.wi, in_bytes = rows * p->cin * 2;
-        OSR_REQUIRE(rows < (1ll << 31) - 1024 && in_bytes < (1ll << 31) - 4096, OSR_ERR_UNSUPPORTED, "%s: level %d too large for 32-bit buffer offsets", who, l);
+        OSR_REQUIRE(conv64_rows_fit(rows) && conv64_bytes_fit(in_bytes), OSR_ERR_UNSUPPORTED, "%s: level %d too large for 32-bit buffer offsets", who, l);
         Conv64Args::Level& L = a.lv[l];
         L.in = v.in; L.out = v.out; L.tail_deltas = v.deltas; L.tail_ctr = v.ctr;
         OSR_REQUIRE((v.weight || a.w) && (v.bias || a.bias), OSR_ERR_INVALID_ARG, "%s: level %d: no weight / bias (neither its own nor a shared one)", who, l);
@@ -1584,29 +1452,26 @@ static osr_status conv64_fill_levels(Conv64Args& a, const osr_conv_params* p, in
     return OSR_OK;
 }
 
+// the single-problem fields of a multi-level launch: shared weights / bias (nullable where every level brings its own), dense channel strides
+static Conv64Args conv64_levels_args(const osr_conv_params* p, const void* weight, const float* bias) {
+    Conv64Args a = conv64_args(p, nullptr, weight, bias, nullptr, 0, (long long)p->cout * p->kh * p->kw * p->cin * 2);
+    a.p.in_stride_w = p->cin; a.p.out_stride_w = p->cout;
+    a.M = 0;  // (n, ho, wo of p are not part of the levels ABI)
+    conv64_stamps(a, false, false);
+    return a;
+}
+
 extern "C" osr_status osr_conv2d_fwd_levels(const osr_conv_params* p, int32_t nlevels, const osr_conv_level* levels, const void* weight, const float* bias,
                                             void* stream) {
-    OSR_REQUIRE(p, OSR_ERR_INVALID_ARG, "osr_conv2d_fwd_levels: null pointer");
-    OSR_REQUIRE((p->in_dtype == OSR_F16 || p->in_dtype == OSR_BF16) && p->out_dtype == p->in_dtype, OSR_ERR_UNSUPPORTED, "osr_conv2d_fwd_levels: f16 / bf16 storage in and out");
-    OSR_REQUIRE((((uintptr_t)weight | (uintptr_t)bias) & 15) == 0, OSR_ERR_INVALID_ARG, "osr_conv2d_fwd_levels: pointers must be 16-byte aligned");
-    Conv64Args a;
-    a.p = *p; a.p.in_stride_w = p->cin; a.p.out_stride_w = p->cout;
-    a.in = nullptr; a.w = weight; a.bias = bias; a.res = nullptr; a.mask = nullptr; a.out = nullptr;
-    a.M = 0; a.K = p->kh * p->kw * p->cin;
-    a.div_howo = a.div_wo = fastdiv_make(1u);
-    a.in_bytes = 0; a.w_bytes = (unsigned)((long long)p->cout * a.K * 2);
-    OSR_REQUIRE((long long)p->cout * a.K * 2 < (1ll << 31) - 4096, OSR_ERR_UNSUPPORTED, "osr_conv2d_fwd_levels: weights too large for 32-bit buffer offsets");
-    a.stem = 0; a.tap_minor = p->kh * p->kw > 1 ? tap_minor_default() : 0;
-    a.tail_w = a.tail_b = nullptr; a.tail_deltas = a.tail_ctr = nullptr;
-    a.w3 = nullptr; a.bias3 = nullptr; a.cout3 = 0; a.w3_bytes = a.out_bytes = 0;
-    a.tail_lds_off = 0;
-#ifdef C64_STAMPS
-    a.dbg = nullptr; a.p8 = nullptr;
-#endif
-    const osr_status s = conv64_fill_levels(a, p, nlevels, levels, false, "osr_conv2d_fwd_levels");
-    if (s != OSR_OK) return s;
+    const char* who = "osr_conv2d_fwd_levels";
+    OSR_REQUIRE(p, OSR_ERR_INVALID_ARG, "%s: null pointer", who);
+    OSR_REQUIRE((p->in_dtype == OSR_F16 || p->in_dtype == OSR_BF16) && p->out_dtype == p->in_dtype, OSR_ERR_UNSUPPORTED, "%s: f16 / bf16 storage in and out", who);
+    C64_CHECK(conv64_check_aligned((uintptr_t)weight | (uintptr_t)bias, who));
+    OSR_REQUIRE(conv64_bytes_fit((long long)p->cout * (p->kh * p->kw * p->cin) * 2), OSR_ERR_UNSUPPORTED, "%s: weights too large for 32-bit buffer offsets", who);
+    Conv64Args a = conv64_levels_args(p, weight, bias);
+    C64_CHECK(conv64_fill_levels(a, p, nlevels, levels, false, who));
     a.tiles_n = p->cout / 256;
-    a.tile0 = 0; a.ntile = a.tiles_m * a.tiles_n; a.ksplit = 1; a.split_stride = 0;
+    a.ntile = a.tiles_m * a.tiles_n;
     a.pw_dense = 2;  // every level's output is a dense (rows, cout) tensor
     for (int l = 0; l < nlevels; ++l)
         if (a.lv[l].M * p->cout >= (1ll << 31)) a.pw_dense = 0;
@@ -1620,49 +1485,24 @@ extern "C" osr_status osr_conv2d_fwd_levels(const osr_conv_params* p, int32_t nl
     });
     if (p->in_dtype == OSR_F16) hipLaunchKernelGGL((conv_igemm64_kernel<f16_t, f16_t, 256, 256, 2, 4, 0, 2, 0>), dim3((unsigned)a.ntile), dim3(512), lds, st, a);
     else hipLaunchKernelGGL((conv_igemm64_kernel<bf16_t, bf16_t, 256, 256, 2, 4, 0, 2, 0>), dim3((unsigned)a.ntile), dim3(512), lds, st, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { osr_set_error("osr_conv2d_fwd_levels: launch failed: %s", hipGetErrorString(e)); return OSR_ERR_LAUNCH; }
-    return OSR_OK;
-}
-
-template <class TI>
-static osr_status cfrpn_levels_launch(Conv64Args& a, hipStream_t st) {
-    a.two_stage = 1;
-    a.tiles_n = 1; a.tile0 = 0; a.ntile = a.tiles_m; a.ksplit = 1; a.split_stride = 0;
-    const size_t t_bytes = (size_t)256 * (256 + 8) * 2, stages = (size_t)2 * (256 + 256) * 128;
-    a.tail_lds_off = (int)(t_bytes > stages ? t_bytes : stages);
-    const size_t lds = (size_t)a.tail_lds_off + C64_TAIL_LDS(256) + 32;
-    static osr_dev_mask attr{0};
-    osr_once_per_device(attr, [] { allow_big_lds(conv_igemm64_kernel<TI, TI, 256, 256, 2, 4, 1, 2>); });
-    hipLaunchKernelGGL((conv_igemm64_kernel<TI, TI, 256, 256, 2, 4, 1, 2>), dim3((unsigned)a.tiles_m), dim3(512), lds, st, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { osr_set_error("osr_cfrpn_head_fwd_levels: launch failed: %s", hipGetErrorString(e)); return OSR_ERR_LAUNCH; }
-    return OSR_OK;
+    return conv64_check_launch(who);
 }
 
 extern "C" osr_status osr_cfrpn_head_fwd_levels(const osr_conv_params* p, int32_t nlevels, const osr_conv_level* levels, const void* weight, const float* bias,
                                                 const float* w_tail, const float* b_tail, void* stream) {
-    OSR_REQUIRE(p && weight && bias && w_tail && b_tail, OSR_ERR_INVALID_ARG, "osr_cfrpn_head_fwd_levels: null pointer");
-    OSR_REQUIRE(p->in_dtype == OSR_F16 || p->in_dtype == OSR_BF16, OSR_ERR_UNSUPPORTED, "osr_cfrpn_head_fwd_levels: in_dtype must be f16/bf16");
-    OSR_REQUIRE(p->cout == 256, OSR_ERR_UNSUPPORTED, "osr_cfrpn_head_fwd_levels: cout must be 256");
-    OSR_REQUIRE((((uintptr_t)weight | (uintptr_t)bias) & 15) == 0, OSR_ERR_INVALID_ARG, "osr_cfrpn_head_fwd_levels: pointers must be 16-byte aligned");
-    Conv64Args a;
-    a.p = *p; a.p.in_stride_w = p->cin; a.p.out_stride_w = p->cout;
-    a.in = nullptr; a.w = weight; a.bias = bias; a.res = nullptr; a.mask = nullptr; a.out = nullptr;
-    a.M = 0; a.K = p->kh * p->kw * p->cin;
-    a.div_howo = a.div_wo = fastdiv_make(1u);
-    a.in_bytes = 0; a.w_bytes = (unsigned)((long long)p->cout * a.K * 2);
-    a.stem = 0; a.tap_minor = p->kh * p->kw > 1 ? tap_minor_default() : 0;
-    a.tail_w = w_tail; a.tail_b = b_tail; a.tail_deltas = a.tail_ctr = nullptr;
-    a.w3 = nullptr; a.bias3 = nullptr; a.cout3 = 0; a.w3_bytes = a.out_bytes = 0;
-#ifdef C64_STAMPS
-    a.dbg = nullptr; a.p8 = nullptr;
-#endif
-    const osr_status s = conv64_fill_levels(a, p, nlevels, levels, true, "osr_cfrpn_head_fwd_levels");
-    if (s != OSR_OK) return s;
-    OSR_REQUIRE(a.K / 64 >= 8, OSR_ERR_UNSUPPORTED, "osr_cfrpn_head_fwd_levels: at least eight K slices");
+    const char* who = "osr_cfrpn_head_fwd_levels";
+    OSR_REQUIRE(p && weight && bias && w_tail && b_tail, OSR_ERR_INVALID_ARG, "%s: null pointer", who);
+    C64_CHECK(conv64_check_storage(p, false, who));
+    OSR_REQUIRE(p->cout == 256, OSR_ERR_UNSUPPORTED, "%s: cout must be 256", who);
+    C64_CHECK(conv64_check_aligned((uintptr_t)weight | (uintptr_t)bias, who));
+    Conv64Args a = conv64_levels_args(p, weight, bias);
+    a.tail_w = w_tail; a.tail_b = b_tail;
+    C64_CHECK(conv64_fill_levels(a, p, nlevels, levels, true, who));
+    OSR_REQUIRE(a.K / 64 >= 8, OSR_ERR_UNSUPPORTED, "%s: at least eight K slices", who);
     hipStream_t st = (hipStream_t)stream;
-    return p->in_dtype == OSR_F16 ? cfrpn_levels_launch<f16_t>(a, st) : cfrpn_levels_launch<bf16_t>(a, st);
+    if (p->in_dtype == OSR_F16) cfrpn_launch_tile<f16_t, 256, 4, 2>(a, a.tiles_m, st);
+    else cfrpn_launch_tile<bf16_t, 256, 4, 2>(a, a.tiles_m, st);
+    return conv64_check_launch(who);
 }
 
 // A bottleneck's conv2 -> conv3 in one launch (include/osr.h: osr_conv2d_chain_fwd):
@@ -1673,62 +1513,39 @@ static osr_status conv_chain_launch(Conv64Args& a, hipStream_t st) {
     constexpr int WM = BM / 64;
     a.two_stage = 1;
     a.tiles_n = 1;
-    a.tiles_m = (int)((a.M + BM - 1) / BM);
-    a.tile0 = 0; a.ntile = a.tiles_m; a.ksplit = 1; a.split_stride = 0;
+    a.tiles_m = a.ntile = (int)((a.M + BM - 1) / BM);
     // parked tile + three weight stages; the K loop's two staging buffers alias the front
     const size_t park = (size_t)2 * BM * 128 + 3 * 16384, stg = (size_t)2 * (BM + 128) * 128, lds = park > stg ? park : stg;
     static osr_dev_mask attr{0};
     osr_once_per_device(attr, [] { allow_big_lds(conv_igemm64_kernel<TI, TI, BM, 128, WM, 2, 2, 1>); });
     hipLaunchKernelGGL((conv_igemm64_kernel<TI, TI, BM, 128, WM, 2, 2, 1>), dim3((unsigned)a.tiles_m), dim3(WM * 2 * 64), lds, st, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { osr_set_error("osr_conv2d_chain_fwd: launch failed: %s", hipGetErrorString(e)); return OSR_ERR_LAUNCH; }
-    return OSR_OK;
-}
-
-extern "C" osr_status osr_conv2d_chain_fwd_ex(const osr_conv_params* p, const void* in, const void* weight, const float* bias, const void* w3,
-                                              const float* bias3, int32_t cout3, const void* residual, void* out, void* mid_out, void* stream);
-extern "C" osr_status osr_conv2d_chain_fwd(const osr_conv_params* p, const void* in, const void* weight, const float* bias, const void* w3,
-                                           const float* bias3, int32_t cout3, const void* residual, void* out, void* stream) {
-    return osr_conv2d_chain_fwd_ex(p, in, weight, bias, w3, bias3, cout3, residual, out, nullptr, stream);
+    return conv64_check_launch("osr_conv2d_chain_fwd");
 }
 
 extern "C" osr_status osr_conv2d_chain_fwd_ex(const osr_conv_params* p, const void* in, const void* weight, const float* bias, const void* w3,
                                               const float* bias3, int32_t cout3, const void* residual, void* out, void* mid_out, void* stream) {
-    OSR_REQUIRE(p && in && weight && bias && w3 && bias3 && residual && out, OSR_ERR_INVALID_ARG, "osr_conv2d_chain_fwd: null pointer");
-    OSR_REQUIRE((((uintptr_t)mid_out) & 15) == 0, OSR_ERR_INVALID_ARG, "osr_conv2d_chain_fwd: mid_out must be 16-byte aligned");
-    OSR_REQUIRE(p->in_dtype == OSR_F16 || p->in_dtype == OSR_BF16, OSR_ERR_UNSUPPORTED, "osr_conv2d_chain_fwd: in_dtype must be f16/bf16");
-    OSR_REQUIRE(p->out_dtype == p->in_dtype, OSR_ERR_UNSUPPORTED, "osr_conv2d_chain_fwd: out_dtype must equal in_dtype");
+    const char* who = "osr_conv2d_chain_fwd";
+    OSR_REQUIRE(p && in && weight && bias && w3 && bias3 && residual && out, OSR_ERR_INVALID_ARG, "%s: null pointer", who);
+    OSR_REQUIRE((((uintptr_t)mid_out) & 15) == 0, OSR_ERR_INVALID_ARG, "%s: mid_out must be 16-byte aligned", who);
+    C64_CHECK(conv64_check_storage(p, true, who));
     OSR_REQUIRE(p->cout == 128 && cout3 == 512 && p->cin % 64 == 0 && p->pad_mode == 0, OSR_ERR_UNSUPPORTED,
-                "osr_conv2d_chain_fwd: needs cout == 128, cout3 == 512, cin %% 64 == 0 (got %d, %d, %d)", p->cout, cout3, p->cin);
-    OSR_REQUIRE(p->n >= 1 && p->hi >= 1 && p->wi >= 1 && p->kh >= 1 && p->kw >= 1 && p->kh <= 16 && p->kw <= 16 && p->stride_h >= 1 && p->stride_w >= 1 &&
-                    p->pad_h >= 0 && p->pad_w >= 0, OSR_ERR_INVALID_ARG, "osr_conv2d_chain_fwd: bad geometry");
-    OSR_REQUIRE((p->hi + 2 * p->pad_h - p->kh) / p->stride_h + 1 == p->ho && (p->wi + 2 * p->pad_w - p->kw) / p->stride_w + 1 == p->wo,
-                OSR_ERR_INVALID_ARG, "osr_conv2d_chain_fwd: ho/wo inconsistent with hi/wi/kernel/stride/pad");
-    OSR_REQUIRE(p->in_stride_w % 8 == 0 && p->in_stride_h % 8 == 0 && p->in_stride_n % 8 == 0 && p->in_stride_n > 0, OSR_ERR_INVALID_ARG,
-                "osr_conv2d_chain_fwd: input strides must be multiples of 8 elements");
-    OSR_REQUIRE((((uintptr_t)in | (uintptr_t)weight | (uintptr_t)bias | (uintptr_t)w3 | (uintptr_t)bias3 | (uintptr_t)residual | (uintptr_t)out) & 15) == 0,
-                OSR_ERR_INVALID_ARG, "osr_conv2d_chain_fwd: pointers must be 16-byte aligned");
+                "%s: needs cout == 128, cout3 == 512, cin %% 64 == 0 (got %d, %d, %d)", who, p->cout, cout3, p->cin);
+    C64_CHECK(conv64_check_geometry(p, p->kh <= 16 && p->kw <= 16, who));
+    C64_CHECK(conv64_check_in_strides(p, who));
+    C64_CHECK(conv64_check_aligned((uintptr_t)in | (uintptr_t)weight | (uintptr_t)bias | (uintptr_t)w3 | (uintptr_t)bias3 | (uintptr_t)residual | (uintptr_t)out, who));
     const long long in_bytes = (long long)p->n * p->in_stride_n * 2, w_bytes = (long long)p->cout * p->kh * p->kw * p->cin * 2;
-    const long long M = (long long)p->n * p->ho * p->wo, out_bytes = M * cout3 * 2;
-    OSR_REQUIRE(osr_conv64_eligible(p, in_bytes, w_bytes) && out_bytes < (1ll << 31) - 4096, OSR_ERR_UNSUPPORTED,
-                "osr_conv2d_chain_fwd: tensor too large for 32-bit buffer offsets");
-    Conv64Args a;
-    a.p = *p; a.in = in; a.w = weight; a.bias = bias; a.res = residual; a.mask = nullptr; a.out = out;
+    const long long out_bytes = (long long)p->n * p->ho * p->wo * cout3 * 2;
+    C64_REQUIRE_FITS(osr_conv64_eligible(p, in_bytes, w_bytes) && conv64_bytes_fit(out_bytes), who);
+    Conv64Args a = conv64_args(p, in, weight, bias, out, in_bytes, w_bytes);
     a.p.row_seg_counts = nullptr;
-    a.M = M;
-    a.K = p->kh * p->kw * p->cin;
-    a.div_howo = fastdiv_make((unsigned)(p->ho * p->wo));
-    a.div_wo = fastdiv_make((unsigned)p->wo);
-    a.in_bytes = (unsigned)in_bytes; a.w_bytes = (unsigned)w_bytes;
-    a.stem = 0;
-    a.tap_minor = p->kh * p->kw > 1 ? tap_minor_default() : 0;
-    a.tail_w = a.tail_b = nullptr; a.tail_deltas = a.tail_ctr = nullptr; a.tail_lds_off = 0;
+    a.res = residual;
     a.w3 = w3; a.bias3 = bias3; a.cout3 = cout3;
     a.w3_bytes = (unsigned)((long long)cout3 * p->cout * 2); a.out_bytes = (unsigned)out_bytes;
     a.mid_out = mid_out;
-#ifdef C64_STAMPS
-    a.dbg = g_c64_stamps; a.p8 = g_p8_stamps;
-#endif
     hipStream_t st = (hipStream_t)stream;
     return p->in_dtype == OSR_F16 ? conv_chain_launch<f16_t, 128>(a, st) : conv_chain_launch<bf16_t, 128>(a, st);
+}
+extern "C" osr_status osr_conv2d_chain_fwd(const osr_conv_params* p, const void* in, const void* weight, const float* bias, const void* w3,
+                                           const float* bias3, int32_t cout3, const void* residual, void* out, void* stream) {
+    return osr_conv2d_chain_fwd_ex(p, in, weight, bias, w3, bias3, cout3, residual, out, nullptr, stream);
 }

@@ -88,6 +88,36 @@ def _new_conv_params() -> "ConvParams":
     return p
 
 
+def _conv_params(n, hi, wi, cin, ho, wo, cout, kh, kw, stride, pad, dt_in, dt_out, relu=False, res_mode=0) -> ConvParams:
+    """A convolution over dense NHWC tensors."""
+    p = _new_conv_params()
+    p.n, p.hi, p.wi, p.cin, p.ho, p.wo, p.cout = n, hi, wi, cin, ho, wo, cout
+    p.kh, p.kw, p.stride_h, p.stride_w, p.pad_h, p.pad_w = kh, kw, stride, stride, pad, pad
+    p.in_stride_n, p.in_stride_h, p.in_stride_w = hi * wi * cin, wi * cin, cin
+    p.out_stride_n, p.out_stride_h, p.out_stride_w = ho * wo * cout, wo * cout, cout
+    p.relu, p.res_mode, p.pad_mode = int(relu), int(res_mode), 0
+    p.in_dtype, p.out_dtype = _DT[dt_in], _DT[dt_out]
+    return p
+
+
+def _stem_params(n, hd, wd, ho, wo, cout, kh, relu, dt) -> ConvParams:
+    """The stem view (pad_mode 1): a (kh, 1, 32) stride-2 convolution over the pre-padded NHWC4 image, whose 'pixels' are 4-element groups."""
+    p = _conv_params(n, hd, wd, 32, ho, wo, cout, kh, 1, 2, 0, dt, dt, relu)
+    p.in_stride_n, p.in_stride_h, p.in_stride_w = hd * wd * 4, wd * 4, 4
+    p.pad_mode = 1
+    return p
+
+
+def _set_residual(p: ConvParams, residual: torch.Tensor, dtype, name: str = "residual") -> None:
+    """Shape check and strides of p's residual: the output's shape (res_mode 1, 3) or its 2x-coarser parent (res_mode 2, FPN top-down)."""
+    _need(residual, dtype, name)
+    rn, rh, rw, rc = residual.shape
+    exp = (p.n, p.ho, p.wo, p.cout) if p.res_mode in (1, 3) else (p.n, (p.ho + 1) // 2, (p.wo + 1) // 2, p.cout)
+    if (rn, rh, rw, rc) != exp:
+        raise OsrError(f"residual shape {tuple(residual.shape)} != expected {exp} for res_mode {p.res_mode}")
+    p.res_stride_n, p.res_stride_h, p.res_stride_w = rh * rw * rc, rw * rc, rc
+
+
 def conv2d(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, stride: int = 1, pad: int = 0, relu: bool = False,
            residual: Optional[torch.Tensor] = None, res_mode: int = 0, out_dtype: Optional[torch.dtype] = None,
            out: Optional[torch.Tensor] = None, post_mask: Optional[torch.Tensor] = None,
@@ -113,13 +143,7 @@ def conv2d(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, stride: in
         assert out.numel() == n * ho * wo * cout
     if FLOP_COUNT is not None:
         FLOP_COUNT["conv"] += 2.0 * n * ho * wo * cout * kh * kw * cin
-    p = _new_conv_params()
-    p.n, p.hi, p.wi, p.cin, p.ho, p.wo, p.cout = n, hi, wi, cin, ho, wo, cout
-    p.kh, p.kw, p.stride_h, p.stride_w, p.pad_h, p.pad_w = kh, kw, stride, stride, pad, pad
-    p.in_stride_n, p.in_stride_h, p.in_stride_w = hi * wi * cin, wi * cin, cin
-    p.out_stride_n, p.out_stride_h, p.out_stride_w = ho * wo * cout, wo * cout, cout
-    p.relu, p.res_mode, p.pad_mode = int(relu), int(res_mode), 0
-    p.in_dtype, p.out_dtype = _DT[x.dtype], _DT[out_dtype]
+    p = _conv_params(n, hi, wi, cin, ho, wo, cout, kh, kw, stride, pad, x.dtype, out_dtype, relu, res_mode)
     if row_seg is not None:
         counts, seg_rows = row_seg
         _need(counts, torch.int32, "row_seg counts")
@@ -127,12 +151,7 @@ def conv2d(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, stride: in
             raise OsrError("row_seg does not cover the output rows")
         p.row_seg_counts, p.row_seg_rows = counts.data_ptr(), int(seg_rows)
     if res_mode:
-        _need(residual, x.dtype, "residual")
-        rn, rh, rw, rc = residual.shape
-        exp = (n, ho, wo, cout) if res_mode in (1, 3) else (n, (ho + 1) // 2, (wo + 1) // 2, cout)
-        if (rn, rh, rw, rc) != exp:
-            raise OsrError(f"residual shape {tuple(residual.shape)} != expected {exp} for res_mode {res_mode}")
-        p.res_stride_n, p.res_stride_h, p.res_stride_w = rh * rw * rc, rw * rc, rc
+        _set_residual(p, residual, x.dtype)
     if post_mask is not None:
         _need(post_mask, x.dtype, "post_mask")
         if tuple(post_mask.shape) != (n, ho, wo, cout):
@@ -170,13 +189,7 @@ def stem_conv(xpad: torch.Tensor, w_view: torch.Tensor, bias: torch.Tensor, hp: 
     out = torch.empty((n, ho, wo, cout), dtype=xpad.dtype, device=xpad.device)
     if FLOP_COUNT is not None:
         FLOP_COUNT["conv"] += 2.0 * n * ho * wo * cout * 147  # 7*7*3 real taps
-    p = _new_conv_params()
-    p.n, p.hi, p.wi, p.cin, p.ho, p.wo, p.cout = n, hd, wd, 32, ho, wo, cout
-    p.kh, p.kw, p.stride_h, p.stride_w, p.pad_h, p.pad_w = kh, 1, 2, 2, 0, 0
-    p.in_stride_n, p.in_stride_h, p.in_stride_w = hd * wd * 4, wd * 4, 4
-    p.out_stride_n, p.out_stride_h, p.out_stride_w = ho * wo * cout, wo * cout, cout
-    p.relu, p.res_mode, p.pad_mode = int(relu), 0, 1
-    p.in_dtype = p.out_dtype = _DT[xpad.dtype]
+    p = _stem_params(n, hd, wd, ho, wo, cout, kh, relu, xpad.dtype)
     check(lib.osr_conv2d_fwd(C.byref(p), _p(xpad), _p(w_view), _p(bias), None, _p(out), _stream()), "osr_conv2d_fwd(stem)")
     return out
 
@@ -398,20 +411,9 @@ def conv2d_split(x: torch.Tensor, w_split, bias: torch.Tensor, stride: int = 1, 
         _need(out, torch.float32, "out")
         if tuple(out.shape) not in ((n, ho, wo, cout), (n * ho * wo, cout)):
             raise OsrError(f"conv2d_split: out {tuple(out.shape)} for a result of {(n, ho, wo, cout)} (or its {(n * ho * wo, cout)} rows)")
-    p = _new_conv_params()
-    p.n, p.hi, p.wi, p.cin, p.ho, p.wo, p.cout = n, hi_, wi, cin, ho, wo, cout
-    p.kh, p.kw, p.stride_h, p.stride_w, p.pad_h, p.pad_w = kh, kw, stride, stride, pad, pad
-    p.in_stride_n, p.in_stride_h, p.in_stride_w = hi_ * wi * cin, wi * cin, cin
-    p.out_stride_n, p.out_stride_h, p.out_stride_w = ho * wo * cout, wo * cout, cout
-    p.relu, p.res_mode, p.pad_mode = int(relu), int(res_mode), 0
-    p.in_dtype = p.out_dtype = _lib.OSR_F32
+    p = _conv_params(n, hi_, wi, cin, ho, wo, cout, kh, kw, stride, pad, torch.float32, torch.float32, relu, res_mode)
     if res_mode:
-        _need(residual, torch.float32, "residual")
-        rn, rh, rw, rc = residual.shape
-        exp = (n, ho, wo, cout) if res_mode in (1, 3) else (n, (ho + 1) // 2, (wo + 1) // 2, cout)
-        if (rn, rh, rw, rc) != exp:
-            raise OsrError(f"residual shape {tuple(residual.shape)} != expected {exp} for res_mode {res_mode}")
-        p.res_stride_n, p.res_stride_h, p.res_stride_w = rh * rw * rc, rw * rc, rc
+        _set_residual(p, residual, torch.float32)
     check(lib.osr_conv2d_split_fwd(C.byref(p), _p(x), _p(hi), _p(lo), _p(bias), _p(residual) if res_mode else None, _p(out), _stream()),
           "osr_conv2d_split_fwd")
     if CONV_SPLIT_COUNT is not None:
@@ -432,13 +434,7 @@ def stem_conv_split(xpad: torch.Tensor, w_split, bias: torch.Tensor, hp: int, wp
     assert tuple(hi.shape[1:]) == (8, 1, 32)
     ho, wo = hp // 2, wp // 2
     out = torch.empty((n, ho, wo, cout), dtype=torch.float32, device=xpad.device)
-    p = _new_conv_params()
-    p.n, p.hi, p.wi, p.cin, p.ho, p.wo, p.cout = n, hd, wd, 32, ho, wo, cout
-    p.kh, p.kw, p.stride_h, p.stride_w, p.pad_h, p.pad_w = 8, 1, 2, 2, 0, 0
-    p.in_stride_n, p.in_stride_h, p.in_stride_w = hd * wd * 4, wd * 4, 4
-    p.out_stride_n, p.out_stride_h, p.out_stride_w = ho * wo * cout, wo * cout, cout
-    p.relu, p.res_mode, p.pad_mode = int(relu), 0, 1
-    p.in_dtype = p.out_dtype = _lib.OSR_F32
+    p = _stem_params(n, hd, wd, ho, wo, cout, 8, relu, torch.float32)
     check(lib.osr_conv2d_split_fwd(C.byref(p), _p(xpad), _p(hi), _p(lo), _p(bias), None, _p(out), _stream()), "osr_conv2d_split_fwd(stem)")
     if CONV_SPLIT_COUNT is not None:
         CONV_SPLIT_COUNT["launches"] += 1
@@ -467,13 +463,7 @@ def conv2d_chain(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, w3: 
     wo = (wi + 2 * pad - kw) // stride + 1
     if tuple(residual.shape) != (n, ho, wo, cout3):
         raise OsrError(f"conv2d_chain: residual shape {tuple(residual.shape)} != {(n, ho, wo, cout3)}")
-    p = _new_conv_params()
-    p.n, p.hi, p.wi, p.cin, p.ho, p.wo, p.cout = n, hi, wi, cin, ho, wo, cmid
-    p.kh, p.kw, p.stride_h, p.stride_w, p.pad_h, p.pad_w = kh, kw, stride, stride, pad, pad
-    p.in_stride_n, p.in_stride_h, p.in_stride_w = hi * wi * cin, wi * cin, cin
-    p.out_stride_n, p.out_stride_h, p.out_stride_w = ho * wo * cmid, wo * cmid, cmid
-    p.relu, p.res_mode, p.pad_mode = 1, 0, 0
-    p.in_dtype = p.out_dtype = _DT[x.dtype]
+    p = _conv_params(n, hi, wi, cin, ho, wo, cmid, kh, kw, stride, pad, x.dtype, x.dtype, relu=True)
     out = torch.empty((n, ho, wo, cout3), dtype=x.dtype, device=x.device)
     mid = torch.empty((n, ho, wo, cmid), dtype=x.dtype, device=x.device) if keep_mid else None
     st = lib.osr_conv2d_chain_fwd_ex(C.byref(p), _p(x), _p(weight), _p(bias), _p(w3), _p(b3), cout3, _p(residual), _p(out), _p(mid), _stream())
@@ -689,12 +679,7 @@ def cfrpn_head_fused(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, 
     ctr = ctr_out if ctr_out is not None else torch.empty((rows,), dtype=torch.float32, device=x.device)
     _need(deltas, torch.float32, "deltas"); _need(ctr, torch.float32, "ctr")
     assert deltas.numel() == rows * 4 and ctr.numel() == rows
-    p = _new_conv_params()
-    p.n, p.hi, p.wi, p.cin, p.ho, p.wo, p.cout = n, hi, wi, cin, hi, wi, cout
-    p.kh, p.kw, p.stride_h, p.stride_w, p.pad_h, p.pad_w = kh, kw, 1, 1, pad, pad
-    p.in_stride_n, p.in_stride_h, p.in_stride_w = hi * wi * cin, wi * cin, cin
-    p.relu, p.res_mode, p.pad_mode = 1, 0, 0
-    p.in_dtype = p.out_dtype = _DT[x.dtype]
+    p = _conv_params(n, hi, wi, cin, hi, wi, cout, kh, kw, 1, pad, x.dtype, x.dtype, relu=True)
     if hidden_out is not None:
         _need(hidden_out, x.dtype, "hidden_out")
         assert hidden_out.numel() == rows * 256
@@ -1362,17 +1347,6 @@ def softmax_ce_loss_fwd(logits, gt_classes, num_classes: int, loss_weight: float
 # ----------------------------------------------------------------------------------------------------------
 # training step, backward half: dense layers
 # ----------------------------------------------------------------------------------------------------------
-def _conv_params(n, hi, wi, cin, ho, wo, cout, kh, kw, stride, pad, dt_in, dt_out) -> ConvParams:
-    p = _new_conv_params()
-    p.n, p.hi, p.wi, p.cin, p.ho, p.wo, p.cout = n, hi, wi, cin, ho, wo, cout
-    p.kh, p.kw, p.stride_h, p.stride_w, p.pad_h, p.pad_w = kh, kw, stride, stride, pad, pad
-    p.in_stride_n, p.in_stride_h, p.in_stride_w = hi * wi * cin, wi * cin, cin
-    p.out_stride_n, p.out_stride_h, p.out_stride_w = ho * wo * cout, wo * cout, cout
-    p.relu, p.res_mode, p.pad_mode = 0, 0, 0
-    p.in_dtype, p.out_dtype = _DT[dt_in], _DT[dt_out]
-    return p
-
-
 def conv2d_dgrad(dy: torch.Tensor, w_dgrad: torch.Tensor, x_hw: Tuple[int, int], stride: int = 1, pad: int = 0,
                  mask: Optional[torch.Tensor] = None, add: Optional[torch.Tensor] = None, out_dtype: Optional[torch.dtype] = None,
                  post_mask: Optional[torch.Tensor] = None, strided_only: bool = False) -> torch.Tensor:
