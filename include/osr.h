@@ -428,7 +428,8 @@ typedef struct osr_pyramid {
 } osr_pyramid;
 
 /* pooled: 1 .. OSR_ROI_MAX_POOLED_FWD for the four forward entry points (1..7: the box pooler's kernels; 8..14, the mask head's 14 x 14
- * pooler: a per-sample kernel of its own, same options, same order independence); the backward entry points take 1..7. */
+ * pooler: a per-sample kernel of its own, same options, same order independence) and for the scatter backward (osr_roi_align_bwd /
+ * _opt: 8..14 likewise through a per-sample kernel); the pixel-centric backward (osr_roi_align_bwd_dense / _opt) takes 1..7. */
 #define OSR_ROI_MAX_POOLED_FWD 14
 osr_status osr_roi_align_fwd(const osr_pyramid* feats, int32_t feat_dtype, int32_t n, const float* boxes,
                              const int32_t* batch_idx, int64_t m, int32_t pooled, int32_t canonical_level,
@@ -598,11 +599,68 @@ osr_status osr_mask_upsample_predict(const void* x, int32_t dtype, int64_t r, in
                                      const void* w_packed, const float* bias, const float* pred_w, const float* pred_b,
                                      int32_t num_rows, const int64_t* classes, const int32_t* rows_valid, int32_t seg_rows,
                                      float* probs, void* stream);
+/* The same launch with a second output, logits (r, 2s, 2s) fp32: the class row's logit before the sigmoid (zeros where probs are
+ * zeros) -- what the training loss reads. Either of probs / logits may be NULL, not both; probs are bit-identical to the call above. */
+osr_status osr_mask_upsample_predict_ex(const void* x, int32_t dtype, int64_t r, int32_t s, int32_t cin, int32_t cmid,
+                                        const void* w_packed, const float* bias, const float* pred_w, const float* pred_b,
+                                        int32_t num_rows, const int64_t* classes, const int32_t* rows_valid, int32_t seg_rows,
+                                        float* probs, float* logits, void* stream);
 /* [d2] paste_masks_in_image (_do_paste_mask, skip_empty=False) for ONE image: probs (r, m, m) fp32, boxes (r, 4) at the output
  * resolution -> out (r, out_h, out_w) uint8, 1 where the bilinear sample (zeros outside the map) of mask i at
  * u = (x + 0.5 - x0) / (x1 - x0) * m - 0.5, v likewise, is >= threshold, else 0. Every byte of out is written. r <= 65535. */
 osr_status osr_paste_masks(const float* probs, const float* boxes, int64_t r, int32_t m, int32_t out_h, int32_t out_w,
                            float threshold, uint8_t* out, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * Mask branch, training ([d2] mask_rcnn_loss; csrc/osr_mask_train.hip). The mask rows are the foreground prefix of each image's
+ * sampled proposals: n segments of seg_rows rows of which the first rows_valid[image] exist (osr_roi_match_and_sample_ex writes an
+ * image's foreground rows first; rows_valid = its foreground count, seg_rows = int(batch_size * positive_fraction)).
+ *
+ * osr_mask_targets ([d2] BitMasks.crop_and_resize): gt_masks (n, gmax, hm, wm) uint8 planes (non-zero = inside), padded with zeros
+ * to the batch's image size; image_hw (n, 2) int32 {h, w} of each image (NULL: every image is hm x wm) -- the validity and clamp
+ * rules of the samples are those of the image's own bitmask. boxes (n * seg_rows, 4), gt_idx (n * seg_rows) int32.
+ * targets[r] (m_side, m_side) uint8 = roi_align(plane[image][gt_idx[r]] as float, boxes[r], m_side x m_side, scale 1,
+ * sampling_ratio 0, aligned) >= 0.5, evaluated in fp32 in the reference loop's order. Rows that do not exist, rows whose gt_idx is
+ * outside [0, gmax) and rows whose box is not finite are zeros. m_side <= 256.
+ *
+ * osr_mask_loss_fwd: logits (rows, m_side, m_side) fp32 (each row's own predictor channel), targets as above. A row counts when
+ * it exists (rows_valid / seg_rows; NULL: all exist) and its class is a predictor row: classes[r] in [0, num_rows), or >= 0 when
+ * num_rows == 1 (class-agnostic; classes may then be NULL). out6 = {loss_mask, foreground rows, incorrect, positive,
+ * false positive, false negative}: loss_mask = loss_weight * sum of max(l,0) - l*t + log1p(exp(-|l|)) over the counted rows'
+ * pixels / max(their number, 1) -- exactly 0 without a counted row; the other four count pixels with (l > 0) != t, t, both without
+ * t and both with t. workspace 6 KiB. At most 2^24 pixels in all (the counts are exact). Repeats are bit-identical.
+ * osr_mask_loss_bwd: d_logits (rows, m_side, m_side) = (sigmoid(l) - t) * scale / max(foreground rows * m_side^2, 1) on counted
+ * rows, exact zeros elsewhere; every element written. workspace 16 bytes.
+ *
+ * osr_mask_upsample_predict_bwd: the backward of osr_mask_upsample_predict_ex's logits, same x / w_packed / bias / pred_w /
+ * num_rows / classes / rows_valid / seg_rows contract, fp16 / bf16, cin <= 448, s >= 8 (a tile of 64 rows reaches at most two RoIs).
+ * It recomputes u = deconv(x) + bias per tile on the MFMA exactly as the forward does and, with
+ * g[pix, n] = d_logits[pix] * pred_w[class][n] * (u > 0) taken from the fp32 accumulators, writes
+ *   dx (r, s, s, cin) in dx_dtype (`dtype`, or OSR_F32): sum over the four taps and n of g W -- a second MFMA contraction, g rounded to `dtype`; its B
+ *     operand w_packed_t is the deconv weight packed with cin and cmid exchanged (pack_deconv_weight of weight.transpose(0, 1));
+ *   g_out (P * 4, r * s * s, cmid) in `dtype`, plane- then tap-major (t = 2 dy + dx), or NULL. P = 1 for fp16; P = 2 for bf16, whose g
+ *     enters both contractions as hi = bf16(g) and lo = bf16(g - hi) (8 bits alone cost 2e-3 of the gradients' magnitude). The
+ *     deconv weight gradient is then 1 x 1 osr_conv2d_wgrad calls of x against g_out[p * 4 + t], summed over p;
+ *   d_pred_w (num_rows, cmid), d_pred_b (num_rows), d_deconv_b (cmid) fp32: per-workgroup partials in the workspace reduced in a
+ *     fixed order (per RoI in tile order, per class in RoI order) -- no atomics, repeats are bit-identical.
+ * RoIs that do not exist or whose class is not a predictor row contribute exact zeros everywhere. r == 0: zeros in the three
+ * parameter gradients.
+ * --------------------------------------------------------------------------------------------------------- */
+int64_t osr_mask_upsample_predict_bwd_workspace_bytes(int64_t r, int32_t s, int32_t cmid);
+osr_status osr_mask_upsample_predict_bwd(const void* x, int32_t dtype, int64_t r, int32_t s, int32_t cin, int32_t cmid,
+                                         const void* w_packed, const void* w_packed_t, const float* bias, const float* pred_w,
+                                         int32_t num_rows, const int64_t* classes, const int32_t* rows_valid, int32_t seg_rows,
+                                         const float* d_logits, void* dx, int32_t dx_dtype, void* g_out, float* d_pred_w, float* d_pred_b,
+                                         float* d_deconv_b, void* workspace, int64_t workspace_bytes, void* stream);
+osr_status osr_mask_targets(const uint8_t* gt_masks, int32_t n, int32_t gmax, int32_t hm, int32_t wm, const int32_t* image_hw,
+                            const float* boxes, const int32_t* gt_idx, const int32_t* rows_valid, int32_t seg_rows,
+                            int32_t m_side, uint8_t* targets, void* stream);
+osr_status osr_mask_loss_fwd(const float* logits, const uint8_t* targets, int64_t rows, int32_t m_side, int32_t num_rows,
+                             const int64_t* classes, const int32_t* rows_valid, int32_t seg_rows, float loss_weight, float* out6,
+                             void* workspace, int64_t workspace_bytes, void* stream);
+osr_status osr_mask_loss_bwd(const float* logits, const uint8_t* targets, int64_t rows, int32_t m_side, int32_t num_rows,
+                             const int64_t* classes, const int32_t* rows_valid, int32_t seg_rows, float scale, float* d_logits,
+                             void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * Test-time augmentation glue ([d2] modeling/test_time_augmentation.py GeneralizedRCNNWithTTA; csrc/osr_tta.hip), over the padded
@@ -718,6 +776,16 @@ osr_status osr_roi_match_and_sample(const float* prop_boxes, const float* prop_l
                                     float* out_boxes, float* out_logits, int64_t* out_classes, float* out_ious,
                                     float* out_gt_boxes, int32_t* out_src, int32_t* out_batch_idx, int32_t* out_counts,
                                     void* workspace, int64_t workspace_bytes, void* stream);
+/* The same with one more output, out_gt_idx (n, batch_size) int32 (may be NULL: the call above): the index of the matched ground-truth
+ * box inside its image's list (the lowest index among equal IoUs) on foreground rows, -1 on background and padding rows -- what the
+ * mask target of a row is cut from (osr_mask_targets). Every other output is bit-identical to the call above. */
+osr_status osr_roi_match_and_sample_ex(const float* prop_boxes, const float* prop_logits, const int32_t* prop_count,
+                                       int64_t pcap, const float* gt_boxes, const int64_t* gt_classes,
+                                       const int32_t* gt_count, int32_t gmax, int32_t n, const float* keys,
+                                       int32_t num_classes, int32_t batch_size, float positive_fraction, float iou_thr,
+                                       float* out_boxes, float* out_logits, int64_t* out_classes, float* out_ious,
+                                       float* out_gt_boxes, int32_t* out_src, int32_t* out_batch_idx, int32_t* out_counts,
+                                       int32_t* out_gt_idx, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* OpensetFastRCNNOutputLayers.losses (osrcnn_fast_rcnn.py:266-370): L1 between the predicted deltas and
  * Box2BoxTransform(reg_weights).get_deltas(proposal, gt), and L1 between the predicted and the matched IoU, over
@@ -920,7 +988,9 @@ osr_status osr_std_rpn_tail_bwd(const float* t, int64_t rows, const float* w_tai
                                 void* stream);
 
 /* RoIAlign backward: d feature pyramid (fp32 NHWC per level, zero-initialised by the caller; `dfeat->data` are written)
- * += scatter of dout (m,P,P,c) with the forward's geometry; fp32 atomic adds. */
+ * += scatter of dout (m,P,P,c) with the forward's geometry; fp32 atomic adds (the sums depend on their order: not bitwise
+ * reproducible). pooled 1..7: one wave per RoI over per-axis weight tables; 8..OSR_ROI_MAX_POOLED_FWD: one workgroup per RoI,
+ * torchvision's loop over every sample. Rows with batch_idx < 0 are not read. */
 osr_status osr_roi_align_bwd(const osr_pyramid* dfeat, int32_t n, const float* boxes, const int32_t* batch_idx, int64_t m,
                              int32_t pooled, int32_t canonical_level, int32_t canonical_size, int32_t min_level,
                              const void* dout, int32_t dout_dtype, void* stream);

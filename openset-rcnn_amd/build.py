@@ -33,6 +33,7 @@ SOURCES = {
     "osr_roi_align.hip": ["-ffp-contract=off"],
     "osr_det_tail.hip": ["-ffp-contract=off"],
     "osr_mask_head.hip": [],
+    "osr_mask_train.hip": ["-ffp-contract=off"],
     "osr_tta.hip": ["-ffp-contract=off"],
     "osr_train_fwd.hip": ["-ffp-contract=off"],
     "osr_rpn_sparse.hip": ["-ffp-contract=off"],

@@ -13,35 +13,8 @@
 // order -- host/weights.py pack_deconv_weight lays them out so that a wave's B fragment is one contiguous load. fp16 / bf16:
 // v_mfma_f32_32x32x16 with fp32 accumulation, BM = 64. fp32 (the parity mode): v_mfma_f32_32x32x2_f32, an exact fp32 FMA chain, BM = 32.
 #include "osr_common.h"
+#include "osr_mask_mfma.h"
 
-typedef float mh_f32x16 __attribute__((ext_vector_type(16)));
-typedef f16_t mh_f16x8 __attribute__((ext_vector_type(8)));
-typedef bf16_t mh_bf16x8 __attribute__((ext_vector_type(8)));
-
-// E: elements of K a lane holds per fragment; a K block is 2 E deep (lanes 0..31 the first E, lanes 32..63 the second).
-template <class T> struct MhFrag;
-template <> struct MhFrag<f16_t> {
-    typedef mh_f16x8 type;
-    static constexpr int BM = 64, E = 8;
-    static __device__ __forceinline__ mh_f32x16 mfma(type a, type b, mh_f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
-};
-template <> struct MhFrag<bf16_t> {
-    typedef mh_bf16x8 type;
-    static constexpr int BM = 64, E = 8;
-    static __device__ __forceinline__ mh_f32x16 mfma(type a, type b, mh_f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
-};
-template <> struct MhFrag<float> {
-    typedef float4 type;
-    static constexpr int BM = 32, E = 4;
-    static __device__ __forceinline__ mh_f32x16 mfma(type a, type b, mh_f32x16 c) {
-        c = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b.x, c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b.y, c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b.z, c, 0, 0, 0);
-        return __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b.w, c, 0, 0, 0);
-    }
-};
-
-#define MH_PAD 16         // bytes of padding per LDS row (rows of Cin elements are a multiple of 128 bytes: all on one bank otherwise)
 #define MH_MAX_LDS 65536  // static limit of a workgroup's LDS without an opt-in
 
 struct MaskHeadArgs {
@@ -52,7 +25,8 @@ struct MaskHeadArgs {
     const float* pred_b;
     const long long* classes;
     const int* rows_valid;
-    float* probs;
+    float* probs;   // sigmoid of the class row's logit, or null
+    float* logits;  // the logit itself (training: the loss reads it), or null
     long long M;  // r * s * s
     int s, cin, cmid, num_rows, seg_rows;
 };
@@ -95,7 +69,9 @@ __global__ __launch_bounds__(256) void mask_upsample_predict_kernel(MaskHeadArgs
                 if (m < a.M) {
                     const long long roi = m / ss;
                     const int rem = (int)(m - roi * ss), y = rem / a.s, xx = rem - y * a.s;
-                    a.probs[roi * (long long)(os * os) + (long long)(2 * y + dy) * os + 2 * xx + dx] = 0.f;
+                    const long long o = roi * (long long)(os * os) + (long long)(2 * y + dy) * os + 2 * xx + dx;
+                    if (a.probs) a.probs[o] = 0.f;
+                    if (a.logits) a.logits[o] = 0.f;
                 }
             }
         }
@@ -189,14 +165,16 @@ __global__ __launch_bounds__(256) void mask_upsample_predict_kernel(MaskHeadArgs
         if (q_own < 16) {
             const long long m = m0 + i * 32 + (q_own & 3) + 8 * (q_own >> 2) + 4 * (lane >> 5);
             if (m < a.M) {
-                float p = 0.f;
+                float p = 0.f, z = 0.f;
                 if (moff >= 0) {
-                    const float z = mine + a.pred_b[moff / a.cmid];
+                    z = mine + a.pred_b[moff / a.cmid];
                     p = 1.0f / (1.0f + expf(-z));
                 }
                 const long long roi = m / ss;
                 const int rem = (int)(m - roi * ss), y = rem / a.s, xx = rem - y * a.s;
-                a.probs[roi * (long long)(os * os) + (long long)(2 * y + dy) * os + 2 * xx + dx] = p;
+                const long long o = roi * (long long)(os * os) + (long long)(2 * y + dy) * os + 2 * xx + dx;
+                if (a.probs) a.probs[o] = p;
+                if (a.logits) a.logits[o] = z;
             }
         }
     }
@@ -214,10 +192,10 @@ static osr_status mask_head_launch(const MaskHeadArgs& a, hipStream_t st) {
     return OSR_OK;
 }
 
-extern "C" osr_status osr_mask_upsample_predict(const void* x, int32_t dtype, int64_t r, int32_t s, int32_t cin, int32_t cmid,
-                                                const void* w_packed, const float* bias, const float* pred_w, const float* pred_b,
-                                                int32_t num_rows, const int64_t* classes, const int32_t* rows_valid, int32_t seg_rows,
-                                                float* probs, void* stream) {
+extern "C" osr_status osr_mask_upsample_predict_ex(const void* x, int32_t dtype, int64_t r, int32_t s, int32_t cin, int32_t cmid,
+                                                   const void* w_packed, const float* bias, const float* pred_w, const float* pred_b,
+                                                   int32_t num_rows, const int64_t* classes, const int32_t* rows_valid, int32_t seg_rows,
+                                                   float* probs, float* logits, void* stream) {
     OSR_REQUIRE(osr_dtype_ok(dtype), OSR_ERR_INVALID_ARG, "osr_mask_upsample_predict: bad dtype");
     OSR_REQUIRE(r >= 0 && s >= 1 && s <= 1024, OSR_ERR_INVALID_ARG, "osr_mask_upsample_predict: bad r / s");
     OSR_REQUIRE(cin >= 64 && cin % 64 == 0 && cmid >= 64 && cmid % 64 == 0, OSR_ERR_UNSUPPORTED,
@@ -226,12 +204,12 @@ extern "C" osr_status osr_mask_upsample_predict(const void* x, int32_t dtype, in
     OSR_REQUIRE(!rows_valid || seg_rows >= 1, OSR_ERR_INVALID_ARG, "osr_mask_upsample_predict: rows_valid needs seg_rows >= 1");
     if (r == 0) return OSR_OK;
     OSR_REQUIRE(num_rows == 1 || classes, OSR_ERR_INVALID_ARG, "osr_mask_upsample_predict: a class-specific predictor needs classes");
-    OSR_REQUIRE(x && w_packed && bias && pred_w && pred_b && probs, OSR_ERR_INVALID_ARG, "osr_mask_upsample_predict: null pointer");
+    OSR_REQUIRE(x && w_packed && bias && pred_w && pred_b && (probs || logits), OSR_ERR_INVALID_ARG, "osr_mask_upsample_predict: null pointer");
     OSR_REQUIRE((((uintptr_t)x | (uintptr_t)w_packed) & 15) == 0, OSR_ERR_INVALID_ARG, "osr_mask_upsample_predict: x / w_packed must be 16-byte aligned");
     OSR_REQUIRE(r <= (1ll << 31) / ((int64_t)4 * s * s), OSR_ERR_UNSUPPORTED, "osr_mask_upsample_predict: too many RoIs");
     MaskHeadArgs a;
     a.x = x; a.w = w_packed; a.bias = bias; a.pred_w = pred_w; a.pred_b = pred_b;
-    a.classes = reinterpret_cast<const long long*>(classes); a.rows_valid = rows_valid; a.probs = probs;
+    a.classes = reinterpret_cast<const long long*>(classes); a.rows_valid = rows_valid; a.probs = probs; a.logits = logits;
     a.M = (long long)r * s * s; a.s = s; a.cin = cin; a.cmid = cmid; a.num_rows = num_rows; a.seg_rows = rows_valid ? seg_rows : 1;
     hipStream_t st = (hipStream_t)stream;
     switch (dtype) {
@@ -239,6 +217,15 @@ extern "C" osr_status osr_mask_upsample_predict(const void* x, int32_t dtype, in
         case OSR_F16: return mask_head_launch<f16_t>(a, st);
         default: return mask_head_launch<bf16_t>(a, st);
     }
+}
+
+extern "C" osr_status osr_mask_upsample_predict(const void* x, int32_t dtype, int64_t r, int32_t s, int32_t cin, int32_t cmid,
+                                                const void* w_packed, const float* bias, const float* pred_w, const float* pred_b,
+                                                int32_t num_rows, const int64_t* classes, const int32_t* rows_valid, int32_t seg_rows,
+                                                float* probs, void* stream) {
+    OSR_REQUIRE(probs || r == 0, OSR_ERR_INVALID_ARG, "osr_mask_upsample_predict: null pointer");
+    return osr_mask_upsample_predict_ex(x, dtype, r, s, cin, cmid, w_packed, bias, pred_w, pred_b, num_rows, classes, rows_valid, seg_rows, probs,
+                                        nullptr, stream);
 }
 
 // ------------------------------------------------------------------------------------------------------

@@ -1231,6 +1231,45 @@ __global__ __launch_bounds__(RA_BWD_WPB * 64) void roi_align_bwd_kernel(RoiAlign
             }
 }
 
+// ---- pooled sizes 8 .. OSR_ROI_MAX_POOLED_FWD (the mask head's 14 x 14 pooler), backward --------------------------------------
+// The mirror of roi_align_big_kernel: the kernel above keeps seven bins of state per axis and is left as it is; the larger grids are
+// pooled for the foreground rows of the sampled proposals only, so they take torchvision's backward loop as written. One workgroup
+// per RoI, one thread per (bin, channel) -- consecutive lanes hold consecutive channels, so a wave-wide atomic covers whole lines --
+// every sample of the bin with its four taps, fp32 atomics into the zeroed pyramid. Generic in the grid, the offset and the clamp
+// (ra_geometry<true>, {0.5, 0, adaptive} for the default pair); no LDS, no tables, no size limit.
+template <class T>
+__global__ __launch_bounds__(RA_BIG_THREADS) void roi_align_bwd_big_kernel(RoiAlignBwdArgs a) {
+    const long long r = blockIdx.x;
+    if (r >= a.m) return;
+    const int b = a.batch_idx[r];
+    if (b < 0) return;  // padding row: not read at all
+    const int P = a.pooled, C = a.c, total = P * P * C;
+    const T* dout = reinterpret_cast<const T*>(a.dout) + (size_t)r * P * P * C;
+    const float bx1 = a.boxes[r * 4 + 0], by1 = a.boxes[r * 4 + 1], bx2 = a.boxes[r * 4 + 2], by2 = a.boxes[r * 4 + 3];
+    const int lv = ra_level_of(bx1, by1, bx2, by2, a.canonical_level, a.canonical_size, a.min_level, a.num_levels);
+    const int H = a.h[lv], W = a.w[lv];
+    float* feat = reinterpret_cast<float*>(a.data[lv]) + (size_t)b * H * W * C;
+    const RaGeom geo = ra_geometry<true>(a.opt, bx1, by1, bx2, by2, a.scale[lv], P);
+    for (int e = threadIdx.x; e < total; e += RA_BIG_THREADS) {
+        const int bin = e / C, ch = e - bin * C;
+        const int ph = bin / P, pw = bin - ph * P;
+        const float g = osr_to_float(dout[e]) / geo.count;
+        if (g == 0.f) continue;  // (a NaN or an Inf is not 0: it reaches every pixel the bin weighs, as in the reference)
+        for (int iy = 0; iy < geo.gh; ++iy) {
+            int yl, yh; float hy, ly;
+            if (!axis_sample(geo.sh, ph, geo.bh, iy, geo.gh, H, &yl, &yh, &hy, &ly)) continue;
+            for (int ix = 0; ix < geo.gw; ++ix) {
+                int xl, xh; float hx, lx;
+                if (!axis_sample(geo.sw, pw, geo.bw, ix, geo.gw, W, &xl, &xh, &hx, &lx)) continue;
+                atomicAdd(feat + ((size_t)yl * W + xl) * C + ch, hy * hx * g);
+                atomicAdd(feat + ((size_t)yl * W + xh) * C + ch, hy * lx * g);
+                atomicAdd(feat + ((size_t)yh * W + xl) * C + ch, ly * hx * g);
+                atomicAdd(feat + ((size_t)yh * W + xh) * C + ch, ly * lx * g);
+            }
+        }
+    }
+}
+
 extern "C" osr_status osr_roi_align_bwd(const osr_pyramid* dfeat, int32_t n, const float* boxes, const int32_t* batch_idx, int64_t m,
                                         int32_t pooled, int32_t canonical_level, int32_t canonical_size, int32_t min_level, const void* dout,
                                         int32_t dout_dtype, void* stream) {
@@ -1244,7 +1283,7 @@ extern "C" osr_status osr_roi_align_bwd_opt(const osr_pyramid* dfeat, int32_t n,
     OSR_REQUIRE(dfeat && boxes && batch_idx && dout, OSR_ERR_INVALID_ARG, "osr_roi_align_bwd: null pointer");
     RA_REQUIRE_OPT(options, "osr_roi_align_bwd");
     RoiAlignBwdArgs a;
-    if (const osr_status e = ra_take_pyramid("osr_roi_align_bwd", dfeat, pooled, false, &a)) return e;
+    if (const osr_status e = ra_take_pyramid("osr_roi_align_bwd", dfeat, pooled, false, &a, OSR_ROI_MAX_POOLED_FWD)) return e;
     OSR_REQUIRE(osr_dtype_ok(dout_dtype), OSR_ERR_INVALID_ARG, "osr_roi_align_bwd: bad dtype");
     OSR_REQUIRE(n >= 1 && m >= 0 && m < (1ll << 31) && canonical_size > 0, OSR_ERR_INVALID_ARG, "osr_roi_align_bwd: bad n / m / canonical_size");
     if (m == 0) return OSR_OK;
@@ -1253,6 +1292,16 @@ extern "C" osr_status osr_roi_align_bwd_opt(const osr_pyramid* dfeat, int32_t n,
     a.dout = dout;
     a.opt = ra_opt_of(options);
     hipStream_t st = (hipStream_t)stream;
+    if (pooled > 7) {  // the per-sample scatter: either option pair
+        const dim3 bgrid((unsigned)m), bblock(RA_BIG_THREADS);
+        switch (dout_dtype) {
+            case OSR_F32: hipLaunchKernelGGL((roi_align_bwd_big_kernel<float>), bgrid, bblock, 0, st, a); break;
+            case OSR_F16: hipLaunchKernelGGL((roi_align_bwd_big_kernel<f16_t>), bgrid, bblock, 0, st, a); break;
+            default: hipLaunchKernelGGL((roi_align_bwd_big_kernel<bf16_t>), bgrid, bblock, 0, st, a); break;
+        }
+        OSR_CHECK_LAUNCH("osr_roi_align_bwd");
+        return OSR_OK;
+    }
     dim3 grid((unsigned)((m + RA_BWD_WPB - 1) / RA_BWD_WPB)), block(RA_BWD_WPB * 64);
     if (ra_opt_default(options)) {
         switch (dout_dtype) {

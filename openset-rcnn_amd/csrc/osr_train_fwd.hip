@@ -511,7 +511,8 @@ __global__ __launch_bounds__(TR_THREADS) void roi_match_sample_kernel(const floa
                                                                       float* __restrict__ ws_iou, int* __restrict__ ws_midx, float* __restrict__ out_boxes,
                                                                       float* __restrict__ out_logits, long long* __restrict__ out_cls,
                                                                       float* __restrict__ out_iou, float* __restrict__ out_gt, int* __restrict__ out_src,
-                                                                      int* __restrict__ out_bidx, int* __restrict__ out_counts) {
+                                                                      int* __restrict__ out_bidx, int* __restrict__ out_counts,
+                                                                      int* __restrict__ out_gidx /* may be null */) {
     __shared__ unsigned long long s_sel[TR_MAXK];
     __shared__ int s_idx[TR_MAXK];
     __shared__ int s_hist[256], s_scan[32];
@@ -566,10 +567,12 @@ __global__ __launch_bounds__(TR_THREADS) void roi_match_sample_kernel(const floa
                                                                : make_float4(0.f, 0.f, 0.f, 0.f);
             out_src[o] = s;
             out_bidx[o] = img;
+            if (out_gidx) out_gidx[o] = j < nfg ? midx[s] : -1;  // (foreground rows come first; a foreground row has G > 0)
         } else {
             *reinterpret_cast<float4*>(out_boxes + o * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
             *reinterpret_cast<float4*>(out_gt + o * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
             out_logits[o] = 0.f; out_cls[o] = -1; out_iou[o] = 0.f; out_src[o] = -1; out_bidx[o] = -1;
+            if (out_gidx) out_gidx[o] = -1;
         }
     }
     if (tid == 0) { out_counts[img * 3 + 0] = nsel; out_counts[img * 3 + 1] = nfg; out_counts[img * 3 + 2] = nbg; }
@@ -580,11 +583,12 @@ extern "C" int64_t osr_roi_match_sample_workspace_bytes(int32_t n, int64_t pcap,
     return (int64_t)n * (pcap + gmax) * 12;
 }
 
-extern "C" osr_status osr_roi_match_and_sample(const float* prop_boxes, const float* prop_logits, const int32_t* prop_count, int64_t pcap,
-                                               const float* gt_boxes, const int64_t* gt_classes, const int32_t* gt_count, int32_t gmax, int32_t n,
-                                               const float* keys, int32_t num_classes, int32_t batch_size, float positive_fraction, float iou_thr,
-                                               float* out_boxes, float* out_logits, int64_t* out_classes, float* out_ious, float* out_gt_boxes,
-                                               int32_t* out_src, int32_t* out_batch_idx, int32_t* out_counts, void* workspace, int64_t workspace_bytes, void* stream) {
+extern "C" osr_status osr_roi_match_and_sample_ex(const float* prop_boxes, const float* prop_logits, const int32_t* prop_count, int64_t pcap,
+                                                  const float* gt_boxes, const int64_t* gt_classes, const int32_t* gt_count, int32_t gmax, int32_t n,
+                                                  const float* keys, int32_t num_classes, int32_t batch_size, float positive_fraction, float iou_thr,
+                                                  float* out_boxes, float* out_logits, int64_t* out_classes, float* out_ious, float* out_gt_boxes,
+                                                  int32_t* out_src, int32_t* out_batch_idx, int32_t* out_counts, int32_t* out_gt_idx, void* workspace,
+                                                  int64_t workspace_bytes, void* stream) {
     OSR_REQUIRE(prop_boxes && prop_logits && prop_count && gt_boxes && gt_classes && gt_count && keys && out_boxes && out_logits && out_classes &&
                     out_ious && out_gt_boxes && out_src && out_batch_idx && out_counts && workspace, OSR_ERR_INVALID_ARG, "osr_roi_match_and_sample: null pointer");
     OSR_REQUIRE(n >= 1 && pcap >= 1 && gmax >= 1 && pcap + gmax < (1ll << 30), OSR_ERR_INVALID_ARG, "osr_roi_match_and_sample: bad sizes");
@@ -601,9 +605,19 @@ extern "C" osr_status osr_roi_match_and_sample(const float* prop_boxes, const fl
     hipLaunchKernelGGL(roi_match_sample_kernel, dim3(n), dim3(TR_THREADS), 0, (hipStream_t)stream, prop_boxes, prop_logits, prop_count, (long long)pcap,
                        gt_boxes, (const long long*)gt_classes, gt_count, gmax, keys, num_classes, batch_size, positive_fraction, iou_thr, gt_logit,
                        (int*)ws, (float*)(ws + c * 4), (int*)(ws + c * 8), out_boxes, out_logits, (long long*)out_classes, out_ious, out_gt_boxes,
-                       out_src, out_batch_idx, out_counts);
+                       out_src, out_batch_idx, out_counts, out_gt_idx);
     OSR_CHECK_LAUNCH("osr_roi_match_and_sample");
     return OSR_OK;
+}
+
+extern "C" osr_status osr_roi_match_and_sample(const float* prop_boxes, const float* prop_logits, const int32_t* prop_count, int64_t pcap,
+                                               const float* gt_boxes, const int64_t* gt_classes, const int32_t* gt_count, int32_t gmax, int32_t n,
+                                               const float* keys, int32_t num_classes, int32_t batch_size, float positive_fraction, float iou_thr,
+                                               float* out_boxes, float* out_logits, int64_t* out_classes, float* out_ious, float* out_gt_boxes,
+                                               int32_t* out_src, int32_t* out_batch_idx, int32_t* out_counts, void* workspace, int64_t workspace_bytes, void* stream) {
+    return osr_roi_match_and_sample_ex(prop_boxes, prop_logits, prop_count, pcap, gt_boxes, gt_classes, gt_count, gmax, n, keys, num_classes, batch_size,
+                                       positive_fraction, iou_thr, out_boxes, out_logits, out_classes, out_ious, out_gt_boxes, out_src, out_batch_idx,
+                                       out_counts, nullptr, workspace, workspace_bytes, stream);
 }
 
 // ------------------------------------------------------------------------------------------------------

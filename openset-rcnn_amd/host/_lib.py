@@ -172,6 +172,13 @@ PROTOTYPES = {
     "osr_detector_postprocess": (I32, [P, P, P, P, I32, I32, P, P, P, P, P, P, P]),
     "osr_mask_upsample_predict": (I32, [P, I32, I64, I32, I32, I32, P, P, P, P, I32, P, P, I32, P, P]),
     "osr_paste_masks": (I32, [P, P, I64, I32, I32, I32, F32, P, P]),
+    # mask branch, training (csrc/osr_mask_train.hip)
+    "osr_mask_targets": (I32, [P, I32, I32, I32, I32, P, P, P, P, I32, I32, P, P]),
+    "osr_mask_loss_fwd": (I32, [P, P, I64, I32, I32, P, P, I32, F32, P, P, I64, P]),
+    "osr_mask_loss_bwd": (I32, [P, P, I64, I32, I32, P, P, I32, F32, P, P, I64, P]),
+    "osr_mask_upsample_predict_ex": (I32, [P, I32, I64, I32, I32, I32, P, P, P, P, I32, P, P, I32, P, P, P]),
+    "osr_mask_upsample_predict_bwd_workspace_bytes": (I64, [I64, I32, I32]),
+    "osr_mask_upsample_predict_bwd": (I32, [P, I32, I64, I32, I32, I32, P, P, P, P, I32, P, P, I32, P, P, I32, P, P, P, P, P, I64, P]),
     "osr_tta_boxes_to_original": (I32, [P, P, P, P, P, I32, I32, I32, I32, I32, I32, I32, P, P, P, P, P]),
     "osr_tta_boxes_to_augmented": (I32, [P, P, P, I32, I32, I32, I32, I32, P, P]),
     "osr_tta_reduce_masks": (I32, [P, P, I32, P, I32, I32, I32, P, P]),
@@ -183,6 +190,7 @@ PROTOTYPES = {
     "osr_rpn_losses_fwd_ex": (I32, [P, P, I32, P, P, P, P, P, P, F32, F32, I32, P, P, P, I64, P]),
     "osr_roi_match_sample_workspace_bytes": (I64, [I32, I64, I32]),
     "osr_roi_match_and_sample": (I32, [P, P, P, I64, P, P, P, I32, I32, P, I32, I32, F32, F32, P, P, P, P, P, P, P, P, P, I64, P]),
+    "osr_roi_match_and_sample_ex": (I32, [P, P, P, I64, P, P, P, I32, I32, P, I32, I32, F32, F32, P, P, P, P, P, P, P, P, P, P, I64, P]),
     "osr_roi_box_losses_fwd": (I32, [P, I32, P, I32, I32, P, P, P, P, I64, I32, P, F32, F32, P, P, I64, P]),
     "osr_roi_box_losses_fwd_ex": (I32, [P, I32, P, I32, I32, P, P, P, P, I64, I32, P, F32, F32, P, P, P, I64, P]),
     "osr_pln_loss_fwd": (I32, [P, I64, I32, P, I32, P, P, F32, F32, F32, F32, P, P, I64, P]),

@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from .parallel import shard_range, world_info
-from .structures import Boxes, Instances
+from .structures import BitMasks, Boxes, Instances
 
 
 def read_image(file_name: str, format: str = "BGR") -> np.ndarray:
@@ -172,6 +172,39 @@ class DeviceResizer:
         return out
 
 
+def decode_segmentation(seg, h: int, w: int) -> np.ndarray:
+    """One annotation's `segmentation` as an (h, w) bool bitmap, for INPUT.MASK_FORMAT "bitmask": a 2-D uint8 / bool array as it is, or an
+    uncompressed COCO RLE dict {"size": [h, w], "counts": [run lengths]} -- column-major runs, starting with zeros -- decoded in
+    numpy. Polygon lists and compressed RLE (counts as a string) need pycocotools, which is not available: ValueError."""
+    if isinstance(seg, dict):
+        counts, size = seg.get("counts"), tuple(int(v) for v in seg.get("size", ()))
+        if isinstance(counts, (str, bytes)):
+            raise ValueError("INPUT.MASK_FORMAT \"bitmask\": compressed RLE needs pycocotools, which is not available; store uncompressed RLE "
+                             "(counts as a list) or a 2-D array")
+        if size != (h, w):
+            raise ValueError(f"segmentation RLE of size {size} on an image of {(h, w)}")
+        runs = np.asarray(counts, dtype=np.int64)
+        if runs.ndim != 1 or (runs < 0).any() or int(runs.sum()) != h * w:
+            raise ValueError(f"segmentation RLE: the runs must be non-negative and sum to {h * w}")
+        flat = np.repeat(np.arange(len(runs)) % 2 == 1, runs)
+        return flat.reshape(w, h).T.copy()  # (RLE runs down the columns)
+    if isinstance(seg, (list, tuple)):
+        raise ValueError("INPUT.MASK_FORMAT \"bitmask\": polygon segmentations need pycocotools to rasterise, which is not available; store "
+                         "a 2-D array or uncompressed RLE per annotation")
+    m = np.asarray(seg)
+    if m.ndim != 2 or m.shape != (h, w) or m.dtype not in (np.uint8, np.bool_):
+        raise ValueError(f"segmentation array {m.shape} {m.dtype}: a 2-D uint8 / bool array of the image's size {(h, w)}")
+    return m.astype(bool)
+
+
+def resize_mask(mask: np.ndarray, new_hw: Tuple[int, int]) -> np.ndarray:
+    """[d2] ResizeTransform.apply_segmentation: PIL nearest neighbour."""
+    from PIL import Image
+    if mask.shape[:2] == tuple(new_hw):
+        return mask
+    return np.asarray(Image.fromarray(mask.astype(np.uint8)).resize((new_hw[1], new_hw[0]), Image.NEAREST)).astype(bool)
+
+
 class DatasetMapper:
     """dataset dict -> model input dict ([d2] DatasetMapper with the default augmentations of cfg.INPUT)."""
 
@@ -186,6 +219,9 @@ class DatasetMapper:
             self.flip = cfg.INPUT.RANDOM_FLIP == "horizontal"
         else:
             self.min_sizes, self.max_size, self.flip = (cfg.INPUT.MIN_SIZE_TEST,), cfg.INPUT.MAX_SIZE_TEST, False
+        # [d2] DatasetMapper.use_instance_mask / instance_mask_format: masks are mapped when the model trains them
+        self.mask_format = str(cfg.INPUT.get("MASK_FORMAT", "polygon"))
+        self.use_instance_mask = bool(is_train and cfg.MODEL.MASK_ON and self.mask_format == "bitmask")
         self.rng = np.random.RandomState(seed)
 
     def __call__(self, d: dict, sample_seed: Optional[int] = None) -> dict:
@@ -209,8 +245,9 @@ class DatasetMapper:
             img = resize_image(np.ascontiguousarray(img), (nh, nw))
             out["image"] = torch.from_numpy(np.ascontiguousarray(img.transpose(2, 0, 1)))
         if self.is_train and "annotations" in d:
-            boxes = np.array([a["bbox"] for a in d["annotations"] if not a.get("iscrowd", 0)], dtype=np.float32).reshape(-1, 4)
-            classes = [a["category_id"] for a in d["annotations"] if not a.get("iscrowd", 0)]
+            annos = [a for a in d["annotations"] if not a.get("iscrowd", 0)]
+            boxes = np.array([a["bbox"] for a in annos], dtype=np.float32).reshape(-1, 4)
+            classes = [a["category_id"] for a in annos]
             if do_flip:
                 boxes = np.stack((w - boxes[:, 2], boxes[:, 1], w - boxes[:, 0], boxes[:, 3]), axis=1) if len(boxes) else boxes
             boxes = boxes * np.array([nw / w, nh / h, nw / w, nh / h], dtype=np.float32)
@@ -219,6 +256,15 @@ class DatasetMapper:
             inst = Instances((nh, nw))
             inst.gt_boxes = Boxes(torch.from_numpy(boxes))
             inst.gt_classes = torch.tensor(classes, dtype=torch.int64)
+            if self.use_instance_mask:
+                # the masks follow the image: flipped with it, resized with nearest neighbour, filtered with the boxes' `keep`
+                masks = []
+                for a in annos:
+                    if "segmentation" not in a:
+                        raise ValueError("INPUT.MASK_FORMAT \"bitmask\": an annotation has no `segmentation`")
+                    m = decode_segmentation(a["segmentation"], h, w)
+                    masks.append(resize_mask(np.ascontiguousarray(m[:, ::-1] if do_flip else m), (nh, nw)))
+                inst.gt_masks = BitMasks(torch.from_numpy(np.stack(masks)) if masks else torch.zeros((0, nh, nw), dtype=torch.bool))
             keep = inst.gt_boxes.nonempty()
             out["instances"] = inst[keep]
         return out

@@ -107,7 +107,9 @@ GRASPNET_SPLITS = {"graspnet_train": "graspnet_os_train.json", **{f"graspnet_tes
 
 def load_coco_json(json_file: str, image_root: str, dataset_name: Optional[str] = None) -> List[dict]:
     """[d2] load_coco_json without pycocotools: one dict per image with file_name, height, width, image_id and annotations
-    [{bbox XYWH_ABS, category_id (contiguous), iscrowd}]; records the category tables in the dataset's metadata."""
+    [{bbox XYWH_ABS, category_id (contiguous), iscrowd, segmentation (when the json has one: polygons, RLE or whatever it holds,
+    untouched -- DatasetMapper decodes what INPUT.MASK_FORMAT "bitmask" can train on)}]; records the category tables in the
+    dataset's metadata."""
     import json
     with open(json_file) as f:
         data = json.load(f)
@@ -129,6 +131,8 @@ def load_coco_json(json_file: str, image_root: str, dataset_name: Optional[str] 
             x, y, w, h = a["bbox"]
             rec["annotations"].append(dict(bbox=[x, y, x + w, y + h], bbox_mode="XYXY_ABS", category_id=id_map[a["category_id"]],
                                            iscrowd=a.get("iscrowd", 0)))
+            if a.get("segmentation") is not None:
+                rec["annotations"][-1]["segmentation"] = a["segmentation"]
         out.append(rec)
     return out
 

@@ -735,21 +735,24 @@ class OpensetRCNNEngine:
         return dict(loss_box_reg=box[0], loss_iou=box[1], loss_dml=dml[0], loss_cls=ce[0], roi_counts=smp["counts"]), state
 
     def forward_losses(self, images: torch.Tensor, image_hw: torch.Tensor, hp: int, wp: int, gt_boxes: torch.Tensor,
-                       gt_classes: torch.Tensor, gt_count: torch.Tensor, keys: Dict[str, torch.Tensor], keep: Optional[dict] = None):
+                       gt_classes: torch.Tensor, gt_count: torch.Tensor, keys: Dict[str, torch.Tensor], keep: Optional[dict] = None,
+                       gt_masks: Optional[torch.Tensor] = None):
         """GeneralizedRCNN.forward in training mode, forward values only (no gradients yet): the loss dict of
         ClsFreeRPN.forward (classification_free_rpn.py:493-547) and OpensetROIHeads._forward_box (osrcnn_roi_heads.py:282-
         318) for a batch, every tensor staying on the GPU. gt_boxes (n,gmax,4) fp32 / gt_classes (n,gmax) int64 padded,
         gt_count (n) int32. keys: uniform fp32 sampling keys 'rpn_reg' (n,R), 'rpn_obj' (n,R), 'roi' (n, cap+gmax) -- the
         randomness [d2] subsample_labels draws with torch.randperm (see include/osr.h). Returns a dict of 0-d / small GPU
-        tensors named as the reference names its losses."""
+        tensors named as the reference names its losses. gt_masks: the stock engine's mask branch (engine_std.py)."""
         c = self.cfg
         n = images.shape[0]
+        mask_kw = {} if gt_masks is None else dict(gt_masks=gt_masks, image_hw=image_hw)
         feats = self._backbone(images, hp, wp, keep)
         sel = self._rpn(feats, image_hw, keep, topk=c["pre_nms_topk_train"])
         if keep is not None:
             keep.update(feats=feats, sel=sel)
         rpn, rpn_state = self.rpn_losses_forward(sel, n, gt_boxes, gt_count, keys, keep)
-        roi, roi_state = self.roi_losses_forward(feats, sel["boxes"], sel["scores"], sel["counts"], gt_boxes, gt_classes, gt_count, keys["roi"])
+        roi, roi_state = self.roi_losses_forward(feats, sel["boxes"], sel["scores"], sel["counts"], gt_boxes, gt_classes, gt_count, keys["roi"],
+                                                 **mask_kw)
         if keep is not None:
             keep.update(rpn_state)
             keep.update({k: roi_state[k] for k in ("sampled", "pooled", "box_feats", "pred", "emb", "rec", "logits")})

@@ -228,13 +228,50 @@ class StandardRCNNEngine(OpensetRCNNEngine):
         return rpn, dict(tg)
 
     # ---- [d2] StandardROIHeads.label_and_sample_proposals + FastRCNNOutputLayers.losses (training) ---------------------------------
+    def mask_losses_forward(self, feats: Dict[str, torch.Tensor], smp: dict, gt_masks: torch.Tensor, image_hw: Optional[torch.Tensor]):
+        """[d2] StandardROIHeads._forward_mask in training + mask_rcnn_loss on the foreground rows of the sampled proposals
+        (select_foreground_proposals). osr_roi_match_and_sample writes an image's foreground rows first, so the mask rows are the
+        prefix of F = int(BATCH_SIZE_PER_IMAGE * POSITIVE_FRACTION) rows per image with the foreground count as rows_valid: fixed
+        capacities, no host sync, no compaction. gt_masks (n, gmax, Hm, Wm) uint8 planes padded to the batch's image size.
+        -> ((6,) {loss_mask, foreground rows, incorrect, positive, false positive, false negative}, what the backward reads)."""
+        c = self.cfg
+        n, bs = smp["boxes"].shape[0], smp["boxes"].shape[1]
+        f = max(int(c["roi_batch_size"] * c["roi_positive_fraction"]), 1)
+        f = min(f, bs)
+        res = c["mask_pooler_resolution"]
+        if gt_masks.dim() != 4 or gt_masks.shape[0] != n or gt_masks.dtype != torch.uint8:
+            raise ValueError(f"gt_masks must be (n, gmax, H, W) uint8 planes, got {tuple(gt_masks.shape)} {gt_masks.dtype}")
+        boxes = smp["boxes"][:, :f].contiguous()
+        cls = smp["gt_classes"][:, :f].reshape(-1).contiguous()
+        gidx = smp["gt_idx"][:, :f].contiguous()
+        rows_valid = smp["counts"][:, 1].contiguous()
+        ar = torch.arange(f, device=self.device, dtype=torch.int32)[None, :]
+        bidx = torch.where(ar < rows_valid[:, None], torch.arange(n, device=self.device, dtype=torch.int32)[:, None],
+                           torch.full((1, 1), -1, device=self.device, dtype=torch.int32)).reshape(-1).contiguous()
+        pooled = ops.roi_align([feats[k] for k in PYRAMID[:4]], c["pooler_scales"], boxes.view(-1, 4), bidx, res, self.dtype,
+                               c["canonical_level"], c["canonical_size"], 2, aligned=c["mask_pooler_aligned"],
+                               sampling_ratio=c["mask_pooler_sampling_ratio"])
+        acts, x = [], pooled
+        for i in range(self.mask_num_conv):
+            x = self._conv(x, f"roi_heads.mask_head.mask_fcn{i + 1}", 1, 1, relu=True)
+            acts.append(x)
+        k = self.mask_pred_w.shape[0]
+        logits = ops.mask_upsample_logits(x, self.mask_deconv_w, self.mask_deconv_b, self.mask_pred_w, self.mask_pred_b, cls, rows_valid, f)
+        targets = ops.mask_targets(gt_masks, boxes, gidx, rows_valid, 2 * res, image_hw)
+        st = ops.mask_loss_fwd(logits, targets, k, cls, rows_valid, f)
+        return st, dict(boxes=boxes.view(-1, 4), batch_idx=bidx, cls=cls, gt_idx=gidx, rows_valid=rows_valid, seg_rows=f, pooled=pooled, acts=acts,
+                        logits=logits, targets=targets)
+
     def roi_losses_forward(self, feats: Dict[str, torch.Tensor], prop_boxes, prop_scores, prop_counts, gt_boxes, gt_classes, gt_count,
-                           keys_roi: torch.Tensor):
+                           keys_roi: torch.Tensor, gt_masks: Optional[torch.Tensor] = None, image_hw: Optional[torch.Tensor] = None):
         """Proposals (detached) + GT appended, Matcher([IOU_THRESHOLDS[0]], [0, 1]), background = NUM_CLASSES, BATCH_SIZE_PER_IMAGE /
         POSITIVE_FRACTION sampling, box head, cls_score / bbox_pred, the two losses. Returns (dict: loss_cls, loss_box_reg,
-        roi_counts (n,3), stats (7); state dict with what the backward reads)."""
+        roi_counts (n,3), stats (7); state dict with what the backward reads). An engine with a mask head also runs the mask branch
+        (mask_losses_forward; gt_masks is then required): loss_mask, mask_stats (6) and state["mask"]."""
         c = self.cfg
         check_std_supported(c)
+        if self.has_mask and gt_masks is None:
+            raise ValueError("MODEL.MASK_ON: training the mask branch needs gt_masks (INPUT.MASK_FORMAT \"bitmask\" ground truth)")
         k = c["std_num_classes"]
         smp = ops.roi_match_and_sample(prop_boxes, prop_scores, prop_counts, gt_boxes, gt_classes, gt_count, keys_roi,
                                        k, c["roi_batch_size"], c["roi_positive_fraction"], c["roi_iou_threshold"])
@@ -248,7 +285,11 @@ class StandardRCNNEngine(OpensetRCNNEngine):
         st = ops.fastrcnn_losses_fwd(logits, deltas, boxes, smp["gt_boxes"].view(-1, 4), cls, k, self.box_w.shape[0] == 4, c["bbox_reg_weights"],
                                      std_loss_beta(c, "roi_box"), c["std_cls_loss_weight"], c["box_reg_weight"])
         state = dict(smp=smp, boxes=boxes, pooled=self.pooled_bin_major(pooled), h1=h1, box_feats=box_feats, logits=logits, deltas=deltas, cls=cls)
-        return dict(loss_cls=st[0], loss_box_reg=st[1], roi_counts=smp["counts"], stats=st), state
+        out = dict(loss_cls=st[0], loss_box_reg=st[1], roi_counts=smp["counts"], stats=st)
+        if self.has_mask:
+            mst, state["mask"] = self.mask_losses_forward(feats, smp, gt_masks, image_hw)
+            out.update(loss_mask=mst[0], mask_stats=mst)
+        return out, state
 
 
 def std_loss_beta(cfg: dict, key: str) -> float:

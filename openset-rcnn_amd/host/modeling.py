@@ -68,8 +68,10 @@ ROI_MASK_HEAD_REGISTRY = Registry("ROI_MASK_HEAD")
 
 
 
-def pad_ground_truth(instances: List["Instances"]):
-    """list[Instances{gt_boxes, gt_classes}] -> padded CPU tensors (n,gmax,4) fp32, (n,gmax) int64, (n) int32 counts."""
+def pad_ground_truth(instances: List["Instances"], masks_hw: Optional[Tuple[int, int]] = None):
+    """list[Instances{gt_boxes, gt_classes}] -> padded CPU tensors (n,gmax,4) fp32, (n,gmax) int64, (n) int32 counts.
+    masks_hw = (Hm, Wm): a fourth tensor, the gt_masks (BitMasks) of the instances as (n, gmax, Hm, Wm) uint8 planes, each image's
+    bitmasks in the top left corner, zeros elsewhere; ValueError when an image with instances carries no gt_masks."""
     n = len(instances)
     gmax = max(1, max(len(x) for x in instances))
     gt = torch.zeros((n, gmax, 4), dtype=torch.float32)
@@ -81,7 +83,20 @@ def pad_ground_truth(instances: List["Instances"]):
         if k:
             gt[i, :k] = x.gt_boxes.tensor.float().cpu()
             gcls[i, :k] = x.gt_classes.cpu()
-    return gt, gcls, gcnt
+    if masks_hw is None:
+        return gt, gcls, gcnt
+    planes = torch.zeros((n, gmax) + tuple(int(v) for v in masks_hw), dtype=torch.uint8)
+    for i, x in enumerate(instances):
+        if len(x) == 0:
+            continue
+        if not x.has("gt_masks"):
+            raise ValueError(f"INPUT.MASK_FORMAT \"bitmask\": image {i} of the batch has {len(x)} instances but no gt_masks "
+                             "(the mapper attaches them from each annotation's `segmentation`)")
+        m = x.gt_masks.tensor if hasattr(x.gt_masks, "tensor") else x.gt_masks
+        if m.dim() != 3 or m.shape[0] != len(x) or m.shape[1] > planes.shape[2] or m.shape[2] > planes.shape[3]:
+            raise ValueError(f"gt_masks of image {i}: {tuple(m.shape)} does not fit {len(x)} instances of an image within {tuple(planes.shape[2:])}")
+        planes[i, : len(x), : m.shape[1], : m.shape[2]] = m.cpu().to(torch.uint8)
+    return gt, gcls, gcnt, planes
 
 
 class _ExplicitBackward(torch.autograd.Function):
@@ -694,8 +709,9 @@ class MaskRCNNConvUpsampleHead(nn.Module):
         nn.init.constant_(self.predictor.bias, 0)
 
 
-MASK_LOSS_MESSAGE = ("MODEL.MASK_ON: training the mask branch needs ground-truth mask rasterisation and the mask loss "
-                     "(mask_rcnn_loss), which the HIP path does not have; the mask head runs at inference only")
+MASK_LOSS_MESSAGE = ("MODEL.MASK_ON with INPUT.MASK_FORMAT \"polygon\": the mask loss (mask_rcnn_loss) trains on bitmask ground truth only "
+                     "-- rasterising polygons needs pycocotools, which the HIP path does not have. Set INPUT.MASK_FORMAT \"bitmask\" "
+                     "(2-D arrays or uncompressed RLE per annotation) to train the mask branch; at inference the mask head runs either way")
 
 
 class FastRCNNOutputLayers(nn.Module):
@@ -737,6 +753,9 @@ class StandardROIHeads(_EngineOwner):
         self.sampler_generator = torch.Generator().manual_seed(max(int(cfg.SEED), 0))  # uniform keys replacing torch.randperm (H6)
         # [d2] StandardROIHeads._init_mask_head: the mask branch pools the same levels with its own resolution / type / ratio
         self.mask_on = bool(cfg.MODEL.MASK_ON)
+        self.mask_format = str(cfg.INPUT.get("MASK_FORMAT", "polygon")) if "INPUT" in cfg else "polygon"
+        if self.mask_on and self.mask_format not in ("polygon", "bitmask"):
+            raise ValueError(f"INPUT.MASK_FORMAT {self.mask_format!r}: \"polygon\" or \"bitmask\"")
         if self.mask_on:
             mh = cfg.MODEL.ROI_MASK_HEAD
             aligned, ratio = pooler_options_from(cfg, "ROI_MASK_HEAD")
@@ -750,16 +769,22 @@ class StandardROIHeads(_EngineOwner):
     def _forward_train(self, features: Dict[str, torch.Tensor], proposals: List[Instances], targets: List[Instances]):
         """[d2] label_and_sample_proposals + FastRCNNOutputLayers.losses: the sampled proposals (gt_classes / gt_boxes attached) and the
         loss values."""
-        if self.mask_on:
+        if self.mask_on and self.mask_format != "bitmask":
             raise NotImplementedError(MASK_LOSS_MESSAGE)
         eng = self.engine()
         boxes, scores, _, counts, cap = OpensetROIHeads._pack_proposals(proposals)
         n, dev = len(proposals), boxes.device
-        gt, gcls, gcnt = pad_ground_truth(targets)
+        mask_kw = {}
+        if self.mask_on:
+            sizes = [tuple(int(v) for v in t.image_size) for t in targets]
+            gt, gcls, gcnt, planes = pad_ground_truth(targets, (max(s[0] for s in sizes), max(s[1] for s in sizes)))
+            mask_kw = dict(gt_masks=planes.to(dev), image_hw=torch.tensor(sizes, dtype=torch.int32, device=dev))
+        else:
+            gt, gcls, gcnt = pad_ground_truth(targets)
         keys = torch.rand((n, cap + gt.shape[1]), generator=self.sampler_generator).to(dev)
         feats = {k: _to_nhwc(features[k], eng.dtype) for k in self.in_features}
         with torch.no_grad():
-            losses, st = eng.roi_losses_forward(feats, boxes, scores, counts, gt.to(dev), gcls.to(dev), gcnt.to(dev), keys)
+            losses, st = eng.roi_losses_forward(feats, boxes, scores, counts, gt.to(dev), gcls.to(dev), gcnt.to(dev), keys, **mask_kw)
         smp = st["smp"]
         host = smp["counts"].cpu()
         self.storage = {"roi_head/num_fg_samples": float(host[:, 1].sum()) / n, "roi_head/num_bg_samples": float(host[:, 2].sum()) / n}
@@ -772,7 +797,7 @@ class StandardROIHeads(_EngineOwner):
             r.gt_classes = smp["gt_classes"][i, :k]
             r.gt_boxes = Boxes(smp["gt_boxes"][i, :k])
             out.append(r)
-        return out, {"loss_cls": losses["loss_cls"], "loss_box_reg": losses["loss_box_reg"]}
+        return out, {k: losses[k] for k in ("loss_cls", "loss_box_reg", "loss_mask") if k in losses}
 
     def forward(self, images: ImageList, features: Dict[str, torch.Tensor], proposals: List[Instances], targets=None):
         del images
@@ -918,7 +943,7 @@ class GeneralizedRCNN(_EngineOwner):
         with torch.no_grad():
             # (several ranks: all apply the same verdicts -- those of the updates up to two iterations back -- at the same iteration)
             trainer.poll_overflow(wait=parallel.is_dist(), lag=trainer.MULTI_RANK_LAG if parallel.is_dist() else 0)
-            losses, saved = trainer._forward(*tensors)
+            losses, saved = trainer._forward(*tensors[:8], **self._mask_kwargs(tensors))
         names = list(losses)
         outs = _ExplicitBackward.apply(self._grad_hook(), trainer, saved, tensors[0].shape[0], *[losses[k] for k in names])
         trainer.grads_ready = False
@@ -958,7 +983,7 @@ class GeneralizedRCNN(_EngineOwner):
         `load_trainer_state(trainer)` writes them back into the module for evaluation / checkpointing."""
         from .train import OpensetRCNNTrainer
         from .train_std import StandardRCNNTrainer
-        if getattr(self.roi_heads, "mask_on", False):
+        if self._mask_training() is False:
             raise NotImplementedError(MASK_LOSS_MESSAGE)
         if self.conv_precision != "storage":
             raise ValueError(f"conv_precision {self.conv_precision!r}: the split-precision convolutions are an inference mode; set it back to \"storage\" to train")
@@ -1017,10 +1042,14 @@ class GeneralizedRCNN(_EngineOwner):
         ecfg = {**DEFAULT_CFG, **self._eng_cfg}
         batch, sizes = self._stack_images([x["image"] for x in batched_inputs])
         n, dev = len(sizes), self.device
-        gt, gcls, gcnt = pad_ground_truth([x["instances"] for x in batched_inputs])
+        hm, wm = int(batch.shape[-2]), int(batch.shape[-1])
+        planes = None
+        if self._mask_training():  # (bitmask ground truth: planes padded to the batch's image size)
+            gt, gcls, gcnt, planes = pad_ground_truth([x["instances"] for x in batched_inputs], (hm, wm))
+        else:
+            gt, gcls, gcnt = pad_ground_truth([x["instances"] for x in batched_inputs])
         gmax = gt.shape[1]
         d = ecfg["size_divisibility"]
-        hm, wm = int(batch.shape[-2]), int(batch.shape[-1])
         hp, wp = (hm + d - 1) // d * d, (wm + d - 1) // d * d
         shapes = [((hp // s), (wp // s)) for s in ecfg["fpn_strides"][:4]]
         shapes.append(((shapes[-1][0] - 1) // 2 + 1, (shapes[-1][1] - 1) // 2 + 1))
@@ -1034,7 +1063,19 @@ class GeneralizedRCNN(_EngineOwner):
             (("rpn_reg", (n, r)), ("rpn_obj", (n, r)), ("roi", (n, cap + gmax)))
         keys = {k: torch.rand(shape, generator=generator).to(dev) for k, shape in kinds}
         hw = torch.tensor(sizes, dtype=torch.int32, device=dev)
-        return batch, hw, hp, wp, gt.to(dev), gcls.to(dev), gcnt.to(dev), keys
+        out = (batch, hw, hp, wp, gt.to(dev), gcls.to(dev), gcnt.to(dev), keys)
+        return out if planes is None else out + (planes.to(dev),)  # (a ninth tensor only when the mask branch trains)
+
+    def _mask_training(self) -> Optional[bool]:
+        """None: the model has no mask branch; True: it trains (INPUT.MASK_FORMAT "bitmask"); False: training is refused."""
+        if not getattr(self.roi_heads, "mask_on", False):
+            return None
+        return self.roi_heads.mask_format == "bitmask"
+
+    @staticmethod
+    def _mask_kwargs(tensors) -> dict:
+        """_train_tensors' ninth tensor as the trainer's / engine's keyword."""
+        return {"gt_masks": tensors[8]} if len(tensors) > 8 else {}
 
     @torch.no_grad()
     def losses_forward(self, batched_inputs: List[dict], generator: Optional[torch.Generator] = None) -> Dict[str, torch.Tensor]:
@@ -1042,14 +1083,18 @@ class GeneralizedRCNN(_EngineOwner):
         only: loss_rpn_loc, loss_rpn_ctr, loss_box_reg, loss_iou, loss_dml, loss_cls. Each input dict carries "image" and
         "instances" (gt_boxes: Boxes, gt_classes); a ragged batch is padded to its largest image. `generator` seeds the
         uniform keys that replace torch.randperm in the two samplers."""
-        out = self.engine().forward_losses(*self._train_tensors(batched_inputs, generator))
+        if self._mask_training() is False:
+            raise NotImplementedError(MASK_LOSS_MESSAGE)
+        tensors = self._train_tensors(batched_inputs, generator)
+        out = self.engine().forward_losses(*tensors[:8], **self._mask_kwargs(tensors))
         return {k: v for k, v in out.items() if k.startswith("loss_")}
 
     @torch.no_grad()
     def train_step(self, trainer, batched_inputs: List[dict], generator: Optional[torch.Generator] = None) -> Dict[str, torch.Tensor]:
         """One iteration of train.py:132-148 on the trainer made by make_trainer(): forward, explicit backward, gradient
         all-reduce over the ranks and the SGD update; returns the loss dict (GPU scalars, this rank's values)."""
-        out = trainer.step(*self._train_tensors(batched_inputs, generator))
+        tensors = self._train_tensors(batched_inputs, generator)
+        out = trainer.step(*tensors[:8], **self._mask_kwargs(tensors))
         return {k: v for k, v in out.items() if k.startswith("loss_")}
 
     @torch.no_grad()

@@ -3,7 +3,7 @@ current HIP stream and output allocation. Every op runs on the HIP library or ra
 from __future__ import annotations
 
 import ctypes as C
-from typing import List, Optional, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
@@ -915,7 +915,7 @@ def roi_locality_order(feats: List[torch.Tensor], scales: Sequence[float], boxes
 
 
 MAX_SAMPLING_RATIO = 64  # include/osr.h OSR_ROI_MAX_SAMPLING_RATIO
-MAX_POOLED_FWD = 14      # include/osr.h OSR_ROI_MAX_POOLED_FWD (the backward takes 1..7)
+MAX_POOLED_FWD = 14      # include/osr.h OSR_ROI_MAX_POOLED_FWD (the scatter backward too; the pixel-centric backward takes 1..7)
 
 
 def check_pooler_options(aligned, sampling_ratio) -> Tuple[bool, int]:
@@ -1119,6 +1119,153 @@ def mask_upsample_predict(x: torch.Tensor, w_packed: torch.Tensor, bias: torch.T
     return probs
 
 
+def _mask_tail_args(x, w_packed, bias, pred_w, classes, rows_valid, seg_rows, name):
+    _need(x, name="x"); _need(w_packed, x.dtype, "w_packed")
+    _need(bias, torch.float32, "bias"); _need(pred_w, torch.float32, "pred_w")
+    r, s, s2, cin = x.shape
+    k, cmid = pred_w.shape
+    if s != s2 or bias.numel() != cmid or w_packed.numel() != 4 * cin * cmid:
+        raise OsrError(f"{name}: x {tuple(x.shape)}, bias {tuple(bias.shape)}, pred_w {tuple(pred_w.shape)}, w_packed {tuple(w_packed.shape)} "
+                       "do not fit together")
+    if classes is not None:
+        _need(classes, torch.int64, "classes")
+        if classes.numel() != r:
+            raise OsrError(f"{name}: {classes.numel()} classes for {r} RoIs")
+    if rows_valid is not None:
+        _need(rows_valid, torch.int32, "rows_valid")
+        if seg_rows < 1 or rows_valid.numel() * seg_rows < r:
+            raise OsrError(f"{name}: rows_valid does not cover the RoIs")
+    return r, s, cin, k, cmid
+
+
+def mask_upsample_logits(x: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor, pred_w: torch.Tensor, pred_b: torch.Tensor,
+                         classes: Optional[torch.Tensor] = None, rows_valid: Optional[torch.Tensor] = None, seg_rows: int = 0,
+                         probs: bool = False):
+    """mask_upsample_predict's launch with the class row's LOGIT as output (training: mask_loss_fwd reads it): (r, 2s, 2s) fp32, zeros
+    on RoIs that do not exist or have no predictor row. probs=True: -> (logits, probs), the probabilities bit-identical to
+    mask_upsample_predict's."""
+    lib = _lib.load()
+    r, s, cin, k, cmid = _mask_tail_args(x, w_packed, bias, pred_w, classes, rows_valid, seg_rows, "mask_upsample_logits")
+    _need(pred_b, torch.float32, "pred_b")
+    logits = torch.empty((r, 2 * s, 2 * s), dtype=torch.float32, device=x.device)
+    pr = torch.empty_like(logits) if probs else None
+    check(lib.osr_mask_upsample_predict_ex(_p(x), _DT[x.dtype], r, s, cin, cmid, _p(w_packed), _p(bias), _p(pred_w), _p(pred_b), k, _p(classes),
+                                           _p(rows_valid), int(seg_rows), _p(pr), _p(logits), _stream()), "osr_mask_upsample_predict")
+    return (logits, pr) if probs else logits
+
+
+def mask_upsample_predict_bwd(x: torch.Tensor, w_packed: torch.Tensor, w_packed_t: torch.Tensor, bias: torch.Tensor, pred_w: torch.Tensor,
+                              d_logits: torch.Tensor, classes: Optional[torch.Tensor] = None, rows_valid: Optional[torch.Tensor] = None,
+                              seg_rows: int = 0, want_g: bool = True, dx_dtype: Optional[torch.dtype] = None):
+    """Backward of mask_upsample_logits. w_packed_t = weights.pack_deconv_weight(deconv_weight.transpose(0, 1), dtype). d_logits
+    (r, 2s, 2s) fp32. Returns dict(dx (r, s, s, cin) like x (or dx_dtype = torch.float32), g (4, r*s*s, cmid) like x -- tap-major gradient of the upsampled
+    activation, for deconv_wgrad; bf16: (8, ...), a hi and a lo plane of four taps each; None without want_g --, d_pred_w (k, cmid), d_pred_b (k), d_deconv_b (cmid) fp32)."""
+    lib = _lib.load()
+    r, s, cin, k, cmid = _mask_tail_args(x, w_packed, bias, pred_w, classes, rows_valid, seg_rows, "mask_upsample_predict_bwd")
+    _need(w_packed_t, x.dtype, "w_packed_t"); _need(d_logits, torch.float32, "d_logits")
+    if w_packed_t.numel() != 4 * cin * cmid or tuple(d_logits.shape) != (r, 2 * s, 2 * s):
+        raise OsrError(f"mask_upsample_predict_bwd: w_packed_t {tuple(w_packed_t.shape)} / d_logits {tuple(d_logits.shape)} do not fit x {tuple(x.shape)}")
+    dev = x.device
+    if dx_dtype not in (None, torch.float32, x.dtype):
+        raise OsrError("mask_upsample_predict_bwd: dx_dtype must be float32 or x's dtype")
+    o = dict(dx=torch.empty_like(x, dtype=dx_dtype or x.dtype), g=torch.empty((8 if x.dtype == torch.bfloat16 else 4, r * s * s, cmid), dtype=x.dtype, device=dev) if want_g else None,
+             d_pred_w=torch.empty((k, cmid), dtype=torch.float32, device=dev), d_pred_b=torch.empty((k,), dtype=torch.float32, device=dev),
+             d_deconv_b=torch.empty((cmid,), dtype=torch.float32, device=dev))
+    wsb = lib.osr_mask_upsample_predict_bwd_workspace_bytes(r, s, cmid)
+    if wsb < 0:
+        check(int(wsb), "osr_mask_upsample_predict_bwd_workspace_bytes")
+    ws = torch.empty((wsb,), dtype=torch.uint8, device=dev)
+    check(lib.osr_mask_upsample_predict_bwd(_p(x), _DT[x.dtype], r, s, cin, cmid, _p(w_packed), _p(w_packed_t), _p(bias), _p(pred_w), k, _p(classes),
+                                            _p(rows_valid), int(seg_rows), _p(d_logits), _p(o["dx"]), _DT[o["dx"].dtype], _p(o["g"]), _p(o["d_pred_w"]), _p(o["d_pred_b"]),
+                                            _p(o["d_deconv_b"]), _p(ws), wsb, _stream()), "osr_mask_upsample_predict_bwd")
+    return o
+
+
+def deconv_wgrad(x: torch.Tensor, g: torch.Tensor) -> torch.Tensor:
+    """The 2 x 2 stride-2 deconvolution's weight gradient (cin, cmid, 2, 2) fp32 from x (r, s, s, cin) and the tap-major g
+    (4, r*s*s, cmid) of mask_upsample_predict_bwd: tap t's (cmid, cin) matrix is the 1 x 1 weight gradient of x against g[t]."""
+    cin, cmid = x.shape[-1], g.shape[-1]
+    m = g.shape[1]
+    dw = torch.empty((4, cmid, cin), dtype=torch.float32, device=x.device)
+    for t in range(g.shape[0]):  # (bf16: the lo plane's four taps are added to the hi plane's)
+        conv2d_wgrad(x.view(1, m, 1, cin), g[t].view(1, m, 1, cmid), 1, 1, dw=dw[t % 4].view(cmid, 1, 1, cin), accumulate=t >= 4)
+    return dw.view(2, 2, cmid, cin).permute(3, 2, 0, 1).contiguous()
+
+
+def mask_targets(gt_masks: torch.Tensor, boxes: torch.Tensor, gt_idx: torch.Tensor, rows_valid: torch.Tensor, m_side: int,
+                 image_hw: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """[d2] BitMasks.crop_and_resize for the mask rows of a batch. gt_masks (n, gmax, hm, wm) uint8 planes padded to the batch's image
+    size, boxes (n, F, 4) fp32 and gt_idx (n, F) int32 of the F mask rows per image of which the first rows_valid[i] (n, int32) exist,
+    image_hw (n, 2) int32 true image sizes (None: the planes' size). Returns targets (n * F, m_side, m_side) uint8:
+    roi_align(plane, box, m_side, aligned) >= 0.5; zeros for rows that do not exist or have gt_idx < 0."""
+    lib = _lib.load()
+    _need(gt_masks, torch.uint8, "gt_masks"); _need(boxes, torch.float32, "boxes"); _need(gt_idx, torch.int32, "gt_idx")
+    _need(rows_valid, torch.int32, "rows_valid")
+    n, gmax, hm, wm = gt_masks.shape
+    seg = boxes.numel() // (4 * n) if n else 0
+    if boxes.numel() != n * seg * 4 or gt_idx.numel() != n * seg or rows_valid.numel() != n or seg < 1:
+        raise OsrError(f"mask_targets: gt_masks {tuple(gt_masks.shape)}, boxes {tuple(boxes.shape)}, gt_idx {tuple(gt_idx.shape)}, "
+                       f"rows_valid {tuple(rows_valid.shape)} do not fit together")
+    if image_hw is not None:
+        _need(image_hw, torch.int32, "image_hw")
+        if image_hw.numel() != 2 * n:
+            raise OsrError(f"mask_targets: image_hw must be (n, 2), got {tuple(image_hw.shape)}")
+    out = torch.empty((n * seg, m_side, m_side), dtype=torch.uint8, device=gt_masks.device)
+    check(lib.osr_mask_targets(_p(gt_masks), n, gmax, hm, wm, _p(image_hw), _p(boxes), _p(gt_idx), _p(rows_valid), seg, int(m_side), _p(out),
+                               _stream()), "osr_mask_targets")
+    return out
+
+
+def _mask_loss_args(logits, targets, num_rows, classes, rows_valid, seg_rows, name):
+    _need(logits, torch.float32, "logits"); _need(targets, torch.uint8, "targets")
+    rows, m, m2 = logits.shape
+    if m != m2 or tuple(targets.shape) != tuple(logits.shape):
+        raise OsrError(f"{name}: logits {tuple(logits.shape)} and targets {tuple(targets.shape)} must both be (rows, M, M)")
+    if classes is not None:
+        _need(classes, torch.int64, "classes")
+        if classes.numel() != rows:
+            raise OsrError(f"{name}: {classes.numel()} classes for {rows} rows")
+    if rows_valid is not None:
+        _need(rows_valid, torch.int32, "rows_valid")
+        if seg_rows < 1 or rows_valid.numel() * seg_rows < rows:
+            raise OsrError(f"{name}: rows_valid does not cover the rows")
+    return rows, m
+
+
+def mask_loss_fwd(logits: torch.Tensor, targets: torch.Tensor, num_rows: int = 1, classes: Optional[torch.Tensor] = None,
+                  rows_valid: Optional[torch.Tensor] = None, seg_rows: int = 0, loss_weight: float = 1.0) -> torch.Tensor:
+    """[d2] mask_rcnn_loss on each row's own logit channel: logits (rows, M, M) fp32, targets (rows, M, M) uint8, classes (rows) int64
+    against num_rows predictor rows (1: class-agnostic, classes may be None), rows_valid / seg_rows as mask_upsample_predict.
+    Returns (6,) fp32 {loss_mask, foreground rows, incorrect, positive, false positive, false negative}."""
+    lib = _lib.load()
+    rows, m = _mask_loss_args(logits, targets, num_rows, classes, rows_valid, seg_rows, "mask_loss_fwd")
+    out = torch.empty((6,), dtype=torch.float32, device=logits.device)
+    ws = _loss_ws(logits.device, 6)
+    check(lib.osr_mask_loss_fwd(_p(logits), _p(targets), rows, m, int(num_rows), _p(classes), _p(rows_valid), int(seg_rows), loss_weight, _p(out),
+                                _p(ws), ws.numel(), _stream()), "osr_mask_loss_fwd")
+    return out
+
+
+def mask_loss_bwd(logits: torch.Tensor, targets: torch.Tensor, num_rows: int = 1, classes: Optional[torch.Tensor] = None,
+                  rows_valid: Optional[torch.Tensor] = None, seg_rows: int = 0, scale: float = 1.0) -> torch.Tensor:
+    """d loss_mask / d logits times `scale` (loss weight x loss scale): (rows, M, M) fp32, exact zeros on rows that do not count."""
+    lib = _lib.load()
+    rows, m = _mask_loss_args(logits, targets, num_rows, classes, rows_valid, seg_rows, "mask_loss_bwd")
+    out = torch.empty_like(logits)
+    ws = torch.empty((16,), dtype=torch.uint8, device=logits.device)
+    check(lib.osr_mask_loss_bwd(_p(logits), _p(targets), rows, m, int(num_rows), _p(classes), _p(rows_valid), int(seg_rows), scale, _p(out), _p(ws), 16,
+                                _stream()), "osr_mask_loss_bwd")
+    return out
+
+
+def mask_loss_scalars(out6: torch.Tensor, m_side: int) -> Dict[str, float]:
+    """[d2] mask_rcnn_loss's three event scalars from mask_loss_fwd's counts (one device-to-host copy)."""
+    _, fg, wrong, pos, fp, fn = (float(v) for v in out6.cpu())
+    numel = fg * m_side * m_side
+    return {"mask_rcnn/accuracy": 1.0 - wrong / max(numel, 1.0), "mask_rcnn/false_positive": fp / max(numel - pos, 1.0),
+            "mask_rcnn/false_negative": fn / max(pos, 1.0)}
+
+
 def paste_masks(probs: torch.Tensor, boxes: torch.Tensor, out_h: int, out_w: int, threshold: float = 0.5,
                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """[d2] paste_masks_in_image for one image: probs (r, m, m) fp32, boxes (r, 4) fp32 at the output resolution -> (r, out_h, out_w)
@@ -1282,11 +1429,12 @@ def roi_match_and_sample(prop_boxes, prop_logits, prop_count, gt_boxes, gt_class
              gt_boxes=torch.empty((n, batch_size, 4), dtype=torch.float32, device=dev),
              src=torch.empty((n, batch_size), dtype=torch.int32, device=dev),
              batch_idx=torch.empty((n * batch_size,), dtype=torch.int32, device=dev),
-             counts=torch.empty((n, 3), dtype=torch.int32, device=dev))
-    check(lib.osr_roi_match_and_sample(_p(prop_boxes), _p(prop_logits), _p(prop_count), pcap, _p(gt_boxes), _p(gt_classes), _p(gt_count), gmax, n,
-                                       _p(keys), num_classes, batch_size, positive_fraction, iou_thr, _p(o["boxes"]), _p(o["logits"]),
-                                       _p(o["gt_classes"]), _p(o["ious"]), _p(o["gt_boxes"]), _p(o["src"]), _p(o["batch_idx"]), _p(o["counts"]), _p(ws), wsb,
-                                       _stream()), "osr_roi_match_and_sample")
+             counts=torch.empty((n, 3), dtype=torch.int32, device=dev),
+             gt_idx=torch.empty((n, batch_size), dtype=torch.int32, device=dev))  # matched GT index; -1: background / padding
+    check(lib.osr_roi_match_and_sample_ex(_p(prop_boxes), _p(prop_logits), _p(prop_count), pcap, _p(gt_boxes), _p(gt_classes), _p(gt_count), gmax, n,
+                                          _p(keys), num_classes, batch_size, positive_fraction, iou_thr, _p(o["boxes"]), _p(o["logits"]),
+                                          _p(o["gt_classes"]), _p(o["ious"]), _p(o["gt_boxes"]), _p(o["src"]), _p(o["batch_idx"]), _p(o["counts"]),
+                                          _p(o["gt_idx"]), _p(ws), wsb, _stream()), "osr_roi_match_and_sample")
     return o
 
 
@@ -1595,17 +1743,24 @@ def pln_loss_bwd(emb, protos_raw, gt_classes, ious, iou_thr: float, alpha: float
 
 def roi_align_bwd(dout: torch.Tensor, shapes: Sequence[Tuple[int, int]], n: int, scales: Sequence[float], boxes, batch_idx,
                   canonical_level: int = 4, canonical_size: int = 224, min_level: int = 2, rois_per_image: Optional[int] = None,
-                  out_dtype: Optional[torch.dtype] = None, aligned: bool = True, sampling_ratio: int = 0) -> List[torch.Tensor]:
+                  out_dtype: Optional[torch.dtype] = None, aligned: bool = True, sampling_ratio: int = 0,
+                  per_sample: bool = False) -> List[torch.Tensor]:
     """dout (m,P,P,c) -> list of (n,h,w,c) feature gradients, one per level: fp32, or out_dtype (= dout's dtype: the fp32 sums rounded
     once; the scatter path casts afterwards). rois_per_image: the list is image-major with this
     fixed stride (rows [b*S, (b+1)*S) are image b's or padding) -- the pixel-centric kernel then gathers (osr_roi_align_bwd_dense: no
     atomics, no zero fill, reproducible bit for bit); otherwise the scatter kernel adds into a zeroed pyramid with fp32 atomics.
-    aligned / sampling_ratio: the forward's (roi_align)."""
+    aligned / sampling_ratio: the forward's (roi_align).
+    per_sample: pooled 8 .. MAX_POOLED_FWD (the mask pooler) exist only as the scatter kernel's per-sample form (osr_roi_align_bwd:
+    one workgroup per RoI, fp32 atomics, not bitwise reproducible, whatever rois_per_image says); a caller asks for it by name,
+    otherwise those sizes stay refused as they always were."""
     lib = _lib.load()
     opt = _roi_options(aligned, sampling_ratio)
     _need(dout, name="dout"); _need(boxes, torch.float32, "boxes"); _need(batch_idx, torch.int32, "batch_idx")
     m, pooled, _, c = dout.shape
-    dense = rois_per_image is not None and m == n * rois_per_image and rois_per_image <= 1024 and c <= 256
+    if pooled > 7 and not per_sample:
+        raise OsrError(f"roi_align_bwd: pooled size 1..7, got {pooled} (8..{MAX_POOLED_FWD}: the per-sample scatter, per_sample=True)")
+    # (pooled 8..14, the mask pooler: the scatter kernel's per-sample form; the pixel-centric kernel holds 7 bins per axis)
+    dense = rois_per_image is not None and m == n * rois_per_image and rois_per_image <= 1024 and c <= 256 and pooled <= 7
     if out_dtype not in (None, torch.float32, dout.dtype):
         raise OsrError("roi_align_bwd: out_dtype must be float32 or dout's dtype")
     odt = out_dtype or torch.float32

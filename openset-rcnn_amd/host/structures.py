@@ -65,6 +65,46 @@ class Boxes:
         return "Boxes(" + str(self.tensor) + ")"
 
 
+class BitMasks:
+    """[d2] BitMasks: (G, H, W) bool, one full-image bitmap per instance (INPUT.MASK_FORMAT "bitmask")."""
+
+    def __init__(self, tensor):
+        tensor = torch.as_tensor(tensor)
+        if tensor.numel() == 0 and tensor.dim() != 3:
+            tensor = tensor.reshape((0, 0, 0))
+        assert tensor.dim() == 3, tensor.size()
+        self.tensor = tensor.to(torch.bool)
+        self.image_size = tuple(self.tensor.shape[1:])
+
+    def to(self, *args, **kwargs) -> "BitMasks":
+        return BitMasks(self.tensor.to(*args, **kwargs))
+
+    @property
+    def device(self):
+        return self.tensor.device
+
+    def __getitem__(self, item) -> "BitMasks":
+        if isinstance(item, int):
+            return BitMasks(self.tensor[item].unsqueeze(0))
+        m = self.tensor[item]
+        assert m.dim() == 3, f"Indexing on BitMasks with {item} returns a tensor with shape {m.shape}!"
+        return BitMasks(m)
+
+    def __len__(self) -> int:
+        return self.tensor.shape[0]
+
+    def nonempty(self) -> torch.Tensor:
+        return self.tensor.flatten(1).any(dim=1)
+
+    @staticmethod
+    def cat(bitmasks_list: Sequence["BitMasks"]) -> "BitMasks":
+        assert len(bitmasks_list) > 0
+        return BitMasks(torch.cat([b.tensor for b in bitmasks_list], dim=0))
+
+    def __repr__(self):
+        return f"BitMasks(num_instances={len(self)})"
+
+
 class Instances:
     """Per-image container of equally long fields (pred_boxes, scores, pred_classes, proposal_boxes, ...)."""
 

@@ -382,8 +382,9 @@ class OpensetRCNNTrainer:
         e.protos = ops.l2_normalize_rows(self.master["protos"])
 
     # ---- forward with saved activations -------------------------------------------------------------------------
-    def _forward(self, images, image_hw, hp, wp, gt_boxes, gt_classes, gt_count, keys):
+    def _forward(self, images, image_hw, hp, wp, gt_boxes, gt_classes, gt_count, keys, gt_masks=None):
         e = self.eng
+        mask_kw = {} if gt_masks is None else dict(gt_masks=gt_masks, image_hw=image_hw)  # (the stock heads' mask branch)
         n = images.shape[0]
         s: dict = {}
         # anchor labels / sampling / targets depend on the ground truth only: a few small-grid launches (one workgroup per image)
@@ -415,7 +416,7 @@ class OpensetRCNNTrainer:
         rpn, rpn_state = e.rpn_losses_forward(sel, n, gt_boxes, gt_count, keys, targets=rpn_targets)
         s.update(rpn_state)
         # RoI heads on the sampled proposals
-        roi, roi_state = e.roi_losses_forward(out, sel["boxes"], sel["scores"], sel["counts"], gt_boxes, gt_classes, gt_count, keys["roi"])
+        roi, roi_state = e.roi_losses_forward(out, sel["boxes"], sel["scores"], sel["counts"], gt_boxes, gt_classes, gt_count, keys["roi"], **mask_kw)
         s.update(roi_state)
         # (_last_forward: what event_scalars() reads -- references only: nothing is computed or copied unless a logger asks)
         losses, self._last_forward = self._loss_dict(n, rpn, roi, sel, roi_state)
@@ -926,15 +927,17 @@ class OpensetRCNNTrainer:
         (`wait=True` is also what the checkpoint writer uses, so that no skipped or half-applied state is written blind.)"""
         return self.scaler.poll(wait, lag)
 
-    def step(self, images, image_hw, hp, wp, gt_boxes, gt_classes, gt_count, keys, update: bool = True, next_images=None) -> Dict[str, torch.Tensor]:
+    def step(self, images, image_hw, hp, wp, gt_boxes, gt_classes, gt_count, keys, update: bool = True, next_images=None,
+             gt_masks=None) -> Dict[str, torch.Tensor]:
         """One iteration: returns the loss dict (GPU scalars). update=False leaves the parameters untouched (gradients stay in
         self.grad, scaled by loss_scale). next_images (optional): the NEXT iteration's image batch, if the loader already has it: its
         frozen prefix (stem + frozen stages) is computed under this iteration's backward (_prefetch_frozen) and used by the next
-        step() that is given that same tensor."""
+        step() that is given that same tensor. gt_masks: (n, gmax, Hm, Wm) uint8 bitmask planes, for a trainer whose heads have a mask
+        branch (StandardRCNNTrainer with MODEL.MASK_ON)."""
         # earlier iterations' verdicts adjust the loss scale here, at one deterministic point of the iteration; with several ranks
         # the call waits for them, so that all ranks change the scale at the same iteration (see poll_overflow)
         self.poll_overflow(wait=parallel.is_dist(), lag=self.MULTI_RANK_LAG if parallel.is_dist() else 0)
-        losses, saved = self._forward(images, image_hw, hp, wp, gt_boxes, gt_classes, gt_count, keys)
+        losses, saved = self._forward(images, image_hw, hp, wp, gt_boxes, gt_classes, gt_count, keys, **({} if gt_masks is None else {"gt_masks": gt_masks}))
         # the data-gradient chain shares the GPU with the weight-gradient stream: tell the conv tile model (osr_conv_params.concurrency; a
         # tile-selection hint only -- results do not depend on it) so that it may take the 256 x 256 tile where a lone stream would not
         with ops.concurrent_streams(self.backward_concurrency_hint):

@@ -13,10 +13,18 @@ the heads). The heads:
   RoI heads  GT appended, Matcher([0.5]), 512 rows per image at 25 % foreground (osr_roi_match_and_sample), box head FC1 / FC2 on
              the MFMA kernels, cls_score / bbox_pred as exact-fp32 GEMMs, cross entropy + smooth-L1 (osr_fastrcnn_losses_fwd / _bwd),
              class-agnostic or class-specific regression.
-The loss dict is {loss_rpn_cls, loss_rpn_loc, loss_cls, loss_box_reg}."""
+  Mask head  (MODEL.MASK_ON, bitmask ground truth) [d2] mask_rcnn_loss on the foreground prefix of every image's sampled rows
+             (F = int(BATCH_SIZE_PER_IMAGE * POSITIVE_FRACTION) rows, the foreground count as rows_valid): 14 x 14 RoIAlign, mask_fcn*
+             on the MFMA convolution, the fused deconv + predictor tail with a logits output, targets cut from the matched instance's
+             bitmask (osr_mask_targets), BCE (osr_mask_loss_fwd / _bwd). Backward: osr_mask_upsample_predict_bwd (predictor, ReLU,
+             deconv in one launch), the mask_fcn layers' data / weight / bias gradients, the per-sample RoIAlign scatter, summed with
+             the box branch's feature gradient. The branch's gradients travel with an extra power-of-two factor (MASK_GRAD_SCALE)
+             that is divided out where they become fp32: the mean over 28 x 28 pixels makes them ~10^3 smaller than the box branch's.
+The loss dict is {loss_rpn_cls, loss_rpn_loc, loss_cls, loss_box_reg} (+ loss_mask)."""
 from __future__ import annotations
 
-from typing import Dict
+import math
+from typing import Dict, List
 
 import torch
 
@@ -24,9 +32,10 @@ from . import ops
 from .engine import PYRAMID, RPN_CONV
 from .engine_std import StandardRCNNEngine, check_std_supported, std_loss_beta
 from .train import OpensetRCNNTrainer
-from .weights import pack_fc1_weight
+from .weights import pack_deconv_weight, pack_fc1_weight, unpack_deconv_weight
 
-LOSS_KEYS = ("loss_rpn_cls", "loss_rpn_loc", "loss_cls", "loss_box_reg")
+LOSS_KEYS = ("loss_rpn_cls", "loss_rpn_loc", "loss_cls", "loss_box_reg")  # (+ "loss_mask" from a trainer with the mask branch)
+MASK_PRE = "roi_heads.mask_head."
 
 
 def _pad16(x: int) -> int:
@@ -39,6 +48,19 @@ class StandardRCNNTrainer(OpensetRCNNTrainer):
     -- reverse order of gradient completion, as the base class lays them out."""
 
     SPLIT_BOX_HEAD = False  # (box_head="split" is refused with the stock engine's ValueError)
+    # The mask branch's gradients carry an extra power-of-two factor on top of the loss scale from the loss down to the places where
+    # they turn fp32 (parameter gradients, the RoIAlign scatter's input), where it is divided out exactly: d loss_mask / d logit is
+    # 1 / (foreground rows x 784) per pixel, which with [d2]'s 0.001 predictor initialiser puts the deconv's output gradient into
+    # fp16's subnormals (measured: DESIGN section 7 item 10). The factor is MASK_GRAD_SCALE, lowered so that loss scale x factor
+    # never exceeds MASK_SCALE_PRODUCT = 2^20: |d logit| <= 2^20 / 784 = 1337 then, whatever the number of foreground rows, so the
+    # gradient of the upsampled activation overflows fp16 only with predictor weights above 49 -- the branch adds no overflow
+    # exposure at a loss scale the user configured higher.
+    MASK_GRAD_SCALE = 1024.0
+    MASK_SCALE_PRODUCT = 2.0 ** 20
+
+    def _mask_grad_scale(self) -> float:
+        room = self.MASK_SCALE_PRODUCT / max(self.loss_scale, 1.0)
+        return float(min(self.MASK_GRAD_SCALE, 2.0 ** max(math.floor(math.log2(room)), 0))) if room >= 1.0 else 1.0
 
     @staticmethod
     def _make_engine(params, cfg, dtype, device, class_map):
@@ -46,9 +68,28 @@ class StandardRCNNTrainer(OpensetRCNNTrainer):
         check_std_supported(eng.cfg)
         return eng
 
+    def _add_mask_masters(self, params) -> None:
+        """mask_fcn1..N (3x3 convs like the trunk's: packed fp32 master, storage-type copy, backward-data copy), the deconv in the
+        tail kernels' fragment order (master and gradient fp32 in that order, so the update refreshes the forward's operand in place;
+        the backward's transposed operand is re-packed in _refresh_heads), the predictor's (rows, CONV_DIM) fp32 matrix, the biases.
+        Reverse order of gradient completion, in front of the box head's."""
+        e = self.eng
+        for i in range(e.mask_num_conv):
+            self._add_conv(f"{MASK_PRE}mask_fcn{i + 1}", params, bias=True)
+        self.master["mask_deconv.w"] = pack_deconv_weight(params[MASK_PRE + "deconv.weight"].detach().float(), torch.float32, frag_elems=8).to(e.device)
+        self.lowp["mask_deconv.w"] = e.mask_deconv_w
+        self.master["mask_deconv.b"] = e.mask_deconv_b
+        self.master["mask_pred.w"], self.master["mask_pred.b"] = e.mask_pred_w, e.mask_pred_b
+
     def _add_head_masters(self, params) -> None:
         e, dev = self.eng, self.eng.device
         a = e.num_anchors
+        if e.has_mask:
+            if self.dtype == torch.float32:
+                raise ValueError("MODEL.MASK_ON: the mask branch trains in fp16 / bf16 (kernel_dtype float32 is an inference mode of the mask head)")
+            if e.cfg["mask_pooler_resolution"] < 8:
+                raise ValueError("MODEL.ROI_MASK_HEAD.POOLER_RESOLUTION below 8: the mask tail's backward needs 8 .. 14")
+            self._add_mask_masters(params)
         # one (5A,256) storage: the forward's two GEMMs read row views of it, the tail backward reads it whole
         e.rpn_wtail = torch.cat([e.rpn_wo, e.rpn_wd]).contiguous()
         e.rpn_btail = torch.cat([e.rpn_bo, e.rpn_bd]).contiguous()
@@ -80,6 +121,11 @@ class StandardRCNNTrainer(OpensetRCNNTrainer):
         if not hasattr(self, "w3_t"):
             self.w3_t = torch.empty((9 * 256, 256), dtype=w3.dtype, device=e.device)
         self.w3_t.copy_(w3.t())
+        if e.has_mask:  # the tail backward's second operand: the deconv weight packed with Cin and Cmid exchanged
+            wt = pack_deconv_weight(unpack_deconv_weight(e.mask_deconv_w).transpose(0, 1), self.dtype)
+            if not hasattr(self, "mask_deconv_wt"):
+                self.mask_deconv_wt = torch.empty_like(wt)
+            self.mask_deconv_wt.copy_(wt)
 
     def _pixel_levels(self, shapes, n):
         """Level table of the pixel rows (one row per location): what the sparse gather / scatter walk."""
@@ -98,13 +144,18 @@ class StandardRCNNTrainer(OpensetRCNNTrainer):
     @staticmethod
     def _loss_dict(n, rpn, roi, sel, roi_state):
         losses = dict(loss_rpn_cls=rpn[0], loss_rpn_loc=rpn[1], loss_cls=roi["loss_cls"], loss_box_reg=roi["loss_box_reg"])
-        return losses, dict(n=n, rpn_counts=rpn[2:4], roi_counts=roi["roi_counts"], stats=roi["stats"])
+        last = dict(n=n, rpn_counts=rpn[2:4], roi_counts=roi["roi_counts"], stats=roi["stats"])
+        if "loss_mask" in roi:
+            losses["loss_mask"] = roi["loss_mask"]
+            last.update(mask_stats=roi["mask_stats"], mask_side=roi_state["mask"]["logits"].shape[-1])
+        return losses, last
 
     def event_scalars(self) -> Dict[str, float]:
         """The scalars [d2] RPN / StandardROIHeads / FastRCNNOutputLayers put into EventStorage for the last forward: rpn/num_pos_anchors,
         rpn/num_neg_anchors (per image), roi_head/num_fg_samples, roi_head/num_bg_samples (means over the images),
         fast_rcnn/cls_accuracy (only when a row was sampled), fast_rcnn/fg_cls_accuracy and fast_rcnn/false_negative (only when a
-        foreground row exists) -- what [d2] FastRCNNOutputLayers puts."""
+        foreground row exists) -- what [d2] FastRCNNOutputLayers puts. With the mask branch: mask_rcnn/accuracy, mask_rcnn/false_positive,
+        mask_rcnn/false_negative as [d2] mask_rcnn_loss computes them (logit > 0 against the target, denominators at least 1)."""
         lf = getattr(self, "_last_forward", None)
         if lf is None:
             return {}
@@ -119,6 +170,8 @@ class StandardRCNNTrainer(OpensetRCNNTrainer):
             if fg > 0:
                 out["fast_rcnn/fg_cls_accuracy"] = fg_correct / fg
                 out["fast_rcnn/false_negative"] = fg_bg / fg
+        if "mask_stats" in lf:
+            out.update(ops.mask_loss_scalars(lf["mask_stats"], lf["mask_side"]))
         return out
 
     # ---- backward ----------------------------------------------------------------------------------------------
@@ -160,13 +213,69 @@ class StandardRCNNTrainer(OpensetRCNNTrainer):
         d_bf2 = self._f32_linear_bwd(s["box_feats"], d_deltas, self.t_box, "box", dy_pad=self.t_box.shape[1])
         d_bf = ops.add_cast(d_bf, d_bf2, torch.float32)
         d_feat = self._box_head_bwd(s, d_bf, n)
+        if e.has_mask:  # the branch's share joins the box branch's feature gradient (storage type) in front of the trunk
+            share = self._mask_head_bwd(s, n, S)
+            d_feat = [ops.add_cast(a_, b_, self.dtype) for a_, b_ in zip(share, self._roi_share(d_feat))] + list(d_feat[4:])
         # --- RPN 3x3 conv: col2im of the listed anchors' per-tap gradients into the RoI heads' feature gradient (p6: into zeros) ---
         self._join_side(rpn_ready, rpn_grad)
         self._backward_trunk(s, self._sparse_rpn_scatter(self._pixel_levels(s["rpn_shapes"], n), s, n, rpn_grad, d_feat), prefetch)
 
+    def _mask_head_bwd(self, s, n, S: float) -> List[torch.Tensor]:
+        """loss_mask's gradient: BCE -> predictor, ReLU, deconv (one launch) -> ReLU, mask_fcnN .. mask_fcn1 -> 14 x 14 RoIAlign. Writes
+        the mask masters' gradients; returns the branch's share of the p2..p5 feature gradient (fp32, times S)."""
+        e, c, g, dt = self.eng, self.eng.cfg, self.grad, self.dtype
+        ms, p = s["mask"], s["p"]
+        B = self._mask_grad_scale()
+        k, cls, rv, f = e.mask_pred_w.shape[0], ms["cls"], ms["rows_valid"], ms["seg_rows"]
+        d_logits = ops.mask_loss_bwd(ms["logits"], ms["targets"], k, cls, rv, f, scale=S * B)
+        acts = ms["acts"]
+        x_top = acts[-1] if acts else ms["pooled"]
+        # (no conv below the tail: its data gradient goes straight to RoIAlign's fp32 sums)
+        o = ops.mask_upsample_predict_bwd(x_top, e.mask_deconv_w, self.mask_deconv_wt, e.mask_deconv_b, e.mask_pred_w, d_logits, cls, rv, f,
+                                          dx_dtype=None if acts else torch.float32)
+        dx, gup = o["dx"], o["g"]
+
+        def tail_grads():
+            torch.mul(o["d_pred_w"], 1.0 / B, out=g["mask_pred.w"])
+            torch.mul(o["d_pred_b"], 1.0 / B, out=g["mask_pred.b"])
+            torch.mul(o["d_deconv_b"], 1.0 / B, out=g["mask_deconv.b"])
+            dw = ops.deconv_wgrad(x_top, gup)
+            torch.mul(pack_deconv_weight(dw, torch.float32, frag_elems=8), 1.0 / B, out=g["mask_deconv.w"])
+        self._wg(tail_grads, x_top, gup, o["d_pred_w"], o["d_pred_b"], o["d_deconv_b"])
+        self._done("mask_pred.w", "mask_pred.b", "mask_deconv.w", "mask_deconv.b")
+        res = c["mask_pooler_resolution"]
+        if acts:
+            ops.relu_mask_(dx, acts[-1])
+        for i in range(len(acts), 0, -1):
+            name = f"{MASK_PRE}mask_fcn{i}"
+            below = acts[i - 2] if i > 1 else ms["pooled"]
+
+            def layer_grads(name=name, below=below, dx=dx):
+                ops.conv2d_wgrad(below, dx, 3, 3, 1, 1, dw=g[name + ".w"])
+                ops.bias_grad(dx, g[name + ".b"])
+                g[name + ".w"].mul_(1.0 / B)
+                g[name + ".b"].mul_(1.0 / B)
+            self._wg(layer_grads, below, dx)
+            self._done(name + ".w", name + ".b")
+            # (the ReLU below a layer rides in its data gradient's epilogue; the lowest layer's leaves in fp32 for RoIAlign's sums)
+            dx = ops.conv2d_dgrad(dx, self.wd[name], (res, res), 1, 1, mask=acts[i - 2] if i > 1 else None,
+                                  out_dtype=None if i > 1 else torch.float32)
+        dx.mul_(1.0 / B)
+        shapes = [(p[k_].shape[1], p[k_].shape[2]) for k_ in PYRAMID[:4]]
+        share = ops.roi_align_bwd(dx, shapes, n, c["pooler_scales"], ms["boxes"], ms["batch_idx"], c["canonical_level"], c["canonical_size"], 2,
+                                  aligned=c["mask_pooler_aligned"], sampling_ratio=c["mask_pooler_sampling_ratio"], per_sample=True)
+        return share
+
     def export_state_dict(self) -> Dict[str, torch.Tensor]:
-        """The trainable parameters under detectron2 names and layouts (StandardRPNHead, FastRCNNOutputLayers keys)."""
+        """The trainable parameters under detectron2 names and layouts (StandardRPNHead, FastRCNNOutputLayers keys; with the mask
+        branch MaskRCNNConvUpsampleHead's: mask_fcn* come with the other convolutions, deconv (Cin, Cmid, 2, 2), predictor (K, Cmid, 1, 1))."""
         out = self._export_trunk()
+        if self.eng.has_mask:
+            out[MASK_PRE + "deconv.weight"] = unpack_deconv_weight(self.master["mask_deconv.w"]).cpu()
+            out[MASK_PRE + "deconv.bias"] = self.master["mask_deconv.b"].cpu().clone()
+            pw = self.master["mask_pred.w"].cpu()
+            out[MASK_PRE + "predictor.weight"] = pw.reshape(pw.shape[0], pw.shape[1], 1, 1).clone()
+            out[MASK_PRE + "predictor.bias"] = self.master["mask_pred.b"].cpu().clone()
         a = self.eng.num_anchors
         t_w, t_b = self.master["rpn_tail.w"].cpu(), self.master["rpn_tail.b"].cpu()
         out["proposal_generator.rpn_head.objectness_logits.weight"] = t_w[:a].reshape(a, -1, 1, 1).clone()

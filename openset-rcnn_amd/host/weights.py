@@ -103,17 +103,26 @@ def pack_fc1_weight(w: torch.Tensor, channels: int, pooled: int, dtype: torch.dt
     return w.view(o, channels, pooled, pooled).permute(0, 2, 3, 1).reshape(o, pooled * pooled * channels).contiguous().to(dtype)
 
 
-def pack_deconv_weight(w: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
+def pack_deconv_weight(w: torch.Tensor, dtype: torch.dtype, frag_elems: int = 0) -> torch.Tensor:
     """[d2] MaskRCNNConvUpsampleHead.deconv weight (cin, cmid, 2, 2) -> the B operand of ops.mask_upsample_predict (include/osr.h
     osr_mask_upsample_predict): one (cmid, cin) matrix per tap t = 2 dy + dx, cut into the MFMA fragments a wave loads -- blocks of 32
     output channels x 2E input channels, E = 8 (fp16 / bf16) or 4 (fp32), laid out [t][n / 32][k / 2E][(k / E) % 2][n % 32][k % E] so
-    that the 64 lanes of a wave read one contiguous block. cin and cmid must be multiples of 64."""
+    that the 64 lanes of a wave read one contiguous block. cin and cmid must be multiples of 64. frag_elems: E whatever the dtype
+    (the trainer keeps its fp32 master and gradient in the fp16 / bf16 kernels' order, E = 8). The backward's second operand
+    (ops.mask_upsample_predict_bwd w_packed_t) is this function on weight.transpose(0, 1)."""
     cin, cmid, kh, kw = w.shape
     if (kh, kw) != (2, 2) or cin % 64 or cmid % 64:
         raise ValueError(f"deconv weight {tuple(w.shape)}: (cin, cmid, 2, 2) with cin and cmid multiples of 64")
-    e = 4 if dtype == torch.float32 else 8
+    e = frag_elems or (4 if dtype == torch.float32 else 8)
     wt = w.detach().permute(2, 3, 1, 0).reshape(4, cmid // 32, 32, cin // (2 * e), 2, e)  # [t][n / 32][n % 32][k / 2E][half][k % E]
     return wt.permute(0, 1, 3, 4, 2, 5).contiguous().to(dtype)
+
+
+def unpack_deconv_weight(p: torch.Tensor) -> torch.Tensor:
+    """The inverse of pack_deconv_weight: fragments (4, cmid / 32, cin / 2E, 2, 32, E) -> (cin, cmid, 2, 2), same dtype."""
+    _, nb, kb, _, _, e = p.shape
+    cmid, cin = nb * 32, kb * 2 * e
+    return p.permute(0, 1, 4, 2, 3, 5).reshape(2, 2, cmid, cin).permute(3, 2, 0, 1).contiguous()
 
 
 def split_fp32_rows(w: torch.Tensor):
