@@ -21,6 +21,24 @@ __device__ __forceinline__ float osr_smooth_l1_grad(float x, float beta) {
     return x > 0.f ? 1.f : (x < 0.f ? -1.f : 0.f);
 }
 
+// [d2] Box2BoxTransform.get_deltas(src, tgt) with weights (wx, wy, ww, wh): the targets of the "smooth_l1" loss
+__device__ __forceinline__ float4 osr_b2b_get_deltas(float4 s, float4 t, float wx, float wy, float ww, float wh) {
+    const float sw = s.z - s.x, sh = s.w - s.y, scx = s.x + 0.5f * sw, scy = s.y + 0.5f * sh;
+    const float tw = t.z - t.x, th = t.w - t.y, tcx = t.x + 0.5f * tw, tcy = t.y + 0.5f * th;
+    return make_float4(wx * (tcx - scx) / sw, wy * (tcy - scy) / sh, ww * logf(tw / sw), wh * logf(th / sh));
+}
+
+// [d2] Box2BoxTransform.apply_deltas(d, src): the decoded box of the other losses. Centre = d/w * size + centre, size =
+// exp(min(d/w, clamp)) * size; the decoded size also goes to *pw, *ph (the gradient through the exponential needs it, and it is zero
+// where d/w reaches the clamp).
+#define OSR_B2B_SCALE_CLAMP 4.135166556742356f  // log(1000 / 16)
+__device__ __forceinline__ float4 osr_b2b_apply_deltas(float4 s, const float* d, float wx, float wy, float ww, float wh, float* pw, float* ph) {
+    const float sw = s.z - s.x, sh = s.w - s.y, scx = s.x + 0.5f * sw, scy = s.y + 0.5f * sh;
+    *pw = expf(fminf(d[2] / ww, OSR_B2B_SCALE_CLAMP)) * sw; *ph = expf(fminf(d[3] / wh, OSR_B2B_SCALE_CLAMP)) * sh;
+    const float pcx = d[0] / wx * sw + scx, pcy = d[1] / wy * sh + scy;
+    return make_float4(pcx - 0.5f * *pw, pcy - 0.5f * *ph, pcx + 0.5f * *pw, pcy + 0.5f * *ph);
+}
+
 // Loss of a predicted box p = (x1, y1, x2, y2) against the target g, and its gradient w.r.t. the four coordinates of p.
 // type: OSR_LOSS_IOU / GIOU / DIOU / CIOU. The enclosing-box / intersection corners pick the predicted coordinate on strict
 // inequality (a tie is a set of measure zero for float boxes; torch's min / max share or route the gradient there).

@@ -47,10 +47,8 @@ __global__ __launch_bounds__(256) void mask_upsample_predict_kernel(MaskHeadArgs
         const long long m = m0 + tid;
         int off = -1;
         if (m < a.M) {
-            const long long roi = m / ss;
-            const long long cls = a.classes ? a.classes[roi] : 0;
-            const bool live = !a.rows_valid || (int)(roi % a.seg_rows) < a.rows_valid[roi / a.seg_rows];
-            if (live && cls >= 0 && (a.num_rows == 1 || cls < a.num_rows)) off = (a.num_rows == 1 ? 0 : (int)cls) * a.cmid;
+            const int row = mt_row_class(m / ss, a.num_rows, a.classes, a.rows_valid, a.seg_rows);
+            if (row >= 0) off = row * a.cmid;
         }
         s_off[tid] = off;
         valid = off >= 0;

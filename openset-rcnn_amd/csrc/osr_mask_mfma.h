@@ -1,5 +1,5 @@
 // The MFMA fragments of the mask head's tail (csrc/osr_mask_head.hip: forward; csrc/osr_mask_train.hip: backward), shared so that the
-// backward recomputes the deconvolution with the very instructions of the forward.
+// backward recomputes the deconvolution with the very instructions of the forward, and the one rule for which mask rows are live.
 #pragma once
 #include "osr_common.h"
 
@@ -31,3 +31,14 @@ template <> struct MhFrag<float> {
 };
 
 #define MH_PAD 16         // bytes of padding per LDS row (rows of Cin elements are a multiple of 128 bytes: all on one bank otherwise)
+
+// does mask row r exist (its segment's count: the first rows_valid[segment] rows of every seg_rows), and which predictor row does it
+// take (-1: none; row 0 when class-agnostic). Forward, loss and backward agree on it: a row that is not live counts nowhere.
+__device__ __forceinline__ int mt_row_class(long long r, int num_rows, const long long* __restrict__ classes, const int* __restrict__ rows_valid, int seg_rows) {
+    if (rows_valid && (int)(r % seg_rows) >= rows_valid[r / seg_rows]) return -1;
+    if (!classes) return 0;
+    const long long c = classes[r];
+    if (c < 0) return -1;
+    if (num_rows == 1) return 0;
+    return c < num_rows ? (int)c : -1;
+}

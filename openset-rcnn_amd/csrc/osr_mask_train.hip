@@ -9,9 +9,10 @@
 // Reductions are two-stage in a fixed order (per-workgroup partials, then one wave): repeats are bit-identical. Compiled with
 // -ffp-contract=off so that a target's bilinear average rounds as the reference loop's.
 #include "osr_common.h"
+#include "osr_loss_common.h"
+#include "osr_mask_mfma.h"
 
 #define MT_THREADS 256
-#define MT_RED_BLOCKS 256
 #define MT_NV 6
 
 // One sample coordinate of torchvision's pre_calc_for_bilinear_interpolate along one axis (the rule csrc/osr_roi_align.hip
@@ -25,16 +26,6 @@ __device__ __forceinline__ bool mt_axis_sample(float start, int bin, float bin_s
     const float f = v - (float)l;
     *lo = l; *hi = h; *wh = f; *wl = 1.f - f;
     return true;
-}
-
-// does mask row r exist (its segment's count), and which predictor row does it take (-1: none)
-__device__ __forceinline__ int mt_row_class(long long r, int num_rows, const long long* __restrict__ classes, const int* __restrict__ rows_valid, int seg_rows) {
-    if (rows_valid && (int)(r % seg_rows) >= rows_valid[r / seg_rows]) return -1;
-    if (!classes) return 0;
-    const long long c = classes[r];
-    if (c < 0) return -1;
-    if (num_rows == 1) return 0;
-    return c < num_rows ? (int)c : -1;
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -101,53 +92,26 @@ struct MaskLoss {
     long long rows; int mm, num_rows, seg_rows;
 };
 
-// F.binary_cross_entropy_with_logits in its stable form
-__device__ __forceinline__ float mt_bce(float x, float y) { return fmaxf(x, 0.f) - x * y + log1pf(expf(-fabsf(x))); }
-__device__ __forceinline__ float mt_sigmoid(float x) {
-    const float e = expf(-fabsf(x));
-    return x >= 0.f ? 1.0f / (1.0f + e) : e / (1.0f + e);
-}
-
-__global__ __launch_bounds__(MT_THREADS) void mask_loss_kernel(MaskLoss p, float* __restrict__ partial /* [MT_RED_BLOCKS][MT_NV] */) {
-    __shared__ float s_red[MT_NV][MT_THREADS / 64];
+__global__ __launch_bounds__(MT_THREADS) void mask_loss_kernel(MaskLoss p, float* __restrict__ partial /* [OSR_LOSS_RED_BLOCKS][MT_NV] */) {
     float v[MT_NV] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};  // bce, pixels of foreground rows, incorrect, positive, false positive, false negative
     const long long total = p.rows * p.mm;
     for (long long i = (long long)blockIdx.x * MT_THREADS + threadIdx.x; i < total; i += (long long)gridDim.x * MT_THREADS) {
         if (mt_row_class(i / p.mm, p.num_rows, p.classes, p.rows_valid, p.seg_rows) < 0) continue;
         const float x = p.logits[i];
         const bool t = p.targets[i] != 0, wrong = (x > 0.f) != t;
-        v[0] += mt_bce(x, t ? 1.f : 0.f);
+        v[0] += osr_bce_with_logits(x, t ? 1.f : 0.f);
         v[1] += 1.f;
         v[2] += wrong ? 1.f : 0.f;
         v[3] += t ? 1.f : 0.f;
         v[4] += wrong && !t ? 1.f : 0.f;
         v[5] += wrong && t ? 1.f : 0.f;
     }
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-#pragma unroll
-    for (int q = 0; q < MT_NV; ++q) {
-        float x = v[q];
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) x += __shfl_down(x, d, 64);
-        if (lane == 0) s_red[q][wid] = x;
-    }
-    __syncthreads();
-    if (threadIdx.x < MT_NV) {
-        float s = 0.f;
-        for (int w = 0; w < MT_THREADS / 64; ++w) s += s_red[threadIdx.x][w];
-        partial[(long long)blockIdx.x * MT_NV + threadIdx.x] = s;
-    }
+    osr_loss_block_reduce_store<MT_NV>(v, partial);
 }
 
 __global__ __launch_bounds__(64) void mask_loss_final(const float* __restrict__ partial, int mm, float weight, float* __restrict__ out) {
     float s[MT_NV];
-    for (int q = 0; q < MT_NV; ++q) {
-        float x = 0.f;
-        for (int b = threadIdx.x; b < MT_RED_BLOCKS; b += 64) x += partial[(long long)b * MT_NV + q];
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) x += __shfl_down(x, d, 64);
-        s[q] = x;
-    }
+    for (int q = 0; q < MT_NV; ++q) s[q] = osr_loss_column_sum(partial, OSR_LOSS_RED_BLOCKS, MT_NV, q);
     if (threadIdx.x == 0) {
         out[0] = s[0] / fmaxf(s[1], 1.0f) * weight;  // (no foreground row: 0 / 1)
         out[1] = s[1] / (float)mm;
@@ -174,35 +138,27 @@ extern "C" osr_status osr_mask_loss_fwd(const float* logits, const uint8_t* targ
     // (the counts are summed as fp32 integers: exact up to 2^24 pixels)
     OSR_REQUIRE(rows * p.mm <= (1ll << 24), OSR_ERR_UNSUPPORTED, "osr_mask_loss_fwd: more than 2^24 mask pixels");
     OSR_REQUIRE(out6 && workspace, OSR_ERR_INVALID_ARG, "osr_mask_loss_fwd: null pointer");
-    OSR_REQUIRE(workspace_bytes >= (int64_t)MT_RED_BLOCKS * MT_NV * 4, OSR_ERR_WORKSPACE, "osr_mask_loss_fwd: workspace needs %d bytes", MT_RED_BLOCKS * MT_NV * 4);
+    OSR_REQUIRE(workspace_bytes >= (int64_t)OSR_LOSS_RED_BLOCKS * MT_NV * 4, OSR_ERR_WORKSPACE, "osr_mask_loss_fwd: workspace needs %d bytes", OSR_LOSS_RED_BLOCKS * MT_NV * 4);
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(mask_loss_kernel, dim3(MT_RED_BLOCKS), dim3(MT_THREADS), 0, st, p, (float*)workspace);
+    hipLaunchKernelGGL(mask_loss_kernel, dim3(OSR_LOSS_RED_BLOCKS), dim3(MT_THREADS), 0, st, p, (float*)workspace);
     OSR_CHECK_LAUNCH("osr_mask_loss_fwd");
     hipLaunchKernelGGL(mask_loss_final, dim3(1), dim3(64), 0, st, (const float*)workspace, p.mm, loss_weight, out6);
     OSR_CHECK_LAUNCH("osr_mask_loss_fwd(final)");
     return OSR_OK;
 }
 
-// foreground rows: one workgroup, so that the backward's normaliser is the forward's
-__global__ __launch_bounds__(MT_THREADS) void mask_loss_count_kernel(MaskLoss p, float* __restrict__ out) {
-    __shared__ int s_cnt[MT_THREADS];
-    int c = 0;
-    for (long long r = threadIdx.x; r < p.rows; r += MT_THREADS) c += mt_row_class(r, p.num_rows, p.classes, p.rows_valid, p.seg_rows) >= 0 ? 1 : 0;
-    s_cnt[threadIdx.x] = c;
-    __syncthreads();
-    for (int s = MT_THREADS / 2; s > 0; s >>= 1) {
-        if (threadIdx.x < s) s_cnt[threadIdx.x] += s_cnt[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[0] = (float)s_cnt[0];
-}
+// foreground rows for osr_loss_count_rows_kernel: the backward's normaliser is the forward's
+struct MaskRowIsForeground {
+    MaskLoss p;
+    __device__ bool operator()(long long r) const { return mt_row_class(r, p.num_rows, p.classes, p.rows_valid, p.seg_rows) >= 0; }
+};
 
 __global__ __launch_bounds__(MT_THREADS) void mask_loss_bwd_kernel(MaskLoss p, float scale, const float* __restrict__ count, float* __restrict__ d_logits) {
     const float s = scale / fmaxf(count[0] * (float)p.mm, 1.0f);
     const long long total = p.rows * p.mm;
     for (long long i = (long long)blockIdx.x * MT_THREADS + threadIdx.x; i < total; i += (long long)gridDim.x * MT_THREADS) {
         const bool fg = mt_row_class(i / p.mm, p.num_rows, p.classes, p.rows_valid, p.seg_rows) >= 0;
-        d_logits[i] = fg ? (mt_sigmoid(p.logits[i]) - (p.targets[i] ? 1.f : 0.f)) * s : 0.f;
+        d_logits[i] = fg ? (osr_sigmoid(p.logits[i]) - (p.targets[i] ? 1.f : 0.f)) * s : 0.f;
     }
 }
 
@@ -217,7 +173,7 @@ extern "C" osr_status osr_mask_loss_bwd(const float* logits, const uint8_t* targ
     OSR_REQUIRE(workspace_bytes >= 16, OSR_ERR_WORKSPACE, "osr_mask_loss_bwd: workspace needs 16 bytes");
     if (rows == 0) return OSR_OK;
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(mask_loss_count_kernel, dim3(1), dim3(MT_THREADS), 0, st, p, (float*)workspace);
+    hipLaunchKernelGGL(osr_loss_count_rows_kernel<MaskRowIsForeground>, dim3(1), dim3(256), 0, st, MaskRowIsForeground{p}, p.rows, (float*)workspace);
     OSR_CHECK_LAUNCH("osr_mask_loss_bwd(count)");
     const long long total = p.rows * p.mm;
     const unsigned blocks = (unsigned)((total + MT_THREADS - 1) / MT_THREADS < 4096 ? (total + MT_THREADS - 1) / MT_THREADS : 4096);
@@ -241,8 +197,6 @@ extern "C" osr_status osr_mask_loss_bwd(const float* logits, const uint8_t* targ
 // The column sums leave the workgroup as one partial per tile in a workspace; two small kernels reduce them in a fixed order
 // (per RoI, then per class): no atomics, repeats are bit-identical.
 // ------------------------------------------------------------------------------------------------------
-#include "osr_mask_mfma.h"
-
 #define MB_BM 64
 #define MB_GROW (64 * 2 + 16)  // bytes per row of a tap's g chunk in LDS: 64 storage elements + padding (16-byte aligned rows)
 #define MB_MAX_LDS (160 * 1024 - 1024)  // dynamic LDS the kernel may ask for: the CU's 160 KB less its static arrays

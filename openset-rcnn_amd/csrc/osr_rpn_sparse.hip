@@ -130,6 +130,19 @@ struct RsGeom {
     void* grad[OSR_MAX_LEVELS];
 };
 
+// the level-major row space of n images (the caller has checked 1 <= num_levels <= OSR_MAX_LEVELS); feat / grad stay null for the
+// caller to set. false: the offsets are not level-major and dense.
+static bool rs_geom_fill(const osr_rpn_levels* lv, int n, RsGeom* g) {
+    *g = RsGeom{};
+    g->nl = lv->num_levels; g->n = n;
+    for (int l = 0; l < g->nl; ++l) {
+        if (lv->offset[l] != (l == 0 ? 0 : lv->offset[l - 1] + (int64_t)n * lv->h[l - 1] * lv->w[l - 1])) return false;
+        g->h[l] = lv->h[l]; g->w[l] = lv->w[l]; g->off[l] = lv->offset[l];
+    }
+    g->off[g->nl] = g->off[g->nl - 1] + (long long)n * g->h[g->nl - 1] * g->w[g->nl - 1];
+    return true;
+}
+
 __device__ __forceinline__ void rs_decode(const RsGeom& g, long long r, int& l, int& img, int& y, int& x) {
     l = 0;
 #pragma unroll
@@ -169,15 +182,11 @@ static osr_status rs_gather_cols(const osr_rpn_levels* lv, const osr_pyramid* fe
     OSR_REQUIRE(lv->num_levels >= 1 && lv->num_levels <= OSR_MAX_LEVELS && lv->num_anchors == 1 && feats->num_levels == lv->num_levels && feats->c == 256,
                 OSR_ERR_UNSUPPORTED, "osr_rpn_gather_cols: one anchor per location, 256 channels, the same levels in both descriptions");
     OSR_REQUIRE(n >= 1 && cap >= 1 && width >= 1 && width <= 64, OSR_ERR_INVALID_ARG, "osr_rpn_gather_cols: bad n / cap / width");
-    RsGeom g{};
-    g.nl = lv->num_levels; g.n = n;
-    for (int l = 0; l < g.nl; ++l) {
+    RsGeom g;
+    for (int l = 0; l < lv->num_levels; ++l)
         OSR_REQUIRE(feats->h[l] == lv->h[l] && feats->w[l] == lv->w[l] && feats->data[l], OSR_ERR_INVALID_ARG, "osr_rpn_gather_cols: level %d disagrees", l);
-        OSR_REQUIRE(lv->offset[l] == (l == 0 ? 0 : lv->offset[l - 1] + (int64_t)n * lv->h[l - 1] * lv->w[l - 1]), OSR_ERR_INVALID_ARG,
-                    "osr_rpn_gather_cols: levels must be level-major and dense");
-        g.h[l] = lv->h[l]; g.w[l] = lv->w[l]; g.off[l] = lv->offset[l]; g.feat[l] = feats->data[l];
-    }
-    g.off[g.nl] = g.off[g.nl - 1] + (long long)n * g.h[g.nl - 1] * g.w[g.nl - 1];
+    OSR_REQUIRE(rs_geom_fill(lv, n, &g), OSR_ERR_INVALID_ARG, "osr_rpn_gather_cols: levels must be level-major and dense");
+    for (int l = 0; l < g.nl; ++l) g.feat[l] = feats->data[l];
     const long long waves = (long long)cap * 9;
     hipLaunchKernelGGL(rs_gather_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, (hipStream_t)stream, g, row_ids, cap, d_out5, width, (uint2*)cols, d_out5_rows);
     OSR_CHECK_LAUNCH("osr_rpn_gather_cols");
@@ -256,15 +265,10 @@ extern "C" osr_status osr_rpn_scatter_cols_add(const osr_rpn_levels* lv, int32_t
     OSR_REQUIRE(grad_dtype == OSR_F16 || grad_dtype == OSR_BF16, OSR_ERR_UNSUPPORTED, "osr_rpn_scatter_cols_add: 2-byte gradients only");
     OSR_REQUIRE(lv->num_levels >= 1 && lv->num_levels <= OSR_MAX_LEVELS && lv->num_anchors == 1 && n >= 1, OSR_ERR_UNSUPPORTED,
                 "osr_rpn_scatter_cols_add: one anchor per location");
-    RsGeom g{};
-    g.nl = lv->num_levels; g.n = n;
-    for (int l = 0; l < g.nl; ++l) {
-        OSR_REQUIRE(grads[l], OSR_ERR_INVALID_ARG, "osr_rpn_scatter_cols_add: level %d has no gradient tensor", l);
-        OSR_REQUIRE(lv->offset[l] == (l == 0 ? 0 : lv->offset[l - 1] + (int64_t)n * lv->h[l - 1] * lv->w[l - 1]), OSR_ERR_INVALID_ARG,
-                    "osr_rpn_scatter_cols_add: levels must be level-major and dense");
-        g.h[l] = lv->h[l]; g.w[l] = lv->w[l]; g.off[l] = lv->offset[l]; g.grad[l] = grads[l];
-    }
-    g.off[g.nl] = g.off[g.nl - 1] + (long long)n * g.h[g.nl - 1] * g.w[g.nl - 1];
+    RsGeom g;
+    for (int l = 0; l < lv->num_levels; ++l) OSR_REQUIRE(grads[l], OSR_ERR_INVALID_ARG, "osr_rpn_scatter_cols_add: level %d has no gradient tensor", l);
+    OSR_REQUIRE(rs_geom_fill(lv, n, &g), OSR_ERR_INVALID_ARG, "osr_rpn_scatter_cols_add: levels must be level-major and dense");
+    for (int l = 0; l < g.nl; ++l) g.grad[l] = grads[l];
     const long long blocks = (g.off[g.nl] + 255) / 256;
     hipStream_t st = (hipStream_t)stream;
     if (grad_dtype == OSR_F16) hipLaunchKernelGGL(rs_scatter_kernel<f16_t>, dim3((unsigned)blocks), dim3(256), 0, st, g, row_map, y);

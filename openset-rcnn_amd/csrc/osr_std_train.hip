@@ -10,99 +10,12 @@
 // -ffp-contract=off like the other loss kernels.
 #include "osr_common.h"
 #include "osr_box_loss.h"
-
-struct StdLevels {
-    int num_levels, num_anchors;
-    int w[OSR_MAX_LEVELS], stride[OSR_MAX_LEVELS];
-    long long pred_off[OSR_MAX_LEVELS];  // element offset of level l in the level-major (rows, A) logits
-    int aoff[OSR_MAX_LEVELS + 1];        // prefix of h*w*A inside one image's anchor list
-    int R;
-};
-
-static bool std_fill(const osr_rpn_levels* in, StdLevels* o) {
-    if (!in || in->num_levels < 1 || in->num_levels > OSR_MAX_LEVELS || in->num_anchors < 1 || in->num_anchors > 8) return false;
-    o->num_levels = in->num_levels; o->num_anchors = in->num_anchors;
-    long long a = 0;
-    for (int l = 0; l < in->num_levels; ++l) {
-        if (in->h[l] < 1 || in->w[l] < 1 || in->stride[l] < 1 || in->offset[l] % in->num_anchors != 0) return false;
-        o->w[l] = in->w[l]; o->stride[l] = in->stride[l]; o->pred_off[l] = in->offset[l];
-        o->aoff[l] = (int)a;
-        a += (long long)in->h[l] * in->w[l] * in->num_anchors;
-        if (a > (1ll << 30)) return false;
-    }
-    o->aoff[in->num_levels] = (int)a;
-    o->R = (int)a;
-    return true;
-}
-
-// anchor r of an image's list (level, y, x, a -- a minor) and its element index in the level-major prediction buffers
-__device__ __forceinline__ float4 std_anchor(const StdLevels& lv, const float* __restrict__ cell, int img, int r, long long* pi) {
-    int l = 0;
-    while (l + 1 < lv.num_levels && r >= lv.aoff[l + 1]) ++l;
-    const int idx = r - lv.aoff[l], A = lv.num_anchors, a = idx % A, c = idx / A;
-    const float sx = (float)(c % lv.w[l]) * (float)lv.stride[l], sy = (float)(c / lv.w[l]) * (float)lv.stride[l];
-    const float* ca = cell + ((long long)l * A + a) * 4;
-    *pi = lv.pred_off[l] + (long long)img * (lv.aoff[l + 1] - lv.aoff[l]) + idx;
-    return make_float4(sx + ca[0], sy + ca[1], sx + ca[2], sy + ca[3]);
-}
-
-// [d2] Box2BoxTransform.get_deltas(src, tgt) with weights (wx, wy, ww, wh)
-__device__ __forceinline__ float4 std_get_deltas(float4 s, float4 t, float wx, float wy, float ww, float wh) {
-    const float sw = s.z - s.x, sh = s.w - s.y, scx = s.x + 0.5f * sw, scy = s.y + 0.5f * sh;
-    const float tw = t.z - t.x, th = t.w - t.y, tcx = t.x + 0.5f * tw, tcy = t.y + 0.5f * th;
-    return make_float4(wx * (tcx - scx) / sw, wy * (tcy - scy) / sh, ww * logf(tw / sw), wh * logf(th / sh));
-}
-
-// F.binary_cross_entropy_with_logits in its stable form and its derivative w.r.t. x
-__device__ __forceinline__ float std_bce(float x, float y) { return fmaxf(x, 0.f) - x * y + log1pf(expf(-fabsf(x))); }
-__device__ __forceinline__ float std_bce_grad(float x, float y) {
-    const float e = expf(-fabsf(x)), sig = x >= 0.f ? 1.0f / (1.0f + e) : e / (1.0f + e);
-    return sig - y;
-}
-
-#define STD_RED_BLOCKS 256
-#define STD_MAXV 8
-
-template <int NV>
-__device__ __forceinline__ void std_block_reduce_store(float v[NV], float* __restrict__ partial /* [gridDim.x][NV] */) {
-    __shared__ float s_red[NV][4];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-#pragma unroll
-    for (int q = 0; q < NV; ++q) {
-        float x = v[q];
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) x += __shfl_down(x, d, 64);
-        if (lane == 0) s_red[q][wid] = x;
-    }
-    __syncthreads();
-    if (threadIdx.x < NV) partial[(long long)blockIdx.x * NV + threadIdx.x] = s_red[threadIdx.x][0] + s_red[threadIdx.x][1] + s_red[threadIdx.x][2] + s_red[threadIdx.x][3];
-}
-
-struct StdScale { float s[STD_MAXV]; };
-
-__device__ __forceinline__ float std_column_sum(const float* __restrict__ partial, int nv, int q) {
-    const int lane = threadIdx.x & 63;
-    float x = 0.f;
-    for (int b = lane; b < STD_RED_BLOCKS; b += 64) x += partial[(long long)b * nv + q];
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) x += __shfl_down(x, d, 64);
-    return __shfl(x, 0, 64);
-}
-
-// out[q] = scale[q] * column sum q; with norm_col >= 0 the columns q < norm_col are also divided by max(column norm_col, 1)
-__global__ __launch_bounds__(64) void std_final_reduce(const float* __restrict__ partial, int nv, StdScale scale, int norm_col, float* __restrict__ out) {
-    const float c = norm_col >= 0 ? std_column_sum(partial, nv, norm_col) : 1.0f;
-    for (int q = 0; q < nv; ++q) {
-        float x = std_column_sum(partial, nv, q);
-        if (norm_col >= 0 && q < norm_col) x = x / fmaxf(c, 1.0f);
-        if (threadIdx.x == 0) out[q] = x * scale.s[q];
-    }
-}
+#include "osr_loss_common.h"
 
 // ------------------------------------------------------------------------------------------------------
 // [d2] RPN.losses, forward: {loss_rpn_cls, loss_rpn_loc, num_pos, num_neg}
 // ------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void std_rpn_losses_kernel(StdLevels lv, const float* __restrict__ cell, int n, const float* __restrict__ logits,
+__global__ __launch_bounds__(256) void std_rpn_losses_kernel(OsrLossLevels lv, const float* __restrict__ cell, int n, const float* __restrict__ logits,
                                                              const float* __restrict__ deltas, const signed char* __restrict__ labels,
                                                              const float* __restrict__ matched, float4 bw, float beta, float* __restrict__ partial) {
     float v[4] = {0.f, 0.f, 0.f, 0.f};
@@ -111,24 +24,25 @@ __global__ __launch_bounds__(256) void std_rpn_losses_kernel(StdLevels lv, const
         const signed char lb = labels[i];
         if (lb < 0) continue;
         const int img = (int)(i / lv.R), r = (int)(i - (long long)img * lv.R);
-        long long pi;
-        const float4 a = std_anchor(lv, cell, img, r, &pi);
-        v[0] += std_bce(logits[pi], (float)lb);
+        int l, ci;
+        const float4 a = osr_loss_anchor(lv, cell, r, &l, &ci);
+        const long long pi = osr_loss_pred_index(lv, l, img, ci);
+        v[0] += osr_bce_with_logits(logits[pi], (float)lb);
         if (lb == 1) {
             v[2] += 1.f;
-            const float4 t = std_get_deltas(a, *reinterpret_cast<const float4*>(matched + i * 4), bw.x, bw.y, bw.z, bw.w);
+            const float4 t = osr_b2b_get_deltas(a, *reinterpret_cast<const float4*>(matched + i * 4), bw.x, bw.y, bw.z, bw.w);
             const float4 d = *reinterpret_cast<const float4*>(deltas + pi * 4);
             v[1] += osr_smooth_l1(d.x - t.x, beta) + osr_smooth_l1(d.y - t.y, beta) + osr_smooth_l1(d.z - t.z, beta) + osr_smooth_l1(d.w - t.w, beta);
         } else {
             v[3] += 1.f;
         }
     }
-    std_block_reduce_store<4>(v, partial);
+    osr_loss_block_reduce_store<4>(v, partial);
 }
 
-static const char* std_rpn_check(const osr_rpn_levels* lvl, StdLevels* lv, const float* cell, const float* logits, const float* deltas,
+static const char* std_rpn_check(const osr_rpn_levels* lvl, OsrLossLevels* lv, const float* cell, const float* logits, const float* deltas,
                                  const int8_t* labels, const float* matched, const float* bw, int n, int batch, float beta) {
-    if (!std_fill(lvl, lv)) return "bad level table (1 <= A <= 8, offsets in whole pixels)";
+    if (!osr_loss_levels_fill(lvl, lv) || !osr_loss_levels_whole_pixels(lvl, 8)) return "bad level table (1 <= A <= 8, offsets in whole pixels)";
     if (!cell || !logits || !deltas || !labels || !matched || !bw) return "null pointer";
     if (n < 1 || batch < 1 || !(beta >= 0.f)) return "bad n / batch size / beta";
     if ((((uintptr_t)deltas | (uintptr_t)matched) & 15) != 0) return "deltas and matched boxes must be 16-byte aligned";
@@ -139,27 +53,27 @@ extern "C" osr_status osr_std_rpn_losses_fwd(const osr_rpn_levels* lvl, const fl
                                              const float* pred_deltas, const int8_t* labels, const float* matched_boxes, const float b2b_weights[4],
                                              float smooth_l1_beta, float cls_weight, float loc_weight, int32_t batch_size_per_image, float* out4,
                                              void* workspace, int64_t workspace_bytes, void* stream) {
-    StdLevels lv;
+    OsrLossLevels lv;
     const char* bad = std_rpn_check(lvl, &lv, cell_anchors, pred_logits, pred_deltas, labels, matched_boxes, b2b_weights, n, batch_size_per_image,
                                     smooth_l1_beta);
     OSR_REQUIRE(!bad, OSR_ERR_INVALID_ARG, "osr_std_rpn_losses_fwd: %s", bad ? bad : "");
     OSR_REQUIRE(out4 && workspace, OSR_ERR_INVALID_ARG, "osr_std_rpn_losses_fwd: null pointer");
-    OSR_REQUIRE(workspace_bytes >= (int64_t)STD_RED_BLOCKS * 4 * 4, OSR_ERR_WORKSPACE, "osr_std_rpn_losses_fwd: workspace needs %d bytes", STD_RED_BLOCKS * 16);
+    OSR_REQUIRE(workspace_bytes >= (int64_t)OSR_LOSS_RED_BLOCKS * 4 * 4, OSR_ERR_WORKSPACE, "osr_std_rpn_losses_fwd: workspace needs %d bytes", OSR_LOSS_RED_BLOCKS * 16);
     hipStream_t st = (hipStream_t)stream;
     float* partial = (float*)workspace;
     const float norm = (float)batch_size_per_image * (float)n;
-    const StdScale scale = {{cls_weight / norm, loc_weight / norm, 1.f, 1.f, 0.f, 0.f, 0.f, 0.f}};
-    hipLaunchKernelGGL(std_rpn_losses_kernel, dim3(STD_RED_BLOCKS), dim3(256), 0, st, lv, cell_anchors, n, pred_logits, pred_deltas,
+    const OsrLossScale scale = {{cls_weight / norm, loc_weight / norm, 1.f, 1.f, 0.f, 0.f, 0.f, 0.f}};
+    hipLaunchKernelGGL(std_rpn_losses_kernel, dim3(OSR_LOSS_RED_BLOCKS), dim3(256), 0, st, lv, cell_anchors, n, pred_logits, pred_deltas,
                        (const signed char*)labels, matched_boxes, make_float4(b2b_weights[0], b2b_weights[1], b2b_weights[2], b2b_weights[3]),
                        smooth_l1_beta, partial);
     OSR_CHECK_LAUNCH("osr_std_rpn_losses_fwd");
-    hipLaunchKernelGGL(std_final_reduce, dim3(1), dim3(64), 0, st, partial, 4, scale, -1, out4);
+    hipLaunchKernelGGL(osr_loss_final_reduce, dim3(1), dim3(64), 0, st, partial, OSR_LOSS_RED_BLOCKS, 4, scale, -1, out4);
     OSR_CHECK_LAUNCH("osr_std_rpn_losses_fwd(final)");
     return OSR_OK;
 }
 
 // backward: every anchor writes its A-column logit gradient and its four delta gradients into d_rows (pixel rows, 5A columns)
-__global__ __launch_bounds__(256) void std_rpn_losses_bwd_kernel(StdLevels lv, const float* __restrict__ cell, int n, const float* __restrict__ logits,
+__global__ __launch_bounds__(256) void std_rpn_losses_bwd_kernel(OsrLossLevels lv, const float* __restrict__ cell, int n, const float* __restrict__ logits,
                                                                  const float* __restrict__ deltas, const signed char* __restrict__ labels,
                                                                  const float* __restrict__ matched, float4 bw, float beta, float s_cls, float s_loc,
                                                                  float* __restrict__ d_rows) {
@@ -168,19 +82,20 @@ __global__ __launch_bounds__(256) void std_rpn_losses_bwd_kernel(StdLevels lv, c
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
         const int img = (int)(i / lv.R), r = (int)(i - (long long)img * lv.R);
         const signed char lb = labels[i];
-        long long pi;
-        const float4 a = std_anchor(lv, cell, img, r, &pi);
+        int l, ci;
+        const float4 a = osr_loss_anchor(lv, cell, r, &l, &ci);
+        const long long pi = osr_loss_pred_index(lv, l, img, ci);
         const long long row = pi / A;
         const int ai = (int)(pi - row * A);
         float* d = d_rows + row * W;
         float g[4] = {0.f, 0.f, 0.f, 0.f};
         if (lb == 1) {
-            const float4 t = std_get_deltas(a, *reinterpret_cast<const float4*>(matched + i * 4), bw.x, bw.y, bw.z, bw.w);
+            const float4 t = osr_b2b_get_deltas(a, *reinterpret_cast<const float4*>(matched + i * 4), bw.x, bw.y, bw.z, bw.w);
             const float4 p = *reinterpret_cast<const float4*>(deltas + pi * 4);
             g[0] = s_loc * osr_smooth_l1_grad(p.x - t.x, beta); g[1] = s_loc * osr_smooth_l1_grad(p.y - t.y, beta);
             g[2] = s_loc * osr_smooth_l1_grad(p.z - t.z, beta); g[3] = s_loc * osr_smooth_l1_grad(p.w - t.w, beta);
         }
-        d[ai] = lb >= 0 ? s_cls * std_bce_grad(logits[pi], (float)lb) : 0.f;
+        d[ai] = lb >= 0 ? s_cls * osr_bce_with_logits_grad(logits[pi], (float)lb) : 0.f;
         // (row stride 5A floats: not 16-byte aligned for A = 3)
         d[A + 4 * ai] = g[0]; d[A + 4 * ai + 1] = g[1]; d[A + 4 * ai + 2] = g[2]; d[A + 4 * ai + 3] = g[3];
     }
@@ -190,7 +105,7 @@ extern "C" osr_status osr_std_rpn_losses_bwd(const osr_rpn_levels* lvl, const fl
                                              const float* pred_deltas, const int8_t* labels, const float* matched_boxes, const float b2b_weights[4],
                                              float smooth_l1_beta, float cls_weight, float loc_weight, int32_t batch_size_per_image, float loss_scale,
                                              float* d_rows, void* stream) {
-    StdLevels lv;
+    OsrLossLevels lv;
     const char* bad = std_rpn_check(lvl, &lv, cell_anchors, pred_logits, pred_deltas, labels, matched_boxes, b2b_weights, n, batch_size_per_image,
                                     smooth_l1_beta);
     OSR_REQUIRE(!bad, OSR_ERR_INVALID_ARG, "osr_std_rpn_losses_bwd: %s", bad ? bad : "");
@@ -234,9 +149,8 @@ __global__ __launch_bounds__(256) void fastrcnn_losses_kernel(StdRoi p, float* _
         float mx = lg[0];
         int arg = 0;
         for (int j = 1; j < nc; ++j)
-            if (lg[j] > mx) { mx = lg[j]; arg = j; }  // (first maximum, as torch.argmax)
-        float sum = 0.f;
-        for (int j = 0; j < nc; ++j) sum += expf(lg[j] - mx);
+            if (lg[j] > mx) { mx = lg[j]; arg = j; }  // (first maximum, as torch.argmax; not osr_softmax_row's fmaxf: they differ on a NaN logit)
+        const float sum = osr_softmax_sum(lg, nc, mx);
         v[0] += logf(sum) + mx - lg[c];
         v[2] += 1.f;
         v[3] += arg == c ? 1.f : 0.f;
@@ -244,11 +158,11 @@ __global__ __launch_bounds__(256) void fastrcnn_losses_kernel(StdRoi p, float* _
         v[4] += 1.f;
         v[5] += arg == c ? 1.f : 0.f;
         v[6] += arg == p.K ? 1.f : 0.f;
-        const float4 t = std_get_deltas(*reinterpret_cast<const float4*>(p.prop + i * 4), *reinterpret_cast<const float4*>(p.gtb + i * 4), p.wx, p.wy, p.ww, p.wh);
+        const float4 t = osr_b2b_get_deltas(*reinterpret_cast<const float4*>(p.prop + i * 4), *reinterpret_cast<const float4*>(p.gtb + i * 4), p.wx, p.wy, p.ww, p.wh);
         const float* d = std_roi_delta(p, i, c);
         v[1] += osr_smooth_l1(d[0] - t.x, p.beta) + osr_smooth_l1(d[1] - t.y, p.beta) + osr_smooth_l1(d[2] - t.z, p.beta) + osr_smooth_l1(d[3] - t.w, p.beta);
     }
-    std_block_reduce_store<7>(v, partial);
+    osr_loss_block_reduce_store<7>(v, partial);
 }
 
 static const char* std_roi_fill(StdRoi* p, const float* logits, const float* deltas, int32_t delta_stride, int32_t agnostic, const float* prop,
@@ -271,29 +185,21 @@ extern "C" osr_status osr_fastrcnn_losses_fwd(const float* logits, const float* 
                                    smooth_l1_beta);
     OSR_REQUIRE(!bad, OSR_ERR_INVALID_ARG, "osr_fastrcnn_losses_fwd: %s", bad ? bad : "");
     OSR_REQUIRE(out7 && workspace, OSR_ERR_INVALID_ARG, "osr_fastrcnn_losses_fwd: null pointer");
-    OSR_REQUIRE(workspace_bytes >= (int64_t)STD_RED_BLOCKS * 7 * 4, OSR_ERR_WORKSPACE, "osr_fastrcnn_losses_fwd: workspace needs %d bytes", STD_RED_BLOCKS * 28);
+    OSR_REQUIRE(workspace_bytes >= (int64_t)OSR_LOSS_RED_BLOCKS * 7 * 4, OSR_ERR_WORKSPACE, "osr_fastrcnn_losses_fwd: workspace needs %d bytes", OSR_LOSS_RED_BLOCKS * 28);
     hipStream_t st = (hipStream_t)stream;
-    const StdScale scale = {{cls_weight, box_weight, 1.f, 1.f, 1.f, 1.f, 1.f, 0.f}};
-    hipLaunchKernelGGL(fastrcnn_losses_kernel, dim3(STD_RED_BLOCKS), dim3(256), 0, st, p, (float*)workspace);
+    const OsrLossScale scale = {{cls_weight, box_weight, 1.f, 1.f, 1.f, 1.f, 1.f, 0.f}};
+    hipLaunchKernelGGL(fastrcnn_losses_kernel, dim3(OSR_LOSS_RED_BLOCKS), dim3(256), 0, st, p, (float*)workspace);
     OSR_CHECK_LAUNCH("osr_fastrcnn_losses_fwd");
-    hipLaunchKernelGGL(std_final_reduce, dim3(1), dim3(64), 0, st, (const float*)workspace, 7, scale, 2, out7);
+    hipLaunchKernelGGL(osr_loss_final_reduce, dim3(1), dim3(64), 0, st, (const float*)workspace, OSR_LOSS_RED_BLOCKS, 7, scale, 2, out7);
     OSR_CHECK_LAUNCH("osr_fastrcnn_losses_fwd(final)");
     return OSR_OK;
 }
 
-// rows that count (class >= 0): one workgroup, so that the backward's normaliser is the forward's
-__global__ __launch_bounds__(256) void fastrcnn_count_kernel(StdRoi p, float* __restrict__ out) {
-    __shared__ int s_cnt[256];
-    int c = 0;
-    for (long long i = threadIdx.x; i < p.m; i += blockDim.x) c += std_roi_target(p, i) >= 0 ? 1 : 0;
-    s_cnt[threadIdx.x] = c;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (threadIdx.x < s) s_cnt[threadIdx.x] += s_cnt[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[0] = (float)s_cnt[0];
-}
+// rows that count (class in 0..K) for osr_loss_count_rows_kernel: the backward's normaliser is the forward's
+struct StdRoiHasTarget {
+    StdRoi p;
+    __device__ bool operator()(long long i) const { return std_roi_target(p, i) >= 0; }
+};
 
 __global__ __launch_bounds__(256) void fastrcnn_losses_bwd_kernel(StdRoi p, float s_cls, float s_box, const float* __restrict__ count,
                                                                   float* __restrict__ d_logits, float* __restrict__ d_deltas) {
@@ -309,13 +215,11 @@ __global__ __launch_bounds__(256) void fastrcnn_losses_bwd_kernel(StdRoi p, floa
             continue;
         }
         const float* lg = p.logits + i * nc;
-        float mx = lg[0];
-        for (int j = 1; j < nc; ++j) mx = fmaxf(mx, lg[j]);
-        float sum = 0.f;
-        for (int j = 0; j < nc; ++j) sum += expf(lg[j] - mx);
+        float sum;
+        const float mx = osr_softmax_row(lg, nc, &sum);
         for (int j = 0; j < nc; ++j) dl[j] = (expf(lg[j] - mx) / sum - (j == c ? 1.f : 0.f)) * s_cls * inv;
         if (c == p.K) continue;
-        const float4 t = std_get_deltas(*reinterpret_cast<const float4*>(p.prop + i * 4), *reinterpret_cast<const float4*>(p.gtb + i * 4), p.wx, p.wy, p.ww, p.wh);
+        const float4 t = osr_b2b_get_deltas(*reinterpret_cast<const float4*>(p.prop + i * 4), *reinterpret_cast<const float4*>(p.gtb + i * 4), p.wx, p.wy, p.ww, p.wh);
         const float* d = std_roi_delta(p, i, c);
         float* g = dd + (p.agnostic ? 0 : 4 * c);
         g[0] = s_box * inv * osr_smooth_l1_grad(d[0] - t.x, p.beta); g[1] = s_box * inv * osr_smooth_l1_grad(d[1] - t.y, p.beta);
@@ -336,7 +240,7 @@ extern "C" osr_status osr_fastrcnn_losses_bwd(const float* logits, const float* 
     OSR_REQUIRE(workspace_bytes >= 16, OSR_ERR_WORKSPACE, "osr_fastrcnn_losses_bwd: workspace needs 16 bytes");
     if (m == 0) return OSR_OK;
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(fastrcnn_count_kernel, dim3(1), dim3(256), 0, st, p, (float*)workspace);
+    hipLaunchKernelGGL(osr_loss_count_rows_kernel<StdRoiHasTarget>, dim3(1), dim3(256), 0, st, StdRoiHasTarget{p}, p.m, (float*)workspace);
     OSR_CHECK_LAUNCH("osr_fastrcnn_losses_bwd(count)");
     const unsigned blocks = (unsigned)((m + 255) / 256);
     hipLaunchKernelGGL(fastrcnn_losses_bwd_kernel, dim3(blocks), dim3(256), 0, st, p, loss_scale * cls_weight, loss_scale * box_weight,

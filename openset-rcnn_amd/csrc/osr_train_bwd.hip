@@ -7,45 +7,14 @@
 // Reductions over rows are two-stage and fixed-order: results are bitwise reproducible.
 #include "osr_common.h"
 #include "osr_box_loss.h"
+#include "osr_loss_common.h"
 #include "osr_pln_dist.h"
-
-struct TbLevels {
-    int num_levels, num_anchors;
-    int h[OSR_MAX_LEVELS], w[OSR_MAX_LEVELS], stride[OSR_MAX_LEVELS];
-    long long pred_off[OSR_MAX_LEVELS];
-    int aoff[OSR_MAX_LEVELS + 1];
-    int R;
-};
-static bool tb_fill(const osr_rpn_levels* in, TbLevels* o) {
-    if (!in || in->num_levels < 1 || in->num_levels > OSR_MAX_LEVELS || in->num_anchors < 1) return false;
-    o->num_levels = in->num_levels; o->num_anchors = in->num_anchors;
-    long long a = 0;
-    for (int l = 0; l < in->num_levels; ++l) {
-        if (in->h[l] < 1 || in->w[l] < 1 || in->stride[l] < 1) return false;
-        o->h[l] = in->h[l]; o->w[l] = in->w[l]; o->stride[l] = in->stride[l]; o->pred_off[l] = in->offset[l];
-        o->aoff[l] = (int)a;
-        a += (long long)in->h[l] * in->w[l] * in->num_anchors;
-        if (a > (1ll << 30)) return false;
-    }
-    o->aoff[in->num_levels] = (int)a;
-    o->R = (int)a;
-    return true;
-}
-__device__ __forceinline__ float4 tb_anchor(const TbLevels& lv, const float* __restrict__ cell, int r, int* level, int* cell_idx) {
-    int l = 0;
-    while (l + 1 < lv.num_levels && r >= lv.aoff[l + 1]) ++l;
-    const int idx = r - lv.aoff[l], A = lv.num_anchors, a = idx % A, c = idx / A;
-    const float sx = (float)(c % lv.w[l]) * (float)lv.stride[l], sy = (float)(c / lv.w[l]) * (float)lv.stride[l];
-    const float* ca = cell + ((long long)l * A + a) * 4;
-    *level = l; *cell_idx = idx;
-    return make_float4(sx + ca[0], sy + ca[1], sx + ca[2], sy + ca[3]);
-}
 
 // ------------------------------------------------------------------------------------------------------
 // ClsFreeRPN.losses backward: gradient w.r.t. the head's five pre-activation outputs per anchor
 // (ltrb deltas, centerness logit). out5 is level-major like the predictions; every row is written.
 // ------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void rpn_losses_bwd_kernel(TbLevels lv, const float* __restrict__ cell, int n, const float* __restrict__ pred_deltas,
+__global__ __launch_bounds__(256) void rpn_losses_bwd_kernel(OsrLossLevels lv, const float* __restrict__ cell, int n, const float* __restrict__ pred_deltas,
                                                              const float* __restrict__ pred_ctr, const signed char* __restrict__ labels_reg,
                                                              const signed char* __restrict__ labels_obj, const float* __restrict__ matched_boxes,
                                                              const float* __restrict__ ctr_target, float s_loc, float s_ctr, int box_type, float box_beta,
@@ -54,8 +23,8 @@ __global__ __launch_bounds__(256) void rpn_losses_bwd_kernel(TbLevels lv, const 
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
         const int img = (int)(i / lv.R), r = (int)(i - (long long)img * lv.R);
         int l, ci;
-        const float4 a = tb_anchor(lv, cell, r, &l, &ci);
-        const long long pi = lv.pred_off[l] + (long long)img * (lv.aoff[l + 1] - lv.aoff[l]) + ci;
+        const float4 a = osr_loss_anchor(lv, cell, r, &l, &ci);
+        const long long pi = osr_loss_pred_index(lv, l, img, ci);
         float g[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
         const signed char lr = labels_reg[i], lo = labels_obj[i];
         if (lr == 1) {
@@ -93,8 +62,8 @@ extern "C" osr_status osr_rpn_losses_bwd_ex(const osr_rpn_levels* lvl, const flo
     const float box_beta = opt ? opt->box_smooth_l1_beta : 0.f, ctr_beta = opt ? opt->aux_smooth_l1_beta : 0.f;
     OSR_REQUIRE(box_type >= OSR_LOSS_IOU && box_type <= OSR_LOSS_CIOU && box_beta >= 0.f && ctr_beta >= 0.f, OSR_ERR_INVALID_ARG,
                 "osr_rpn_losses_bwd: bad loss options (type %d)", box_type);
-    TbLevels lv;
-    OSR_REQUIRE(tb_fill(lvl, &lv), OSR_ERR_INVALID_ARG, "osr_rpn_losses_bwd: bad level table");
+    OsrLossLevels lv;
+    OSR_REQUIRE(osr_loss_levels_fill(lvl, &lv), OSR_ERR_INVALID_ARG, "osr_rpn_losses_bwd: bad level table");
     OSR_REQUIRE(cell_anchors && pred_deltas && pred_ctr && labels_reg && labels_obj && matched_boxes && ctr_target && d_out5, OSR_ERR_INVALID_ARG,
                 "osr_rpn_losses_bwd: null pointer");
     OSR_REQUIRE(n >= 1 && batch_size_per_image >= 1, OSR_ERR_INVALID_ARG, "osr_rpn_losses_bwd: bad n / batch size");
@@ -236,18 +205,10 @@ extern "C" osr_status osr_cfrpn_tail_bwd(const void* t, int32_t dtype, int64_t r
 // RoI-head losses backward
 // ------------------------------------------------------------------------------------------------------
 // rows counted = rows with class >= 0 (as in the forward); one tiny kernel counts them so that both passes agree
-__global__ void count_rows_kernel(const long long* __restrict__ cls, long long m, int lo, int hi_excl, float* __restrict__ out) {
-    __shared__ int s_cnt[256];
-    int c = 0;
-    for (long long i = threadIdx.x; i < m; i += blockDim.x) c += (cls[i] >= lo && (hi_excl < 0 || cls[i] < hi_excl)) ? 1 : 0;
-    s_cnt[threadIdx.x] = c;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (threadIdx.x < s) s_cnt[threadIdx.x] += s_cnt[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[0] = (float)s_cnt[0];
-}
+struct ClassInRange {  // lo <= class, and class < hi_excl unless hi_excl < 0
+    const long long* cls; int lo, hi_excl;
+    __device__ bool operator()(long long i) const { return cls[i] >= lo && (hi_excl < 0 || cls[i] < hi_excl); }
+};
 
 __global__ __launch_bounds__(256) void roi_box_losses_bwd_kernel(const float* __restrict__ pred, int pstride, const float* __restrict__ prop,
                                                                  const float* __restrict__ gtb, const long long* __restrict__ cls,
@@ -261,23 +222,19 @@ __global__ __launch_bounds__(256) void roi_box_losses_bwd_kernel(const float* __
         if (c >= 0 && c < num_classes) {
             const float4 s = *reinterpret_cast<const float4*>(prop + i * 4), t = *reinterpret_cast<const float4*>(gtb + i * 4);
             const float* d = pred + i * pstride;
-            const float sw = s.z - s.x, sh = s.w - s.y, scx = s.x + 0.5f * sw, scy = s.y + 0.5f * sh;
-            const float tw = t.z - t.x, th = t.w - t.y, tcx = t.x + 0.5f * tw, tcy = t.y + 0.5f * th;
             if (box_type == OSR_LOSS_SMOOTH_L1) {
-                const float tg[4] = {wx * (tcx - scx) / sw, wy * (tcy - scy) / sh, ww * logf(tw / sw), wh * logf(th / sh)};
+                const float4 t4 = osr_b2b_get_deltas(s, t, wx, wy, ww, wh);
+                const float tg[4] = {t4.x, t4.y, t4.z, t4.w};
 #pragma unroll
                 for (int q = 0; q < 4; ++q) g[q] = osr_smooth_l1_grad(d[q] - tg[q], box_beta) * s_box / r;
-            } else {  // through [d2] Box2BoxTransform.apply_deltas: centre = d/w * size + centre, size = exp(min(d/w, clamp)) * size
-                const float kClamp = 4.135166556742356f;
-                const float ew = d[2] / ww, eh = d[3] / wh;
-                const float pw = expf(fminf(ew, kClamp)) * sw, ph = expf(fminf(eh, kClamp)) * sh;
-                const float pcx = d[0] / wx * sw + scx, pcy = d[1] / wy * sh + scy;
-                float dp[4];
-                (void)osr_box_loss<true>(box_type, make_float4(pcx - 0.5f * pw, pcy - 0.5f * ph, pcx + 0.5f * pw, pcy + 0.5f * ph), t, dp);
+            } else {  // through the decoded box: centre = d/w * size + centre, size = exp(min(d/w, clamp)) * size
+                const float sw = s.z - s.x, sh = s.w - s.y;
+                float pw, ph, dp[4];
+                (void)osr_box_loss<true>(box_type, osr_b2b_apply_deltas(s, d, wx, wy, ww, wh, &pw, &ph), t, dp);
                 g[0] = (dp[0] + dp[2]) * sw / wx * s_box / r;
                 g[1] = (dp[1] + dp[3]) * sh / wy * s_box / r;
-                g[2] = ew < kClamp ? 0.5f * (dp[2] - dp[0]) * pw / ww * s_box / r : 0.f;
-                g[3] = eh < kClamp ? 0.5f * (dp[3] - dp[1]) * ph / wh * s_box / r : 0.f;
+                g[2] = d[2] / ww < OSR_B2B_SCALE_CLAMP ? 0.5f * (dp[2] - dp[0]) * pw / ww * s_box / r : 0.f;
+                g[3] = d[3] / wh < OSR_B2B_SCALE_CLAMP ? 0.5f * (dp[3] - dp[1]) * ph / wh * s_box / r : 0.f;
             }
             const float sg = 1.0f / (1.0f + expf(-d[4]));
             g[4] = osr_smooth_l1_grad(sg - gt_iou[i], iou_beta) * sg * (1.f - sg) * s_iou / r;
@@ -299,7 +256,7 @@ extern "C" osr_status osr_roi_box_losses_bwd_ex(const float* pred5, const float*
                 "osr_roi_box_losses_bwd: null pointer");
     OSR_REQUIRE(m >= 1 && workspace_bytes >= 16, OSR_ERR_INVALID_ARG, "osr_roi_box_losses_bwd: bad m / workspace (16 bytes)");
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(count_rows_kernel, dim3(1), dim3(256), 0, st, (const long long*)gt_classes, (long long)m, 0, -1, (float*)workspace);
+    hipLaunchKernelGGL(osr_loss_count_rows_kernel<ClassInRange>, dim3(1), dim3(256), 0, st, ClassInRange{(const long long*)gt_classes, 0, -1}, (long long)m, (float*)workspace);
     OSR_CHECK_LAUNCH("osr_roi_box_losses_bwd(count)");
     hipLaunchKernelGGL(roi_box_losses_bwd_kernel, dim3(256), dim3(256), 0, st, pred5, 5, proposal_boxes, gt_boxes, (const long long*)gt_classes, gt_iou, (long long)m,
                        num_classes, reg_weights[0], reg_weights[1], reg_weights[2], reg_weights[3], loss_scale * box_weight, loss_scale * iou_weight,
@@ -316,21 +273,10 @@ extern "C" osr_status osr_roi_box_losses_bwd(const float* pred5, const float* pr
 }
 
 // softmax cross entropy: d logits = (softmax - onehot) * weight / count over the rows with a valid target
-__global__ __launch_bounds__(256) void ce_count_kernel(const long long* __restrict__ cls, long long m, int num_classes, int K, float* __restrict__ out) {
-    __shared__ int s_cnt[256];
-    int c = 0;
-    for (long long i = threadIdx.x; i < m; i += blockDim.x) {
-        const long long v = cls[i];
-        c += ((v >= 0 && v < K) || v == num_classes) ? 1 : 0;
-    }
-    s_cnt[threadIdx.x] = c;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (threadIdx.x < s) s_cnt[threadIdx.x] += s_cnt[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[0] = (float)s_cnt[0];
-}
+struct CeHasTarget {  // known class or background (the rows id_map keeps)
+    const long long* cls; int num_classes, K;
+    __device__ bool operator()(long long i) const { const long long v = cls[i]; return (v >= 0 && v < K) || v == num_classes; }
+};
 
 __global__ __launch_bounds__(256) void ce_bwd_kernel(const float* __restrict__ logits, long long m, int nc, const long long* __restrict__ cls, int num_classes,
                                                      int K, float s, const float* __restrict__ count, float* __restrict__ d_logits) {
@@ -344,10 +290,8 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(const float* __restrict__ l
             continue;
         }
         const float* lg = logits + i * nc;
-        float mx = lg[0];
-        for (int j = 1; j < nc; ++j) mx = fmaxf(mx, lg[j]);
-        float sum = 0.f;
-        for (int j = 0; j < nc; ++j) sum += expf(lg[j] - mx);
+        float sum;
+        const float mx = osr_softmax_row(lg, nc, &sum);
         for (int j = 0; j < nc; ++j) dl[j] = (expf(lg[j] - mx) / sum - (j == t ? 1.f : 0.f)) * s / cnt;
     }
 }
@@ -357,7 +301,8 @@ extern "C" osr_status osr_softmax_ce_loss_bwd(const float* logits, int64_t m, in
     OSR_REQUIRE(logits && gt_classes && d_logits && workspace, OSR_ERR_INVALID_ARG, "osr_softmax_ce_loss_bwd: null pointer");
     OSR_REQUIRE(m >= 1 && num_known >= 1 && workspace_bytes >= 16, OSR_ERR_INVALID_ARG, "osr_softmax_ce_loss_bwd: bad sizes / workspace (16 bytes)");
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(ce_count_kernel, dim3(1), dim3(256), 0, st, (const long long*)gt_classes, (long long)m, num_classes, num_known, (float*)workspace);
+    hipLaunchKernelGGL(osr_loss_count_rows_kernel<CeHasTarget>, dim3(1), dim3(256), 0, st, CeHasTarget{(const long long*)gt_classes, num_classes, num_known}, (long long)m,
+                       (float*)workspace);
     OSR_CHECK_LAUNCH("osr_softmax_ce_loss_bwd(count)");
     hipLaunchKernelGGL(ce_bwd_kernel, dim3(256), dim3(256), 0, st, logits, (long long)m, num_known + 1, (const long long*)gt_classes, num_classes, num_known,
                        loss_scale * loss_weight, (const float*)workspace, d_logits);
@@ -638,7 +583,7 @@ extern "C" osr_status osr_pln_loss_bwd_ex(const float* emb, int64_t m, int32_t d
     float* pair_coef = (float*)((char*)workspace + 16 + m * 8);
     float* row_inv = (float*)((char*)workspace + 16 + m * 16);
     float* pair_dist = (float*)((char*)workspace + 16 + m * 20);
-    hipLaunchKernelGGL(count_rows_kernel, dim3(1), dim3(256), 0, st, (const long long*)gt_classes, (long long)m, 0, -1, rows);
+    hipLaunchKernelGGL(osr_loss_count_rows_kernel<ClassInRange>, dim3(1), dim3(256), 0, st, ClassInRange{(const long long*)gt_classes, 0, -1}, (long long)m, rows);
     OSR_CHECK_LAUNCH("osr_pln_loss_bwd(count)");
     const float s = loss_scale * loss_weight;
     const size_t smem_rows = (size_t)kr * d * 4, smem_protos = (size_t)(kr * d + 3 * kr + d) * 4;

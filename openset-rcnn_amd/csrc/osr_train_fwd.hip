@@ -12,43 +12,10 @@
 // reproducible run to run. Compile with -ffp-contract=off (labels / sampled index lists must be bit-exact).
 #include "osr_common.h"
 #include "osr_box_loss.h"
+#include "osr_loss_common.h"
 #include "osr_pln_dist.h"
 static_assert(OSR_LOSS_IOU == OSR_BOX_LOSS_IOU && OSR_LOSS_SMOOTH_L1 == OSR_BOX_LOSS_SMOOTH_L1 && OSR_LOSS_GIOU == OSR_BOX_LOSS_GIOU &&
                   OSR_LOSS_DIOU == OSR_BOX_LOSS_DIOU && OSR_LOSS_CIOU == OSR_BOX_LOSS_CIOU, "osr_box_loss.h and include/osr.h number the losses alike");
-
-struct TrLevels {
-    int num_levels, num_anchors;
-    int h[OSR_MAX_LEVELS], w[OSR_MAX_LEVELS], stride[OSR_MAX_LEVELS];
-    long long pred_off[OSR_MAX_LEVELS];  // element offset of level l in the level-major prediction buffers
-    int aoff[OSR_MAX_LEVELS + 1];        // prefix of h*w*a: index base inside an image's concatenated anchor list
-    int R;
-};
-
-static bool tr_fill(const osr_rpn_levels* in, TrLevels* o) {
-    if (!in || in->num_levels < 1 || in->num_levels > OSR_MAX_LEVELS || in->num_anchors < 1) return false;
-    o->num_levels = in->num_levels; o->num_anchors = in->num_anchors;
-    long long a = 0;
-    for (int l = 0; l < in->num_levels; ++l) {
-        if (in->h[l] < 1 || in->w[l] < 1 || in->stride[l] < 1) return false;
-        o->h[l] = in->h[l]; o->w[l] = in->w[l]; o->stride[l] = in->stride[l]; o->pred_off[l] = in->offset[l];
-        o->aoff[l] = (int)a;
-        a += (long long)in->h[l] * in->w[l] * in->num_anchors;
-        if (a > (1ll << 30)) return false;
-    }
-    o->aoff[in->num_levels] = (int)a;
-    o->R = (int)a;
-    return true;
-}
-
-__device__ __forceinline__ float4 tr_anchor(const TrLevels& lv, const float* __restrict__ cell, int r, int* level, int* cell_idx) {
-    int l = 0;
-    while (l + 1 < lv.num_levels && r >= lv.aoff[l + 1]) ++l;
-    const int idx = r - lv.aoff[l], A = lv.num_anchors, a = idx % A, c = idx / A;
-    const float sx = (float)(c % lv.w[l]) * (float)lv.stride[l], sy = (float)(c / lv.w[l]) * (float)lv.stride[l];
-    const float* ca = cell + ((long long)l * A + a) * 4;
-    *level = l; *cell_idx = idx;
-    return make_float4(sx + ca[0], sy + ca[1], sx + ca[2], sy + ca[3]);
-}
 
 // [d2] pairwise_iou element: inter / (a1 + a2 - inter) when inter > 0, else 0 (a1 = GT area, a2 = box area)
 __device__ __forceinline__ float tr_iou(const float4 g, const float4 b) {
@@ -61,13 +28,13 @@ __device__ __forceinline__ float tr_iou(const float4 g, const float4 b) {
 // ------------------------------------------------------------------------------------------------------
 // anchor <-> GT matching (both Matchers share the IoU matrix and its argmax)
 // ------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void rpn_match_pass1(TrLevels lv, const float* __restrict__ cell, const float* __restrict__ gt,
+__global__ __launch_bounds__(256) void rpn_match_pass1(OsrLossLevels lv, const float* __restrict__ cell, const float* __restrict__ gt,
                                                        const int* __restrict__ gt_count, int gmax, int* __restrict__ matched_idx,
                                                        float* __restrict__ matched_iou, unsigned int* __restrict__ gtmax) {
     const int img = blockIdx.y, r = blockIdx.x * blockDim.x + threadIdx.x;
     const bool valid = r < lv.R;  // (no early return: the whole wave takes part in the per-GT maximum below)
     int l, ci;
-    const float4 b = tr_anchor(lv, cell, valid ? r : 0, &l, &ci);
+    const float4 b = osr_loss_anchor(lv, cell, valid ? r : 0, &l, &ci);
     const int G = min(gt_count[img], gmax);
     float best = 0.f;
     int bi = 0;
@@ -90,7 +57,7 @@ __global__ __launch_bounds__(256) void rpn_match_pass1(TrLevels lv, const float*
 
 __device__ __forceinline__ signed char tr_label(float v, float lo, float hi) { return v < lo ? 0 : (v < hi ? -1 : 1); }
 
-__global__ __launch_bounds__(256) void rpn_match_pass2(TrLevels lv, const float* __restrict__ cell, const float* __restrict__ gt,
+__global__ __launch_bounds__(256) void rpn_match_pass2(OsrLossLevels lv, const float* __restrict__ cell, const float* __restrict__ gt,
                                                        const int* __restrict__ gt_count, int gmax, const float* __restrict__ matched_iou,
                                                        const unsigned int* __restrict__ gtmax, float reg_lo, float reg_hi, float obj_lo,
                                                        float obj_hi, int low_quality, signed char* __restrict__ labels_reg,
@@ -104,7 +71,7 @@ __global__ __launch_bounds__(256) void rpn_match_pass2(TrLevels lv, const float*
     signed char lr = tr_label(v, reg_lo, reg_hi), lo_ = tr_label(v, obj_lo, obj_hi);
     if (low_quality) {
         int l, ci;
-        const float4 b = tr_anchor(lv, cell, r, &l, &ci);
+        const float4 b = osr_loss_anchor(lv, cell, r, &l, &ci);
         bool lq = false;
         for (int g = 0; g < G; ++g) {
             const float4 gb = *reinterpret_cast<const float4*>(gt + ((long long)img * gmax + g) * 4);
@@ -120,8 +87,8 @@ extern "C" osr_status osr_rpn_match_anchors(const osr_rpn_levels* lvl, const flo
                                             const int32_t* gt_count, int32_t gmax, float reg_lo, float reg_hi, float obj_lo, float obj_hi,
                                             int32_t* matched_idx, float* matched_iou, int8_t* labels_reg, int8_t* labels_obj,
                                             void* workspace, int64_t workspace_bytes, void* stream) {
-    TrLevels lv;
-    OSR_REQUIRE(tr_fill(lvl, &lv), OSR_ERR_INVALID_ARG, "osr_rpn_match_anchors: bad level table");
+    OsrLossLevels lv;
+    OSR_REQUIRE(osr_loss_levels_fill(lvl, &lv), OSR_ERR_INVALID_ARG, "osr_rpn_match_anchors: bad level table");
     OSR_REQUIRE(cell_anchors && gt_boxes && gt_count && matched_idx && matched_iou && labels_reg && labels_obj && workspace, OSR_ERR_INVALID_ARG,
                 "osr_rpn_match_anchors: null pointer");
     OSR_REQUIRE(n >= 1 && n <= 65535 && gmax >= 1, OSR_ERR_INVALID_ARG, "osr_rpn_match_anchors: bad n / gmax");
@@ -334,7 +301,7 @@ extern "C" osr_status osr_subsample_labels(int8_t* labels, const float* keys, in
 // ------------------------------------------------------------------------------------------------------
 // matched GT boxes + centerness targets (classification_free_rpn.py:386-402)
 // ------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void rpn_targets_kernel(TrLevels lv, const float* __restrict__ cell, const float* __restrict__ gt,
+__global__ __launch_bounds__(256) void rpn_targets_kernel(OsrLossLevels lv, const float* __restrict__ cell, const float* __restrict__ gt,
                                                           const int* __restrict__ gt_count, int gmax, const int* __restrict__ matched_idx,
                                                           const signed char* __restrict__ labels_obj, float* __restrict__ matched_boxes,
                                                           float* __restrict__ ctr_target) {
@@ -348,7 +315,7 @@ __global__ __launch_bounds__(256) void rpn_targets_kernel(TrLevels lv, const flo
         return;
     }
     int l, ci;
-    const float4 a = tr_anchor(lv, cell, r, &l, &ci);
+    const float4 a = osr_loss_anchor(lv, cell, r, &l, &ci);
     const float4 g = *reinterpret_cast<const float4*>(gt + ((long long)img * gmax + matched_idx[o]) * 4);
     *reinterpret_cast<float4*>(matched_boxes + o * 4) = g;
     // [d2] Box2BoxTransformLinear(normalize_by_size=True).get_deltas, reordered to l, r, t, b
@@ -363,8 +330,8 @@ __global__ __launch_bounds__(256) void rpn_targets_kernel(TrLevels lv, const flo
 extern "C" osr_status osr_rpn_anchor_targets(const osr_rpn_levels* lvl, const float* cell_anchors, int32_t n, const float* gt_boxes,
                                              const int32_t* gt_count, int32_t gmax, const int32_t* matched_idx, const int8_t* labels_obj,
                                              float* matched_boxes, float* ctr_target, void* stream) {
-    TrLevels lv;
-    OSR_REQUIRE(tr_fill(lvl, &lv), OSR_ERR_INVALID_ARG, "osr_rpn_anchor_targets: bad level table");
+    OsrLossLevels lv;
+    OSR_REQUIRE(osr_loss_levels_fill(lvl, &lv), OSR_ERR_INVALID_ARG, "osr_rpn_anchor_targets: bad level table");
     OSR_REQUIRE(cell_anchors && gt_boxes && gt_count && matched_idx && labels_obj && matched_boxes && ctr_target, OSR_ERR_INVALID_ARG,
                 "osr_rpn_anchor_targets: null pointer");
     OSR_REQUIRE(n >= 1 && n <= 65535 && gmax >= 1, OSR_ERR_INVALID_ARG, "osr_rpn_anchor_targets: bad n / gmax");
@@ -376,60 +343,9 @@ extern "C" osr_status osr_rpn_anchor_targets(const osr_rpn_levels* lvl, const fl
 }
 
 // ------------------------------------------------------------------------------------------------------
-// deterministic two-stage reductions
-// ------------------------------------------------------------------------------------------------------
-#define RED_BLOCKS 256
-#define RED_MAXV 8
-
-template <int NV>
-__device__ __forceinline__ void tr_block_reduce_store(float v[NV], float* __restrict__ partial /* [gridDim.x][NV] */) {
-    __shared__ float s_red[RED_MAXV][16];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
-#pragma unroll
-    for (int q = 0; q < NV; ++q) {
-        float x = v[q];
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) x += __shfl_down(x, d, 64);
-        if (lane == 0) s_red[q][wid] = x;
-    }
-    __syncthreads();
-    if (threadIdx.x < NV) {
-        float x = 0.f;
-        for (int w = 0; w < nw; ++w) x += s_red[threadIdx.x][w];
-        partial[(long long)blockIdx.x * NV + threadIdx.x] = x;
-    }
-}
-
-// out[q] = scale[q] * sum_b partial[b][q]   (fixed order)
-struct TrScale { float s[RED_MAXV]; };
-// out[q] = scale[q] * sum_b partial[b][q] (fixed order); with norm_col >= 0 every column q < norm_col is also divided by
-// max(sum_b partial[b][norm_col], 1) -- the "rows that count" normaliser when the row list is padded.
-// One wave: lane l adds the partials of workgroups l, l + 64, ... of column q, then the 64 lane sums go down a shuffle tree -- a fixed
-// order, so the value is reproducible. (One thread walking all the workgroups' partials was a 16-30 us dependent chain per loss, four
-// times on the training step's critical stream.)
-__device__ __forceinline__ float tr_wave_column_sum(const float* __restrict__ partial, int nblocks, int nv, int q) {
-    const int lane = threadIdx.x & 63;
-    float x = 0.f;
-#pragma unroll 4
-    for (int b = lane; b < nblocks; b += 64) x += partial[(long long)b * nv + q];
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) x += __shfl_down(x, d, 64);
-    return __shfl(x, 0, 64);
-}
-
-__global__ __launch_bounds__(64) void tr_final_reduce(const float* __restrict__ partial, int nblocks, int nv, TrScale scale, int norm_col, float* __restrict__ out) {
-    const float c = norm_col >= 0 ? tr_wave_column_sum(partial, nblocks, nv, norm_col) : 1.0f;
-    for (int q = 0; q < nv; ++q) {
-        float x = tr_wave_column_sum(partial, nblocks, nv, q);
-        if (norm_col >= 0 && q < norm_col) x = x / fmaxf(c, 1.0f);
-        if (threadIdx.x == 0) out[q] = x * scale.s[q];
-    }
-}
-
-// ------------------------------------------------------------------------------------------------------
 // RPN losses forward: "iou" localisation loss + L1 centerness loss (+ the four logged anchor counts)
 // ------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void rpn_losses_kernel(TrLevels lv, const float* __restrict__ cell, int n, const float* __restrict__ pred_deltas,
+__global__ __launch_bounds__(256) void rpn_losses_kernel(OsrLossLevels lv, const float* __restrict__ cell, int n, const float* __restrict__ pred_deltas,
                                                          const float* __restrict__ pred_ctr, const signed char* __restrict__ labels_reg,
                                                          const signed char* __restrict__ labels_obj, const float* __restrict__ matched_boxes,
                                                          const float* __restrict__ ctr_target, int box_type, float box_beta, float ctr_beta,
@@ -442,8 +358,8 @@ __global__ __launch_bounds__(256) void rpn_losses_kernel(TrLevels lv, const floa
         v[2] += lr == 1; v[3] += lr == 0; v[4] += lo == 1; v[5] += lo == 0;
         if (lr != 1 && lo == -1) continue;
         int l, ci;
-        const float4 a = tr_anchor(lv, cell, r, &l, &ci);
-        const long long pi = lv.pred_off[l] + (long long)img * (lv.aoff[l + 1] - lv.aoff[l]) + ci;
+        const float4 a = osr_loss_anchor(lv, cell, r, &l, &ci);
+        const long long pi = osr_loss_pred_index(lv, l, img, ci);
         if (lr == 1) {
             const float4 d = *reinterpret_cast<const float4*>(pred_deltas + pi * 4);
             const float cx = 0.5f * (a.x + a.z), cy = 0.5f * (a.y + a.w), aw = a.z - a.x, ah = a.w - a.y;
@@ -462,7 +378,7 @@ __global__ __launch_bounds__(256) void rpn_losses_kernel(TrLevels lv, const floa
         }
         if (lo != -1) v[1] += osr_smooth_l1(pred_ctr[pi] - ctr_target[i], ctr_beta);
     }
-    tr_block_reduce_store<6>(v, partial);
+    osr_loss_block_reduce_store<6>(v, partial);
 }
 
 extern "C" osr_status osr_rpn_losses_fwd_ex(const osr_rpn_levels* lvl, const float* cell_anchors, int32_t n, const float* pred_deltas,
@@ -473,21 +389,21 @@ extern "C" osr_status osr_rpn_losses_fwd_ex(const osr_rpn_levels* lvl, const flo
     const float box_beta = opt ? opt->box_smooth_l1_beta : 0.f, ctr_beta = opt ? opt->aux_smooth_l1_beta : 0.f;
     OSR_REQUIRE(box_type >= OSR_LOSS_IOU && box_type <= OSR_LOSS_CIOU && box_beta >= 0.f && ctr_beta >= 0.f, OSR_ERR_INVALID_ARG,
                 "osr_rpn_losses_fwd: bad loss options (type %d)", box_type);
-    TrLevels lv;
-    OSR_REQUIRE(tr_fill(lvl, &lv), OSR_ERR_INVALID_ARG, "osr_rpn_losses_fwd: bad level table");
+    OsrLossLevels lv;
+    OSR_REQUIRE(osr_loss_levels_fill(lvl, &lv), OSR_ERR_INVALID_ARG, "osr_rpn_losses_fwd: bad level table");
     OSR_REQUIRE(cell_anchors && pred_deltas && pred_ctr && labels_reg && labels_obj && matched_boxes && ctr_target && out6 && workspace,
                 OSR_ERR_INVALID_ARG, "osr_rpn_losses_fwd: null pointer");
     OSR_REQUIRE(n >= 1 && batch_size_per_image >= 1, OSR_ERR_INVALID_ARG, "osr_rpn_losses_fwd: bad n / batch size");
-    OSR_REQUIRE(workspace_bytes >= (int64_t)RED_BLOCKS * 6 * 4, OSR_ERR_WORKSPACE, "osr_rpn_losses_fwd: workspace needs %d bytes", RED_BLOCKS * 6 * 4);
+    OSR_REQUIRE(workspace_bytes >= (int64_t)OSR_LOSS_RED_BLOCKS * 6 * 4, OSR_ERR_WORKSPACE, "osr_rpn_losses_fwd: workspace needs %d bytes", OSR_LOSS_RED_BLOCKS * 6 * 4);
     OSR_REQUIRE((((uintptr_t)pred_deltas | (uintptr_t)matched_boxes) & 15) == 0, OSR_ERR_INVALID_ARG, "osr_rpn_losses_fwd: box arrays must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     float* partial = (float*)workspace;
     const float norm = (float)batch_size_per_image * (float)n;
-    const TrScale scale = {{1.0f / norm * loc_weight, 1.0f / norm * ctr_weight, 1.f, 1.f, 1.f, 1.f, 0.f, 0.f}};
-    hipLaunchKernelGGL(rpn_losses_kernel, dim3(RED_BLOCKS), dim3(256), 0, st, lv, cell_anchors, n, pred_deltas, pred_ctr, (const signed char*)labels_reg,
+    const OsrLossScale scale = {{1.0f / norm * loc_weight, 1.0f / norm * ctr_weight, 1.f, 1.f, 1.f, 1.f, 0.f, 0.f}};
+    hipLaunchKernelGGL(rpn_losses_kernel, dim3(OSR_LOSS_RED_BLOCKS), dim3(256), 0, st, lv, cell_anchors, n, pred_deltas, pred_ctr, (const signed char*)labels_reg,
                        (const signed char*)labels_obj, matched_boxes, ctr_target, box_type, box_beta, ctr_beta, partial);
     OSR_CHECK_LAUNCH("osr_rpn_losses_fwd");
-    hipLaunchKernelGGL(tr_final_reduce, dim3(1), dim3(64), 0, st, partial, RED_BLOCKS, 6, scale, -1, out6);
+    hipLaunchKernelGGL(osr_loss_final_reduce, dim3(1), dim3(64), 0, st, partial, OSR_LOSS_RED_BLOCKS, 6, scale, -1, out6);
     OSR_CHECK_LAUNCH("osr_rpn_losses_fwd(final)");
     return OSR_OK;
 }
@@ -636,25 +552,19 @@ __global__ __launch_bounds__(256) void roi_box_losses_kernel(const float* __rest
         if (c >= num_classes) continue;
         const float4 s = *reinterpret_cast<const float4*>(prop + i * 4), t = *reinterpret_cast<const float4*>(gtb + i * 4);
         const float* d = pred_deltas + i * delta_stride;
-        // [d2] Box2BoxTransform.get_deltas
-        const float sw = s.z - s.x, sh = s.w - s.y, scx = s.x + 0.5f * sw, scy = s.y + 0.5f * sh;
-        const float tw = t.z - t.x, th = t.w - t.y, tcx = t.x + 0.5f * tw, tcy = t.y + 0.5f * th;
         if (box_type == OSR_LOSS_SMOOTH_L1) {
-            const float dx = wx * (tcx - scx) / sw, dy = wy * (tcy - scy) / sh, dw = ww * logf(tw / sw), dh = wh * logf(th / sh);
-            v[0] += osr_smooth_l1(d[0] - dx, box_beta) + osr_smooth_l1(d[1] - dy, box_beta) + osr_smooth_l1(d[2] - dw, box_beta) +
-                    osr_smooth_l1(d[3] - dh, box_beta);
-        } else {  // [d2] Box2BoxTransform.apply_deltas, then the box loss (box_regression_w_iou.py:49-82)
-            const float kClamp = 4.135166556742356f;  // log(1000 / 16)
-            const float pw = expf(fminf(d[2] / ww, kClamp)) * sw, ph = expf(fminf(d[3] / wh, kClamp)) * sh;
-            const float pcx = d[0] / wx * sw + scx, pcy = d[1] / wy * sh + scy;
-            float unused[4];
-            v[0] += osr_box_loss<false>(box_type, make_float4(pcx - 0.5f * pw, pcy - 0.5f * ph, pcx + 0.5f * pw, pcy + 0.5f * ph), t, unused);
+            const float4 tg = osr_b2b_get_deltas(s, t, wx, wy, ww, wh);
+            v[0] += osr_smooth_l1(d[0] - tg.x, box_beta) + osr_smooth_l1(d[1] - tg.y, box_beta) + osr_smooth_l1(d[2] - tg.z, box_beta) +
+                    osr_smooth_l1(d[3] - tg.w, box_beta);
+        } else {  // the decoded box, then the box loss (box_regression_w_iou.py:49-82)
+            float pw, ph, unused[4];
+            v[0] += osr_box_loss<false>(box_type, osr_b2b_apply_deltas(s, d, wx, wy, ww, wh, &pw, &ph), t, unused);
         }
         float pi = pred_iou[i * iou_stride];
         if (iou_is_logit) pi = 1.0f / (1.0f + expf(-pi));  // OpensetFastRCNNOutputLayers.forward: iou_pred(x).sigmoid()
         v[1] += osr_smooth_l1(pi - gt_iou[i], iou_beta);
     }
-    tr_block_reduce_store<3>(v, partial);
+    osr_loss_block_reduce_store<3>(v, partial);
 }
 
 extern "C" osr_status osr_roi_box_losses_fwd_ex(const float* pred_deltas, int32_t delta_stride, const float* pred_iou, int32_t iou_stride,
@@ -669,16 +579,16 @@ extern "C" osr_status osr_roi_box_losses_fwd_ex(const float* pred_deltas, int32_
     OSR_REQUIRE(pred_deltas && pred_iou && proposal_boxes && gt_boxes && gt_classes && gt_iou && reg_weights && out3 && workspace, OSR_ERR_INVALID_ARG,
                 "osr_roi_box_losses_fwd: null pointer");
     OSR_REQUIRE(m >= 0 && delta_stride >= 4 && iou_stride >= 1, OSR_ERR_INVALID_ARG, "osr_roi_box_losses_fwd: bad m / strides");
-    OSR_REQUIRE(workspace_bytes >= (int64_t)RED_BLOCKS * 3 * 4, OSR_ERR_WORKSPACE, "osr_roi_box_losses_fwd: workspace needs %d bytes", RED_BLOCKS * 3 * 4);
+    OSR_REQUIRE(workspace_bytes >= (int64_t)OSR_LOSS_RED_BLOCKS * 3 * 4, OSR_ERR_WORKSPACE, "osr_roi_box_losses_fwd: workspace needs %d bytes", OSR_LOSS_RED_BLOCKS * 3 * 4);
     OSR_REQUIRE((((uintptr_t)proposal_boxes | (uintptr_t)gt_boxes) & 15) == 0, OSR_ERR_INVALID_ARG, "osr_roi_box_losses_fwd: box arrays must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     float* partial = (float*)workspace;
-    const TrScale scale = {{box_weight, iou_weight, 1.f, 0.f, 0.f, 0.f, 0.f, 0.f}};
-    hipLaunchKernelGGL(roi_box_losses_kernel, dim3(RED_BLOCKS), dim3(256), 0, st, pred_deltas, delta_stride, pred_iou, iou_stride, iou_is_logit, proposal_boxes,
+    const OsrLossScale scale = {{box_weight, iou_weight, 1.f, 0.f, 0.f, 0.f, 0.f, 0.f}};
+    hipLaunchKernelGGL(roi_box_losses_kernel, dim3(OSR_LOSS_RED_BLOCKS), dim3(256), 0, st, pred_deltas, delta_stride, pred_iou, iou_stride, iou_is_logit, proposal_boxes,
                        gt_boxes, (const long long*)gt_classes, gt_iou, (long long)m, num_classes, reg_weights[0], reg_weights[1], reg_weights[2],
                        reg_weights[3], box_type, box_beta, iou_beta, partial);
     OSR_CHECK_LAUNCH("osr_roi_box_losses_fwd");
-    hipLaunchKernelGGL(tr_final_reduce, dim3(1), dim3(64), 0, st, partial, RED_BLOCKS, 3, scale, 2, out3);
+    hipLaunchKernelGGL(osr_loss_final_reduce, dim3(1), dim3(64), 0, st, partial, OSR_LOSS_RED_BLOCKS, 3, scale, 2, out3);
     OSR_CHECK_LAUNCH("osr_roi_box_losses_fwd(final)");
     return OSR_OK;
 }
@@ -781,13 +691,13 @@ __global__ __launch_bounds__(256) void pln_loss_kernel(const float* __restrict__
             v[2] += fmaxf(beta + alpha - cd, 0.f);
         }
     }
-    tr_block_reduce_store<4>(v, partial);
+    osr_loss_block_reduce_store<4>(v, partial);
 }
 
 // loss = weight / M * (sum intra + sum inter + sum center), each sum in workgroup order
 __global__ __launch_bounds__(64) void pln_finish(const float* __restrict__ partial, int nblocks, float scale, float* __restrict__ out) {
-    const float a = tr_wave_column_sum(partial, nblocks, 4, 0), b = tr_wave_column_sum(partial, nblocks, 4, 1);
-    const float c = tr_wave_column_sum(partial, nblocks, 4, 2), rows = tr_wave_column_sum(partial, nblocks, 4, 3);
+    const float a = osr_loss_column_sum(partial, nblocks, 4, 0), b = osr_loss_column_sum(partial, nblocks, 4, 1);
+    const float c = osr_loss_column_sum(partial, nblocks, 4, 2), rows = osr_loss_column_sum(partial, nblocks, 4, 3);
     if (threadIdx.x == 0) out[0] = ((a + b) + c) * scale / fmaxf(rows, 1.0f);
 }
 
@@ -798,7 +708,7 @@ extern "C" osr_status osr_pln_loss_fwd_ex(const float* emb, int64_t m, int32_t d
     OSR_REQUIRE(m >= 0 && d >= 1 && num_known >= 1 && reps >= 1 && (long long)num_known * reps * d <= 36864, OSR_ERR_UNSUPPORTED,
                 "osr_pln_loss_fwd: bad sizes (the prototypes must fit a 144 KB LDS table)");
     OSR_REQUIRE(distance_type >= OSR_DIST_COS && distance_type <= OSR_DIST_L2, OSR_ERR_INVALID_ARG, "osr_pln_loss_fwd: distance_type %d", distance_type);
-    OSR_REQUIRE(workspace_bytes >= (int64_t)RED_BLOCKS * 4 * 4, OSR_ERR_WORKSPACE, "osr_pln_loss_fwd: workspace needs %d bytes", RED_BLOCKS * 4 * 4);
+    OSR_REQUIRE(workspace_bytes >= (int64_t)OSR_LOSS_RED_BLOCKS * 4 * 4, OSR_ERR_WORKSPACE, "osr_pln_loss_fwd: workspace needs %d bytes", OSR_LOSS_RED_BLOCKS * 4 * 4);
     hipStream_t st = (hipStream_t)stream;
     float* partial = (float*)workspace;
     const size_t smem = (size_t)num_known * reps * d * 4;
@@ -810,13 +720,13 @@ extern "C" osr_status osr_pln_loss_fwd_ex(const float* emb, int64_t m, int32_t d
         });
     }
     if (d <= 256)
-        hipLaunchKernelGGL(pln_loss_kernel<4>, dim3(RED_BLOCKS), dim3(256), smem, st, emb, (long long)m, d, protos_normed, num_known, reps, distance_type,
+        hipLaunchKernelGGL(pln_loss_kernel<4>, dim3(OSR_LOSS_RED_BLOCKS), dim3(256), smem, st, emb, (long long)m, d, protos_normed, num_known, reps, distance_type,
                            (const long long*)gt_classes, ious, iou_thr, alpha, beta, partial);
     else
-        hipLaunchKernelGGL(pln_loss_kernel<OSR_PLN_REG>, dim3(RED_BLOCKS), dim3(256), smem, st, emb, (long long)m, d, protos_normed, num_known, reps, distance_type,
+        hipLaunchKernelGGL(pln_loss_kernel<OSR_PLN_REG>, dim3(OSR_LOSS_RED_BLOCKS), dim3(256), smem, st, emb, (long long)m, d, protos_normed, num_known, reps, distance_type,
                            (const long long*)gt_classes, ious, iou_thr, alpha, beta, partial);
     OSR_CHECK_LAUNCH("osr_pln_loss_fwd");
-    hipLaunchKernelGGL(pln_finish, dim3(1), dim3(64), 0, st, (const float*)partial, RED_BLOCKS, loss_weight, out1);
+    hipLaunchKernelGGL(pln_finish, dim3(1), dim3(64), 0, st, (const float*)partial, OSR_LOSS_RED_BLOCKS, loss_weight, out1);
     OSR_CHECK_LAUNCH("osr_pln_loss_fwd(final)");
     return OSR_OK;
 }
@@ -839,18 +749,16 @@ __global__ __launch_bounds__(256) void ce_loss_kernel(const float* __restrict__ 
         const int t = (c >= 0 && c < K) ? (int)c : (c == num_classes ? K : -1);  // id_map: known -> itself, background -> K, others -> -1
         if (t < 0) continue;
         const float* lg = logits + i * nc;
-        float mx = lg[0];
-        for (int j = 1; j < nc; ++j) mx = fmaxf(mx, lg[j]);
-        float s = 0.f;
-        for (int j = 0; j < nc; ++j) s += expf(lg[j] - mx);
+        float s;
+        const float mx = osr_softmax_row(lg, nc, &s);
         v[0] += (logf(s) + mx) - lg[t];
         v[1] += 1.f;
     }
-    tr_block_reduce_store<2>(v, partial);
+    osr_loss_block_reduce_store<2>(v, partial);
 }
 
 __global__ __launch_bounds__(64) void ce_finish(const float* __restrict__ partial, int nblocks, float weight, float* __restrict__ out) {
-    const float s = tr_wave_column_sum(partial, nblocks, 2, 0), c = tr_wave_column_sum(partial, nblocks, 2, 1);
+    const float s = osr_loss_column_sum(partial, nblocks, 2, 0), c = osr_loss_column_sum(partial, nblocks, 2, 1);
     if (threadIdx.x == 0) out[0] = c > 0.f ? weight * (s / c) : 0.f;
 }
 
@@ -858,12 +766,12 @@ extern "C" osr_status osr_softmax_ce_loss_fwd(const float* logits, int64_t m, in
                                               float loss_weight, float* out1, void* workspace, int64_t workspace_bytes, void* stream) {
     OSR_REQUIRE(logits && gt_classes && out1 && workspace, OSR_ERR_INVALID_ARG, "osr_softmax_ce_loss_fwd: null pointer");
     OSR_REQUIRE(m >= 0 && num_known >= 1 && num_known <= 1024, OSR_ERR_INVALID_ARG, "osr_softmax_ce_loss_fwd: bad sizes");
-    OSR_REQUIRE(workspace_bytes >= (int64_t)RED_BLOCKS * 2 * 4, OSR_ERR_WORKSPACE, "osr_softmax_ce_loss_fwd: workspace needs %d bytes", RED_BLOCKS * 2 * 4);
+    OSR_REQUIRE(workspace_bytes >= (int64_t)OSR_LOSS_RED_BLOCKS * 2 * 4, OSR_ERR_WORKSPACE, "osr_softmax_ce_loss_fwd: workspace needs %d bytes", OSR_LOSS_RED_BLOCKS * 2 * 4);
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(ce_loss_kernel, dim3(RED_BLOCKS), dim3(256), 0, st, logits, (long long)m, num_known + 1, (const long long*)gt_classes, num_classes, num_known,
+    hipLaunchKernelGGL(ce_loss_kernel, dim3(OSR_LOSS_RED_BLOCKS), dim3(256), 0, st, logits, (long long)m, num_known + 1, (const long long*)gt_classes, num_classes, num_known,
                        (float*)workspace);
     OSR_CHECK_LAUNCH("osr_softmax_ce_loss_fwd");
-    hipLaunchKernelGGL(ce_finish, dim3(1), dim3(64), 0, st, (const float*)workspace, RED_BLOCKS, loss_weight, out1);
+    hipLaunchKernelGGL(ce_finish, dim3(1), dim3(64), 0, st, (const float*)workspace, OSR_LOSS_RED_BLOCKS, loss_weight, out1);
     OSR_CHECK_LAUNCH("osr_softmax_ce_loss_fwd(final)");
     return OSR_OK;
 }

@@ -1398,7 +1398,7 @@ def rpn_losses_fwd(lv: RpnLevels, cell_anchors, n: int, pred_deltas, pred_ctr, l
     _need(matched_boxes, torch.float32, "matched_boxes"); _need(ctr_target, torch.float32, "ctr_target")
     dev = pred_ctr.device
     out = torch.empty((6,), dtype=torch.float32, device=dev)
-    ws = torch.empty((256 * 6 * 4,), dtype=torch.uint8, device=dev)
+    ws = _loss_ws(dev, 6)
     opt = _loss_options(box_loss, ctr_beta)
     check(lib.osr_rpn_losses_fwd_ex(C.byref(lv), _p(cell_anchors), n, _p(pred_deltas), _p(pred_ctr), _p(labels_reg), _p(labels_obj),
                                     _p(matched_boxes), _p(ctr_target), loc_weight, ctr_weight, batch_size_per_image, C.byref(opt), _p(out), _p(ws),
@@ -2027,7 +2027,7 @@ def std_rpn_losses_fwd(lv: RpnLevels, cell_anchors, n: int, pred_logits, pred_de
     _need(labels, torch.int8, "labels"); _need(matched_boxes, torch.float32, "matched_boxes")
     dev = pred_logits.device
     out = torch.empty((4,), dtype=torch.float32, device=dev)
-    ws = torch.empty((256 * 4 * 4,), dtype=torch.uint8, device=dev)
+    ws = _loss_ws(dev, 4)
     check(lib.osr_std_rpn_losses_fwd(C.byref(lv), _p(cell_anchors), n, _p(pred_logits), _p(pred_deltas), _p(labels), _p(matched_boxes),
                                      _f4(b2b_weights), beta, cls_weight, loc_weight, batch_size_per_image, _p(out), _p(ws), ws.numel(), _stream()),
           "osr_std_rpn_losses_fwd")
@@ -2058,7 +2058,7 @@ def fastrcnn_losses_fwd(logits, pred_deltas, proposal_boxes, gt_boxes, gt_classe
     _need(gt_classes, torch.int64, "gt_classes"); _need(pred_deltas, torch.float32, "pred_deltas")
     m = logits.shape[0]
     out = torch.empty((7,), dtype=torch.float32, device=logits.device)
-    ws = torch.empty((256 * 7 * 4,), dtype=torch.uint8, device=logits.device)
+    ws = _loss_ws(logits.device, 7)
     check(lib.osr_fastrcnn_losses_fwd(_p(logits), _p(pred_deltas), pred_deltas.shape[1], int(cls_agnostic), _p(proposal_boxes), _p(gt_boxes),
                                       _p(gt_classes), m, num_classes, _f4(reg_weights), beta, cls_weight, box_weight, _p(out), _p(ws), ws.numel(),
                                       _stream()), "osr_fastrcnn_losses_fwd")
