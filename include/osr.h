@@ -503,6 +503,7 @@ osr_status osr_box_predictor_tail(const float* x, int64_t m, int32_t k, const fl
  * thr >= 1 suppresses nothing (pure sort + top-k). Segment s covers elements
  * [s*seg_stride, s*seg_stride + seg_len[s]) of boxes/scores/cls/cand; cand==0 elements are skipped.
  * keep: (num_segments, topk) indices relative to the segment start; keep_count: (num_segments).
+ * With thr < 1 the kept boxes sit in LDS: topk <= 2048 (OSR_ERR_UNSUPPORTED above; up to 1024 the kernel with the 1024-entry table).
  * --------------------------------------------------------------------------------------------------------- */
 int64_t osr_nms_topk_workspace_bytes(int32_t num_segments, int64_t seg_stride);
 osr_status osr_nms_topk(const float* boxes, const float* scores, const int32_t* cls /* nullable: one class */,
@@ -566,6 +567,40 @@ osr_status osr_fastrcnn_candidates(const float* logits, const float* deltas, int
                                    int32_t n, int32_t seg_rows, const int32_t* image_hw, const float reg_weights[4],
                                    float score_thresh, float* c_boxes, float* c_scores, int32_t* c_cls, int32_t* c_row,
                                    int32_t* c_count, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * [d2] CascadeROIHeads (Cascade R-CNN; csrc/osr_cascade.hip): the glue between the stages, on the stock engine's fixed-capacity
+ * row lists. m = n * seg_rows rows; row r belongs to image r / seg_rows and exists iff batch_idx[r] >= 0. No compaction, no
+ * atomics, no host sync; repeats are bit-identical.
+ *
+ * osr_cascade_refine: one launch per stage transition ([d2] predict_boxes + _create_proposals_from_boxes +
+ * _match_and_label_boxes). Per existing row: Box2BoxTransform(reg_weights).apply_deltas of the stage's class-agnostic deltas (m,4)
+ * on the stage's input box, clipped to the row's image_hw (a NaN stays a NaN). drop_empty (training): a row whose clipped box has
+ * width <= 0 or height <= 0 (or a NaN there) stops existing: batch_idx_out -1, class -1, a zero box. Without it (inference) every
+ * existing row stays, so the stages' scores stay aligned. gt_boxes (n,gmax,4) / gt_classes (n,gmax) / gt_count (n) -- all NULL at
+ * inference, the three matching outputs are then not written and may be NULL --: pairwise_iou in fp32 against the image's boxes
+ * (inter / (a1 + a2 - inter) where inter > 0, else 0), the maximum with the lowest index among equal IoUs; foreground iff the
+ * maximum >= iou_thr (Matcher([thr], [0, 1]), no low-quality matches): classes_out int64 = the matched class (background:
+ * num_classes), gt_boxes_out = the matched box (on background rows too; zeros when gt_count is 0), gt_idx_out = the matched index
+ * (-1 off foreground). counts (n,3) = {rows, foreground, background} (foreground / background 0 without ground truth).
+ * gmax <= 1024: an image's ground truth sits in a static LDS table; OSR_ERR_INVALID_ARG above it. Not in place.
+ *
+ * osr_cascade_candidates: osr_fastrcnn_candidates for num_stages <= OSR_CASCADE_MAX_STAGES stages. logits[s] (m, K+1) for
+ * s < num_stages (a host array of device pointers), the last stage's deltas (m,4) and input boxes (m,4). Per existing row: softmax
+ * of each stage in fp32, score = ((p0 + p1) + p2 ...) * (float)(1.0 / num_stages); decode with reg_weights, clip; the row is
+ * dropped when any box coordinate or score is non-finite; every (row, class < K) with score > score_thresh becomes a candidate,
+ * row-major. Outputs and padding as osr_fastrcnn_candidates; with one stage they are bit-identical to it.
+ * --------------------------------------------------------------------------------------------------------- */
+#define OSR_CASCADE_MAX_STAGES 4
+osr_status osr_cascade_refine(const float* boxes, const int32_t* batch_idx, const float* deltas, int32_t n, int32_t seg_rows,
+                              const int32_t* image_hw, const float reg_weights[4], int32_t drop_empty, const float* gt_boxes,
+                              const int64_t* gt_classes, const int32_t* gt_count, int32_t gmax, int32_t num_classes,
+                              float iou_thr, float* boxes_out, int32_t* batch_idx_out, int64_t* classes_out,
+                              float* gt_boxes_out, int32_t* gt_idx_out, int32_t* counts, void* stream);
+osr_status osr_cascade_candidates(const float* const* logits, int32_t num_stages, const float* deltas, int32_t num_classes,
+                                  const float* boxes, const int32_t* batch_idx, int32_t n, int32_t seg_rows,
+                                  const int32_t* image_hw, const float reg_weights[4], float score_thresh, float* c_boxes,
+                                  float* c_scores, int32_t* c_cls, int32_t* c_row, int32_t* c_count, void* stream);
 
 /* Final assembly: output order [unknown..., known...] (softmax_classifier.py:328-334), class ids int64
  * (unknown_id for the unknown group, class_map[c] or c for known). out_* padded to (n, u_topk + k_topk). */

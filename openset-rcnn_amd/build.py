@@ -32,6 +32,7 @@ SOURCES = {
     "osr_rpn.hip": ["-ffp-contract=off"],
     "osr_roi_align.hip": ["-ffp-contract=off"],
     "osr_det_tail.hip": ["-ffp-contract=off"],
+    "osr_cascade.hip": ["-ffp-contract=off"],  # (as osr_det_tail.hip: one stage reproduces osr_fastrcnn_candidates bit for bit)
     "osr_mask_head.hip": [],
     "osr_mask_train.hip": ["-ffp-contract=off"],
     "osr_tta.hip": ["-ffp-contract=off"],

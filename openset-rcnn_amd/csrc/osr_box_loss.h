@@ -21,6 +21,15 @@ __device__ __forceinline__ float osr_smooth_l1_grad(float x, float beta) {
     return x > 0.f ? 1.f : (x < 0.f ? -1.f : 0.f);
 }
 
+// [d2] pairwise_iou of two boxes in fp32: inter / (a1 + a2 - inter) where inter > 0, else 0 (the matchers of the RPN, the RoI heads
+// and the cascade's stage transitions; built without FMA contraction wherever an index depends on it)
+__device__ __forceinline__ float osr_pairwise_iou(const float4 g, const float4 b) {
+    const float a1 = (g.z - g.x) * (g.w - g.y), a2 = (b.z - b.x) * (b.w - b.y);
+    const float w = fmaxf(fminf(g.z, b.z) - fmaxf(g.x, b.x), 0.f), h = fmaxf(fminf(g.w, b.w) - fmaxf(g.y, b.y), 0.f);
+    const float inter = w * h;
+    return inter > 0.f ? inter / (a1 + a2 - inter) : 0.f;
+}
+
 // [d2] Box2BoxTransform.get_deltas(src, tgt) with weights (wx, wy, ww, wh): the targets of the "smooth_l1" loss
 __device__ __forceinline__ float4 osr_b2b_get_deltas(float4 s, float4 t, float wx, float wy, float ww, float wh) {
     const float sw = s.z - s.x, sh = s.w - s.y, scx = s.x + 0.5f * sw, scy = s.y + 0.5f * sh;

@@ -161,14 +161,18 @@ __global__ __launch_bounds__(SORT_THREADS) void seg_sort_kernel(const float* __r
     if (tid == 0) ws_count[seg] = tot;
 }
 
-#define NMS_MAX_TOPK 1024
+// The kept boxes sit in LDS: 24 bytes each. Up to 1024 (every inference list, the stock RPN's POST_NMS_TOPK_TRAIN 1000) the kernel is the
+// one it always was; a longer list -- [d2]'s cascade configs train on POST_NMS_TOPK_TRAIN 2000 proposals -- takes the 2048-entry
+// instantiation (48 KB of static LDS for its one wave).
+#define NMS_MAX_TOPK 2048
 
+template <int CAP>
 __global__ __launch_bounds__(64) void nms_greedy_kernel(const float* __restrict__ boxes, const int* __restrict__ cls, long long seg_stride,
                                                         const int* __restrict__ ws_order, const int* __restrict__ ws_count, float thr,
                                                         int topk, int* __restrict__ keep, int* __restrict__ keep_count) {
-    __shared__ float4 s_box[NMS_MAX_TOPK];
-    __shared__ float s_area[NMS_MAX_TOPK];
-    __shared__ int s_cls[NMS_MAX_TOPK];
+    __shared__ float4 s_box[CAP];
+    __shared__ float s_area[CAP];
+    __shared__ int s_cls[CAP];
     const int seg = blockIdx.x, lane = threadIdx.x;
     const int n = ws_count[seg];
     const int* order = ws_order + seg * seg_stride;
@@ -275,8 +279,12 @@ extern "C" osr_status osr_nms_topk(const float* boxes, const float* scores, cons
     hipLaunchKernelGGL(seg_sort_kernel, dim3(num_segments), dim3(SORT_THREADS), smem, st, scores, cand, (long long)seg_stride, seg_len, ws_order,
                        ws_count, ws_keys, ks, lds_cap);
     OSR_CHECK_LAUNCH("osr_nms_topk(sort)");
-    hipLaunchKernelGGL(nms_greedy_kernel, dim3(num_segments), dim3(64), 0, st, boxes, cls, (long long)seg_stride, ws_order, ws_count, thr, topk,
-                       keep, keep_count);
+    if (topk <= 1024)
+        hipLaunchKernelGGL(nms_greedy_kernel<1024>, dim3(num_segments), dim3(64), 0, st, boxes, cls, (long long)seg_stride, ws_order, ws_count, thr,
+                           topk, keep, keep_count);
+    else  // (thr >= 1 never touches the table: any topk)
+        hipLaunchKernelGGL(nms_greedy_kernel<NMS_MAX_TOPK>, dim3(num_segments), dim3(64), 0, st, boxes, cls, (long long)seg_stride, ws_order, ws_count,
+                           thr, topk, keep, keep_count);
     OSR_CHECK_LAUNCH("osr_nms_topk(nms)");
     return OSR_OK;
 }

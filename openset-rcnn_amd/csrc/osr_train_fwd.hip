@@ -17,14 +17,6 @@
 static_assert(OSR_LOSS_IOU == OSR_BOX_LOSS_IOU && OSR_LOSS_SMOOTH_L1 == OSR_BOX_LOSS_SMOOTH_L1 && OSR_LOSS_GIOU == OSR_BOX_LOSS_GIOU &&
                   OSR_LOSS_DIOU == OSR_BOX_LOSS_DIOU && OSR_LOSS_CIOU == OSR_BOX_LOSS_CIOU, "osr_box_loss.h and include/osr.h number the losses alike");
 
-// [d2] pairwise_iou element: inter / (a1 + a2 - inter) when inter > 0, else 0 (a1 = GT area, a2 = box area)
-__device__ __forceinline__ float tr_iou(const float4 g, const float4 b) {
-    const float a1 = (g.z - g.x) * (g.w - g.y), a2 = (b.z - b.x) * (b.w - b.y);
-    const float w = fmaxf(fminf(g.z, b.z) - fmaxf(g.x, b.x), 0.f), h = fmaxf(fminf(g.w, b.w) - fmaxf(g.y, b.y), 0.f);
-    const float inter = w * h;
-    return inter > 0.f ? inter / (a1 + a2 - inter) : 0.f;
-}
-
 // ------------------------------------------------------------------------------------------------------
 // anchor <-> GT matching (both Matchers share the IoU matrix and its argmax)
 // ------------------------------------------------------------------------------------------------------
@@ -40,7 +32,7 @@ __global__ __launch_bounds__(256) void rpn_match_pass1(OsrLossLevels lv, const f
     int bi = 0;
     for (int g = 0; g < G; ++g) {
         const float4 gb = *reinterpret_cast<const float4*>(gt + ((long long)img * gmax + g) * 4);
-        const float v = valid ? tr_iou(gb, b) : 0.f;
+        const float v = valid ? osr_pairwise_iou(gb, b) : 0.f;
         if (g == 0 || v > best) { best = v; bi = g; }  // first maximum wins
         // best IoU of the GT over all anchors: maximum over the wave first, one atomic per wave (every lane doing its own
         // atomicMax on the handful of per-GT words serialised 11 M atomics on 128 addresses: 0.8 ms)
@@ -75,7 +67,7 @@ __global__ __launch_bounds__(256) void rpn_match_pass2(OsrLossLevels lv, const f
         bool lq = false;
         for (int g = 0; g < G; ++g) {
             const float4 gb = *reinterpret_cast<const float4*>(gt + ((long long)img * gmax + g) * 4);
-            lq |= __float_as_uint(tr_iou(gb, b)) == gtmax[(long long)img * gmax + g];  // quality == best_of_gt (incl. the 0 == 0 quirk)
+            lq |= __float_as_uint(osr_pairwise_iou(gb, b)) == gtmax[(long long)img * gmax + g];  // quality == best_of_gt (incl. the 0 == 0 quirk)
         }
         if (lq) { lr = 1; lo_ = 1; }
     }
@@ -451,7 +443,7 @@ __global__ __launch_bounds__(TR_THREADS) void roi_match_sample_kernel(const floa
         float best = 0.f;
         int bi = 0;
         for (int g = 0; g < G; ++g) {
-            const float v = tr_iou(*reinterpret_cast<const float4*>(gt + ((long long)img * gmax + g) * 4), b);
+            const float v = osr_pairwise_iou(*reinterpret_cast<const float4*>(gt + ((long long)img * gmax + g) * 4), b);
             if (g == 0 || v > best) { best = v; bi = g; }
         }
         const bool fg = G > 0 && best >= iou_thr;  // [d2] Matcher([0.5], [0, 1])

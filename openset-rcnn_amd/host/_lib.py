@@ -154,6 +154,8 @@ PROTOTYPES = {
     "osr_rpn_select": (I32, [C.POINTER(RpnLevels), P, P, P, I32, P, I32, F32, P, P, P, P, P, P, P, I64, P]),
     "osr_rpn_select_ex": (I32, [C.POINTER(RpnLevels), P, P, P, I32, P, I32, F32, I32, P, P, P, P, P, P, P, P, P, I64, P]),
     "osr_fastrcnn_candidates": (I32, [P, P, I32, I32, P, P, I32, I32, P, P, F32, P, P, P, P, P, P]),
+    "osr_cascade_refine": (I32, [P, P, P, I32, I32, P, P, I32, P, P, P, I32, I32, F32, P, P, P, P, P, P, P]),
+    "osr_cascade_candidates": (I32, [P, I32, P, I32, P, P, I32, I32, P, P, F32, P, P, P, P, P, P]),
     "osr_roi_align_fwd": (I32, [C.POINTER(Pyramid), I32, I32, P, P, I64, I32, I32, I32, I32, P, I32, P]),
     "osr_roi_align_fwd_ordered": (I32, [C.POINTER(Pyramid), I32, I32, P, P, I64, I32, I32, I32, I32, P, P, P, I32, P]),
     "osr_roi_align_fwd_ordered_ex": (I32, [C.POINTER(Pyramid), I32, I32, P, P, I64, I32, I32, I32, I32, P, P, I32, P, I32, P]),

@@ -164,6 +164,9 @@ def get_cfg() -> CfgNode:
                          "BBOX_REG_WEIGHTS": (10.0, 10.0, 5.0, 5.0), "SMOOTH_L1_BETA": 0.0, "POOLER_RESOLUTION": 14,
                          "POOLER_SAMPLING_RATIO": 0, "POOLER_TYPE": "ROIAlignV2", "NUM_FC": 0, "FC_DIM": 1024, "NUM_CONV": 0,
                          "CONV_DIM": 256, "NORM": "", "CLS_AGNOSTIC_BBOX_REG": False, "TRAIN_ON_PRED_BOXES": False})
+    # [d2] CascadeROIHeads: one entry per stage (host/engine_cascade.py)
+    m.ROI_BOX_CASCADE_HEAD = CN({"BBOX_REG_WEIGHTS": ((10.0, 10.0, 5.0, 5.0), (20.0, 20.0, 10.0, 10.0), (30.0, 30.0, 15.0, 15.0)),
+                                 "IOUS": (0.5, 0.6, 0.7)})
     m.ROI_MASK_HEAD = CN({"NAME": "MaskRCNNConvUpsampleHead", "POOLER_RESOLUTION": 14, "POOLER_SAMPLING_RATIO": 0, "NUM_CONV": 0,
                           "CONV_DIM": 256, "NORM": "", "CLS_AGNOSTIC_MASK": False, "POOLER_TYPE": "ROIAlignV2"})
     c.INPUT = CN({"MIN_SIZE_TRAIN": (800,), "MIN_SIZE_TRAIN_SAMPLING": "choice", "MAX_SIZE_TRAIN": 1333, "MIN_SIZE_TEST": 800,

@@ -86,6 +86,7 @@ class OpensetRCNNEngine:
     FP32_POINTS = ("backbone", "rpn_hidden", "pooled", "h1")
     BOX_HEADS = ("storage", "split")
     CONVS = ("storage", "split")
+    ROI_LOSSES_NEED_IMAGE_HW = False  # roi_losses_forward takes image_hw whether or not a mask branch trains (engine_cascade.py)
 
     def __init__(self, params: Dict[str, torch.Tensor], cfg: Optional[dict] = None, dtype: torch.dtype = torch.float16,
                  device: str = "cuda", class_map: Optional[torch.Tensor] = None, fp32_points: Sequence[str] = (), box_head: str = "storage",
@@ -746,6 +747,8 @@ class OpensetRCNNEngine:
         c = self.cfg
         n = images.shape[0]
         mask_kw = {} if gt_masks is None else dict(gt_masks=gt_masks, image_hw=image_hw)
+        if self.ROI_LOSSES_NEED_IMAGE_HW:
+            mask_kw["image_hw"] = image_hw
         feats = self._backbone(images, hp, wp, keep)
         sel = self._rpn(feats, image_hw, keep, topk=c["pre_nms_topk_train"])
         if keep is not None:

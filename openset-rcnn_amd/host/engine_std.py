@@ -189,6 +189,13 @@ class StandardRCNNEngine(OpensetRCNNEngine):
         deltas = ops.gemm_f32(box_feats, self.box_w, self.box_b)
         k = c["std_num_classes"]
         cands = ops.fastrcnn_candidates(logits, deltas, sel["boxes"], sel["counts"], image_hw, k, c["bbox_reg_weights"], c["score_thresh_test"])
+        if keep is not None:
+            keep.update(pooled=pooled, h1=h1, box_feats=box_feats, logits=logits, deltas=deltas)
+        return self._detections(feats, cands, n, keep, mask)
+
+    def _detections(self, feats, cands, n, keep=None, mask: bool = True):
+        """[d2] fast_rcnn_inference behind the candidates: per-class NMS, the best DETECTIONS_PER_IMAGE, then the mask head on them."""
+        c = self.cfg
         topk = c["std_detections_per_image"]
         dk, dcnt = ops.nms_topk(cands["boxes"], cands["scores"], cands["cls"], None, n, cands["cap"], cands["count"], c["std_nms_thresh_test"], topk)
         ob = ops.gather_rows(cands["boxes"].view(-1, 4), cands["cap"], dk, dcnt)
@@ -197,7 +204,7 @@ class StandardRCNNEngine(OpensetRCNNEngine):
         ocl = ops.gather_rows(cands["cls"].view(-1).view(torch.float32), cands["cap"], dk, dcnt).view(n, topk).view(torch.int32).to(torch.int64)
         ocl = torch.where(torch.arange(topk, device=self.device)[None, :] < dcnt[:, None], ocl, torch.full_like(ocl, -1))
         if keep is not None:
-            keep.update(pooled=pooled, h1=h1, box_feats=box_feats, logits=logits, deltas=deltas, cands=cands, det_keep=dk, det_count=dcnt)
+            keep.update(cands=cands, det_keep=dk, det_count=dcnt)
         if self.has_mask and mask:  # (a fifth output only when the engine has a mask head: MASK_ON False returns what it always has)
             return ob, osc, ocl, dcnt, self._mask_head(feats, ob, ocl, dcnt)
         return ob, osc, ocl, dcnt

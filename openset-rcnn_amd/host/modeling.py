@@ -26,6 +26,7 @@ from torch import nn
 from . import ops, parallel
 from .config import CfgNode
 from .engine import DEFAULT_CFG, OpensetRCNNEngine
+from .engine_cascade import CascadeRCNNEngine, check_cascade_options
 from .engine_std import StandardRCNNEngine, check_std_supported
 from .structures import Boxes, ImageList, Instances, ShapeSpec
 from .weights import R50_BLOCKS, R50_MID, fold_frozen_bn
@@ -583,6 +584,9 @@ def engine_cfg_from(cfg: CfgNode) -> dict:
         rpn_nms_thresh=cfg.MODEL.RPN.NMS_THRESH, rpn_bbox_reg_weights=tuple(cfg.MODEL.RPN.BBOX_REG_WEIGHTS), std_num_classes=rh.NUM_CLASSES,
         score_thresh_test=rh.SCORE_THRESH_TEST, std_nms_thresh_test=rh.NMS_THRESH_TEST, std_detections_per_image=cfg.TEST.DETECTIONS_PER_IMAGE,
         cls_agnostic_bbox_reg=bool(bh.CLS_AGNOSTIC_BBOX_REG), post_nms_topk_train=cfg.MODEL.RPN.POST_NMS_TOPK_TRAIN, rpn_cls_weight=rpn.LOSS_WEIGHT,
+        # [d2] CascadeROIHeads (engine_cascade.CascadeRCNNEngine): one entry per stage
+        cascade_bbox_reg_weights=tuple(tuple(w) if isinstance(w, (list, tuple)) else w for w in cfg.MODEL.ROI_BOX_CASCADE_HEAD.BBOX_REG_WEIGHTS),
+        cascade_ious=tuple(cfg.MODEL.ROI_BOX_CASCADE_HEAD.IOUS),
         # checked by engine.check_supported_losses when a loss is first computed (inference never needs them)
         loss_types=dict(rpn_box=(rpn.BBOX_REG_LOSS_TYPE, float(rpn.SMOOTH_L1_BETA)), rpn_ctr=(rpn.CTR_REG_LOSS_TYPE, float(rpn.CTR_SMOOTH_L1_BETA)),
                         roi_box=(bh.BBOX_REG_LOSS_TYPE, float(bh.SMOOTH_L1_BETA)), roi_iou=(bh.IOU_REG_LOSS_TYPE, float(bh.IOU_SMOOTH_L1_BETA))),
@@ -781,11 +785,13 @@ class StandardROIHeads(_EngineOwner):
             mask_kw = dict(gt_masks=planes.to(dev), image_hw=torch.tensor(sizes, dtype=torch.int32, device=dev))
         else:
             gt, gcls, gcnt = pad_ground_truth(targets)
+        if eng.ROI_LOSSES_NEED_IMAGE_HW and not mask_kw:
+            mask_kw = dict(image_hw=torch.tensor([tuple(int(v) for v in t.image_size) for t in targets], dtype=torch.int32, device=dev))
         keys = torch.rand((n, cap + gt.shape[1]), generator=self.sampler_generator).to(dev)
         feats = {k: _to_nhwc(features[k], eng.dtype) for k in self.in_features}
         with torch.no_grad():
             losses, st = eng.roi_losses_forward(feats, boxes, scores, counts, gt.to(dev), gcls.to(dev), gcnt.to(dev), keys, **mask_kw)
-        smp = st["smp"]
+        smp = st["smp"]  # ([d2] CascadeROIHeads returns these too: the first stage's sampled proposals)
         host = smp["counts"].cpu()
         self.storage = {"roi_head/num_fg_samples": float(host[:, 1].sum()) / n, "roi_head/num_bg_samples": float(host[:, 2].sum()) / n}
         out = []
@@ -797,7 +803,7 @@ class StandardROIHeads(_EngineOwner):
             r.gt_classes = smp["gt_classes"][i, :k]
             r.gt_boxes = Boxes(smp["gt_boxes"][i, :k])
             out.append(r)
-        return out, {k: losses[k] for k in ("loss_cls", "loss_box_reg", "loss_mask") if k in losses}
+        return out, {k: v for k, v in losses.items() if k.startswith("loss_")}
 
     def forward(self, images: ImageList, features: Dict[str, torch.Tensor], proposals: List[Instances], targets=None):
         del images
@@ -854,6 +860,30 @@ class StandardROIHeads(_EngineOwner):
         return out
 
 
+@ROI_HEADS_REGISTRY.register()
+class CascadeROIHeads(StandardROIHeads):
+    """[d2] CascadeROIHeads (Cascade R-CNN; configs/cascade_rcnn_fpn.yaml): S = len(MODEL.ROI_BOX_CASCADE_HEAD.IOUS) box stages.
+    `box_head` and `box_predictor` are ModuleLists of S entries under [d2]'s parameter names (roi_heads.box_head.{s}.fc1.weight,
+    roi_heads.box_predictor.{s}.cls_score.weight, roi_heads.box_predictor.{s}.bbox_pred.weight with 4 rows), so model-zoo cascade
+    checkpoints load. Inference: every stage refines the previous stage's boxes, the stages' class scores are averaged, the last
+    stage's boxes are kept. Training: stage 0 on label_and_sample_proposals' rows, stage s on the previous stage's boxes re-labelled
+    at IOUS[s]; losses loss_cls_stage{s} / loss_box_reg_stage{s}; the mask head (MODEL.MASK_ON) trains on stage 0's rows and runs on
+    the final detections. What [d2] asserts is refused with a ValueError when the model is built."""
+    _engine_cls = CascadeRCNNEngine
+
+    def __init__(self, cfg: CfgNode, input_shape: Dict[str, ShapeSpec], class_id=None):
+        ch = cfg.MODEL.ROI_BOX_CASCADE_HEAD
+        stages = check_cascade_options(ch.IOUS, ch.BBOX_REG_WEIGHTS, first_iou=cfg.MODEL.ROI_HEADS.IOU_THRESHOLDS[0],
+                                       cls_agnostic=bool(cfg.MODEL.ROI_BOX_HEAD.CLS_AGNOSTIC_BBOX_REG))
+        super().__init__(cfg, input_shape, class_id)
+        res = cfg.MODEL.ROI_BOX_HEAD.POOLER_RESOLUTION
+        shape = ShapeSpec(channels=input_shape[self.in_features[0]].channels, height=res, width=res)
+        heads = [ROI_BOX_HEAD_REGISTRY.get(cfg.MODEL.ROI_BOX_HEAD.NAME)(cfg, shape) for _ in range(stages)]
+        self.box_predictor = nn.ModuleList([FastRCNNOutputLayers(cfg, h.output_shape) for h in heads])
+        self.box_head = nn.ModuleList(heads)
+        self.num_cascade_stages = stages
+
+
 def _std_instances(image_size, r: dict) -> Instances:
     """Instances of one image from OpensetRCNNEngine.to_instances' dict; pred_masks (k, 1, M, M) probabilities when the engine has a
     mask head ([d2] mask_rcnn_inference)."""
@@ -906,8 +936,8 @@ class GeneralizedRCNN(_EngineOwner):
         self._eng_cfg = engine_cfg_from(cfg)
         self._freeze_at = freeze_at_of(cfg)  # the trainer's (a negative value is refused here, when the model is built)
         self._class_map = class_id
-        self._engine_cls = StandardRCNNEngine if isinstance(self.roi_heads, StandardROIHeads) else OpensetRCNNEngine
-        if self._engine_cls is StandardRCNNEngine:
+        self._engine_cls = self.roi_heads._engine_cls if isinstance(self.roi_heads, StandardROIHeads) else OpensetRCNNEngine
+        if issubclass(self._engine_cls, StandardRCNNEngine):
             self._eng_cfg["pooler_scales"] = self.roi_heads._eng_cfg["pooler_scales"]
         self._trainer = None
         self._hook: Optional[torch.Tensor] = None
@@ -982,6 +1012,7 @@ class GeneralizedRCNN(_EngineOwner):
         trainable, un-folded from their FrozenBN; FPN; heads);
         `load_trainer_state(trainer)` writes them back into the module for evaluation / checkpointing."""
         from .train import OpensetRCNNTrainer
+        from .train_cascade import CascadeRCNNTrainer
         from .train_std import StandardRCNNTrainer
         if self._mask_training() is False:
             raise NotImplementedError(MASK_LOSS_MESSAGE)
@@ -998,10 +1029,11 @@ class GeneralizedRCNN(_EngineOwner):
                 bn[pre] = (sd[pre + ".weight"], scale)
         # class_map: the GraspNet id_map of the PLN / classifier losses (prototype_learning_network.py:80-95) -- without it the
         # trainer would treat dataset ids 0..NUM_KNOWN-1 as the known classes
-        if self._engine_cls is StandardRCNNEngine:  # the trainer by engine class: Base-RCNN-FPN.yaml's stock heads
-            return StandardRCNNTrainer(fold_frozen_bn(sd), self._eng_cfg, self.kernel_dtype, str(self.device), lr=lr, momentum=momentum,
-                                       weight_decay=weight_decay, loss_scale=loss_scale, freeze_at=self._freeze_at, frozen_bn=bn,
-                                       box_head=self._box_head_precision())  # ("split" is refused: ValueError, as engine() does)
+        if issubclass(self._engine_cls, StandardRCNNEngine):  # the trainer by engine class: Base-RCNN-FPN.yaml's stock heads, or the cascade
+            cls = CascadeRCNNTrainer if issubclass(self._engine_cls, CascadeRCNNEngine) else StandardRCNNTrainer
+            return cls(fold_frozen_bn(sd), self._eng_cfg, self.kernel_dtype, str(self.device), lr=lr, momentum=momentum,
+                       weight_decay=weight_decay, loss_scale=loss_scale, freeze_at=self._freeze_at, frozen_bn=bn,
+                       box_head=self._box_head_precision())  # ("split" is refused: ValueError, as engine() does)
         # the trainer's box head multiplies as the model's engine does: a model evaluated with box_head_precision="split" trains that way
         return OpensetRCNNTrainer(fold_frozen_bn(sd), self._eng_cfg, self.kernel_dtype, str(self.device), lr=lr, momentum=momentum,
                                   weight_decay=weight_decay, loss_scale=loss_scale, freeze_at=self._freeze_at, frozen_bn=bn,
@@ -1055,11 +1087,11 @@ class GeneralizedRCNN(_EngineOwner):
         shapes.append(((shapes[-1][0] - 1) // 2 + 1, (shapes[-1][1] - 1) // 2 + 1))
         r = sum(a * b for a, b in shapes)
         cap = sum(min(ecfg["pre_nms_topk_train"], a * b) for a, b in shapes)
-        if self._engine_cls is StandardRCNNEngine:  # A anchors per location; the RoI heads sample from the POST_NMS_TOPK_TRAIN list
+        if issubclass(self._engine_cls, StandardRCNNEngine):  # A anchors per location; the RoI heads sample from the POST_NMS_TOPK_TRAIN list
             r *= len(ecfg["anchor_ratios"])
             cap = ecfg["post_nms_topk_train"]
         # (the stock RPN has one label set: no objectness keys)
-        kinds = (("rpn_reg", (n, r)), ("roi", (n, cap + gmax))) if self._engine_cls is StandardRCNNEngine else \
+        kinds = (("rpn_reg", (n, r)), ("roi", (n, cap + gmax))) if issubclass(self._engine_cls, StandardRCNNEngine) else \
             (("rpn_reg", (n, r)), ("rpn_obj", (n, r)), ("roi", (n, cap + gmax)))
         keys = {k: torch.rand(shape, generator=generator).to(dev) for k, shape in kinds}
         hw = torch.tensor(sizes, dtype=torch.int32, device=dev)

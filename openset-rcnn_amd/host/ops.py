@@ -884,6 +884,68 @@ def fastrcnn_candidates(logits, deltas, prop_boxes, prop_count, image_hw, num_cl
     return o
 
 
+CASCADE_MAX_STAGES = 4   # include/osr.h OSR_CASCADE_MAX_STAGES
+CASCADE_MAX_GT = 1024    # csrc/osr_cascade.hip CR_MAX_GT: an image's ground truth in the refine kernel's LDS table
+
+
+def cascade_refine(boxes, batch_idx, deltas, n: int, image_hw, reg_weights, drop_empty: bool = False, gt_boxes=None, gt_classes=None,
+                   gt_count=None, num_classes: int = 0, iou_thr: float = 0.5):
+    """[d2] CascadeROIHeads between two stages (include/osr.h osr_cascade_refine): boxes (m,4) fp32, batch_idx (m) int32 (-1: the row
+    does not exist), deltas (m,4) class-agnostic, m = n x rows per image. -> dict(boxes (m,4), batch_idx (m), counts (n,3) = {rows,
+    foreground, background}); with ground truth (gt_boxes (n,gmax,4), gt_classes (n,gmax) int64, gt_count (n) int32) also gt_classes (m)
+    int64 (-1: no row), gt_boxes (m,4) the matched box, gt_idx (m) int32 (-1 off foreground)."""
+    lib = _lib.load()
+    _need(boxes, torch.float32, "boxes"); _need(batch_idx, torch.int32, "batch_idx"); _need(deltas, torch.float32, "deltas")
+    _need(image_hw, torch.int32, "image_hw")
+    m, dev = batch_idx.numel(), boxes.device
+    if n < 1 or m % n or m == 0 or boxes.numel() != m * 4 or tuple(deltas.shape) != (m, 4) or image_hw.numel() != 2 * n:
+        raise OsrError(f"cascade_refine: boxes {tuple(boxes.shape)} / deltas {tuple(deltas.shape)} / batch_idx {tuple(batch_idx.shape)} do not fit "
+                       f"{n} images (class-agnostic deltas (m,4), m a multiple of n)")
+    o = dict(boxes=torch.empty((m, 4), dtype=torch.float32, device=dev), batch_idx=torch.empty((m,), dtype=torch.int32, device=dev),
+             counts=torch.empty((n, 3), dtype=torch.int32, device=dev))
+    gmax = 0
+    if gt_boxes is not None:
+        _need(gt_boxes, torch.float32, "gt_boxes"); _need(gt_classes, torch.int64, "gt_classes"); _need(gt_count, torch.int32, "gt_count")
+        gmax = gt_boxes.shape[1]
+        if gt_boxes.shape[0] != n or tuple(gt_classes.shape) != (n, gmax) or gt_count.numel() != n:
+            raise OsrError(f"cascade_refine: ground truth {tuple(gt_boxes.shape)} / {tuple(gt_classes.shape)} does not fit {n} images")
+        o.update(gt_classes=torch.empty((m,), dtype=torch.int64, device=dev), gt_boxes=torch.empty((m, 4), dtype=torch.float32, device=dev),
+                 gt_idx=torch.empty((m,), dtype=torch.int32, device=dev))
+    check(lib.osr_cascade_refine(_p(boxes), _p(batch_idx), _p(deltas), n, m // n, _p(image_hw), _f4(reg_weights), int(bool(drop_empty)),
+                                 _p(gt_boxes), _p(gt_classes), _p(gt_count), gmax, int(num_classes), float(iou_thr), _p(o["boxes"]),
+                                 _p(o["batch_idx"]), _p(o.get("gt_classes")), _p(o.get("gt_boxes")), _p(o.get("gt_idx")), _p(o["counts"]),
+                                 _stream()), "osr_cascade_refine")
+    return o
+
+
+def cascade_candidates(logits: Sequence[torch.Tensor], deltas, boxes, batch_idx, image_hw, num_classes: int, reg_weights=(30.0, 30.0, 15.0, 15.0),
+                       score_thresh: float = 0.05):
+    """[d2] CascadeROIHeads._forward_box at inference up to the NMS (include/osr.h osr_cascade_candidates): logits[s] (n*rows, K+1)
+    per stage, the last stage's deltas (n*rows, 4) and input boxes (n, rows, 4), batch_idx (n*rows) int32. The outputs of
+    fastrcnn_candidates; with one stage bit-identical to it."""
+    lib = _lib.load()
+    logits = list(logits)
+    if not 1 <= len(logits) <= CASCADE_MAX_STAGES:
+        raise OsrError(f"cascade_candidates: 1 .. {CASCADE_MAX_STAGES} stages, got {len(logits)}")
+    for s, l in enumerate(logits):
+        _need(l, torch.float32, f"logits[{s}]")
+    _need(deltas, torch.float32, "deltas"); _need(boxes, torch.float32, "boxes"); _need(batch_idx, torch.int32, "batch_idx")
+    _need(image_hw, torch.int32, "image_hw")
+    n, rows = boxes.shape[0], boxes.shape[1]
+    if any(tuple(l.shape) != (n * rows, num_classes + 1) for l in logits) or tuple(deltas.shape) != (n * rows, 4) or batch_idx.numel() != n * rows:
+        raise OsrError(f"cascade_candidates: logits {[tuple(l.shape) for l in logits]} / deltas {tuple(deltas.shape)} do not fit {n} x {rows} rows, "
+                       f"{num_classes} classes, class-agnostic deltas")
+    dev, cap = deltas.device, rows * num_classes
+    o = dict(boxes=torch.empty((n, cap, 4), dtype=torch.float32, device=dev), scores=torch.empty((n, cap), dtype=torch.float32, device=dev),
+             cls=torch.empty((n, cap), dtype=torch.int32, device=dev), row=torch.empty((n, cap), dtype=torch.int32, device=dev),
+             count=torch.empty((n,), dtype=torch.int32, device=dev), cap=cap)
+    ptrs = (C.c_void_p * len(logits))(*[l.data_ptr() for l in logits])
+    check(lib.osr_cascade_candidates(ptrs, len(logits), _p(deltas), num_classes, _p(boxes), _p(batch_idx), n, rows, _p(image_hw), _f4(reg_weights),
+                                     float(score_thresh), _p(o["boxes"]), _p(o["scores"]), _p(o["cls"]), _p(o["row"]), _p(o["count"]), _stream()),
+          "osr_cascade_candidates")
+    return o
+
+
 def _pyramid(feats, scales) -> "Pyramid":
     py = Pyramid()
     py.num_levels, py.c = len(feats), feats[0].shape[3]

@@ -385,6 +385,8 @@ class OpensetRCNNTrainer:
     def _forward(self, images, image_hw, hp, wp, gt_boxes, gt_classes, gt_count, keys, gt_masks=None):
         e = self.eng
         mask_kw = {} if gt_masks is None else dict(gt_masks=gt_masks, image_hw=image_hw)  # (the stock heads' mask branch)
+        if e.ROI_LOSSES_NEED_IMAGE_HW:  # (the cascade clips the boxes it hands from stage to stage)
+            mask_kw["image_hw"] = image_hw
         n = images.shape[0]
         s: dict = {}
         # anchor labels / sampling / targets depend on the ground truth only: a few small-grid launches (one workgroup per image)
@@ -713,9 +715,13 @@ class OpensetRCNNTrainer:
         ops.rpn_scatter_cols_add_(levels, n, rmap, y_rows, glist)
         return dict(zip(PYRAMID, glist))
 
-    def _box_head_bwd(self, s, d_bf, n):
-        """d box features (m,1024) fp32 -> FC2, FC1 (data + weight gradients) -> RoIAlign backward: the feature gradient per level."""
+    def _box_head_bwd(self, s, d_bf, n, fc=("fc1", "fc2"), pooled_grad_scale: float = 1.0, feat_f32: bool = False):
+        """d box features (m,1024) fp32 -> FC2, FC1 (data + weight gradients) -> RoIAlign backward: the feature gradient per level.
+        fc: the names of the two layers' masters and backward-data weights (a cascade has one pair per stage). pooled_grad_scale: a
+        factor on the gradient that leaves the box head for RoIAlign ([d2] _ScaleGradient on the pooled features). feat_f32: the
+        feature gradient in fp32 whatever the storage type (the caller sums several)."""
         c, g, dt = self.eng.cfg, self.grad, self.dtype
+        fc1, fc2 = fc
         p = s["p"]
         if self.box_head_probe is not None:
             self.box_head_probe["d_bf"] = d_bf.clone()
@@ -724,32 +730,34 @@ class OpensetRCNNTrainer:
         if self.box_head == "split":
             # --- box head in fp32 operands: no cast of d_bf; FC2, FC1 on the split-precision kernels (the ReLU mask of h1 in the data
             #     gradient's epilogue), weight / bias gradients from the fp32 rows on the second stream ---
-            d_h1 = ops.linear_split_dgrad(d_bf, self.wt_split["fc2"], mask=s["h1"])
-            self._wg(lambda: (ops.linear_split_wgrad(s["h1"], d_bf, dw=g["fc2.w"]), ops.bias_grad(d_bf, g["fc2.b"])), d_bf)
-            self._done("fc2.w", "fc2.b")
+            d_h1 = ops.linear_split_dgrad(d_bf, self.wt_split[fc2], mask=s["h1"])
+            self._wg(lambda: (ops.linear_split_wgrad(s["h1"], d_bf, dw=g[fc2 + ".w"]), ops.bias_grad(d_bf, g[fc2 + ".b"])), d_bf)
+            self._done(fc2 + ".w", fc2 + ".b")
             pooled2 = s["pooled"].view(m, -1)
-            d_pooled = ops.linear_split_dgrad(d_h1, self.wt_split["fc1"])  # fp32: RoIAlign's backward sums it in fp32, _roi_share casts
-            self._wg(lambda: (ops.linear_split_wgrad(pooled2, d_h1, dw=g["fc1.w"]), ops.bias_grad(d_h1, g["fc1.b"])), d_h1)
-            self._done("fc1.w", "fc1.b")
+            d_pooled = ops.linear_split_dgrad(d_h1, self.wt_split[fc1])  # fp32: RoIAlign's backward sums it in fp32, _roi_share casts
+            self._wg(lambda: (ops.linear_split_wgrad(pooled2, d_h1, dw=g[fc1 + ".w"]), ops.bias_grad(d_h1, g[fc1 + ".b"])), d_h1)
+            self._done(fc1 + ".w", fc1 + ".b")
         else:
             dy2 = ops.add_cast(d_bf, None, dt)                                                  # (m,1024) low precision
             # --- box head: FC2, FC1 on the MFMA kernels ---
-            d_h1 = ops.conv2d_dgrad(dy2.view(1, m, 1, -1), self.wd["fc2"], (m, 1), mask=s["h1"].view(1, m, 1, -1)).view(m, -1)
-            self._wg(lambda: (ops.conv2d_wgrad(s["h1"].view(1, m, 1, -1), dy2.view(1, m, 1, -1), 1, 1, dw=g["fc2.w"].view(-1, 1, 1, g["fc2.w"].shape[1])),
-                              ops.bias_grad(dy2, g["fc2.b"])), dy2)
-            self._done("fc2.w", "fc2.b")
+            d_h1 = ops.conv2d_dgrad(dy2.view(1, m, 1, -1), self.wd[fc2], (m, 1), mask=s["h1"].view(1, m, 1, -1)).view(m, -1)
+            self._wg(lambda: (ops.conv2d_wgrad(s["h1"].view(1, m, 1, -1), dy2.view(1, m, 1, -1), 1, 1, dw=g[fc2 + ".w"].view(-1, 1, 1, g[fc2 + ".w"].shape[1])),
+                              ops.bias_grad(dy2, g[fc2 + ".b"])), dy2)
+            self._done(fc2 + ".w", fc2 + ".b")
             pooled2 = s["pooled"].view(1, m, 1, -1)
-            d_pooled = ops.conv2d_dgrad(d_h1.view(1, m, 1, -1), self.wd["fc1"], (m, 1))
-            self._wg(lambda: (ops.conv2d_wgrad(pooled2, d_h1.view(1, m, 1, -1), 1, 1, dw=g["fc1.w"].view(-1, 1, 1, g["fc1.w"].shape[1])),
-                              ops.bias_grad(d_h1, g["fc1.b"])), d_h1)
-            self._done("fc1.w", "fc1.b")
+            d_pooled = ops.conv2d_dgrad(d_h1.view(1, m, 1, -1), self.wd[fc1], (m, 1))
+            self._wg(lambda: (ops.conv2d_wgrad(pooled2, d_h1.view(1, m, 1, -1), 1, 1, dw=g[fc1 + ".w"].view(-1, 1, 1, g[fc1 + ".w"].shape[1])),
+                              ops.bias_grad(d_h1, g[fc1 + ".b"])), d_h1)
+            self._done(fc1 + ".w", fc1 + ".b")
+        if pooled_grad_scale != 1.0:  # (behind the weight gradients' launches, which read d_h1, not d_pooled)
+            d_pooled.mul_(pooled_grad_scale)
         if self.box_head_probe is not None:
             self.box_head_probe["d_pooled"] = d_pooled
         P = c["pooler_resolution"]
         shapes = [(p[k].shape[1], p[k].shape[2]) for k in PYRAMID[:4]]
         d_feat = ops.roi_align_bwd(d_pooled.view(m, P, P, -1), shapes, n, c["pooler_scales"], s["boxes"], s["smp"]["batch_idx"], c["canonical_level"],
                                    c["canonical_size"], 2, rois_per_image=m // n if m % n == 0 else None,  # (the sampled list is (n, S))
-                                   out_dtype=dt if d_pooled.dtype == dt else None, aligned=c["pooler_aligned"],
+                                   out_dtype=dt if d_pooled.dtype == dt and not feat_f32 else None, aligned=c["pooler_aligned"],
                                    sampling_ratio=c["pooler_sampling_ratio"])
         if self.box_head_probe is not None:
             self.box_head_probe["d_feat"] = [d.clone() for d in d_feat]  # (the RPN's share is added into these tensors later)
@@ -997,10 +1005,16 @@ class OpensetRCNNTrainer:
             out[n + ".weight"] = self.master[n + ".w"].permute(0, 3, 1, 2).contiguous().cpu()
             if n + ".b" in self.master:
                 out[n + ".bias"] = self.master[n + ".b"].cpu().clone()
-        pr = self.eng.cfg["pooler_resolution"]
-        fc1 = self.master["fc1.w"]  # (out, ph, pw, c) flattened -> the reference's (out, c*ph*pw)
-        out["roi_heads.box_head.fc1.weight"] = fc1.view(fc1.shape[0], pr, pr, -1).permute(0, 3, 1, 2).reshape(fc1.shape[0], -1).contiguous().cpu()
-        out["roi_heads.box_head.fc1.bias"] = self.master["fc1.b"].cpu().clone()
-        out["roi_heads.box_head.fc2.weight"] = self.master["fc2.w"].cpu().clone()
-        out["roi_heads.box_head.fc2.bias"] = self.master["fc2.b"].cpu().clone()
+        self._export_box_heads(out)
         return out
+
+    def _export_box_heads(self, out: Dict[str, torch.Tensor]) -> None:
+        self._export_box_head(out, "fc1", "fc2", "roi_heads.box_head.")
+
+    def _export_box_head(self, out: Dict[str, torch.Tensor], fc1_name: str, fc2_name: str, prefix: str) -> None:
+        pr = self.eng.cfg["pooler_resolution"]
+        fc1 = self.master[fc1_name + ".w"]  # (out, ph, pw, c) flattened -> the reference's (out, c*ph*pw)
+        out[prefix + "fc1.weight"] = fc1.view(fc1.shape[0], pr, pr, -1).permute(0, 3, 1, 2).reshape(fc1.shape[0], -1).contiguous().cpu()
+        out[prefix + "fc1.bias"] = self.master[fc1_name + ".b"].cpu().clone()
+        out[prefix + "fc2.weight"] = self.master[fc2_name + ".w"].cpu().clone()
+        out[prefix + "fc2.bias"] = self.master[fc2_name + ".b"].cpu().clone()

@@ -95,6 +95,12 @@ class StandardRCNNTrainer(OpensetRCNNTrainer):
         e.rpn_btail = torch.cat([e.rpn_bo, e.rpn_bd]).contiguous()
         e.rpn_wo, e.rpn_wd, e.rpn_bo, e.rpn_bd = e.rpn_wtail[:a], e.rpn_wtail[a:], e.rpn_btail[:a], e.rpn_btail[a:]
         self.master["rpn_tail.w"], self.master["rpn_tail.b"] = e.rpn_wtail, e.rpn_btail
+        self._add_box_masters(params)
+        self._pixel_lv: Dict[tuple, object] = {}
+
+    def _add_box_masters(self, params) -> None:
+        """The box head and the two output layers (CascadeRCNNTrainer: one set per stage)."""
+        e, dev = self.eng, self.eng.device
         self.master["fc1.w"] = pack_fc1_weight(params["roi_heads.box_head.fc1.weight"], 256, e.cfg["pooler_resolution"], torch.float32).to(dev)
         self.lowp["fc1.w"] = e.fc1_w
         self.master["fc1.b"] = e.fc1_b
@@ -103,7 +109,6 @@ class StandardRCNNTrainer(OpensetRCNNTrainer):
         self.master["fc2.b"] = e.fc2_b
         self.master["box.w"], self.master["box.b"] = e.box_w, e.box_b
         self.master["cls.w"], self.master["cls.b"] = e.cls_w, e.cls_b
-        self._pixel_lv: Dict[tuple, object] = {}
 
     def _param_rows(self):
         a = self.eng.num_anchors
@@ -111,11 +116,7 @@ class StandardRCNNTrainer(OpensetRCNNTrainer):
 
     def _refresh_heads(self) -> None:
         e = self.eng
-        if not hasattr(self, "t_cls"):  # zero-padded transposes of the fp32 output layers: the padding columns are written once
-            self.t_cls = torch.zeros((e.cls_w.shape[1], _pad16(e.cls_w.shape[0])), dtype=torch.float32, device=e.device)
-            self.t_box = torch.zeros((e.box_w.shape[1], _pad16(e.box_w.shape[0])), dtype=torch.float32, device=e.device)
-        self.t_cls[:, : e.cls_w.shape[0]].copy_(e.cls_w.t())
-        self.t_box[:, : e.box_w.shape[0]].copy_(e.box_w.t())
+        self._refresh_box_heads()
         # the RPN 3x3 conv's weight as the (2304, 256) matrix of its per-tap data gradient y = dt . W (a function of the parameters)
         w3 = e.w[RPN_CONV + ".w"].view(256, 9 * 256)
         if not hasattr(self, "w3_t"):
@@ -126,6 +127,14 @@ class StandardRCNNTrainer(OpensetRCNNTrainer):
             if not hasattr(self, "mask_deconv_wt"):
                 self.mask_deconv_wt = torch.empty_like(wt)
             self.mask_deconv_wt.copy_(wt)
+
+    def _refresh_box_heads(self) -> None:
+        e = self.eng
+        if not hasattr(self, "t_cls"):  # zero-padded transposes of the fp32 output layers: the padding columns are written once
+            self.t_cls = torch.zeros((e.cls_w.shape[1], _pad16(e.cls_w.shape[0])), dtype=torch.float32, device=e.device)
+            self.t_box = torch.zeros((e.box_w.shape[1], _pad16(e.box_w.shape[0])), dtype=torch.float32, device=e.device)
+        self.t_cls[:, : e.cls_w.shape[0]].copy_(e.cls_w.t())
+        self.t_box[:, : e.box_w.shape[0]].copy_(e.box_w.t())
 
     def _pixel_levels(self, shapes, n):
         """Level table of the pixel rows (one row per location): what the sparse gather / scatter walk."""
@@ -204,7 +213,18 @@ class StandardRCNNTrainer(OpensetRCNNTrainer):
 
         rpn_grad, rpn_ready = self._on_side(rpn_chain)
         self._done("rpn_tail.w", "rpn_tail.b", rn + ".w", rn + ".b")
-        # --- Fast R-CNN losses -> cls_score / bbox_pred (fp32) -> box head -> RoIAlign ---
+        d_feat = self._box_branch_bwd(s, n, S)
+        if e.has_mask:  # the branch's share joins the box branch's feature gradient (storage type) in front of the trunk
+            share = self._mask_head_bwd(s, n, S)
+            d_feat = [ops.add_cast(a_, b_, self.dtype) for a_, b_ in zip(share, self._roi_share(d_feat))] + list(d_feat[4:])
+        # --- RPN 3x3 conv: col2im of the listed anchors' per-tap gradients into the RoI heads' feature gradient (p6: into zeros) ---
+        self._join_side(rpn_ready, rpn_grad)
+        self._backward_trunk(s, self._sparse_rpn_scatter(self._pixel_levels(s["rpn_shapes"], n), s, n, rpn_grad, d_feat), prefetch)
+
+    def _box_branch_bwd(self, s, n, S: float):
+        """Fast R-CNN losses -> cls_score / bbox_pred (fp32) -> box head -> RoIAlign: the box branch's share of the p2..p5 feature
+        gradient (times S); writes its masters' gradients."""
+        e, c = self.eng, self.eng.cfg
         k = c["std_num_classes"]
         d_logits, d_deltas = ops.fastrcnn_losses_bwd(s["logits"], s["deltas"], s["boxes"], s["smp"]["gt_boxes"].view(-1, 4), s["cls"], k,
                                                      e.box_w.shape[0] == 4, c["bbox_reg_weights"], std_loss_beta(c, "roi_box"),
@@ -212,13 +232,7 @@ class StandardRCNNTrainer(OpensetRCNNTrainer):
         d_bf = self._f32_linear_bwd(s["box_feats"], d_logits, self.t_cls, "cls", dy_pad=self.t_cls.shape[1])
         d_bf2 = self._f32_linear_bwd(s["box_feats"], d_deltas, self.t_box, "box", dy_pad=self.t_box.shape[1])
         d_bf = ops.add_cast(d_bf, d_bf2, torch.float32)
-        d_feat = self._box_head_bwd(s, d_bf, n)
-        if e.has_mask:  # the branch's share joins the box branch's feature gradient (storage type) in front of the trunk
-            share = self._mask_head_bwd(s, n, S)
-            d_feat = [ops.add_cast(a_, b_, self.dtype) for a_, b_ in zip(share, self._roi_share(d_feat))] + list(d_feat[4:])
-        # --- RPN 3x3 conv: col2im of the listed anchors' per-tap gradients into the RoI heads' feature gradient (p6: into zeros) ---
-        self._join_side(rpn_ready, rpn_grad)
-        self._backward_trunk(s, self._sparse_rpn_scatter(self._pixel_levels(s["rpn_shapes"], n), s, n, rpn_grad, d_feat), prefetch)
+        return self._box_head_bwd(s, d_bf, n)
 
     def _mask_head_bwd(self, s, n, S: float) -> List[torch.Tensor]:
         """loss_mask's gradient: BCE -> predictor, ReLU, deconv (one launch) -> ReLU, mask_fcnN .. mask_fcn1 -> 14 x 14 RoIAlign. Writes
@@ -269,6 +283,13 @@ class StandardRCNNTrainer(OpensetRCNNTrainer):
     def export_state_dict(self) -> Dict[str, torch.Tensor]:
         """The trainable parameters under detectron2 names and layouts (StandardRPNHead, FastRCNNOutputLayers keys; with the mask
         branch MaskRCNNConvUpsampleHead's: mask_fcn* come with the other convolutions, deconv (Cin, Cmid, 2, 2), predictor (K, Cmid, 1, 1))."""
+        out = self._export_rpn_and_mask()
+        for short, long in (("cls", "roi_heads.box_predictor.cls_score"), ("box", "roi_heads.box_predictor.bbox_pred")):
+            out[long + ".weight"], out[long + ".bias"] = self.master[short + ".w"].cpu().clone(), self.master[short + ".b"].cpu().clone()
+        return out
+
+    def _export_rpn_and_mask(self) -> Dict[str, torch.Tensor]:
+        """The trunk, the box head's FC layers, the mask head and the RPN head's output layers."""
         out = self._export_trunk()
         if self.eng.has_mask:
             out[MASK_PRE + "deconv.weight"] = unpack_deconv_weight(self.master["mask_deconv.w"]).cpu()
@@ -282,6 +303,4 @@ class StandardRCNNTrainer(OpensetRCNNTrainer):
         out["proposal_generator.rpn_head.objectness_logits.bias"] = t_b[:a].clone()
         out["proposal_generator.rpn_head.anchor_deltas.weight"] = t_w[a:].reshape(4 * a, -1, 1, 1).clone()
         out["proposal_generator.rpn_head.anchor_deltas.bias"] = t_b[a:].clone()
-        for short, long in (("cls", "roi_heads.box_predictor.cls_score"), ("box", "roi_heads.box_predictor.bbox_pred")):
-            out[long + ".weight"], out[long + ".bias"] = self.master[short + ".w"].cpu().clone(), self.master[short + ".b"].cpu().clone()
         return out

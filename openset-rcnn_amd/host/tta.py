@@ -44,7 +44,10 @@ class GeneralizedRCNNWithTTA(nn.Module):
 
     def __init__(self, cfg, model):
         super().__init__()
-        from .modeling import GeneralizedRCNN, StandardROIHeads
+        from .modeling import CascadeROIHeads, GeneralizedRCNN, StandardROIHeads
+        if isinstance(getattr(model, "roi_heads", None), CascadeROIHeads):
+            raise ValueError("TEST.AUG: test-time augmentation is not implemented for CascadeROIHeads (the merge re-scores the augmented boxes with "
+                             "one box head; a cascade has one per stage)")
         if not isinstance(model, GeneralizedRCNN) or not isinstance(model.roi_heads, StandardROIHeads):
             raise ValueError(f"TEST.AUG: test-time augmentation is implemented for StandardROIHeads only, not {type(getattr(model, 'roi_heads', model)).__name__} "
                              "(the merge indexes a (rows, NUM_CLASSES + 1) score table with the class id, which the Openset heads' unknown id does not fit)")

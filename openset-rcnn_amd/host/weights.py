@@ -210,3 +210,19 @@ def random_standard_params(seed: int = 0, num_classes: int = 80, num_anchors: in
     p["roi_heads.box_predictor.bbox_pred.weight"] = torch.randn(4 if cls_agnostic else 4 * num_classes, fc_dim, generator=g) * 0.03
     p["roi_heads.box_predictor.bbox_pred.bias"] = torch.zeros(4 if cls_agnostic else 4 * num_classes)
     return p
+
+
+def random_cascade_params(seed: int = 0, stages: int = 3, num_classes: int = 80, num_anchors: int = 3, fc_dim: int = 1024) -> Dict[str, torch.Tensor]:
+    """random_standard_params with [d2] CascadeROIHeads' box stages: roi_heads.box_head.{s}.* and roi_heads.box_predictor.{s}.* for
+    s < stages (class-agnostic bbox_pred). Stage 0 carries random_standard_params(seed)'s box head and output layers, stage s > 0
+    those of seed + 100 s, so a one-stage cascade computes what the stock heads compute."""
+    p = {}
+    for s in range(stages):
+        for k, v in random_standard_params(seed + 100 * s, num_classes, num_anchors, True, fc_dim).items():
+            if k.startswith("roi_heads.box_head."):
+                p[f"roi_heads.box_head.{s}." + k[len("roi_heads.box_head."):]] = v
+            elif k.startswith("roi_heads.box_predictor."):
+                p[f"roi_heads.box_predictor.{s}." + k[len("roi_heads.box_predictor."):]] = v
+            elif s == 0:
+                p[k] = v
+    return p
