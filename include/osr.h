@@ -523,8 +523,9 @@ osr_status osr_l2_normalize_rows(const float* x, int32_t rows, int32_t d, float*
  * PLN inference tail (prototype_learning_network.py:206-223, COS distance): normalise each embedding, cosine
  * distance to the (already normalised) prototypes, min over reps then min/argmin over classes (ties: lower
  * class), unknown if min > unk_thr. class_map (nullable, (num_known)): GraspNet class_id remap (:222).
- * emb: (rows, d). rows_valid (nullable): per-segment valid counts for padded (segments, seg_rows) layouts;
- * padded rows get class -1. Outputs: pred_class (rows) int64, min_dist (rows).
+ * emb: (rows, d). rows_valid (nullable): per-segment valid counts for padded (segments, seg_rows) layouts
+ * (rows must then be a multiple of seg_rows: OSR_ERR_INVALID_ARG otherwise); padded rows get class -1 and
+ * distance 0. Outputs: pred_class (rows) int64, min_dist (rows).
  * --------------------------------------------------------------------------------------------------------- */
 osr_status osr_pln_tail(const float* emb, int64_t rows, int32_t d, const float* protos_normed, int32_t num_known,
                         int32_t reps, float unk_thr, int64_t unknown_id, const int64_t* class_map,

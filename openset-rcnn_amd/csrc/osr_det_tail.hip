@@ -333,13 +333,27 @@ __global__ __launch_bounds__(256) void l2norm_kernel(const float* __restrict__ x
     float ss = 0.f;
     for (int i = lane; i < d; i += 64) { float v = x[(long long)r * d + i]; ss += v * v; }
     ss = osr_wave_sum(ss);
+    if (ss > 3.402823466e38f) {  // the sum of squares left fp32's range (wave-uniform): norm = max|x| * ||x / max|x|||
+        float mx = 0.f;
+        for (int i = lane; i < d; i += 64) mx = fmaxf(mx, fabsf(x[(long long)r * d + i]));
+#pragma unroll
+        for (int s = 32; s > 0; s >>= 1) mx = fmaxf(mx, __shfl_xor(mx, s, 64));
+        if (osr_finite(mx)) {  // (a row that holds an Inf keeps the plain form below)
+            float s2 = 0.f;
+            for (int i = lane; i < d; i += 64) { float v = x[(long long)r * d + i] / mx; s2 += v * v; }
+            const float nrm = sqrtf(osr_wave_sum(s2));
+            for (int i = lane; i < d; i += 64) out[(long long)r * d + i] = x[(long long)r * d + i] / mx / nrm;
+            return;
+        }
+    }
     const float den = fmaxf(sqrtf(ss), 1e-12f);
     for (int i = lane; i < d; i += 64) out[(long long)r * d + i] = x[(long long)r * d + i] / den;
 }
 
 extern "C" osr_status osr_l2_normalize_rows(const float* x, int32_t rows, int32_t d, float* out, void* stream) {
-    OSR_REQUIRE(x && out && rows >= 0 && d >= 1, OSR_ERR_INVALID_ARG, "osr_l2_normalize_rows: bad arguments");
-    if (rows == 0) return OSR_OK;
+    OSR_REQUIRE(rows >= 0 && d >= 1, OSR_ERR_INVALID_ARG, "osr_l2_normalize_rows: bad arguments");
+    if (rows == 0) return OSR_OK;  // (an empty tensor has no storage: its pointers may be null)
+    OSR_REQUIRE(x && out, OSR_ERR_INVALID_ARG, "osr_l2_normalize_rows: null pointer");
     hipLaunchKernelGGL(l2norm_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, x, rows, d, out);
     OSR_CHECK_LAUNCH("osr_l2_normalize_rows");
     return OSR_OK;
@@ -399,6 +413,9 @@ extern "C" osr_status osr_pln_tail_ex(const float* emb, int64_t rows, int32_t d,
     OSR_REQUIRE(rows >= 0 && d >= 1 && num_known >= 1 && reps >= 1, OSR_ERR_INVALID_ARG, "osr_pln_tail: bad sizes");
     OSR_REQUIRE((long long)num_known * reps * d <= 36864, OSR_ERR_UNSUPPORTED, "osr_pln_tail: prototypes exceed the 144 KB LDS table");
     OSR_REQUIRE(!rows_valid || seg_rows >= 1, OSR_ERR_INVALID_ARG, "osr_pln_tail: seg_rows must be >= 1 with rows_valid");
+    // (a trailing partial segment would index rows_valid past its last entry)
+    OSR_REQUIRE(!rows_valid || rows % seg_rows == 0, OSR_ERR_INVALID_ARG, "osr_pln_tail: rows %lld is not a whole number of %d-row segments",
+                (long long)rows, seg_rows);
     if (rows == 0) return OSR_OK;
     long long blocks = (rows + 3) / 4;
     if (blocks > 2048) blocks = 2048;
