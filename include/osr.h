@@ -210,6 +210,23 @@ osr_status osr_maxpool3x3s2(const void* in, int32_t n, int32_t hi, int32_t wi, i
 osr_status osr_subsample2(const void* in, int32_t n, int32_t hi, int32_t wi, int32_t c, void* out, int32_t dtype,
                           void* stream);
 
+/* The gather half of a 3x3 deformable convolution, padding 1, dilation 1 ([d2] DeformConv / ModulatedDeformConv as
+ * DeformBottleneckBlock's conv2; MODEL.RESNETS.DEFORM_ON_PER_STAGE): cols (n*ho*wo, 9, c), x's dtype, holds for output pixel
+ * p = (b, y, x), tap k = 3 i + j and channel ch (group g = ch / (c / groups)) the masked bilinear sample
+ *     cols[p][k][ch] = m * bilinear(x[b, :, :, ch], y * stride - 1 + i + dy, x * stride - 1 + j + dx),
+ *     dy = om[p][2 (9 g + k)], dx = om[p][2 (9 g + k) + 1], m = sigmoid(om[p][18 groups + 9 g + k]) when modulated, else 1;
+ * the layer is then the 1x1 convolution of cols (as (1, n*ho*wo, 1, 9 c)) with the (cout, 3, 3, c) weight. x (n,h,w,c) NHWC
+ * contiguous f16 / bf16 / f32; om (n,ho,wo,ch) fp32, ch >= 18 groups (27 groups when modulated) the row pitch (channels beyond are
+ * padding, not read); ho = (h - 1) / stride + 1, wo likewise; stride 1 or 2.
+ * Bilinear rule at (hs, ws) on the h x w map: unless hs > -1, ws > -1, hs < h and ws < w the sample is 0 and nothing is read (NaN
+ * and +-Inf coordinates included); else with h0 = floor(hs), lh = hs - h0 (w alike) the corners (h0,w0), (h0,w0+1), (h0+1,w0),
+ * (h0+1,w0+1) weigh (1-lh)(1-lw), (1-lh) lw, lh (1-lw), lh lw, and a corner outside [0,h-1] x [0,w-1] contributes 0 and is not
+ * read. Blend and mask multiply in fp32, one rounding to the storage dtype. No atomics, no workspace; one launch on `stream`.
+ * c % 8 != 0, c % groups != 0, (c / groups) % 8 != 0, or n*ho*wo*9*c/8 >= 2^31: OSR_ERR_UNSUPPORTED with nothing launched. x and
+ * cols 16-byte aligned. */
+osr_status osr_deform_cols(const void* x, const float* om, int32_t n, int32_t h, int32_t w, int32_t c, int32_t ho, int32_t wo,
+                           int32_t ch, int32_t stride, int32_t groups, int32_t modulated, void* cols, int32_t dtype, void* stream);
+
 /* fp32 GEMM out[m,n] = a[m,k] * w[n,k]^T + bias[n] on the exact-f32 MFMA (PLN encoder/decoder,
  * prototype_learning_network.py:204-205; cls_score, softmax_classifier.py:306). lda/ldo in elements. */
 osr_status osr_gemm_f32(const float* a, int64_t lda, const float* w, const float* bias, float* out, int64_t ldo,

@@ -29,6 +29,7 @@ SOURCES = {
     "osr_conv_split.hip": [],
     "osr_bottleneck.hip": [],
     "osr_stem_pool.hip": [],
+    "osr_deform.hip": ["-ffp-contract=off"],  # (exact-index gather: the sample positions and the zero-offset / integer-offset results are bit-exact)
     "osr_rpn.hip": ["-ffp-contract=off"],
     "osr_roi_align.hip": ["-ffp-contract=off"],
     "osr_det_tail.hip": ["-ffp-contract=off"],

@@ -133,6 +133,7 @@ PROTOTYPES = {
     "osr_stem_wgrad_workspace_bytes": (I64, [I32, I32, I32]),
     "osr_stem_wgrad": (I32, [P, P, I32, I32, I32, P, I32, P, I64, I32, P]),
     "osr_subsample2": (I32, [P, I32, I32, I32, I32, P, I32, P]),
+    "osr_deform_cols": (I32, [P, P, I32, I32, I32, I32, I32, I32, I32, I32, I32, I32, P, I32, P]),
     "osr_gemm_f32": (I32, [P, I64, P, P, P, I64, I32, I32, I32, I32, P]),
     "osr_gemm_f32_tn_workspace_bytes": (I64, [I32, I32, I32]),
     "osr_gemm_f32_tn": (I32, [P, I64, P, I64, P, I64, I32, I32, I32, P, I64, P]),

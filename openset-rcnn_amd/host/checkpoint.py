@@ -86,7 +86,8 @@ def convert_d2_backbone_name(name: str) -> str:
     if name.startswith("stem.fc.") or name.endswith(".num_batches_tracked"):
         return ""
     if re.fullmatch(r"stem\.conv1\.(weight|norm\.(weight|bias|running_mean|running_var))", name) or \
-            re.fullmatch(r"res[2-5]\.\d+\.(shortcut|conv1|conv2|conv3)\.(weight|norm\.(weight|bias|running_mean|running_var))", name):
+            re.fullmatch(r"res[2-5]\.\d+\.(shortcut|conv1|conv2|conv3)\.(weight|norm\.(weight|bias|running_mean|running_var))", name) or \
+            re.fullmatch(r"res[2-5]\.\d+\.conv2_offset\.(weight|bias)", name):  # ([d2] DeformBottleneckBlock: bias, no norm)
         return _BOTTOM_UP + name
     raise KeyError(f"unrecognised detectron2 backbone name '{name}'")
 

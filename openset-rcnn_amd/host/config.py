@@ -147,7 +147,9 @@ def get_cfg() -> CfgNode:
     m.PIXEL_STD = [1.0, 1.0, 1.0]
     m.BACKBONE = CN({"NAME": "build_resnet_backbone", "FREEZE_AT": 2})
     m.RESNETS = CN({"DEPTH": 50, "OUT_FEATURES": ["res4"], "NUM_GROUPS": 1, "NORM": "FrozenBN", "WIDTH_PER_GROUP": 64,
-                    "STRIDE_IN_1X1": True, "RES5_DILATION": 1, "RES2_OUT_CHANNELS": 256, "STEM_OUT_CHANNELS": 64})
+                    "STRIDE_IN_1X1": True, "RES5_DILATION": 1, "RES2_OUT_CHANNELS": 256, "STEM_OUT_CHANNELS": 64,
+                    # [d2] DeformBottleneckBlock: a deformable conv2 in the blocks of res2..res5 (inference; host/engine.py _deform_conv2)
+                    "DEFORM_ON_PER_STAGE": [False, False, False, False], "DEFORM_MODULATED": False, "DEFORM_NUM_GROUPS": 1})
     m.FPN = CN({"IN_FEATURES": [], "OUT_CHANNELS": 256, "NORM": "", "FUSE_TYPE": "sum"})
     m.ANCHOR_GENERATOR = CN({"NAME": "DefaultAnchorGenerator", "SIZES": [[32, 64, 128, 256, 512]],
                              "ASPECT_RATIOS": [[0.5, 1.0, 2.0]], "ANGLES": [[-90, 0, 90]], "OFFSET": 0.0})

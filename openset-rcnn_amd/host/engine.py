@@ -17,7 +17,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import torch
 
 from . import ops
-from .weights import R50_BLOCKS, pack_conv_weight, pack_fc1_weight, pack_stem_weight, split_conv_weight, split_fp32_rows, split_stem_weight
+from .weights import R50_BLOCKS, R50_MID, pack_conv_weight, pack_fc1_weight, pack_stem_weight, split_conv_weight, split_fp32_rows, split_stem_weight
 
 BOTTOM_UP = "backbone.bottom_up"
 STEM = BOTTOM_UP + ".stem.conv1"
@@ -44,7 +44,36 @@ DEFAULT_CFG = dict(
     pln_alpha=0.1, pln_beta=0.9, pln_iou_threshold=0.5, pln_loss_weight=0.5, cls_loss_weight=0.9,
     # MODEL.RESNETS.STRIDE_IN_1X1: True (MSRA R-50.pkl) puts a stage's stride in conv1 of its first block, False (torchvision) in conv2
     stride_in_1x1=True,
+    # MODEL.RESNETS.DEFORM_ON_PER_STAGE (res2..res5) / DEFORM_MODULATED / DEFORM_NUM_GROUPS: [d2] DeformBottleneckBlock's deformable conv2
+    deform_on_per_stage=(False, False, False, False), deform_modulated=False, deform_num_groups=1,
 )
+
+DEFORM_KEY = "MODEL.RESNETS.DEFORM_ON_PER_STAGE"
+DEFORM_TRAINING_MESSAGE = (f"{DEFORM_KEY}: a deformable stage runs at inference only -- its backward (the gradients of the gather with "
+                           "respect to the input, the offsets and the mask) has no kernel yet. Train with every stage False")
+
+
+def check_deform_options(on_per_stage, modulated=False, groups=1) -> Tuple[bool, ...]:
+    """MODEL.RESNETS.DEFORM_ON_PER_STAGE / DEFORM_MODULATED / DEFORM_NUM_GROUPS as [d2] build_resnet_backbone reads them -> the four
+    flags of res2..res5. ValueError naming the key: four bools; a bool; G >= 1 with every enabled stage's bottleneck width (64, 128,
+    256, 512) divisible by G into groups of a multiple of 8 channels (the gather's 8-channel vectors stay inside one group)."""
+    if not isinstance(on_per_stage, (list, tuple)) or len(on_per_stage) != 4 or not all(isinstance(v, bool) for v in on_per_stage):
+        raise ValueError(f"{DEFORM_KEY} {on_per_stage!r}: four bools, one per stage res2..res5")
+    if not isinstance(modulated, bool):
+        raise ValueError(f"MODEL.RESNETS.DEFORM_MODULATED {modulated!r}: a bool")
+    if isinstance(groups, bool) or not isinstance(groups, int) or groups < 1:
+        raise ValueError(f"MODEL.RESNETS.DEFORM_NUM_GROUPS {groups!r}: an integer >= 1")
+    for on, mid in zip(on_per_stage, R50_MID):
+        if on and (mid % groups or (mid // groups) % 8):
+            raise ValueError(f"MODEL.RESNETS.DEFORM_NUM_GROUPS {groups}: the {mid} channels of a deformable stage's conv2 must split into "
+                             "groups of a multiple of 8 channels")
+    return tuple(on_per_stage)
+
+
+def refuse_deform_training(cfg: dict) -> None:
+    """NotImplementedError naming the key while any stage of cfg (an engine configuration) is deformable."""
+    if any(cfg.get("deform_on_per_stage") or ()):
+        raise NotImplementedError(DEFORM_TRAINING_MESSAGE)
 
 
 DEFAULT_LOSS_TYPES = dict(rpn_box=("iou", 0.0), rpn_ctr=("smooth_l1", 0.0), roi_box=("smooth_l1", 0.0), roi_iou=("smooth_l1", 0.0))
@@ -123,6 +152,11 @@ class OpensetRCNNEngine:
         if cfg:
             self.cfg.update(cfg)
         ops.check_pooler_options(self.cfg["pooler_aligned"], self.cfg["pooler_sampling_ratio"])  # (ValueError before anything is packed)
+        # res2..res5: the stage's blocks run conv2 as a deformable convolution (_deform_conv2)
+        self.deform = check_deform_options(self.cfg["deform_on_per_stage"], self.cfg["deform_modulated"], self.cfg["deform_num_groups"])
+        if any(self.deform) and conv == "split":
+            raise ValueError(f'conv="split" with {DEFORM_KEY}: the split-precision convolution has no deformable form; '
+                             'use conv="storage" (dtype=float32 is the parity mode of a deformable trunk)')
         self.dtype = dtype
         self.device = torch.device(device)
         dev = self.device
@@ -174,6 +208,13 @@ class OpensetRCNNEngine:
             if k.startswith("roi_heads.mask_head.") and not k.startswith("roi_heads.mask_head.mask_fcn"):
                 continue  # (deconv and predictor have layouts of their own: engine_std._init_mask_head)
             pre = k[: -len(".weight")]
+            if pre.endswith(".conv2_offset"):
+                # the offset / mask layer of a deformable conv2: zero rows up to the next output width the convolution takes (a
+                # multiple of 8); the gather reads the padded width as its row pitch and never the padding
+                rows = (v.shape[0] + 7) // 8 * 8
+                w[pre + ".w"] = pack_conv_weight(torch.cat((v.float(), v.new_zeros((rows - v.shape[0],) + tuple(v.shape[1:]), dtype=torch.float32))), dtype).to(dev)
+                w[pre + ".b"] = torch.cat((params[pre + ".bias"].float(), torch.zeros(rows - v.shape[0]))).contiguous().to(dev)
+                continue
             if self.conv == "split":
                 w[pre + ".w"] = tuple(t.to(dev) for t in (split_stem_weight(v) if pre == STEM else split_conv_weight(v)))
             elif pre == STEM:
@@ -250,14 +291,35 @@ class OpensetRCNNEngine:
             return flops, nbytes, flops
         return self._timed(name + " (split)", lambda: ops.conv2d_split(x, w_split, self.w[name + ".b"], stride, pad, relu, residual, res_mode, out), cost)
 
-    def _bottleneck(self, x, pre: str, first: bool, stride: int = 1, save: Optional[list] = None, chain: Optional[bool] = None):
+    def _deform_conv2(self, o1, pre: str, stride: int):
+        """conv2 of a [d2] DeformBottleneckBlock: om = conv2_offset(o1) in fp32 (3x3, conv2's stride, bias, no norm), then
+        relu(dconv(o1, om) + b2) as the gather (ops.deform_cols) and the 1x1 contraction of its (pixels, 9 c) rows with conv2's weight,
+        which is stored (cout,3,3,c) and so is that matrix already. Three launches, each profiled like any layer."""
+        c, w2, b2 = self.cfg, self.w[pre + ".conv2.w"], self.w[pre + ".conv2.b"]
+        om = self._conv(o1, pre + ".conv2_offset", stride, 1, out_dtype=torch.float32)
+        cin, cout, es = o1.shape[-1], w2.shape[0], o1.element_size()
+        cols = self._timed(pre + ".conv2 (deform gather)", lambda: ops.deform_cols(o1, om, stride, c["deform_num_groups"], c["deform_modulated"]),
+                           lambda t: (8.0 * t.numel(), o1.numel() * es + om.numel() * 4 + t.numel() * es, 8.0 * t.numel()))
+        m = cols.shape[0]
+
+        def cost(y):
+            flops = 2.0 * m * w2.numel()
+            return flops, (cols.numel() + w2.numel() + y.numel()) * es, flops
+        o2 = self._timed(pre + ".conv2 (deform contraction)", lambda: ops.conv2d(cols.view(1, m, 1, 9 * cin), w2.view(cout, 1, 1, 9 * cin), b2, relu=True), cost)
+        return o2.view(om.shape[0], om.shape[1], om.shape[2], cout)
+
+    def _bottleneck(self, x, pre: str, first: bool, stride: int = 1, save: Optional[list] = None, chain: Optional[bool] = None,
+                    deform: bool = False):
         """One [d2] BottleneckBlock (conv1 1x1 -> conv2 3x3 -> conv3 1x1 + shortcut, ReLU after each). res2's blocks run as one
         fused launch when the engine allows it (the intermediates never reach HBM); everything else as separate launches.
         save (a list: the training forward): the block keeps what its backward reads -- no fused res2 launch (its intermediates
         never reach memory), the chained launch also stores conv2's output -- and appends the record of it (_stages adds the
-        block's place in its stage). chain: the caller's switch for the chained launch in place of chain_res3."""
+        block's place in its stage). chain: the caller's switch for the chained launch in place of chain_res3. deform: the block's
+        conv2 is deformable (_deform_conv2) -- neither the fused res2 launch nor the chained one applies; inference only."""
         w = self.w
-        if save is None and self.fuse_res2 and stride == 1 and w[pre + ".conv1.w"].shape[0] == 64:
+        if deform and save is not None:
+            raise NotImplementedError(DEFORM_TRAINING_MESSAGE)
+        if not deform and save is None and self.fuse_res2 and stride == 1 and w[pre + ".conv1.w"].shape[0] == 64:
             names = ["conv1", "conv2", "conv3"] + (["shortcut"] if first else [])
 
             def cost_fused(y):
@@ -280,7 +342,9 @@ class OpensetRCNNEngine:
             o1 = self._conv(x, pre + ".conv1", s1, relu=True)
         y = o2 = None
         # res3: conv2 -> conv3 + shortcut as ONE launch (with save it also stores conv2's output for the backward), bit-identical to the two
-        if (self.chain_res3 if chain is None else chain) and w[pre + ".conv2.w"].shape[0] == 128 and w[pre + ".conv3.w"].shape[0] == 512:
+        if deform:
+            o2 = self._deform_conv2(o1, pre, s2)
+        elif (self.chain_res3 if chain is None else chain) and w[pre + ".conv2.w"].shape[0] == 128 and w[pre + ".conv3.w"].shape[0] == 512:
             def cost_chain(r):
                 y_, mid = r if save is not None else (r, None)
                 px, es = y_.numel() // y_.shape[-1], y_.element_size()
@@ -292,7 +356,8 @@ class OpensetRCNNEngine:
             if r is not None:
                 y, o2 = r if save is not None else (r, None)
         if y is None:
-            o2 = self._conv(o1, pre + ".conv2", s2, 1, relu=True)
+            if o2 is None:
+                o2 = self._conv(o1, pre + ".conv2", s2, 1, relu=True)
             y = self._conv(o2, pre + ".conv3", relu=True, residual=sc, res_mode=1)
         if save is not None:
             save.append(dict(pre=pre, x=x, o1=o1, o2=o2, y=y, stride=stride, s1=s1, s2=s2, first=first))
@@ -348,7 +413,7 @@ class OpensetRCNNEngine:
             nb = R50_BLOCKS[stage - 2]
             for b in range(nb):
                 stride = 2 if (b == 0 and stage > 2) else 1  # in conv1 or conv2 of the block: cfg stride_in_1x1
-                x = self._bottleneck(x, f"{BOTTOM_UP}.res{stage}.{b}", b == 0, stride, save=save, chain=chain)
+                x = self._bottleneck(x, f"{BOTTOM_UP}.res{stage}.{b}", b == 0, stride, save=save, chain=chain, deform=self.deform[stage - 2])
                 if save is not None:
                     save[-1].update(stage=stage, last_of_stage=b == nb - 1)
             res[f"res{stage}"] = x
@@ -745,6 +810,7 @@ class OpensetRCNNEngine:
         randomness [d2] subsample_labels draws with torch.randperm (see include/osr.h). Returns a dict of 0-d / small GPU
         tensors named as the reference names its losses. gt_masks: the stock engine's mask branch (engine_std.py)."""
         c = self.cfg
+        refuse_deform_training(c)
         n = images.shape[0]
         mask_kw = {} if gt_masks is None else dict(gt_masks=gt_masks, image_hw=image_hw)
         if self.ROI_LOSSES_NEED_IMAGE_HW:

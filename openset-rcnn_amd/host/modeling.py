@@ -25,7 +25,7 @@ from torch import nn
 
 from . import ops, parallel
 from .config import CfgNode
-from .engine import DEFAULT_CFG, OpensetRCNNEngine
+from .engine import DEFAULT_CFG, OpensetRCNNEngine, check_deform_options, refuse_deform_training
 from .engine_cascade import CascadeRCNNEngine, check_cascade_options
 from .engine_std import StandardRCNNEngine, check_std_supported
 from .structures import Boxes, ImageList, Instances, ShapeSpec
@@ -214,12 +214,18 @@ class _ConvBias(nn.Module):
 
 
 class _Bottleneck(nn.Module):
-    def __init__(self, cin, mid, cout, first):
+    """[d2] BottleneckBlock; with offset_channels > 0 a DeformBottleneckBlock: `conv2_offset` (3x3, bias, no norm, zero-initialised as
+    [d2] does) predicts conv2's sampling offsets (and mask logits), conv2 keeps its names, shape and FrozenBN."""
+
+    def __init__(self, cin, mid, cout, first, offset_channels: int = 0):
         super().__init__()
         if first:
             self.shortcut = _ConvBN(cin, cout, 1, 0.7)
         self.conv1 = _ConvBN(cin, mid, 1)
         self.conv2 = _ConvBN(mid, mid, 3)
+        if offset_channels:
+            self.conv2_offset = _ConvBias(mid, offset_channels, 3)
+            nn.init.constant_(self.conv2_offset.weight, 0)
         self.conv3 = _ConvBN(mid, cout, 1, 0.5)
 
 
@@ -230,16 +236,24 @@ class _Stem(nn.Module):
 
 
 class _BottomUp(nn.Module):
-    def __init__(self):
+    def __init__(self, deform_on_per_stage=(False, False, False, False), offset_channels: int = 0):
         super().__init__()
         self.stem = _Stem()
         cin = 64
         for si, (nb, mid) in enumerate(zip(R50_BLOCKS, R50_MID)):
             blocks = []
             for b in range(nb):
-                blocks.append(_Bottleneck(cin, mid, mid * 4, b == 0))
+                blocks.append(_Bottleneck(cin, mid, mid * 4, b == 0, offset_channels if deform_on_per_stage[si] else 0))
                 cin = mid * 4
             setattr(self, f"res{si + 2}", nn.Sequential(*blocks))
+
+
+def deform_options_from(cfg: CfgNode) -> dict:
+    """MODEL.RESNETS.DEFORM_ON_PER_STAGE / DEFORM_MODULATED / DEFORM_NUM_GROUPS -> the engine's three keys, validated
+    (engine.check_deform_options: a ValueError names the key)."""
+    r = cfg.MODEL.RESNETS
+    on = check_deform_options(r.DEFORM_ON_PER_STAGE, r.DEFORM_MODULATED, r.DEFORM_NUM_GROUPS)
+    return dict(deform_on_per_stage=on, deform_modulated=bool(r.DEFORM_MODULATED), deform_num_groups=int(r.DEFORM_NUM_GROUPS))
 
 
 class ResNetFPN(_EngineOwner):
@@ -251,8 +265,9 @@ class ResNetFPN(_EngineOwner):
         super().__init__()
         assert cfg.MODEL.RESNETS.DEPTH == 50, "only R-50 is on the hot path (VOC-COCO / GraspNet yaml: DEPTH 50)"
         assert cfg.MODEL.RESNETS.NORM == "FrozenBN", "only FrozenBN is on the hot path"
-        self.bottom_up = _BottomUp()
-        self._eng_cfg = {"stride_in_1x1": bool(cfg.MODEL.RESNETS.STRIDE_IN_1X1)}  # (a stand-alone backbone's engine)
+        deform = deform_options_from(cfg)  # (ValueError naming the key when the model is built)
+        self.bottom_up = _BottomUp(deform["deform_on_per_stage"], ops.deform_offset_channels(deform["deform_num_groups"], deform["deform_modulated"]))
+        self._eng_cfg = {"stride_in_1x1": bool(cfg.MODEL.RESNETS.STRIDE_IN_1X1), **deform}  # (a stand-alone backbone's engine)
         for lvl, c in zip((2, 3, 4, 5), (256, 512, 1024, 2048)):
             setattr(self, f"fpn_lateral{lvl}", _ConvBias(c, 256, 1, 0.7))
             setattr(self, f"fpn_output{lvl}", _ConvBias(256, 256, 3, 0.7))
@@ -567,7 +582,7 @@ def engine_cfg_from(cfg: CfgNode) -> dict:
         obj_score_thresh=rh.OBJ_SCORE_THRESH_TEST, nms_thresh_test=rh.NMS_THRESH_TEST, detections_per_image=cfg.TEST.DETECTIONS_PER_IMAGE,
         known_score_thresh=rh.KNOWN_SCORE_THRESH, known_nms_thresh=rh.KNOWN_NMS_THRESH, known_topk=rh.KNOWN_TOPK,
         unknown_score_thresh=rh.UNKNOWN_SCORE_THRESH, unknown_nms_thresh=rh.UNKNOWN_NMS_THRESH, unknown_topk=rh.UNKNOWN_TOPK,
-        stride_in_1x1=bool(cfg.MODEL.RESNETS.STRIDE_IN_1X1),
+        stride_in_1x1=bool(cfg.MODEL.RESNETS.STRIDE_IN_1X1), **deform_options_from(cfg),
         num_classes=rh.NUM_CLASSES, num_known=rh.NUM_KNOWN_CLASSES, reps_per_class=cfg.MODEL.PLN.REPS_PER_CLASS, pln_distance=cfg.MODEL.PLN.DISTANCE_TYPE,
         # the reference hard-codes the unknown id: 80 with --opendet-benchmark, else 1000
         unknown_id=80 if cfg.OPENDET_BENCHMARK else 1000, unk_thr=cfg.MODEL.PLN.UNK_THR,
@@ -1014,6 +1029,7 @@ class GeneralizedRCNN(_EngineOwner):
         from .train import OpensetRCNNTrainer
         from .train_cascade import CascadeRCNNTrainer
         from .train_std import StandardRCNNTrainer
+        refuse_deform_training(self._eng_cfg)  # (NotImplementedError naming MODEL.RESNETS.DEFORM_ON_PER_STAGE)
         if self._mask_training() is False:
             raise NotImplementedError(MASK_LOSS_MESSAGE)
         if self.conv_precision != "storage":
@@ -1115,6 +1131,7 @@ class GeneralizedRCNN(_EngineOwner):
         only: loss_rpn_loc, loss_rpn_ctr, loss_box_reg, loss_iou, loss_dml, loss_cls. Each input dict carries "image" and
         "instances" (gt_boxes: Boxes, gt_classes); a ragged batch is padded to its largest image. `generator` seeds the
         uniform keys that replace torch.randperm in the two samplers."""
+        refuse_deform_training(self._eng_cfg)
         if self._mask_training() is False:
             raise NotImplementedError(MASK_LOSS_MESSAGE)
         tensors = self._train_tensors(batched_inputs, generator)

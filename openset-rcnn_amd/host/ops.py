@@ -617,6 +617,42 @@ def subsample2(x: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def deform_offset_channels(groups: int, modulated: bool) -> int:
+    """Channels of a deformable layer's `conv2_offset` output: 18 G offsets (dy, dx per tap and group), then 9 G mask logits when modulated."""
+    return (27 if modulated else 18) * int(groups)
+
+
+def deform_cols(x: torch.Tensor, om: torch.Tensor, stride: int = 1, groups: int = 1, modulated: bool = False) -> torch.Tensor:
+    """The gather of a 3x3 deformable convolution (osr_deform_cols, include/osr.h): x (n,h,w,c) f16 / bf16 / f32, om (n,ho,wo,ch) fp32
+    with ch >= deform_offset_channels(groups, modulated) as the row pitch -> cols (n*ho*wo, 9, c) in x's dtype, the masked bilinear
+    sample of every (output pixel, tap, channel). c, and c / groups, must be multiples of 8: OsrError (status -2, nothing launched)."""
+    lib = _lib.load()
+    _need(x, name="x"); _need(om, torch.float32, "om")
+    n, h, w, c = x.shape
+    ho, wo = (h - 1) // stride + 1, (w - 1) // stride + 1
+    if om.dim() != 4 or tuple(om.shape[:3]) != (n, ho, wo):
+        raise OsrError(f"deform_cols: om {tuple(om.shape)} does not match the output pixels {(n, ho, wo)} of x {tuple(x.shape)} at stride {stride}")
+    cols = torch.empty((n * ho * wo, 9, c), dtype=x.dtype, device=x.device)
+    check(lib.osr_deform_cols(_p(x), _p(om), n, h, w, c, ho, wo, int(om.shape[3]), int(stride), int(groups), int(bool(modulated)), _p(cols),
+                              _DT[x.dtype], _stream()), "osr_deform_cols")
+    return cols
+
+
+def deform_conv2d(x: torch.Tensor, om: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, stride: int = 1, groups: int = 1,
+                  modulated: bool = False, relu: bool = False) -> torch.Tensor:
+    """3x3 deformable convolution, padding 1 ([d2] DeformConv / ModulatedDeformConv; `groups` = deformable groups, the weight is dense)
+    as two launches: deform_cols, then the 1x1 contraction of its (pixels, 9 c) rows with weight (cout,3,3,c) viewed as (cout, 9 c) --
+    conv2d's kernels, fp32 ones for fp32 tensors. -> (n,ho,wo,cout) in x's dtype."""
+    n, h, w, c = x.shape
+    cout = weight.shape[0]
+    if tuple(weight.shape[1:]) != (3, 3, c):
+        raise OsrError(f"deform_conv2d: weight {tuple(weight.shape)} is not (cout, 3, 3, {c})")
+    cols = deform_cols(x, om, stride, groups, modulated)
+    m = cols.shape[0]
+    y = conv2d(cols.view(1, m, 1, 9 * c), weight.view(cout, 1, 1, 9 * c), bias, relu=relu)
+    return y.view(n, (h - 1) // stride + 1, (w - 1) // stride + 1, cout)
+
+
 def gemm_f32(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], relu: bool = False) -> torch.Tensor:
     lib = _lib.load()
     _need(a, torch.float32, "a"); _need(w, torch.float32, "w")

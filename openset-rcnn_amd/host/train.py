@@ -23,7 +23,7 @@ from typing import Dict, List, Optional, Tuple
 import torch
 
 from . import ops, parallel
-from .engine import PYRAMID, RPN_CONV, STEM, OpensetRCNNEngine, loss_types_of
+from .engine import PYRAMID, RPN_CONV, STEM, OpensetRCNNEngine, loss_types_of, refuse_deform_training
 from .weights import R50_BLOCKS, pack_conv_weight, pack_fc1_weight, pack_stem_weight
 
 
@@ -129,6 +129,7 @@ class OpensetRCNNTrainer:
         no low-precision copy: their fp32 masters are re-split into the kernels' bf16 planes after every update.
         conv: "storage" only. The split-precision convolutions (OpensetRCNNEngine conv="split") have no backward: ValueError."""
         freeze_at = self._check_freeze_at(freeze_at)
+        refuse_deform_training(cfg or {})  # (a deformable stage has no backward: NotImplementedError naming its key)
         if conv != "storage":
             raise ValueError(f"conv_precision {conv!r}: the split-precision convolutions are an inference mode, training keeps conv=\"storage\"")
         if box_head not in OpensetRCNNEngine.BOX_HEADS:

@@ -31,11 +31,29 @@ def fold_frozen_bn(state: Dict[str, torch.Tensor], eps: float = 1e-5) -> Dict[st
     return out
 
 
-def random_params(seed: int = 0, num_known: int = 20, fc_dim: int = 1024, emd: int = 256, res_gain: float = 0.5,
-                  spread: bool = True) -> Dict[str, torch.Tensor]:
-    """Seeded synthetic parameters (already BN-folded) for R50-FPN + CF-RPN head + Openset RoI heads."""
-    g = torch.Generator().manual_seed(seed)
+def deform_offset_params(deform_on_per_stage, modulated: bool = False, groups: int = 1, std: float = 0.0, seed: int = 0) -> Dict[str, torch.Tensor]:
+    """`conv2_offset.{weight,bias}` of every block of the deformable stages (MODEL.RESNETS.DEFORM_ON_PER_STAGE, res2..res5) under
+    detectron2's names: weight ((27 if modulated else 18) * groups, mid, 3, 3) and bias. std 0: zeros, [d2]'s initialisation (the layer
+    then samples on the regular grid); std > 0: seeded normal weights and biases, scaled by the fan-in so that a unit-variance input
+    gives offsets of about `std` pixels."""
+    g = torch.Generator().manual_seed(seed + 3000)
     p: Dict[str, torch.Tensor] = {}
+    ch = (27 if modulated else 18) * groups
+    for si, (nb, mid) in enumerate(zip(R50_BLOCKS, R50_MID)):
+        for b in range(nb if deform_on_per_stage[si] else 0):
+            pre = f"backbone.bottom_up.res{si + 2}.{b}.conv2_offset"
+            p[pre + ".weight"] = torch.randn(ch, mid, 3, 3, generator=g) * (std / math.sqrt(9.0 * mid)) if std else torch.zeros(ch, mid, 3, 3)
+            p[pre + ".bias"] = torch.randn(ch, generator=g) * (0.5 * std) if std else torch.zeros(ch)
+    return p
+
+
+def random_params(seed: int = 0, num_known: int = 20, fc_dim: int = 1024, emd: int = 256, res_gain: float = 0.5,
+                  spread: bool = True, deform_on_per_stage=(False, False, False, False), deform_modulated: bool = False,
+                  deform_num_groups: int = 1, deform_std: float = 0.0) -> Dict[str, torch.Tensor]:
+    """Seeded synthetic parameters (already BN-folded) for R50-FPN + CF-RPN head + Openset RoI heads; with deformable stages also
+    their deform_offset_params (every other tensor is what the same seed gives without them)."""
+    g = torch.Generator().manual_seed(seed)
+    p: Dict[str, torch.Tensor] = deform_offset_params(deform_on_per_stage, deform_modulated, deform_num_groups, deform_std, seed)
 
     def conv(name, cout, cin, k, gain=1.0, bias_std=0.05):
         std = gain * math.sqrt(2.0 / (cout * k * k))
