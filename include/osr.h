@@ -744,6 +744,40 @@ osr_status osr_tta_boxes_to_augmented(const float* boxes, const int32_t* counts,
 osr_status osr_tta_reduce_masks(const float* maps, const int32_t* flip, int32_t num_aug, const int32_t* counts, int32_t n,
                                 int32_t topk, int32_t m, float* out, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * RetinaNet inference tail: [d2] RetinaNet.inference_single_image before its batched NMS, for all images and levels in two
+ * launches (csrc/osr_retinanet.hip). detectron2 is not at hand: the semantics are written from memory of detectron2 v0.6, and
+ * THIS TEXT is the contract the tests check.
+ * Inputs: lv with num_anchors = A (offset[l] counts anchors, a multiple of A: level l starts offset[l] / A cells into both
+ * buffers); cell_anchors (L,A,4) fp32; logits, level-major, per level (n, h, w, pitch_cls) of logits_dtype (f16 / bf16 / f32) with
+ * channel a*K + k, pitch_cls >= A*K; deltas, level-major, per level (n, h, w, pitch_box) fp32 with channel a*4 + j, pitch_box >= 4A
+ * and a multiple of 4. The channels [A*K, pitch_cls) and [4A, pitch_box) are padding and are never read as candidates.
+ * Candidates: per (image, level) the flat index is i = (cell*A + a)*K + k over the real channels; element i is a candidate iff
+ * logit > logit_thresh (the caller passes log(t / (1 - t)) of SCORE_THRESH_TEST, evaluated in double and rounded once to fp32).
+ * NaN never passes, +Inf does.
+ * Selection: the min(topk, #candidates) candidates with the largest logit, equal logits lower i first; output order is logit
+ * descending, then i ascending. (Ordering by the raw logit refines [d2]'s ordering by sigmoid in fp32: the two differ only where
+ * distinct logits round to one probability, an order [d2]'s unstable sort leaves open.)
+ * Per selected element: score 1 / (1 + expf(-logit)) in fp32; class i % K; the anchor shift + cell_anchor in fp32 as
+ * osr_rpn_select forms it; Box2BoxTransform(reg_weights).apply_deltas exactly as osr_rpn_select_ex's decode_mode 1 (dw, dh clamped
+ * at log(1000/16)); NOT clipped to the image ([d2] v0.6 does not clip before the NMS; osr_detector_postprocess clips later).
+ * c_cand = 0 (and the row's box zeroed, bit 0 of status_flags[0] set) when a decoded coordinate or one of the four deltas is
+ * non-finite; the row keeps its score, class and index.
+ * Outputs, padded to cap = osr_retinanet_select_capacity() = L * topk rows per image, level l's rows at [l*topk, l*topk + count_l):
+ * c_boxes (n,cap,4) fp32, c_scores (n,cap), c_cls (n,cap) int32 (-1 padding), c_cand (n,cap) int32 (0 padding), c_src (n,cap)
+ * int32 (the flat index i; -1 padding), counts (n,L) int32. osr_nms_topk(cls = c_cls, cand = c_cand, seg_len = cap) consumes them.
+ * Repeats are bit-identical for any input; no host sync; capturable; integer atomics only. OSR_ERR_UNSUPPORTED, nothing launched,
+ * for topk > 2048, a level of >= 2^31 elements per image, or logits / deltas / c_boxes / workspace not 16-byte aligned;
+ * OSR_ERR_INVALID_ARG for a pitch below the real width.
+ * --------------------------------------------------------------------------------------------------------- */
+int32_t osr_retinanet_select_capacity(const osr_rpn_levels* lv, int32_t topk);
+int64_t osr_retinanet_select_workspace_bytes(const osr_rpn_levels* lv, int32_t n, int32_t num_classes, int32_t topk);
+osr_status osr_retinanet_select(const osr_rpn_levels* lv, const float* cell_anchors, const void* logits, int32_t logits_dtype,
+                                int64_t pitch_cls, const float* deltas, int64_t pitch_box, int32_t n, int32_t num_classes,
+                                int32_t topk, float logit_thresh, const float reg_weights[4], float* c_boxes, float* c_scores,
+                                int32_t* c_cls, int32_t* c_cand, int32_t* c_src, int32_t* counts, int32_t* status_flags,
+                                void* workspace, int64_t workspace_bytes, void* stream);
+
 /* =========================================================================================================
  * Training step, forward half: targets and losses. Gradients are not
  * produced by this library yet; every function below is a forward kernel whose outputs equal the reference's

@@ -31,6 +31,7 @@ SOURCES = {
     "osr_stem_pool.hip": [],
     "osr_deform.hip": ["-ffp-contract=off"],  # (exact-index gather: the sample positions and the zero-offset / integer-offset results are bit-exact)
     "osr_rpn.hip": ["-ffp-contract=off"],
+    "osr_retinanet.hip": ["-ffp-contract=off"],  # (decodes like osr_rpn.hip's decode_mode 1)
     "osr_roi_align.hip": ["-ffp-contract=off"],
     "osr_det_tail.hip": ["-ffp-contract=off"],
     "osr_cascade.hip": ["-ffp-contract=off"],  # (as osr_det_tail.hip: one stage reproduces osr_fastrcnn_candidates bit for bit)

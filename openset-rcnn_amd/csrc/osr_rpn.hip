@@ -6,6 +6,7 @@
 //   find_top_rpn_proposals                         find_top_proposals.py:60-127
 // Compile with -ffp-contract=off: the decode/clip arithmetic must round exactly like the oracle's.
 #include "osr_common.h"
+#include "osr_select.h"
 
 // ------------------------------------------------------------------------------------------------------
 // head tail: one wave per pixel row of t (c channels, channels-last). 5 dot products + sum of squares.
@@ -80,9 +81,6 @@ extern "C" osr_status osr_cfrpn_head_tail(const void* t, int32_t t_dtype, int64_
 // ------------------------------------------------------------------------------------------------------
 // proposal selection
 // ------------------------------------------------------------------------------------------------------
-#define SEL_THREADS 1024
-#define SEL_MAXK 2048
-#define SEL_BINS 2048  // histogram bins of a radix-select pass (11 key bits)
 
 struct SelLevels {
     int num_levels, num_anchors;
@@ -93,48 +91,6 @@ struct SelLevels {
     int aoff[OSR_MAX_LEVELS];    // prefix of h*w*a (index into the image's concatenated anchor list)
     int cap;
 };
-
-// descending bitonic sort of 64-bit keys in LDS, n power of two
-__device__ __forceinline__ void bitonic_desc(unsigned long long* buf, int n) {
-    for (int k = 2; k <= n; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = threadIdx.x; i < n; i += blockDim.x) {
-                int ixj = i ^ j;
-                if (ixj > i) {
-                    unsigned long long a = buf[i], b = buf[ixj];
-                    bool desc = (i & k) == 0;
-                    if (desc ? (a < b) : (a > b)) { buf[i] = b; buf[ixj] = a; }
-                }
-            }
-            __syncthreads();
-        }
-    }
-}
-
-// osr_float_key with every NaN mapped to the largest key. torch.sort(descending=True), which find_top_rpn_proposals selects with, puts
-// a NaN score first whatever its sign bit; osr_float_key orders a sign-set NaN (0xffc00000, an x86 host's inf - inf) below -inf, so
-// the anchor would never be selected, never reach the finite filter and never raise status_flags. NaNs tie with each other: lower
-// index first, like every other tie.
-__device__ __forceinline__ uint32_t sel_key(float f) { return f != f ? 0xffffffffu : osr_float_key(f); }
-
-// hist[digit] += 1 for the lanes with `on`, called by all 64 lanes of a wave. Two rounds of "the first pending lane's digit: every
-// lane that shares it is added by ONE atomic", then one atomic per lane that is still pending. Same histogram as 64 plain atomics.
-__device__ __forceinline__ void sel_hist_add(int* hist, int digit, bool on) {
-    const int lane = threadIdx.x & 63;
-    unsigned long long act = __ballot(on);
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-        if (!act) return;  // wave-uniform
-        const int leader = __ffsll((long long)act) - 1;
-        const int d0 = __shfl(digit, leader, 64);
-        const bool mine = on && digit == d0;
-        const unsigned long long m = __ballot(mine);
-        if (lane == leader) atomicAdd(&hist[d0], __popcll(m));
-        if (mine) on = false;
-        act &= ~m;
-    }
-    if (on) atomicAdd(&hist[digit], 1);
-}
 
 // Stage A: grid (level, image). Stable top-k by radix select + bitonic sort, ltrb decode, filters.
 // Writes staging arrays st_box/st_score/st_src/st_flag at [img][koff[l] + rank].

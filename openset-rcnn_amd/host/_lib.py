@@ -154,6 +154,9 @@ PROTOTYPES = {
     "osr_rpn_select_workspace_bytes": (I64, [C.POINTER(RpnLevels), I32, I32]),
     "osr_rpn_select": (I32, [C.POINTER(RpnLevels), P, P, P, I32, P, I32, F32, P, P, P, P, P, P, P, I64, P]),
     "osr_rpn_select_ex": (I32, [C.POINTER(RpnLevels), P, P, P, I32, P, I32, F32, I32, P, P, P, P, P, P, P, P, P, I64, P]),
+    "osr_retinanet_select_capacity": (I32, [C.POINTER(RpnLevels), I32]),
+    "osr_retinanet_select_workspace_bytes": (I64, [C.POINTER(RpnLevels), I32, I32, I32]),
+    "osr_retinanet_select": (I32, [C.POINTER(RpnLevels), P, P, I32, I64, P, I64, I32, I32, I32, F32, P, P, P, P, P, P, P, P, P, I64, P]),
     "osr_fastrcnn_candidates": (I32, [P, P, I32, I32, P, P, I32, I32, P, P, F32, P, P, P, P, P, P]),
     "osr_cascade_refine": (I32, [P, P, P, I32, I32, P, P, I32, P, P, P, I32, I32, F32, P, P, P, P, P, P, P]),
     "osr_cascade_candidates": (I32, [P, I32, P, I32, P, P, I32, I32, P, P, F32, P, P, P, P, P, P]),

@@ -171,6 +171,12 @@ def get_cfg() -> CfgNode:
                                  "IOUS": (0.5, 0.6, 0.7)})
     m.ROI_MASK_HEAD = CN({"NAME": "MaskRCNNConvUpsampleHead", "POOLER_RESOLUTION": 14, "POOLER_SAMPLING_RATIO": 0, "NUM_CONV": 0,
                           "CONV_DIM": 256, "NORM": "", "CLS_AGNOSTIC_MASK": False, "POOLER_TYPE": "ROIAlignV2"})
+    # [d2] RetinaNet (host/engine_retinanet.py). IOU_THRESHOLDS .. BBOX_REG_LOSS_TYPE are training keys: carried so that detectron2's
+    # yaml files merge, read by nothing yet
+    m.RETINANET = CN({"NUM_CLASSES": 80, "IN_FEATURES": ["p3", "p4", "p5", "p6", "p7"], "NUM_CONVS": 4, "PRIOR_PROB": 0.01,
+                      "SCORE_THRESH_TEST": 0.05, "TOPK_CANDIDATES_TEST": 1000, "NMS_THRESH_TEST": 0.5, "BBOX_REG_WEIGHTS": (1.0, 1.0, 1.0, 1.0),
+                      "NORM": "", "IOU_THRESHOLDS": [0.4, 0.5], "IOU_LABELS": [0, -1, 1], "FOCAL_LOSS_GAMMA": 2.0, "FOCAL_LOSS_ALPHA": 0.25,
+                      "SMOOTH_L1_LOSS_BETA": 0.1, "BBOX_REG_LOSS_TYPE": "smooth_l1"})
     c.INPUT = CN({"MIN_SIZE_TRAIN": (800,), "MIN_SIZE_TRAIN_SAMPLING": "choice", "MAX_SIZE_TRAIN": 1333, "MIN_SIZE_TEST": 800,
                   "MAX_SIZE_TEST": 1333, "FORMAT": "BGR", "RANDOM_FLIP": "horizontal", "MASK_FORMAT": "polygon"})
     c.DATASETS = CN({"TRAIN": (), "TEST": (), "PROPOSAL_FILES_TRAIN": (), "PROPOSAL_FILES_TEST": ()})

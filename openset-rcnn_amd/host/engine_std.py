@@ -29,14 +29,16 @@ STD_DEFAULT_CFG = dict(
 
 def cell_anchor_table(sizes, ratios) -> torch.Tensor:
     """[d2] DefaultAnchorGenerator.generate_cell_anchors per level: for (size, ratio): area = size^2, w = sqrt(area / ratio),
-    h = ratio * w, anchor [-w/2, -h/2, w/2, h/2], computed in double and rounded to fp32 as torch.tensor() does. (L, A, 4)."""
+    h = ratio * w, anchor [-w/2, -h/2, w/2, h/2], computed in double and rounded to fp32 as torch.tensor() does. (L, A, 4).
+    A level's entry of `sizes` is one size or a list of sizes (RetinaNet: three per level): size-major, then ratio, [d2]'s order."""
     rows = []
-    for z in sizes:
+    for level in sizes:
         cells = []
-        for r in ratios:
-            w = math.sqrt(float(z) ** 2 / r)
-            h = r * w
-            cells.append([-w / 2.0, -h / 2.0, w / 2.0, h / 2.0])
+        for z in (level if isinstance(level, (list, tuple)) else (level,)):
+            for r in ratios:
+                w = math.sqrt(float(z) ** 2 / r)
+                h = r * w
+                cells.append([-w / 2.0, -h / 2.0, w / 2.0, h / 2.0])
         rows.append(cells)
     return torch.tensor(rows, dtype=torch.float32)
 

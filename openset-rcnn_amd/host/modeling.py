@@ -27,6 +27,7 @@ from . import ops, parallel
 from .config import CfgNode
 from .engine import DEFAULT_CFG, OpensetRCNNEngine, check_deform_options, refuse_deform_training
 from .engine_cascade import CascadeRCNNEngine, check_cascade_options
+from .engine_retinanet import RETINA_PYRAMID, TRAINING_MESSAGE as RETINANET_TRAINING_MESSAGE, RetinaNetEngine, check_retina_anchors
 from .engine_std import StandardRCNNEngine, check_std_supported
 from .structures import Boxes, ImageList, Instances, ShapeSpec
 from .weights import R50_BLOCKS, R50_MID, fold_frozen_bn
@@ -1180,6 +1181,169 @@ class GeneralizedRCNN(_EngineOwner):
             res = ops.detector_postprocess(res[0], res[1], res[2], res[3], scale, torch.tensor(outs, dtype=torch.int32, device=self.device))
         else:
             outs = sizes
+        insts = OpensetRCNNEngine.to_instances(res, len(sizes))
+        return [{"instances": Instances(o, pred_boxes=Boxes(r["pred_boxes"]), scores=r["scores"], pred_classes=r["pred_classes"])}
+                for r, o in zip(insts, outs)]
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# RetinaNet
+# ---------------------------------------------------------------------------------------------------------------
+class LastLevelP6P7(nn.Module):
+    """[d2] v0.6 LastLevelP6P7: p6 = conv3x3/2(res5), p7 = conv3x3/2(relu(p6))."""
+
+    def __init__(self, in_channels: int, out_channels: int):
+        super().__init__()
+        self.p6 = _ConvBias(in_channels, out_channels, 3, 0.7)
+        self.p7 = _ConvBias(out_channels, out_channels, 3, 0.7)
+
+
+class RetinaNetResNetFPN(_EngineOwner):
+    """[d2] build_retinanet_resnet_fpn_backbone for R-50 (Base-RetinaNet.yaml): laterals and output convs on res3..res5 only (no
+    fpn_lateral2 / fpn_output2), top block LastLevelP6P7 fed from res5; forward(x) -> p3..p7."""
+    _prefix = "backbone."
+    _engine_cls = RetinaNetEngine
+
+    def __init__(self, cfg: CfgNode):
+        super().__init__()
+        assert cfg.MODEL.RESNETS.DEPTH == 50, "only R-50 is on the hot path"
+        assert cfg.MODEL.RESNETS.NORM == "FrozenBN", "only FrozenBN is on the hot path"
+        if list(cfg.MODEL.FPN.IN_FEATURES) != ["res3", "res4", "res5"]:
+            raise ValueError(f"MODEL.FPN.IN_FEATURES {list(cfg.MODEL.FPN.IN_FEATURES)!r}: build_retinanet_resnet_fpn_backbone reads res3, res4, res5")
+        deform = deform_options_from(cfg)
+        self.bottom_up = _BottomUp(deform["deform_on_per_stage"], ops.deform_offset_channels(deform["deform_num_groups"], deform["deform_modulated"]))
+        self._eng_cfg = {"stride_in_1x1": bool(cfg.MODEL.RESNETS.STRIDE_IN_1X1), **deform}
+        for lvl, c in zip((3, 4, 5), (512, 1024, 2048)):
+            setattr(self, f"fpn_lateral{lvl}", _ConvBias(c, 256, 1, 0.7))
+            setattr(self, f"fpn_output{lvl}", _ConvBias(256, 256, 3, 0.7))
+        self.top_block = LastLevelP6P7(2048, 256)
+        self._out_features = list(RETINA_PYRAMID)
+        self.size_divisibility = 32
+
+    def output_shape(self) -> Dict[str, ShapeSpec]:
+        return {f"p{l}": ShapeSpec(channels=256, stride=2 ** l) for l in range(3, 8)}
+
+    def forward(self, x: torch.Tensor) -> Dict[str, torch.Tensor]:
+        n, _, h, w = x.shape
+        assert h % 32 == 0 and w % 32 == 0, "pad the batch to a multiple of 32 (ImageList.from_tensors(..., 32))"
+        feats = self.engine()._backbone(x.float().contiguous(), h, w, normalized=True)
+        return {k: v.permute(0, 3, 1, 2) for k, v in feats.items()}
+
+
+@BACKBONE_REGISTRY.register()
+def build_retinanet_resnet_fpn_backbone(cfg: CfgNode, input_shape=None):
+    return RetinaNetResNetFPN(cfg)
+
+
+class RetinaNetHead(nn.Module):
+    """[d2] RetinaNetHead under its parameter names: cls_subnet / bbox_subnet of NUM_CONVS x (3x3 conv 256 -> 256, ReLU) shared across
+    the levels (cls_subnet.{0,2,4,6}), cls_score (3x3, 256 -> A*K), bbox_pred (3x3, 256 -> A*4). Weights N(0, 0.01), zero bias,
+    cls_score.bias = -log((1 - PRIOR_PROB) / PRIOR_PROB)."""
+
+    def __init__(self, cfg: CfgNode, input_shape: List[ShapeSpec], num_anchors: int):
+        super().__init__()
+        rn = cfg.MODEL.RETINANET
+        ch = input_shape[0].channels
+        assert ch == 256 and len(set(s.channels for s in input_shape)) == 1, "the head reads 256 channels on every level"
+        for name in ("cls_subnet", "bbox_subnet"):
+            layers = []
+            for _ in range(int(rn.NUM_CONVS)):
+                layers += [nn.Conv2d(ch, ch, 3, padding=1), nn.ReLU()]
+            setattr(self, name, nn.Sequential(*layers))
+        self.cls_score = nn.Conv2d(ch, num_anchors * int(rn.NUM_CLASSES), 3, padding=1)
+        self.bbox_pred = nn.Conv2d(ch, num_anchors * 4, 3, padding=1)
+        for m in self.modules():
+            if isinstance(m, nn.Conv2d):
+                nn.init.normal_(m.weight, std=0.01)
+                nn.init.constant_(m.bias, 0)
+        nn.init.constant_(self.cls_score.bias, -math.log((1 - rn.PRIOR_PROB) / rn.PRIOR_PROB))
+
+
+def retinanet_engine_cfg_from(cfg: CfgNode) -> dict:
+    rn = cfg.MODEL.RETINANET
+    return dict(pixel_mean=tuple(cfg.MODEL.PIXEL_MEAN), pixel_std=tuple(cfg.MODEL.PIXEL_STD), stride_in_1x1=bool(cfg.MODEL.RESNETS.STRIDE_IN_1X1),
+                **deform_options_from(cfg), anchor_ratios=tuple(float(r) for r in cfg.MODEL.ANCHOR_GENERATOR.ASPECT_RATIOS[0]),
+                retina_anchor_sizes=tuple(tuple(float(v) for v in s) for s in cfg.MODEL.ANCHOR_GENERATOR.SIZES),
+                retina_num_classes=int(rn.NUM_CLASSES), retina_num_convs=int(rn.NUM_CONVS), retina_score_thresh=float(rn.SCORE_THRESH_TEST),
+                retina_topk=int(rn.TOPK_CANDIDATES_TEST), retina_nms_thresh=float(rn.NMS_THRESH_TEST),
+                retina_bbox_reg_weights=tuple(float(v) for v in rn.BBOX_REG_WEIGHTS), std_detections_per_image=int(cfg.TEST.DETECTIONS_PER_IMAGE))
+
+
+@META_ARCH_REGISTRY.register()
+class RetinaNet(_EngineOwner):
+    """[d2] RetinaNet (configs/retinanet_fpn.yaml): backbone (p3..p7) + RetinaNetHead, at inference. model(list[dict{image, height,
+    width}]) -> list[{"instances": Instances(pred_boxes, scores, pred_classes)}] in eval mode. Training mode, make_trainer() and
+    losses_forward raise NotImplementedError naming the meta architecture; TEST.AUG, MASK_ON, KEYPOINT_ON, RETINANET.NORM and
+    conv_precision "split" are ValueErrors."""
+    _prefix = ""
+    _engine_cls = RetinaNetEngine
+    TTA_MESSAGE = ('TEST.AUG: test-time augmentation is implemented for META_ARCHITECTURE "GeneralizedRCNN" with StandardROIHeads only, not for '
+                   'META_ARCHITECTURE "RetinaNet"')
+
+    def __init__(self, cfg: CfgNode, class_id: Optional[torch.Tensor] = None):
+        super().__init__()
+        rn = cfg.MODEL.RETINANET
+        if rn.NORM != "":
+            raise ValueError(f"MODEL.RETINANET.NORM {rn.NORM!r}: the head's convolutions have no normalisation on the HIP path (\"\")")
+        if cfg.MODEL.MASK_ON or cfg.MODEL.KEYPOINT_ON:
+            raise ValueError('MODEL.MASK_ON / MODEL.KEYPOINT_ON with META_ARCHITECTURE "RetinaNet": a one-stage detector has no mask or keypoint head')
+        if cfg.TEST.AUG.ENABLED:
+            raise ValueError(self.TTA_MESSAGE)
+        if list(rn.IN_FEATURES) != list(RETINA_PYRAMID):
+            raise ValueError(f"MODEL.RETINANET.IN_FEATURES {list(rn.IN_FEATURES)!r}: the HIP path reads {list(RETINA_PYRAMID)}")
+        if int(rn.NUM_CONVS) < 0 or int(rn.NUM_CLASSES) < 1 or int(rn.TOPK_CANDIDATES_TEST) < 1:
+            raise ValueError("MODEL.RETINANET: NUM_CONVS >= 0, NUM_CLASSES >= 1, TOPK_CANDIDATES_TEST >= 1")
+        if int(rn.TOPK_CANDIDATES_TEST) > 2048:
+            raise ValueError(f"MODEL.RETINANET.TOPK_CANDIDATES_TEST {rn.TOPK_CANDIDATES_TEST}: at most 2048 per level on the HIP path")
+        self.num_anchors = check_retina_anchors(cfg.MODEL.ANCHOR_GENERATOR.SIZES, cfg.MODEL.ANCHOR_GENERATOR.ASPECT_RATIOS[0])
+        self.backbone = BACKBONE_REGISTRY.get(cfg.MODEL.BACKBONE.NAME)(cfg)
+        shapes = self.backbone.output_shape()
+        missing = [f for f in rn.IN_FEATURES if f not in shapes]
+        if missing:
+            raise ValueError(f"MODEL.BACKBONE.NAME {cfg.MODEL.BACKBONE.NAME!r} has no {missing}: RetinaNet needs build_retinanet_resnet_fpn_backbone")
+        self.head = RetinaNetHead(cfg, [shapes[f] for f in rn.IN_FEATURES], self.num_anchors)
+        self.register_buffer("pixel_mean", torch.tensor(cfg.MODEL.PIXEL_MEAN).view(-1, 1, 1), False)
+        self.register_buffer("pixel_std", torch.tensor(cfg.MODEL.PIXEL_STD).view(-1, 1, 1), False)
+        self._eng_cfg = retinanet_engine_cfg_from(cfg)
+        self.num_classes = int(rn.NUM_CLASSES)
+
+    @property
+    def device(self):
+        return self.pixel_mean.device
+
+    def engine(self) -> RetinaNetEngine:
+        eng = super().engine()
+        self.backbone._shared = eng  # one packed copy of the weights for the whole model
+        return eng
+
+    def refresh(self):
+        super().refresh()
+        self.backbone._shared = None
+        self.backbone.refresh()
+
+    def forward(self, batched_inputs: List[dict]):
+        if self.training:
+            raise NotImplementedError(RETINANET_TRAINING_MESSAGE)
+        return self.inference(batched_inputs)
+
+    def make_trainer(self, *a, **k):
+        raise NotImplementedError(RETINANET_TRAINING_MESSAGE)
+
+    trainer = make_trainer  # (run_net.py's training loop asks for model.trainer())
+
+    def losses_forward(self, *a, **k):
+        raise NotImplementedError(RETINANET_TRAINING_MESSAGE)
+
+    @torch.no_grad()
+    def inference(self, batched_inputs: List[dict], do_postprocess: bool = True):
+        """[d2] RetinaNet.inference + detector_postprocess on the device (rescale to each input's height / width, clip, drop empties)."""
+        eng = self.engine()
+        batch, sizes = GeneralizedRCNN._stack_images(self, [x["image"] for x in batched_inputs])
+        res = eng.forward(batch, sizes)
+        outs = [(int(inp.get("height", s[0])), int(inp.get("width", s[1]))) if do_postprocess else s for inp, s in zip(batched_inputs, sizes)]
+        # (without postprocessing the boxes are still clipped to the image: [d2] v0.6 clips nowhere else)
+        scale = torch.tensor([[ow / s[1], oh / s[0]] for (oh, ow), s in zip(outs, sizes)], dtype=torch.float32, device=self.device)
+        res = ops.detector_postprocess(res[0], res[1], res[2], res[3], scale, torch.tensor(outs, dtype=torch.int32, device=self.device))
         insts = OpensetRCNNEngine.to_instances(res, len(sizes))
         return [{"instances": Instances(o, pred_boxes=Boxes(r["pred_boxes"]), scores=r["scores"], pred_classes=r["pred_classes"])}
                 for r, o in zip(insts, outs)]

@@ -3,6 +3,7 @@ current HIP stream and output allocation. Every op runs on the HIP library or ra
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
@@ -897,6 +898,61 @@ def _rpn_select_ex(lv, cell_anchors, ctr, deltas, n, image_hw, pre_nms_topk, min
     check(lib.osr_rpn_select_ex(C.byref(lv), _p(cell_anchors), _p(ctr), _p(deltas), n, _p(image_hw), pre_nms_topk, float(min_box_size), 1, rw,
                                 _p(boxes), _p(scores), _p(src), _p(bidx), _p(level), _p(counts), _p(flags), _p(ws), wsb, _stream()), "osr_rpn_select_ex")
     return dict(boxes=boxes, scores=scores, src_index=src, batch_idx=bidx, level=level, counts=counts, status_flags=flags, cap=cap)
+
+
+def retinanet_logit_thresh(score_thresh: float) -> float:
+    """log(t / (1 - t)) in double, rounded once to fp32 (include/osr.h osr_retinanet_select: the candidates are `logit > this`)."""
+    t = float(score_thresh)
+    if t <= 0.0:
+        return float("-inf")
+    if t >= 1.0:
+        return float("inf")
+    return float(torch.tensor(math.log(t / (1.0 - t)), dtype=torch.float64).to(torch.float32))
+
+
+def retinanet_select(lv: RpnLevels, cell_anchors: torch.Tensor, logits: torch.Tensor, deltas: torch.Tensor, n: int, num_classes: int, topk: int,
+                     score_thresh: float, reg_weights: Sequence[float] = (1.0, 1.0, 1.0, 1.0), pitch_cls: Optional[int] = None,
+                     pitch_box: Optional[int] = None, out: Optional[dict] = None):
+    """[d2] RetinaNet.inference_single_image before its NMS (osr_retinanet_select, include/osr.h): logits / deltas are the level-major
+    buffers with row pitches pitch_cls (default A*K) / pitch_box (default 4A). -> dict(c_boxes, c_scores, c_cls, c_cand, c_src, counts,
+    status_flags, cap). `out`: a dict of these tensors to write into instead of fresh ones."""
+    lib = _lib.load()
+    a = lv.num_anchors
+    pitch_cls = a * num_classes if pitch_cls is None else int(pitch_cls)
+    pitch_box = 4 * a if pitch_box is None else int(pitch_box)
+    _need(cell_anchors, torch.float32, "cell_anchors"); _need(logits, None, "logits"); _need(deltas, torch.float32, "deltas")
+    if logits.dtype not in _DT:
+        raise OsrError(f"logits must be float32 / float16 / bfloat16, got {logits.dtype}")
+    cells = sum(n * lv.h[i] * lv.w[i] for i in range(lv.num_levels))
+    if pitch_cls >= a * num_classes and pitch_box >= 4 * a and (logits.numel() < cells * pitch_cls or deltas.numel() < cells * pitch_box):
+        raise OsrError(f"retinanet_select: logits ({logits.numel()}) / deltas ({deltas.numel()}) are shorter than {cells} cells x the pitches")
+    if tuple(cell_anchors.shape) != (lv.num_levels, a, 4):
+        raise OsrError(f"retinanet_select: cell_anchors {tuple(cell_anchors.shape)} != ({lv.num_levels}, {a}, 4)")
+    cap = lib.osr_retinanet_select_capacity(C.byref(lv), topk)
+    if cap < 0:
+        check(cap, "osr_retinanet_select_capacity")
+    wsb = lib.osr_retinanet_select_workspace_bytes(C.byref(lv), n, num_classes, topk)
+    if wsb < 0:
+        check(int(wsb), "osr_retinanet_select_workspace_bytes")
+    dev = logits.device
+    ws = torch.empty((wsb,), dtype=torch.uint8, device=dev)
+    if out is None:
+        out = dict(c_boxes=torch.empty((n, cap, 4), dtype=torch.float32, device=dev), c_scores=torch.empty((n, cap), dtype=torch.float32, device=dev),
+                   c_cls=torch.empty((n, cap), dtype=torch.int32, device=dev), c_cand=torch.empty((n, cap), dtype=torch.int32, device=dev),
+                   c_src=torch.empty((n, cap), dtype=torch.int32, device=dev), counts=torch.empty((n, lv.num_levels), dtype=torch.int32, device=dev),
+                   status_flags=torch.zeros((1,), dtype=torch.int32, device=dev))
+    else:
+        out = dict(out)
+        for key, dt in (("c_boxes", torch.float32), ("c_scores", torch.float32), ("c_cls", torch.int32), ("c_cand", torch.int32), ("c_src", torch.int32),
+                        ("counts", torch.int32), ("status_flags", torch.int32)):
+            _need(out[key], dt, key)
+        assert out["c_boxes"].numel() == n * cap * 4 and out["c_scores"].numel() == n * cap and out["counts"].numel() == n * lv.num_levels
+    rw = (C.c_float * 4)(*[float(v) for v in reg_weights])
+    check(lib.osr_retinanet_select(C.byref(lv), _p(cell_anchors), _p(logits), _DT[logits.dtype], pitch_cls, _p(deltas), pitch_box, n, num_classes, topk,
+                                   retinanet_logit_thresh(score_thresh), rw, _p(out["c_boxes"]), _p(out["c_scores"]), _p(out["c_cls"]), _p(out["c_cand"]),
+                                   _p(out["c_src"]), _p(out["counts"]), _p(out["status_flags"]), _p(ws), wsb, _stream()), "osr_retinanet_select")
+    out["cap"] = cap
+    return out
 
 
 def fastrcnn_candidates(logits, deltas, prop_boxes, prop_count, image_hw, num_classes: int, reg_weights=(10.0, 10.0, 5.0, 5.0),

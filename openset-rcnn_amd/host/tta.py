@@ -44,7 +44,9 @@ class GeneralizedRCNNWithTTA(nn.Module):
 
     def __init__(self, cfg, model):
         super().__init__()
-        from .modeling import CascadeROIHeads, GeneralizedRCNN, StandardROIHeads
+        from .modeling import CascadeROIHeads, GeneralizedRCNN, RetinaNet, StandardROIHeads
+        if isinstance(model, RetinaNet):
+            raise ValueError(RetinaNet.TTA_MESSAGE)
         if isinstance(getattr(model, "roi_heads", None), CascadeROIHeads):
             raise ValueError("TEST.AUG: test-time augmentation is not implemented for CascadeROIHeads (the merge re-scores the augmented boxes with "
                              "one box head; a cascade has one per stage)")

@@ -244,3 +244,25 @@ def random_cascade_params(seed: int = 0, stages: int = 3, num_classes: int = 80,
             elif s == 0:
                 p[k] = v
     return p
+
+
+def random_retinanet_params(seed: int = 0, num_classes: int = 80, num_anchors: int = 9, num_convs: int = 4, cls_bias: float = -4.595) -> Dict[str, torch.Tensor]:
+    """Seeded synthetic parameters for META_ARCHITECTURE "RetinaNet": random_params' BN-folded trunk with the FPN on res3..res5 only,
+    [d2] LastLevelP6P7 (backbone.top_block.p6 from res5, .p7) and RetinaNetHead (cls_subnet / bbox_subnet .{0,2,..}, cls_score,
+    bbox_pred), scaled so that the towers keep their input's scale and logits and deltas spread (the [d2] initialiser, std 0.01, gives
+    near-constant outputs). cls_bias: cls_score's bias (-4.595 = [d2]'s PRIOR_PROB 0.01)."""
+    p = {k: v for k, v in random_params(seed).items() if k.startswith("backbone.") and not k.startswith(("backbone.fpn_lateral2.", "backbone.fpn_output2."))}
+    g = torch.Generator().manual_seed(seed + 3000)
+
+    def conv(name, cout, cin, std, bias=0.0, bias_std=0.02):
+        p[name + ".weight"] = torch.randn(cout, cin, 3, 3, generator=g) * std
+        p[name + ".bias"] = torch.randn(cout, generator=g) * bias_std + bias
+
+    conv("backbone.top_block.p6", 256, 2048, 0.7 * math.sqrt(2.0 / (256 * 9)))
+    conv("backbone.top_block.p7", 256, 256, 0.7 * math.sqrt(2.0 / (256 * 9)))
+    for sub in ("cls_subnet", "bbox_subnet"):
+        for i in range(num_convs):
+            conv(f"head.{sub}.{2 * i}", 256, 256, math.sqrt(2.0 / (256 * 9)))
+    conv("head.cls_score", num_anchors * num_classes, 256, 0.02, bias=cls_bias, bias_std=0.0)
+    conv("head.bbox_pred", num_anchors * 4, 256, 0.004, bias_std=0.0)
+    return p
