@@ -275,11 +275,9 @@ def ops(osr):
 # ------------------------------------------------------------------------------------------------------------------------------
 # 1. the table against the engine
 # ------------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("stride_in_1x1", [True, False])
-def test_table_is_the_engines_forward(ops, stride_in_1x1):
-    from openset_rcnn_amd.host.engine import OpensetRCNNEngine
-    from openset_rcnn_amd.host.weights import random_params
-
+def record_launches(ops, fn):
+    """fn() with ops.conv2d / ops.linear wrapped -> [(the launch as an L(...) entry without its name, it came through ops.linear)], in
+    launch order; synchronised. (tests/test_conv_fwd_plans_engines.py records the later engines with it.)"""
     real_conv, real_linear = ops.conv2d, ops.linear
     sig = inspect.signature(real_conv)
     log, depth = [], [0]
@@ -301,27 +299,45 @@ def test_table_is_the_engines_forward(ops, stride_in_1x1):
         finally:
             depth[0] -= 1
 
+    ops.conv2d, ops.linear = conv, linear
+    try:
+        fn()
+        torch.cuda.synchronize()
+    finally:
+        ops.conv2d, ops.linear = real_conv, real_linear
+    return log
+
+
+def record_pass(ops, eng, n, H, W, streams):
+    """record_launches of one eng.forward_device pass over n random uint8 images padded to H x W under concurrent_streams(streams)."""
+    g = torch.Generator().manual_seed(n + H)
+    images = torch.randint(0, 256, (n, 3, H, W), generator=g, dtype=torch.uint8).to(DEV)
+    image_hw = torch.tensor([(H, W)] * n, dtype=torch.int32).to(DEV)
+
+    def run():
+        with ops.concurrent_streams(streams):
+            eng.forward_device(images, image_hw, H, W)
+    try:
+        return record_launches(ops, run)
+    finally:
+        del images
+        torch.cuda.empty_cache()
+
+
+@pytest.mark.parametrize("stride_in_1x1", [True, False])
+def test_table_is_the_engines_forward(ops, stride_in_1x1):
+    from openset_rcnn_amd.host.engine import OpensetRCNNEngine
+    from openset_rcnn_amd.host.weights import random_params
+
     eng = OpensetRCNNEngine(random_params(0), cfg=dict(stride_in_1x1=stride_in_1x1), dtype=F16, device=DEV)
     eng.fuse_res2 = eng.chain_res3 = eng.fuse_levels = False
     for gname, (n, H, W, streams) in GEOMS.items():
-        g = torch.Generator().manual_seed(n + H)
-        images = torch.randint(0, 256, (n, 3, H, W), generator=g, dtype=torch.uint8).to(DEV)
-        image_hw = torch.tensor([(H, W)] * n, dtype=torch.int32).to(DEV)
-        log.clear()
-        ops.conv2d, ops.linear = conv, linear
-        try:
-            with ops.concurrent_streams(streams):
-                eng.forward_device(images, image_hw, H, W)
-            torch.cuda.synchronize()
-        finally:
-            ops.conv2d, ops.linear = real_conv, real_linear
+        log = record_pass(ops, eng, n, H, W, streams)
         want = forward_table(n, H, W, streams, stride_in_1x1)
         for i, ((got, via_linear), e) in enumerate(zip(log, want)):
             assert got == e[1:], f"{gname}: launch {i} ({e[0]}): engine {got} != table {e[1:]}"
             assert via_linear == (e[8] is not None), f"{gname}: launch {i} ({e[0]}): ops.linear {via_linear}"
         assert len(log) == len(want), f"{gname}: {len(log)} launches, table {len(want)}"
-        del images
-        torch.cuda.empty_cache()
 
 
 # ------------------------------------------------------------------------------------------------------------------------------

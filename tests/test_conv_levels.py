@@ -25,9 +25,11 @@ def _pyramid(g, n, shapes, cin, dtype):
     return [(torch.randn(n, h, w, cin, generator=g) * 0.5).to(dtype).to(DEV) for h, w in shapes]
 
 
-# (n, level shapes, cin, cout, k): the bench's pyramid at batch 2; a 1 x 1 layer with two K slices and two column tiles; a single level
+# (n, level shapes, cin, cout, k): the bench's pyramid at batch 2; a 1 x 1 layer with two K slices and two column tiles; a single level;
+# a RetinaNet tower layer's pyramid (p3..p7 of a 104 x 136 pad, shared weight): p6 and p7 smaller than the filter
 CASES = [(2, [(200, 336), (100, 168), (50, 84), (25, 42)], 256, 256, 3),
          (3, [(37, 53), (19, 27), (10, 14), (5, 7), (3, 4)], 256, 256, 3),
+         (2, [(13, 17), (7, 9), (4, 5), (2, 3), (1, 2)], 256, 256, 3),
          (2, [(64, 65), (7, 9), (1, 1)], 128, 512, 1),
          (1, [(40, 52)], 192, 256, 3)]
 
