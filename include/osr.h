@@ -587,7 +587,7 @@ osr_status osr_fastrcnn_candidates(const float* logits, const float* deltas, int
                                    int32_t* c_count, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
- * [d2] CascadeROIHeads (Cascade R-CNN; csrc/osr_cascade.hip): the glue between the stages, on the stock engine's fixed-capacity
+ * [d2] CascadeROIHeads (Cascade R-CNN; csrc/osr_cascade.hip, csrc/osr_det_tail.hip): the glue between the stages, on the stock engine's fixed-capacity
  * row lists. m = n * seg_rows rows; row r belongs to image r / seg_rows and exists iff batch_idx[r] >= 0. No compaction, no
  * atomics, no host sync; repeats are bit-identical.
  *

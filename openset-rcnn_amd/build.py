@@ -34,7 +34,7 @@ SOURCES = {
     "osr_retinanet.hip": ["-ffp-contract=off"],  # (decodes like osr_rpn.hip's decode_mode 1)
     "osr_roi_align.hip": ["-ffp-contract=off"],
     "osr_det_tail.hip": ["-ffp-contract=off"],
-    "osr_cascade.hip": ["-ffp-contract=off"],  # (as osr_det_tail.hip: one stage reproduces osr_fastrcnn_candidates bit for bit)
+    "osr_cascade.hip": ["-ffp-contract=off"],  # (decodes and matches like osr_det_tail.hip / osr_std_train.hip)
     "osr_mask_head.hip": [],
     "osr_mask_train.hip": ["-ffp-contract=off"],
     "osr_tta.hip": ["-ffp-contract=off"],

@@ -7,6 +7,7 @@
 // Both shipped yaml files use "iou" for the CF-RPN and "smooth_l1" with beta 0 everywhere else.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "osr_boxes.h"
 
 enum OsrBoxLoss { OSR_LOSS_IOU = 0, OSR_LOSS_SMOOTH_L1 = 1, OSR_LOSS_GIOU = 2, OSR_LOSS_DIOU = 3, OSR_LOSS_CIOU = 4 };
 
@@ -21,15 +22,6 @@ __device__ __forceinline__ float osr_smooth_l1_grad(float x, float beta) {
     return x > 0.f ? 1.f : (x < 0.f ? -1.f : 0.f);
 }
 
-// [d2] pairwise_iou of two boxes in fp32: inter / (a1 + a2 - inter) where inter > 0, else 0 (the matchers of the RPN, the RoI heads
-// and the cascade's stage transitions; built without FMA contraction wherever an index depends on it)
-__device__ __forceinline__ float osr_pairwise_iou(const float4 g, const float4 b) {
-    const float a1 = (g.z - g.x) * (g.w - g.y), a2 = (b.z - b.x) * (b.w - b.y);
-    const float w = fmaxf(fminf(g.z, b.z) - fmaxf(g.x, b.x), 0.f), h = fmaxf(fminf(g.w, b.w) - fmaxf(g.y, b.y), 0.f);
-    const float inter = w * h;
-    return inter > 0.f ? inter / (a1 + a2 - inter) : 0.f;
-}
-
 // [d2] Box2BoxTransform.get_deltas(src, tgt) with weights (wx, wy, ww, wh): the targets of the "smooth_l1" loss
 __device__ __forceinline__ float4 osr_b2b_get_deltas(float4 s, float4 t, float wx, float wy, float ww, float wh) {
     const float sw = s.z - s.x, sh = s.w - s.y, scx = s.x + 0.5f * sw, scy = s.y + 0.5f * sh;
@@ -37,16 +29,8 @@ __device__ __forceinline__ float4 osr_b2b_get_deltas(float4 s, float4 t, float w
     return make_float4(wx * (tcx - scx) / sw, wy * (tcy - scy) / sh, ww * logf(tw / sw), wh * logf(th / sh));
 }
 
-// [d2] Box2BoxTransform.apply_deltas(d, src): the decoded box of the other losses. Centre = d/w * size + centre, size =
-// exp(min(d/w, clamp)) * size; the decoded size also goes to *pw, *ph (the gradient through the exponential needs it, and it is zero
-// where d/w reaches the clamp).
-#define OSR_B2B_SCALE_CLAMP 4.135166556742356f  // log(1000 / 16)
-__device__ __forceinline__ float4 osr_b2b_apply_deltas(float4 s, const float* d, float wx, float wy, float ww, float wh, float* pw, float* ph) {
-    const float sw = s.z - s.x, sh = s.w - s.y, scx = s.x + 0.5f * sw, scy = s.y + 0.5f * sh;
-    *pw = expf(fminf(d[2] / ww, OSR_B2B_SCALE_CLAMP)) * sw; *ph = expf(fminf(d[3] / wh, OSR_B2B_SCALE_CLAMP)) * sh;
-    const float pcx = d[0] / wx * sw + scx, pcy = d[1] / wy * sh + scy;
-    return make_float4(pcx - 0.5f * *pw, pcy - 0.5f * *ph, pcx + 0.5f * *pw, pcy + 0.5f * *ph);
-}
+// [d2] Box2BoxTransform.apply_deltas(d, src), the decoded box of the other losses, is osr_boxes.h's osr_b2b_apply_deltas in its
+// default (fminf) form, with OSR_B2B_SCALE_CLAMP; the matchers' osr_pairwise_iou lives there too.
 
 // Loss of a predicted box p = (x1, y1, x2, y2) against the target g, and its gradient w.r.t. the four coordinates of p.
 // type: OSR_LOSS_IOU / GIOU / DIOU / CIOU. The enclosing-box / intersection corners pick the predicted coordinate on strict

@@ -1,24 +1,21 @@
-// [d2] CascadeROIHeads: what sits between the stages (osr_cascade_refine) and the S-stage inference tail in front of the NMS
-// (osr_cascade_candidates). Both work on the stock engine's fixed-capacity row lists: m = n x seg_rows rows, row r belongs to image
-// r / seg_rows and exists iff batch_idx[r] >= 0. No compaction, no atomics, no host sync; every sum is taken in a fixed order, so a
-// repeat is bit-identical. Built without FMA contraction, like osr_det_tail.hip: the decode of osr_box_loss.h then rounds exactly as
-// fastrcnn_cand_kernel's does, and osr_cascade_candidates with one stage reproduces osr_fastrcnn_candidates bit for bit.
+// [d2] CascadeROIHeads: what sits between the stages (osr_cascade_refine). The S-stage inference tail in front of the NMS,
+// osr_cascade_candidates, is cand_kernel of osr_det_tail.hip. It works on the stock engine's fixed-capacity row lists: m = n x seg_rows
+// rows, row r belongs to image r / seg_rows and exists iff batch_idx[r] >= 0. No compaction, no atomics, no host sync; every sum is
+// taken in a fixed order, so a repeat is bit-identical. Built without FMA contraction, like osr_det_tail.hip: the decode of
+// osr_boxes.h rounds alike in both.
 //
-// Launch shape: these are latency-bound glue kernels (a few hundred to two thousand rows per image, tens of flops per row and
-// ground-truth box). One workgroup per image, one thread per row and pass; the image's ground truth sits in LDS (16-byte boxes), the
-// rows are read and written as float4. The per-image counts are integer sums over the workgroup: wave shuffles, then the wave
-// partials in wave order by one thread.
+// Launch shape: a latency-bound glue kernel (a few hundred to two thousand rows per image, tens of flops per row and ground-truth
+// box). One workgroup per image, one thread per row and pass; the image's ground truth sits in LDS (16-byte boxes), the rows are read
+// and written as float4. The per-image counts are integer sums over the workgroup: wave shuffles, then the wave partials in wave
+// order by one thread.
 //
 // gmax is bounded by the static LDS table of the image's ground truth: CR_MAX_GT = 1024 boxes (16 KB) + their classes (8 KB), far
 // above what a COCO / LVIS image carries; a larger gmax is refused with OSR_ERR_INVALID_ARG.
 #include "osr_common.h"
-#include "osr_box_loss.h"
+#include "osr_boxes.h"
 
 #define CR_MAX_GT 1024
 #define CR_THREADS 256
-
-// [d2] Boxes.clip: clamp(min = 0, max = size); a NaN stays a NaN
-__device__ __forceinline__ float cr_clamp(float v, float hi) { return v < 0.f ? 0.f : (v > hi ? hi : v); }
 
 __device__ __forceinline__ int cr_wave_sum_int(int v) {
 #pragma unroll
@@ -58,13 +55,9 @@ __global__ __launch_bounds__(CR_THREADS) void cascade_refine_kernel(const float*
         if (exists) {
             const float4 s = *reinterpret_cast<const float4*>(boxes + r * 4);
             const float4 d4 = *reinterpret_cast<const float4*>(deltas + r * 4);
-            const float d[4] = {d4.x, d4.y, d4.z, d4.w};
-            float pw, ph;
-            b = osr_b2b_apply_deltas(s, d, rw.x, rw.y, rw.z, rw.w, &pw, &ph);
-            // (fminf inside the decode drops a NaN size delta; torch.clamp keeps it)
-            if (d4.z != d4.z) { b.x = d4.z; b.z = d4.z; }
-            if (d4.w != d4.w) { b.y = d4.w; b.w = d4.w; }
-            b.x = cr_clamp(b.x, iw); b.y = cr_clamp(b.y, ih); b.z = cr_clamp(b.z, iw); b.w = cr_clamp(b.w, ih);
+            // a box that is not valid is handed on as torch computes it, its NaN kept through the clip: without drop_empty every row stays
+            bool valid;
+            b = osr_box_clip<true>(osr_b2b_decode(s, d4, rw, &valid), iw, ih);
             // [d2] Boxes.nonempty: width > 0 and height > 0 (false for a NaN)
             if (drop_empty && !((b.z - b.x) > 0.f && (b.w - b.y) > 0.f)) { exists = false; b = zero; }
         }
@@ -129,122 +122,5 @@ extern "C" osr_status osr_cascade_refine(const float* boxes, const int32_t* batc
                        (const long long*)gt_classes, gt_count, gmax, num_classes, iou_thr, boxes_out, batch_idx_out, (long long*)classes_out,
                        gt_boxes_out, gt_idx_out, counts);
     OSR_CHECK_LAUNCH("osr_cascade_refine");
-    return OSR_OK;
-}
-
-// ------------------------------------------------------------------------------------------------------
-// [d2] CascadeROIHeads._forward_box at inference, behind the last stage: the stages' softmax scores averaged, the last stage's
-// class-agnostic deltas decoded on its input boxes, then fast_rcnn_inference_single_image up to its NMS. fastrcnn_cand_kernel of
-// osr_det_tail.hip with S score sets: workgroup per image, thread per row, (row, class) pairs in row-major order.
-// ------------------------------------------------------------------------------------------------------
-#define CC_MAX_CLASSES 128
-
-struct CcLogits { const float* p[OSR_CASCADE_MAX_STAGES]; };
-
-template <int S>
-__device__ __forceinline__ float cc_score(const CcLogits& lg, long long off, int c, const float (&mx)[S], const float (&sum)[S], float inv) {
-    float acc = expf(lg.p[0][off + c] - mx[0]) / sum[0];
-#pragma unroll
-    for (int s = 1; s < S; ++s) acc += expf(lg.p[s][off + c] - mx[s]) / sum[s];
-    return S == 1 ? acc : acc * inv;  // (one stage: the factor is exactly 1)
-}
-
-template <int S>
-__global__ __launch_bounds__(1024) void cascade_cand_kernel(CcLogits lg, const float* __restrict__ deltas, int K, const float* __restrict__ boxes,
-                                                            const int* __restrict__ batch_idx, int seg_rows, const int* __restrict__ image_hw,
-                                                            float4 rw, float score_thresh, float inv, float* __restrict__ c_boxes,
-                                                            float* __restrict__ c_scores, int* __restrict__ c_cls, int* __restrict__ c_row,
-                                                            int* __restrict__ c_count) {
-    __shared__ int s_scan[32];
-    const int img = blockIdx.x, tid = threadIdx.x;
-    const long long ccap = (long long)seg_rows * K;
-    const float ih = (float)image_hw[img * 2], iw = (float)image_hw[img * 2 + 1];
-    int run = 0;
-    for (int j0 = 0; j0 < seg_rows; j0 += blockDim.x) {
-        const int j = j0 + tid;
-        const long long r = (long long)img * seg_rows + j, off = r * (K + 1);
-        int nk = 0;
-        float mx[S], sum[S];
-        float4 b = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (j < seg_rows && batch_idx[r] >= 0) {
-#pragma unroll
-            for (int s = 0; s < S; ++s) {
-                const float* l = lg.p[s] + off;
-                float m = l[0];
-                for (int c = 1; c <= K; ++c) m = fmaxf(m, l[c]);
-                float t = 0.f;
-                for (int c = 0; c <= K; ++c) t += expf(l[c] - m);
-                mx[s] = m; sum[s] = t;
-            }
-            // one walk over the classes: every score (the background's too) must be finite, the foreground ones are counted
-            bool ok = true;
-            int above = 0;
-            for (int c = 0; c <= K; ++c) {
-                const float p = cc_score<S>(lg, off, c, mx, sum, inv);
-                ok = ok && osr_finite(p);
-                above += c < K && p > score_thresh;
-            }
-            const float4 pb = *reinterpret_cast<const float4*>(boxes + r * 4);
-            const float4 d4 = *reinterpret_cast<const float4*>(deltas + r * 4);
-            const float d[4] = {d4.x, d4.y, d4.z, d4.w};
-            float pw, ph;
-            b = osr_b2b_apply_deltas(pb, d, rw.x, rw.y, rw.z, rw.w, &pw, &ph);
-            // (fminf drops a NaN delta; torch.clamp keeps it)
-            ok = ok && osr_finite(b.x) && osr_finite(b.y) && osr_finite(b.z) && osr_finite(b.w) && d4.z == d4.z && d4.w == d4.w;
-            b.x = fminf(fmaxf(b.x, 0.f), iw); b.y = fminf(fmaxf(b.y, 0.f), ih);
-            b.z = fminf(fmaxf(b.z, 0.f), iw); b.w = fminf(fmaxf(b.w, 0.f), ih);
-            nk = ok ? above : 0;
-        }
-        int tot;
-        const int pos = run + osr_block_excl_scan(nk, s_scan, &tot);
-        if (nk) {
-            int o = pos;
-            for (int c = 0; c < K; ++c) {
-                const float p = cc_score<S>(lg, off, c, mx, sum, inv);
-                if (p > score_thresh) {
-                    const long long q = (long long)img * ccap + o;
-                    *reinterpret_cast<float4*>(c_boxes + q * 4) = b;
-                    c_scores[q] = p; c_cls[q] = c; c_row[q] = j;
-                    ++o;
-                }
-            }
-        }
-        run += tot;
-    }
-    if (tid == 0) c_count[img] = run;
-}
-
-extern "C" osr_status osr_cascade_candidates(const float* const* logits, int32_t num_stages, const float* deltas, int32_t num_classes,
-                                             const float* boxes, const int32_t* batch_idx, int32_t n, int32_t seg_rows, const int32_t* image_hw,
-                                             const float reg_weights[4], float score_thresh, float* c_boxes, float* c_scores, int32_t* c_cls,
-                                             int32_t* c_row, int32_t* c_count, void* stream) {
-    OSR_REQUIRE(logits && deltas && boxes && batch_idx && image_hw && reg_weights && c_boxes && c_scores && c_cls && c_row && c_count,
-                OSR_ERR_INVALID_ARG, "osr_cascade_candidates: null pointer");
-    OSR_REQUIRE(num_stages >= 1 && num_stages <= OSR_CASCADE_MAX_STAGES, OSR_ERR_INVALID_ARG, "osr_cascade_candidates: 1..%d stages", OSR_CASCADE_MAX_STAGES);
-    OSR_REQUIRE(n >= 1 && seg_rows >= 1 && num_classes >= 1 && num_classes <= CC_MAX_CLASSES && (int64_t)n * seg_rows * num_classes < (1ll << 31),
-                OSR_ERR_INVALID_ARG, "osr_cascade_candidates: bad sizes (1..%d classes)", CC_MAX_CLASSES);
-    OSR_REQUIRE(reg_weights[0] > 0.f && reg_weights[1] > 0.f && reg_weights[2] > 0.f && reg_weights[3] > 0.f, OSR_ERR_INVALID_ARG,
-                "osr_cascade_candidates: regression weights must be positive");
-    OSR_REQUIRE((((uintptr_t)boxes | (uintptr_t)deltas | (uintptr_t)c_boxes) & 15) == 0, OSR_ERR_INVALID_ARG,
-                "osr_cascade_candidates: box arrays must be 16-byte aligned");
-    CcLogits lg;
-    for (int s = 0; s < OSR_CASCADE_MAX_STAGES; ++s) {
-        lg.p[s] = s < num_stages ? logits[s] : logits[0];
-        OSR_REQUIRE(lg.p[s], OSR_ERR_INVALID_ARG, "osr_cascade_candidates: null logits of stage %d", s);
-    }
-    const float4 rw = make_float4(reg_weights[0], reg_weights[1], reg_weights[2], reg_weights[3]);
-    const float inv = (float)(1.0 / (double)num_stages);  // [d2]: sum(scores) * (1.0 / num_stages), the factor rounded to fp32
-    hipStream_t st = (hipStream_t)stream;
-#define CC_LAUNCH(S_)                                                                                                                       \
-    hipLaunchKernelGGL(cascade_cand_kernel<S_>, dim3(n), dim3(1024), 0, st, lg, deltas, num_classes, boxes, batch_idx, seg_rows, image_hw, rw, \
-                       score_thresh, inv, c_boxes, c_scores, c_cls, c_row, c_count)
-    switch (num_stages) {
-        case 1: CC_LAUNCH(1); break;
-        case 2: CC_LAUNCH(2); break;
-        case 3: CC_LAUNCH(3); break;
-        default: CC_LAUNCH(4); break;
-    }
-#undef CC_LAUNCH
-    OSR_CHECK_LAUNCH("osr_cascade_candidates");
     return OSR_OK;
 }

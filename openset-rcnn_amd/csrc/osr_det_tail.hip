@@ -7,9 +7,9 @@
 // Compile with -ffp-contract=off: IoU / clip / threshold arithmetic must round like the oracle's so that
 // kept-index lists are bit-exact.
 #include "osr_common.h"
+#include "osr_boxes.h"
+#include "osr_loss_common.h"
 #include "osr_pln_dist.h"
-
-#define SCALE_CLAMP_F 4.135166556742356f  // log(1000/16)
 
 // ------------------------------------------------------------------------------------------------------
 // box predictor tail: wave per RoI row
@@ -54,27 +54,16 @@ __global__ __launch_bounds__(256) void box_pred_tail_kernel(const float* __restr
             d0 += b[0]; d1 += b[1]; d2 += b[2]; d3 += b[3];
             const float iou = 1.0f / (1.0f + expf(-(d4 + b[4])));
             const float4 p = *reinterpret_cast<const float4*>(proposals + r * 4);
-            // [d2] Box2BoxTransform.apply_deltas
-            const float pw_ = p.z - p.x, ph_ = p.w - p.y;
-            const float cx = p.x + 0.5f * pw_, cy = p.y + 0.5f * ph_;
-            const float dx = d0 / wx, dy = d1 / wy;
-            float dw = d2 / ww, dh = d3 / wh;
-            dw = dw > SCALE_CLAMP_F ? SCALE_CLAMP_F : dw;  // NaN stays NaN like torch.clamp(max=)
-            dh = dh > SCALE_CLAMP_F ? SCALE_CLAMP_F : dh;
-            const float pcx = dx * pw_ + cx, pcy = dy * ph_ + cy;
-            const float qw = expf(dw) * pw_, qh = expf(dh) * ph_;
-            float x1 = pcx - 0.5f * qw, y1 = pcy - 0.5f * qh, x2 = pcx + 0.5f * qw, y2 = pcy + 0.5f * qh;
+            bool valid;
+            const float4 box = osr_b2b_decode(p, make_float4(d0, d1, d2, d3), make_float4(wx, wy, ww, wh), &valid);
             const float c_ = ctr[r];
             const float s = mean_type == 0 ? sqrtf(iou * c_) : (iou + c_) / 2.0f;
-            const bool valid = osr_finite(x1) && osr_finite(y1) && osr_finite(x2) && osr_finite(y2) && osr_finite(s);
             const float ih = (float)image_hw[bi * 2], iw = (float)image_hw[bi * 2 + 1];
-            x1 = fminf(fmaxf(x1, 0.f), iw); y1 = fminf(fmaxf(y1, 0.f), ih);
-            x2 = fminf(fmaxf(x2, 0.f), iw); y2 = fminf(fmaxf(y2, 0.f), ih);
             *reinterpret_cast<float4*>(pred_deltas + r * 4) = make_float4(d0, d1, d2, d3);
             pred_iou[r] = iou;
-            *reinterpret_cast<float4*>(boxes + r * 4) = make_float4(x1, y1, x2, y2);
+            *reinterpret_cast<float4*>(boxes + r * 4) = osr_box_clip(box, iw, ih);
             score[r] = s;
-            cand[r] = (valid && s > score_thresh) ? 1 : 0;
+            cand[r] = (valid && osr_finite(s) && s > score_thresh) ? 1 : 0;
         }
     }
 }
@@ -443,6 +432,21 @@ extern "C" osr_status osr_pln_tail(const float* emb, int64_t rows, int32_t d, co
 // ------------------------------------------------------------------------------------------------------
 #define SM_MAX_KNOWN 64
 
+// The candidates of one row, written from slot q on: every class c < K with score(c) > thresh, in class order, as (box(c), score,
+// class, row). The emit half of the scan-then-emit loop of softmax_cand_kernel and cand_kernel.
+template <class Score, class Box>
+__device__ __forceinline__ void cand_emit_row(int K, float thresh, Score score, Box box, long long q, int row, float* __restrict__ o_boxes,
+                                              float* __restrict__ o_scores, int* __restrict__ o_cls, int* __restrict__ o_row) {
+    for (int c = 0; c < K; ++c) {
+        const float p = score(c);
+        if (p > thresh) {
+            *reinterpret_cast<float4*>(o_boxes + q * 4) = box(c);
+            o_scores[q] = p; o_cls[q] = c; o_row[q] = row;
+            ++q;
+        }
+    }
+}
+
 __global__ __launch_bounds__(1024) void softmax_cand_kernel(const float* __restrict__ logits, int K, const float* __restrict__ det_boxes,
                                                             const float* __restrict__ det_scores, const long long* __restrict__ pred_class,
                                                             const int* __restrict__ det_count, int seg_rows, long long unknown_id,
@@ -465,15 +469,12 @@ __global__ __launch_bounds__(1024) void softmax_cand_kernel(const float* __restr
         bool known = false, okbox = false;
         if (j < cnt) {
             bx = *reinterpret_cast<const float4*>(det_boxes + r * 4);
-            okbox = osr_finite(bx.x) && osr_finite(bx.y) && osr_finite(bx.z) && osr_finite(bx.w);
+            okbox = osr_box_finite(bx);
             const long long pc = pred_class[r];
             known = pc != unknown_id;
             if (known) {
                 const float* lg = logits + r * (K + 1);
-                mx = lg[0];
-                for (int c = 1; c <= K; ++c) mx = fmaxf(mx, lg[c]);
-                sum = 0.f;
-                for (int c = 0; c <= K; ++c) sum += expf(lg[c] - mx);
+                mx = osr_softmax_row(lg, K + 1, &sum);
                 bool okp = true;
                 for (int c = 0; c <= K; ++c) okp = okp && osr_finite(expf(lg[c] - mx) / sum);
                 if (okbox && okp)
@@ -488,16 +489,8 @@ __global__ __launch_bounds__(1024) void softmax_cand_kernel(const float* __restr
         const int pu = run_u + osr_block_excl_scan(nu, s_scan, &tu);
         if (nk) {
             const float* lg = logits + r * (K + 1);
-            int o = pk;
-            for (int c = 0; c < K; ++c) {
-                const float p = expf(lg[c] - mx) / sum;
-                if (p > known_thresh) {
-                    const long long q = (long long)img * kcap + o;
-                    *reinterpret_cast<float4*>(k_boxes + q * 4) = bx;
-                    k_scores[q] = p; k_cls[q] = c; k_det[q] = j;
-                    ++o;
-                }
-            }
+            cand_emit_row(K, known_thresh, [&](int c) { return expf(lg[c] - mx) / sum; }, [&](int) { return bx; }, (long long)img * kcap + pk, j,
+                          k_boxes, k_scores, k_cls, k_det);
         }
         if (nu) {
             const long long q = (long long)img * seg_rows + pu;
@@ -527,79 +520,84 @@ extern "C" osr_status osr_softmax_candidates(const float* logits, int32_t num_kn
 }
 
 // ------------------------------------------------------------------------------------------------------
-// [d2] FastRCNNOutputLayers.inference -> fast_rcnn_inference_single_image, everything before the NMS (BASELINE config 1:
-// Base-RCNN-FPN.yaml's StandardROIHeads): softmax over K+1 logits, class-specific Box2BoxTransform decode (K*4 deltas per
-// row; 4 when class-agnostic), rows with a non-finite box or probability dropped, clip, (row, class) pairs with
-// p > score_thresh emitted in row-major order (= nonzero()). Block per image, thread per proposal row.
+// [d2] FastRCNNOutputLayers.inference -> fast_rcnn_inference_single_image, everything before the NMS, for StandardROIHeads (BASELINE
+// config 1: Base-RCNN-FPN.yaml) and, with S score sets, for CascadeROIHeads._forward_box behind its last stage: softmax over K+1
+// logits (the mean of the S stages' softmax scores), Box2BoxTransform decode of the row's box (K*4 deltas per row, 4 when
+// class-agnostic), rows with a non-finite box or score dropped, clip, (row, class) pairs with score > score_thresh emitted in
+// row-major order (= nonzero()). Block per image, thread per row and pass; S is a compile-time constant.
+// A row exists below the image's prefix count (prop_count, StandardROIHeads' lists) and where batch_idx is not negative (the
+// cascade's lists, which keep every row's slot from stage to stage); either pointer may be null.
 // ------------------------------------------------------------------------------------------------------
-#define FR_MAX_CLASSES 128
+#define CAND_MAX_CLASSES 128
 
-__global__ __launch_bounds__(1024) void fastrcnn_cand_kernel(const float* __restrict__ logits, const float* __restrict__ deltas, int K, int kbox,
-                                                             const float* __restrict__ prop_boxes, const int* __restrict__ prop_count,
-                                                             int seg_rows, const int* __restrict__ image_hw, float4 rw, float score_thresh,
-                                                             float* __restrict__ c_boxes, float* __restrict__ c_scores, int* __restrict__ c_cls,
-                                                             int* __restrict__ c_row, int* __restrict__ c_count) {
+struct CandLogits { const float* p[OSR_CASCADE_MAX_STAGES]; };
+
+template <int S>
+__device__ __forceinline__ float cand_score(const CandLogits& lg, long long off, int c, const float (&mx)[S], const float (&sum)[S], float inv) {
+    float acc = expf(lg.p[0][off + c] - mx[0]) / sum[0];
+#pragma unroll
+    for (int s = 1; s < S; ++s) acc += expf(lg.p[s][off + c] - mx[s]) / sum[s];
+    return S == 1 ? acc : acc * inv;  // (one stage: the factor is exactly 1)
+}
+
+template <int S>
+__global__ __launch_bounds__(1024) void cand_kernel(CandLogits lg, const float* __restrict__ deltas, int K, int kbox, const float* __restrict__ boxes,
+                                                    const int* __restrict__ prop_count, const int* __restrict__ batch_idx, int seg_rows,
+                                                    const int* __restrict__ image_hw, float4 rw, float score_thresh, float inv,
+                                                    float* __restrict__ c_boxes, float* __restrict__ c_scores, int* __restrict__ c_cls,
+                                                    int* __restrict__ c_row, int* __restrict__ c_count) {
     __shared__ int s_scan[32];
     const int img = blockIdx.x, tid = threadIdx.x;
-    int cnt = prop_count[img];
-    if (cnt > seg_rows) cnt = seg_rows;
+    const int cnt = prop_count ? min(prop_count[img], seg_rows) : seg_rows;
     const long long ccap = (long long)seg_rows * K;
     const float ih = (float)image_hw[img * 2], iw = (float)image_hw[img * 2 + 1];
-    const float kClamp = 4.135166556742356f;  // log(1000 / 16)
     int run = 0;
     for (int j0 = 0; j0 < seg_rows; j0 += blockDim.x) {
         const int j = j0 + tid;
-        const long long r = (long long)img * seg_rows + j;
+        const long long r = (long long)img * seg_rows + j, off = r * (K + 1);
+        const float* dl = deltas + r * (long long)kbox * 4;
+        const auto delta = [&](int c) { return make_float4(dl[c * 4], dl[c * 4 + 1], dl[c * 4 + 2], dl[c * 4 + 3]); };
         int nk = 0;
-        float mx = 0.f, sum = 1.f;
-        float4 pb = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (j < cnt) {
-            pb = *reinterpret_cast<const float4*>(prop_boxes + r * 4);
-            const float* lg = logits + r * (K + 1);
-            mx = lg[0];
-            for (int c = 1; c <= K; ++c) mx = fmaxf(mx, lg[c]);
-            sum = 0.f;
-            for (int c = 0; c <= K; ++c) sum += expf(lg[c] - mx);
+        float mx[S], sum[S];
+        float4 pb = make_float4(0.f, 0.f, 0.f, 0.f), b0 = pb;
+        if (j < cnt && (!batch_idx || batch_idx[r] >= 0)) {
+#pragma unroll
+            for (int s = 0; s < S; ++s) mx[s] = osr_softmax_row(lg.p[s] + off, K + 1, &sum[s]);
+            // one walk over the classes: every score (the background's too) must be finite, the foreground ones are counted
             bool ok = true;
-            for (int c = 0; c <= K; ++c) ok = ok && osr_finite(expf(lg[c] - mx) / sum);
-            // every class's decoded box must be finite, or the whole row is dropped (valid_mask over dim 1)
-            const float w = pb.z - pb.x, h = pb.w - pb.y, cx = pb.x + 0.5f * w, cy = pb.y + 0.5f * h;
-            const float* dl = deltas + r * (long long)kbox * 4;
-            for (int c = 0; c < kbox && ok; ++c) {
-                const float dx = dl[c * 4] / rw.x, dy = dl[c * 4 + 1] / rw.y, dw = fminf(dl[c * 4 + 2] / rw.z, kClamp), dh = fminf(dl[c * 4 + 3] / rw.w, kClamp);
-                const float pcx = dx * w + cx, pcy = dy * h + cy, pw = expf(dw) * w, ph = expf(dh) * h;
-                ok = osr_finite(pcx - 0.5f * pw) && osr_finite(pcy - 0.5f * ph) && osr_finite(pcx + 0.5f * pw) && osr_finite(pcy + 0.5f * ph) &&
-                     dl[c * 4 + 2] == dl[c * 4 + 2] && dl[c * 4 + 3] == dl[c * 4 + 3];  // (fminf drops a NaN delta; torch.clamp keeps it)
+            int above = 0;
+            for (int c = 0; c <= K; ++c) {
+                const float p = cand_score<S>(lg, off, c, mx, sum, inv);
+                ok = ok && osr_finite(p);
+                above += c < K && p > score_thresh;
             }
-            if (ok)
-                for (int c = 0; c < K; ++c) nk += (expf(lg[c] - mx) / sum) > score_thresh;
+            // every class's decoded box must be valid, or the whole row is dropped (valid_mask over dim 1); b0 ends as the
+            // class-agnostic box
+            pb = *reinterpret_cast<const float4*>(boxes + r * 4);
+            for (int c = 0; c < kbox && ok; ++c) b0 = osr_b2b_decode(pb, delta(c), rw, &ok);
+            nk = ok ? above : 0;
         }
         int tot;
         const int pos = run + osr_block_excl_scan(nk, s_scan, &tot);
-        if (nk) {
-            const float* lg = logits + r * (K + 1);
-            const float* dl = deltas + r * (long long)kbox * 4;
-            const float w = pb.z - pb.x, h = pb.w - pb.y, cx = pb.x + 0.5f * w, cy = pb.y + 0.5f * h;
-            int o = pos;
-            for (int c = 0; c < K; ++c) {
-                const float p = expf(lg[c] - mx) / sum;
-                if (p > score_thresh) {
-                    const int cb = kbox > 1 ? c : 0;
-                    const float dx = dl[cb * 4] / rw.x, dy = dl[cb * 4 + 1] / rw.y, dw = fminf(dl[cb * 4 + 2] / rw.z, kClamp), dh = fminf(dl[cb * 4 + 3] / rw.w, kClamp);
-                    const float pcx = dx * w + cx, pcy = dy * h + cy, pw = expf(dw) * w, ph = expf(dh) * h;
-                    float4 b = make_float4(pcx - 0.5f * pw, pcy - 0.5f * ph, pcx + 0.5f * pw, pcy + 0.5f * ph);
-                    b.x = fminf(fmaxf(b.x, 0.f), iw); b.y = fminf(fmaxf(b.y, 0.f), ih);
-                    b.z = fminf(fmaxf(b.z, 0.f), iw); b.w = fminf(fmaxf(b.w, 0.f), ih);
-                    const long long q = (long long)img * ccap + o;
-                    *reinterpret_cast<float4*>(c_boxes + q * 4) = b;
-                    c_scores[q] = p; c_cls[q] = c; c_row[q] = j;
-                    ++o;
-                }
-            }
+        if (nk) {  // a class's own box is decoded again here, for the emitted pairs only (its verdict was settled above)
+            bool v;
+            const auto box = [&](int c) { return osr_box_clip(kbox > 1 ? osr_b2b_decode(pb, delta(c), rw, &v) : b0, iw, ih); };
+            cand_emit_row(K, score_thresh, [&](int c) { return cand_score<S>(lg, off, c, mx, sum, inv); }, box, (long long)img * ccap + pos, j,
+                          c_boxes, c_scores, c_cls, c_row);
         }
         run += tot;
     }
     if (tid == 0) c_count[img] = run;
+}
+
+template <int S>
+static void cand_launch(const CandLogits& lg, const float* deltas, int K, int kbox, const float* boxes, const int* prop_count, const int* batch_idx,
+                        int n, int seg_rows, const int* image_hw, const float reg_weights[4], float score_thresh, float* c_boxes, float* c_scores,
+                        int* c_cls, int* c_row, int* c_count, void* stream) {
+    const float inv = (float)(1.0 / (double)S);  // [d2]: sum(scores) * (1.0 / num_stages), the factor rounded to fp32
+    hipLaunchKernelGGL(cand_kernel<S>, dim3(n), dim3(1024), 0, (hipStream_t)stream, lg, deltas, K, kbox, boxes, prop_count, batch_idx, seg_rows, image_hw,
+                       make_float4(reg_weights[0], reg_weights[1], reg_weights[2], reg_weights[3]), score_thresh, inv, c_boxes, c_scores, c_cls, c_row,
+                       c_count);
 }
 
 extern "C" osr_status osr_fastrcnn_candidates(const float* logits, const float* deltas, int32_t num_classes, int32_t num_bbox_reg_classes,
@@ -608,15 +606,47 @@ extern "C" osr_status osr_fastrcnn_candidates(const float* logits, const float* 
                                               float* c_scores, int32_t* c_cls, int32_t* c_row, int32_t* c_count, void* stream) {
     OSR_REQUIRE(logits && deltas && prop_boxes && prop_count && image_hw && reg_weights && c_boxes && c_scores && c_cls && c_row && c_count,
                 OSR_ERR_INVALID_ARG, "osr_fastrcnn_candidates: null pointer");
-    OSR_REQUIRE(n >= 1 && seg_rows >= 1 && num_classes >= 1 && num_classes <= FR_MAX_CLASSES && (num_bbox_reg_classes == 1 || num_bbox_reg_classes == num_classes),
-                OSR_ERR_INVALID_ARG, "osr_fastrcnn_candidates: bad sizes (1..%d classes; box regression class-agnostic or per class)", FR_MAX_CLASSES);
+    OSR_REQUIRE(n >= 1 && seg_rows >= 1 && num_classes >= 1 && num_classes <= CAND_MAX_CLASSES && (num_bbox_reg_classes == 1 || num_bbox_reg_classes == num_classes),
+                OSR_ERR_INVALID_ARG, "osr_fastrcnn_candidates: bad sizes (1..%d classes; box regression class-agnostic or per class)", CAND_MAX_CLASSES);
     OSR_REQUIRE(reg_weights[0] > 0.f && reg_weights[1] > 0.f && reg_weights[2] > 0.f && reg_weights[3] > 0.f, OSR_ERR_INVALID_ARG,
                 "osr_fastrcnn_candidates: regression weights must be positive");
     OSR_REQUIRE((((uintptr_t)prop_boxes | (uintptr_t)c_boxes) & 15) == 0, OSR_ERR_INVALID_ARG, "osr_fastrcnn_candidates: box arrays must be 16-byte aligned");
-    hipLaunchKernelGGL(fastrcnn_cand_kernel, dim3(n), dim3(1024), 0, (hipStream_t)stream, logits, deltas, num_classes, num_bbox_reg_classes, prop_boxes,
-                       prop_count, seg_rows, image_hw, make_float4(reg_weights[0], reg_weights[1], reg_weights[2], reg_weights[3]), score_thresh, c_boxes,
-                       c_scores, c_cls, c_row, c_count);
+    CandLogits lg;
+    for (int s = 0; s < OSR_CASCADE_MAX_STAGES; ++s) lg.p[s] = logits;
+    cand_launch<1>(lg, deltas, num_classes, num_bbox_reg_classes, prop_boxes, prop_count, nullptr, n, seg_rows, image_hw, reg_weights, score_thresh,
+                   c_boxes, c_scores, c_cls, c_row, c_count, stream);
     OSR_CHECK_LAUNCH("osr_fastrcnn_candidates");
+    return OSR_OK;
+}
+
+extern "C" osr_status osr_cascade_candidates(const float* const* logits, int32_t num_stages, const float* deltas, int32_t num_classes,
+                                             const float* boxes, const int32_t* batch_idx, int32_t n, int32_t seg_rows, const int32_t* image_hw,
+                                             const float reg_weights[4], float score_thresh, float* c_boxes, float* c_scores, int32_t* c_cls,
+                                             int32_t* c_row, int32_t* c_count, void* stream) {
+    OSR_REQUIRE(logits && deltas && boxes && batch_idx && image_hw && reg_weights && c_boxes && c_scores && c_cls && c_row && c_count,
+                OSR_ERR_INVALID_ARG, "osr_cascade_candidates: null pointer");
+    OSR_REQUIRE(num_stages >= 1 && num_stages <= OSR_CASCADE_MAX_STAGES, OSR_ERR_INVALID_ARG, "osr_cascade_candidates: 1..%d stages", OSR_CASCADE_MAX_STAGES);
+    OSR_REQUIRE(n >= 1 && seg_rows >= 1 && num_classes >= 1 && num_classes <= CAND_MAX_CLASSES && (int64_t)n * seg_rows * num_classes < (1ll << 31),
+                OSR_ERR_INVALID_ARG, "osr_cascade_candidates: bad sizes (1..%d classes)", CAND_MAX_CLASSES);
+    OSR_REQUIRE(reg_weights[0] > 0.f && reg_weights[1] > 0.f && reg_weights[2] > 0.f && reg_weights[3] > 0.f, OSR_ERR_INVALID_ARG,
+                "osr_cascade_candidates: regression weights must be positive");
+    OSR_REQUIRE((((uintptr_t)boxes | (uintptr_t)deltas | (uintptr_t)c_boxes) & 15) == 0, OSR_ERR_INVALID_ARG,
+                "osr_cascade_candidates: box arrays must be 16-byte aligned");
+    CandLogits lg;
+    for (int s = 0; s < OSR_CASCADE_MAX_STAGES; ++s) {
+        lg.p[s] = s < num_stages ? logits[s] : logits[0];
+        OSR_REQUIRE(lg.p[s], OSR_ERR_INVALID_ARG, "osr_cascade_candidates: null logits of stage %d", s);
+    }
+#define CAND_LAUNCH(S_) \
+    cand_launch<S_>(lg, deltas, num_classes, 1, boxes, nullptr, batch_idx, n, seg_rows, image_hw, reg_weights, score_thresh, c_boxes, c_scores, c_cls, c_row, c_count, stream)
+    switch (num_stages) {
+        case 1: CAND_LAUNCH(1); break;
+        case 2: CAND_LAUNCH(2); break;
+        case 3: CAND_LAUNCH(3); break;
+        default: CAND_LAUNCH(4); break;
+    }
+#undef CAND_LAUNCH
+    OSR_CHECK_LAUNCH("osr_cascade_candidates");
     return OSR_OK;
 }
 

@@ -17,6 +17,7 @@
 // themselves instead of the list: one workgroup, exact, slow.
 // Compile with -ffp-contract=off: the decode rounds like rpn_select_kernel's decode_mode 1.
 #include "osr_common.h"
+#include "osr_boxes.h"
 #include "osr_select.h"
 
 #define RN_FILTER_THREADS 256
@@ -353,21 +354,12 @@ __global__ __launch_bounds__(SEL_THREADS) void rn_select_kernel(RnLevels lv, con
         const int t = idx / K, kc = idx - t * K;
         const int cell = t / A, a = t - cell * A;
         const float4 d = *reinterpret_cast<const float4*>(dl + (long long)cell * lv.pitch_box + a * 4);
-        const float sx = (float)(cell % W) * fstride, sy = (float)(cell / W) * fstride;
-        const float* ca = cell_anchors + ((long long)l * A + a) * 4;
-        const float ax1 = sx + ca[0], ay1 = sy + ca[1], ax2 = sx + ca[2], ay2 = sy + ca[3];
-        const float aw = ax2 - ax1, ah = ay2 - ay1;
         // [d2] Box2BoxTransform(weights).apply_deltas, as rpn_select_kernel's decode_mode 1
-        const float cx = ax1 + 0.5f * aw, cy = ay1 + 0.5f * ah;
-        const float kClamp = 4.135166556742356f;
-        const float dx = d.x / rw.x, dy = d.y / rw.y, dw = fminf(d.z / rw.z, kClamp), dh = fminf(d.w / rw.w, kClamp);
-        const float pcx = dx * aw + cx, pcy = dy * ah + cy, pw = expf(dw) * aw, ph = expf(dh) * ah;
-        const float x1 = pcx - 0.5f * pw, y1 = pcy - 0.5f * ph, x2 = pcx + 0.5f * pw, y2 = pcy + 0.5f * ph;
-        const bool dnan = (d.x != d.x) || (d.y != d.y) || (d.z != d.z) || (d.w != d.w);  // (fminf drops a NaN)
-        const bool dfin = osr_finite(d.x) && osr_finite(d.y) && osr_finite(d.z) && osr_finite(d.w);
-        const bool valid = osr_finite(x1) && osr_finite(y1) && osr_finite(x2) && osr_finite(y2) && dfin && !dnan;
+        bool valid;
+        const float4 b = osr_b2b_decode(osr_cell_anchor(cell_anchors, l, A, a, cell, W, fstride), d, rw, &valid);
+        valid = valid && osr_box_finite(d);  // dfin: an infinite size delta gives a finite box (the clamp, or exp(-Inf) = 0)
         bad |= !valid;
-        *reinterpret_cast<float4*>(c_boxes + o * 4) = valid ? make_float4(x1, y1, x2, y2) : make_float4(0.f, 0.f, 0.f, 0.f);
+        *reinterpret_cast<float4*>(c_boxes + o * 4) = valid ? b : make_float4(0.f, 0.f, 0.f, 0.f);
         c_scores[o] = 1.0f / (1.0f + expf(-z));
         c_cls[o] = kc;
         c_cand[o] = valid ? 1 : 0;

@@ -6,6 +6,7 @@
 //   find_top_rpn_proposals                         find_top_proposals.py:60-127
 // Compile with -ffp-contract=off: the decode/clip arithmetic must round exactly like the oracle's.
 #include "osr_common.h"
+#include "osr_boxes.h"
 #include "osr_select.h"
 
 // ------------------------------------------------------------------------------------------------------
@@ -241,35 +242,25 @@ __global__ __launch_bounds__(SEL_THREADS) void rpn_select_kernel(SelLevels lv, c
         const int idx = (int)(0xffffffffu - (unsigned int)(comp & 0xffffffffull));
         const float s = sc[idx];
         const float4 d = *reinterpret_cast<const float4*>(dl + (long long)idx * 4);
-        const int a = idx % A, cell = idx / A;
-        const float sx = (float)(cell % W) * fstride, sy = (float)(cell / W) * fstride;
-        const float* ca = cell_anchors + ((long long)l * A + a) * 4;
-        const float ax1 = sx + ca[0], ay1 = sy + ca[1], ax2 = sx + ca[2], ay2 = sy + ca[3];
-        const float aw = ax2 - ax1, ah = ay2 - ay1;
-        float x1, y1, x2, y2;
+        const float4 an = osr_cell_anchor(cell_anchors, l, A, idx % A, idx / A, W, fstride);
+        float4 b;
+        bool valid;
         if (decode_mode == 0) {
             // [d2] Box2BoxTransformLinear(normalize_by_size=True).apply_deltas (the CF-RPN, classification_free_rpn.py:607)
-            const float cx = 0.5f * (ax1 + ax2), cy = 0.5f * (ay1 + ay2);
-            const float dl_ = fmaxf(d.x, 0.f) * aw, dt_ = fmaxf(d.y, 0.f) * ah, dr_ = fmaxf(d.z, 0.f) * aw, db_ = fmaxf(d.w, 0.f) * ah;
-            x1 = cx - dl_; y1 = cy - dt_; x2 = cx + dr_; y2 = cy + db_;
+            const float aw = an.z - an.x, ah = an.w - an.y, cx = 0.5f * (an.x + an.z), cy = 0.5f * (an.y + an.w);
+            b = make_float4(cx - fmaxf(d.x, 0.f) * aw, cy - fmaxf(d.y, 0.f) * ah, cx + fmaxf(d.z, 0.f) * aw, cy + fmaxf(d.w, 0.f) * ah);
+            // relu(NaN) must stay NaN like torch's: fmaxf drops a NaN, so test the raw deltas too
+            valid = osr_box_finite(b) && !((d.x != d.x) || (d.y != d.y) || (d.z != d.z) || (d.w != d.w));
         } else {
-            // [d2] Box2BoxTransform(weights).apply_deltas (the stock RPN of Base-RCNN-FPN.yaml: weights 1,1,1,1): dw, dh clamped
-            // from above at log(1000/16)
-            const float cx = ax1 + 0.5f * aw, cy = ay1 + 0.5f * ah;
-            const float kClamp = 4.135166556742356f;
-            const float dx = d.x / rw.x, dy = d.y / rw.y, dw = fminf(d.z / rw.z, kClamp), dh = fminf(d.w / rw.w, kClamp);
-            const float pcx = dx * aw + cx, pcy = dy * ah + cy, pw = expf(dw) * aw, ph = expf(dh) * ah;
-            x1 = pcx - 0.5f * pw; y1 = pcy - 0.5f * ph; x2 = pcx + 0.5f * pw; y2 = pcy + 0.5f * ph;
+            // [d2] Box2BoxTransform(weights).apply_deltas (the stock RPN of Base-RCNN-FPN.yaml: weights 1,1,1,1)
+            b = osr_b2b_decode(an, d, rw, &valid);
         }
-        // relu(NaN) / clamp(NaN) must stay NaN like torch's: fmaxf / fminf drop NaN, so test the raw deltas too
-        const bool dnan = (d.x != d.x) || (d.y != d.y) || (d.z != d.z) || (d.w != d.w);
-        const bool valid = osr_finite(x1) && osr_finite(y1) && osr_finite(x2) && osr_finite(y2) && osr_finite(s) && !dnan;
+        valid = valid && osr_finite(s);
         bad |= !valid;
-        x1 = fminf(fmaxf(x1, 0.f), iw); y1 = fminf(fmaxf(y1, 0.f), ih);
-        x2 = fminf(fmaxf(x2, 0.f), iw); y2 = fminf(fmaxf(y2, 0.f), ih);
-        const bool keep = valid && (x2 - x1 > min_box_size) && (y2 - y1 > min_box_size);
+        b = osr_box_clip(b, iw, ih);
+        const bool keep = valid && (b.z - b.x > min_box_size) && (b.w - b.y > min_box_size);
         const long long o = (long long)img * lv.cap + lv.koff[l] + j;
-        *reinterpret_cast<float4*>(st_box + o * 4) = make_float4(x1, y1, x2, y2);
+        *reinterpret_cast<float4*>(st_box + o * 4) = b;
         st_score[o] = s;
         st_src[o] = lv.aoff[l] + idx;
         st_flag[o] = keep ? 1 : 0;

@@ -2,7 +2,7 @@
 S box stages, each with a box head and a class-agnostic FastRCNNOutputLayers of its own, each fed the previous stage's decoded boxes.
 Everything below the RoI heads -- backbone, FPN, the stock RPN -- and the mask head are StandardRCNNEngine's. A stage is the stock
 engine's own chain (osr_roi_align_fwd, FC1 / FC2 on the MFMA kernels, osr_gemm_f32 for cls_score / bbox_pred, osr_fastrcnn_losses_fwd
-in training); between two stages sits one osr_cascade_refine launch, behind the last one osr_cascade_candidates (csrc/osr_cascade.hip).
+in training); between two stages sits one osr_cascade_refine launch, behind the last one osr_cascade_candidates (csrc/osr_cascade.hip, csrc/osr_det_tail.hip).
 The row lists keep their fixed capacity from stage to stage: a row that stops existing gets batch_idx -1 and class -1, which RoIAlign
 and the loss kernels already skip."""
 from __future__ import annotations
@@ -12,7 +12,6 @@ from typing import Dict, Optional
 import torch
 
 from . import ops
-from .engine import PYRAMID
 from .engine_std import StandardRCNNEngine, check_std_supported, std_loss_beta
 from .weights import pack_fc1_weight
 
@@ -80,17 +79,9 @@ class CascadeRCNNEngine(StandardRCNNEngine):
             if self.cls_ws[s].shape[0] != k + 1 or self.box_ws[s].shape[0] != 4:
                 raise ValueError(f"cascade stage {s}: cls_score needs NUM_CLASSES + 1 rows and bbox_pred 4 (MODEL.ROI_BOX_HEAD.CLS_AGNOSTIC_BBOX_REG True)")
 
-    def _stage(self, s: int, feats, boxes, batch_idx):
-        """Stage s on its rows: RoIAlign, FC1, FC2, cls_score, bbox_pred. -> (pooled (m, P, P, 256), h1, box_feats, logits, deltas)."""
-        c = self.cfg
-        pooled = ops.roi_align([feats[k] for k in PYRAMID[:4]], c["pooler_scales"], boxes, batch_idx, c["pooler_resolution"], self.dtype,
-                               c["canonical_level"], c["canonical_size"], 2, aligned=c["pooler_aligned"], sampling_ratio=c["pooler_sampling_ratio"])
-        m = pooled.shape[0]
-        h1 = self._linear(pooled.view(m, -1), self.fc1_ws[s], self.fc1_bs[s], True, name=f"roi_heads.box_head.{s}.fc1")
-        box_feats = self._linear(h1, self.fc2_ws[s], self.fc2_bs[s], True, torch.float32, name=f"roi_heads.box_head.{s}.fc2")
-        logits = ops.gemm_f32(box_feats, self.cls_ws[s], self.cls_bs[s])
-        deltas = ops.gemm_f32(box_feats, self.box_ws[s], self.box_bs[s])
-        return pooled, h1, box_feats, logits, deltas
+    def _box_stage_params(self, s: int):
+        return (f"roi_heads.box_head.{s}", self.fc1_ws[s], self.fc1_bs[s], self.fc2_ws[s], self.fc2_bs[s], self.cls_ws[s], self.cls_bs[s],
+                self.box_ws[s], self.box_bs[s])
 
     # ---- [d2] CascadeROIHeads._forward_box (inference) --------------------------------------------------------------------------
     def _roi_heads(self, feats, sel, image_hw, keep=None, mask: bool = True):
@@ -102,7 +93,7 @@ class CascadeRCNNEngine(StandardRCNNEngine):
             if s > 0:  # the previous stage's boxes, decoded and clipped; every row stays, so the stages' scores stay aligned
                 ref = ops.cascade_refine(boxes, bidx, deltas, n, image_hw, self.stage_weights[s - 1])
                 boxes, bidx = ref["boxes"], ref["batch_idx"]
-            pooled, h1, box_feats, logits, deltas = self._stage(s, feats, boxes, bidx)
+            pooled, h1, box_feats, logits, deltas = self._box_stage(feats, boxes, bidx, s)
             all_logits.append(logits)
             if keep is not None:
                 keep.update({f"pooled_s{s}": pooled, f"logits_s{s}": logits, f"deltas_s{s}": deltas, f"boxes_s{s}": boxes, f"box_feats_s{s}": box_feats})
@@ -135,7 +126,7 @@ class CascadeRCNNEngine(StandardRCNNEngine):
                 ref = ops.cascade_refine(boxes, bidx, deltas, n, image_hw, self.stage_weights[s - 1], True, gt_boxes, gt_classes, gt_count, k,
                                          self.stage_ious[s])
                 boxes, bidx, cls, gtb, counts = ref["boxes"], ref["batch_idx"], ref["gt_classes"], ref["gt_boxes"], ref["counts"]
-            pooled, h1, box_feats, logits, deltas = self._stage(s, feats, boxes, bidx)
+            pooled, h1, box_feats, logits, deltas = self._box_stage(feats, boxes, bidx, s)
             st = ops.fastrcnn_losses_fwd(logits, deltas, boxes, gtb, cls, k, True, self.stage_weights[s], std_loss_beta(c, "roi_box"),
                                          c["std_cls_loss_weight"], c["box_reg_weight"])
             out[f"loss_cls_stage{s}"], out[f"loss_box_reg_stage{s}"] = st[0], st[1]

@@ -180,13 +180,8 @@ class RetinaNetEngine(StandardRCNNEngine):
         c = self.cfg
         topk, cap = c["std_detections_per_image"], cands["cap"]
         seg = torch.full((n,), cap, dtype=torch.int32, device=self.device)
-        dk, dcnt = self._hbm("nms_topk(retinanet, per class)", lambda: ops.nms_topk(cands["c_boxes"], cands["c_scores"], cands["c_cls"], cands["c_cand"], n, cap, seg,
-                                                                                     c["std_nms_thresh_test"], topk), n * cap * 28)
-        ob = ops.gather_rows(cands["c_boxes"].view(-1, 4), cap, dk, dcnt)
-        osc = ops.gather_rows(cands["c_scores"].view(-1), cap, dk, dcnt).view(n, topk)
-        # (class ids travel through the fp32 row gather as bit patterns: it only copies)
-        ocl = ops.gather_rows(cands["c_cls"].view(-1).view(torch.float32), cap, dk, dcnt).view(n, topk).view(torch.int32).to(torch.int64)
-        ocl = torch.where(torch.arange(topk, device=self.device)[None, :] < dcnt[:, None], ocl, torch.full_like(ocl, -1))
+        ob, osc, ocl, dcnt, dk = ops.nms_gather(cands["c_boxes"], cands["c_scores"], cands["c_cls"], cands["c_cand"], n, cap, seg, c["std_nms_thresh_test"], topk,
+                                                timed=lambda nms: self._hbm("nms_topk(retinanet, per class)", nms, n * cap * 28))
         if keep is not None:
             keep.update(cands=cands, det_keep=dk, det_count=dcnt)
         return ob, osc, ocl, dcnt

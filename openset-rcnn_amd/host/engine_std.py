@@ -112,17 +112,19 @@ class StandardRCNNEngine(OpensetRCNNEngine):
             raise ops.OsrError("this engine was built without a mask head (MODEL.MASK_ON False)")
         n, topk = boxes.shape[0], boxes.shape[1]
         res = c["mask_pooler_resolution"]
-        ar = torch.arange(topk, device=self.device, dtype=torch.int32)[None, :]
-        bidx = torch.where(ar < counts[:, None], torch.arange(n, device=self.device, dtype=torch.int32)[:, None],
-                           torch.full((1, 1), -1, device=self.device, dtype=torch.int32)).reshape(-1).contiguous()
-        x = ops.roi_align([feats[k] for k in PYRAMID[:4]], c["pooler_scales"], boxes.reshape(-1, 4).contiguous(), bidx, res, self.dtype,
-                          c["canonical_level"], c["canonical_size"], 2, aligned=c["mask_pooler_aligned"],
-                          sampling_ratio=c["mask_pooler_sampling_ratio"])
+        x = self.pool_mask_rois(feats, boxes.reshape(-1, 4).contiguous(), ops.padded_batch_idx(counts, topk))
         for i in range(self.mask_num_conv):
             x = self._conv(x, f"roi_heads.mask_head.mask_fcn{i + 1}", 1, 1, relu=True)
         probs = ops.mask_upsample_predict(x, self.mask_deconv_w, self.mask_deconv_b, self.mask_pred_w, self.mask_pred_b,
                                           classes.reshape(-1).contiguous(), counts, topk)
         return probs.view(n, topk, 2 * res, 2 * res)
+
+    def pool_mask_rois(self, feats, boxes, batch_idx):
+        """pool_rois with the mask pooler's three options (ROI_MASK_HEAD.POOLER_*) -> (m, R, R, 256)."""
+        c = self.cfg
+        return ops.roi_align([feats[k] for k in PYRAMID[:4]], c["pooler_scales"], boxes, batch_idx, c["mask_pooler_resolution"], self.dtype,
+                             c["canonical_level"], c["canonical_size"], 2, aligned=c["mask_pooler_aligned"],
+                             sampling_ratio=c["mask_pooler_sampling_ratio"])
 
     def _levels(self, shapes, n):
         key = (tuple(shapes), n)
@@ -157,9 +159,7 @@ class StandardRCNNEngine(OpensetRCNNEngine):
         pk, pcnt = ops.nms_topk(sel["boxes"], sel["scores"], sel["level"], None, n, sel["cap"], sel["counts"], c["rpn_nms_thresh"], post)
         boxes = ops.gather_rows(sel["boxes"].view(-1, 4), sel["cap"], pk, pcnt)
         scores = ops.gather_rows(sel["scores"].view(-1), sel["cap"], pk, pcnt).view(n, post)
-        ar = torch.arange(post, device=self.device, dtype=torch.int32)[None, :]
-        bidx = torch.where(ar < pcnt[:, None], torch.arange(n, device=self.device, dtype=torch.int32)[:, None], torch.full((1, 1), -1, device=self.device, dtype=torch.int32))
-        out = dict(boxes=boxes, scores=scores, counts=pcnt, batch_idx=bidx.reshape(-1).contiguous(), cap=post, pre=sel, keep_idx=pk,
+        out = dict(boxes=boxes, scores=scores, counts=pcnt, batch_idx=ops.padded_batch_idx(pcnt, post), cap=post, pre=sel, keep_idx=pk,
                    status_flags=sel["status_flags"], levels=self._levels(shapes, n), pred_logits=logits, pred_deltas=deltas)
         if keep is not None:
             keep.update(rpn_t=t_all, rpn_logits=logits, rpn_deltas=deltas, rpn_shapes=shapes, rpn_pre=sel, rpn_keep=pk)
@@ -177,34 +177,32 @@ class StandardRCNNEngine(OpensetRCNNEngine):
             keep.update(feats=feats, sel=sel)
         return self._roi_heads(feats, sel, image_hw, keep, mask=False)
 
+    def _box_stage_params(self, s: int):
+        """Box stage s: (its box head's parameter prefix, fc1_w, fc1_b, fc2_w, fc2_b, cls_w, cls_b, box_w, box_b). StandardROIHeads has one."""
+        return "roi_heads.box_head", self.fc1_w, self.fc1_b, self.fc2_w, self.fc2_b, self.cls_w, self.cls_b, self.box_w, self.box_b
+
+    def _box_stage(self, feats, boxes, batch_idx, s: int = 0):
+        """A box stage on its rows: RoIAlign, FC1, FC2, cls_score, bbox_pred. -> (pooled (m, P, P, 256), h1, box_feats, logits, deltas)."""
+        head, fc1_w, fc1_b, fc2_w, fc2_b, cls_w, cls_b, box_w, box_b = self._box_stage_params(s)
+        pooled = self.pool_rois(feats, boxes, batch_idx)
+        h1 = self._linear(pooled, fc1_w, fc1_b, True, name=head + ".fc1")
+        box_feats = self._linear(h1, fc2_w, fc2_b, True, torch.float32, name=head + ".fc2")
+        return self.pooled_bin_major(pooled), h1, box_feats, ops.gemm_f32(box_feats, cls_w, cls_b), ops.gemm_f32(box_feats, box_w, box_b)
+
     def _roi_heads(self, feats, sel, image_hw, keep=None, mask: bool = True):
         c = self.cfg
-        n, cap = sel["boxes"].shape[0], sel["cap"]
-        boxes = sel["boxes"].view(-1, 4)
-        pooled = ops.roi_align([feats[k] for k in PYRAMID[:4]], c["pooler_scales"], boxes, sel["batch_idx"], c["pooler_resolution"],
-                               self.dtype, c["canonical_level"], c["canonical_size"], 2, aligned=c["pooler_aligned"],
-                               sampling_ratio=c["pooler_sampling_ratio"])
-        m = pooled.shape[0]
-        h1 = self._linear(pooled.view(m, -1), self.fc1_w, self.fc1_b, True, name="roi_heads.box_head.fc1")
-        box_feats = self._linear(h1, self.fc2_w, self.fc2_b, True, torch.float32, name="roi_heads.box_head.fc2")
-        logits = ops.gemm_f32(box_feats, self.cls_w, self.cls_b)
-        deltas = ops.gemm_f32(box_feats, self.box_w, self.box_b)
-        k = c["std_num_classes"]
-        cands = ops.fastrcnn_candidates(logits, deltas, sel["boxes"], sel["counts"], image_hw, k, c["bbox_reg_weights"], c["score_thresh_test"])
+        pooled, h1, box_feats, logits, deltas = self._box_stage(feats, sel["boxes"].view(-1, 4), sel["batch_idx"])
+        cands = ops.fastrcnn_candidates(logits, deltas, sel["boxes"], sel["counts"], image_hw, c["std_num_classes"], c["bbox_reg_weights"],
+                                        c["score_thresh_test"])
         if keep is not None:
             keep.update(pooled=pooled, h1=h1, box_feats=box_feats, logits=logits, deltas=deltas)
-        return self._detections(feats, cands, n, keep, mask)
+        return self._detections(feats, cands, sel["boxes"].shape[0], keep, mask)
 
     def _detections(self, feats, cands, n, keep=None, mask: bool = True):
         """[d2] fast_rcnn_inference behind the candidates: per-class NMS, the best DETECTIONS_PER_IMAGE, then the mask head on them."""
         c = self.cfg
-        topk = c["std_detections_per_image"]
-        dk, dcnt = ops.nms_topk(cands["boxes"], cands["scores"], cands["cls"], None, n, cands["cap"], cands["count"], c["std_nms_thresh_test"], topk)
-        ob = ops.gather_rows(cands["boxes"].view(-1, 4), cands["cap"], dk, dcnt)
-        osc = ops.gather_rows(cands["scores"].view(-1), cands["cap"], dk, dcnt).view(n, topk)
-        # (class ids travel through the fp32 row gather as bit patterns: it only copies)
-        ocl = ops.gather_rows(cands["cls"].view(-1).view(torch.float32), cands["cap"], dk, dcnt).view(n, topk).view(torch.int32).to(torch.int64)
-        ocl = torch.where(torch.arange(topk, device=self.device)[None, :] < dcnt[:, None], ocl, torch.full_like(ocl, -1))
+        ob, osc, ocl, dcnt, dk = ops.nms_gather(cands["boxes"], cands["scores"], cands["cls"], None, n, cands["cap"], cands["count"],
+                                                c["std_nms_thresh_test"], c["std_detections_per_image"])
         if keep is not None:
             keep.update(cands=cands, det_keep=dk, det_count=dcnt)
         if self.has_mask and mask:  # (a fifth output only when the engine has a mask head: MASK_ON False returns what it always has)
@@ -254,12 +252,8 @@ class StandardRCNNEngine(OpensetRCNNEngine):
         cls = smp["gt_classes"][:, :f].reshape(-1).contiguous()
         gidx = smp["gt_idx"][:, :f].contiguous()
         rows_valid = smp["counts"][:, 1].contiguous()
-        ar = torch.arange(f, device=self.device, dtype=torch.int32)[None, :]
-        bidx = torch.where(ar < rows_valid[:, None], torch.arange(n, device=self.device, dtype=torch.int32)[:, None],
-                           torch.full((1, 1), -1, device=self.device, dtype=torch.int32)).reshape(-1).contiguous()
-        pooled = ops.roi_align([feats[k] for k in PYRAMID[:4]], c["pooler_scales"], boxes.view(-1, 4), bidx, res, self.dtype,
-                               c["canonical_level"], c["canonical_size"], 2, aligned=c["mask_pooler_aligned"],
-                               sampling_ratio=c["mask_pooler_sampling_ratio"])
+        bidx = ops.padded_batch_idx(rows_valid, f)
+        pooled = self.pool_mask_rois(feats, boxes.view(-1, 4), bidx)
         acts, x = [], pooled
         for i in range(self.mask_num_conv):
             x = self._conv(x, f"roi_heads.mask_head.mask_fcn{i + 1}", 1, 1, relu=True)
@@ -285,15 +279,11 @@ class StandardRCNNEngine(OpensetRCNNEngine):
         smp = ops.roi_match_and_sample(prop_boxes, prop_scores, prop_counts, gt_boxes, gt_classes, gt_count, keys_roi,
                                        k, c["roi_batch_size"], c["roi_positive_fraction"], c["roi_iou_threshold"])
         boxes = smp["boxes"].view(-1, 4)
-        pooled = self.pool_rois(feats, boxes, smp["batch_idx"])
-        h1 = self._linear(pooled, self.fc1_w, self.fc1_b, True, name="roi_heads.box_head.fc1")
-        box_feats = self._linear(h1, self.fc2_w, self.fc2_b, True, torch.float32, name="roi_heads.box_head.fc2")
-        logits = ops.gemm_f32(box_feats, self.cls_w, self.cls_b)
-        deltas = ops.gemm_f32(box_feats, self.box_w, self.box_b)
+        pooled, h1, box_feats, logits, deltas = self._box_stage(feats, boxes, smp["batch_idx"])
         cls = smp["gt_classes"].view(-1)
         st = ops.fastrcnn_losses_fwd(logits, deltas, boxes, smp["gt_boxes"].view(-1, 4), cls, k, self.box_w.shape[0] == 4, c["bbox_reg_weights"],
                                      std_loss_beta(c, "roi_box"), c["std_cls_loss_weight"], c["box_reg_weight"])
-        state = dict(smp=smp, boxes=boxes, pooled=self.pooled_bin_major(pooled), h1=h1, box_feats=box_feats, logits=logits, deltas=deltas, cls=cls)
+        state = dict(smp=smp, boxes=boxes, pooled=pooled, h1=h1, box_feats=box_feats, logits=logits, deltas=deltas, cls=cls)
         out = dict(loss_cls=st[0], loss_box_reg=st[1], roi_counts=smp["counts"], stats=st)
         if self.has_mask:
             mst, state["mask"] = self.mask_losses_forward(feats, smp, gt_masks, image_hw)

@@ -1014,7 +1014,7 @@ def cascade_candidates(logits: Sequence[torch.Tensor], deltas, boxes, batch_idx,
                        score_thresh: float = 0.05):
     """[d2] CascadeROIHeads._forward_box at inference up to the NMS (include/osr.h osr_cascade_candidates): logits[s] (n*rows, K+1)
     per stage, the last stage's deltas (n*rows, 4) and input boxes (n, rows, 4), batch_idx (n*rows) int32. The outputs of
-    fastrcnn_candidates; with one stage bit-identical to it."""
+    fastrcnn_candidates; with one stage it is the same kernel instantiation."""
     lib = _lib.load()
     logits = list(logits)
     if not 1 <= len(logits) <= CASCADE_MAX_STAGES:
@@ -1163,6 +1163,29 @@ def gather_rows(src, seg_stride: int, keep, keep_count) -> torch.Tensor:
     dst = torch.empty((nseg, topk, row), dtype=torch.float32, device=src.device)
     check(lib.osr_gather_rows(_p(src), seg_stride, row, _p(keep), _p(keep_count), nseg, topk, _p(dst), _stream()), "osr_gather_rows")
     return dst
+
+
+def padded_batch_idx(counts: torch.Tensor, width: int) -> torch.Tensor:
+    """batch_idx (n * width,) int32 of n padded lists of `width` slots: image i in its first counts[i] slots, -1 behind them."""
+    n, dev = counts.numel(), counts.device
+    ar = torch.arange(width, device=dev, dtype=torch.int32)[None, :]
+    return torch.where(ar < counts.view(n, 1), torch.arange(n, device=dev, dtype=torch.int32)[:, None],
+                       torch.full((1, 1), -1, device=dev, dtype=torch.int32)).reshape(-1).contiguous()
+
+
+def nms_gather(boxes, scores, cls, cand, n: int, cap: int, counts, thresh: float, topk: int, timed=None):
+    """The tail behind a candidate list ([d2] batched_nms by class + the best `topk`): one nms_topk over n segments of `cap` candidates
+    (boxes (n, cap, 4), scores, cls int32, cand int32 flags or None, counts (n,) int32), then the kept boxes, scores and classes
+    gathered into padded lists. -> (boxes (n, topk, 4), scores (n, topk), classes (n, topk) int64 with -1 behind the count, counts,
+    keep). timed: a callable that runs the NMS launch (an engine's profiling wrapper); None calls it directly."""
+    nms = lambda: nms_topk(boxes, scores, cls, cand, n, cap, counts, thresh, topk)  # noqa: E731
+    keep, cnt = timed(nms) if timed is not None else nms()
+    ob = gather_rows(boxes.view(-1, 4), cap, keep, cnt)
+    osc = gather_rows(scores.view(-1), cap, keep, cnt).view(n, topk)
+    # (class ids travel through the fp32 row gather as bit patterns: it only copies)
+    ocl = gather_rows(cls.view(-1).view(torch.float32), cap, keep, cnt).view(n, topk).view(torch.int32).to(torch.int64)
+    ocl = torch.where(torch.arange(topk, device=ocl.device)[None, :] < cnt[:, None], ocl, torch.full_like(ocl, -1))
+    return ob, osc, ocl, cnt, keep
 
 
 def l2_normalize_rows(x: torch.Tensor) -> torch.Tensor:

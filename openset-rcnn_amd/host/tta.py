@@ -110,13 +110,7 @@ class GeneralizedRCNNWithTTA(nn.Module):
             b, s, c, cnt = eng.forward_device(img, hw, *self._padded(eng, ha, wa), mask=False)
             ops.tta_boxes_to_original(b, s, c, cnt, sizes, ha, wa, fl, a * topk, c_boxes, c_scores, c_cls, c_cand)
         seg_len = torch.full((n,), cap, dtype=torch.int32, device=dev)
-        keep, cnt = ops.nms_topk(c_boxes, c_scores, c_cls, c_cand, n, cap, seg_len, self.nms_thresh, topk)
-        mb = ops.gather_rows(c_boxes.view(-1, 4), cap, keep, cnt)
-        ms = ops.gather_rows(c_scores.view(-1), cap, keep, cnt).view(n, topk)
-        # (class ids travel through the fp32 row gather as bit patterns: it only copies)
-        mc = ops.gather_rows(c_cls.view(-1).view(torch.float32), cap, keep, cnt).view(n, topk).view(torch.int32).to(torch.int64)
-        mc = torch.where(torch.arange(topk, device=dev)[None, :] < cnt[:, None], mc, torch.full_like(mc, -1))
-        return mb, ms, mc, cnt
+        return ops.nms_gather(c_boxes, c_scores, c_cls, c_cand, n, cap, seg_len, self.nms_thresh, topk)[:4]
 
     def mask_stage(self, eng, images: torch.Tensor, sizes: torch.Tensor, augs, mb, mc, cnt) -> torch.Tensor:
         """The mask branch on the merged boxes in every augmentation (its pyramid recomputed: the pass is deterministic), the mean of

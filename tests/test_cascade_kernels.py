@@ -1,5 +1,5 @@
-"""osr_cascade_refine and osr_cascade_candidates (csrc/osr_cascade.hip) against a torch fp32 restatement of detectron2's
-CascadeROIHeads written here: predict_boxes + _create_proposals_from_boxes + _match_and_label_boxes between two stages, and the
+"""osr_cascade_refine (csrc/osr_cascade.hip) and osr_cascade_candidates (csrc/osr_det_tail.hip) against a torch fp32 restatement
+of detectron2's CascadeROIHeads written here: predict_boxes + _create_proposals_from_boxes + _match_and_label_boxes between two stages, and the
 averaged scores + fast_rcnn_inference_single_image up to its NMS behind the last one.
 
 Integer outputs (classes, matched indices, batch_idx, counts) are compared bit-exactly, boxes under the project's 1e-4 fp32 contract
@@ -252,6 +252,9 @@ def _cand_case(stages, n=2, rows=1100, k=7, seed=3):
 
 @pytest.mark.gpu
 def test_cascade_candidates_one_stage_is_fastrcnn_candidates(osr):
+    """Both entry points launch one kernel template (cand_kernel<1>), so this compares a kernel with itself: what it still checks is
+    that a row list given by batch_idx selects the rows its prefix counts select. What the two separate kernels computed before they
+    were merged is held by tests/test_det_tail_pin.py."""
     from openset_rcnn_amd.host import ops
     logits, deltas, boxes, counts, bidx, hw, k = _cand_case(1)
     dev = lambda t: t.to(DEV)  # noqa: E731

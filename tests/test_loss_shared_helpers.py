@@ -1,5 +1,5 @@
-"""The building blocks the loss kernels share (csrc/osr_loss_common.h, the Box2BoxTransform pair of csrc/osr_box_loss.h, the mask
-head's row rule of csrc/osr_mask_mfma.h) through every entry point that is built from them, at the smallest shapes at which they can
+"""The building blocks the loss kernels share (csrc/osr_loss_common.h, the Box2BoxTransform pair of csrc/osr_box_loss.h and
+csrc/osr_boxes.h, the mask head's row rule of csrc/osr_mask_mfma.h) through every entry point that is built from them, at the smallest shapes at which they can
 go wrong: less than a wave of rows, a ragged second wave group, one row in a second grid-stride turn, no counted row at all, two
 pyramid levels with A = 1 and A = 3, a mask batch whose segments end early.
 
