@@ -946,7 +946,7 @@ osr_status osr_conv2d_dgrad_s2(const osr_conv_params* p, const void* dy, const v
 
 /* ---------------------------------------------------------------------------------------------------------
  * Training step, backward half: losses and per-row stages. Every gradient is d(sum of weighted losses)/d(tensor)
- * times `loss_scale` (static loss scaling for fp16 gradient tensors; osr_sgd_step divides it out via grad_scale).
+ * times `loss_scale` (static loss scaling for fp16 gradient tensors; osr_sgd_step_multi_ex divides it out via grad_scale).
  * --------------------------------------------------------------------------------------------------------- */
 
 /* Gradient of osr_rpn_losses_fwd w.r.t. the head's five pre-activation outputs per anchor: d_out5 (rows, 5) level-major
@@ -1116,36 +1116,16 @@ osr_status osr_add_cast(const float* a_f32, const void* b, void* out, int32_t dt
 osr_status osr_pool_bwd(const void* src, int32_t hs, int32_t ws, const void* base, void* out, int32_t n, int32_t ho,
                         int32_t wo, int32_t c, int32_t mode, int32_t dtype, void* stream);
 
-/* SGD with momentum and weight decay ([d2] build_optimizer -> torch.optim.SGD): g' = grad*grad_scale*row_scale + wd*param;
- * buf = momentum*buf + g'; param -= lr*buf; lowp_copy (nullable) = (T)(param*row_scale). row_scale (nullable): folded
- * FrozenBN scale per leading-dimension row of row_elems elements. apply_flag (nullable, device int32): when it reads 0 the
- * launch changes nothing (the overflow guard of the fp16 step, see osr_check_finite). */
-osr_status osr_sgd_step(float* param, const float* grad, float* momentum_buf, int64_t n, float lr, float momentum,
-                        float weight_decay, float grad_scale, const float* row_scale, int64_t row_elems, void* lowp_copy,
-                        int32_t lowp_dtype, const int32_t* apply_flag, void* stream);
-
 /* Backward-data weight of a convolution, (cout,kh,kw,cin) -> (cin,kh,kw,cout) spatially flipped (the forward MFMA kernel run on
  * it with padding k-1-pad is the data gradient; a 1x1 layer / FC matrix is transposed). Run once per SGD step on the refreshed
  * working copies. dtype: element type of both tensors (f16/bf16/f32). out must not alias weight. */
 osr_status osr_pack_dgrad_weight(const void* weight, void* out, int32_t cout, int32_t kh, int32_t kw, int32_t cin,
                                  int32_t dtype, void* stream);
 
-/* The update of a whole training step as two launches (csrc/osr_multi_tensor.hip): osr_sgd_step over every entry of a DEVICE-resident
- * table, and osr_pack_dgrad_weight over every entry of another. `chunks`: (tensor index, chunk index) int32 pairs, one per workgroup,
- * on the device: for the SGD launch chunk c of tensor t is the elements [c * chunk_elems, min((c + 1) * chunk_elems, n)); for the packing
- * launch it is the linear index of a 32 x 32 tile, (tap * ceil(cout / 32) + co_tile) * ceil(cin / 32) + ci_tile. The caller builds both
- * once (the buffers' addresses are stable across steps). Same arithmetic per element as the single-tensor entry points: bit-identical. */
-typedef struct osr_sgd_tensor {
-    float* param;
-    const float* grad;
-    float* momentum;
-    const float* row_scale; /* nullable */
-    void* lowp;             /* nullable: low-precision working copy, lowp_dtype */
-    int64_t n;
-    int64_t row_elems;      /* >= 1 */
-    int32_t lowp_dtype;
-    int32_t reserved;
-} osr_sgd_tensor;
+/* osr_pack_dgrad_weight over every entry of a DEVICE-resident table, one launch (csrc/osr_pack_dgrad.hip; the same tile body).
+ * `chunks`: (tensor index, tile index) int32 pairs, one per workgroup, on the device; the tile index of a 32 x 32 tile is
+ * (tap * ceil(cout / 32) + co_tile) * ceil(cin / 32) + ci_tile. The caller builds both once (the buffers' addresses are stable
+ * across steps). */
 typedef struct osr_pack_tensor {
     const void* src;        /* (cout, kh, kw, cin) */
     void* dst;              /* (cin, kh, kw, cout), spatially flipped */
@@ -1153,22 +1133,24 @@ typedef struct osr_pack_tensor {
     int32_t elem_bytes;     /* 2 or 4 */
     int32_t reserved;
 } osr_pack_tensor;
-osr_status osr_sgd_step_multi(const osr_sgd_tensor* table, const int32_t* chunks, int32_t num_chunks, int32_t chunk_elems,
-                              float lr, float momentum, float weight_decay, float grad_scale, const int32_t* apply_flag,
-                              void* stream);
 osr_status osr_pack_dgrad_weight_multi(const osr_pack_tensor* table, const int32_t* chunks, int32_t num_chunks, void* stream);
 
-/* The solver options of [d2] build_optimizer beyond one SGD group (csrc/osr_solver.hip): per-parameter gradient clipping
- * (SOLVER.CLIP_GRADIENTS, CLIP_TYPE "value" / "norm"), a learning-rate factor and weight decay per parameter group
- * (BIAS_LR_FACTOR, WEIGHT_DECAY_BIAS) and Nesterov momentum. The table entries are SEGMENTS: one parameter each, a row-aligned
- * element range of a master (param / grad / momentum / row_scale / lowp already offset to its first row). `chunks` as for
- * osr_sgd_step_multi; the chunks of a segment are the contiguous run [chunk0, chunk0 + nchunks) of the list.
+/* The SGD of a training step ([d2] build_optimizer -> torch.optim.SGD, csrc/osr_solver.hip): momentum and weight decay on the fp32
+ * masters, with the solver options beyond one SGD group -- per-parameter gradient clipping (SOLVER.CLIP_GRADIENTS, CLIP_TYPE
+ * "value" / "norm"), a learning-rate factor and weight decay per parameter group (BIAS_LR_FACTOR, WEIGHT_DECAY_BIAS) and Nesterov
+ * momentum. The whole update is ONE launch, osr_sgd_step_multi_ex, over a DEVICE-resident table the caller builds once; norm
+ * clipping puts the norm pass, osr_grad_norm_partials, in front of it. The table entries are SEGMENTS: one parameter each, a
+ * row-aligned element range of a master (param / grad / momentum / row_scale / lowp already offset to its first row).
+ * `chunks`: (segment index, chunk index) int32 pairs, one per workgroup, on the device; chunk c of a segment is its elements
+ * [c * chunk_elems, min((c + 1) * chunk_elems, n)), and the chunks of a segment are the contiguous run [chunk0, chunk0 + nchunks)
+ * of the list. row_scale (nullable): the folded FrozenBN scale per leading-dimension row of row_elems elements.
  * Per element, with d = grad*grad_scale*row_scale:
  *   clip_mode VALUE: d = clamp(d, -clip_value, clip_value); NORM: d *= c when c = clip_value / (||d||_norm_type + 1e-6) < 1,
  *   the norm over the segment's elements (inf: max |d|);
  *   d += weight_decay*param; buf = momentum*buf + d; d = nesterov ? d + momentum*buf : buf; param -= lr*lr_factor*d;
  *   lowp (nullable) = (T)(param*row_scale).
- * With clip_mode NONE, lr_factor 1, nesterov 0 the arithmetic is osr_sgd_step_multi's (same bits). */
+ * Every product and sum is rounded to fp32 on its own (no fused multiply-add): with clip_mode NONE, lr_factor 1, nesterov 0 this
+ * is torch.optim.SGD's plain step, and how the table is cut into segments and chunks does not change a bit of the result. */
 typedef enum { OSR_CLIP_NONE = 0, OSR_CLIP_VALUE = 1, OSR_CLIP_NORM = 2 } osr_clip_mode;
 typedef struct osr_sgd_segment {
     float* param;

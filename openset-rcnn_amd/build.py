@@ -41,8 +41,8 @@ SOURCES = {
     "osr_train_fwd.hip": ["-ffp-contract=off"],
     "osr_rpn_sparse.hip": ["-ffp-contract=off"],
     "osr_std_train.hip": ["-ffp-contract=off"],
-    "osr_multi_tensor.hip": [],  # (same contraction setting as osr_train_bwd.hip: the multi-tensor SGD must round like osr_sgd_step)
-    "osr_solver.hip": [],
+    "osr_pack_dgrad.hip": [],
+    "osr_solver.hip": [],  # (the SGD element switches contraction off itself)
     "osr_conv_bwd.hip": [],
     "osr_conv_dgrad_s2.hip": [],
     "osr_stem_bwd.hip": [],

@@ -1,11 +1,16 @@
-// The solver options of [d2] build_optimizer beyond one SGD group: per-parameter gradient clipping (maybe_add_gradient_clipping,
-// CLIP_TYPE "value" / "norm"), per-group learning-rate factor and weight decay (BIAS_LR_FACTOR, WEIGHT_DECAY_BIAS) and Nesterov
-// momentum, as two launches over the flat fp32 gradient of a training step:
+// The SGD of a training step ([d2] build_optimizer -> torch.optim.SGD.step over every parameter), the library's only one: momentum
+// and weight decay on the fp32 masters, the low-precision working copy written in the same pass, and the solver options beyond one
+// SGD group -- per-parameter gradient clipping (maybe_add_gradient_clipping, CLIP_TYPE "value" / "norm"), per-group learning-rate
+// factor and weight decay (BIAS_LR_FACTOR, WEIGHT_DECAY_BIAS), Nesterov momentum. One launch over the flat fp32 gradient, a second
+// in front of it when norm clipping is on:
 //   osr_grad_norm_partials  one read of the gradient: per chunk, sum |g*gs*rs|^p (or max |.| for p = inf) into partials[chunk],
 //                           and the overflow flag cleared where a gradient is inf / NaN (it replaces osr_check_finite there)
-//   osr_sgd_step_multi_ex   the multi-tensor SGD over SEGMENTS (one parameter each: a row range of a master): every workgroup first
-//                           sums its parameter's partials in a fixed order, then clips g*gs*rs, adds weight decay and applies
+//   osr_sgd_step_multi_ex   the multi-tensor SGD over SEGMENTS (one parameter each: a row range of a master), a table and a chunk
+//                           list the caller builds once and keeps on the device: with norm clipping every workgroup first sums
+//                           its parameter's partials in a fixed order; then it clips g*gs*rs, adds weight decay and applies
 //                           (Nesterov) momentum
+// row_scale (nullable, one value per leading-dimension row) is the folded FrozenBN scale of a conv: the master weight is the un-folded
+// one, the kernels read w * scale, and the chain rule multiplies the gradient by it.
 // No atomics: the partials and their sums are in a fixed order, so repeated steps give identical bits.
 #include <cmath>
 
@@ -61,7 +66,7 @@ __global__ __launch_bounds__(256) void norm_partials_kernel(const osr_sgd_segmen
             rc.advance(blockDim.x);
         }
         bad |= !osr_finite(x);
-        const float a = fabsf(x * gs * rs);  // (the product osr_sgd_element forms, in its order)
+        const float a = fabsf(x * gs * rs);  // (the product sgd_element forms, in its order)
         if (KIND == NORM_L1) acc += (double)a;
         else if (KIND == NORM_L2) acc += (double)a * (double)a;
         else if (KIND == NORM_INF) acc = fmax(acc, (double)a);
@@ -84,7 +89,9 @@ __device__ float segment_clip_coef(const osr_sgd_segment& s, const double* __res
     return c < 1.0f ? c : 1.0f;
 }
 
-__device__ __forceinline__ void sgd_element_ex(float& p, float& v, float g, float rs, float lr, float mu, float wd, float gs, int clip_mode, float cv,
+// One element of the update. Contraction into fused multiply-adds is off: every product and sum rounds on its own, as the recorded
+// results of tests/golden/update_pin_v1.npz do, whatever the compiler would make of the surrounding loop.
+__device__ __forceinline__ void sgd_element(float& p, float& v, float g, float rs, float lr, float mu, float wd, float gs, int clip_mode, float cv,
                                                float coef, bool nesterov) {
 #pragma clang fp contract(off)
     float d = g * gs * rs;
@@ -115,7 +122,7 @@ __device__ __forceinline__ void sgd_ex_run(const osr_sgd_segment& s, long long i
             rc.advance(blockDim.x);
         }
         float pi = p[i], vi = v[i];
-        sgd_element_ex(pi, vi, g[i], rs, lr_s, mu, wd, gs, clip_mode, cv, coef, nesterov);
+        sgd_element(pi, vi, g[i], rs, lr_s, mu, wd, gs, clip_mode, cv, coef, nesterov);
         v[i] = vi;
         p[i] = pi;
         if (lp) lp[i] = osr_from_float<T>(pi * rs);

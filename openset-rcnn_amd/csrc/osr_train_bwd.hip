@@ -761,50 +761,9 @@ extern "C" osr_status osr_pool_bwd(const void* src, int32_t hs, int32_t ws, cons
 }
 
 // ------------------------------------------------------------------------------------------------------
-// SGD with momentum and weight decay ([d2] build_optimizer -> torch.optim.SGD): g' = g * grad_scale * row_scale + wd * p;
-// v = mu * v + g';  p -= lr * v;  then the low-precision working copy lp = (T)(p * row_scale) in the same layout.
-// row_scale (nullable, one value per leading-dimension row of row_elems elements) is the folded FrozenBN scale of a conv:
-// the master weight is the un-folded one, the kernels read w * scale, and the chain rule multiplies the gradient by it.
-// ------------------------------------------------------------------------------------------------------
-template <class T>
-__global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ v, long long n, float lr, float mu,
-                                                  float wd, float grad_scale, const float* __restrict__ row_scale, long long row_elems, T* __restrict__ lp,
-                                                  const int* __restrict__ gate) {
-    if (gate && *gate == 0) return;  // this iteration's gradients held an inf / NaN (osr_check_finite): leave parameters and momentum alone
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-        const float rs = row_scale ? row_scale[i / row_elems] : 1.0f;
-        float pi = p[i], vi = v[i];
-        osr_sgd_element(pi, vi, g[i], rs, lr, mu, wd, grad_scale);
-        v[i] = vi;
-        p[i] = pi;
-        if (lp) lp[i] = osr_from_float<T>(pi * rs);
-    }
-}
-
-extern "C" osr_status osr_sgd_step(float* param, const float* grad, float* momentum_buf, int64_t n, float lr, float momentum, float weight_decay,
-                                   float grad_scale, const float* row_scale, int64_t row_elems, void* lowp_copy, int32_t lowp_dtype, const int32_t* apply_flag,
-                                   void* stream) {
-    OSR_REQUIRE(param && grad && momentum_buf && n >= 0, OSR_ERR_INVALID_ARG, "osr_sgd_step: null pointer / bad n");
-    OSR_REQUIRE(!row_scale || row_elems >= 1, OSR_ERR_INVALID_ARG, "osr_sgd_step: row_elems must be >= 1 with a row scale");
-    OSR_REQUIRE(!lowp_copy || osr_dtype_ok(lowp_dtype), OSR_ERR_INVALID_ARG, "osr_sgd_step: bad low-precision dtype");
-    if (n == 0) return OSR_OK;
-    hipStream_t st = (hipStream_t)stream;
-    const dim3 grid((unsigned)((n + 255) / 256 < 8192 ? (n + 255) / 256 : 8192));
-    const long long re = row_scale ? row_elems : 1;
-    if (!lowp_copy || lowp_dtype == OSR_F32)
-        hipLaunchKernelGGL(sgd_kernel<float>, grid, dim3(256), 0, st, param, grad, momentum_buf, (long long)n, lr, momentum, weight_decay, grad_scale, row_scale, re, (float*)lowp_copy, apply_flag);
-    else if (lowp_dtype == OSR_F16)
-        hipLaunchKernelGGL(sgd_kernel<f16_t>, grid, dim3(256), 0, st, param, grad, momentum_buf, (long long)n, lr, momentum, weight_decay, grad_scale, row_scale, re, (f16_t*)lowp_copy, apply_flag);
-    else
-        hipLaunchKernelGGL(sgd_kernel<bf16_t>, grid, dim3(256), 0, st, param, grad, momentum_buf, (long long)n, lr, momentum, weight_decay, grad_scale, row_scale, re, (bf16_t*)lowp_copy, apply_flag);
-    OSR_CHECK_LAUNCH("osr_sgd_step");
-    return OSR_OK;
-}
-
-// ------------------------------------------------------------------------------------------------------
 // Overflow guard of the fp16 training step (static / dynamic loss scaling): *flag is cleared when any x[i] is inf or NaN.
 // The caller presets *flag = 1 once per iteration, runs this over the (all-reduced) flat gradient buffer and hands the flag to
-// every osr_sgd_step launch of the iteration, which then leave parameters and momentum untouched -- no host sync in between.
+// the update launch of the iteration (osr_sgd_step_multi_ex), which then leaves parameters and momentum untouched -- no host sync in between.
 // ------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void check_finite_kernel(const float* __restrict__ x, long long n, int* __restrict__ flag) {
     bool bad = false;
@@ -829,39 +788,3 @@ extern "C" osr_status osr_check_finite(const float* x, int64_t n, int32_t* flag,
     return OSR_OK;
 }
 
-
-// ------------------------------------------------------------------------------------------------------
-// Backward-data weight of a convolution from its forward weight, once per SGD step (instead of flip + permute + copy kernels of
-// the tensor library every iteration): dst[ci][kh-1-y][kw-1-x][co] = src[co][y][x][ci]. For 1x1 layers and FC matrices this is
-// the plain transpose. 32 x 32 tiles through LDS, both sides coalesced; 2- or 4-byte elements.
-// ------------------------------------------------------------------------------------------------------
-template <class T>
-__global__ __launch_bounds__(256) void pack_dgrad_kernel(const T* __restrict__ src, T* __restrict__ dst, int cout, int kh, int kw, int cin) {
-    __shared__ T tile[32][33];
-    const int tap = blockIdx.z, y = tap / kw, x = tap % kw;
-    const int ci0 = blockIdx.x * 32, co0 = blockIdx.y * 32;
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;  // 32 x 8
-    const long long taps = (long long)kh * kw;
-    for (int r = ty; r < 32; r += 8) {
-        const int co = co0 + r, ci = ci0 + tx;
-        if (co < cout && ci < cin) tile[r][tx] = src[((long long)co * taps + tap) * cin + ci];
-    }
-    __syncthreads();
-    const int ftap = (kh - 1 - y) * kw + (kw - 1 - x);
-    for (int r = ty; r < 32; r += 8) {
-        const int ci = ci0 + r, co = co0 + tx;
-        if (ci < cin && co < cout) dst[((long long)ci * taps + ftap) * cout + co] = tile[tx][r];
-    }
-}
-
-extern "C" osr_status osr_pack_dgrad_weight(const void* weight, void* out, int32_t cout, int32_t kh, int32_t kw, int32_t cin, int32_t dtype, void* stream) {
-    OSR_REQUIRE(weight && out && weight != out, OSR_ERR_INVALID_ARG, "osr_pack_dgrad_weight: null or aliased pointers");
-    OSR_REQUIRE(cout >= 1 && cin >= 1 && kh >= 1 && kw >= 1 && kh * kw <= 65535 && osr_dtype_ok(dtype), OSR_ERR_INVALID_ARG, "osr_pack_dgrad_weight: bad sizes / dtype");
-    const dim3 grid((cin + 31) / 32, (cout + 31) / 32, kh * kw);
-    OSR_REQUIRE(grid.y <= 65535, OSR_ERR_UNSUPPORTED, "osr_pack_dgrad_weight: cout too large");
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == OSR_F32) hipLaunchKernelGGL(pack_dgrad_kernel<float>, grid, dim3(256), 0, st, (const float*)weight, (float*)out, cout, kh, kw, cin);
-    else hipLaunchKernelGGL(pack_dgrad_kernel<unsigned short>, grid, dim3(256), 0, st, (const unsigned short*)weight, (unsigned short*)out, cout, kh, kw, cin);
-    OSR_CHECK_LAUNCH("osr_pack_dgrad_weight");
-    return OSR_OK;
-}

@@ -74,11 +74,6 @@ class RpnLevels(C.Structure):
     ]
 
 
-class SgdTensor(C.Structure):
-    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("momentum", C.c_void_p), ("row_scale", C.c_void_p), ("lowp", C.c_void_p),
-                ("n", C.c_int64), ("row_elems", C.c_int64), ("lowp_dtype", C.c_int32), ("reserved", C.c_int32)]
-
-
 class SgdSegment(C.Structure):
     """include/osr.h osr_sgd_segment: one parameter (a row range of a master) of osr_sgd_step_multi_ex / osr_grad_norm_partials."""
     _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("momentum", C.c_void_p), ("row_scale", C.c_void_p), ("lowp", C.c_void_p),
@@ -237,10 +232,8 @@ PROTOTYPES = {
     "osr_relu_mask": (I32, [P, I32, P, I32, I64, P]),
     "osr_add_cast": (I32, [P, P, P, I32, I64, P]),
     "osr_pool_bwd": (I32, [P, I32, I32, P, P, I32, I32, I32, I32, I32, I32, P]),
-    "osr_sgd_step": (I32, [P, P, P, I64, F32, F32, F32, F32, P, I64, P, I32, P, P]),
     "osr_check_finite": (I32, [P, I64, P, P]),
     "osr_pack_dgrad_weight": (I32, [P, P, I32, I32, I32, I32, I32, P]),
-    "osr_sgd_step_multi": (I32, [P, P, I32, I32, F32, F32, F32, F32, P, P]),
     "osr_pack_dgrad_weight_multi": (I32, [P, P, I32, P]),
     "osr_grad_norm_partials": (I32, [P, P, I32, I32, F32, F32, P, P, P]),
     "osr_sgd_step_multi_ex": (I32, [P, P, I32, I32, F32, F32, F32, I32, F32, F32, P, P, P]),

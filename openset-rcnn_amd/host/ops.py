@@ -2016,7 +2016,7 @@ def pack_dgrad_weight(w: torch.Tensor, out: Optional[torch.Tensor] = None) -> to
 
 
 class MultiTensorPlan:
-    """Device-resident table + chunk list of a multi-tensor launch (osr_sgd_step_multi / osr_pack_dgrad_weight_multi). `keep` holds the
+    """Device-resident table + chunk list of a multi-tensor launch (osr_sgd_step_multi_ex / osr_pack_dgrad_weight_multi). `keep` holds the
     tensors the table points at: the plan is only valid while they live at the same addresses."""
 
     def __init__(self, table: torch.Tensor, chunks: torch.Tensor, num_chunks: int, keep, chunk_elems: int = 0):
@@ -2029,41 +2029,6 @@ def _upload_struct_array(arr, device) -> torch.Tensor:
 
 
 SGD_CHUNK_ELEMS = 16384
-
-
-def sgd_multi_plan(entries, device) -> MultiTensorPlan:
-    """entries: [(param, grad, momentum_buf, row_scale | None, lowp | None)], fp32 param / grad / buf of equal size."""
-    tab = (_lib.SgdTensor * len(entries))()
-    chunks: List[int] = []
-    keep = []
-    for ti, (pm, gr, buf, rs, lp) in enumerate(entries):
-        _need(pm, torch.float32, "param"); _need(gr, torch.float32, "grad"); _need(buf, torch.float32, "buf")
-        if gr.numel() != pm.numel() or buf.numel() != pm.numel() or (lp is not None and lp.numel() != pm.numel()):
-            raise OsrError("sgd_multi_plan: size mismatch")
-        if rs is not None:
-            _need(rs, torch.float32, "row_scale")
-        if lp is not None:
-            _need(lp, name="lowp")
-        t = tab[ti]
-        t.param, t.grad, t.momentum = pm.data_ptr(), gr.data_ptr(), buf.data_ptr()
-        t.row_scale = rs.data_ptr() if rs is not None else None
-        t.lowp = lp.data_ptr() if lp is not None else None
-        t.n = pm.numel()
-        t.row_elems = pm.numel() // pm.shape[0] if rs is not None else 1
-        t.lowp_dtype = _DT[lp.dtype] if lp is not None else 0
-        for c in range((pm.numel() + SGD_CHUNK_ELEMS - 1) // SGD_CHUNK_ELEMS):
-            chunks += [ti, c]
-        keep += [pm, gr, buf, rs, lp]
-    ch = torch.tensor(chunks, dtype=torch.int32).to(device)
-    return MultiTensorPlan(_upload_struct_array(tab, device), ch, len(chunks) // 2, keep, SGD_CHUNK_ELEMS)
-
-
-def sgd_step_multi_(plan: MultiTensorPlan, lr: float, momentum: float, weight_decay: float, grad_scale: float = 1.0,
-                    apply_flag: Optional[torch.Tensor] = None) -> None:
-    """osr_sgd_step on every tensor of the plan, one launch."""
-    lib = _lib.load()
-    check(lib.osr_sgd_step_multi(_p(plan.table), _p(plan.chunks), plan.num_chunks, plan.chunk_elems, lr, momentum, weight_decay, grad_scale,
-                                 _p(apply_flag), _stream()), "osr_sgd_step_multi")
 
 
 CLIP_MODES = {None: _lib.OSR_CLIP_NONE, "value": _lib.OSR_CLIP_VALUE, "norm": _lib.OSR_CLIP_NORM}
@@ -2179,13 +2144,9 @@ def check_finite_(x: torch.Tensor, flag: torch.Tensor) -> torch.Tensor:
 
 def sgd_step_(param, grad, buf, lr: float, momentum: float, weight_decay: float, grad_scale: float = 1.0, row_scale=None, lowp=None,
               apply_flag: Optional[torch.Tensor] = None):
-    lib = _lib.load()
-    _need(param, torch.float32, "param"); _need(grad, torch.float32, "grad"); _need(buf, torch.float32, "buf")
-    if grad.numel() != param.numel() or buf.numel() != param.numel():
-        raise OsrError("sgd_step_: size mismatch")
-    row_elems = param.numel() // param.shape[0] if row_scale is not None else 1
-    check(lib.osr_sgd_step(_p(param), _p(grad), _p(buf), param.numel(), lr, momentum, weight_decay, grad_scale, _p(row_scale), row_elems,
-                           _p(lowp), _DT[lowp.dtype] if lowp is not None else 0, _p(apply_flag), _stream()), "osr_sgd_step")
+    """Plain SGD on one tensor: a one-segment plan through sgd_step_multi_ex_ (a convenience: a training step builds its plan once)."""
+    plan = sgd_segment_plan([(param, grad, buf, row_scale, lowp, 0, param.shape[0], 1.0, weight_decay, False)], param.device)
+    sgd_step_multi_ex_(plan, lr, momentum, grad_scale, apply_flag=apply_flag)
 
 
 # ----------------------------------------------------------------------------------------------------------

@@ -7,29 +7,20 @@ and `build_lr_scheduler(cfg, optimizer)`, so that the loop body of train.py:135-
 
 `losses.backward()` runs the explicit HIP backward into the trainer's flat fp32 gradient buffer (modeling._ExplicitBackward);
 `optimizer.step()` sums that buffer over the ranks (RCCL, bucketed, overlapped with the tail of the backward when several ranks
-run) and applies SGD with momentum and weight decay on the fp32 masters (osr_sgd_step), gated by the overflow guard. The
-[d2] options beyond one plain SGD group -- SOLVER.CLIP_GRADIENTS (per parameter), BIAS_LR_FACTOR / WEIGHT_DECAY_BIAS (a bias
-group) and NESTEROV -- run through osr_grad_norm_partials / osr_sgd_step_multi_ex (csrc/osr_solver.hip); with none of them on
-the update is the plain launch, bit for bit."""
+run) and applies SGD with momentum and weight decay on the fp32 masters, gated by the overflow guard: one launch over every
+parameter, osr_sgd_step_multi_ex (csrc/osr_solver.hip). The [d2] options beyond one plain SGD group -- SOLVER.CLIP_GRADIENTS (per
+parameter), BIAS_LR_FACTOR / WEIGHT_DECAY_BIAS (a bias group) and NESTEROV -- are arguments of that launch and entries of its
+table (norm clipping adds the norm pass, osr_grad_norm_partials, in front of it); with none of them on it is torch.optim.SGD's
+plain step, through the same kernel."""
 from __future__ import annotations
 
 import bisect
 import math
-from typing import Callable, List, NamedTuple, Optional
+from typing import Callable, List, Optional
 
-from .train import warmup_multistep_lr
+from .train import SolverOptions, warmup_multistep_lr
 
 CLIP_TYPES = ("value", "norm")
-
-
-class SolverOptions(NamedTuple):
-    """What the trainer's update needs beyond group 0's lr / momentum / weight decay (OpensetRCNNTrainer.solver_options)."""
-    bias_lr_factor: float = 1.0          # bias group lr / base group lr
-    weight_decay_bias: Optional[float] = None  # None: the bias parameters are in the base group
-    nesterov: bool = False
-    clip: Optional[str] = None           # None, "value" or "norm" ([d2] maybe_add_gradient_clipping, per parameter)
-    clip_value: float = 1.0
-    norm_type: float = 2.0
 
 
 class HipSGD:

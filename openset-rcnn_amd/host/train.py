@@ -18,7 +18,7 @@ wraps the model in DDP) and the update divides by the world size."
 from __future__ import annotations
 
 import collections
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, NamedTuple, Optional, Tuple
 
 import torch
 
@@ -38,9 +38,20 @@ def warmup_multistep_lr(iteration: int, base_lr: float, steps: Tuple[int, ...], 
     return lr
 
 
+class SolverOptions(NamedTuple):
+    """What the trainer's update needs beyond group 0's lr / momentum / weight decay (OpensetRCNNTrainer.solver_options; solver.HipSGD
+    derives it from its parameter groups). The defaults are one plain SGD group."""
+    bias_lr_factor: float = 1.0          # bias group lr / base group lr
+    weight_decay_bias: Optional[float] = None  # None: the bias parameters are in the base group
+    nesterov: bool = False
+    clip: Optional[str] = None           # None, "value" or "norm" ([d2] maybe_add_gradient_clipping, per parameter)
+    clip_value: float = 1.0
+    norm_type: float = 2.0
+
+
 class DynamicLossScale:
     """Host half of the overflow guard: one (event, pinned slot) per update, drained IN ORDER. The device half is a flag that
-    osr_check_finite clears and every osr_sgd_step launch of the iteration reads (a poisoned update changes nothing, no host
+    osr_check_finite clears and the update launch of the iteration reads (a poisoned update changes nothing, no host
     sync). `record(flag)` queues that flag's copy into a slot of its own right after an update; `poll(wait)` applies the verdicts
     of the updates that have finished -- an overflow halves the scale (floor 1.0), `growth_interval` consecutive clean updates
     double it again, never past the configured scale (what torch's GradScaler does) -- so no verdict is ever overwritten however
@@ -191,7 +202,7 @@ class OpensetRCNNTrainer:
         self.mom = {k: torch.zeros_like(t) for k, t in self.master.items()}
         # (the stem master is the padded (64, 8, 1, 32) view: its 6 976 padding zeros are not parameters)
         self.num_params = sum(t.numel() for t in self.master.values()) - (16384 - 9408 if STEM + ".w" in self.master else 0)
-        # overflow guard: device flag read by every osr_sgd_step launch; its host half is self.scaler (DynamicLossScale)
+        # overflow guard: device flag read by the update launch; its host half is self.scaler (DynamicLossScale)
         self._ok = torch.ones((1,), dtype=torch.int32, device=dev)
         self._cside: Optional[torch.cuda.Stream] = None  # stream the gradient buckets' collectives are issued from (see _done)
         self._overlap = False
@@ -201,12 +212,10 @@ class OpensetRCNNTrainer:
         self._wside: Optional[torch.cuda.Stream] = None  # stream of the weight / bias gradient launches (see _wg)
         self.side_wgrad = True
         self.chain_forward = True  # res3 blocks: conv2 -> conv3 in one launch that also stores conv2's output (osr_conv2d_chain_fwd_ex)
-        self.multi_tensor_update = True  # the update as two launches (ops.sgd_step_multi_, ops.pack_dgrad_weight_multi_); False: one launch per tensor
-        self._sgd_plan = None
-        self._segment_plan = None
-        # [d2] solver options beyond one plain SGD group (solver.SolverOptions: clipping, bias group, Nesterov), set by HipSGD.step;
-        # None: the plain update (osr_check_finite + osr_sgd_step_multi)
-        self.solver_options = None
+        self._sgd_plans = (None, {})  # (addresses of the buffers, {(bias lr factor, bias weight decay, weight decay, nesterov): plan}), see _sgd_plan
+        # [d2] solver options beyond one plain SGD group (SolverOptions: clipping, bias group, Nesterov), set by HipSGD.step;
+        # None: the neutral SolverOptions()
+        self.solver_options: Optional[SolverOptions] = None
         self._pack_plan = None
         self._pre: Optional[torch.cuda.Stream] = None  # stream of the next batch's frozen prefix (_prefetch_frozen)
         self.backward_concurrency_hint = 2  # launch streams of the backward (data gradients + weight gradients): see step(); 24.0 -> 23.7 ms
@@ -291,27 +300,6 @@ class OpensetRCNNTrainer:
             self.master[name + ".b"] = e.w[name + ".b"]
         self.conv_names.append(name)
 
-    def _fan(self, jobs) -> None:
-        """Independent in-place launches dealt round-robin over the trainer's streams: all start after the main stream's current
-        point, the main stream continues when all have finished. (No allocation inside the jobs: nothing changes stream.)"""
-        if not self.side_wgrad or not torch.cuda.is_available() or self.device.type != "cuda":
-            for job in jobs:
-                job()
-            return
-        cur = torch.cuda.current_stream(self.device)
-        if self._wside is None:
-            self._wside = torch.cuda.Stream(device=self.device)
-        if self._side is None:
-            self._side = torch.cuda.Stream(device=self.device)
-        sts = [cur, self._wside, self._side]
-        for st in sts[1:]:
-            st.wait_stream(cur)
-        for i, job in enumerate(jobs):
-            with torch.cuda.stream(sts[i % len(sts)]):
-                job()
-        for st in sts[1:]:
-            cur.wait_stream(st)
-
     def _refresh_derived(self):
         """Everything that is a function of the parameters and read by a kernel: backward-data weights, transposed fp32 heads,
         normalised prototypes."""
@@ -330,7 +318,7 @@ class OpensetRCNNTrainer:
                 wd["fc1"] = ops.pack_dgrad_weight(e.fc1_w).view(e.fc1_w.shape[1], 1, 1, e.fc1_w.shape[0])
                 wd["fc2"] = ops.pack_dgrad_weight(e.fc2_w).view(e.fc2_w.shape[1], 1, 1, e.fc2_w.shape[0])
             self.wd = wd
-        elif self.multi_tensor_update:
+        else:  # every backward-data weight in one launch
             pairs = [(e.w[n + ".w"], wd[n]) for n in self.conv_names]
             if not split:
                 pairs += [(e.fc1_w, wd["fc1"].view(e.fc1_w.shape[1], e.fc1_w.shape[0])), (e.fc2_w, wd["fc2"].view(e.fc2_w.shape[1], e.fc2_w.shape[0]))]
@@ -352,15 +340,14 @@ class OpensetRCNNTrainer:
                 if split:
                     self._resplit_transposed()
                 self._pack_done = None
-        else:
-            jobs = [lambda n=n: ops.pack_dgrad_weight(e.w[n + ".w"], wd[n]) for n in self.conv_names]
-            if split:
-                jobs.append(self._resplit_transposed)
-            else:
-                jobs.append(lambda: ops.pack_dgrad_weight(e.fc1_w, wd["fc1"].view(e.fc1_w.shape[1], e.fc1_w.shape[0])))
-                jobs.append(lambda: ops.pack_dgrad_weight(e.fc2_w, wd["fc2"].view(e.fc2_w.shape[1], e.fc2_w.shape[0])))
-            self._fan(jobs)
         self._refresh_heads()
+
+    def _wait_pack(self) -> None:
+        """The main stream waits for the repack behind the previous update (_refresh_derived runs it on the weight-gradient stream):
+        before the backward reads the backward-data weights, and before the next update rewrites what the repack reads."""
+        if getattr(self, "_pack_done", None) is not None:
+            torch.cuda.current_stream(self.device).wait_event(self._pack_done)
+            self._pack_done = None
 
     def _resplit_transposed(self) -> None:
         """box_head="split": the transposed bf16 planes of fc1.w / fc2.w (what the NEXT BACKWARD's data gradients read) from the
@@ -584,9 +571,7 @@ class OpensetRCNNTrainer:
         self._scale_used = self.loss_scale  # the update divides out the scale THIS backward multiplied in, whatever a poll does in between
         self._overlap = overlap and parallel.is_dist()
         self.buckets.reset()
-        if getattr(self, "_pack_done", None) is not None:  # the repack of the backward-data weights behind the previous update (_refresh_derived)
-            torch.cuda.current_stream(self.device).wait_event(self._pack_done)
-            self._pack_done = None
+        self._wait_pack()
         return S
 
     def _on_side(self, fn):
@@ -855,12 +840,7 @@ class OpensetRCNNTrainer:
         NaN changes neither parameters nor momentum (the reference trains in fp32 and cannot overflow; fp16 gradients can). The
         flag is read back lazily by `poll_overflow()` -- no host sync here."""
         gs = 1.0 / (getattr(self, "_scale_used", self.loss_scale) * world)
-        self._ok.fill_(1)
-        if self.solver_options is None:
-            ops.check_finite_(self.grad_flat, self._ok)
-            self._apply_sgd(self.lr, self.momentum, self.weight_decay, gs)
-        else:
-            self._apply_sgd_ex(self.solver_options, gs)
+        self._apply_sgd(self.solver_options or SolverOptions(), self.lr, self.momentum, self.weight_decay, gs)
         self.scaler.record(self._ok, getattr(self, "_proposal_status", None))
         self._proposal_status = None
 
@@ -868,25 +848,7 @@ class OpensetRCNNTrainer:
         """The update's launches with nothing to apply (bench.py's no-collective timing): the caller has zeroed the gradient; learning
         rate 0, weight decay 0 and momentum factor 1 make p' = p - 0 * (1 * v + 0) and v' = 1 * v + 0 -- parameters, momentum buffers,
         low-precision copies and backward-data weights come out bit for bit as they went in, no verdict is queued in the loss scaler."""
-        self._ok.fill_(1)
-        ops.check_finite_(self.grad_flat, self._ok)
-        self._apply_sgd(0.0, 1.0, 0.0, 1.0)
-
-    def _apply_sgd(self, lr: float, momentum: float, weight_decay: float, gs: float) -> None:
-        if self.multi_tensor_update:
-            # every parameter tensor in ONE launch (osr_sgd_step_multi over a device-resident table), then every backward-data weight in
-            # one more (_refresh_derived): ~145 launches of a few microseconds of work each became two; same bits per element
-            sig = tuple(t.data_ptr() for k in self.master for t in (self.master[k], self.grad[k], self.mom[k]) + ((self.lowp[k],) if self.lowp.get(k) is not None else ()))
-            if self._sgd_plan is None or self._sgd_plan[0] != sig:
-                self._sgd_plan = (sig, ops.sgd_multi_plan([(pm, self.grad[k], self.mom[k], self.row_scale.get(k), self.lowp.get(k))
-                                                           for k, pm in self.master.items()], self.device))
-            ops.sgd_step_multi_(self._sgd_plan[1], lr, momentum, weight_decay, gs, self._ok)
-        else:
-            # ~75 in-place launches of a few microseconds each (one per parameter tensor), then ~70 repacking launches: dealt over the
-            # three streams of the trainer they run three abreast instead of one behind the other
-            self._fan([lambda k=k, pm=pm: ops.sgd_step_(pm, self.grad[k], self.mom[k], lr, momentum, weight_decay, gs, self.row_scale.get(k),
-                                                       self.lowp.get(k), self._ok) for k, pm in self.master.items()])
-        self._refresh_derived()
+        self._apply_sgd(SolverOptions(), 0.0, 1.0, 0.0, 1.0)
 
     def _param_rows(self) -> Dict[str, List[int]]:
         """Masters that hold several detectron2 parameters as contiguous row ranges: name -> row boundaries (see export_state_dict).
@@ -894,15 +856,17 @@ class OpensetRCNNTrainer:
         return {"rpn_tail.w": [0, 4, 5], "rpn_tail.b": [0, 4, 5],  # anchor_deltas, centerness
                 "pred.w": [0, 4, 5], "pred.b": [0, 4, 5]}          # bbox_pred, iou_pred
 
-    def _apply_sgd_ex(self, o, gs: float) -> None:
-        """The update with the [d2] solver options (solver.SolverOptions o): one segment per detectron2 parameter (bias masters in the
-        bias group), per-parameter clipping of the averaged gradient grad * gs * row_scale, Nesterov momentum. Norm clipping: the
-        norm pass also clears the overflow flag (osr_grad_norm_partials covers every master: the flat buffer's alignment padding is
-        never written). Runs after all_reduce_grads(), so every rank computes the same coefficients."""
-        wd_bias = self.weight_decay if o.weight_decay_bias is None else o.weight_decay_bias
-        key = (tuple(t.data_ptr() for k in self.master for t in (self.master[k], self.grad[k], self.mom[k]) + ((self.lowp[k],) if self.lowp.get(k) is not None else ())),
-               o.bias_lr_factor, wd_bias, self.weight_decay, o.nesterov)
-        if self._segment_plan is None or self._segment_plan[0] != key:
+    def _sgd_plan(self, o: SolverOptions, weight_decay: float):
+        """The device-resident segment table of the update, built once per (bias lr factor, bias weight decay, weight decay, Nesterov)
+        -- what the table itself carries -- and dropped when a buffer moves: one segment per detectron2 parameter (_param_rows), bias
+        masters in the bias group."""
+        sig = tuple(t.data_ptr() for k in self.master for t in (self.master[k], self.grad[k], self.mom[k]) + ((self.lowp[k],) if self.lowp.get(k) is not None else ()))
+        if self._sgd_plans[0] != sig:
+            self._sgd_plans = (sig, {})
+        wd_bias = weight_decay if o.weight_decay_bias is None else o.weight_decay_bias
+        key = (o.bias_lr_factor, wd_bias, weight_decay, o.nesterov)
+        plans = self._sgd_plans[1]
+        if key not in plans:
             rows = self._param_rows()
             entries = []
             for k, pm in self.master.items():
@@ -910,14 +874,25 @@ class OpensetRCNNTrainer:
                 bounds = rows.get(k, [0, pm.shape[0]])
                 for r0, r1 in zip(bounds[:-1], bounds[1:]):
                     entries.append((pm, self.grad[k], self.mom[k], self.row_scale.get(k), self.lowp.get(k), r0, r1,
-                                    o.bias_lr_factor if bias else 1.0, wd_bias if bias else self.weight_decay, o.nesterov))
-            self._segment_plan = (key, ops.sgd_segment_plan(entries, self.device))
-        plan = self._segment_plan[1]
+                                    o.bias_lr_factor if bias else 1.0, wd_bias if bias else weight_decay, o.nesterov))
+            plans[key] = ops.sgd_segment_plan(entries, self.device)
+        return plans[key]
+
+    def _apply_sgd(self, o: SolverOptions, lr: float, momentum: float, weight_decay: float, gs: float) -> None:
+        """Every master in ONE launch (osr_sgd_step_multi_ex over the segment table), then every backward-data weight in one more
+        (_refresh_derived). The [d2] solver options o: per-parameter clipping of the averaged gradient grad * gs * row_scale, the bias
+        group, Nesterov momentum; the neutral SolverOptions() is torch.optim.SGD's plain step. The overflow flag is cleared by
+        osr_check_finite over the flat buffer, or, with norm clipping, by the norm pass (osr_grad_norm_partials covers every master:
+        the flat buffer's alignment padding is never written). Runs after all_reduce_grads(), so every rank computes the same
+        coefficients."""
+        self._wait_pack()  # (two updates without a backward in between: the previous repack still reads the copies this one rewrites)
+        self._ok.fill_(1)
+        if o.clip != "norm":  # (in front of the plan lookup: the host's walk over the buffers' addresses then runs under this launch)
+            ops.check_finite_(self.grad_flat, self._ok)
+        plan = self._sgd_plan(o, weight_decay)
         if o.clip == "norm":
             ops.grad_norm_partials_(plan, gs, o.norm_type, self._ok)
-        else:
-            ops.check_finite_(self.grad_flat, self._ok)
-        ops.sgd_step_multi_ex_(plan, self.lr, self.momentum, gs, o.clip, o.clip_value, o.norm_type, self._ok)
+        ops.sgd_step_multi_ex_(plan, lr, momentum, gs, o.clip, o.clip_value, o.norm_type, self._ok)
         self._refresh_derived()
 
     # several ranks: step k applies the verdicts of the updates up to k - 1 - MULTI_RANK_LAG, waited for -- the same set on every rank

@@ -1,6 +1,7 @@
-"""Cost of the [d2] solver options on the Openset train step (VOC-COCO yaml, batch 16, 3x800x1333, fp16, one GPU): the update with
-every option off (osr_check_finite + osr_sgd_step_multi), and through the segment launch (csrc/osr_solver.hip) with value clipping,
-norm clipping (NORM_TYPE 2, the fused norm / overflow pass) and norm clipping with a bias group and Nesterov. Random-init weights,
+"""Cost of the [d2] solver options on the Openset train step (VOC-COCO yaml, batch 16, 3x800x1333, fp16, one GPU): the update
+(osr_check_finite + osr_sgd_step_multi_ex, csrc/osr_solver.hip) with every option off, with value clipping, with norm clipping
+(NORM_TYPE 2: the fused norm / overflow pass osr_grad_norm_partials replaces osr_check_finite) and with norm clipping, a bias group
+and Nesterov. Random-init weights,
 synthetic uint8 images with 8 GT boxes each; WARMUP untimed steps, then STEPS whole steps timed one at a time with HIP events, then
 UPDATES update launches alone (the gradient of the last step, re-applied). Prints one JSON line: per variant, median / min / max ms.
 

@@ -7,15 +7,9 @@ from collections import defaultdict
 
 rows = list(csv.DictReader(open(sys.argv[1])))
 rows.sort(key=lambda r: int(r["Start_Timestamp"]))
-# an iteration ends with its SGD launch(es) (one sgd_multi_kernel, or a burst of sgd_kernel): take the window between the last two
-sgd = [int(r["End_Timestamp"]) for r in rows if "sgd_kernel" in r["Kernel_Name"] or "sgd_multi_kernel" in r["Kernel_Name"]]
-bursts = []
-for t in sgd:
-    if not bursts or t - bursts[-1][1] > 2e6:
-        bursts.append([t, t])
-    else:
-        bursts[-1][1] = t
-t0, t1 = bursts[-2][1], bursts[-1][1]
+# an iteration ends with its SGD launch, one sgd_multi_ex_kernel whatever the solver options: take the window between the last two
+sgd = [int(r["End_Timestamp"]) for r in rows if "sgd_multi_ex_kernel" in r["Kernel_Name"]]
+t0, t1 = sgd[-2], sgd[-1]
 it = [r for r in rows if t0 < int(r["Start_Timestamp"]) <= t1]
 print(f"iteration window {(t1 - t0) / 1e6:.2f} ms, {len(it)} kernels")
 byq = defaultdict(list)

@@ -3,7 +3,8 @@ group and Nesterov momentum.
   * kernel level: osr_grad_norm_partials + osr_sgd_step_multi_ex against a float64 restatement, every clip type and norm;
   * whole step, both trainers: `model(data)` / `backward` / `step` against torch.nn.utils.clip_grad_* + torch.optim.SGD applied per
     detectron2 parameter to the exported fp32 parameters;
-  * with every option off the update is the plain launch, and the segment launch with neutral options gives the same bits;
+  * with every option off the update is the same launch with the neutral options: one plan, the same bits (what that launch computed
+    before it became the only one is pinned in tests/test_update_pin.py);
   * run_net.py's loop trains with clipping, a bias group, Nesterov and WarmupCosineLR on."""
 import logging
 import math
@@ -157,26 +158,6 @@ def test_two_runs_give_identical_bits(osr, clip, p):
         assert torch.equal(pa.partials.cpu(), pb.partials.cpu())
 
 
-def test_neutral_segment_launch_is_bit_identical_to_sgd_step_multi(osr):
-    ops = osr.ops
-    ms = _masters(4)
-    res = []
-    for ex in (False, True):
-        dev = [dict(p=m["p"].to(DEV), g=m["g"].to(DEV), v=m["v"].to(DEV), rs=m["rs"].to(DEV) if m["rs"] is not None else None) for m in ms]
-        for d in dev:
-            d["lp"] = torch.zeros(d["p"].shape, dtype=torch.bfloat16, device=DEV) if d["rs"] is not None else None
-        if ex:
-            plan = ops.sgd_segment_plan([(d["p"], d["g"], d["v"], d["rs"], d["lp"], 0, d["p"].shape[0], 1.0, 1e-4, False) for d in dev], torch.device(DEV))
-            ops.sgd_step_multi_ex_(plan, 0.02, 0.9, 1.0 / 3072.0)
-        else:
-            plan = ops.sgd_multi_plan([(d["p"], d["g"], d["v"], d["rs"], d["lp"]) for d in dev], torch.device(DEV))
-            ops.sgd_step_multi_(plan, 0.02, 0.9, 1e-4, 1.0 / 3072.0)
-        torch.cuda.synchronize()
-        res.append([{k: t.cpu() for k, t in d.items() if t is not None} for d in dev])
-    for a, b in zip(*res):
-        assert all(torch.equal(a[k], b[k]) for k in a)
-
-
 def test_plan_refuses_bad_rows(osr):
     p = torch.zeros((5, 8), device=DEV)
     with pytest.raises(osr.ops.OsrError):
@@ -302,8 +283,8 @@ def _twin(cfg):
 
 @pytest.mark.parametrize("yaml", ["voc_coco.yaml", "base_rcnn_fpn.yaml"])
 def test_options_off_is_the_plain_update_bit_for_bit(osr, yaml):
-    """Every option off: the update runs osr_check_finite + osr_sgd_step_multi (no segment plan is built), and the segment launch
-    with neutral options (factor 1, one weight decay, no clip, no Nesterov) gives the same parameters after three steps."""
+    """Every option off (solver_options None) and the neutral SolverOptions() (factor 1, one weight decay, no clip, no Nesterov) share
+    one plan and give the same parameters after three steps. (tests/test_update_pin.py holds both to the plain update's bits.)"""
     from tests.test_train_loop import _data
     from openset_rcnn_amd.host.solver import SolverOptions, build_optimizer
     cfg = _cfg(yaml)
@@ -321,7 +302,7 @@ def test_options_off_is_the_plain_update_bit_for_bit(osr, yaml):
             total.backward()
             if forced is None:
                 opt.step()
-            else:  # the same step, through the segment launch
+            else:  # the same step, the neutral options spelled out
                 t = model.trainer()
                 g = opt.param_groups[0]
                 t.lr, t.momentum, t.weight_decay = g["lr"], g["momentum"], g["weight_decay"]
@@ -329,7 +310,7 @@ def test_options_off_is_the_plain_update_bit_for_bit(osr, yaml):
                 t._update(t.all_reduce_grads())
                 t.grads_ready = False
         t = model.trainer()
-        assert (t._segment_plan is None) == (forced is None)
+        assert len(t._sgd_plans[1]) == 1
         outs.append(({k: v.clone() for k, v in t.master.items()}, {k: v.clone() for k, v in t.mom.items()}))
     for k in outs[0][0]:
         assert torch.equal(outs[0][0][k], outs[1][0][k]), k

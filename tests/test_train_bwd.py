@@ -315,9 +315,11 @@ def test_elementwise_and_sgd(ops):
 
 def test_pack_dgrad_weight_kernel_and_overflow_flag(ops):
     """osr_pack_dgrad_weight against the host packing (weights.pack_dgrad_weight: flip + permute), ragged channel counts, both
-    element sizes, in-place refill of a preallocated buffer; osr_check_finite clears its flag on inf / NaN only."""
+    element sizes, in-place refill of a preallocated buffer, and osr_pack_dgrad_weight_multi over the same pairs in one plan;
+    osr_check_finite clears its flag on inf / NaN only."""
     from openset_rcnn_amd.host.weights import pack_conv_weight, pack_dgrad_weight
     gg = g(77)
+    pairs, wants = [], []
     for cout, cin, k, dt in ((40, 96, 3, torch.float16), (256, 64, 1, torch.bfloat16), (33, 17, 5, torch.float32), (128, 128, 3, torch.float16)):
         w = torch.randn(cout, cin, k, k, generator=gg)
         fwd = pack_conv_weight(w, dt).to(DEV)           # (cout,kh,kw,cin): what the forward kernels read
@@ -326,6 +328,12 @@ def test_pack_dgrad_weight_kernel_and_overflow_flag(ops):
         assert got.shape == want.shape and torch.equal(got.cpu(), want)
         buf = torch.zeros_like(got)
         assert ops.pack_dgrad_weight(fwd, buf) is buf and torch.equal(buf.cpu(), want)
+        pairs.append((fwd, torch.zeros_like(got)))
+        wants.append(want)
+    # the multi launch: the same four pairs through one table, one launch (the same tile body)
+    ops.pack_dgrad_weight_multi_(ops.pack_dgrad_multi_plan(pairs, torch.device(DEV)))
+    for (_, out), want in zip(pairs, wants):
+        assert torch.equal(out.cpu(), want)
     m = torch.randn(21, 1024, generator=gg).to(DEV)
     assert torch.equal(ops.pack_dgrad_weight(m).cpu(), m.t().cpu())
     flag = torch.ones(1, dtype=torch.int32, device=DEV)

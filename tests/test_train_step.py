@@ -252,10 +252,12 @@ def test_weight_gradients_on_the_second_stream_are_the_same_gradients(setup):
 
 
 def test_multi_tensor_update_is_bit_identical_to_one_launch_per_tensor(setup):
-    """The update as two launches (osr_sgd_step_multi, osr_pack_dgrad_weight_multi over device-resident tables) against ~145 launches
-    (osr_sgd_step / osr_pack_dgrad_weight per tensor), from the SAME gradients, masters and momentum: two updates in a row -- masters,
-    momentum buffers, the low-precision working copies and the backward-data weights agree bit for bit; an overflowed iteration (flag
-    0) changes nothing in either form."""
+    """The trainer's update as two launches (osr_sgd_step_multi_ex over its segment table, osr_pack_dgrad_weight_multi over its pack
+    table) against ~145 launches built here -- ops.sgd_step_ per master (a one-entry plan each) and ops.pack_dgrad_weight per tensor --
+    from the SAME gradients, masters and momentum: two updates in a row -- masters, momentum buffers, the low-precision working copies
+    and the backward-data weights agree bit for bit, which holds the big tables' pointers, row ranges and chunk lists to the trivially
+    built ones; an overflowed iteration (flag 0) changes nothing in either form."""
+    from openset_rcnn_amd.host import ops
     from openset_rcnn_amd.host.train import OpensetRCNNTrainer
     d = setup["dev"]
     args = (d["images"], d["hw"], setup["h"], setup["w"], d["gt"], d["gcls"], d["gcnt"], d["keys"])
@@ -263,26 +265,40 @@ def test_multi_tensor_update_is_bit_identical_to_one_launch_per_tensor(setup):
     tr.step(*args, update=False)  # gradients of a real step
     torch.cuda.synchronize()
     snap = dict(master={k: v.clone() for k, v in tr.master.items()}, mom={k: v.clone() for k, v in tr.mom.items()}, grad=tr.grad_flat.clone())
+    ok = torch.ones((1,), dtype=torch.int32, device=DEV)
+
+    def per_tensor_update():
+        e = tr.eng
+        ok.fill_(1)
+        ops.check_finite_(tr.grad_flat, ok)
+        for k, pm in tr.master.items():
+            ops.sgd_step_(pm, tr.grad[k], tr.mom[k], tr.lr, tr.momentum, tr.weight_decay, 1.0 / tr._scale_used, tr.row_scale.get(k), tr.lowp.get(k), ok)
+        for n in tr.conv_names:
+            ops.pack_dgrad_weight(e.w[n + ".w"], tr.wd[n])
+        for fc, w in (("fc1", e.fc1_w), ("fc2", e.fc2_w)):
+            ops.pack_dgrad_weight(w, tr.wd[fc].view(w.shape[1], w.shape[0]))
+
     state = {}
     for multi in (True, False):
+        update = (lambda: tr._update(1)) if multi else per_tensor_update
         for k in snap["master"]:
             tr.master[k].copy_(snap["master"][k])
             tr.mom[k].copy_(snap["mom"][k])
-        tr.multi_tensor_update = multi
         for _ in range(2):
             tr.grad_flat.copy_(snap["grad"])
-            tr._update(1)
+            update()
         # a poisoned gradient: the overflow flag gates the whole update
         before = {k: v.clone() for k, v in tr.master.items()}
         tr.grad_flat.fill_(float("inf"))
-        tr._update(1)
+        update()
         torch.cuda.synchronize()
         assert all(torch.equal(before[k], tr.master[k]) for k in before), "an overflowed update must not touch the masters"
-        assert tr.poll_overflow(wait=True)
+        assert tr.poll_overflow(wait=True) if multi else int(ok) == 0
         state[multi] = dict(master={k: v.clone() for k, v in tr.master.items()}, mom={k: v.clone() for k, v in tr.mom.items()},
                             lowp={k: v.clone() for k, v in tr.lowp.items() if v is not None}, wd={k: v.clone() for k, v in tr.wd.items()})
     moved = sum(int(not torch.equal(state[True]["master"][k], snap["master"][k])) for k in snap["master"])
     assert moved == len(snap["master"]), "every parameter tensor must have been updated"
+    assert sorted(state[True]["wd"]) == sorted(tr.conv_names + ["fc1", "fc2"])  # (the per-tensor form above repacks every one of them)
     for group in ("master", "mom", "lowp", "wd"):
         for k, a in state[True][group].items():
             assert torch.equal(a, state[False][group][k]), (group, k)
