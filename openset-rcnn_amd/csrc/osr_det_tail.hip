@@ -10,6 +10,7 @@
 #include "osr_boxes.h"
 #include "osr_loss_common.h"
 #include "osr_pln_dist.h"
+#include "osr_select.h"
 
 // ------------------------------------------------------------------------------------------------------
 // box predictor tail: wave per RoI row
@@ -93,23 +94,6 @@ extern "C" osr_status osr_box_predictor_tail(const float* x, int64_t m, int32_t 
 #define SORT_THREADS 1024
 #define SORT_LDS_CAP 8192
 
-template <class P>
-__device__ __forceinline__ void bitonic_desc_any(P buf, int n) {
-    for (int k = 2; k <= n; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = threadIdx.x; i < n; i += blockDim.x) {
-                int ixj = i ^ j;
-                if (ixj > i) {
-                    unsigned long long a = buf[i], b = buf[ixj];
-                    bool desc = (i & k) == 0;
-                    if (desc ? (a < b) : (a > b)) { buf[i] = b; buf[ixj] = a; }
-                }
-            }
-            __syncthreads();
-        }
-    }
-}
-
 static inline long long pow2ceil(long long v) { long long p = 1; while (p < v) p <<= 1; return p; }
 
 // workspace per segment: order[seg_stride] int32, then (16-byte aligned) keys[pow2ceil(seg_stride)] u64
@@ -134,7 +118,7 @@ __global__ __launch_bounds__(SORT_THREADS) void seg_sort_kernel(const float* __r
     for (int i = tid; i < np; i += blockDim.x) {
         unsigned long long key = 0ull;
         if (i < len && (!cd || cd[i])) {
-            key = ((unsigned long long)osr_float_key(sc[i]) << 32) | (unsigned int)(0xffffffffu - (unsigned int)i);
+            key = sel_pair(osr_float_key(sc[i]), (unsigned int)i);
             ++nvalid;
         }
         if (in_lds) s_keys[i] = key; else gk[i] = key;
@@ -142,11 +126,8 @@ __global__ __launch_bounds__(SORT_THREADS) void seg_sort_kernel(const float* __r
     int tot;
     osr_block_excl_scan(nvalid, s_scan, &tot);
     __syncthreads();
-    if (in_lds) bitonic_desc_any(s_keys, np); else bitonic_desc_any(gk, np);
-    for (int i = tid; i < tot; i += blockDim.x) {
-        unsigned long long key = in_lds ? s_keys[i] : gk[i];
-        order[i] = (int)(0xffffffffu - (unsigned int)(key & 0xffffffffull));
-    }
+    if (in_lds) bitonic_desc(s_keys, np); else bitonic_desc(gk, np);
+    for (int i = tid; i < tot; i += blockDim.x) order[i] = sel_pair_index(in_lds ? s_keys[i] : gk[i]);
     if (tid == 0) ws_count[seg] = tot;
 }
 

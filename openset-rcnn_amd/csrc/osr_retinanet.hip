@@ -151,7 +151,7 @@ __global__ __launch_bounds__(RN_FILTER_THREADS) void rn_filter_kernel(RnLevels l
         mine += __popc(m);
         if constexpr (MODE == 1) {
 #pragma unroll
-            for (int e = 0; e < VEC; ++e) sel_hist_add(s_dig, (int)(osr_float_key(v[e]) >> RN_DIGIT_SHIFT), (m >> e) & 1u);  // (all lanes call it)
+            for (int e = 0; e < VEC; ++e) sel_hist_add<2>(s_dig, (int)(osr_float_key(v[e]) >> RN_DIGIT_SHIFT), (m >> e) & 1u);  // (all lanes call it)
         }
     }
     if constexpr (MODE == 1) {
@@ -182,7 +182,7 @@ __global__ __launch_bounds__(RN_FILTER_THREADS) void rn_filter_kernel(RnLevels l
             while (c >= pitch) { c -= pitch; ++row; }
             if ((pass[it] >> e) & 1u) {
                 const unsigned int i = (unsigned)(row * AK + c);
-                if (pos < cap) out[pos] = ((unsigned long long)osr_float_key(v[e]) << 32) | (0xffffffffu - i);
+                if (pos < cap) out[pos] = sel_pair(osr_float_key(v[e]), i);
                 ++pos;
             }
             ++c;
@@ -196,36 +196,16 @@ __global__ __launch_bounds__(RN_FILTER_THREADS) void rn_filter_kernel(RnLevels l
 // ------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(64) void rn_refine_kernel(RnLevels lv, const int* __restrict__ surv_cnt, const int* __restrict__ hist,
                                                        unsigned int* __restrict__ thr2) {
-    const int l = blockIdx.x, img = blockIdx.y, lane = threadIdx.x;
+    const int l = blockIdx.x, img = blockIdx.y;
     const int segid = img * lv.num_levels + l;
     if (surv_cnt[segid] <= lv.caps[l]) return;
-    constexpr int BPL = RN_DIGITS / 64;
-    const int* h = hist + (long long)segid * RN_DIGITS + lane * BPL;
-    int sum = 0;
-    for (int j = 0; j < BPL; ++j) sum += h[j];
-    int inc = sum;  // becomes the sum over this lane's bins and all higher lanes'
-#pragma unroll
-    for (int dd = 1; dd < 64; dd <<= 1) {
-        const int t = __shfl_down(inc, dd, 64);
-        if (lane + dd < 64) inc += t;
-    }
-    const int above = inc - sum, want = lv.topk;  // (an overflowed segment has more than caps >= RN_MIN_SURVIVORS > topk candidates)
-    if (above < want && want <= inc) {
-        int acc = above, d = lane * BPL;
-        for (int j = BPL - 1; j >= 0; --j) {
-            if (acc + h[j] >= want) { d = lane * BPL + j; break; }
-            acc += h[j];
-        }
-        thr2[segid] = (unsigned int)d << RN_DIGIT_SHIFT;
-    }
+    int d, above, bucket;  // (an overflowed segment has more than caps >= RN_MIN_SURVIVORS > topk >= 1 candidates, all in its histogram)
+    if (sel_digit_of_rank<RN_DIGITS>(hist + (long long)segid * RN_DIGITS, lv.topk, &d, &above, &bucket)) thr2[segid] = (unsigned int)d << RN_DIGIT_SHIFT;
 }
 
 // ------------------------------------------------------------------------------------------------------
 // pass 2: one workgroup per segment
 // ------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float rn_key_to_float(uint32_t key) {
-    return __uint_as_float((key & 0x80000000u) ? (key ^ 0x80000000u) : ~key);
-}
 
 template <class T>
 __global__ __launch_bounds__(SEL_THREADS) void rn_select_kernel(RnLevels lv, const float* __restrict__ cell_anchors, const T* __restrict__ logits,
@@ -249,8 +229,8 @@ __global__ __launch_bounds__(SEL_THREADS) void rn_select_kernel(RnLevels lv, con
 
     __shared__ unsigned long long s_sel[SEL_MAXK];
     __shared__ __attribute__((aligned(16))) int s_hist[SEL_BINS];
-    __shared__ unsigned long long s_prefix;
-    __shared__ int s_remaining, s_bucket, s_fill;
+    __shared__ SelBcast<unsigned long long> s_bc;
+    __shared__ int s_fill;
 
     // element j of the segment's source as its (key, ~index) pair; 0 = not a candidate
     auto load = [&](int j) -> unsigned long long {
@@ -258,83 +238,41 @@ __global__ __launch_bounds__(SEL_THREADS) void rn_select_kernel(RnLevels lv, con
         if (!fallback) return list[j];
         const int row = (int)((unsigned)j / (unsigned)AK);
         const float v = osr_to_float(seg[(long long)row * lv.pitch_cls + (j - row * AK)]);
-        return v > thresh ? ((unsigned long long)osr_float_key(v) << 32) | (0xffffffffu - (unsigned)j) : 0ull;
+        return v > thresh ? sel_pair(osr_float_key(v), (unsigned)j) : 0ull;
     };
     const int nit = (m + SEL_THREADS - 1) / SEL_THREADS;
 
     // ---- 1. radix select of the k-th largest pair, MSB first: 11 + 11 + 10 key bits, then 11 + 11 + 10 index bits. It stops as soon
     //      as the bucket of the current prefix holds exactly the elements still wanted: with distinct logits after the key bits. ----
-    unsigned long long prefix = 0ull, mask = 0ull;
-    if (nsrc > k) {
-        int remaining = k;
+    SelRank<unsigned long long> rank{0ull, 0ull, k};
+    if (nsrc > k) {  // (nsrc candidates reach the first histogram: more than k = remaining >= 1)
 #pragma unroll 1
         for (int pass = 0; pass < 6; ++pass) {
             const int shift = pass == 0 ? 53 : pass == 1 ? 42 : pass == 2 ? 32 : pass == 3 ? 21 : pass == 4 ? 10 : 0;
-            const int nbins = (pass == 2 || pass == 5) ? 1024 : 2048;
-            for (int i = tid; i < SEL_BINS; i += blockDim.x) s_hist[i] = 0;
-            __syncthreads();
-            for (int it = 0; it < nit; ++it) {
-                const unsigned long long c = load(it * SEL_THREADS + tid);
-                sel_hist_add(s_hist, (int)((c >> shift) & (unsigned long long)(nbins - 1)), c != 0ull && (c & mask) == prefix);
-            }
-            __syncthreads();
-            if (tid < 64) {
-                // the digit whose bucket holds the rank (rpn_select_kernel's walk): the largest d with sum(hist[d..]) >= remaining
-                constexpr int BPL = SEL_BINS / 64;
-                int sum = 0;
-#pragma unroll
-                for (int j = 0; j < BPL; j += 4) {
-                    const int4 h4 = *reinterpret_cast<const int4*>(&s_hist[tid * BPL + j]);
-                    sum += h4.x + h4.y + h4.z + h4.w;
+            const int bucket = sel_radix_pass<SEL_BINS, 2>(rank, shift, (pass == 2 || pass == 5) ? 10 : 11, s_hist, &s_bc, [&](auto add) {
+                for (int it = 0; it < nit; ++it) {
+                    const unsigned long long c = load(it * SEL_THREADS + tid);
+                    add(c, c != 0ull);
                 }
-                int inc = sum;
-#pragma unroll
-                for (int dd = 1; dd < 64; dd <<= 1) {
-                    const int t = __shfl_down(inc, dd, 64);
-                    if (tid + dd < 64) inc += t;
-                }
-                const int above = inc - sum;
-                if (above < remaining && remaining <= inc) {  // exactly one lane: the histogram holds >= remaining elements
-                    int acc = above, d = tid * BPL, hd = s_hist[tid * BPL];
-                    for (int j = BPL - 1; j >= 0; --j) {
-                        const int hj = s_hist[tid * BPL + j];
-                        if (acc + hj >= remaining) { d = tid * BPL + j; hd = hj; break; }
-                        acc += hj;
-                    }
-                    s_prefix = prefix | ((unsigned long long)d << shift);
-                    s_remaining = remaining - acc;
-                    s_bucket = hd;
-                }
-            }
-            __syncthreads();
-            prefix = s_prefix;
-            remaining = s_remaining;
-            const int bucket = s_bucket;
-            mask |= (unsigned long long)(nbins - 1) << shift;
-            __syncthreads();
-            if (bucket == remaining) break;  // uniform: every element of the bucket is selected
+            });
+            if (bucket == rank.remaining) break;  // uniform: every element of the bucket is selected
         }
     }
     // Now: the selected elements are the candidates with (pair & mask) >= prefix -- exactly k of them (all, when ncand <= k).
 
-    // ---- 2. compaction into LDS: the order is free (integer atomics), the sort below fixes it ----
+    // ---- 2. compaction into LDS [0, k): the order is free (integer atomics), the sort below fixes it ----
     if (tid == 0) s_fill = 0;
     __syncthreads();
     for (int it = 0; it < nit; ++it) {
         const unsigned long long c = load(it * SEL_THREADS + tid);
-        if (c != 0ull && (c & mask) >= prefix) {
+        if (c != 0ull && (c & rank.mask) >= rank.prefix) {
             const int p = atomicAdd(&s_fill, 1);
             if (p < SEL_MAXK) s_sel[p] = c;
         }
     }
-    int kp = 1;
-    while (kp < k) kp <<= 1;
-    __syncthreads();
-    for (int i = k + tid; i < kp; i += blockDim.x) s_sel[i] = 0ull;  // padding sorts last
-    __syncthreads();
 
     // ---- 3. logit descending, index ascending ----
-    if (k > 1) bitonic_desc(s_sel, kp);
+    sel_pad_and_sort(s_sel, k);
 
     // ---- 4. score, class, decode ----
     const float fstride = (float)lv.stride[l];
@@ -349,8 +287,8 @@ __global__ __launch_bounds__(SEL_THREADS) void rn_select_kernel(RnLevels lv, con
             continue;
         }
         const unsigned long long comp = s_sel[j];
-        const int idx = (int)(0xffffffffu - (unsigned int)(comp & 0xffffffffull));
-        const float z = rn_key_to_float((uint32_t)(comp >> 32));
+        const int idx = sel_pair_index(comp);
+        const float z = sel_pair_key_float(comp);
         const int t = idx / K, kc = idx - t * K;
         const int cell = t / A, a = t - cell * A;
         const float4 d = *reinterpret_cast<const float4*>(dl + (long long)cell * lv.pitch_box + a * 4);
@@ -456,14 +394,15 @@ extern "C" osr_status osr_retinanet_select(const osr_rpn_levels* lv, const float
     const int64_t cnt_bytes = rn_counter_bytes(n, s.num_levels);
     const int64_t need = (int64_t)surv_total * 8 + cnt_bytes;
     OSR_REQUIRE(workspace_bytes >= need, OSR_ERR_WORKSPACE, "osr_retinanet_select: workspace %lld < %lld bytes", (long long)workspace_bytes, (long long)need);
-    unsigned long long* surv = (unsigned long long*)workspace;
+    // the histograms first: rn_refine_kernel reads them 16 bytes at a time
     const int nseg = n * s.num_levels;
-    int* surv_cnt = (int*)((char*)workspace + (int64_t)surv_total * 8);
+    int* hist = (int*)workspace;
+    int* surv_cnt = hist + (int64_t)nseg * RN_DIGITS;
     int* cnt2 = surv_cnt + nseg;
     unsigned int* thr2 = (unsigned int*)(cnt2 + nseg);
-    int* hist = cnt2 + 2 * nseg;
+    unsigned long long* surv = (unsigned long long*)((char*)workspace + cnt_bytes);
     hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(status_flags, 0, sizeof(int32_t), st) != hipSuccess || hipMemsetAsync(surv_cnt, 0, (size_t)cnt_bytes, st) != hipSuccess) {
+    if (hipMemsetAsync(status_flags, 0, sizeof(int32_t), st) != hipSuccess || hipMemsetAsync(workspace, 0, (size_t)cnt_bytes, st) != hipSuccess) {
         osr_set_error("osr_retinanet_select: memset failed");
         return OSR_ERR_LAUNCH;
     }

@@ -111,7 +111,7 @@ __global__ __launch_bounds__(SEL_THREADS) void rpn_select_kernel(SelLevels lv, c
     __shared__ unsigned long long s_sel[SEL_MAXK];
     __shared__ __attribute__((aligned(16))) int s_hist[SEL_BINS];
     __shared__ int s_scan[32];
-    __shared__ unsigned int s_prefix, s_remaining;
+    __shared__ SelBcast<unsigned int> s_bc;
 
     // Four scores per thread and load (16 bytes per lane) where the segment allows it: the level's score run must be 16-byte
     // aligned and a multiple of 4 long (true for p2..p4 of every image; the small levels take the scalar form).
@@ -122,73 +122,32 @@ __global__ __launch_bounds__(SEL_THREADS) void rpn_select_kernel(SelLevels lv, c
     // ---- 1. radix select: key T of the k-th largest element (3 passes: 11 + 11 + 10 key bits, MSB first). The scores of a level are sigmoid
     //      outputs: their leading key byte is the same for almost every anchor, so one LDS atomic per element would put all 67 200
     //      adds of a p2 pass on one histogram bin, one behind the other. sel_hist_add adds a wave's most common digits once per wave. ----
-    unsigned int prefix = 0, mask = 0;
-    int remaining = k;  // rank (1-based, from the top) still to resolve inside the current prefix bucket
-    if (cnt > k) {
+    SelRank<unsigned int> rank{0u, 0u, k};
+    if (cnt > k) {  // (so the first histogram holds cnt > k = remaining elements, and every later one its prefix's bucket, which holds the rank)
         // three passes over the scores: 11 + 11 + 10 key bits, MSB first (four 8-bit passes read the 269 KB of a p2 level once more)
 #pragma unroll 1
         for (int pass = 0; pass < 3; ++pass) {
-            const int shift = pass == 0 ? 21 : pass == 1 ? 10 : 0, nbins = pass == 2 ? 1024 : 2048;
-            for (int i = tid; i < SEL_BINS; i += blockDim.x) s_hist[i] = 0;
-            __syncthreads();
-            for (int it = 0; it < nit; ++it) {
-                const int i = (it * SEL_THREADS + tid) * per;
-                unsigned int key[4] = {0u, 0u, 0u, 0u};
-                if (i < cnt) {
-                    if (vec4) {
-                        const float4 v = *reinterpret_cast<const float4*>(sc + i);
-                        key[0] = sel_key(v.x); key[1] = sel_key(v.y); key[2] = sel_key(v.z); key[3] = sel_key(v.w);
-                    } else key[0] = sel_key(sc[i]);
-                }
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    if (e < per) sel_hist_add(s_hist, (int)((key[e] >> shift) & (unsigned)(nbins - 1)), i < cnt && (key[e] & mask) == prefix);
-            }
-            __syncthreads();
-            if (tid < 64) {
-                // the digit d whose bucket holds the rank: the largest d with sum(hist[d..]) >= remaining (d = 0 when only the whole
-                // histogram reaches it). One wave: SEL_BINS / 64 bins per lane, suffix sums over the lanes, then the lane that holds
-                // the crossing walks its own bins (a serial walk over all bins: dependent LDS reads, 7 us per 256 of them).
-                constexpr int BPL = SEL_BINS / 64;
-                int sum = 0;
-#pragma unroll
-                for (int j = 0; j < BPL; j += 4) {
-                    const int4 h4 = *reinterpret_cast<const int4*>(&s_hist[tid * BPL + j]);
-                    sum += h4.x + h4.y + h4.z + h4.w;
-                }
-                int inc = sum;  // becomes the sum over this lane's bins and all higher lanes'
-#pragma unroll
-                for (int dd = 1; dd < 64; dd <<= 1) {
-                    const int t = __shfl_down(inc, dd, 64);
-                    if (tid + dd < 64) inc += t;
-                }
-                const int above = inc - sum;
-                const bool here = above < remaining && remaining <= inc;
-                if (here) {
-                    int acc = above, d = tid * BPL;
-                    for (int j = BPL - 1; j >= 0; --j) {
-                        const int hj = s_hist[tid * BPL + j];
-                        if (acc + hj >= remaining) { d = tid * BPL + j; break; }
-                        acc += hj;
+            sel_radix_pass<SEL_BINS, 2>(rank, pass == 0 ? 21 : pass == 1 ? 10 : 0, pass == 2 ? 10 : 11, s_hist, &s_bc, [&](auto add) {
+                for (int it = 0; it < nit; ++it) {
+                    const int i = (it * SEL_THREADS + tid) * per;
+                    unsigned int key[4] = {0u, 0u, 0u, 0u};
+                    if (i < cnt) {
+                        if (vec4) {
+                            const float4 v = *reinterpret_cast<const float4*>(sc + i);
+                            key[0] = sel_key(v.x); key[1] = sel_key(v.y); key[2] = sel_key(v.z); key[3] = sel_key(v.w);
+                        } else key[0] = sel_key(sc[i]);
                     }
-                    s_prefix = prefix | ((unsigned int)d << shift);
-                    s_remaining = remaining - acc;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e)
+                        if (e < per) add(key[e], i < cnt);
                 }
-                if (!__ballot(here) && tid == 0) {  // (cannot happen while the bucket holds >= remaining elements: the serial walk's d = 0 exit)
-                    s_prefix = prefix;
-                    s_remaining = remaining - (inc - s_hist[0]);
-                }
-            }
-            __syncthreads();
-            prefix = s_prefix;
-            remaining = s_remaining;
-            mask |= (unsigned)(nbins - 1) << shift;
-            __syncthreads();
+            });
         }
     }
     // Now: elements with key > prefix are all selected; of those with key == prefix the first `remaining`
     // in index order are selected (stable tie rule). If cnt <= k everything is selected.
-    const unsigned int T = prefix;
+    const unsigned int T = rank.prefix;
+    const int remaining = rank.remaining;
     const bool all = cnt <= k;
 
     // ---- 2. ordered compaction into s_sel as (key << 32) | ~index: strictly greater keys to [0, ngt), ties to [ngt, k). The k-th
@@ -215,7 +174,7 @@ __global__ __launch_bounds__(SEL_THREADS) void rpn_select_kernel(SelLevels lv, c
 #pragma unroll
             for (int e = 0; e < 4; ++e)
                 if (e < per) {
-                    const unsigned long long comp = ((unsigned long long)key[e] << 32) | (unsigned int)(0xffffffffu - (unsigned int)(i + e));
+                    const unsigned long long comp = sel_pair(key[e], (unsigned int)(i + e));
                     const bool g = all || key[e] > T, q = !all && key[e] == T;
                     if (g) { if (pg < SEL_MAXK) s_sel[pg] = comp; ++pg; }
                     if (q) { if (pe < remaining && ngt_total + pe < SEL_MAXK) s_sel[ngt_total + pe] = comp; ++pe; }
@@ -225,21 +184,16 @@ __global__ __launch_bounds__(SEL_THREADS) void rpn_select_kernel(SelLevels lv, c
         base_eq += tot >> 16;
         if (!all && base_eq >= remaining && base_gt >= ngt_total) break;  // uniform
     }
-    int kp = 1;
-    while (kp < k) kp <<= 1;
-    for (int i = k + tid; i < kp; i += blockDim.x) s_sel[i] = 0ull;  // padding sorts last
-    __syncthreads();
 
     // ---- 3. sort the survivors: score descending, index ascending ----
-    bitonic_desc(s_sel, kp);
+    sel_pad_and_sort(s_sel, k);
 
     // ---- 4. decode + filters ----
     const float ih = (float)image_hw[img * 2 + 0], iw = (float)image_hw[img * 2 + 1];
     const float fstride = (float)lv.stride[l];
     bool bad = false;
     for (int j = tid; j < k; j += blockDim.x) {
-        const unsigned long long comp = s_sel[j];
-        const int idx = (int)(0xffffffffu - (unsigned int)(comp & 0xffffffffull));
+        const int idx = sel_pair_index(s_sel[j]);
         const float s = sc[idx];
         const float4 d = *reinterpret_cast<const float4*>(dl + (long long)idx * 4);
         const float4 an = osr_cell_anchor(cell_anchors, l, A, idx % A, idx / A, W, fstride);

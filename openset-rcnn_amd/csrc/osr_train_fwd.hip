@@ -14,6 +14,7 @@
 #include "osr_box_loss.h"
 #include "osr_loss_common.h"
 #include "osr_pln_dist.h"
+#include "osr_select.h"
 static_assert(OSR_LOSS_IOU == OSR_BOX_LOSS_IOU && OSR_LOSS_SMOOTH_L1 == OSR_BOX_LOSS_SMOOTH_L1 && OSR_LOSS_GIOU == OSR_BOX_LOSS_GIOU &&
                   OSR_LOSS_DIOU == OSR_BOX_LOSS_DIOU && OSR_LOSS_CIOU == OSR_BOX_LOSS_CIOU, "osr_box_loss.h and include/osr.h number the losses alike");
 
@@ -102,49 +103,18 @@ extern "C" osr_status osr_rpn_match_anchors(const osr_rpn_levels* lvl, const flo
 // ------------------------------------------------------------------------------------------------------
 #define TR_THREADS 1024
 #define TR_MAXK 512
+#define TR_BINS 256  // four 8-bit radix passes
 
-__device__ __forceinline__ void tr_bitonic_desc(unsigned long long* buf, int n) {
-    for (int k = 2; k <= n; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = threadIdx.x; i < n; i += blockDim.x) {
-                const int ixj = i ^ j;
-                if (ixj > i) {
-                    const unsigned long long a = buf[i], b = buf[ixj];
-                    const bool desc = (i & k) == 0;
-                    if (desc ? (a < b) : (a > b)) { buf[i] = b; buf[ixj] = a; }
-                }
-            }
-            __syncthreads();
-        }
-}
-
-// One histogram increment per lane with `pred`, wave-aggregated: keys of a narrow range share their leading byte (uniform keys in [0.5, 1):
-// one exponent), so a plain LDS atomic per lane serialises 64 ways on one address. Up to four rounds elect a leader, count the lanes
-// that share its bin with one ballot and add the count once; whatever is left (the well-spread later bytes) goes out as plain atomics.
-__device__ __forceinline__ void tr_hist_add(int* s_hist, int bin, bool pred) {
-    const int lane = threadIdx.x & 63;
-    unsigned long long act = __ballot(pred);
-#pragma unroll
-    for (int it = 0; it < 4; ++it) {
-        if (!act) break;  // (wave-uniform)
-        const int leader = __ffsll((long long)act) - 1;
-        const int b = __shfl(bin, leader, 64);
-        const unsigned long long same = __ballot(pred && bin == b) & act;
-        if (lane == leader) atomicAdd(&s_hist[b], __popcll(same));
-        act &= ~same;
-    }
-    if ((act >> lane) & 1ull) atomicAdd(&s_hist[bin], 1);
-}
-
-// member(i) -> bool, keyf(i) -> float (both must be readable for every i < cnt). Selects min(k, #members) entries; s_sel[j] low 32 bits =
-// 0xffffffff - index, in ascending (key, index) order. Returns the number selected (uniform). Must be called by the whole block.
+// member(i) -> bool, keyf(i) -> float (both must be readable for every i < cnt). Selects min(k, #members) entries; s_sel[j] is the pair
+// (inverted key, ~index) of osr_select.h, in ascending (key, index) order. Returns the number selected (uniform). Must be called by the whole
+// block. s_hist: TR_BINS ints, 16-byte aligned.
 // Round 5: every pass over the list keeps TR_UNROLL independent (member, key) loads per thread in flight -- the passes used to issue one
 // dependent 1-byte + 4-byte load pair per trip, ~15 passes x 88 trips of memory latency per image -- and the compaction ranks its candidates
 // with ONE block scan over per-thread counts of a blocked layout (thread t owns a contiguous run: thread order = index order, which is what
 // the tie rule needs) instead of one block scan per 1024 elements. Same selection bit for bit (tests/test_train_fwd.py, golden fixtures).
 template <int TR_UNROLL = 1, class MemberF, class KeyF>  // TR_UNROLL: (member, key) pairs a thread keeps in flight (8 for the 89 523-anchor lists; 1 where the accessors are heavy)
 __device__ int tr_select_smallest(MemberF member, KeyF keyf, int cnt, int k, unsigned long long* s_sel,
-                                  int* s_hist, int* s_scan, unsigned int* s_bc) {
+                                  int* s_hist, int* s_scan, SelBcast<unsigned int>* s_bc) {
     const int tid = threadIdx.x, nt = blockDim.x;
     // batched walk, interleaved layout (coalesced): BODY(i, mem, v) for every i < cnt with mem = member(i), v = inverted monotone key
 #define TR_WALK(BODY)                                                                                          \
@@ -168,46 +138,15 @@ __device__ int tr_select_smallest(MemberF member, KeyF keyf, int cnt, int k, uns
     if (k > TR_MAXK) k = TR_MAXK;
     if (k <= 0) return 0;
     // inverted monotone key: the k smallest floats are the k largest v
-    unsigned int prefix = 0, mask = 0;
-    int remaining = k;
+    SelRank<unsigned int> rank{0u, 0u, k};
     const bool all = m <= k;
-    if (!all) {
-        for (int pass = 0; pass < 4; ++pass) {
-            const int shift = 24 - 8 * pass;
-            for (int i = tid; i < 256; i += nt) s_hist[i] = 0;
-            __syncthreads();
-            TR_WALK({ tr_hist_add(s_hist, (int)((v >> shift) & 255), mem && (v & mask) == prefix); })
-            __syncthreads();
-            if (tid < 64) {
-                // the digit d (from 255 down) at which the count of larger digits first reaches `remaining`: lane l owns digits 255 - 4 l .. 252 - 4 l
-                // (a serial walk by one thread was 256 dependent LDS reads per pass: ~12 us, eight times per call)
-                const int h0 = s_hist[255 - 4 * tid], h1 = s_hist[254 - 4 * tid], h2 = s_hist[253 - 4 * tid], h3 = s_hist[252 - 4 * tid];
-                const int mine = h0 + h1 + h2 + h3;
-                const int before = osr_wave_incl_scan(mine) - mine;  // digits larger than this lane's four
-                // first lane (lowest index = largest digits) whose inclusive count reaches `remaining`; digit 0 takes whatever is left
-                const bool hit = before + mine >= remaining;
-                const unsigned long long hits = __ballot(hit);
-                const int sel = hits ? __ffsll((long long)hits) - 1 : 63;
-                if (tid == sel) {
-                    int acc = before, d = 255 - 4 * tid;
-                    const int hh[4] = {h0, h1, h2, h3};
-                    int j = 0;
-                    for (; j < 3; ++j) {
-                        if (d - j == 0 || acc + hh[j] >= remaining) break;
-                        acc += hh[j];
-                    }
-                    s_bc[0] = prefix | ((unsigned int)(d - j) << shift);
-                    s_bc[1] = (unsigned int)(remaining - acc);
-                }
-            }
-            __syncthreads();
-            prefix = s_bc[0];
-            remaining = (int)s_bc[1];
-            mask |= 255u << shift;
-            __syncthreads();
-        }
+    if (!all) {  // (so the first histogram holds m > k = remaining >= 1 members)
+#pragma unroll 1
+        for (int pass = 0; pass < 4; ++pass)
+            sel_radix_pass<TR_BINS, 4>(rank, 24 - 8 * pass, 8, s_hist, s_bc, [&](auto add) { TR_WALK({ add(v, mem); }) });
     }
-    const unsigned int T = prefix;
+    const unsigned int T = rank.prefix;
+    const int remaining = rank.remaining;
     // compaction, blocked layout: thread t owns [t * chunk, (t + 1) * chunk): its candidates greater than T and equal to T, counted, ranked by
     // one block scan, then written in index order (candidates equal to T: the first `remaining` of them by index)
     const int chunk = (cnt + nt - 1) / nt, lo = min(tid * chunk, cnt), hi = min(lo + chunk, cnt);
@@ -237,18 +176,14 @@ __device__ int tr_select_smallest(MemberF member, KeyF keyf, int cnt, int k, uns
     const int ngt_total = tot & 0x7ff;
     TR_WALK_BLOCKED({
         if (mem) {
-            const unsigned long long comp = ((unsigned long long)v << 32) | (unsigned int)(0xffffffffu - (unsigned int)i);
+            const unsigned long long comp = sel_pair(v, (unsigned int)i);
             if (all || v > T) { if (pg < TR_MAXK) s_sel[pg] = comp; ++pg; }
             else if (v == T) { if (pe < remaining && ngt_total + pe < TR_MAXK) s_sel[ngt_total + pe] = comp; ++pe; }
         }
     })
 #undef TR_WALK
 #undef TR_WALK_BLOCKED
-    int kp = 1;
-    while (kp < k) kp <<= 1;
-    for (int i = k + tid; i < kp; i += blockDim.x) s_sel[i] = 0ull;
-    __syncthreads();
-    tr_bitonic_desc(s_sel, kp);  // v descending == key ascending; index ascending inside ties
+    sel_pad_and_sort(s_sel, k);  // v descending == key ascending; index ascending inside ties
     return k;
 }
 
@@ -258,18 +193,19 @@ __global__ __launch_bounds__(TR_THREADS) void subsample_kernel(signed char* __re
                                                                int* __restrict__ num_neg_out) {
     __shared__ unsigned long long s_sel[TR_MAXK];
     __shared__ int s_pos[TR_MAXK], s_neg[TR_MAXK];
-    __shared__ int s_hist[256], s_scan[32];
-    __shared__ unsigned int s_bc[2];
+    __shared__ __attribute__((aligned(16))) int s_hist[TR_BINS];
+    __shared__ int s_scan[32];
+    __shared__ SelBcast<unsigned int> s_bc;
     const int img = blockIdx.x, tid = threadIdx.x;
     signed char* lab = labels + (long long)img * R;
     const float* ky = keys + (long long)img * R;
     const int cnt = (int)R;
     const int want_pos = (int)((float)num_samples * pos_fraction);
-    const int np = tr_select_smallest<8>([&](int i) { return lab[i] == 1; }, [&](int i) { return ky[i]; }, cnt, want_pos, s_sel, s_hist, s_scan, s_bc);
-    for (int j = tid; j < np; j += blockDim.x) s_pos[j] = (int)(0xffffffffu - (unsigned int)(s_sel[j] & 0xffffffffull));
+    const int np = tr_select_smallest<8>([&](int i) { return lab[i] == 1; }, [&](int i) { return ky[i]; }, cnt, want_pos, s_sel, s_hist, s_scan, &s_bc);
+    for (int j = tid; j < np; j += blockDim.x) s_pos[j] = sel_pair_index(s_sel[j]);
     __syncthreads();
-    const int nn = tr_select_smallest<8>([&](int i) { return lab[i] == 0; }, [&](int i) { return ky[i]; }, cnt, num_samples - np, s_sel, s_hist, s_scan, s_bc);
-    for (int j = tid; j < nn; j += blockDim.x) s_neg[j] = (int)(0xffffffffu - (unsigned int)(s_sel[j] & 0xffffffffull));
+    const int nn = tr_select_smallest<8>([&](int i) { return lab[i] == 0; }, [&](int i) { return ky[i]; }, cnt, num_samples - np, s_sel, s_hist, s_scan, &s_bc);
+    for (int j = tid; j < nn; j += blockDim.x) s_neg[j] = sel_pair_index(s_sel[j]);
     __syncthreads();
     for (int i = tid; i < cnt; i += blockDim.x) lab[i] = -1;  // label.fill_(-1)
     __syncthreads();
@@ -423,8 +359,9 @@ __global__ __launch_bounds__(TR_THREADS) void roi_match_sample_kernel(const floa
                                                                       int* __restrict__ out_gidx /* may be null */) {
     __shared__ unsigned long long s_sel[TR_MAXK];
     __shared__ int s_idx[TR_MAXK];
-    __shared__ int s_hist[256], s_scan[32];
-    __shared__ unsigned int s_bc[2];
+    __shared__ __attribute__((aligned(16))) int s_hist[TR_BINS];
+    __shared__ int s_scan[32];
+    __shared__ SelBcast<unsigned int> s_bc;
     const int img = blockIdx.x, tid = threadIdx.x;
     const int P = min((long long)prop_count[img], pcap), G = min(gt_count[img], gmax);
     const int C = P + G;
@@ -455,12 +392,12 @@ __global__ __launch_bounds__(TR_THREADS) void roi_match_sample_kernel(const floa
     // [d2] subsample_labels(gt_classes, batch_size, positive_fraction, bg = num_classes): fg first, then bg
     const int want_fg = (int)((float)batch_size * pos_fraction);
     int nsel = 0;
-    const int nfg = tr_select_smallest([&](int i) { return cls[i] != num_classes && cls[i] != -1; }, keyf, C, want_fg, s_sel, s_hist, s_scan, s_bc);
-    for (int j = tid; j < nfg; j += blockDim.x) s_idx[j] = (int)(0xffffffffu - (unsigned int)(s_sel[j] & 0xffffffffull));
+    const int nfg = tr_select_smallest([&](int i) { return cls[i] != num_classes && cls[i] != -1; }, keyf, C, want_fg, s_sel, s_hist, s_scan, &s_bc);
+    for (int j = tid; j < nfg; j += blockDim.x) s_idx[j] = sel_pair_index(s_sel[j]);
     __syncthreads();
     nsel = nfg;
-    const int nbg = tr_select_smallest([&](int i) { return cls[i] == num_classes; }, keyf, C, batch_size - nfg, s_sel, s_hist, s_scan, s_bc);
-    for (int j = tid; j < nbg; j += blockDim.x) s_idx[nsel + j] = (int)(0xffffffffu - (unsigned int)(s_sel[j] & 0xffffffffull));
+    const int nbg = tr_select_smallest([&](int i) { return cls[i] == num_classes; }, keyf, C, batch_size - nfg, s_sel, s_hist, s_scan, &s_bc);
+    for (int j = tid; j < nbg; j += blockDim.x) s_idx[nsel + j] = sel_pair_index(s_sel[j]);
     __syncthreads();
     nsel += nbg;
     for (int j = tid; j < batch_size; j += blockDim.x) {

@@ -125,24 +125,34 @@ def test_rpn_targets_full_size(ops):
     _check_rpn_losses(ops, c, lr, lo, mb, ct, 36)
 
 
-@pytest.mark.parametrize("kind", ["all_equal", "two_values", "equal_tail"])
+@pytest.mark.parametrize("kind", ["all_equal", "two_values", "equal_tail", "signs"])
 def test_subsample_heavily_tied_keys_against_the_oracle(ops, kind):
     """the compaction's packed (gt, eq) scan must survive more than 65 535 candidates whose key EQUALS the selection
-    threshold (all-equal keys: every label-0 anchor of the 89 523). Tie rule: lower index wins (tests/test_oracle_kat.py)."""
-    r, n = 89523, 3
+    threshold (all-equal keys: every label-0 anchor of the 89 523). Tie rule: lower index wins (tests/test_oracle_kat.py).
+    "signs": every other key here lies in [0, 1), which reaches neither the key's sign handling nor the leading-byte digits of the
+    radix passes. One full trip of 1024 x 8 plus a tail; image 0 selects by radix (300 > 128 positives), image 1 takes all its 40.
+    Heavy ties over both signs and many exponents; -0.0 and +0.0 tie by index. No NaN or inf keys (the kernel's NaN order is not torch's)."""
+    r, n, ignored, pos0 = (9001, 2, 500, 300) if kind == "signs" else (89523, 3, 3000, 700)
     gg = g(91)
     lab = torch.zeros(n, r, dtype=torch.int8)
-    lab[:, torch.randperm(r, generator=gg)[:3000]] = -1
-    lab[0, torch.randperm(r, generator=gg)[:700]] = 1
+    lab[:, torch.randperm(r, generator=gg)[:ignored]] = -1
+    lab[0, torch.randperm(r, generator=gg)[:pos0]] = 1
     lab[1, torch.randperm(r, generator=gg)[:40]] = 1
     if kind == "all_equal":
         keys = torch.full((n, r), 0.5)
     elif kind == "two_values":  # 80 000+ at the threshold value, the rest above it
         keys = torch.where(torch.rand(n, r, generator=gg) < 0.93, torch.tensor(0.25), torch.tensor(0.75))
-    else:  # a few distinct small keys, then one huge tie group that the threshold lands in
+    elif kind == "equal_tail":  # a few distinct small keys, then one huge tie group that the threshold lands in
         keys = torch.full((n, r), 0.5)
         keys[:, torch.randperm(r, generator=gg)[:100]] = torch.rand(n, 100, generator=gg) * 0.4
-    assert int((lab[2] == 0).sum()) > 65536
+    else:
+        vals = torch.tensor([-3.5, -1e-30, -0.0, 0.0, 1e-30, 2.0 ** -20, 0.5, 3.0, 1e30])
+        tied = vals[torch.randint(0, vals.numel(), (n, r), generator=gg)]
+        spread = torch.randn(n, r, generator=gg) * torch.exp(torch.rand(n, r, generator=gg) * 40 - 20)
+        keys = torch.where(torch.rand(n, r, generator=gg) < 2 / 3, tied, spread)
+        assert bool(torch.isfinite(keys).all()) and bool((keys < 0).any()) and bool((keys == 0).any())
+    if kind != "signs":
+        assert int((lab[2] == 0).sum()) > 65536
     out = lab.clone().to(DEV)
     np_, nn_ = ops.subsample_labels_(out, keys.to(DEV), 256, 0.5)
     for i in range(n):
@@ -172,12 +182,15 @@ def _roi_case(seed, n, pcap, counts_p, counts_g, hw=(600, 800), gmax=8, ties=Fal
         pb[i, k:p] = torch.cat((ctr - size / 2, ctr + size / 2), dim=1)
         pl[i, :p] = torch.randn(p, generator=gg)
     keys = torch.rand(n, pcap + gmax, generator=gg)
-    if ties:
+    if ties == "signed":  # both signs, ties and both zeros
+        keys = ((keys - 0.5) * 40).round() / 40
+    elif ties:
         keys = (keys * 40).round() / 40
     return pb, pl, torch.tensor(counts_p, dtype=torch.int32), gt, cls, gcnt, keys
 
 
-@pytest.mark.parametrize("pcap,counts_p,counts_g,ties", [(300, [300, 120, 40], [4, 0, 8], True), (7323, [7323, 5000], [6, 2], False)])
+@pytest.mark.parametrize("pcap,counts_p,counts_g,ties", [(300, [300, 120, 40], [4, 0, 8], True), (7323, [7323, 5000], [6, 2], False),
+                                                              (300, [300, 120, 40], [4, 0, 8], "signed")])
 def test_roi_match_and_sample(ops, pcap, counts_p, counts_g, ties):
     n = len(counts_p)
     pb, pl, pcnt, gt, cls, gcnt, keys = _roi_case(41, n, pcap, counts_p, counts_g, ties=ties)
