@@ -778,6 +778,66 @@ osr_status osr_retinanet_select(const osr_rpn_levels* lv, const float* cell_anch
                                 int32_t* c_cls, int32_t* c_cand, int32_t* c_src, int32_t* counts, int32_t* status_flags,
                                 void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * Panoptic FPN at inference: the elementwise half of [d2] SemSegFPNHead, its output path, and
+ * combine_semantic_and_instance_outputs (csrc/osr_semseg.hip, csrc/osr_panoptic.hip). detectron2 is not at hand: the semantics are
+ * written from memory of detectron2 v0.6, and THIS TEXT is the contract the tests check. Tensors are NHWC in f16 / bf16 / f32, all
+ * arithmetic is fp32, every launch is deterministic (integer atomics only, fixed summation orders: repeats are bit-identical),
+ * nothing syncs with the host, every function is capturable.
+ *
+ * osr_group_norm_stats: x (n, h, w, c), c in {64, 128, 256}, 32 groups of c / 32 consecutive channels of every pixel ->
+ * mean, rstd (n, 32) fp32, rstd = 1 / sqrt(biased variance + eps). Two launches: per-chunk (count, mean, M2) partials (shifted sums
+ * per thread, Chan merges in thread order) into the workspace, then a merge of the chunks in chunk order. x 16-byte aligned.
+ *
+ * osr_gn_relu_merge: out (n, ho, wo, c) = sum over the terms, in order, of up_t(relu(gn_t(x_t))), summed in fp32 and rounded once
+ * to dtype. A term's input is (n, h, w, c) of dtype; with mean / rstd (n, 32) and gamma / beta (c) fp32 it is normalised as
+ * (x - mean) * rstd * gamma + beta, with all four NULL it is only rectified. up2 != 0: torch's bilinear x2 with
+ * align_corners=False applied after the ReLU (src = max(0, (dst + 0.5) / 2 - 0.5), second tap clamped to the last row / column),
+ * h = ho / 2, w = wo / 2; up2 == 0: h = ho, w = wo. 1 .. OSR_GN_MAX_TERMS terms; c in {64, 128, 256}.
+ *
+ * osr_semseg_resample: ONE image. logits (h4, w4, pitch) of dtype, channels [0, num_classes) real, [num_classes, pitch) padding
+ * that is never compared or written; pitch a multiple of 4. Per output pixel and class: bilinear x4 to (4 h4, 4 w4), crop to
+ * (ih, iw), bilinear resize of the crop to (oh, ow), both align_corners=False without antialiasing, composed without forming the
+ * x4 map; second-stage coordinates src = max(0, ((float)ih / oh) * (dst + 0.5) - 0.5), second taps clamped to the crop's last row /
+ * column. mode OSR_SEMSEG_LABELS: out (oh, ow) int32, the argmax over the real classes, the lowest class on a tie (strict
+ * comparisons: NaN never wins). mode OSR_SEMSEG_VALUES: out (num_classes, oh, ow) fp32. 1 <= ih <= 4 h4, 1 <= iw <= 4 w4.
+ *
+ * osr_panoptic_combine: ONE image. masks (k, h, w) bytes (non-zero = set; torch bool), scores (k) fp32, classes (k) int64, count
+ * (device int32, NULL = k): the first min(count, k) instances are walked by descending score (equal scores: lower index first,
+ * whatever the input order), stopping at the first score < instances_confidence_thresh; an instance of area 0 is skipped; with
+ * inter = its pixels already painted it is skipped when (double)inter / area > (double)overlap_thresh, else its unpainted pixels
+ * get the next id (1, 2, ..). Then the labels (h, w) int32 present in the map, ascending, without label 0 (labels outside
+ * 0 .. 255 are ignored): a label with at least stuff_area_limit unpainted pixels paints them with the next id. Outputs:
+ * panoptic_seg (h, w) int32 (0 = none), seg_table (k + 255, 4) int32 rows {isthing, category_id, instance_id or -1, area (painted
+ * pixels)}, seg_scores (k + 255) fp32 (0 for stuff), seg_count (1) int32; row r describes id r + 1. Six launches whatever k is.
+ * k > 1024: OSR_ERR_UNSUPPORTED, nothing launched. h * w <= 2^30.
+ * --------------------------------------------------------------------------------------------------------- */
+#define OSR_GN_MAX_TERMS 4
+typedef struct osr_gn_term {
+    const void* x;
+    const float* mean;
+    const float* rstd;
+    const float* gamma;
+    const float* beta;
+    int32_t h, w;
+    int32_t up2;
+    int32_t reserved;
+} osr_gn_term;
+#define OSR_SEMSEG_LABELS 0
+#define OSR_SEMSEG_VALUES 1
+int64_t osr_group_norm_stats_workspace_bytes(int32_t n, int32_t h, int32_t w, int32_t c);
+osr_status osr_group_norm_stats(const void* x, int32_t dtype, int32_t n, int32_t h, int32_t w, int32_t c, float eps, float* mean,
+                                float* rstd, void* workspace, int64_t workspace_bytes, void* stream);
+osr_status osr_gn_relu_merge(const osr_gn_term* terms, int32_t num_terms, int32_t dtype, int32_t n, int32_t ho, int32_t wo, int32_t c,
+                             void* out, void* stream);
+osr_status osr_semseg_resample(const void* logits, int32_t dtype, int32_t h4, int32_t w4, int32_t pitch, int32_t num_classes, int32_t ih,
+                               int32_t iw, int32_t oh, int32_t ow, int32_t mode, void* out, void* stream);
+int64_t osr_panoptic_combine_workspace_bytes(int32_t k, int32_t h, int32_t w);
+osr_status osr_panoptic_combine(const uint8_t* masks, const float* scores, const int64_t* classes, const int32_t* count, int32_t k,
+                                const int32_t* labels, int32_t h, int32_t w, float overlap_thresh, int32_t stuff_area_limit,
+                                float instances_confidence_thresh, int32_t* panoptic_seg, int32_t* seg_table, float* seg_scores,
+                                int32_t* seg_count, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* =========================================================================================================
  * Training step, forward half: targets and losses. Gradients are not
  * produced by this library yet; every function below is a forward kernel whose outputs equal the reference's

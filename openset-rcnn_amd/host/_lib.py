@@ -94,6 +94,18 @@ class RoiOptions(C.Structure):
     _fields_ = [("aligned", C.c_int32), ("sampling_ratio", C.c_int32)]
 
 
+class GnTerm(C.Structure):
+    """include/osr.h osr_gn_term: one term of osr_gn_relu_merge."""
+    _fields_ = [("x", C.c_void_p), ("mean", C.c_void_p), ("rstd", C.c_void_p), ("gamma", C.c_void_p), ("beta", C.c_void_p),
+                ("h", C.c_int32), ("w", C.c_int32), ("up2", C.c_int32), ("reserved", C.c_int32)]
+
+
+GN_MAX_TERMS = 4
+SEMSEG_LABELS, SEMSEG_VALUES = 0, 1
+PANOPTIC_MAX_INSTANCES = 1024  # csrc/osr_panoptic.hip PC_MAX_K
+PANOPTIC_MAX_STUFF = 255       # labels 1 .. 255
+
+
 class Pyramid(C.Structure):
     _fields_ = [
         ("num_levels", C.c_int32), ("c", C.c_int32),
@@ -152,6 +164,13 @@ PROTOTYPES = {
     "osr_retinanet_select_capacity": (I32, [C.POINTER(RpnLevels), I32]),
     "osr_retinanet_select_workspace_bytes": (I64, [C.POINTER(RpnLevels), I32, I32, I32]),
     "osr_retinanet_select": (I32, [C.POINTER(RpnLevels), P, P, I32, I64, P, I64, I32, I32, I32, F32, P, P, P, P, P, P, P, P, P, I64, P]),
+    # Panoptic FPN (csrc/osr_semseg.hip, csrc/osr_panoptic.hip)
+    "osr_group_norm_stats_workspace_bytes": (I64, [I32, I32, I32, I32]),
+    "osr_group_norm_stats": (I32, [P, I32, I32, I32, I32, I32, F32, P, P, P, I64, P]),
+    "osr_gn_relu_merge": (I32, [C.POINTER(GnTerm), I32, I32, I32, I32, I32, I32, P, P]),
+    "osr_semseg_resample": (I32, [P, I32, I32, I32, I32, I32, I32, I32, I32, I32, I32, P, P]),
+    "osr_panoptic_combine_workspace_bytes": (I64, [I32, I32, I32]),
+    "osr_panoptic_combine": (I32, [P, P, P, P, I32, P, I32, I32, F32, I32, F32, P, P, P, P, P, I64, P]),
     "osr_fastrcnn_candidates": (I32, [P, P, I32, I32, P, P, I32, I32, P, P, F32, P, P, P, P, P, P]),
     "osr_cascade_refine": (I32, [P, P, P, I32, I32, P, P, I32, P, P, P, I32, I32, F32, P, P, P, P, P, P, P]),
     "osr_cascade_candidates": (I32, [P, I32, P, I32, P, P, I32, I32, P, P, F32, P, P, P, P, P, P]),

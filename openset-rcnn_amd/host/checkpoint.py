@@ -17,7 +17,8 @@ False) --
 Both carry real BatchNorm statistics (not pre-reduced like the MSRA blobs); `weights.fold_frozen_bn` folds them.
 
 Checkpoints of the other zoo families ([d2] `.pth`, or the model zoo's `.pkl` = {"model": {name: ndarray}, "__author__": ...} without
-"matching_heuristics") load by name as they are: mask_rcnn, cascade, dconv and retinanet_R_50_FPN (backbone.top_block.p6 / p7, head.*).
+"matching_heuristics") load by name as they are: mask_rcnn, cascade, dconv, retinanet_R_50_FPN (backbone.top_block.p6 / p7, head.*) and panoptic_fpn_R_50 (sem_seg_head.*: its
+GroupNorm `.norm.weight` / `.norm.bias` carry no running statistics and are not folded).
 
 Nothing here reads from the network: paths are local files. The result is a flat {d2 name: fp32 tensor} dict, ready for
 `model.load_state_dict` (host/modeling.py) or, after `weights.fold_frozen_bn`, for `OpensetRCNNEngine`."""

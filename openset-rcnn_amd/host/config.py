@@ -177,6 +177,12 @@ def get_cfg() -> CfgNode:
                       "SCORE_THRESH_TEST": 0.05, "TOPK_CANDIDATES_TEST": 1000, "NMS_THRESH_TEST": 0.5, "BBOX_REG_WEIGHTS": (1.0, 1.0, 1.0, 1.0),
                       "NORM": "", "IOU_THRESHOLDS": [0.4, 0.5], "IOU_LABELS": [0, -1, 1], "FOCAL_LOSS_GAMMA": 2.0, "FOCAL_LOSS_ALPHA": 0.25,
                       "SMOOTH_L1_LOSS_BETA": 0.1, "BBOX_REG_LOSS_TYPE": "smooth_l1"})
+    # [d2] SemSegFPNHead and PanopticFPN (host/engine_panoptic.py). IGNORE_VALUE, LOSS_WEIGHT and INSTANCE_LOSS_WEIGHT are training
+    # keys: carried so that detectron2's yaml files merge, read by nothing yet
+    m.SEM_SEG_HEAD = CN({"NAME": "SemSegFPNHead", "IN_FEATURES": ["p2", "p3", "p4", "p5"], "IGNORE_VALUE": 255, "NUM_CLASSES": 54,
+                         "CONVS_DIM": 128, "COMMON_STRIDE": 4, "NORM": "GN", "LOSS_WEIGHT": 1.0})
+    m.PANOPTIC_FPN = CN({"INSTANCE_LOSS_WEIGHT": 1.0})
+    m.PANOPTIC_FPN.COMBINE = CN({"ENABLED": True, "OVERLAP_THRESH": 0.5, "STUFF_AREA_LIMIT": 4096, "INSTANCES_CONFIDENCE_THRESH": 0.5})
     c.INPUT = CN({"MIN_SIZE_TRAIN": (800,), "MIN_SIZE_TRAIN_SAMPLING": "choice", "MAX_SIZE_TRAIN": 1333, "MIN_SIZE_TEST": 800,
                   "MAX_SIZE_TEST": 1333, "FORMAT": "BGR", "RANDOM_FLIP": "horizontal", "MASK_FORMAT": "polygon"})
     c.DATASETS = CN({"TRAIN": (), "TEST": (), "PROPOSAL_FILES_TRAIN": (), "PROPOSAL_FILES_TEST": ()})

@@ -27,6 +27,7 @@ from . import ops, parallel
 from .config import CfgNode
 from .engine import DEFAULT_CFG, OpensetRCNNEngine, check_deform_options, refuse_deform_training
 from .engine_cascade import CascadeRCNNEngine, check_cascade_options
+from .engine_panoptic import PanopticFPNEngine, check_sem_seg_options, training_message as panoptic_training_message
 from .engine_retinanet import RETINA_PYRAMID, TRAINING_MESSAGE as RETINANET_TRAINING_MESSAGE, RetinaNetEngine, check_retina_anchors
 from .engine_std import StandardRCNNEngine, check_std_supported
 from .structures import Boxes, ImageList, Instances, ShapeSpec
@@ -1347,6 +1348,201 @@ class RetinaNet(_EngineOwner):
         insts = OpensetRCNNEngine.to_instances(res, len(sizes))
         return [{"instances": Instances(o, pred_boxes=Boxes(r["pred_boxes"]), scores=r["scores"], pred_classes=r["pred_classes"])}
                 for r, o in zip(insts, outs)]
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Panoptic FPN
+# ---------------------------------------------------------------------------------------------------------------
+class _ConvGN(nn.Module):
+    """A bias-free 3x3 convolution with its GroupNorm(32) under [d2] Conv2d's names: `.weight`, `.norm.weight`, `.norm.bias`."""
+
+    def __init__(self, cin, cout):
+        super().__init__()
+        self.weight = nn.Parameter(torch.empty(cout, cin, 3, 3))
+        self.norm = nn.GroupNorm(32, cout)
+
+
+class _Conv3x3(nn.Module):
+    def __init__(self, cin, cout):
+        super().__init__()
+        self.weight = nn.Parameter(torch.empty(cout, cin, 3, 3))
+        self.bias = nn.Parameter(torch.zeros(cout))
+
+
+class SemSegFPNHead(nn.Module):
+    """[d2] SemSegFPNHead under its parameter names: per input feature of stride s, head_length = max(1, log2(s) - log2(COMMON_STRIDE))
+    times (3x3 conv, NORM, ReLU, and a bilinear x2 where s != COMMON_STRIDE) as a Sequential whose even entries are the convolutions
+    (`<feat>.<2k>.weight`, `.norm.*` with NORM "GN", `.bias` with NORM "") and whose odd entries are the parameterless upsamples; the
+    results are summed and a 1x1 `predictor` gives NUM_CLASSES logits at COMMON_STRIDE. c2_msra_fill; GroupNorm weight 1, bias 0."""
+
+    def __init__(self, cfg: CfgNode, input_shape: Dict[str, ShapeSpec]):
+        super().__init__()
+        h = cfg.MODEL.SEM_SEG_HEAD
+        check_sem_seg_options(h.NAME, h.IN_FEATURES, h.NUM_CLASSES, h.CONVS_DIM, h.COMMON_STRIDE, h.NORM)
+        self.in_features = list(h.IN_FEATURES)
+        missing = [f for f in self.in_features if f not in input_shape]
+        if missing:
+            raise ValueError(f"MODEL.SEM_SEG_HEAD.IN_FEATURES: MODEL.BACKBONE.NAME {cfg.MODEL.BACKBONE.NAME!r} has no {missing}")
+        self.common_stride, self.num_classes, dim = int(h.COMMON_STRIDE), int(h.NUM_CLASSES), int(h.CONVS_DIM)
+        for feat in self.in_features:
+            stride, cin = input_shape[feat].stride, input_shape[feat].channels
+            length = max(1, int(math.log2(stride) - math.log2(self.common_stride)))
+            layers = []
+            for k in range(length):
+                layers.append(_ConvGN(cin if k == 0 else dim, dim) if h.NORM == "GN" else _Conv3x3(cin if k == 0 else dim, dim))
+                nn.init.kaiming_normal_(layers[-1].weight, mode="fan_out", nonlinearity="relu")
+                if stride != self.common_stride:
+                    layers.append(nn.Upsample(scale_factor=2, mode="bilinear", align_corners=False))
+            setattr(self, feat, nn.Sequential(*layers))
+        self.predictor = nn.Conv2d(dim, self.num_classes, 1)
+        nn.init.kaiming_normal_(self.predictor.weight, mode="fan_out", nonlinearity="relu")
+        nn.init.constant_(self.predictor.bias, 0)
+
+
+def sem_seg_engine_cfg_from(cfg: CfgNode) -> dict:
+    h, comb = cfg.MODEL.SEM_SEG_HEAD, cfg.MODEL.PANOPTIC_FPN.COMBINE
+    return dict(sem_seg_num_classes=int(h.NUM_CLASSES), sem_seg_convs_dim=int(h.CONVS_DIM), sem_seg_norm=str(h.NORM), sem_seg_common_stride=int(h.COMMON_STRIDE),
+                combine_overlap_thresh=float(comb.OVERLAP_THRESH), combine_stuff_area_limit=int(comb.STUFF_AREA_LIMIT),
+                combine_instances_confidence_thresh=float(comb.INSTANCES_CONFIDENCE_THRESH))
+
+
+def _refuse_sem_seg_extras(cfg: CfgNode, meta_arch: str) -> str:
+    """The refusals the two semantic meta architectures share; -> the TEST.AUG message."""
+    msg = ('TEST.AUG: test-time augmentation is implemented for META_ARCHITECTURE "GeneralizedRCNN" with StandardROIHeads only, not for '
+           f'META_ARCHITECTURE "{meta_arch}"')
+    if cfg.MODEL.KEYPOINT_ON:
+        raise ValueError("MODEL.KEYPOINT_ON: the HIP path has no keypoint head (box, mask and semantic branches only)")
+    if cfg.TEST.AUG.ENABLED:
+        raise ValueError(msg)
+    return msg
+
+
+def _sem_seg_outputs(eng, logits: torch.Tensor, num_classes: int, sizes, outs):
+    """[d2] sem_seg_postprocess per image from the stride-4 logits: (C, oh, ow) fp32."""
+    return [ops.semseg_resample(logits[i], num_classes, s, o, labels=False) for i, (s, o) in enumerate(zip(sizes, outs))]
+
+
+@META_ARCH_REGISTRY.register()
+class SemanticSegmentor(_EngineOwner):
+    """[d2] SemanticSegmentor: backbone + SemSegFPNHead at inference. model(list[dict{image, height, width}]) ->
+    list[{"sem_seg": (NUM_CLASSES, height, width) fp32 logits}] in eval mode. Training mode, make_trainer(), trainer() and
+    losses_forward raise NotImplementedError naming the meta architecture."""
+    _prefix = ""
+    _engine_cls = PanopticFPNEngine
+    META_ARCH = "SemanticSegmentor"
+
+    def __init__(self, cfg: CfgNode, class_id: Optional[torch.Tensor] = None):
+        super().__init__()
+        self.TTA_MESSAGE = _refuse_sem_seg_extras(cfg, self.META_ARCH)
+        self.backbone = BACKBONE_REGISTRY.get(cfg.MODEL.BACKBONE.NAME)(cfg)
+        self.sem_seg_head = SemSegFPNHead(cfg, self.backbone.output_shape())
+        self.register_buffer("pixel_mean", torch.tensor(cfg.MODEL.PIXEL_MEAN).view(-1, 1, 1), False)
+        self.register_buffer("pixel_std", torch.tensor(cfg.MODEL.PIXEL_STD).view(-1, 1, 1), False)
+        self._eng_cfg = dict(pixel_mean=tuple(cfg.MODEL.PIXEL_MEAN), pixel_std=tuple(cfg.MODEL.PIXEL_STD), stride_in_1x1=bool(cfg.MODEL.RESNETS.STRIDE_IN_1X1),
+                             **deform_options_from(cfg), **sem_seg_engine_cfg_from(cfg))
+        self.num_classes = int(cfg.MODEL.SEM_SEG_HEAD.NUM_CLASSES)
+
+    @property
+    def device(self):
+        return self.pixel_mean.device
+
+    def engine(self) -> PanopticFPNEngine:
+        eng = super().engine()
+        self.backbone._shared = eng  # one packed copy of the weights for the whole model
+        return eng
+
+    def refresh(self):
+        super().refresh()
+        self.backbone._shared = None
+        self.backbone.refresh()
+
+    def forward(self, batched_inputs: List[dict]):
+        if self.training:
+            raise NotImplementedError(panoptic_training_message(self.META_ARCH))
+        return self.inference(batched_inputs)
+
+    def make_trainer(self, *a, **k):
+        raise NotImplementedError(panoptic_training_message(self.META_ARCH))
+
+    trainer = make_trainer
+
+    def losses_forward(self, *a, **k):
+        raise NotImplementedError(panoptic_training_message(self.META_ARCH))
+
+    @torch.no_grad()
+    def inference(self, batched_inputs: List[dict]):
+        eng = self.engine()
+        batch, sizes = GeneralizedRCNN._stack_images(self, [x["image"] for x in batched_inputs])
+        (logits,) = eng.forward(batch, sizes)
+        outs = [(int(inp.get("height", s[0])), int(inp.get("width", s[1]))) for inp, s in zip(batched_inputs, sizes)]
+        return [{"sem_seg": r} for r in _sem_seg_outputs(eng, logits, self.num_classes, sizes, outs)]
+
+
+@META_ARCH_REGISTRY.register()
+class PanopticFPN(GeneralizedRCNN):
+    """[d2] PanopticFPN (configs/panoptic_fpn.yaml): GeneralizedRCNN with StandardROIHeads (MASK_ON) plus SemSegFPNHead, at inference.
+    model(list[dict{image, height, width}]) -> list[{"sem_seg": (C, H, W) fp32 logits, "instances": Instances, "panoptic_seg":
+    ((H, W) int32, segments_info)}] in eval mode; "panoptic_seg" only with MODEL.PANOPTIC_FPN.COMBINE.ENABLED. segments_info is [d2]'s
+    list of dicts (things: id, isthing, score, category_id, instance_id; stuff: id, isthing, category_id, area). Training mode,
+    make_trainer(), trainer() and losses_forward raise NotImplementedError naming the meta architecture."""
+    META_ARCH = "PanopticFPN"
+
+    def __init__(self, cfg: CfgNode, class_id: Optional[torch.Tensor] = None):
+        tta_message = _refuse_sem_seg_extras(cfg, self.META_ARCH)
+        comb = cfg.MODEL.PANOPTIC_FPN.COMBINE
+        if cfg.MODEL.ROI_HEADS.NAME != "StandardROIHeads":
+            raise ValueError(f'MODEL.ROI_HEADS.NAME {cfg.MODEL.ROI_HEADS.NAME!r} with META_ARCHITECTURE "PanopticFPN": the HIP path combines the '
+                             'detections of "StandardROIHeads" only')
+        if comb.ENABLED and not cfg.MODEL.MASK_ON:
+            raise ValueError("MODEL.PANOPTIC_FPN.COMBINE.ENABLED needs MODEL.MASK_ON True: the panoptic map is painted from the instance masks")
+        super().__init__(cfg, class_id)
+        self.TTA_MESSAGE = tta_message
+        self.sem_seg_head = SemSegFPNHead(cfg, self.backbone.output_shape())
+        self._engine_cls = PanopticFPNEngine
+        self._eng_cfg.update(sem_seg_engine_cfg_from(cfg))
+        self._eng_cfg.update({k: v for k, v in self.roi_heads._eng_cfg.items() if k.startswith("mask_pooler_")})
+        self.combine_enabled = bool(comb.ENABLED)
+        self.sem_num_classes = int(cfg.MODEL.SEM_SEG_HEAD.NUM_CLASSES)
+
+    def forward(self, batched_inputs: List[dict]):
+        if self.training:
+            raise NotImplementedError(panoptic_training_message(self.META_ARCH))
+        return self.inference(batched_inputs)
+
+    def make_trainer(self, *a, **k):
+        raise NotImplementedError(panoptic_training_message(self.META_ARCH))
+
+    def trainer(self, *a, **k):
+        raise NotImplementedError(panoptic_training_message(self.META_ARCH))
+
+    def losses_forward(self, *a, **k):
+        raise NotImplementedError(panoptic_training_message(self.META_ARCH))
+
+    @torch.no_grad()
+    def inference(self, batched_inputs: List[dict], do_postprocess: bool = True):
+        """[d2] PanopticFPN.inference: the stock detector with its device postprocess (masks pasted at the requested size), the semantic
+        logits resampled from stride 4 by one kernel per image, and combine_semantic_and_instance_outputs on the device."""
+        eng = self.engine()
+        c = eng.cfg
+        batch, sizes = self._stack_images([x["image"] for x in batched_inputs])
+        res = eng.forward(batch, sizes)
+        dets, logits = res[:-1], res[-1]
+        outs = [(int(inp.get("height", s[0])), int(inp.get("width", s[1]))) if do_postprocess else s for inp, s in zip(batched_inputs, sizes)]
+        insts = [_std_instances(s, r) for r, s in zip(OpensetRCNNEngine.to_instances(dets, len(sizes)), sizes)]
+        insts = [detector_postprocess(r, o[0], o[1]) for r, o in zip(insts, outs)]
+        sem = _sem_seg_outputs(eng, logits, self.sem_num_classes, sizes, outs)
+        results = []
+        for i, (r, s, o) in enumerate(zip(insts, sizes, outs)):
+            out = {"sem_seg": sem[i], "instances": r}
+            if self.combine_enabled:
+                labels = ops.semseg_resample(logits[i], self.sem_num_classes, s, o, labels=True)
+                dev = labels.device
+                pan, table, scores, count = ops.panoptic_combine(r.pred_masks.contiguous(), r.scores.float().to(dev).contiguous(),
+                                                                 r.pred_classes.to(torch.int64).to(dev).contiguous(), labels, c["combine_overlap_thresh"],
+                                                                 c["combine_stuff_area_limit"], c["combine_instances_confidence_thresh"])
+                out["panoptic_seg"] = (pan, ops.segments_info_from_table(table, scores, count))
+            results.append(out)
+        return results
 
 
 def build_model(cfg: CfgNode, class_id: Optional[torch.Tensor] = None) -> nn.Module:

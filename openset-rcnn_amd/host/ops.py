@@ -1461,6 +1461,152 @@ def paste_masks(probs: torch.Tensor, boxes: torch.Tensor, out_h: int, out_w: int
     return out
 
 
+# ---- Panoptic FPN (csrc/osr_semseg.hip, csrc/osr_panoptic.hip; host/engine_panoptic.py) ----------------------------------------------
+GN_GROUPS = 32
+GN_EPS = 1e-5
+
+
+def _nhwc_float(x: torch.Tensor, name: str):
+    _need(x, None, name)
+    if x.dtype not in _DT:
+        raise OsrError(f"{name} must be float32 / float16 / bfloat16, got {x.dtype}")
+    if x.dim() != 4:
+        raise OsrError(f"{name} must be (n, h, w, c), got {tuple(x.shape)}")
+    return tuple(int(v) for v in x.shape)
+
+
+def group_norm_stats(x: torch.Tensor, eps: float = GN_EPS) -> Tuple[torch.Tensor, torch.Tensor]:
+    """GroupNorm(32) statistics of x (n, h, w, c) NHWC, c in {64, 128, 256} -> (mean, rstd), each (n, 32) fp32 (include/osr.h
+    osr_group_norm_stats: biased variance, rstd = 1 / sqrt(var + eps))."""
+    lib = _lib.load()
+    n, h, w, c = _nhwc_float(x, "x")
+    wsb = int(lib.osr_group_norm_stats_workspace_bytes(n, h, w, c))
+    if wsb < 0:
+        check(wsb, "osr_group_norm_stats")
+    ws = torch.empty((max(wsb, 16),), dtype=torch.uint8, device=x.device)
+    mean = torch.empty((n, GN_GROUPS), dtype=torch.float32, device=x.device)
+    rstd = torch.empty_like(mean)
+    check(lib.osr_group_norm_stats(_p(x), _DT[x.dtype], n, h, w, c, float(eps), _p(mean), _p(rstd), _p(ws), wsb, _stream()), "osr_group_norm_stats")
+    return mean, rstd
+
+
+def gn_relu_merge(terms: Sequence[tuple], out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """sum_t up_t(relu(gn_t(x_t))) in one launch (include/osr.h osr_gn_relu_merge). A term is (x, stats, gamma, beta, up2): x (n, h, w, c)
+    NHWC; stats = (mean, rstd) from group_norm_stats with gamma / beta (c) fp32, or None (gamma and beta then None too: the term is only
+    rectified); up2: bilinear x2 after the ReLU. Every term has the output's dtype and, after its up2, the output's size."""
+    lib = _lib.load()
+    if not 1 <= len(terms) <= _lib.GN_MAX_TERMS:
+        raise OsrError(f"gn_relu_merge: 1 .. {_lib.GN_MAX_TERMS} terms, got {len(terms)}")
+    arr = (_lib.GnTerm * len(terms))()
+    n0 = c0 = ho = wo = dt = None
+    for i, (x, stats, gamma, beta, up2) in enumerate(terms):
+        n, h, w, c = _nhwc_float(x, f"term {i}")
+        f = 2 if up2 else 1
+        if n0 is None:
+            n0, c0, ho, wo, dt = n, c, h * f, w * f, x.dtype
+        if (n, c, x.dtype) != (n0, c0, dt):
+            raise OsrError(f"gn_relu_merge: term {i} is {tuple(x.shape)} {x.dtype}; term 0 has n {n0}, c {c0}, {dt}")
+        arr[i].x, arr[i].h, arr[i].w, arr[i].up2 = x.data_ptr(), h, w, int(bool(up2))
+        if stats is not None:
+            mean, rstd = stats
+            for t, shape, nm in ((mean, (n, GN_GROUPS), "mean"), (rstd, (n, GN_GROUPS), "rstd"), (gamma, (c,), "gamma"), (beta, (c,), "beta")):
+                if t is None:
+                    raise OsrError(f"gn_relu_merge: term {i} has statistics but no {nm}")
+                _need(t, torch.float32, f"term {i} {nm}")
+                if tuple(t.shape) != shape:
+                    raise OsrError(f"gn_relu_merge: term {i} {nm} {tuple(t.shape)} != {shape}")
+            arr[i].mean, arr[i].rstd, arr[i].gamma, arr[i].beta = mean.data_ptr(), rstd.data_ptr(), gamma.data_ptr(), beta.data_ptr()
+        elif gamma is not None or beta is not None:
+            raise OsrError(f"gn_relu_merge: term {i} has gamma / beta but no statistics")
+    if out is None:
+        out = torch.empty((n0, ho, wo, c0), dtype=dt, device=terms[0][0].device)
+    else:
+        _need(out, dt, "out")
+        if tuple(out.shape) != (n0, ho, wo, c0):
+            raise OsrError(f"gn_relu_merge: out {tuple(out.shape)} != {(n0, ho, wo, c0)}")
+    check(lib.osr_gn_relu_merge(arr, len(terms), _DT[dt], n0, ho, wo, c0, _p(out), _stream()), "osr_gn_relu_merge")
+    return out
+
+
+def semseg_resample(logits: torch.Tensor, num_classes: int, crop_hw: Tuple[int, int], out_hw: Tuple[int, int], labels: bool,
+                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """[d2] sem_seg_postprocess (+ argmax) of ONE image from its stride-4 logits (h4, w4, pitch) (include/osr.h osr_semseg_resample):
+    bilinear x4, crop to crop_hw, bilinear resize to out_hw, composed. labels=True -> (oh, ow) int32 argmax over the first num_classes
+    channels; labels=False -> (num_classes, oh, ow) fp32."""
+    lib = _lib.load()
+    _need(logits, None, "logits")
+    if logits.dtype not in _DT or logits.dim() != 3:
+        raise OsrError(f"semseg_resample: logits must be (h4, w4, pitch) float32 / float16 / bfloat16, got {tuple(logits.shape)} {logits.dtype}")
+    h4, w4, pitch = (int(v) for v in logits.shape)
+    (ih, iw), (oh, ow) = (int(v) for v in crop_hw), (int(v) for v in out_hw)
+    shape, dt = ((oh, ow), torch.int32) if labels else ((int(num_classes), oh, ow), torch.float32)
+    if min(oh, ow, ih, iw, int(num_classes)) < 1:
+        raise OsrError(f"semseg_resample: crop {crop_hw}, output {out_hw}, {num_classes} classes")
+    if out is None:
+        out = torch.empty(shape, dtype=dt, device=logits.device)
+    else:
+        _need(out, dt, "out")
+        if tuple(out.shape) != shape:
+            raise OsrError(f"semseg_resample: out {tuple(out.shape)} != {shape}")
+    check(lib.osr_semseg_resample(_p(logits), _DT[logits.dtype], h4, w4, pitch, int(num_classes), ih, iw, oh, ow,
+                                  _lib.SEMSEG_LABELS if labels else _lib.SEMSEG_VALUES, _p(out), _stream()), "osr_semseg_resample")
+    return out
+
+
+def panoptic_combine(masks: torch.Tensor, scores: torch.Tensor, classes: torch.Tensor, labels: torch.Tensor, overlap_thresh: float,
+                     stuff_area_limit: int, instances_confidence_thresh: float, count: Optional[torch.Tensor] = None):
+    """[d2] combine_semantic_and_instance_outputs for ONE image on the device (include/osr.h osr_panoptic_combine). masks (k, H, W) bool /
+    uint8, scores (k) fp32, classes (k) int64, labels (H, W) int32, count (1) int32 or None (= k). -> (panoptic_seg (H, W) int32,
+    seg_table (k + 255, 4) int32, seg_scores (k + 255) fp32, seg_count (1) int32); segments_info_from_table turns the last three
+    into [d2]'s list of dicts."""
+    lib = _lib.load()
+    _need(masks, None, "masks"); _need(scores, torch.float32, "scores"); _need(classes, torch.int64, "classes"); _need(labels, torch.int32, "labels")
+    if masks.dtype not in (torch.bool, torch.uint8):
+        raise OsrError(f"panoptic_combine: masks must be bool or uint8, got {masks.dtype}")
+    if labels.dim() != 2 or masks.dim() != 3 or tuple(masks.shape[1:]) != tuple(labels.shape):
+        raise OsrError(f"panoptic_combine: masks {tuple(masks.shape)} / labels {tuple(labels.shape)}: (k, H, W) and (H, W)")
+    k, h, w = (int(v) for v in masks.shape)
+    if k > _lib.PANOPTIC_MAX_INSTANCES:
+        raise OsrError(f"panoptic_combine: at most {_lib.PANOPTIC_MAX_INSTANCES} instances per image, got {k}")
+    if scores.numel() != k or classes.numel() != k:
+        raise OsrError(f"panoptic_combine: {scores.numel()} scores and {classes.numel()} classes for {k} masks")
+    if count is not None:
+        _need(count, torch.int32, "count")
+    wsb = int(lib.osr_panoptic_combine_workspace_bytes(k, h, w))
+    if wsb < 0:
+        check(wsb, "osr_panoptic_combine")
+    dev = labels.device
+    ws = torch.empty((wsb,), dtype=torch.uint8, device=dev)
+    cap = k + _lib.PANOPTIC_MAX_STUFF
+    pan = torch.empty((h, w), dtype=torch.int32, device=dev)
+    table = torch.zeros((cap, 4), dtype=torch.int32, device=dev)
+    sscores = torch.zeros((cap,), dtype=torch.float32, device=dev)
+    scount = torch.zeros((1,), dtype=torch.int32, device=dev)
+    check(lib.osr_panoptic_combine(_p(masks), _p(scores), _p(classes), _p(count), k, _p(labels), h, w, float(overlap_thresh), int(stuff_area_limit),
+                                   float(instances_confidence_thresh), _p(pan), _p(table), _p(sscores), _p(scount), _p(ws), wsb, _stream()),
+          "osr_panoptic_combine")
+    return pan, table, sscores, scount
+
+
+def segments_info_from_table(table: torch.Tensor, seg_scores: torch.Tensor, seg_count: torch.Tensor) -> List[dict]:
+    """panoptic_combine's table -> [d2]'s segments_info, with ONE device-to-host copy (the three tensors are packed first).
+    Things: {id, isthing True, score, category_id, instance_id}; stuff: {id, isthing False, category_id, area}."""
+    rows = table.shape[0]
+    packed = torch.cat((seg_count.reshape(1).to(torch.int32), table.reshape(-1).to(torch.int32), seg_scores.reshape(-1).view(torch.int32)))
+    host = packed.cpu()
+    cnt = int(host[0])
+    tab = host[1:1 + rows * 4].view(rows, 4).tolist()
+    sc = host[1 + rows * 4:].view(torch.float32).tolist()
+    out = []
+    for r in range(min(cnt, rows)):
+        isthing, cat, inst, area = tab[r]
+        if isthing:
+            out.append({"id": r + 1, "isthing": True, "score": sc[r], "category_id": cat, "instance_id": inst})
+        else:
+            out.append({"id": r + 1, "isthing": False, "category_id": cat, "area": area})
+    return out
+
+
 # ---- test-time augmentation glue (csrc/osr_tta.hip; host/tta.py) ---------------------------------------------------------------
 def _tta_lists(boxes, counts, sizes, name):
     _need(boxes, torch.float32, "boxes"); _need(counts, torch.int32, "counts"); _need(sizes, torch.int32, "sizes")

@@ -44,9 +44,11 @@ class GeneralizedRCNNWithTTA(nn.Module):
 
     def __init__(self, cfg, model):
         super().__init__()
-        from .modeling import CascadeROIHeads, GeneralizedRCNN, RetinaNet, StandardROIHeads
+        from .modeling import CascadeROIHeads, GeneralizedRCNN, PanopticFPN, RetinaNet, SemanticSegmentor, StandardROIHeads
         if isinstance(model, RetinaNet):
             raise ValueError(RetinaNet.TTA_MESSAGE)
+        if isinstance(model, (PanopticFPN, SemanticSegmentor)):
+            raise ValueError(model.TTA_MESSAGE)
         if isinstance(getattr(model, "roi_heads", None), CascadeROIHeads):
             raise ValueError("TEST.AUG: test-time augmentation is not implemented for CascadeROIHeads (the merge re-scores the augmented boxes with "
                              "one box head; a cascade has one per stage)")

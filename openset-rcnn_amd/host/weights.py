@@ -21,6 +21,8 @@ def fold_frozen_bn(state: Dict[str, torch.Tensor], eps: float = 1e-5) -> Dict[st
     for k in list(state.keys()):
         if k.endswith(".norm.weight"):
             pre = k[: -len(".norm.weight")]
+            if pre + ".norm.running_mean" not in state:
+                continue  # (a GroupNorm: sem_seg_head.*.norm has no running statistics and is not folded)
             w, b = state[pre + ".norm.weight"], state[pre + ".norm.bias"]
             mean, var = state[pre + ".norm.running_mean"], state[pre + ".norm.running_var"]
             scale = w * (var + eps).rsqrt()
@@ -265,4 +267,46 @@ def random_retinanet_params(seed: int = 0, num_classes: int = 80, num_anchors: i
             conv(f"head.{sub}.{2 * i}", 256, 256, math.sqrt(2.0 / (256 * 9)))
     conv("head.cls_score", num_anchors * num_classes, 256, 0.02, bias=cls_bias, bias_std=0.0)
     conv("head.bbox_pred", num_anchors * 4, 256, 0.004, bias_std=0.0)
+    return p
+
+
+SEM_SEG_FEATURES = (("p2", 4), ("p3", 8), ("p4", 16), ("p5", 32))
+
+
+def sem_seg_head_lengths(common_stride: int = 4) -> Dict[str, int]:
+    """[d2] SemSegFPNHead: head_length = max(1, log2(stride) - log2(COMMON_STRIDE)) 3x3 convolutions per input feature."""
+    return {f: max(1, int(math.log2(s)) - int(math.log2(common_stride))) for f, s in SEM_SEG_FEATURES}
+
+
+def random_panoptic_params(seed: int = 0, num_classes: int = 80, sem_classes: int = 54, convs_dim: int = 128, norm: str = "GN", mask_conv: int = 4,
+                           predictor_gain: float = 1.0, rcnn: bool = True) -> Dict[str, torch.Tensor]:
+    """Seeded synthetic parameters for META_ARCHITECTURE "PanopticFPN" (rcnn=False: "SemanticSegmentor", the backbone and the semantic
+    head only): random_standard_params' detector, He-style MaskRCNNConvUpsampleHead parameters (class-agnostic predictor) and [d2]
+    SemSegFPNHead under its names -- sem_seg_head.<feat>.<2k>.weight, with `.norm.weight` / `.norm.bias` (NORM "GN": no conv bias) or
+    `.bias` (NORM ""), and sem_seg_head.predictor -- with affine parameters away from (1, 0) and a predictor whose logits spread."""
+    base = random_standard_params(seed, num_classes=num_classes)
+    p = dict(base) if rcnn else {k: v for k, v in base.items() if k.startswith("backbone.")}
+    g = torch.Generator().manual_seed(seed + 5000)
+    if rcnn:
+        pre, cin = "roi_heads.mask_head.", 256
+        for i in range(1, mask_conv + 1):
+            p[f"{pre}mask_fcn{i}.weight"] = torch.randn(256, cin, 3, 3, generator=g) * math.sqrt(2.0 / (cin * 9))
+            p[f"{pre}mask_fcn{i}.bias"] = torch.randn(256, generator=g) * 0.02
+        p[pre + "deconv.weight"] = torch.randn(256, 256, 2, 2, generator=g) * math.sqrt(2.0 / 256)
+        p[pre + "deconv.bias"] = torch.randn(256, generator=g) * 0.02
+        p[pre + "predictor.weight"] = torch.randn(1, 256, 1, 1, generator=g) * 0.5
+        p[pre + "predictor.bias"] = torch.zeros(1)
+    for feat, length in sem_seg_head_lengths().items():
+        cin = 256
+        for k in range(length):
+            name = f"sem_seg_head.{feat}.{2 * k}"
+            p[name + ".weight"] = torch.randn(convs_dim, cin, 3, 3, generator=g) * math.sqrt(2.0 / (cin * 9))
+            if norm == "GN":
+                p[name + ".norm.weight"] = 1.0 + 0.2 * torch.randn(convs_dim, generator=g)
+                p[name + ".norm.bias"] = 0.2 * torch.randn(convs_dim, generator=g)
+            else:
+                p[name + ".bias"] = torch.randn(convs_dim, generator=g) * 0.05
+            cin = convs_dim
+    p["sem_seg_head.predictor.weight"] = torch.randn(sem_classes, convs_dim, 1, 1, generator=g) * (predictor_gain / math.sqrt(convs_dim))
+    p["sem_seg_head.predictor.bias"] = torch.randn(sem_classes, generator=g) * 0.1
     return p
