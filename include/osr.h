@@ -838,6 +838,57 @@ osr_status osr_panoptic_combine(const uint8_t* masks, const float* scores, const
                                 float instances_confidence_thresh, int32_t* panoptic_seg, int32_t* seg_table, float* seg_scores,
                                 int32_t* seg_count, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * Scoring what the two models above produce: the pixel passes of [d2] SemSegEvaluator (mIoU) and of panopticapi's
+ * pq_compute_single_core (PQ), csrc/osr_seg_eval.hip. Neither detectron2 nor panopticapi is at hand: the rules are written from
+ * memory of detectron2 v0.6 and panopticapi, and THIS TEXT is the contract the tests check. Common to the three: integer arithmetic
+ * and integer atomics only (no float atomics), repeats give identical bits, nothing syncs with the host, every function is
+ * capturable, every argument is validated before anything is launched (no GPU needed for a refusal), h * w <= 2^30.
+ *
+ * osr_semseg_confusion: ONE image, one launch. Adds the image into conf (C + 1, C + 1) int64, indexed [pred][gt]; conf is
+ * accumulated in place and never zeroed by the call. 1 <= C <= 255. mode OSR_CONF_LABELS: pred (h, w) int32 (what
+ * osr_semseg_resample's label mode gives). mode OSR_CONF_VALUES: pred (C, h, w) fp32 (the models' "sem_seg"); the argmax is fused,
+ * with osr_semseg_resample's rule (strict comparisons from class 0 up: the lowest class wins a tie, NaN never wins). gt (h, w)
+ * uint8; a value equal to ignore_value goes to column C. A ground-truth value in [C, 255] other than ignore_value, or a predicted
+ * label outside [0, C), is not counted in conf: each such pixel adds 1 to invalid[0], a device int64 also accumulated in place.
+ * The grid is sized by the CUs; per workgroup an LDS histogram for C <= 126, above that per-thread runs of equal (pred, gt)
+ * flushed with 64-bit integer atomics.
+ *
+ * osr_panoptic_pair_counts: ONE image; panopticapi's np.unique(gt * OFFSET + pred, return_counts=True). gt_rgb (h, w, 3) uint8,
+ * the ground-truth PNG as decoded: segment id = R + 256 G + 65536 B. gt_ids (num_gt) int32, strictly ascending: the ids of the
+ * image's segments_info. pred (h, w) int32: ids 0 .. num_pred, 0 = VOID. counts (num_gt + 2, num_pred + 1) int32, zeroed by the
+ * call: row 0 is ground-truth id 0 (VOID), row 1 + i is gt_ids[i], row num_gt + 1 every other id ("unlisted"); the column is the
+ * predicted id. A predicted id outside 0 .. num_pred is not counted and adds 1 to flags[0] (device int64, accumulated in place).
+ * The id decode and the search in gt_ids run on the device, the search once per run of equal ids. 0 <= num_gt <= 1023,
+ * 0 <= num_pred <= 2047; beyond either: OSR_ERR_UNSUPPORTED, nothing launched.
+ *
+ * osr_pq_accumulate: ONE image, one workgroup. Adds the image's matches into the running per-category statistics pq_counts
+ * (num_categories, 3) int64 {tp, fp, fn} and pq_iou (num_categories) float64, both accumulated in place. counts: as written by
+ * osr_panoptic_pair_counts. gt_meta (num_gt, 4) int32 {category slot, iscrowd, area as the JSON states it, crowd_pick};
+ * crowd_pick marks the LAST crowd segment of its category in the JSON's segments_info order (panopticapi's crowd_labels_dict
+ * overwrites), at most one row per slot. pred_slot (num_pred) int32: the category slot of predicted id p + 1.
+ *   - the area of predicted id p is its column sum (counted from the map; VOID and unlisted rows included);
+ *   - for every row g in 1 .. num_gt and column p in 1 .. num_pred with counts[g][p] > 0, ground truth not crowd and equal slots:
+ *     union = area_p + area_g - inter - counts[0][p]; iou = (double)inter / (double)union; iou > 0.5 (strictly): tp += 1 and
+ *     pq_iou += iou for the slot, both sides are matched. Pairs are tested independently of each other;
+ *   - every unmatched ground-truth row that is not crowd adds fn for its slot;
+ *   - every unmatched predicted id adds fp for its slot, unless (double)(counts[0][p] + counts[row of the slot's crowd_pick, if
+ *     any][p]) / area_p > 0.5 (strictly);
+ *   - row num_gt + 1 takes part in nothing but the areas.
+ * The adds to pq_iou[slot] happen in ascending (g, p) order onto the running sum: the result is bit-equal to a float64 reference
+ * that adds in (image, gt id, pred id) order. What the reference raises on becomes a counter: flags[1] += predicted ids with a
+ * valid slot and area 0, flags[2] += predicted ids (and ground-truth rows) whose slot is outside [0, num_categories); such an id
+ * or row counts as nothing else. Same limits on num_gt / num_pred as above; num_categories >= 1.
+ * --------------------------------------------------------------------------------------------------------- */
+#define OSR_CONF_LABELS 0
+#define OSR_CONF_VALUES 1
+osr_status osr_semseg_confusion(const void* pred, int32_t mode, const uint8_t* gt, int32_t h, int32_t w, int32_t num_classes,
+                                int32_t ignore_value, int64_t* conf, int64_t* invalid, void* stream);
+osr_status osr_panoptic_pair_counts(const uint8_t* gt_rgb, const int32_t* gt_ids, int32_t num_gt, const int32_t* pred, int32_t num_pred,
+                                    int32_t h, int32_t w, int32_t* counts, int64_t* flags, void* stream);
+osr_status osr_pq_accumulate(const int32_t* counts, int32_t num_gt, int32_t num_pred, const int32_t* gt_meta, const int32_t* pred_slot,
+                             int32_t num_categories, int64_t* pq_counts, double* pq_iou, int64_t* flags, void* stream);
+
 /* =========================================================================================================
  * Training step, forward half: targets and losses. Gradients are not
  * produced by this library yet; every function below is a forward kernel whose outputs equal the reference's

@@ -34,6 +34,7 @@ SOURCES = {
     "osr_retinanet.hip": ["-ffp-contract=off"],  # (decodes like osr_rpn.hip's decode_mode 1)
     "osr_semseg.hip": [],
     "osr_panoptic.hip": [],
+    "osr_seg_eval.hip": [],
     "osr_roi_align.hip": ["-ffp-contract=off"],
     "osr_det_tail.hip": ["-ffp-contract=off"],
     "osr_cascade.hip": ["-ffp-contract=off"],  # (decodes and matches like osr_det_tail.hip / osr_std_train.hip)

@@ -104,6 +104,8 @@ GN_MAX_TERMS = 4
 SEMSEG_LABELS, SEMSEG_VALUES = 0, 1
 PANOPTIC_MAX_INSTANCES = 1024  # csrc/osr_panoptic.hip PC_MAX_K
 PANOPTIC_MAX_STUFF = 255       # labels 1 .. 255
+CONF_LABELS, CONF_VALUES = 0, 1
+PQ_MAX_GT, PQ_MAX_PRED = 1023, 2047  # csrc/osr_seg_eval.hip PP_MAX_G / PP_MAX_P
 
 
 class Pyramid(C.Structure):
@@ -171,6 +173,10 @@ PROTOTYPES = {
     "osr_semseg_resample": (I32, [P, I32, I32, I32, I32, I32, I32, I32, I32, I32, I32, P, P]),
     "osr_panoptic_combine_workspace_bytes": (I64, [I32, I32, I32]),
     "osr_panoptic_combine": (I32, [P, P, P, P, I32, P, I32, I32, F32, I32, F32, P, P, P, P, P, I64, P]),
+    # segmentation evaluators (csrc/osr_seg_eval.hip)
+    "osr_semseg_confusion": (I32, [P, I32, P, I32, I32, I32, I32, P, P, P]),
+    "osr_panoptic_pair_counts": (I32, [P, P, I32, P, I32, I32, I32, P, P, P]),
+    "osr_pq_accumulate": (I32, [P, I32, I32, P, P, I32, P, P, P, P]),
     "osr_fastrcnn_candidates": (I32, [P, P, I32, I32, P, P, I32, I32, P, P, F32, P, P, P, P, P, P]),
     "osr_cascade_refine": (I32, [P, P, P, I32, I32, P, P, I32, P, P, P, I32, I32, F32, P, P, P, P, P, P, P]),
     "osr_cascade_candidates": (I32, [P, I32, P, I32, P, P, I32, I32, P, P, F32, P, P, P, P, P, P]),

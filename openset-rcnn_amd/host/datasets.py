@@ -155,10 +155,107 @@ def graspnet_class_map(thing_classes: Sequence[str]):
     return torch.tensor(sorted(thing_classes.index(n) for n in GRASPNET_KNOWN_CATEGORIES if n in thing_classes), dtype=torch.int64)
 
 
+# ---------------------------------------------------------------------------------------------------------------
+# Semantic and panoptic segmentation datasets ([d2] data/datasets/coco.py load_sem_seg, coco_panoptic.py
+# register_coco_panoptic_separated, builtin.py register_all_coco; written from memory of detectron2 v0.6)
+# ---------------------------------------------------------------------------------------------------------------
+def _files_by_stem(root: str, ext: str) -> Dict[str, str]:
+    out = {}
+    for base, _, files in os.walk(root):
+        for f in files:
+            if f.lower().endswith(ext):
+                full = os.path.join(base, f)
+                out[os.path.splitext(os.path.relpath(full, root))[0]] = full
+    return out
+
+
+def load_sem_seg(gt_root: str, image_root: str, gt_ext: str = ".png", image_ext: str = ".jpg") -> List[dict]:
+    """[d2] load_sem_seg: one dict {file_name, sem_seg_file_name} per image, the two directories paired by relative path without
+    the extension; a file without its partner is left out, the rest is sorted by path."""
+    images, gts = _files_by_stem(image_root, image_ext), _files_by_stem(gt_root, gt_ext)
+    return [dict(file_name=images[k], sem_seg_file_name=gts[k]) for k in sorted(set(images) & set(gts))]
+
+
+def register_sem_seg(name: str, gt_root: str, image_root: str, stuff_classes: Sequence[str], ignore_label: int = 255) -> None:
+    DatasetCatalog.register(name, lambda: load_sem_seg(gt_root, image_root))
+    meta = MetadataCatalog.get(name)
+    meta.sem_seg_root, meta.image_root, meta.stuff_classes, meta.ignore_label = gt_root, image_root, list(stuff_classes), int(ignore_label)
+    meta.evaluator_type = "sem_seg"
+
+
+def panoptic_separated_tables(categories: Sequence[dict]) -> dict:
+    """The metadata tables of detectron2's "separated" panoptic format from a panoptic JSON's `categories` ({id, name, isthing}):
+    things get contiguous ids 0 .. in ascending dataset id; stuff contiguous id 0 is "things" (every thing pixel of the semantic
+    ground truth; dataset id 0) and the stuff categories follow from 1 in ascending dataset id."""
+    cats = sorted(categories, key=lambda c: c["id"])
+    things, stuff = [c for c in cats if c["isthing"]], [c for c in cats if not c["isthing"]]
+    return dict(thing_classes=[c["name"] for c in things], stuff_classes=["things"] + [c["name"] for c in stuff],
+                thing_dataset_id_to_contiguous_id={c["id"]: i for i, c in enumerate(things)},
+                stuff_dataset_id_to_contiguous_id={0: 0, **{c["id"]: i + 1 for i, c in enumerate(stuff)}})
+
+
+def _read_json(path: str):
+    import json
+    with open(path) as f:
+        return json.load(f)
+
+
+def load_coco_panoptic_separated(name: str) -> List[dict]:
+    """load_coco_json's dicts of the instances JSON plus sem_seg_file_name, pan_seg_file_name and segments_info (the panoptic
+    JSON's, category ids made contiguous through the thing / stuff tables, with `isthing`)."""
+    meta = MetadataCatalog.get(name)
+    pan = {a["image_id"]: a for a in _read_json(meta.panoptic_json)["annotations"]}
+    thing, stuff = meta.thing_dataset_id_to_contiguous_id, meta.stuff_dataset_id_to_contiguous_id
+    out = []
+    for rec in load_coco_json(meta.json_file, meta.image_root):
+        a = pan[rec["image_id"]]
+        rec["pan_seg_file_name"] = os.path.join(meta.panoptic_root, a["file_name"])
+        rec["sem_seg_file_name"] = os.path.join(meta.sem_seg_root, os.path.splitext(os.path.basename(rec["file_name"]))[0] + ".png")
+        rec["segments_info"] = [dict(s, isthing=s["category_id"] in thing, category_id=thing[s["category_id"]] if s["category_id"] in thing
+                                     else stuff[s["category_id"]]) for s in a["segments_info"]]
+        out.append(rec)
+    return out
+
+
+def register_coco_panoptic_separated(name: str, image_root: str, panoptic_root: str, panoptic_json: str, sem_seg_root: str, instances_json: str) -> None:
+    """[d2] register_coco_panoptic_separated: the instances JSON for the detector, <sem_seg_root>/<image>.png for the semantic head
+    (stuff ids as in panoptic_separated_tables, 255 = ignore), the panoptic PNGs + JSON for PQ. Reads the panoptic JSON's categories."""
+    DatasetCatalog.register(name, lambda: load_coco_panoptic_separated(name))
+    meta = MetadataCatalog.get(name)
+    for k, v in panoptic_separated_tables(_read_json(panoptic_json)["categories"]).items():
+        setattr(meta, k, v)
+    meta.image_root, meta.panoptic_root, meta.panoptic_json, meta.sem_seg_root, meta.json_file = image_root, panoptic_root, panoptic_json, sem_seg_root, instances_json
+    meta.ignore_label, meta.evaluator_type = 255, "coco_panoptic_seg"
+
+
+def register_coco_panoptic(root: str) -> None:
+    """coco_2017_{train,val}_panoptic_separated under detectron2's directory names, when the files exist:
+    coco/{train,val}2017, coco/panoptic_{split}2017, coco/annotations/panoptic_{split}2017.json, coco/panoptic_stuff_{split}2017,
+    coco/annotations/instances_{split}2017.json."""
+    coco = os.path.join(root, "coco")
+    for split in ("train", "val"):
+        pj, ij = os.path.join(coco, "annotations", f"panoptic_{split}2017.json"), os.path.join(coco, "annotations", f"instances_{split}2017.json")
+        if os.path.isfile(pj) and os.path.isfile(ij):
+            register_coco_panoptic_separated(f"coco_2017_{split}_panoptic_separated", os.path.join(coco, f"{split}2017"), os.path.join(coco, f"panoptic_{split}2017"),
+                                             pj, os.path.join(coco, f"panoptic_stuff_{split}2017"), ij)
+
+
 def get_evaluator(cfg, dataset_name: str, output_folder=None):
-    """train.py:57-78: "pascal_voc" -> open-set VOC evaluator, "coco" -> open-set COCO-style evaluator (GraspNet)."""
+    """train.py:57-78: "pascal_voc" -> open-set VOC evaluator, "coco" -> open-set COCO-style evaluator (GraspNet); [d2] train_net.py:
+    "sem_seg" -> SemSegEvaluator, "coco_panoptic_seg" -> SemSegEvaluator + COCOPanopticEvaluator (box / mask AP for these datasets
+    is not built: there is no pycocotools)."""
     from .evaluation import PascalVOCDetectionEvaluator
     meta = MetadataCatalog.get(dataset_name)
+    if getattr(meta, "evaluator_type", None) in ("sem_seg", "coco_panoptic_seg"):
+        from .evaluation import DatasetEvaluators
+        from .seg_evaluation import COCOPanopticEvaluator, SemSegEvaluator
+        sem = SemSegEvaluator(dataset_name, len(meta.stuff_classes), meta.ignore_label, meta.stuff_classes, output_folder)
+        if meta.evaluator_type == "sem_seg":
+            return sem
+        evaluators = [sem]
+        if cfg.MODEL.PANOPTIC_FPN.COMBINE.ENABLED:
+            evaluators.append(COCOPanopticEvaluator(dataset_name, output_folder))
+        return DatasetEvaluators(evaluators)
     if getattr(meta, "evaluator_type", None) == "coco":
         from .os_coco_evaluation import OpensetCOCOEvaluator
         if not hasattr(meta, "thing_dataset_id_to_contiguous_id"):

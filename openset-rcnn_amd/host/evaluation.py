@@ -208,6 +208,34 @@ class PascalVOCDetectionEvaluator:
         return {key: round(float(v), 2) for key, v in res.items()}
 
 
+class DatasetEvaluators:
+    """[d2] DatasetEvaluators: several evaluators fed with the same inputs and outputs; evaluate() merges their result dicts (rank 0;
+    None on the other ranks, where every member returns None)."""
+
+    def __init__(self, evaluators: Sequence):
+        self._evaluators = list(evaluators)
+
+    def reset(self) -> None:
+        for e in self._evaluators:
+            e.reset()
+
+    def process(self, inputs, outputs) -> None:
+        for e in self._evaluators:
+            e.process(inputs, outputs)
+
+    def evaluate(self) -> Optional[dict]:
+        results = None
+        for e in self._evaluators:
+            res = e.evaluate()
+            if res is None:
+                continue
+            results = {} if results is None else results
+            for k, v in res.items():
+                assert k not in results, f"two evaluators report '{k}'"
+                results[k] = v
+        return results
+
+
 def inference_on_dataset(model, batches, evaluator, rank: Optional[int] = None, world: Optional[int] = None):
     """[d2] inference_on_dataset as train.py:96 drives it: every rank runs the model over its share of the batches and feeds
     the evaluator; evaluate() gathers on rank 0 (None elsewhere). `batches` is a sequence of list[dict] inputs (each dict with

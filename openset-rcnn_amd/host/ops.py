@@ -1607,6 +1607,66 @@ def segments_info_from_table(table: torch.Tensor, seg_scores: torch.Tensor, seg_
     return out
 
 
+# ---- segmentation evaluators (csrc/osr_seg_eval.hip; host/seg_evaluation.py) -----------------------------------------------------------
+def semseg_confusion(pred: torch.Tensor, gt: torch.Tensor, num_classes: int, ignore_value: int, conf: torch.Tensor, invalid: torch.Tensor) -> None:
+    """ONE image added into the running confusion matrix (include/osr.h osr_semseg_confusion). pred (H, W) int32 labels or
+    (num_classes, H, W) fp32 values (the argmax is fused: lowest class on a tie); gt (H, W) uint8; conf (num_classes + 1,
+    num_classes + 1) int64 indexed [pred][gt], column num_classes = ignore_value; invalid (1) int64. Both accumulate in place."""
+    lib = _lib.load()
+    _need(pred, None, "pred"); _need(gt, torch.uint8, "gt"); _need(conf, torch.int64, "conf"); _need(invalid, torch.int64, "invalid")
+    c = int(num_classes)
+    if pred.dtype == torch.int32 and pred.dim() == 2:
+        mode, hw = _lib.CONF_LABELS, tuple(pred.shape)
+    elif pred.dtype == torch.float32 and pred.dim() == 3 and pred.shape[0] == c:
+        mode, hw = _lib.CONF_VALUES, tuple(pred.shape[1:])
+    else:
+        raise OsrError(f"semseg_confusion: pred must be (H, W) int32 or ({c}, H, W) float32, got {tuple(pred.shape)} {pred.dtype}")
+    if tuple(gt.shape) != hw:
+        raise OsrError(f"semseg_confusion: gt {tuple(gt.shape)} != prediction {hw}")
+    if tuple(conf.shape) != (c + 1, c + 1) or invalid.numel() < 1:
+        raise OsrError(f"semseg_confusion: conf {tuple(conf.shape)} must be {(c + 1, c + 1)}, invalid (1)")
+    check(lib.osr_semseg_confusion(_p(pred), mode, _p(gt), int(hw[0]), int(hw[1]), c, int(ignore_value), _p(conf), _p(invalid), _stream()),
+          "osr_semseg_confusion")
+
+
+def panoptic_pair_counts(gt_rgb: torch.Tensor, gt_ids: torch.Tensor, pred: torch.Tensor, num_pred: int, flags: torch.Tensor,
+                         out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ONE image's (ground-truth segment, predicted segment) pixel counts (include/osr.h osr_panoptic_pair_counts). gt_rgb (H, W, 3)
+    uint8, the panoptic PNG as decoded; gt_ids (G) int32 strictly ascending; pred (H, W) int32 with ids 0 .. num_pred; flags (3)
+    int64, accumulated. -> counts (G + 2, num_pred + 1) int32: row 0 VOID, 1 + i gt_ids[i], G + 1 unlisted ids."""
+    lib = _lib.load()
+    _need(gt_rgb, torch.uint8, "gt_rgb"); _need(gt_ids, torch.int32, "gt_ids"); _need(pred, torch.int32, "pred"); _need(flags, torch.int64, "flags")
+    if pred.dim() != 2 or tuple(gt_rgb.shape) != tuple(pred.shape) + (3,) or gt_ids.dim() != 1 or flags.numel() < 3:
+        raise OsrError(f"panoptic_pair_counts: gt_rgb {tuple(gt_rgb.shape)}, pred {tuple(pred.shape)}, gt_ids {tuple(gt_ids.shape)}: (H, W, 3), (H, W), (G); flags (3)")
+    g, p = int(gt_ids.numel()), int(num_pred)
+    h, w = (int(v) for v in pred.shape)
+    if out is None:
+        out = torch.empty((max(g, 0) + 2, max(p, 0) + 1), dtype=torch.int32, device=pred.device)
+    else:
+        _need(out, torch.int32, "out")
+        if tuple(out.shape) != (g + 2, p + 1):
+            raise OsrError(f"panoptic_pair_counts: out {tuple(out.shape)} != {(g + 2, p + 1)}")
+    check(lib.osr_panoptic_pair_counts(_p(gt_rgb), _p(gt_ids) if g else None, g, _p(pred), p, h, w, _p(out), _p(flags), _stream()), "osr_panoptic_pair_counts")
+    return out
+
+
+def pq_accumulate(counts: torch.Tensor, gt_meta: torch.Tensor, pred_slot: torch.Tensor, pq_counts: torch.Tensor, pq_iou: torch.Tensor,
+                  flags: torch.Tensor) -> None:
+    """ONE image's matches added into the running PQ statistics (include/osr.h osr_pq_accumulate). counts (G + 2, P + 1) int32 from
+    panoptic_pair_counts; gt_meta (G, 4) int32 {slot, iscrowd, area, crowd_pick}; pred_slot (P) int32; pq_counts (ncat, 3) int64
+    {tp, fp, fn}, pq_iou (ncat) float64, flags (3) int64: all accumulated in place."""
+    lib = _lib.load()
+    _need(counts, torch.int32, "counts"); _need(gt_meta, torch.int32, "gt_meta"); _need(pred_slot, torch.int32, "pred_slot")
+    _need(pq_counts, torch.int64, "pq_counts"); _need(pq_iou, torch.float64, "pq_iou"); _need(flags, torch.int64, "flags")
+    g, p = int(gt_meta.shape[0]), int(pred_slot.numel())
+    ncat = int(pq_iou.numel())
+    if counts.dim() != 2 or tuple(counts.shape) != (g + 2, p + 1) or tuple(gt_meta.shape) != (g, 4) or tuple(pq_counts.shape) != (ncat, 3) or flags.numel() < 3:
+        raise OsrError(f"pq_accumulate: counts {tuple(counts.shape)} must be {(g + 2, p + 1)}, gt_meta {tuple(gt_meta.shape)} (G, 4), "
+                       f"pq_counts {tuple(pq_counts.shape)} ({ncat}, 3), flags (3)")
+    check(lib.osr_pq_accumulate(_p(counts), g, p, _p(gt_meta) if g else None, _p(pred_slot) if p else None, ncat, _p(pq_counts), _p(pq_iou), _p(flags),
+                                _stream()), "osr_pq_accumulate")
+
+
 # ---- test-time augmentation glue (csrc/osr_tta.hip; host/tta.py) ---------------------------------------------------------------
 def _tta_lists(boxes, counts, sizes, name):
     _need(boxes, torch.float32, "boxes"); _need(counts, torch.int32, "counts"); _need(sizes, torch.int32, "sizes")

@@ -96,6 +96,7 @@ def register_datasets(cfg):
     D.register_graspnet_os(root)
     D.register_opendet_voc_coco(root)
     D.register_builtin_pascal_voc(root)
+    D.register_coco_panoptic(root)
     return D
 
 
@@ -138,7 +139,11 @@ def do_test(cfg, args, model, D, iteration: int = 0):
         if res is not None:
             logger.info("Evaluation results for %s:", name)
             flat = res.get("bbox", res) if isinstance(res, dict) else res
-            logger.info("  %s", ", ".join(f"{k}={v}" for k, v in flat.items()))
+            if flat and all(isinstance(v, dict) for v in flat.values()):  # one line per task (sem_seg, panoptic_seg)
+                for task, figures in flat.items():
+                    logger.info("  %s: %s", task, ", ".join(f"{k}={v:.4f}" for k, v in figures.items()))
+            else:
+                logger.info("  %s", ", ".join(f"{k}={v}" for k, v in flat.items()))
     return list(results.values())[0] if len(results) == 1 else results
 
 
