@@ -665,6 +665,38 @@ osr_status osr_paste_masks(const float* probs, const float* boxes, int64_t r, in
                            float threshold, uint8_t* out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * Keypoint branch ([d2] KRCNNConvDeconvUpsampleHead's tail and heatmaps_to_keypoints; csrc/osr_keypoint.hip). detectron2 is not at
+ * hand: the semantics are stated here and are the contract.
+ *
+ * osr_keypoint_upsample: x (r, s, s, cin) NHWC in `dtype` (the output of the last conv_fcn). One launch computes
+ *   low[r, j, oy, ox] = bias[j] + sum over c, ky, kx of x[r, iy, ix, c] * w[c, j, ky, kx]   over the taps with oy = 2 iy - 1 + ky,
+ *   ox = 2 ix - 1 + kx, 0 <= iy, ix < s  (ConvTranspose2d(cin -> k, 4 x 4, stride 2, padding 1): a 2s x 2s map),
+ * then bilinear x2 with align_corners = false (source (d + 0.5) / 2 - 0.5 clamped below at 0, second tap min(i0 + 1, 2s - 1)):
+ * heatmaps (r, k, 4s, 4s) fp32. The 2s x 2s map stays on chip in fp32; the contraction runs on the MFMA with k padded to 32.
+ * w_packed: the score_lowres weight (cin, k, 4, 4) in `dtype`, in MFMA fragment order (host/weights.py
+ *   pack_keypoint_deconv_weight): with E = 8 (f16 / bf16) or 4 (f32), element [ky * 4 + kx][c / 2E][(c / E) % 2][j (32)][c % E] =
+ *   w[c][j][ky][kx], zeros for j >= k: 16 * cin * 32 elements.
+ * bias (k) fp32. rows_valid / seg_rows: as osr_mask_upsample_predict; RoIs that do not exist are written as zeros.
+ * cin a multiple of 64, at most 512; k 1 .. 32; s 8 .. 14: anything else is OSR_ERR_UNSUPPORTED with nothing launched. x, w_packed
+ * and heatmaps are 16-byte aligned. r == 0: OSR_OK without a launch. Repeats are bit-identical.
+ *
+ * osr_heatmaps_to_keypoints: maps (r, k, m, m) fp32, m <= 56; rois (r, 4) xyxy; out (r, k, 4) = {x, y, logit, score}. Per RoI
+ * w = max(x1 - x0, 1), h likewise, wc = ceil(w), hc = ceil(h) (a side above 16384 px counts as 16384). U is the bicubic resize of
+ * the map to hc x wc by F.interpolate(mode="bicubic", align_corners=False)'s rules: source (m / wc) * (d + 0.5) - 0.5 (not clamped),
+ * t = src - floor(src), Keys' cubic convolution with A = -0.75 over the taps floor(src) - 1 .. + 2, tap indices clamped to
+ * [0, m - 1]. p = the first row-major position of max U (ties: the lowest y * wc + x);
+ *   x = (px + 0.5) * (w / wc) + x0,  y = (py + 0.5) * (h / hc) + y0,  logit = U[p],
+ *   score = 1 / sum over the m x m INPUT map of exp(map - U[p]).
+ * U is never stored. RoIs that do not exist (rows_valid / seg_rows as above) are written as zeros. r == 0 launches nothing. Repeats
+ * are bit-identical.
+ * --------------------------------------------------------------------------------------------------------- */
+osr_status osr_keypoint_upsample(const void* x, int32_t dtype, int64_t r, int32_t s, int32_t cin, int32_t k,
+                                 const void* w_packed, const float* bias, const int32_t* rows_valid, int32_t seg_rows,
+                                 float* heatmaps, void* stream);
+osr_status osr_heatmaps_to_keypoints(const float* maps, const float* rois, int64_t r, int32_t k, int32_t m,
+                                     const int32_t* rows_valid, int32_t seg_rows, float* out, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Mask branch, training ([d2] mask_rcnn_loss; csrc/osr_mask_train.hip). The mask rows are the foreground prefix of each image's
  * sampled proposals: n segments of seg_rows rows of which the first rows_valid[image] exist (osr_roi_match_and_sample_ex writes an
  * image's foreground rows first; rows_valid = its foreground count, seg_rows = int(batch_size * positive_fraction)).

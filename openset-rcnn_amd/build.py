@@ -39,6 +39,7 @@ SOURCES = {
     "osr_det_tail.hip": ["-ffp-contract=off"],
     "osr_cascade.hip": ["-ffp-contract=off"],  # (decodes and matches like osr_det_tail.hip / osr_std_train.hip)
     "osr_mask_head.hip": [],
+    "osr_keypoint.hip": [],
     "osr_mask_train.hip": ["-ffp-contract=off"],
     "osr_tta.hip": ["-ffp-contract=off"],
     "osr_train_fwd.hip": ["-ffp-contract=off"],

@@ -198,6 +198,9 @@ PROTOTYPES = {
     "osr_detector_postprocess": (I32, [P, P, P, P, I32, I32, P, P, P, P, P, P, P]),
     "osr_mask_upsample_predict": (I32, [P, I32, I64, I32, I32, I32, P, P, P, P, I32, P, P, I32, P, P]),
     "osr_paste_masks": (I32, [P, P, I64, I32, I32, I32, F32, P, P]),
+    # keypoint branch (csrc/osr_keypoint.hip)
+    "osr_keypoint_upsample": (I32, [P, I32, I64, I32, I32, I32, P, P, P, I32, P, P]),
+    "osr_heatmaps_to_keypoints": (I32, [P, P, I64, I32, I32, P, I32, P, P]),
     # mask branch, training (csrc/osr_mask_train.hip)
     "osr_mask_targets": (I32, [P, I32, I32, I32, I32, P, P, P, P, I32, I32, P, P]),
     "osr_mask_loss_fwd": (I32, [P, P, I64, I32, I32, P, P, I32, F32, P, P, I64, P]),

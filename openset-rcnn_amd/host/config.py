@@ -171,6 +171,11 @@ def get_cfg() -> CfgNode:
                                  "IOUS": (0.5, 0.6, 0.7)})
     m.ROI_MASK_HEAD = CN({"NAME": "MaskRCNNConvUpsampleHead", "POOLER_RESOLUTION": 14, "POOLER_SAMPLING_RATIO": 0, "NUM_CONV": 0,
                           "CONV_DIM": 256, "NORM": "", "CLS_AGNOSTIC_MASK": False, "POOLER_TYPE": "ROIAlignV2"})
+    # [d2] the keypoint branch (KRCNNConvDeconvUpsampleHead; host/engine_std.py _keypoint_head). MIN_KEYPOINTS_PER_IMAGE,
+    # NORMALIZE_LOSS_BY_VISIBLE_KEYPOINTS and LOSS_WEIGHT are training keys: carried so that detectron2's yaml files merge, read by nothing yet
+    m.ROI_KEYPOINT_HEAD = CN({"NAME": "KRCNNConvDeconvUpsampleHead", "POOLER_RESOLUTION": 14, "POOLER_SAMPLING_RATIO": 0,
+                              "POOLER_TYPE": "ROIAlignV2", "CONV_DIMS": (512,) * 8, "NUM_KEYPOINTS": 17, "MIN_KEYPOINTS_PER_IMAGE": 1,
+                              "NORMALIZE_LOSS_BY_VISIBLE_KEYPOINTS": True, "LOSS_WEIGHT": 1.0})
     # [d2] RetinaNet (host/engine_retinanet.py). IOU_THRESHOLDS .. BBOX_REG_LOSS_TYPE are training keys: carried so that detectron2's
     # yaml files merge, read by nothing yet
     m.RETINANET = CN({"NUM_CLASSES": 80, "IN_FEATURES": ["p3", "p4", "p5", "p6", "p7"], "NUM_CONVS": 4, "PRIOR_PROB": 0.01,
@@ -192,7 +197,7 @@ def get_cfg() -> CfgNode:
                    "WARMUP_ITERS": 1000, "WARMUP_METHOD": "linear", "CHECKPOINT_PERIOD": 5000, "IMS_PER_BATCH": 16,
                    "BIAS_LR_FACTOR": 1.0, "WEIGHT_DECAY_BIAS": 0.0001, "BASE_LR_END": 0.0})
     c.SOLVER.CLIP_GRADIENTS = CN({"ENABLED": False, "CLIP_TYPE": "value", "CLIP_VALUE": 1.0, "NORM_TYPE": 2.0})
-    c.TEST = CN({"EVAL_PERIOD": 0, "DETECTIONS_PER_IMAGE": 100})
+    c.TEST = CN({"EVAL_PERIOD": 0, "DETECTIONS_PER_IMAGE": 100, "KEYPOINT_OKS_SIGMAS": []})
     # [d2] test-time augmentation (GeneralizedRCNNWithTTA: host/tta.py)
     c.TEST.AUG = CN({"ENABLED": False, "MIN_SIZES": (400, 500, 600, 700, 800, 900, 1000, 1100, 1200), "MAX_SIZE": 4000, "FLIP": True})
     return c

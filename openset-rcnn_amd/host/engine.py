@@ -207,6 +207,8 @@ class OpensetRCNNEngine:
                 continue
             if k.startswith("roi_heads.mask_head.") and not k.startswith("roi_heads.mask_head.mask_fcn"):
                 continue  # (deconv and predictor have layouts of their own: engine_std._init_mask_head)
+            if k == "roi_heads.keypoint_head.score_lowres.weight":
+                continue  # (the transposed convolution's fragment order: engine_std._init_keypoint_head)
             pre = k[: -len(".weight")]
             if pre.endswith(".conv2_offset"):
                 # the offset / mask layer of a deformable conv2: zero rows up to the next output width the convolution takes (a
@@ -267,7 +269,9 @@ class OpensetRCNNEngine:
         self.cls_w, self.cls_b = f32("roi_heads.softmaxcls.cls_score.weight"), f32("roi_heads.softmaxcls.cls_score.bias")
 
     # ---- backbone -------------------------------------------------------------------------------------------
-    def _conv(self, x, name, stride=1, pad=0, relu=False, residual=None, res_mode=0, out=None, out_dtype=None):
+    def _conv(self, x, name, stride=1, pad=0, relu=False, residual=None, res_mode=0, out=None, out_dtype=None, row_seg=None):
+        """row_seg: ops.conv2d's (counts, rows per segment) -- the MFMA kernel skips the tiles of padded rows; the split-precision and
+        fp32 kernels compute every row."""
         w = self.w[name + ".w"]
         if self.conv == "split":
             return self._conv_split(x, name, w, stride, pad, relu, residual, res_mode, out)
@@ -278,7 +282,7 @@ class OpensetRCNNEngine:
                 (residual.numel() * residual.element_size() if residual is not None else 0)
             flops = 2.0 * rows * w.shape[0] * w.shape[1] * w.shape[2] * w.shape[3]
             return flops, nbytes, flops
-        return self._timed(name, lambda: ops.conv2d(x, w, self.w[name + ".b"], stride, pad, relu, residual, res_mode, out_dtype, out), cost)
+        return self._timed(name, lambda: ops.conv2d(x, w, self.w[name + ".b"], stride, pad, relu, residual, res_mode, out_dtype, out, row_seg=row_seg), cost)
 
     def _conv_split(self, x, name, w_split, stride, pad, relu, residual, res_mode, out):
         """_conv on the split-precision kernel: fp32 in, fp32 out. The credited FLOPs are the layer's (one product per element pair),
@@ -828,15 +832,20 @@ class OpensetRCNNEngine:
         return dict(loss_rpn_loc=rpn[0], loss_rpn_ctr=rpn[1], rpn_anchor_counts=rpn[2:], **roi)
 
     @staticmethod
-    def to_instances(result, n: int) -> List[dict]:
+    def to_instances(result, n: int, fields: Sequence[str] = ("pred_masks",)) -> List[dict]:
         """One D2H copy; list of {'pred_boxes','scores','pred_classes'} per image (the fields the evaluators read,
-        pascal_voc_evaluation.py:58-61). A fifth tensor (the stock engine's mask probabilities, (n, cap, M, M)) stays on the device
-        and is sliced into 'pred_masks' (k, 1, M, M), as [d2] mask_rcnn_inference attaches them."""
+        pascal_voc_evaluation.py:58-61). Tensors behind the first four stay on the device and are sliced to each image's count under
+        the names in `fields`, in order (the stock engine names its own: StandardRCNNEngine.output_fields). 'pred_masks' (n, cap, M, M)
+        becomes (k, 1, M, M), as [d2] mask_rcnn_inference attaches it; 'pred_keypoints' (n, cap, K, 3) and 'pred_keypoint_heatmaps'
+        (n, cap, K, 4P, 4P) are sliced as they are. A tuple with more tensors than names is an error, not a guess."""
+        extra = result[4:]
+        if len(extra) > len(fields):
+            raise ValueError(f"to_instances: {len(extra)} tensors behind the four box outputs, names for {len(fields)} ({tuple(fields)})")
         ob, osc, ocl, on = [t.cpu() for t in result[:4]]
         out = []
         for i in range(n):
             c = int(on[i])
             out.append(dict(pred_boxes=ob[i, :c], scores=osc[i, :c], pred_classes=ocl[i, :c]))
-            if len(result) > 4:
-                out[-1]["pred_masks"] = result[4][i, :c].unsqueeze(1)
+            for name, t in zip(fields, extra):
+                out[-1][name] = t[i, :c].unsqueeze(1) if name == "pred_masks" else t[i, :c]
         return out

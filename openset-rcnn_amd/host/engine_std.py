@@ -14,7 +14,7 @@ import torch
 
 from . import ops
 from .engine import PYRAMID, RPN_CONV, OpensetRCNNEngine, loss_types_of
-from .weights import pack_deconv_weight, pack_fc1_weight
+from .weights import pack_deconv_weight, pack_fc1_weight, pack_keypoint_deconv_weight
 
 STD_DEFAULT_CFG = dict(
     anchor_ratios=(0.5, 1.0, 2.0), post_nms_topk_test=1000, rpn_nms_thresh=0.7, rpn_bbox_reg_weights=(1.0, 1.0, 1.0, 1.0),
@@ -24,6 +24,8 @@ STD_DEFAULT_CFG = dict(
     loss_types=dict(rpn_box=("smooth_l1", 0.0), roi_box=("smooth_l1", 0.0)),
     # the mask branch (MODEL.MASK_ON; ROI_MASK_HEAD of Base-RCNN-FPN.yaml:29-33): built when the parameters carry a mask head
     mask_pooler_resolution=14, mask_pooler_aligned=True, mask_pooler_sampling_ratio=0,
+    # the keypoint branch (MODEL.KEYPOINT_ON; ROI_KEYPOINT_HEAD): built when the parameters carry a keypoint head
+    keypoint_pooler_resolution=14, keypoint_pooler_aligned=True, keypoint_pooler_sampling_ratio=0,
 )
 
 
@@ -44,6 +46,8 @@ def cell_anchor_table(sizes, ratios) -> torch.Tensor:
 
 
 class StandardRCNNEngine(OpensetRCNNEngine):
+    has_keypoint = False  # (set by _init_keypoint_head; an engine whose RoI heads are built elsewhere has no keypoint head)
+
     def __init__(self, params: Dict[str, torch.Tensor], cfg: Optional[dict] = None, dtype: torch.dtype = torch.float16, device: str = "cuda",
                  conv: str = "storage"):
         if conv != "storage":
@@ -72,6 +76,7 @@ class StandardRCNNEngine(OpensetRCNNEngine):
         f32 = lambda k: params[k].float().contiguous().to(dev)  # noqa: E731
         self.has_roi = "roi_heads.box_predictor.cls_score.weight" in params
         self._init_mask_head(params)
+        self._init_keypoint_head(params)
         if not self.has_roi:
             return
         self.fc1_w = pack_fc1_weight(params["roi_heads.box_head.fc1.weight"], 256, c["pooler_resolution"], dtype).to(dev)
@@ -126,6 +131,49 @@ class StandardRCNNEngine(OpensetRCNNEngine):
                              c["canonical_level"], c["canonical_size"], 2, aligned=c["mask_pooler_aligned"],
                              sampling_ratio=c["mask_pooler_sampling_ratio"])
 
+    def _init_keypoint_head(self, params) -> None:
+        """[d2] KRCNNConvDeconvUpsampleHead: conv_fcn1..N (3x3, packed with the other convolutions by _pack_convs) and score_lowres in
+        the fused tail's fragment order (weights.pack_keypoint_deconv_weight)."""
+        dev, c = self.device, self.cfg
+        pre = "roi_heads.keypoint_head."
+        self.has_keypoint = pre + "score_lowres.weight" in params
+        if not self.has_keypoint:
+            return
+        ops.check_pooler_options(c["keypoint_pooler_aligned"], c["keypoint_pooler_sampling_ratio"])
+        self.keypoint_num_conv = 0
+        while f"{pre}conv_fcn{self.keypoint_num_conv + 1}.weight" in params:
+            self.keypoint_num_conv += 1
+        self.keypoint_deconv_w = pack_keypoint_deconv_weight(params[pre + "score_lowres.weight"], self.dtype).to(dev)
+        self.keypoint_deconv_b = params[pre + "score_lowres.bias"].float().contiguous().to(dev)
+
+    # ---- [d2] StandardROIHeads._forward_keypoint + keypoint_rcnn_inference (inference) ---------------------------------------------
+    def _keypoint_head(self, feats, boxes, counts):
+        """boxes (n, topk, 4) fp32, counts (n,) int32: the padded detection lists (or any boxes: the head is callable on its own).
+        -> (keypoints (n, topk, K, 3) fp32 {x, y, score} in the boxes' coordinates, heatmaps (n, topk, K, 4P, 4P) fp32); the rows
+        beyond an image's count are zeros. The conv_fcn layers skip the tiles of those rows. No host sync: the capacities are fixed."""
+        c = self.cfg
+        if not self.has_keypoint:
+            raise ops.OsrError("this engine was built without a keypoint head (MODEL.KEYPOINT_ON False)")
+        n, topk = boxes.shape[0], boxes.shape[1]
+        res = c["keypoint_pooler_resolution"]
+        flat = boxes.reshape(-1, 4).contiguous()
+        x = self.pool_keypoint_rois(feats, flat, ops.padded_batch_idx(counts, topk))
+        seg = (counts * (res * res), topk * res * res)  # (an image's detections are a prefix of its topk * P * P pixel rows)
+        for i in range(self.keypoint_num_conv):
+            x = self._conv(x, f"roi_heads.keypoint_head.conv_fcn{i + 1}", 1, 1, relu=True, row_seg=seg)
+        heat = ops.keypoint_upsample(x, self.keypoint_deconv_w, self.keypoint_deconv_b, counts, topk)
+        kp = ops.heatmaps_to_keypoints(heat, flat, counts, topk)
+        k = heat.shape[1]
+        kp = kp.view(n, topk, k, 4)
+        return torch.cat((kp[..., :2], kp[..., 3:]), dim=-1), heat.view(n, topk, k, 4 * res, 4 * res)
+
+    def pool_keypoint_rois(self, feats, boxes, batch_idx):
+        """pool_rois with the keypoint pooler's three options (ROI_KEYPOINT_HEAD.POOLER_*) -> (m, R, R, 256)."""
+        c = self.cfg
+        return ops.roi_align([feats[k] for k in PYRAMID[:4]], c["pooler_scales"], boxes, batch_idx, c["keypoint_pooler_resolution"], self.dtype,
+                             c["canonical_level"], c["canonical_size"], 2, aligned=c["keypoint_pooler_aligned"],
+                             sampling_ratio=c["keypoint_pooler_sampling_ratio"])
+
     def _levels(self, shapes, n):
         key = (tuple(shapes), n)
         if key not in self._lv_cache:
@@ -167,8 +215,9 @@ class StandardRCNNEngine(OpensetRCNNEngine):
 
     # ---- [d2] StandardROIHeads._forward_box (inference) -----------------------------------------------------------------------
     def forward_device(self, images, image_hw, hp, wp, keep=None, mask: bool = True):
-        """mask=False: the pass without the mask branch -- the four box outputs, whether or not the engine has a mask head ([d2]
-        GeneralizedRCNNWithTTA._turn_off_roi_heads: the box stage of test-time augmentation). The engine's state is not touched."""
+        """mask=False: the pass without the per-detection branches behind the boxes (the mask head and the keypoint head) -- the four
+        box outputs, whichever heads the engine has ([d2] GeneralizedRCNNWithTTA._turn_off_roi_heads: the box stage of test-time
+        augmentation). The engine's state is not touched. What follows the four box outputs otherwise: output_fields()."""
         if mask:
             return super().forward_device(images, image_hw, hp, wp, keep)
         feats = self._backbone(images, hp, wp, keep)
@@ -176,6 +225,16 @@ class StandardRCNNEngine(OpensetRCNNEngine):
         if keep is not None:
             keep.update(feats=feats, sel=sel)
         return self._roi_heads(feats, sel, image_hw, keep, mask=False)
+
+    def output_fields(self, mask: bool = True):
+        """The names of the tensors forward_device returns behind (boxes, scores, classes, counts), in order -- what to_instances
+        takes as `fields`. mask: forward_device's flag."""
+        names = ()
+        if self.has_mask and mask:
+            names += ("pred_masks",)
+        if self.has_keypoint and mask:
+            names += ("pred_keypoints", "pred_keypoint_heatmaps")
+        return names
 
     def _box_stage_params(self, s: int):
         """Box stage s: (its box head's parameter prefix, fc1_w, fc1_b, fc2_w, fc2_b, cls_w, cls_b, box_w, box_b). StandardROIHeads has one."""
@@ -199,15 +258,19 @@ class StandardRCNNEngine(OpensetRCNNEngine):
         return self._detections(feats, cands, sel["boxes"].shape[0], keep, mask)
 
     def _detections(self, feats, cands, n, keep=None, mask: bool = True):
-        """[d2] fast_rcnn_inference behind the candidates: per-class NMS, the best DETECTIONS_PER_IMAGE, then the mask head on them."""
+        """[d2] fast_rcnn_inference behind the candidates: per-class NMS, the best DETECTIONS_PER_IMAGE, then the mask head and the
+        keypoint head on them (mask=False: neither). The outputs behind the first four are named by output_fields(mask)."""
         c = self.cfg
         ob, osc, ocl, dcnt, dk = ops.nms_gather(cands["boxes"], cands["scores"], cands["cls"], None, n, cands["cap"], cands["count"],
                                                 c["std_nms_thresh_test"], c["std_detections_per_image"])
         if keep is not None:
             keep.update(cands=cands, det_keep=dk, det_count=dcnt)
+        out = (ob, osc, ocl, dcnt)
         if self.has_mask and mask:  # (a fifth output only when the engine has a mask head: MASK_ON False returns what it always has)
-            return ob, osc, ocl, dcnt, self._mask_head(feats, ob, ocl, dcnt)
-        return ob, osc, ocl, dcnt
+            out += (self._mask_head(feats, ob, ocl, dcnt),)
+        if self.has_keypoint and mask:  # (two more, last, only with a keypoint head: output_fields names them)
+            out += self._keypoint_head(feats, ob, dcnt)
+        return out
 
     # ---- [d2] RPN.label_and_sample_anchors + RPN.losses (training) ---------------------------------------------------------------
     def rpn_targets_forward(self, lv, n: int, gt_boxes: torch.Tensor, gt_count: torch.Tensor, keys: Dict[str, torch.Tensor],
@@ -273,6 +336,8 @@ class StandardRCNNEngine(OpensetRCNNEngine):
         (mask_losses_forward; gt_masks is then required): loss_mask, mask_stats (6) and state["mask"]."""
         c = self.cfg
         check_std_supported(c)
+        if self.has_keypoint:
+            raise NotImplementedError(KEYPOINT_LOSS_MESSAGE)
         if self.has_mask and gt_masks is None:
             raise ValueError("MODEL.MASK_ON: training the mask branch needs gt_masks (INPUT.MASK_FORMAT \"bitmask\" ground truth)")
         k = c["std_num_classes"]
@@ -289,6 +354,10 @@ class StandardRCNNEngine(OpensetRCNNEngine):
             mst, state["mask"] = self.mask_losses_forward(feats, smp, gt_masks, image_hw)
             out.update(loss_mask=mst[0], mask_stats=mst)
         return out, state
+
+
+KEYPOINT_LOSS_MESSAGE = ("MODEL.KEYPOINT_ON: the keypoint loss (keypoint_rcnn_loss) is not built on the HIP path -- the keypoint branch runs at "
+                         "inference only; train the box (and mask) branches with MODEL.KEYPOINT_ON False")
 
 
 def std_loss_beta(cfg: dict, key: str) -> float:

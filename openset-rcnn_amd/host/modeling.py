@@ -29,7 +29,7 @@ from .engine import DEFAULT_CFG, OpensetRCNNEngine, check_deform_options, refuse
 from .engine_cascade import CascadeRCNNEngine, check_cascade_options
 from .engine_panoptic import PanopticFPNEngine, check_sem_seg_options, training_message as panoptic_training_message
 from .engine_retinanet import RETINA_PYRAMID, TRAINING_MESSAGE as RETINANET_TRAINING_MESSAGE, RetinaNetEngine, check_retina_anchors
-from .engine_std import StandardRCNNEngine, check_std_supported
+from .engine_std import KEYPOINT_LOSS_MESSAGE, StandardRCNNEngine, check_std_supported
 from .structures import Boxes, ImageList, Instances, ShapeSpec
 from .weights import R50_BLOCKS, R50_MID, fold_frozen_bn
 
@@ -68,6 +68,7 @@ RPN_HEAD_REGISTRY = Registry("RPN_HEAD")
 ROI_HEADS_REGISTRY = Registry("ROI_HEADS")
 ROI_BOX_HEAD_REGISTRY = Registry("ROI_BOX_HEAD")
 ROI_MASK_HEAD_REGISTRY = Registry("ROI_MASK_HEAD")
+ROI_KEYPOINT_HEAD_REGISTRY = Registry("ROI_KEYPOINT_HEAD")
 
 
 
@@ -730,6 +731,38 @@ class MaskRCNNConvUpsampleHead(nn.Module):
         nn.init.constant_(self.predictor.bias, 0)
 
 
+@ROI_KEYPOINT_HEAD_REGISTRY.register()
+class KRCNNConvDeconvUpsampleHead(nn.Module):
+    """[d2] KRCNNConvDeconvUpsampleHead with [d2]'s parameter names, so that model-zoo keypoint_rcnn checkpoints load: conv_fcn1..N
+    (3x3, CONV_DIMS[i], ReLU), score_lowres (ConvTranspose2d 4x4 stride 2 pad 1 to NUM_KEYPOINTS maps), then bilinear x2 (no
+    parameters). Initialiser: kaiming_normal_(fan_out, relu) for every weight, zero biases. What the fused tail
+    (ops.keypoint_upsample) and the convolution do not take is refused here by key name."""
+
+    def __init__(self, cfg: CfgNode, input_shape: ShapeSpec):
+        super().__init__()
+        kh = cfg.MODEL.ROI_KEYPOINT_HEAD
+        dims = [int(d) for d in kh.CONV_DIMS]
+        if not dims:
+            raise ValueError("MODEL.ROI_KEYPOINT_HEAD.CONV_DIMS is empty: the head needs at least one conv_fcn layer")
+        if any(d < 64 or d % 64 or d > 512 for d in dims):
+            raise ValueError(f"MODEL.ROI_KEYPOINT_HEAD.CONV_DIMS {tuple(dims)}: every entry a multiple of 64, at most 512")
+        k = kh.NUM_KEYPOINTS
+        if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= 32:
+            raise ValueError(f"MODEL.ROI_KEYPOINT_HEAD.NUM_KEYPOINTS {k!r}: an integer 1 .. 32 (the MFMA tile of the fused tail)")
+        cur = input_shape.channels
+        self.num_conv, self.num_keypoints = len(dims), int(k)
+        for i, d in enumerate(dims):
+            conv = nn.Conv2d(cur, d, 3, padding=1)
+            self.add_module(f"conv_fcn{i + 1}", conv)
+            cur = d
+        self.score_lowres = nn.ConvTranspose2d(cur, self.num_keypoints, 4, stride=2, padding=1)
+        for name, prm in self.named_parameters():
+            if name.endswith("bias"):
+                nn.init.constant_(prm, 0)
+            else:
+                nn.init.kaiming_normal_(prm, mode="fan_out", nonlinearity="relu")
+
+
 MASK_LOSS_MESSAGE = ("MODEL.MASK_ON with INPUT.MASK_FORMAT \"polygon\": the mask loss (mask_rcnn_loss) trains on bitmask ground truth only "
                      "-- rasterising polygons needs pycocotools, which the HIP path does not have. Set INPUT.MASK_FORMAT \"bitmask\" "
                      "(2-D arrays or uncompressed RLE per annotation) to train the mask branch; at inference the mask head runs either way")
@@ -758,11 +791,14 @@ class StandardROIHeads(_EngineOwner):
     sampled proposals (gradients: the model-level call, see the module docstring)."""
     _prefix = "roi_heads."
     _engine_cls = StandardRCNNEngine
+    _keypoint_branch = True  # (CascadeROIHeads: False -- MODEL.KEYPOINT_ON is refused there)
 
     def __init__(self, cfg: CfgNode, input_shape: Dict[str, ShapeSpec], class_id=None):
         super().__init__()
-        if cfg.MODEL.KEYPOINT_ON:
-            raise ValueError("MODEL.KEYPOINT_ON: the HIP path has no keypoint head (box and mask branches only)")
+        self.keypoint_on = bool(cfg.MODEL.KEYPOINT_ON)
+        if self.keypoint_on and (not self._keypoint_branch or cfg.MODEL.ROI_HEADS.NUM_CLASSES != 1):
+            raise ValueError(f"MODEL.KEYPOINT_ON: the keypoint branch is built for StandardROIHeads with ROI_HEADS.NUM_CLASSES 1, the one-class "
+                             f"person detector of [d2]'s Keypoint R-CNN configs (got {type(self).__name__}, NUM_CLASSES {cfg.MODEL.ROI_HEADS.NUM_CLASSES})")
         self.in_features = self.box_in_features = list(cfg.MODEL.ROI_HEADS.IN_FEATURES)
         res = cfg.MODEL.ROI_BOX_HEAD.POOLER_RESOLUTION
         ch = input_shape[self.in_features[0]].channels
@@ -786,10 +822,24 @@ class StandardROIHeads(_EngineOwner):
             self.mask_in_features = self.in_features
             self.mask_head = ROI_MASK_HEAD_REGISTRY.get(mh.NAME)(cfg, ShapeSpec(channels=ch, height=mres, width=mres))
             self._eng_cfg.update(mask_pooler_resolution=int(mres), mask_pooler_aligned=aligned, mask_pooler_sampling_ratio=ratio)
+        # [d2] StandardROIHeads._init_keypoint_head: the same levels again, with the keypoint pooler's resolution / type / ratio
+        if self.keypoint_on:
+            kh = cfg.MODEL.ROI_KEYPOINT_HEAD
+            aligned, ratio = pooler_options_from(cfg, "ROI_KEYPOINT_HEAD")
+            kres = kh.POOLER_RESOLUTION
+            if isinstance(kres, bool) or not isinstance(kres, int) or not 8 <= kres <= 14:
+                raise ValueError(f"MODEL.ROI_KEYPOINT_HEAD.POOLER_RESOLUTION {kres!r}: an integer 8 .. 14 (the fused tail keeps one RoI's map on chip)")
+            if kh.NAME not in ROI_KEYPOINT_HEAD_REGISTRY:
+                raise ValueError(f"MODEL.ROI_KEYPOINT_HEAD.NAME {kh.NAME!r}: not a registered keypoint head")
+            self.keypoint_in_features = self.in_features
+            self.keypoint_head = ROI_KEYPOINT_HEAD_REGISTRY.get(kh.NAME)(cfg, ShapeSpec(channels=ch, height=kres, width=kres))
+            self._eng_cfg.update(keypoint_pooler_resolution=int(kres), keypoint_pooler_aligned=aligned, keypoint_pooler_sampling_ratio=ratio)
 
     def _forward_train(self, features: Dict[str, torch.Tensor], proposals: List[Instances], targets: List[Instances]):
         """[d2] label_and_sample_proposals + FastRCNNOutputLayers.losses: the sampled proposals (gt_classes / gt_boxes attached) and the
         loss values."""
+        if self.keypoint_on:
+            raise NotImplementedError(KEYPOINT_LOSS_MESSAGE)
         if self.mask_on and self.mask_format != "bitmask":
             raise NotImplementedError(MASK_LOSS_MESSAGE)
         eng = self.engine()
@@ -833,7 +883,7 @@ class StandardROIHeads(_EngineOwner):
         sel = dict(boxes=boxes, scores=scores, batch_idx=bidx.view(-1), counts=counts, cap=cap)
         hw = torch.tensor([p.image_size for p in proposals], dtype=torch.int32, device=boxes.device)
         feats = {k: _to_nhwc(features[k], eng.dtype) for k in self.in_features}
-        res = OpensetRCNNEngine.to_instances(eng._roi_heads(feats, sel, hw), n)
+        res = OpensetRCNNEngine.to_instances(eng._roi_heads(feats, sel, hw), n, eng.output_fields())
         out = []
         for r, p in zip(res, proposals):
             out.append(_std_instances(p.image_size, r))
@@ -841,23 +891,25 @@ class StandardROIHeads(_EngineOwner):
 
 
     def forward_with_given_boxes(self, features: Dict[str, torch.Tensor], instances: List[Instances]) -> List[Instances]:
-        """[d2] StandardROIHeads.forward_with_given_boxes: the mask branch on boxes the caller supplies. instances carry pred_boxes and
-        pred_classes; they come back with pred_masks (k, 1, M, M) probabilities added, every other field as given -- unchanged when the
-        model has no mask head. features: the NCHW pyramid of the backbone."""
+        """[d2] StandardROIHeads.forward_with_given_boxes: the mask and keypoint branches on boxes the caller supplies. instances carry
+        pred_boxes and pred_classes; they come back with pred_masks (k, 1, M, M) probabilities (MASK_ON) and pred_keypoints (k, K, 3) /
+        pred_keypoint_heatmaps (k, K, 4P, 4P) (KEYPOINT_ON) added, every other field as given -- unchanged when the model has neither
+        head. features: the NCHW pyramid of the backbone."""
         assert not self.training, "forward_with_given_boxes is an inference entry"
         for inst in instances:
             if not (inst.has("pred_boxes") and inst.has("pred_classes")):
                 raise ValueError("forward_with_given_boxes: every Instances needs pred_boxes and pred_classes")
-        if not self.mask_on:
+        if not (self.mask_on or self.keypoint_on):
             return instances
         eng = self.engine()
         feats = {k: _to_nhwc(features[k], eng.dtype) for k in self.in_features}
-        return self._attach_masks(eng, feats, instances)
+        return self._attach_branches(eng, feats, instances)
 
     @staticmethod
-    def _attach_masks(eng, feats: Dict[str, torch.Tensor], instances: List[Instances]) -> List[Instances]:
-        """The engine's mask head on the given boxes, over its NHWC pyramid. The lists are padded to the engine's detection capacity (or
-        the longest list, when longer), so a pass's own detections run through the very launches that made its masks."""
+    def _attach_branches(eng, feats: Dict[str, torch.Tensor], instances: List[Instances]) -> List[Instances]:
+        """The engine's mask and keypoint heads (those it has) on the given boxes, over its NHWC pyramid. The lists are padded to the
+        engine's detection capacity (or the longest list, when longer), so a pass's own detections run through the very launches that
+        made its masks and keypoints."""
         dev = eng.device
         n = len(instances)
         cap = max([int(eng.cfg["std_detections_per_image"])] + [len(i) for i in instances])
@@ -868,11 +920,16 @@ class StandardROIHeads(_EngineOwner):
             boxes[i, :k] = inst.pred_boxes.tensor.detach().float().cpu()
             classes[i, :k] = inst.pred_classes.detach().to(torch.int64).cpu()
         counts = torch.tensor([len(i) for i in instances], dtype=torch.int32)
-        probs = eng._mask_head(feats, boxes.to(dev), classes.to(dev), counts.to(dev))
+        boxes, counts = boxes.to(dev), counts.to(dev)
+        probs = eng._mask_head(feats, boxes, classes.to(dev), counts) if eng.has_mask else None
+        kp, heat = eng._keypoint_head(feats, boxes, counts) if eng.has_keypoint else (None, None)
         out = []
         for i, inst in enumerate(instances):
             r = Instances(inst.image_size, **inst.get_fields())
-            r.pred_masks = probs[i, : len(inst)].unsqueeze(1)
+            if probs is not None:
+                r.pred_masks = probs[i, : len(inst)].unsqueeze(1)
+            if kp is not None:
+                r.pred_keypoints, r.pred_keypoint_heatmaps = kp[i, : len(inst)], heat[i, : len(inst)]
             out.append(r)
         return out
 
@@ -887,6 +944,8 @@ class CascadeROIHeads(StandardROIHeads):
     at IOUS[s]; losses loss_cls_stage{s} / loss_box_reg_stage{s}; the mask head (MODEL.MASK_ON) trains on stage 0's rows and runs on
     the final detections. What [d2] asserts is refused with a ValueError when the model is built."""
     _engine_cls = CascadeRCNNEngine
+
+    _keypoint_branch = False
 
     def __init__(self, cfg: CfgNode, input_shape: Dict[str, ShapeSpec], class_id=None):
         ch = cfg.MODEL.ROI_BOX_CASCADE_HEAD
@@ -903,10 +962,12 @@ class CascadeROIHeads(StandardROIHeads):
 
 def _std_instances(image_size, r: dict) -> Instances:
     """Instances of one image from OpensetRCNNEngine.to_instances' dict; pred_masks (k, 1, M, M) probabilities when the engine has a
-    mask head ([d2] mask_rcnn_inference)."""
+    mask head ([d2] mask_rcnn_inference), pred_keypoints (k, K, 3) {x, y, score} and pred_keypoint_heatmaps (k, K, 4P, 4P) when it has a
+    keypoint head ([d2] keypoint_rcnn_inference)."""
     inst = Instances(image_size, pred_boxes=Boxes(r["pred_boxes"]), scores=r["scores"], pred_classes=r["pred_classes"])
-    if "pred_masks" in r:
-        inst.pred_masks = r["pred_masks"]
+    for f in ("pred_masks", "pred_keypoints", "pred_keypoint_heatmaps"):
+        if f in r:
+            inst.set(f, r[f])
     return inst
 
 
@@ -918,10 +979,13 @@ MASK_THRESHOLD = 0.5  # [d2] detector_postprocess's mask_threshold
 
 def detector_postprocess(results: Instances, output_height: int, output_width: int, mask_threshold: float = MASK_THRESHOLD) -> Instances:
     """[d2] rescale to the requested output resolution, clip, drop empty boxes; pred_masks (k, 1, M, M) probabilities on the GPU are
-    then pasted into (k, H, W) bool bitmasks at the output resolution (ops.paste_masks: [d2] paste_masks_in_image)."""
+    then pasted into (k, H, W) bool bitmasks at the output resolution (ops.paste_masks: [d2] paste_masks_in_image); pred_keypoints
+    (k, K, 3) have x and y multiplied by the scale factors (scores as they are) and lose the rows of dropped boxes, as the
+    pred_keypoint_heatmaps do, which are otherwise passed through."""
     sx, sy = output_width / results.image_size[1], output_height / results.image_size[0]
     fields = dict(results.get_fields())
     masks = fields.pop("pred_masks", None)
+    kpts, heat = fields.pop("pred_keypoints", None), fields.pop("pred_keypoint_heatmaps", None)
     out = Instances((output_height, output_width), **fields)
     b = out.pred_boxes.clone()
     b.scale(sx, sy)
@@ -933,6 +997,10 @@ def detector_postprocess(results: Instances, output_height: int, output_width: i
         probs = masks[keep.to(masks.device)][:, 0].float().contiguous()
         boxes = out.pred_boxes.tensor.float().to(probs.device).contiguous()
         out.pred_masks = ops.paste_masks(probs, boxes, output_height, output_width, mask_threshold).bool()
+    if kpts is not None:
+        out.pred_keypoints = kpts[keep.to(kpts.device)] * kpts.new_tensor([sx, sy, 1.0])
+    if heat is not None:
+        out.pred_keypoint_heatmaps = heat[keep.to(heat.device)]
     return out
 
 
@@ -985,6 +1053,7 @@ class GeneralizedRCNN(_EngineOwner):
         buffer (`solver.build_optimizer(cfg, model).step()` then all-reduces and applies it)."""
         if not self.training:
             return self.inference(batched_inputs)
+        self._refuse_keypoint_training()
         trainer = self.trainer()
         tensors = self._train_tensors(batched_inputs, self.sampler_generator)
         with torch.no_grad():
@@ -1032,6 +1101,7 @@ class GeneralizedRCNN(_EngineOwner):
         from .train_cascade import CascadeRCNNTrainer
         from .train_std import StandardRCNNTrainer
         refuse_deform_training(self._eng_cfg)  # (NotImplementedError naming MODEL.RESNETS.DEFORM_ON_PER_STAGE)
+        self._refuse_keypoint_training()
         if self._mask_training() is False:
             raise NotImplementedError(MASK_LOSS_MESSAGE)
         if self.conv_precision != "storage":
@@ -1116,6 +1186,10 @@ class GeneralizedRCNN(_EngineOwner):
         out = (batch, hw, hp, wp, gt.to(dev), gcls.to(dev), gcnt.to(dev), keys)
         return out if planes is None else out + (planes.to(dev),)  # (a ninth tensor only when the mask branch trains)
 
+    def _refuse_keypoint_training(self) -> None:
+        if getattr(self.roi_heads, "keypoint_on", False):
+            raise NotImplementedError(KEYPOINT_LOSS_MESSAGE)
+
     def _mask_training(self) -> Optional[bool]:
         """None: the model has no mask branch; True: it trains (INPUT.MASK_FORMAT "bitmask"); False: training is refused."""
         if not getattr(self.roi_heads, "mask_on", False):
@@ -1134,6 +1208,7 @@ class GeneralizedRCNN(_EngineOwner):
         "instances" (gt_boxes: Boxes, gt_classes); a ragged batch is padded to its largest image. `generator` seeds the
         uniform keys that replace torch.randperm in the two samplers."""
         refuse_deform_training(self._eng_cfg)
+        self._refuse_keypoint_training()
         if self._mask_training() is False:
             raise NotImplementedError(MASK_LOSS_MESSAGE)
         tensors = self._train_tensors(batched_inputs, generator)
@@ -1161,17 +1236,17 @@ class GeneralizedRCNN(_EngineOwner):
             if len(detected_instances) != len(batched_inputs):
                 raise ValueError(f"detected_instances: {len(detected_instances)} Instances for {len(batched_inputs)} inputs")
             insts = list(detected_instances)
-            if self.roi_heads.mask_on:
+            if self.roi_heads.mask_on or self.roi_heads.keypoint_on:
                 d = eng.cfg["size_divisibility"]
                 hp, wp = (int(batch.shape[-2]) + d - 1) // d * d, (int(batch.shape[-1]) + d - 1) // d * d
-                insts = StandardROIHeads._attach_masks(eng, eng._backbone(batch, hp, wp), insts)
+                insts = StandardROIHeads._attach_branches(eng, eng._backbone(batch, hp, wp), insts)
             if do_postprocess:
                 insts = [detector_postprocess(r, int(inp.get("height", s[0])), int(inp.get("width", s[1])))
                          for r, inp, s in zip(insts, batched_inputs, sizes)]
             return [{"instances": r} for r in insts]
         res = eng.forward(batch, sizes)
-        if len(res) > 4:  # mask head: the masks follow their boxes through the per-image postprocess, which pastes them
-            insts = [_std_instances(s, r) for r, s in zip(OpensetRCNNEngine.to_instances(res, len(sizes)), sizes)]
+        if len(res) > 4:  # mask / keypoint head: their outputs follow the boxes through the per-image postprocess (paste; scale)
+            insts = [_std_instances(s, r) for r, s in zip(OpensetRCNNEngine.to_instances(res, len(sizes), eng.output_fields()), sizes)]
             if do_postprocess:
                 insts = [detector_postprocess(r, int(inp.get("height", s[0])), int(inp.get("width", s[1])))
                          for r, inp, s in zip(insts, batched_inputs, sizes)]

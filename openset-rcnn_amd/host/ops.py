@@ -1296,6 +1296,49 @@ def mask_upsample_predict(x: torch.Tensor, w_packed: torch.Tensor, bias: torch.T
     return probs
 
 
+def _rows_valid_arg(rows_valid, seg_rows, r, name):
+    if rows_valid is not None:
+        _need(rows_valid, torch.int32, "rows_valid")
+        if seg_rows < 1 or rows_valid.numel() * seg_rows < r:
+            raise OsrError(f"{name}: rows_valid does not cover the RoIs")
+
+
+def keypoint_upsample(x: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor, rows_valid: Optional[torch.Tensor] = None,
+                      seg_rows: int = 0) -> torch.Tensor:
+    """[d2] KRCNNConvDeconvUpsampleHead's tail in one launch (include/osr.h osr_keypoint_upsample): score_lowres =
+    ConvTranspose2d(cin -> k, 4 x 4, stride 2, padding 1) and the bilinear x2 (align_corners=False). x (r, s, s, cin) NHWC; w_packed:
+    weights.pack_keypoint_deconv_weight in x's dtype; bias (k) fp32; rows_valid (segments) int32 with seg_rows RoIs per segment: the
+    RoIs beyond a segment's count come out as zeros. Returns heatmaps (r, k, 4s, 4s) fp32."""
+    lib = _lib.load()
+    _need(x, name="x"); _need(w_packed, x.dtype, "w_packed"); _need(bias, torch.float32, "bias")
+    if x.dim() != 4 or x.shape[1] != x.shape[2]:
+        raise OsrError(f"keypoint_upsample: x {tuple(x.shape)} is not (r, s, s, cin)")
+    r, s, _, cin = x.shape
+    k = bias.numel()
+    if w_packed.numel() != 16 * cin * 32:
+        raise OsrError(f"keypoint_upsample: w_packed {tuple(w_packed.shape)} is not pack_keypoint_deconv_weight of a ({cin}, k, 4, 4) weight")
+    _rows_valid_arg(rows_valid, seg_rows, r, "keypoint_upsample")
+    heat = torch.empty((r, k, 4 * s, 4 * s), dtype=torch.float32, device=x.device)
+    check(lib.osr_keypoint_upsample(_p(x), _DT[x.dtype], r, s, cin, k, _p(w_packed), _p(bias), _p(rows_valid), int(seg_rows), _p(heat), _stream()),
+          "osr_keypoint_upsample")
+    return heat
+
+
+def heatmaps_to_keypoints(maps: torch.Tensor, rois: torch.Tensor, rows_valid: Optional[torch.Tensor] = None, seg_rows: int = 0) -> torch.Tensor:
+    """[d2] heatmaps_to_keypoints on the device without the resized maps (include/osr.h osr_heatmaps_to_keypoints): maps (r, k, m, m)
+    fp32, m <= 56; rois (r, 4) fp32 xyxy. Returns (r, k, 4) fp32 {x, y, logit, score}: the first row-major maximum of the map resized
+    bicubically to the RoI's ceil(h) x ceil(w), mapped into the image; zeros for the RoIs beyond a segment's count."""
+    lib = _lib.load()
+    _need(maps, torch.float32, "maps"); _need(rois, torch.float32, "rois")
+    if maps.dim() != 4 or maps.shape[2] != maps.shape[3] or rois.shape != (maps.shape[0], 4):
+        raise OsrError(f"heatmaps_to_keypoints: maps {tuple(maps.shape)} / rois {tuple(rois.shape)} are not (r, k, m, m) / (r, 4)")
+    r, k, m, _ = maps.shape
+    _rows_valid_arg(rows_valid, seg_rows, r, "heatmaps_to_keypoints")
+    out = torch.empty((r, k, 4), dtype=torch.float32, device=maps.device)
+    check(lib.osr_heatmaps_to_keypoints(_p(maps), _p(rois), r, k, m, _p(rows_valid), int(seg_rows), _p(out), _stream()), "osr_heatmaps_to_keypoints")
+    return out
+
+
 def _mask_tail_args(x, w_packed, bias, pred_w, classes, rows_valid, seg_rows, name):
     _need(x, name="x"); _need(w_packed, x.dtype, "w_packed")
     _need(bias, torch.float32, "bias"); _need(pred_w, torch.float32, "pred_w")

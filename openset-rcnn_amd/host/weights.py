@@ -145,6 +145,22 @@ def unpack_deconv_weight(p: torch.Tensor) -> torch.Tensor:
     return p.permute(0, 1, 4, 2, 3, 5).reshape(2, 2, cmid, cin).permute(3, 2, 0, 1).contiguous()
 
 
+def pack_keypoint_deconv_weight(w: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
+    """[d2] KRCNNConvDeconvUpsampleHead.score_lowres weight (cin, k, 4, 4) -> the B operand of ops.keypoint_upsample (include/osr.h
+    osr_keypoint_upsample): one (32, cin) matrix per tap ky * 4 + kx -- the k keypoints padded with zero rows to the MFMA's N = 32 --
+    cut into the fragments a wave loads: blocks of 2E input channels, E = 8 (fp16 / bf16) or 4 (fp32), laid out
+    [ky * 4 + kx][c / 2E][(c / E) % 2][j][c % E], so that the 64 lanes of a wave read one contiguous block. cin a multiple of 64,
+    k 1 .. 32."""
+    cin, k, kh, kw = w.shape
+    if (kh, kw) != (4, 4) or cin % 64 or not 1 <= k <= 32:
+        raise ValueError(f"score_lowres weight {tuple(w.shape)}: (cin, k, 4, 4) with cin a multiple of 64 and k in 1 .. 32")
+    e = 4 if dtype == torch.float32 else 8
+    wt = torch.zeros((16, 32, cin), dtype=w.dtype)
+    wt[:, :k] = w.detach().cpu().permute(2, 3, 1, 0).reshape(16, k, cin)
+    wt = wt.reshape(16, 32, cin // (2 * e), 2, e)  # [tap][j][c / 2E][half][c % E]
+    return wt.permute(0, 2, 3, 1, 4).contiguous().to(dtype)
+
+
 def split_fp32_rows(w: torch.Tensor):
     """The operand format of the split-precision box head (ops.linear_split, include/osr.h osr_linear_split_fwd): an fp32 matrix as
     two bf16 planes, w = hi + lo to 2^-17 of each element's magnitude, hi = bf16(w), lo = bf16(w - hi), both rounded to nearest
