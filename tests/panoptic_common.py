@@ -4,7 +4,10 @@
   resample_reference        F.interpolate(x4) -> crop -> F.interpolate(size) in float64
   combine_reference         detectron2's combine_semantic_and_instance_outputs loop, with the branch each instance / label took
   combine_scene             the 40 x 56 scene of tests/test_panoptic_combine.py
-  resample_logits           the seeded stride-4 logits of tests/test_semseg_resample.py"""
+  combine_ragged_plane, combine_limits, combine_boundary_scene, combine_rounded_threshold_scene, combine_scene_with_ignored_labels
+                            the inputs that take osr_panoptic_combine past word 1024, to k = 1024 and 255 labels, and onto its thresholds
+  resample_logits           the seeded stride-4 logits of tests/test_semseg_resample.py
+  RESAMPLE_WIDE_CASES       more classes than one LDS pass of osr_semseg_resample holds, and one-row / one-cell maps"""
 import torch
 import torch.nn.functional as F
 
@@ -111,6 +114,131 @@ def segments_info_reference(table, seg_scores):
         else:
             out.append({"id": r + 1, "isthing": False, "category_id": row[1], "area": row[3]})
     return out
+
+
+def word_range(mask, width):
+    """mask (H, W) bool with a set pixel -> (wlo, whi): the 64-pixel words [wlo, whi) of the rows from its first to its last set one,
+    the range pc_walk_kernel walks for the instance (csrc/osr_panoptic.hip)."""
+    rows = torch.nonzero(mask.any(dim=1)).flatten()
+    y0, y1 = int(rows[0]), int(rows[-1]) + 1
+    return y0 * width // 64, (y1 * width + 63) // 64
+
+
+RAGGED_THRESHOLDS = dict(overlap_thresh=0.5, stuff_area_limit=256, instances_confidence_thresh=0.5)
+
+
+def combine_ragged_plane(seed=4):
+    """300 x 333 = 99 900 pixels = 1560 words and 60 pixels, k = 48 -> (masks bool, scores, classes, labels): instance 0 covers every
+    row (a range of 1561 words), 1 starts at word 1092, 2 is the last row's tail in the partial last word, 3 overlaps 0 and 1; then
+    44 seeded rectangles with sides 4 .. 120 and scores 0.4 .. 0.9; labels of 54 classes in 16 x 16 blocks."""
+    g = torch.Generator().manual_seed(seed)
+    h, w, k = 300, 333, 48
+    masks = torch.zeros(k, h, w, dtype=torch.bool)
+    masks[0, :, 100:140] = True
+    masks[1, 210:290, 5:300] = True
+    masks[2, 299:300, 300:333] = True
+    masks[3, 205:215, 120:200] = True
+    for i in range(4, k):
+        y0, x0 = int(torch.randint(0, h - 4, (1,), generator=g)), int(torch.randint(0, w - 4, (1,), generator=g))
+        y1, x1 = y0 + int(torch.randint(4, 121, (1,), generator=g)), x0 + int(torch.randint(4, 121, (1,), generator=g))
+        masks[i, y0:min(y1, h), x0:min(x1, w)] = True
+    scores = torch.rand(k, generator=g) * 0.5 + 0.4
+    scores[:4] = torch.tensor([0.99, 0.98, 0.97, 0.96])
+    classes = torch.randint(0, 80, (k,), generator=g)
+    blocks = torch.randint(0, 54, (h // 16 + 1, w // 16 + 1), generator=g)
+    labels = blocks.repeat_interleave(16, 0).repeat_interleave(16, 1)[:h, :w].to(torch.int32).contiguous()
+    return masks, scores, classes, labels
+
+
+LIMITS_THRESHOLDS = dict(overlap_thresh=0.5, stuff_area_limit=2, instances_confidence_thresh=0.5)
+
+
+def combine_limits(seed=9):
+    """32 x 48, k = 1024 single-pixel masks at distinct positions, scores from eight values in [0.5, 1.0] (long runs of equal scores);
+    the other 512 pixels carry the labels 1 .. 255 twice each and 0 twice, the instance pixels random labels 0 .. 255: with
+    stuff_area_limit = 2 every instance and every label takes a row, 1024 + 255 = the table's capacity."""
+    g = torch.Generator().manual_seed(seed)
+    h, w, k = 32, 48, 1024
+    perm = torch.randperm(h * w, generator=g)
+    masks = torch.zeros(k, h * w, dtype=torch.bool)
+    masks[torch.arange(k), perm[:k]] = True
+    scores = torch.linspace(0.5, 1.0, 8)[torch.randint(0, 8, (k,), generator=g)].contiguous()
+    classes = torch.randint(0, 80, (k,), generator=g)
+    labels = torch.zeros(h * w, dtype=torch.int32)
+    labels[perm[:k]] = torch.randint(0, 256, (k,), generator=g).to(torch.int32)
+    labels[perm[k:k + 510]] = torch.arange(1, 256, dtype=torch.int32).repeat(2)
+    return masks.reshape(k, h, w), scores, classes, labels.reshape(h, w).contiguous()
+
+
+def f32(v):
+    """The double that a C `float` argument holds for the Python float v."""
+    return float(torch.tensor(v, dtype=torch.float32))
+
+
+def below(v):
+    """The next fp32 value under v, as a double."""
+    return float(torch.nextafter(torch.tensor(v, dtype=torch.float32), torch.tensor(0.0)))
+
+
+def combine_boundary_scene(frac, conf):
+    """8 x 40: A = columns 0 .. 7 (kept); B has `frac` of its 64 pixels on A: inter / area == frac exactly (kept where the threshold is
+    frac: the test is `>`); C has one column more on A and B than that (overlap); D's score is `conf` exactly (kept); E's is the next
+    fp32 value below (ends the walk); F would be kept but comes after E. frac in {0.5, 0.25}; frac and conf dyadic."""
+    n = int(8 * frac)
+    boxes = [(0, 8, 0, 8), (0, 8, 8 - n, 16 - n), (0, 8, 15 - 2 * n, 23 - 2 * n), (2, 6, 30, 36), (0, 2, 36, 40), (6, 8, 36, 40)]
+    masks = torch.zeros(len(boxes), 8, 40, dtype=torch.bool)
+    for i, (y0, y1, x0, x1) in enumerate(boxes):
+        masks[i, y0:y1, x0:x1] = True
+    scores = torch.tensor([0.9, 0.8, 0.75, conf, below(conf), 0.3], dtype=torch.float32)
+    classes = torch.tensor([1, 2, 3, 4, 5, 6], dtype=torch.int64)
+    labels = torch.zeros(8, 40, dtype=torch.int32)
+    labels[:, 20:30] = 4
+    return masks, scores, classes, labels
+
+
+def combine_rounded_threshold_scene():
+    """4 x 32 for overlap_thresh = instances_confidence_thresh = 0.7, which a C float holds as 0.699999988: B has 7 of its 10 pixels
+    on A, and 7 / 10 in double is above that float (overlap) though not above the double 0.7; C's score is float32(0.7), which is
+    not below that float (kept) though below the double 0.7; D's is the next fp32 value below (ends the walk)."""
+    boxes = [(0, 4, 0, 7), (0, 1, 0, 10), (2, 4, 20, 30), (0, 2, 12, 18)]
+    masks = torch.zeros(len(boxes), 4, 32, dtype=torch.bool)
+    for i, (y0, y1, x0, x1) in enumerate(boxes):
+        masks[i, y0:y1, x0:x1] = True
+    scores = torch.tensor([0.9, 0.8, 0.7, below(0.7)], dtype=torch.float32)
+    classes = torch.tensor([1, 2, 3, 4], dtype=torch.int64)
+    labels = torch.zeros(4, 32, dtype=torch.int32)
+    labels[:, 16:32] = 2
+    return masks, scores, classes, labels
+
+
+IGNORED_LABELS = (256, 100000, -1)
+
+
+def combine_scene_with_ignored_labels():
+    """combine_scene() with the labels 256, 100000 and -1 painted over label-0 pixels that no kept instance covers (224, 224 and 24
+    pixels). -> (masks, scores, classes, labels as given to the kernel, labels with those pixels set to 0 for the reference)."""
+    masks, scores, classes, labels = combine_scene()
+    dirty = labels.clone()
+    dirty[2:16, 40:56], dirty[16:30, 40:56], dirty[0:2, 44:56] = IGNORED_LABELS
+    assert bool((labels[dirty != labels] == 0).all())
+    return masks, scores, classes, dirty, labels
+
+
+# (name, C, pitch, (h4, w4), crop, output) for osr_semseg_resample beyond one 56-class pass through LDS, and on degenerate maps
+RESAMPLE_WIDE_CASES = [
+    ("a", 57, 60, (5, 9), (19, 34), (23, 70)),      # the second pass holds exactly one real class
+    ("b", 133, 136, (5, 9), (19, 34), (23, 70)),    # three passes
+    ("c", 150, 152, (5, 9), (20, 36), (20, 36)),    # three passes, identity scale
+    ("d", 150, 152, (1, 7), (4, 27), (9, 65)),      # h4 == 1 (every second row tap clamps), a 65-pixel output row
+    ("e", 19, 20, (1, 1), (3, 2), (7, 5)),          # a single stride-4 cell
+]
+
+
+def resample_wide_logits(case, seed=21):
+    """Standard-normal logits (h4, w4, C) of a RESAMPLE_WIDE_CASES row under torch.manual_seed(seed)."""
+    _, c, _, (h4, w4), _, _ = case
+    torch.manual_seed(seed)
+    return torch.randn(h4, w4, c)
 
 
 def combine_scene():

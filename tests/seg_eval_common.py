@@ -107,6 +107,107 @@ class PQReference:
             self.counts[slot, 1] += 1
 
 
+def pq_matches(counts, gt_meta, pred_slot, ncat):
+    """The matches of one table in the contract's (g, p) order: [(g, p, slot, iou)] (g a row of gt_meta, p a predicted id).
+    PQReference.add restated as a list, for the checks on the synthesized tables below."""
+    counts = np.asarray(counts, dtype=np.int64)
+    area_p = counts.sum(axis=0)
+    out = []
+    for g in range(counts.shape[0] - 2):
+        slot, crowd, area_g, _ = (int(v) for v in gt_meta[g])
+        if crowd or not 0 <= slot < ncat:
+            continue
+        for p in np.nonzero(counts[1 + g, 1:])[0] + 1:
+            if int(pred_slot[p - 1]) != slot:
+                continue
+            inter = int(counts[1 + g, p])
+            iou = float(inter) / float(int(area_p[p]) + area_g - inter - int(counts[0, p]))
+            if iou > 0.5:
+                out.append((g, int(p), slot, iou))
+    return out
+
+
+PQ_LARGE = dict(G=1023, P=2047, ncat=1500, hot=(7, 1300))
+
+
+def pq_large_table(seed=0, G=PQ_LARGE["G"], P=PQ_LARGE["P"], ncat=PQ_LARGE["ncat"], hot=PQ_LARGE["hot"]):
+    """A sparse seeded (G + 2, P + 1) count table with consistent areas, built without pixels -> (counts int32, gt_meta (G, 4) int32,
+    pred_slot (P) int32). Every predicted id has one main row (the first G ids a permutation of the rows, so that every row has a
+    partner), up to two small side rows, VOID and unlisted-row mass on a fifth each; a few ids are empty. A quarter of the rows lie
+    in each of the two `hot` slots (one below 1024, one above), the others in random slots; some rows and ids carry slots outside
+    [0, ncat) on both sides; 6 % of the rows are crowds; hot[0] and every second other slot that has crowds mark their last one
+    crowd_pick, hot[1] marks none.
+    The last row and the last predicted id are partners in hot[1]."""
+    rng = np.random.default_rng(seed)
+    counts = np.zeros((G + 2, P + 1), dtype=np.int64)
+    slot_g = rng.integers(0, ncat, size=G)
+    u = rng.random(G)
+    slot_g[u < 0.25], slot_g[(u >= 0.25) & (u < 0.5)] = hot[0], hot[1]
+    slot_g[rng.choice(G - 1, size=6, replace=False)] = [-1, -7, ncat, ncat + 1, ncat + 500, -2]
+    slot_g[G - 1] = hot[1]
+    crowd = rng.random(G) < 0.06
+    crowd[G - 1] = False
+    main = np.concatenate((rng.permutation(G), rng.integers(0, G, size=P - G)))
+    slot_p = np.where(rng.random(P) < 0.75, slot_g[main], rng.integers(0, ncat, size=P))
+    slot_p[rng.choice(P - 1, size=6, replace=False)] = [-3, -1, ncat, ncat + 2, 2 * ncat, -100]
+    slot_p[P - 1] = hot[1]
+    empty = rng.choice(np.arange(1, P), size=5, replace=False)  # predicted ids without a pixel (never the last)
+    for p in range(1, P + 1):
+        if p in empty:
+            continue
+        counts[1 + main[p - 1], p] = rng.integers(60, 300) if p <= G else rng.integers(3, 40)  # (a row's first partner dominates it)
+        for g in rng.integers(0, G, size=rng.integers(0, 3)):
+            counts[1 + g, p] += rng.integers(1, 60)
+        if rng.random() < 0.2:
+            counts[0, p] = rng.integers(1, 80)      # VOID under the prediction
+        if rng.random() < 0.2:
+            counts[G + 1, p] = rng.integers(1, 80)  # ids the JSON does not list
+    counts[:, 0] = rng.integers(0, 50, size=G + 2)  # pixels without a prediction
+    counts[G, 1:], counts[:, P] = 0, 0                # the last row and the last id are partners, and little else
+    counts[G, P], counts[0, P], counts[G + 1, P] = 150, 7, 9
+    area_g = counts[1:G + 1].sum(axis=1)
+    pick = np.zeros(G, dtype=bool)
+    for i, s in enumerate(np.unique(slot_g[crowd])):
+        if s == hot[0] or (s != hot[1] and i % 2 == 0):
+            pick[np.nonzero(crowd & (slot_g == s))[0][-1]] = True
+    meta = np.stack((slot_g, crowd.astype(np.int64), area_g, pick.astype(np.int64)), axis=1)
+    return counts.astype(np.int32), meta.astype(np.int32), slot_p.astype(np.int32)
+
+
+def pq_multi_match_table(seed=5, G=40, P=90, ncat=4, slot=1, multi=(9, 17, 18, 30)):
+    """A table whose gt_meta areas are SMALLER than the row sums for the rows in `multi` (inconsistent areas: impossible from pixels,
+    allowed by the contract), so that those rows match two or three predicted ids each with IoU > 0.5. Every row lies in `slot` and
+    has one ordinary partner except the `multi` rows; the ids in between belong to another slot or overlap too little. The multi
+    rows' partners are spread over the ids, so that a row's terms are not neighbours in p.
+    -> (counts int32, gt_meta (G, 4) int32, pred_slot (P) int32)."""
+    rng = np.random.default_rng(seed)
+    counts = np.zeros((G + 2, P + 1), dtype=np.int64)
+    slot_p = np.full(P, (slot + 1) % ncat, dtype=np.int64)
+    area_g = np.zeros(G, dtype=np.int64)
+    ids = rng.permutation(P) + 1
+    nxt = 0
+    for g in range(G):
+        n = int(rng.integers(2, 4)) if g in multi else 1
+        inters = rng.integers(85, 100, size=n) if g in multi else rng.integers(60, 100, size=n)
+        for inter in inters:
+            p = ids[nxt]
+            nxt += 1
+            counts[1 + g, p] = inter
+            counts[G + 1, p] = rng.integers(0, 15)  # the prediction's pixels elsewhere
+            slot_p[p - 1] = slot
+        counts[1 + g, 0] = rng.integers(0, 10)
+        area_g[g] = int(inters.max()) + counts[1 + g, 0]  # (what one partner alone would leave of the row)
+    for p in ids[nxt:]:  # the other ids: the wrong slot, or the right one with too little overlap
+        g = int(rng.integers(0, G))
+        counts[1 + g, p] = rng.integers(1, 10)
+        counts[G + 1, p] = 100
+        slot_p[p - 1] = slot if rng.random() < 0.5 else (slot + 1) % ncat
+    single = np.array([g not in multi for g in range(G)])
+    area_g[single] = counts[1:G + 1].sum(axis=1)[single]
+    meta = np.stack((np.full(G, slot), np.zeros(G, dtype=np.int64), area_g, np.zeros(G, dtype=np.int64)), axis=1)
+    return counts.astype(np.int32), meta.astype(np.int32), slot_p.astype(np.int32)
+
+
 def sem_seg_figures(conf, names):
     """mIoU / fwIoU / mACC / pACC and the per-class figures from the (C + 1, C + 1) matrix, x100, with python loops."""
     m = np.asarray(conf, dtype=np.int64)[:-1, :-1]

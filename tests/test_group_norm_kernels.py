@@ -5,7 +5,7 @@ rounds once, the reference's own rounding is the other ulp. The statistics are f
 import pytest
 import torch
 
-from tests.panoptic_common import gn_merge_reference, gn_stats_reference
+from tests.panoptic_common import EPS, gn_merge_reference, gn_stats_reference
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -105,6 +105,43 @@ def test_group_means_thirty_standard_deviations_out(osr, dtype):
     gamma, beta = _affine(128, 6)
     out = ops.gn_relu_merge([(xd, (mean, rstd), gamma.to(DEV), beta.to(DEV), True)])
     _check(out, gn_merge_reference([(x, gamma, beta, True)]), dtype, "offset input merge")
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
+def test_a_constant_group_has_variance_zero(osr, dtype):
+    """Groups 3 and 17 are constant over the whole image (and over their channels): M2 is exactly zero and rstd = 1 / sqrt(eps)."""
+    ops = osr.ops
+    x = _input((2, 16, 20, 128), dtype, 7)
+    x[..., 12:16], x[..., 68:72] = 2.5, -0.375  # (exact in every storage type)
+    rmean, rrstd = gn_stats_reference(x)
+    assert float(rrstd[:, [3, 17]].min()) == float(rrstd.max()) == 1.0 / EPS ** 0.5
+    mean, rstd = ops.group_norm_stats(x.to(DEV))
+    for got, ref, what in ((mean, rmean, "mean"), (rstd, rrstd, "rstd")):
+        err = float((got.cpu().double() - ref).abs().max())
+        print(f"[gn] constant groups {what} {str(dtype)[6:]}: {err / float(ref.abs().max()):.3e}")
+        assert err <= 1e-4 * float(ref.abs().max()), (what, err)
+    assert bool((rstd.cpu()[:, [3, 17]].double() - 1.0 / EPS ** 0.5).abs().max() <= 1e-4 / EPS ** 0.5)
+    gamma, beta = _affine(128, 8)
+    out = ops.gn_relu_merge([(x.to(DEV), (mean, rstd), gamma.to(DEV), beta.to(DEV), False)])
+    _check(out, gn_merge_reference([(x, gamma, beta, False)]), dtype, "constant groups merge")
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
+@pytest.mark.parametrize("c", [64, 128, 256])
+def test_a_one_pixel_map(osr, c, dtype):
+    """h = w = 1: a group is c / 32 values, one thread per vector slot holds them all, 255 of the 256 threads' triples are empty."""
+    ops = osr.ops
+    x = _input((3, 1, 1, c), dtype, 9)
+    rmean, rrstd = gn_stats_reference(x)
+    mean, rstd = ops.group_norm_stats(x.to(DEV))
+    for got, ref, what in ((mean, rmean, "mean"), (rstd, rrstd, "rstd")):
+        err = float((got.cpu().double() - ref).abs().max())
+        print(f"[gn] 1 x 1 map c={c} {what} {str(dtype)[6:]}: {err / float(ref.abs().max()):.3e}")
+        assert err <= 1e-4 * float(ref.abs().max()), (what, err)
+    gamma, beta = _affine(c, 10)
+    for up2 in (False, True):
+        out = ops.gn_relu_merge([(x.to(DEV), (mean, rstd), gamma.to(DEV), beta.to(DEV), up2)])
+        _check(out, gn_merge_reference([(x, gamma, beta, up2)]), dtype, f"1 x 1 map c={c} up2={up2}")
 
 
 def test_bad_arguments_are_refused(osr):

@@ -12,7 +12,8 @@ is 2.2e-3; torch's own fp32 interpolation stays within e32 = 1.6e-5 of float64 a
   - requires logit within max(4 * e32, 1e-5) (4: another product order and fp32 coordinates);
   - requires score within a relative 4 * (e32 of the score), floor 1e-5.
 Measured on the MI355X: every position the reference's, |dx|, |dy| <= 9e-6 px; ten boxes |dlogit| 1.6e-5 (e32 1.6e-5), relative
-|dscore| 1.6e-5 (e32 1.6e-5); m = 32: 5.8e-6 / 5.7e-6 (e32 5.8e-6); 1333 x 800: 1.7e-6 / 1.7e-6 (e32 1.7e-6), gap 1.1e-3."""
+|dscore| 1.6e-5 (e32 1.6e-5); m = 32: 5.8e-6 / 5.7e-6 (e32 5.8e-6); 1333 x 800: 1.7e-6 / 1.7e-6 (e32 1.7e-6), gap 1.1e-3;
+m = 36, k = 17: 1.4e-5 / 1.4e-5 (e32 1.5e-5), gap 3.1e-3; m = 52, k = 17: 1.6e-5 / 1.6e-5 (e32 1.5e-5), gap 1.7e-2."""
 import functools
 
 import pytest
@@ -104,6 +105,19 @@ def test_smaller_maps_and_fewer_keypoints(ops):
     rois = boxes_at([(1.5, 2.25), (0.0, 4.0), (9.75, 0.5), (2.0, 2.0)], [(32, 32), (45.5, 70), (10, 13.25), (150, 90)])
     ref, r32 = decode_chain(maps, rois, torch.float64), decode_chain(maps, rois, torch.float32)
     _check(ops.heatmaps_to_keypoints(maps.to(DEV), rois.to(DEV)), ref, r32, "m = 32, k = 5")
+
+
+@pytest.mark.parametrize("m,seed", [(36, 31), (52, 33)])
+def test_the_map_sizes_of_the_other_pooler_resolutions(ops, m, seed):
+    """m = 4 s for s = 9 and 13: lanes m .. 63 of a wave sit out the vertical blend, the map is no multiple of the 256 staging threads.
+    Measured on the CPU: the float64 reference's smallest gap is 3.1e-3 (m = 36) and 1.7e-2 (m = 52); torch's fp32 chain picks the
+    same positions."""
+    torch.manual_seed(seed)
+    maps = 2 * torch.randn(4, 17, m, m)
+    rois = boxes_at([(1.5, 2.25), (0.0, 4.0), (9.75, 0.5), (2.0, 2.0)], [(m, m), (45.5, 70), (10, 13.25), (150, 90)])
+    ref, r32 = decode_chain(maps, rois, torch.float64), decode_chain(maps, rois, torch.float32)
+    assert torch.equal(r32["pos"], ref["pos"]), "torch's own fp32 interpolation picks the reference positions"
+    _check(ops.heatmaps_to_keypoints(maps.to(DEV), rois.to(DEV)), ref, r32, f"m = {m}, k = 17")
 
 
 def test_an_image_sized_box(ops):

@@ -8,7 +8,10 @@ A chain that rounded the 2s x 2s map to fp16 exceeds the bound (test_a_lossy_low
 
 (r, cin, k): (1, 64, 17) one chunk of the channel stream; (3, 512, 17) the production width, eight chunks (sixteen in fp32);
 (2, 128, 5); k = 1 and k = 32 the ends of the padded N tile (k = 32 takes two interpolation passes, as 17 does). s = 14 has a
-partial last M block (196 = 6 * 32 + 4), s = 8 exactly two."""
+partial last M block (196 = 6 * 32 + 4), s = 8 exactly two. s = 9 .. 13, the other sizes the entry point accepts: the index splits by a
+float reciprocal ((int)((m + 0.5f) * (1 / s)), also for 4s and 16 s^2 in the interpolation), partial last M blocks of 17, 4, 25, 16 and
+9 rows, and 648 .. 1352 prefetch pieces for 256 threads (three to six rounds, the last partial). Measured on the MI355X for s = 9 .. 13:
+err 0.6e-6 .. 2.8e-6 = 0.3 .. 1.4 e32 (bounds 1.5e-5 .. 9.7e-5)."""
 import functools
 
 import pytest
@@ -19,7 +22,8 @@ from tests.keypoint_common import upsample_chain
 DEV = "cuda:0"
 gpu = pytest.mark.gpu
 DTYPES = [torch.float16, torch.bfloat16, torch.float32]
-CASES = [(1, 64, 17, 14), (3, 512, 17, 14), (2, 128, 5, 14), (1, 64, 1, 14), (1, 64, 32, 14), (2, 128, 5, 8)]
+CASES = [(1, 64, 17, 14), (3, 512, 17, 14), (2, 128, 5, 14), (1, 64, 1, 14), (1, 64, 32, 14), (2, 128, 5, 8),
+         (1, 128, 17, 9), (1, 64, 17, 10), (1, 64, 17, 11), (1, 64, 5, 12), (2, 64, 17, 13)]
 
 
 @pytest.fixture(scope="module")

@@ -119,3 +119,14 @@ def test_limits_are_refused_with_nothing_launched(osr):
     assert lib.osr_pq_accumulate(a, 4, 2048, a, a, 3, a, a, a, None) == osr._lib.ERR_UNSUPPORTED
     assert lib.osr_pq_accumulate(a, 4, 4, a, a, 0, a, a, a, None) == -1 and b"categories" in lib.osr_last_error()
     assert lib.osr_pq_accumulate(None, 4, 4, a, a, 3, a, a, a, None) == -1 and b"null pointer" in lib.osr_last_error()
+
+
+@pytest.mark.gpu
+def test_a_workgroup_chunk_of_more_than_1024_pixels(osr):
+    """1100 x 1000 pixels exceed 4 * 256 CUs * 1024: se_chunk gives a workgroup 2048 pixels, its first pixel is no longer
+    blockIdx.x * 1024 and a thread walks eight pixels. On a device with more than 268 CUs the case stops reaching chunk > 1024."""
+    h, w = 1100, 1000
+    assert h * w > 4 * 256 * 1024
+    ids_map, pred = _blocky_case(h, w)
+    ref, bad = _check(osr, ids_map, GT_IDS, pred, 9)
+    assert bad == 0 and ref.sum() == h * w and ref[0].sum() > 0 and ref[len(GT_IDS) + 1].sum() > 0

@@ -1,11 +1,15 @@
 """osr_pq_accumulate (csrc/osr_seg_eval.hip) on maps of a few dozen pixels with known answers, fed through
 osr_panoptic_pair_counts: tp / fp / fn equal to the hand count and to the reference (tests/seg_eval_common.py), the IoU sums
-bit-equal to the float64 reference that adds in (image, gt id, pred id) order."""
+bit-equal to the float64 reference that adds in (image, gt id, pred id) order.
+
+At its table limits the kernel gets count tables synthesized in numpy (tests/seg_eval_common.py; their reach is asserted on the CPU in
+tests/test_pq_table_reference.py): G = 1023, P = 2047, ncat = 1500, where every strided loop of the one workgroup takes a second step
+and the LDS tables are filled to their ends; rows with several matches (the full-row walk of phase 3); two calls into one result."""
 import numpy as np
 import pytest
 import torch
 
-from tests.seg_eval_common import PQReference, ids_to_rgb, pair_counts_reference
+from tests.seg_eval_common import PQ_LARGE, PQReference, ids_to_rgb, pair_counts_reference, pq_large_table, pq_multi_match_table
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -167,3 +171,55 @@ def test_three_images_accumulate_in_order(osr):
         assert before != probe.iou
     assert all(sum(terms[s]) == iou[s] for s in (0, 1))
     assert any(sum(sorted(terms[s])) != iou[s] or sum(reversed(terms[s])) != iou[s] for s in (0, 1))
+
+
+class Tables:
+    """The device statistics and the reference, fed with the same synthesized count tables."""
+
+    def __init__(self, osr, ncat):
+        self.ops = osr.ops
+        self.counts = torch.zeros((ncat, 3), dtype=torch.int64, device=DEV)
+        self.iou = torch.zeros((ncat,), dtype=torch.float64, device=DEV)
+        self.flags = torch.zeros((3,), dtype=torch.int64, device=DEV)
+        self.ref = PQReference(ncat)
+
+    def add(self, table, meta, slots):
+        self.ops.pq_accumulate(torch.from_numpy(table).to(DEV), torch.from_numpy(meta).to(DEV), torch.from_numpy(slots).to(DEV), self.counts, self.iou, self.flags)
+        self.ref.add(table, meta, slots)
+        return self
+
+    def check(self):
+        got = self.counts.cpu().numpy()
+        assert np.array_equal(got, self.ref.counts), np.nonzero((got != self.ref.counts).any(axis=1))[0]
+        assert self.flags.tolist() == self.ref.flags.tolist()
+        iou, want = self.iou.cpu().numpy(), np.array(self.ref.iou, dtype=np.float64)
+        assert iou.tobytes() == want.tobytes(), np.nonzero(iou != want)[0]  # bit-equal
+        return got
+
+
+def test_the_largest_table_with_more_slots_than_threads(osr):
+    """G = 1023, P = 2047, ncat = 1500: 1025 table rows, 2047 ids, 2 094 081 pairs and 1500 slots for 1024 threads; matches in the last row,
+    the last column and slots on both sides of 1024; crowds with and without crowd_pick, VOID, unlisted rows, empty ids, unknown slots."""
+    t = Tables(osr, PQ_LARGE["ncat"]).add(*pq_large_table())
+    got = t.check()
+    assert got[:, 0].max() >= 100 and got[1024:, 0].sum() > 0 and got[:, 1].sum() > 0 and got[:, 2].sum() > 0 and min(t.flags.tolist()[1:]) > 0
+    again = Tables(osr, PQ_LARGE["ncat"]).add(*pq_large_table())
+    assert torch.equal(again.iou, t.iou) and torch.equal(again.counts, t.counts)
+
+
+def test_rows_with_several_matches_are_walked_in_p_order(osr):
+    """Inconsistent areas give four rows three matches each (g_nmatch > 1), between ordinary rows of the same slot: the sum is bit-equal
+    to the (g, p) order, which differs from the reversed, the p-major and the multi-rows-last orders (asserted on the CPU)."""
+    t = Tables(osr, 4).add(*pq_multi_match_table())
+    got = t.check()
+    assert got[1, 0] >= 3 * 2 + 2  # three rows with two matches and an ordinary row on either side, at the least
+
+
+def test_two_tables_of_different_size_accumulate(osr):
+    """The large table, then the multi-match table in the large one's first hot slot: the second call goes on from the first's sums."""
+    ncat, slot = PQ_LARGE["ncat"], PQ_LARGE["hot"][0]
+    t = Tables(osr, ncat).add(*pq_large_table())
+    first = t.check()[slot].copy()
+    before = float(t.iou[slot])
+    second = t.add(*pq_multi_match_table(ncat=ncat, slot=slot)).check()[slot]
+    assert second[0] > first[0] >= 100 and float(t.iou[slot]) > before > 0

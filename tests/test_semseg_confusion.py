@@ -151,3 +151,21 @@ def test_arguments_are_validated_without_a_gpu(osr):
     with pytest.raises(osr.OsrError):
         osr.ops.semseg_confusion(torch.zeros(4, 4, dtype=torch.int32), torch.zeros(4, 4, dtype=torch.uint8), 19, 255, torch.zeros(20, 20, dtype=torch.int64),
                                  torch.zeros(1, dtype=torch.int64))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("h,w", [(1100, 1000), (1099, 1001)], ids=["vector", "scalar"])
+def test_a_workgroup_chunk_of_more_than_1024_pixels(osr, h, w):
+    """se_chunk gives a workgroup 1024 pixels until the plane exceeds 4 * CUs * 1024 of them: 1 048 576 with 256 CUs. 1100 x 1000 (a
+    multiple of 4: the vector path) and 1099 x 1001 (the scalar path) lie above that: the chunk is 2048, a block's first pixel is no
+    longer blockIdx.x * 1024 and a thread takes a second step. On a device with more than 268 CUs these planes stop reaching
+    chunk > 1024; the comparison still holds there."""
+    c = 54
+    assert h * w > 4 * 256 * 1024 and (h * w % 4 == 0) == (h == 1100)
+    labels, gt = _maps(h, w, c, seed=21)
+    ref, bad = confusion_reference(labels, gt, c, IGNORE)
+    conf, invalid = _run(osr, labels.astype(np.int32), gt, c)
+    assert bad == 0 and int(invalid[0]) == 0 and ref[:, c].sum() > 0
+    assert np.array_equal(conf.cpu().numpy(), ref)
+    again, _ = _run(osr, labels.astype(np.int32), gt, c)
+    assert torch.equal(again, conf)
