@@ -203,7 +203,9 @@ osr_status osr_stem_pool_bwd(const void* s, const void* dpool, int32_t n, int32_
 int64_t osr_stem_wgrad_workspace_bytes(int32_t n, int32_t hp, int32_t wp);
 osr_status osr_stem_wgrad(const void* xpad, const void* ds, int32_t n, int32_t hp, int32_t wp, float* dw, int32_t accumulate, void* workspace,
                           int64_t workspace_bytes, int32_t dtype, void* stream);
-/* [d2] F.max_pool2d(k=3,s=2,p=1) of the ResNet stem, NHWC contiguous. */
+/* [d2] F.max_pool2d(k=3,s=2,p=1) of the ResNet stem, NHWC contiguous. Non-finite inputs included: the maximum starts at -inf and is
+ * replaced when (v > max) || isnan(v), scanning ky then kx -- a window of -inf gives -inf, +inf wins, a NaN once seen stays: the rule
+ * osr_stem_pool_bwd uses to find the same maximum. */
 osr_status osr_maxpool3x3s2(const void* in, int32_t n, int32_t hi, int32_t wi, int32_t c, void* out, int32_t dtype,
                             void* stream);
 /* [d2] LastLevelMaxPool: p6 = max_pool2d(p5, k=1, s=2) = stride-2 subsample, NHWC contiguous. */

@@ -60,7 +60,7 @@ __global__ __launch_bounds__(256) void maxpool_kernel(const T* __restrict__ in, 
         const int ox = (int)((i / c8) % wo), oy = (int)((i / ((long long)c8 * wo)) % ho), b = (int)(i / ((long long)c8 * wo * ho));
         float m[8];
 #pragma unroll
-        for (int k = 0; k < 8; ++k) m[k] = -3.402823466e38f;
+        for (int k = 0; k < 8; ++k) m[k] = -INFINITY;  // (a window of -inf pools to -inf; every window holds at least one pixel)
         for (int dy = 0; dy < 3; ++dy) {
             const int y = oy * 2 - 1 + dy;
             if (y < 0 || y >= hi) continue;
@@ -69,7 +69,10 @@ __global__ __launch_bounds__(256) void maxpool_kernel(const T* __restrict__ in, 
                 if (x < 0 || x >= wi) continue;
                 const t8 v = *reinterpret_cast<const t8*>(in + (((long long)b * hi + y) * wi + x) * c + cc);
 #pragma unroll
-                for (int k = 0; k < 8; ++k) m[k] = fmaxf(m[k], (float)v[k]);
+                for (int k = 0; k < 8; ++k) {  // torch's rule, and osr_stem_pool_bwd's: a NaN, once seen, stays
+                    const float f = (float)v[k];
+                    if (f > m[k] || f != f) m[k] = f;
+                }
             }
         }
         t8 o;

@@ -1,6 +1,7 @@
 """osr_deform_cols (the gather of a 3x3 deformable convolution) and ops.deform_conv2d against a float64 restatement of the definition in
 include/osr.h, written here with index arithmetic and torch.gather. Shapes: n = 2, c = 64, maps of 5 x 7 and 6 x 8 (odd and even, so
-stride 2 meets both edge cases; 2 x 35 x 9 x 8 = 5040 work items: twenty 256-lane blocks).
+stride 2 meets both edge cases; 2 x 35 x 9 x 8 = 5040 work items: ten 256-lane blocks at two items per lane, one trip round the
+kernel's loop each). The last test runs 6,451,200 items, more than three steps of the grid capped at 8192 blocks: a second trip.
 
 Bounds. u = 2^-24 (fp32 unit roundoff), S = the sum of |weight * value * m| over the four corners of one sample.
   gather: |err| <= 6 u S + half_ulp(ref, dtype). The kernel never rounds a sample position (the cell and the fraction come from the fp32
@@ -261,3 +262,25 @@ def test_unsupported_channel_counts_launch_nothing(ops):
             ops.deform_cols(x, om, 1, groups, False)
     with pytest.raises(ops.OsrError, match="om"):  # too few offset channels for the groups: refused, not read past the row
         ops.deform_cols(torch.ones((2, 5, 7, 64), device=DEV, dtype=F16), torch.zeros((2, 5, 7, 24), device=DEV), 1, 2, False)
+
+
+@pytest.mark.gpu
+def test_second_loop_iteration_past_the_grid_cap(ops):
+    """n, h, w, c = 2, 160, 140, 128 at stride 1 (fp16, modulated, two groups): 2 x 22400 x 9 x 16 = 6,451,200 work items against a grid
+    capped at 8192 blocks x 256 lanes = 2,097,152 items per step, two steps per trip round the loop. Every lane makes a second trip;
+    its second item there is live on the first 159,744 lanes only (3 steps + 159,744 = total) and dead on the rest. cols is this test's
+    own NaN-filled buffer, handed to the C entry: a row no lane wrote fails _check's finiteness. Same bound as above."""
+    n, h, w, c, G, dt = 2, 160, 140, 128, 2, F16
+    total = n * h * w * 9 * (c // 8)
+    assert total == 6451200 and total > 3 * 8192 * 256, "the shape must need a second trip, with a live and a dead second item"
+    x = _x((n, h, w, c), dt, 60)
+    g = torch.Generator(device=DEV).manual_seed(61)
+    om = torch.randn((n, h, w, offset_channels(G, True)), generator=g, device=DEV) * 1.5
+    omp = _padded_om(om)
+    cols = torch.full((n * h * w, 9, c), NAN, device=DEV, dtype=dt)
+    status = ops._lib.load().osr_deform_cols(C.c_void_p(x.data_ptr()), C.c_void_p(omp.data_ptr()), n, h, w, c, h, w, int(omp.shape[3]), 1, G, 1,
+                                             C.c_void_p(cols.data_ptr()), ops._lib.OSR_F16, C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    assert status == 0
+    torch.cuda.synchronize()
+    ref, S = ref_cols(x, om, 1, G, True)
+    _check(cols, ref, S, dt, "160x140 past the grid cap")

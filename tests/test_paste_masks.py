@@ -96,3 +96,49 @@ def test_other_thresholds_and_sizes(ops):
 def test_no_masks(ops):
     out = ops.paste_masks(torch.zeros(0, M, M, device=DEV), torch.zeros(0, 4, device=DEV), H, W)
     assert out.shape == (0, H, W) and out.dtype == torch.uint8
+
+
+def test_degenerate_boxes_paste_nothing(ops):
+    """Among the ordinary boxes: a zero-width box, a zero-height box, a box with a NaN coordinate and one with x1 = inf paste nothing --
+    an all-zero plane, every byte written over the 0xFF fill. (Zero extent: the sample coordinate is +-inf, never 0 / 0, as no pixel
+    centre x + 0.5 equals the integer edge. NaN: every comparison is false. x1 = inf: every pixel samples u = -0.5, half of the
+    mask's first column, below the threshold 0.5 as every probability is below 1 -- a condition on the inputs, asserted.)
+    The inverted box (x1 < x0) is no special case of the definition: u = M - 1 - u' of the box with its edges swapped, so the
+    float64 grid_sample restatement pastes the mask mirrored along x into [x1, x0], and so must the kernel."""
+    masks, boxes = _inputs()
+    assert float(masks.max()) < 1.0 - 1e-4
+    boxes[4] = torch.tensor([20.0, 5.0, 20.0, 30.0])           # zero width
+    boxes[5] = torch.tensor([10.0, 12.0, 40.0, 12.0])          # zero height
+    boxes[6] = torch.tensor([40.0, 5.0, 12.0, 30.0])           # inverted along x
+    boxes[7] = torch.tensor([float("nan"), 5.0, 30.0, 20.0])   # a NaN coordinate
+    boxes[8] = torch.tensor([10.0, 5.0, float("inf"), 20.0])   # an inf coordinate
+    nothing = [4, 5, 7, 8]
+    rest = [i for i in range(12) if i not in nothing]
+    ref = _reference(masks[rest], boxes[rest])
+    want = (ref >= THR).to(torch.uint8)
+    band = (ref - THR).abs() < 1e-5
+    assert int(band.sum()) < 1e-3 * int((ref > 0).sum()), "too many reference values at the threshold: choose other inputs"
+    inv = rest.index(6)
+    swapped = boxes[6:7, [2, 1, 0, 3]]
+    assert torch.equal(want[inv], (_reference(torch.flip(masks[6:7], dims=[-1]), swapped) >= THR).to(torch.uint8)[0]) and int(want[inv].sum()) > 0
+    out = torch.full((12, H, W), 0xFF, dtype=torch.uint8, device=DEV)
+    got = ops.paste_masks(masks.to(DEV), boxes.to(DEV), H, W, THR, out=out).cpu()
+    assert set(got.unique().tolist()) <= {0, 1}, "every byte is written, 0 or 1"
+    for i in nothing:
+        assert int(got[i].sum()) == 0, f"box {i} ({boxes[i].tolist()}) pasted something"
+    diff = (got[rest] != want) & ~band
+    print(f"ordinary and inverted boxes: {int(want.sum())} ones, {int(band.sum())} in the threshold band, {int(diff.sum())} differ")
+    assert int(diff.sum()) == 0
+
+
+def test_a_value_exactly_at_the_threshold_is_pasted(ops):
+    """A mask of 0.5 everywhere in the box (0, 0, W, H) at threshold 0.5: one pixel in from each edge all four taps lie inside the mask,
+    their weights sum to 1 and the blend of equal values is the value (products by 0.5 are exact; (1 - a) + a rounds to 1 for every
+    fraction a of a coordinate >= 0.25) -- with >= every interior byte is 1. (On the rim a tap is outside: half the value, 0.)"""
+    masks = torch.full((1, M, M), 0.5)
+    boxes = torch.tensor([[0.0, 0.0, float(W), float(H)]])
+    out = torch.full((1, H, W), 0xFF, dtype=torch.uint8, device=DEV)
+    got = ops.paste_masks(masks.to(DEV), boxes.to(DEV), H, W, 0.5, out=out).cpu()
+    assert set(got.unique().tolist()) <= {0, 1}, "every byte is written, 0 or 1"
+    inner = got[0, 1:-1, 1:-1]
+    assert int(inner.sum()) == inner.numel(), f"{inner.numel() - int(inner.sum())} interior pixels at the threshold were not pasted"
