@@ -718,6 +718,7 @@ osr_status osr_heatmaps_to_keypoints(const float* maps, const float* rois, int64
  * t and both with t. workspace 6 KiB. At most 2^24 pixels in all (the counts are exact). Repeats are bit-identical.
  * osr_mask_loss_bwd: d_logits (rows, m_side, m_side) = (sigmoid(l) - t) * scale / max(foreground rows * m_side^2, 1) on counted
  * rows, exact zeros elsewhere; every element written. workspace 16 bytes.
+ * rows == 0 (logits, targets and classes may then be NULL whatever num_rows): out6 is six zeros, d_logits is not touched.
  *
  * osr_mask_upsample_predict_bwd: the backward of osr_mask_upsample_predict_ex's logits, same x / w_packed / bias / pred_w /
  * num_rows / classes / rows_valid / seg_rows contract, fp16 / bf16, cin <= 448, s >= 8 (a tile of 64 rows reaches at most two RoIs).

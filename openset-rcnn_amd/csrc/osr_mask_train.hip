@@ -124,7 +124,7 @@ static const char* mask_loss_fill(MaskLoss* p, const float* logits, const uint8_
     if (rows < 0 || m_side < 1 || m_side > 256 || num_rows < 1) return "bad rows / m_side / num_rows";
     if (rows > 0 && (!logits || !targets)) return "null pointer";
     if (rows_valid && seg_rows < 1) return "rows_valid needs seg_rows >= 1";
-    if (num_rows > 1 && !classes) return "a class-specific predictor needs classes";
+    if (rows > 0 && num_rows > 1 && !classes) return "a class-specific predictor needs classes";
     *p = MaskLoss{logits, targets, (const long long*)classes, rows_valid, (long long)rows, m_side * m_side, num_rows, seg_rows};
     return nullptr;
 }
