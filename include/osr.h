@@ -924,6 +924,67 @@ osr_status osr_panoptic_pair_counts(const uint8_t* gt_rgb, const int32_t* gt_ids
 osr_status osr_pq_accumulate(const int32_t* counts, int32_t num_gt, int32_t num_pred, const int32_t* gt_meta, const int32_t* pred_slot,
                              int32_t num_categories, int64_t* pq_counts, double* pq_iou, int64_t* flags, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * COCO box and keypoint AP: the per-image half of pycocotools' COCOeval (computeIoU / computeOks and evaluateImg),
+ * csrc/osr_coco_eval.hip. pycocotools is not at hand: the rules are written from memory of pycocotools 2.0 and detectron2 v0.6, and
+ * THIS TEXT is the contract; host/coco_evaluation.py's numpy COCOeval states the same rules as a literal sequential loop and the
+ * tests hold the two against each other.
+ *
+ * osr_coco_match: ONE launch scores n images against their ground truth, for every (image, category) group, every area range and
+ * every IoU threshold. No host sync, no atomics, capturable, repeats are bit-identical. Every argument is validated before anything
+ * is launched (no GPU needed for a refusal); n == 0 or cap == 0 is OSR_OK without a launch.
+ *
+ * Detections, the engines' padded lists (need not be sorted): boxes (n, cap, 4) fp32 xyxy, scores (n, cap) fp32, classes (n, cap)
+ * int64 contiguous ids, counts (n) int32 (clamped to 0 .. cap); task OSR_COCO_KEYPOINTS also keypoints (n, cap, Kp, 3) fp32
+ * {x, y, score} (NULL for OSR_COCO_BBOX, where num_keypoints is not read).
+ * Ground truth, built by the host from the JSON, grouped by (image, category) in the JSON's annotation order: gt_seg_off
+ * (n * K + 1) int32, group i * K + c owns entries gt_seg_off[i * K + c] .. gt_seg_off[i * K + c + 1]; gt_box (NG, 4) fp64 xywh;
+ * gt_area (NG) fp64; gt_flags (NG) uint8, bit 0 iscrowd, bit 1 ignore; keypoints only: gt_kpts (NG, Kp, 3) fp64 {x, y, v} and
+ * sigmas (Kp) fp64. max_gt_per_group: the largest group, which the host knows since it built the table (a longer group is cut there).
+ * Host arrays: iou_thrs (T) fp64, passed as the doubles np.linspace(.5, .95, 10) gives and never recomputed; area_rng (A, 2) fp64
+ * {lo, hi}; max_det.
+ *
+ * Per (image i, category c):
+ *   - the detection list is the rows r < counts[i] with classes[i][r] == c, by descending score, equal scores the lower row first
+ *     (mergesort's stable order; scores compare by their order-preserving bit key, -0 == +0), cut to max_det. rank (n, cap) int32
+ *     is the row's position in that list, -1 for rows >= counts[i], rows whose class is outside [0, K) and rows beyond max_det;
+ *   - detection geometry, as detectron2's instances_to_coco_json followed by COCO.loadRes. bbox: x = x0, y = y0, w = x1 - x0 and
+ *     h = y1 - y0 in fp32, then widened to fp64, area = w * h in fp64. keypoints: x - 0.5 and y - 0.5 in fp32, then widened,
+ *     area = (max x - min x) * (max y - min y) over the Kp points;
+ *   - similarity, fp64. bbox, maskUtils.iou on xywh: iw = max(min(dx + dw, gx + gw) - max(dx, gx), 0), ih likewise,
+ *     inter = iw * ih, union = (dw * dh + gw * gh) - inter, or dw * dh for a crowd ground truth; inter / union, 0 where the union
+ *     is not positive. keypoints, computeOks: k1 = the ground truth's points with v > 0; if k1 > 0: dx = xd - xg, dy = yd - yg;
+ *     otherwise with its bbox (bx, by, bw, bh): x0 = bx - bw, x1 = bx + bw * 2, y0 and y1 likewise, dx = max(0, x0 - xd) +
+ *     max(0, xd - x1), dy likewise; e = (dx * dx + dy * dy) / (2 sigma)^2 / (gt_area + 2^-52) / 2; oks = the sum of exp(-e) over
+ *     the points with v > 0, in ascending point order, divided by k1; over all Kp points and divided by Kp when k1 == 0;
+ *   - in area range a a ground truth is ignored when its ignore bit is set or its area is outside [lo, hi];
+ *   - per threshold t the detections are matched in list order. thr = min(t, 1 - 1e-10). A ground truth is available when no
+ *     earlier detection of this (t, a) took it, or it is crowd. Among the available, not ignored ground truths with similarity >=
+ *     thr the detection takes the largest similarity, equal similarities going to the HIGHEST position in the group (pycocotools'
+ *     loop replaces on `not <`); if there is none, the same rule among the available ignored ones; else it stays unmatched. This
+ *     equals pycocotools' loop over the ground truths sorted ignored-last (stably) with its break;
+ *   - a matched detection is ignored iff its ground truth is ignored at a; an unmatched one iff its own area is outside [lo, hi].
+ *
+ * Outputs (all written in full by the call): flags (n, cap, A) uint32, bit t = matched at threshold t, bit 16 + t = ignored at
+ * threshold t, 0 where rank is -1; rank; match (n, cap, A, T) int32 or NULL: the matched ground truth's index into gt_*, else -1.
+ * The similarity matrix goes to `sim` when given, else to `workspace` (sim NULL): either holds
+ * osr_coco_match_workspace_bytes(cap, max_det, NG) = min(cap, max_det) * NG * 8 bytes. Layout: group (i, c) with G ground truths
+ * starting at g0 = gt_seg_off[i * K + c] and M listed detections owns the doubles from g0 * min(cap, max_det); entry
+ * [rank d][position j] is at d * G + j. Entries outside the groups' M x G blocks are not written.
+ *
+ * Limits, OSR_ERR_UNSUPPORTED with nothing launched beyond them: cap <= 1024, max_det <= 128, T <= 16, A <= 8, Kp <= 32,
+ * max_gt_per_group <= 4096. K >= 1, n * K < 2^31. A NaN score orders by its bit pattern; NaN similarities match nothing.
+ * --------------------------------------------------------------------------------------------------------- */
+#define OSR_COCO_BBOX 0
+#define OSR_COCO_KEYPOINTS 1
+int64_t osr_coco_match_workspace_bytes(int32_t cap, int32_t max_det, int32_t num_gt);
+osr_status osr_coco_match(int32_t task, const float* boxes, const float* scores, const int64_t* classes, const int32_t* counts,
+                          const float* keypoints, int32_t n, int32_t cap, int32_t num_categories, int32_t num_keypoints,
+                          const int32_t* gt_seg_off, const double* gt_box, const double* gt_area, const uint8_t* gt_flags,
+                          const double* gt_kpts, const double* sigmas, int32_t num_gt, int32_t max_gt_per_group, const double* iou_thrs,
+                          int32_t num_thrs, const double* area_rng, int32_t num_areas, int32_t max_det, uint32_t* flags, int32_t* rank,
+                          int32_t* match, double* sim, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* =========================================================================================================
  * Training step, forward half: targets and losses. Gradients are not
  * produced by this library yet; every function below is a forward kernel whose outputs equal the reference's

@@ -35,6 +35,7 @@ SOURCES = {
     "osr_semseg.hip": [],
     "osr_panoptic.hip": [],
     "osr_seg_eval.hip": [],
+    "osr_coco_eval.hip": ["-ffp-contract=off"],  # (fp64 similarities that round like numpy's: the bbox flags are bit-exact)
     "osr_roi_align.hip": ["-ffp-contract=off"],
     "osr_det_tail.hip": ["-ffp-contract=off"],
     "osr_cascade.hip": ["-ffp-contract=off"],  # (decodes and matches like osr_det_tail.hip / osr_std_train.hip)

@@ -106,6 +106,8 @@ PANOPTIC_MAX_INSTANCES = 1024  # csrc/osr_panoptic.hip PC_MAX_K
 PANOPTIC_MAX_STUFF = 255       # labels 1 .. 255
 CONF_LABELS, CONF_VALUES = 0, 1
 PQ_MAX_GT, PQ_MAX_PRED = 1023, 2047  # csrc/osr_seg_eval.hip PP_MAX_G / PP_MAX_P
+COCO_BBOX, COCO_KEYPOINTS = 0, 1
+COCO_MAX_CAP, COCO_MAX_DET, COCO_MAX_THRS, COCO_MAX_AREAS, COCO_MAX_KPTS, COCO_MAX_GROUP = 1024, 128, 16, 8, 32, 4096  # csrc/osr_coco_eval.hip CM_MAX_*
 
 
 class Pyramid(C.Structure):
@@ -177,6 +179,9 @@ PROTOTYPES = {
     "osr_semseg_confusion": (I32, [P, I32, P, I32, I32, I32, I32, P, P, P]),
     "osr_panoptic_pair_counts": (I32, [P, P, I32, P, I32, I32, I32, P, P, P]),
     "osr_pq_accumulate": (I32, [P, I32, I32, P, P, I32, P, P, P, P]),
+    # COCO box / keypoint matching (csrc/osr_coco_eval.hip)
+    "osr_coco_match_workspace_bytes": (I64, [I32, I32, I32]),
+    "osr_coco_match": (I32, [I32, P, P, P, P, P, I32, I32, I32, I32, P, P, P, P, P, P, I32, I32, P, I32, P, I32, I32, P, P, P, P, P, I64, P]),
     "osr_fastrcnn_candidates": (I32, [P, P, I32, I32, P, P, I32, I32, P, P, F32, P, P, P, P, P, P]),
     "osr_cascade_refine": (I32, [P, P, P, I32, I32, P, P, I32, P, P, P, I32, I32, F32, P, P, P, P, P, P, P]),
     "osr_cascade_candidates": (I32, [P, I32, P, I32, P, P, I32, I32, P, P, F32, P, P, P, P, P, P]),

@@ -143,6 +143,27 @@ def register_graspnet_instances(name: str, json_file: str, image_root: str) -> N
     meta.json_file, meta.image_root, meta.evaluator_type = json_file, image_root, "coco"
 
 
+def register_coco_instances(name: str, metadata: dict, json_file: str, image_root: str) -> None:
+    """[d2] register_coco_instances: a plain COCO instances (or person-keypoints) dataset. `closed_set` tells get_evaluator that the
+    name is scored with COCOEvaluator (box and keypoint AP); a GraspNet registration carries no such mark."""
+    DatasetCatalog.register(name, lambda: load_coco_json(json_file, image_root, name))
+    meta = MetadataCatalog.get(name)
+    for k, v in dict(metadata).items():
+        setattr(meta, k, v)
+    meta.json_file, meta.image_root, meta.evaluator_type, meta.closed_set = json_file, image_root, "coco", True
+
+
+def register_builtin_coco(root: str) -> None:
+    """coco_2017_{train,val} and keypoints_coco_2017_{train,val} under detectron2's directory names, when their files exist:
+    coco/{train,val}2017 with coco/annotations/instances_{split}2017.json and coco/annotations/person_keypoints_{split}2017.json."""
+    coco = os.path.join(root, "coco")
+    for split in ("train", "val"):
+        for name, jf in ((f"coco_2017_{split}", f"instances_{split}2017.json"), (f"keypoints_coco_2017_{split}", f"person_keypoints_{split}2017.json")):
+            jf = os.path.join(coco, "annotations", jf)
+            if os.path.isfile(jf):
+                register_coco_instances(name, {}, jf, os.path.join(coco, f"{split}2017"))
+
+
 def register_graspnet_os(root: str) -> None:
     for name, jf in GRASPNET_SPLITS.items():
         register_graspnet_instances(name, os.path.join(root, "graspnet_os", "annotations", jf), os.path.join(root, "graspnet_os", "images"))
@@ -242,8 +263,9 @@ def register_coco_panoptic(root: str) -> None:
 
 def get_evaluator(cfg, dataset_name: str, output_folder=None):
     """train.py:57-78: "pascal_voc" -> open-set VOC evaluator, "coco" -> open-set COCO-style evaluator (GraspNet); [d2] train_net.py:
-    "sem_seg" -> SemSegEvaluator, "coco_panoptic_seg" -> SemSegEvaluator + COCOPanopticEvaluator (box / mask AP for these datasets
-    is not built: there is no pycocotools)."""
+    "coco" on a register_coco_instances name (metadata closed_set) -> COCOEvaluator (box and keypoint AP; segm is not built),
+    "sem_seg" -> SemSegEvaluator, "coco_panoptic_seg" -> SemSegEvaluator + COCOPanopticEvaluator (box AP is not wired into the
+    panoptic datasets)."""
     from .evaluation import PascalVOCDetectionEvaluator
     meta = MetadataCatalog.get(dataset_name)
     if getattr(meta, "evaluator_type", None) in ("sem_seg", "coco_panoptic_seg"):
@@ -256,6 +278,11 @@ def get_evaluator(cfg, dataset_name: str, output_folder=None):
         if cfg.MODEL.PANOPTIC_FPN.COMBINE.ENABLED:
             evaluators.append(COCOPanopticEvaluator(dataset_name, output_folder))
         return DatasetEvaluators(evaluators)
+    if getattr(meta, "evaluator_type", None) == "coco" and getattr(meta, "closed_set", False):
+        from .coco_evaluation import COCOEvaluator
+        if not hasattr(meta, "thing_dataset_id_to_contiguous_id"):
+            DatasetCatalog[dataset_name]()  # loading the json fills the category tables
+        return COCOEvaluator(dataset_name, cfg, output_folder, max_dets_per_image=cfg.TEST.DETECTIONS_PER_IMAGE)
     if getattr(meta, "evaluator_type", None) == "coco":
         from .os_coco_evaluation import OpensetCOCOEvaluator
         if not hasattr(meta, "thing_dataset_id_to_contiguous_id"):

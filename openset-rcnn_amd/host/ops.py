@@ -1710,6 +1710,56 @@ def pq_accumulate(counts: torch.Tensor, gt_meta: torch.Tensor, pred_slot: torch.
                                 _stream()), "osr_pq_accumulate")
 
 
+# ---- COCO box / keypoint matching (csrc/osr_coco_eval.hip; host/coco_evaluation.py) ------------------------------------------------------
+def coco_match(boxes: torch.Tensor, scores: torch.Tensor, classes: torch.Tensor, counts: torch.Tensor, num_categories: int, gt_seg_off: torch.Tensor,
+               gt_box: torch.Tensor, gt_area: torch.Tensor, gt_flags: torch.Tensor, max_gt_per_group: int, iou_thrs: Sequence[float],
+               area_rng: Sequence[Sequence[float]], max_det: int, keypoints: Optional[torch.Tensor] = None, gt_kpts: Optional[torch.Tensor] = None,
+               sigmas: Optional[torch.Tensor] = None, want_match: bool = False, want_sim: bool = False):
+    """A batch of images scored against its ground truth in one launch (include/osr.h osr_coco_match, which states every rule).
+    boxes (n, cap, 4) fp32 xyxy, scores (n, cap) fp32, classes (n, cap) int64, counts (n) int32; gt_seg_off (n * K + 1) int32,
+    gt_box (NG, 4) / gt_area (NG) float64, gt_flags (NG) uint8; iou_thrs and area_rng are host sequences of doubles. With
+    `keypoints` (n, cap, Kp, 3) fp32 the task is OKS and needs gt_kpts (NG, Kp, 3) and sigmas (Kp) float64.
+    -> (flags (n, cap, A) int32 holding the uint32 words, rank (n, cap) int32, match (n, cap, A, T) int32 or None, sim (min(cap,
+    max_det) * NG) float64 in the header's layout or None)."""
+    lib = _lib.load()
+    kp = keypoints is not None
+    _need(boxes, torch.float32, "boxes"); _need(scores, torch.float32, "scores"); _need(classes, torch.int64, "classes"); _need(counts, torch.int32, "counts")
+    _need(gt_seg_off, torch.int32, "gt_seg_off"); _need(gt_box, torch.float64, "gt_box"); _need(gt_area, torch.float64, "gt_area")
+    _need(gt_flags, torch.uint8, "gt_flags")
+    if boxes.dim() != 3 or boxes.shape[2] != 4:
+        raise OsrError(f"coco_match: boxes {tuple(boxes.shape)} must be (n, cap, 4)")
+    n, cap = int(boxes.shape[0]), int(boxes.shape[1])
+    k, ng = int(num_categories), int(gt_area.numel())
+    kpn = 0
+    if kp:
+        _need(keypoints, torch.float32, "keypoints")
+        if gt_kpts is None or sigmas is None:
+            raise OsrError("coco_match: the keypoint task needs gt_kpts and sigmas")
+        _need(gt_kpts, torch.float64, "gt_kpts"); _need(sigmas, torch.float64, "sigmas")
+        kpn = int(sigmas.numel())
+        if keypoints.dim() != 4 or tuple(keypoints.shape) != (n, cap, kpn, 3) or tuple(gt_kpts.shape) != (ng, kpn, 3):
+            raise OsrError(f"coco_match: keypoints {tuple(keypoints.shape)} must be {(n, cap, kpn, 3)}, gt_kpts {tuple(gt_kpts.shape)} {(ng, kpn, 3)}")
+    if tuple(scores.shape) != (n, cap) or tuple(classes.shape) != (n, cap) or counts.numel() != n or gt_seg_off.numel() != n * k + 1 or \
+            tuple(gt_box.shape) != (ng, 4) or gt_flags.numel() != ng:
+        raise OsrError(f"coco_match: scores {tuple(scores.shape)} / classes {tuple(classes.shape)} must be {(n, cap)}, counts ({n}), gt_seg_off "
+                       f"({n * k + 1}) got {gt_seg_off.numel()}, gt_box {tuple(gt_box.shape)} ({ng}, 4), gt_flags ({ng})")
+    thrs = [float(v) for v in iou_thrs]
+    rng = [float(v) for r in area_rng for v in r]
+    t, a = len(thrs), len(rng) // 2
+    dev = boxes.device
+    flags = torch.empty((n, cap, a), dtype=torch.int32, device=dev)
+    rank = torch.empty((n, cap), dtype=torch.int32, device=dev)
+    match = torch.empty((n, cap, a, t), dtype=torch.int32, device=dev) if want_match else None
+    ws_bytes = int(lib.osr_coco_match_workspace_bytes(cap, int(max_det), ng))
+    sim = torch.empty((max(ws_bytes, 0) // 8,), dtype=torch.float64, device=dev)  # the matrix itself; handed over as `sim` or as the workspace
+    check(lib.osr_coco_match(_lib.COCO_KEYPOINTS if kp else _lib.COCO_BBOX, _p(boxes), _p(scores), _p(classes), _p(counts), _p(keypoints) if kp else None,
+                             n, cap, k, kpn, _p(gt_seg_off), _p(gt_box) if ng else None, _p(gt_area) if ng else None, _p(gt_flags) if ng else None,
+                             _p(gt_kpts) if kp and ng else None, _p(sigmas) if kp else None, ng, int(max_gt_per_group), (C.c_double * t)(*thrs), t,
+                             (C.c_double * (2 * a))(*rng), a, int(max_det), _p(flags), _p(rank), _p(match), _p(sim) if want_sim else None,
+                             None if want_sim else _p(sim), 0 if want_sim else ws_bytes, _stream()), "osr_coco_match")
+    return flags, rank, match, (sim if want_sim else None)
+
+
 # ---- test-time augmentation glue (csrc/osr_tta.hip; host/tta.py) ---------------------------------------------------------------
 def _tta_lists(boxes, counts, sizes, name):
     _need(boxes, torch.float32, "boxes"); _need(counts, torch.int32, "counts"); _need(sizes, torch.int32, "sizes")

@@ -8,7 +8,8 @@ back and does not synchronise. The statistics stay on the device for the whole d
 device-to-host copy, gathers them on rank 0 (host.parallel) and does the final arithmetic in float64 numpy. There is no CPU
 fallback: a prediction that is not on the GPU is refused by the ops, like everywhere else.
 
-Not built: box / mask AP for these datasets (that needs pycocotools' COCOeval) and TEST.AUG for the two meta-architectures."""
+Not built: mask AP, box AP under the panoptic dataset names (host/coco_evaluation.py scores plain COCO instances datasets) and
+TEST.AUG for the two meta-architectures."""
 from __future__ import annotations
 
 import json

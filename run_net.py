@@ -97,6 +97,7 @@ def register_datasets(cfg):
     D.register_opendet_voc_coco(root)
     D.register_builtin_pascal_voc(root)
     D.register_coco_panoptic(root)
+    D.register_builtin_coco(root)
     return D
 
 
@@ -138,7 +139,8 @@ def do_test(cfg, args, model, D, iteration: int = 0):
         results[name] = res
         if res is not None:
             logger.info("Evaluation results for %s:", name)
-            flat = res.get("bbox", res) if isinstance(res, dict) else res
+            multi = isinstance(res, dict) and "bbox" in res and "keypoints" in res  # COCOEvaluator with both tasks: one line each
+            flat = res if multi else res.get("bbox", res) if isinstance(res, dict) else res
             if flat and all(isinstance(v, dict) for v in flat.values()):  # one line per task (sem_seg, panoptic_seg)
                 for task, figures in flat.items():
                     logger.info("  %s: %s", task, ", ".join(f"{k}={v:.4f}" for k, v in figures.items()))
