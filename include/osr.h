@@ -430,6 +430,20 @@ osr_status osr_rpn_select_ex(const osr_rpn_levels* lv, const float* cell_anchors
                              int32_t* src_index, int32_t* batch_idx, int32_t* level_out, int32_t* counts,
                              int32_t* status_flags, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* osr_rpn_select_ex for a single-scale RPN ([d2] Base-RCNN-C4.yaml: one level, 15 anchors per cell, PRE_NMS_TOPK_TEST 6000): the
+ * same contract word for word -- stable top-k (value descending, lower index first), NaN first and flagged, both decode modes,
+ * level_out, padding -- with pre_nms_topk 1 .. OSR_RPN_SELECT_WIDE_MAXK. Above that: OSR_ERR_UNSUPPORTED, nothing launched (the
+ * capacity / workspace queries return it too). For pre_nms_topk <= 2048 every output is bit-identical to osr_rpn_select_ex: the two
+ * run one kernel, instantiated with a 2048-pair and an 8192-pair list in LDS (16 KiB / 64 KiB beside the 8 KiB histogram). */
+#define OSR_RPN_SELECT_WIDE_MAXK 8192
+int32_t osr_rpn_select_wide_capacity(const osr_rpn_levels* lv, int32_t pre_nms_topk);
+int64_t osr_rpn_select_wide_workspace_bytes(const osr_rpn_levels* lv, int32_t n, int32_t pre_nms_topk);
+osr_status osr_rpn_select_wide(const osr_rpn_levels* lv, const float* cell_anchors, const float* ctr, const float* deltas,
+                               int32_t n, const int32_t* image_hw, int32_t pre_nms_topk, float min_box_size,
+                               int32_t decode_mode, const float reg_weights[4], float* boxes, float* scores,
+                               int32_t* src_index, int32_t* batch_idx, int32_t* level_out, int32_t* counts,
+                               int32_t* status_flags, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---------------------------------------------------------------------------------------------------------
  * RoIAlign over the pyramid: [d2] ROIPooler.forward (level = floor(4+log2(sqrt(area)/224+1e-8)) clamped to
  * [min,max]) -> torchvision roi_align(aligned=True, sampling_ratio=0) (osrcnn_roi_heads.py:108-113,306).
@@ -495,6 +509,24 @@ osr_status osr_roi_align_fwd_ordered_opt(const osr_pyramid* feats, int32_t feat_
                                          int32_t canonical_size, int32_t min_level, const int32_t* order,
                                          const int32_t* order_nvalid, int32_t flags, const osr_roi_options* options, void* out,
                                          int32_t out_dtype, void* stream);
+/* osr_roi_align_fwd_ordered_opt for a consumer that reads every bin_stride-th bin only ([d2] Res5ROIHeads with STRIDE_IN_1X1: res5's
+ * first block enters through two 1 x 1 convolutions of stride 2, which read the even bins of the 14 x 14 grid and nothing else).
+ * out is (m, q, q, c) with q = ceil(pooled / bin_stride) and holds bins (bin_stride * i, bin_stride * j) of the pooled x pooled grid,
+ * each bit-identical to the same bin of osr_roi_align_fwd_ordered_opt; the other bins are neither sampled nor written.
+ * bin_stride 1 is that call. bin_stride 2 is served for pooled 8 .. OSR_ROI_MAX_POOLED_FWD (the per-sample kernel); any other
+ * pair returns OSR_ERR_UNSUPPORTED with nothing launched. Options, flags, padding rule and order independence as there. */
+osr_status osr_roi_align_fwd_strided(const osr_pyramid* feats, int32_t feat_dtype, int32_t n, const float* boxes,
+                                     const int32_t* batch_idx, int64_t m, int32_t pooled, int32_t bin_stride, int32_t canonical_level,
+                                     int32_t canonical_size, int32_t min_level, const int32_t* order,
+                                     const int32_t* order_nvalid, int32_t flags, const osr_roi_options* options, void* out,
+                                     int32_t out_dtype, void* stream);
+/* Mean over the positions of a RoI ([d2] Res5ROIHeads: res5's output .mean(dim=[2, 3]), the input of box_predictor).
+ * x: (r, s, c) in `dtype`, the s positions of a RoI, channels last. out: (r, c) fp32 = (the sum over the positions in ascending
+ * order, accumulated in fp32) / s. rows_valid / seg_rows: as osr_mask_upsample_predict; RoIs that do not exist are written as zeros
+ * and their x is not read. c a multiple of 4, s 1 .. 196: anything else is OSR_ERR_UNSUPPORTED with nothing launched. x and out
+ * 16-byte aligned. r == 0 launches nothing. No atomics: repeats are bit-identical. */
+osr_status osr_avgpool_rows(const void* x, int32_t dtype, int64_t r, int32_t s, int32_t c, const int32_t* rows_valid,
+                            int32_t seg_rows, float* out, void* stream);
 int64_t osr_roi_locality_order_workspace_bytes(int32_t n, int64_t m);
 osr_status osr_roi_locality_order(const osr_pyramid* feats, int32_t n, const float* boxes, const int32_t* batch_idx, int64_t m,
                                   int32_t canonical_level, int32_t canonical_size, int32_t min_level, int32_t* order,

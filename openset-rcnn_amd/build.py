@@ -29,6 +29,7 @@ SOURCES = {
     "osr_conv_split.hip": [],
     "osr_bottleneck.hip": [],
     "osr_stem_pool.hip": [],
+    "osr_avgpool.hip": ["-ffp-contract=off"],  # (a sum and a division: nothing to contract, and it stays so)
     "osr_deform.hip": ["-ffp-contract=off"],  # (exact-index gather: the sample positions and the zero-offset / integer-offset results are bit-exact)
     "osr_rpn.hip": ["-ffp-contract=off"],
     "osr_retinanet.hip": ["-ffp-contract=off"],  # (decodes like osr_rpn.hip's decode_mode 1)

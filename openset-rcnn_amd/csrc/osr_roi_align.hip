@@ -706,14 +706,16 @@ __global__ __launch_bounds__(RA_THREADS, (sizeof(TI) == 4 ? 3 : RA_MINW)) void r
 // 256 channels a wave is one bin (uniform control flow, one 512-byte line per tap). Generic in the grid, the offset and the clamp
 // (ra_geometry<true> with the options of the call, {0.5, 0, adaptive} for the default pair); no LDS, no tables, no size limit.
 #define RA_BIG_THREADS 256
-template <class TI, class TO>
+// BS: the bin stride (osr_roi_align_fwd_strided). The kernel pools bins (BS * i, BS * j) only, into a (Q, Q, c) row with
+// Q = ceil(P / BS); a bin's arithmetic does not know BS, so a bin is the same bits under every stride. BS = 1 is the kernel as it was.
+template <class TI, class TO, int BS>
 __global__ __launch_bounds__(RA_BIG_THREADS) void roi_align_big_kernel(RoiAlignArgs a) {
     long long r = blockIdx.x;
     if (r >= a.m) return;
     if (a.order) r = a.order[r];
-    const int P = a.pooled, C = a.c, cq = C >> 2, total = P * P * cq;
+    const int P = a.pooled, Q = (P + BS - 1) / BS, C = a.c, cq = C >> 2, total = Q * Q * cq;
     const int tid = threadIdx.x;
-    TO* out = reinterpret_cast<TO*>(a.out) + (size_t)r * P * P * C;
+    TO* out = reinterpret_cast<TO*>(a.out) + (size_t)r * Q * Q * C;
     const int b = a.batch_idx[r];
     if (b < 0) {  // padding row: zeros (or nothing: the caller never reads it)
         if (a.no_pad_fill) return;
@@ -728,7 +730,7 @@ __global__ __launch_bounds__(RA_BIG_THREADS) void roi_align_big_kernel(RoiAlignA
     const RaGeom geo = ra_geometry<true>(a.opt, bx1, by1, bx2, by2, a.scale[lv], P);
     for (int e = tid; e < total; e += RA_BIG_THREADS) {
         const int bin = e / cq, c0 = (e - bin * cq) * 4;
-        const int ph = bin / P, pw = bin - ph * P;
+        const int qh = bin / Q, ph = qh * BS, pw = (bin - qh * Q) * BS;
         float acc[4] = {0.f, 0.f, 0.f, 0.f};
         for (int iy = 0; iy < geo.gh; ++iy) {
             int yl, yh; float hy, ly;
@@ -752,13 +754,13 @@ __global__ __launch_bounds__(RA_BIG_THREADS) void roi_align_big_kernel(RoiAlignA
     }
 }
 
-template <class TI>
+template <class TI, int BS>
 static osr_status launch_big(const RoiAlignArgs& a, int out_dtype, hipStream_t st) {
     dim3 grid((unsigned)a.m), block(RA_BIG_THREADS);
     switch (out_dtype) {
-        case OSR_F32: hipLaunchKernelGGL((roi_align_big_kernel<TI, float>), grid, block, 0, st, a); break;
-        case OSR_F16: hipLaunchKernelGGL((roi_align_big_kernel<TI, f16_t>), grid, block, 0, st, a); break;
-        default: hipLaunchKernelGGL((roi_align_big_kernel<TI, bf16_t>), grid, block, 0, st, a); break;
+        case OSR_F32: hipLaunchKernelGGL((roi_align_big_kernel<TI, float, BS>), grid, block, 0, st, a); break;
+        case OSR_F16: hipLaunchKernelGGL((roi_align_big_kernel<TI, f16_t, BS>), grid, block, 0, st, a); break;
+        default: hipLaunchKernelGGL((roi_align_big_kernel<TI, bf16_t, BS>), grid, block, 0, st, a); break;
     }
     OSR_CHECK_LAUNCH("osr_roi_align_fwd");
     return OSR_OK;
@@ -780,7 +782,7 @@ static osr_status roi_align_fwd_impl(const osr_pyramid* f, int32_t feat_dtype, i
                                      const int32_t* batch_idx, int64_t m, int32_t pooled, int32_t canonical_level,
                                      int32_t canonical_size, int32_t min_level, const int32_t* order,
                                      const int32_t* order_nvalid, void* out, int32_t out_dtype, void* stream, int32_t flags = 0,
-                                     const osr_roi_options* opt = nullptr) {
+                                     const osr_roi_options* opt = nullptr, int32_t bin_stride = 1) {
     OSR_REQUIRE(f && boxes && batch_idx && out, OSR_ERR_INVALID_ARG, "osr_roi_align_fwd: null pointer");
     RA_REQUIRE_OPT(opt, "osr_roi_align_fwd");
     RoiAlignArgs a;
@@ -788,6 +790,8 @@ static osr_status roi_align_fwd_impl(const osr_pyramid* f, int32_t feat_dtype, i
     OSR_REQUIRE(osr_dtype_ok(feat_dtype) && osr_dtype_ok(out_dtype), OSR_ERR_INVALID_ARG, "osr_roi_align_fwd: bad dtype");
     OSR_REQUIRE(n >= 1 && m >= 0 && m < (1ll << 31), OSR_ERR_INVALID_ARG, "osr_roi_align_fwd: bad n/m");
     OSR_REQUIRE(canonical_size > 0, OSR_ERR_INVALID_ARG, "osr_roi_align_fwd: canonical_size must be > 0");
+    OSR_REQUIRE(bin_stride == 1 || (bin_stride == 2 && pooled > 7), OSR_ERR_UNSUPPORTED,
+                "osr_roi_align_fwd_strided: bin_stride 1, or 2 with pooled 8..%d; got bin_stride %d with pooled %d", OSR_ROI_MAX_POOLED_FWD, bin_stride, pooled);
     if (m == 0) return OSR_OK;
     a.num_levels = f->num_levels; a.c = f->c; a.boxes = boxes; a.batch_idx = batch_idx; a.m = m;
     a.pooled = pooled; a.canonical_level = canonical_level; a.canonical_size = canonical_size; a.min_level = min_level;
@@ -796,10 +800,17 @@ static osr_status roi_align_fwd_impl(const osr_pyramid* f, int32_t feat_dtype, i
     a.opt = ra_opt_of(opt);
     hipStream_t st = (hipStream_t)stream;
     if (pooled > 7) {  // (the kernels below hold 7 bins of state per axis)
+        if (bin_stride == 2) {
+            switch (feat_dtype) {
+                case OSR_F32: return launch_big<float, 2>(a, out_dtype, st);
+                case OSR_F16: return launch_big<f16_t, 2>(a, out_dtype, st);
+                default: return launch_big<bf16_t, 2>(a, out_dtype, st);
+            }
+        }
         switch (feat_dtype) {
-            case OSR_F32: return launch_big<float>(a, out_dtype, st);
-            case OSR_F16: return launch_big<f16_t>(a, out_dtype, st);
-            default: return launch_big<bf16_t>(a, out_dtype, st);
+            case OSR_F32: return launch_big<float, 1>(a, out_dtype, st);
+            case OSR_F16: return launch_big<f16_t, 1>(a, out_dtype, st);
+            default: return launch_big<bf16_t, 1>(a, out_dtype, st);
         }
     }
     if (ra_opt_default(opt)) {
@@ -841,6 +852,16 @@ extern "C" osr_status osr_roi_align_fwd_ordered_opt(const osr_pyramid* f, int32_
     OSR_REQUIRE((flags & ~OSR_ROI_NO_PADDING_FILL) == 0, OSR_ERR_INVALID_ARG, "osr_roi_align_fwd_ordered_opt: unknown flag bits 0x%x", flags);
     return roi_align_fwd_impl(f, feat_dtype, n, boxes, batch_idx, m, pooled, canonical_level, canonical_size, min_level, order, order_nvalid,
                               out, out_dtype, stream, flags, options);
+}
+
+extern "C" osr_status osr_roi_align_fwd_strided(const osr_pyramid* f, int32_t feat_dtype, int32_t n, const float* boxes,
+                                                const int32_t* batch_idx, int64_t m, int32_t pooled, int32_t bin_stride,
+                                                int32_t canonical_level, int32_t canonical_size, int32_t min_level, const int32_t* order,
+                                                const int32_t* order_nvalid, int32_t flags, const osr_roi_options* options, void* out,
+                                                int32_t out_dtype, void* stream) {
+    OSR_REQUIRE((flags & ~OSR_ROI_NO_PADDING_FILL) == 0, OSR_ERR_INVALID_ARG, "osr_roi_align_fwd_strided: unknown flag bits 0x%x", flags);
+    return roi_align_fwd_impl(f, feat_dtype, n, boxes, batch_idx, m, pooled, canonical_level, canonical_size, min_level, order, order_nvalid,
+                              out, out_dtype, stream, flags, options, bin_stride);
 }
 
 extern "C" osr_status osr_roi_align_fwd(const osr_pyramid* f, int32_t feat_dtype, int32_t n, const float* boxes,

@@ -95,6 +95,10 @@ struct SelLevels {
 
 // Stage A: grid (level, image). Stable top-k by radix select + bitonic sort, ltrb decode, filters.
 // Writes staging arrays st_box/st_score/st_src/st_flag at [img][koff[l] + rank].
+// MAXK is the length of the pair list in LDS: SEL_MAXK for osr_rpn_select(_ex), SEL_WIDE_MAXK for osr_rpn_select_wide. Nothing else
+// differs between the two instantiations, so for a k both serve they select, sort and decode alike, bit for bit.
+#define SEL_WIDE_MAXK OSR_RPN_SELECT_WIDE_MAXK  // 8192 pairs = 64 KiB beside the 8 KiB histogram: 72 KiB of the 160 KiB a workgroup may hold
+template <int MAXK>
 __global__ __launch_bounds__(SEL_THREADS) void rpn_select_kernel(SelLevels lv, const float* __restrict__ cell_anchors,
                                                                  const float* __restrict__ ctr, const float* __restrict__ deltas,
                                                                  int n_img, const int* __restrict__ image_hw, float min_box_size,
@@ -108,7 +112,7 @@ __global__ __launch_bounds__(SEL_THREADS) void rpn_select_kernel(SelLevels lv, c
     const float* sc = ctr + lv.offset[l] + (long long)img * cnt;
     const float* dl = deltas + (lv.offset[l] + (long long)img * cnt) * 4;
 
-    __shared__ unsigned long long s_sel[SEL_MAXK];
+    __shared__ unsigned long long s_sel[MAXK];
     __shared__ __attribute__((aligned(16))) int s_hist[SEL_BINS];
     __shared__ int s_scan[32];
     __shared__ SelBcast<unsigned int> s_bc;
@@ -176,8 +180,8 @@ __global__ __launch_bounds__(SEL_THREADS) void rpn_select_kernel(SelLevels lv, c
                 if (e < per) {
                     const unsigned long long comp = sel_pair(key[e], (unsigned int)(i + e));
                     const bool g = all || key[e] > T, q = !all && key[e] == T;
-                    if (g) { if (pg < SEL_MAXK) s_sel[pg] = comp; ++pg; }
-                    if (q) { if (pe < remaining && ngt_total + pe < SEL_MAXK) s_sel[ngt_total + pe] = comp; ++pe; }
+                    if (g) { if (pg < MAXK) s_sel[pg] = comp; ++pg; }
+                    if (q) { if (pe < remaining && ngt_total + pe < MAXK) s_sel[ngt_total + pe] = comp; ++pe; }
                 }
         }
         base_gt += tot & 0xffff;
@@ -261,8 +265,8 @@ __global__ __launch_bounds__(SEL_THREADS) void rpn_compact_kernel(int cap, const
     if (tid == 0) counts[img] = running;
 }
 
-static bool fill_levels(const osr_rpn_levels* in, int topk, SelLevels* o) {
-    if (!in || in->num_levels < 1 || in->num_levels > OSR_MAX_LEVELS || in->num_anchors < 1 || topk < 1 || topk > SEL_MAXK) return false;
+static bool fill_levels(const osr_rpn_levels* in, int topk, SelLevels* o, int maxk = SEL_MAXK) {
+    if (!in || in->num_levels < 1 || in->num_levels > OSR_MAX_LEVELS || in->num_anchors < 1 || topk < 1 || topk > maxk) return false;
     o->num_levels = in->num_levels;
     o->num_anchors = in->num_anchors;
     int ko = 0;
@@ -294,13 +298,15 @@ extern "C" int64_t osr_rpn_select_workspace_bytes(const osr_rpn_levels* lv, int3
     return (int64_t)n * s.cap * (4 * 4 + 4 + 4 + 4);
 }
 
-extern "C" osr_status osr_rpn_select_ex(const osr_rpn_levels* lv, const float* cell_anchors, const float* ctr, const float* deltas,
-                                        int32_t n, const int32_t* image_hw, int32_t pre_nms_topk, float min_box_size, int32_t decode_mode,
-                                        const float reg_weights[4], float* boxes, float* scores, int32_t* src_index, int32_t* batch_idx,
-                                        int32_t* level_out, int32_t* counts, int32_t* status_flags, void* workspace, int64_t workspace_bytes,
-                                        void* stream) {
+// The two launches behind osr_rpn_select_ex (MAXK = SEL_MAXK) and osr_rpn_select_wide (MAXK = SEL_WIDE_MAXK).
+template <int MAXK>
+static osr_status rpn_select_impl(const osr_rpn_levels* lv, const float* cell_anchors, const float* ctr, const float* deltas,
+                                  int32_t n, const int32_t* image_hw, int32_t pre_nms_topk, float min_box_size, int32_t decode_mode,
+                                  const float reg_weights[4], float* boxes, float* scores, int32_t* src_index, int32_t* batch_idx,
+                                  int32_t* level_out, int32_t* counts, int32_t* status_flags, void* workspace, int64_t workspace_bytes,
+                                  void* stream) {
     SelLevels s;
-    OSR_REQUIRE(fill_levels(lv, pre_nms_topk, &s), OSR_ERR_INVALID_ARG, "osr_rpn_select: bad level table / topk (1..%d)", SEL_MAXK);
+    OSR_REQUIRE(fill_levels(lv, pre_nms_topk, &s, MAXK), OSR_ERR_INVALID_ARG, "osr_rpn_select: bad level table / topk (1..%d)", MAXK);
     OSR_REQUIRE(cell_anchors && ctr && deltas && image_hw && boxes && scores && src_index && batch_idx && counts && status_flags && workspace,
                 OSR_ERR_INVALID_ARG, "osr_rpn_select: null pointer");
     OSR_REQUIRE(n >= 1 && n <= 65535, OSR_ERR_INVALID_ARG, "osr_rpn_select: n out of range");
@@ -317,13 +323,48 @@ extern "C" osr_status osr_rpn_select_ex(const osr_rpn_levels* lv, const float* c
     hipStream_t st = (hipStream_t)stream;
     if (hipMemsetAsync(status_flags, 0, sizeof(int32_t), st) != hipSuccess) { osr_set_error("osr_rpn_select: memset failed"); return OSR_ERR_LAUNCH; }
     const float4 rw = decode_mode == 1 ? make_float4(reg_weights[0], reg_weights[1], reg_weights[2], reg_weights[3]) : make_float4(1.f, 1.f, 1.f, 1.f);
-    hipLaunchKernelGGL(rpn_select_kernel, dim3(s.num_levels, n), dim3(SEL_THREADS), 0, st, s, cell_anchors, ctr, deltas, n, image_hw,
+    hipLaunchKernelGGL(rpn_select_kernel<MAXK>, dim3(s.num_levels, n), dim3(SEL_THREADS), 0, st, s, cell_anchors, ctr, deltas, n, image_hw,
                        min_box_size, decode_mode, rw, st_box, st_score, st_src, st_flag, status_flags);
     OSR_CHECK_LAUNCH("osr_rpn_select(select)");
     hipLaunchKernelGGL(rpn_compact_kernel, dim3(n), dim3(SEL_THREADS), 0, st, s.cap, st_box, st_score, st_src, st_flag, boxes, scores,
                        src_index, batch_idx, counts, s, level_out);
     OSR_CHECK_LAUNCH("osr_rpn_select(compact)");
     return OSR_OK;
+}
+
+extern "C" osr_status osr_rpn_select_ex(const osr_rpn_levels* lv, const float* cell_anchors, const float* ctr, const float* deltas,
+                                        int32_t n, const int32_t* image_hw, int32_t pre_nms_topk, float min_box_size, int32_t decode_mode,
+                                        const float reg_weights[4], float* boxes, float* scores, int32_t* src_index, int32_t* batch_idx,
+                                        int32_t* level_out, int32_t* counts, int32_t* status_flags, void* workspace, int64_t workspace_bytes,
+                                        void* stream) {
+    return rpn_select_impl<SEL_MAXK>(lv, cell_anchors, ctr, deltas, n, image_hw, pre_nms_topk, min_box_size, decode_mode, reg_weights, boxes,
+                                     scores, src_index, batch_idx, level_out, counts, status_flags, workspace, workspace_bytes, stream);
+}
+
+// ---- osr_rpn_select_wide: the same selection with up to OSR_RPN_SELECT_WIDE_MAXK proposals per level (the single-level C4 RPN's
+// PRE_NMS_TOPK_TEST 6000). One workgroup per (level, image) as above; its pair list takes 64 KiB of LDS, so one workgroup per CU. ----
+extern "C" int32_t osr_rpn_select_wide_capacity(const osr_rpn_levels* lv, int32_t pre_nms_topk) {
+    SelLevels s;
+    if (pre_nms_topk > SEL_WIDE_MAXK) { osr_set_error("osr_rpn_select_wide_capacity: pre_nms_topk %d > %d", pre_nms_topk, SEL_WIDE_MAXK); return OSR_ERR_UNSUPPORTED; }
+    if (!fill_levels(lv, pre_nms_topk, &s, SEL_WIDE_MAXK)) { osr_set_error("osr_rpn_select_wide_capacity: bad level table / topk (1..%d)", SEL_WIDE_MAXK); return OSR_ERR_INVALID_ARG; }
+    return s.cap;
+}
+
+extern "C" int64_t osr_rpn_select_wide_workspace_bytes(const osr_rpn_levels* lv, int32_t n, int32_t pre_nms_topk) {
+    SelLevels s;
+    if (pre_nms_topk > SEL_WIDE_MAXK) { osr_set_error("osr_rpn_select_wide_workspace_bytes: pre_nms_topk %d > %d", pre_nms_topk, SEL_WIDE_MAXK); return OSR_ERR_UNSUPPORTED; }
+    if (!fill_levels(lv, pre_nms_topk, &s, SEL_WIDE_MAXK) || n < 1) { osr_set_error("osr_rpn_select_wide_workspace_bytes: bad arguments"); return OSR_ERR_INVALID_ARG; }
+    return (int64_t)n * s.cap * (4 * 4 + 4 + 4 + 4);
+}
+
+extern "C" osr_status osr_rpn_select_wide(const osr_rpn_levels* lv, const float* cell_anchors, const float* ctr, const float* deltas,
+                                          int32_t n, const int32_t* image_hw, int32_t pre_nms_topk, float min_box_size, int32_t decode_mode,
+                                          const float reg_weights[4], float* boxes, float* scores, int32_t* src_index, int32_t* batch_idx,
+                                          int32_t* level_out, int32_t* counts, int32_t* status_flags, void* workspace, int64_t workspace_bytes,
+                                          void* stream) {
+    OSR_REQUIRE(pre_nms_topk <= SEL_WIDE_MAXK, OSR_ERR_UNSUPPORTED, "osr_rpn_select_wide: pre_nms_topk %d > %d", pre_nms_topk, SEL_WIDE_MAXK);
+    return rpn_select_impl<SEL_WIDE_MAXK>(lv, cell_anchors, ctr, deltas, n, image_hw, pre_nms_topk, min_box_size, decode_mode, reg_weights, boxes,
+                                          scores, src_index, batch_idx, level_out, counts, status_flags, workspace, workspace_bytes, stream);
 }
 
 extern "C" osr_status osr_rpn_select(const osr_rpn_levels* lv, const float* cell_anchors, const float* ctr, const float* deltas,

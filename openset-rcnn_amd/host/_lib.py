@@ -12,6 +12,7 @@ LIB_PATH = os.path.join(PKG_DIR, "libosr_hip.so")
 
 OSR_MAX_LEVELS = 8
 OSR_F32, OSR_F16, OSR_BF16 = 0, 1, 2
+RPN_SELECT_MAXK, RPN_SELECT_WIDE_MAXK = 2048, 8192  # csrc/osr_select.h SEL_MAXK; include/osr.h OSR_RPN_SELECT_WIDE_MAXK
 ABI_VERSION = 1
 
 
@@ -165,6 +166,9 @@ PROTOTYPES = {
     "osr_rpn_select_workspace_bytes": (I64, [C.POINTER(RpnLevels), I32, I32]),
     "osr_rpn_select": (I32, [C.POINTER(RpnLevels), P, P, P, I32, P, I32, F32, P, P, P, P, P, P, P, I64, P]),
     "osr_rpn_select_ex": (I32, [C.POINTER(RpnLevels), P, P, P, I32, P, I32, F32, I32, P, P, P, P, P, P, P, P, P, I64, P]),
+    "osr_rpn_select_wide_capacity": (I32, [C.POINTER(RpnLevels), I32]),
+    "osr_rpn_select_wide_workspace_bytes": (I64, [C.POINTER(RpnLevels), I32, I32]),
+    "osr_rpn_select_wide": (I32, [C.POINTER(RpnLevels), P, P, P, I32, P, I32, F32, I32, P, P, P, P, P, P, P, P, P, I64, P]),
     "osr_retinanet_select_capacity": (I32, [C.POINTER(RpnLevels), I32]),
     "osr_retinanet_select_workspace_bytes": (I64, [C.POINTER(RpnLevels), I32, I32, I32]),
     "osr_retinanet_select": (I32, [C.POINTER(RpnLevels), P, P, I32, I64, P, I64, I32, I32, I32, F32, P, P, P, P, P, P, P, P, P, I64, P]),
@@ -189,6 +193,8 @@ PROTOTYPES = {
     "osr_roi_align_fwd_ordered": (I32, [C.POINTER(Pyramid), I32, I32, P, P, I64, I32, I32, I32, I32, P, P, P, I32, P]),
     "osr_roi_align_fwd_ordered_ex": (I32, [C.POINTER(Pyramid), I32, I32, P, P, I64, I32, I32, I32, I32, P, P, I32, P, I32, P]),
     "osr_roi_align_fwd_ordered_opt": (I32, [C.POINTER(Pyramid), I32, I32, P, P, I64, I32, I32, I32, I32, P, P, I32, C.POINTER(RoiOptions), P, I32, P]),
+    "osr_roi_align_fwd_strided": (I32, [C.POINTER(Pyramid), I32, I32, P, P, I64, I32, I32, I32, I32, I32, P, P, I32, C.POINTER(RoiOptions), P, I32, P]),
+    "osr_avgpool_rows": (I32, [P, I32, I64, I32, I32, P, I32, P, P]),
     "osr_roi_locality_order_workspace_bytes": (I64, [I32, I64]),
     "osr_roi_locality_order": (I32, [C.POINTER(Pyramid), I32, P, P, I64, I32, I32, I32, P, P, P, I64, P]),
     "osr_box_predictor_tail": (I32, [P, I64, I32, P, P, P, P, P, P, C.POINTER(C.c_float), I32, F32, P, P, P, P, P, P]),

@@ -18,7 +18,9 @@ Both carry real BatchNorm statistics (not pre-reduced like the MSRA blobs); `wei
 
 Checkpoints of the other zoo families ([d2] `.pth`, or the model zoo's `.pkl` = {"model": {name: ndarray}, "__author__": ...} without
 "matching_heuristics") load by name as they are: mask_rcnn, cascade, dconv, retinanet_R_50_FPN (backbone.top_block.p6 / p7, head.*) and panoptic_fpn_R_50 (sem_seg_head.*: its
-GroupNorm `.norm.weight` / `.norm.bias` carry no running statistics and are not folded).
+GroupNorm `.norm.weight` / `.norm.bias` carry no running statistics and are not folded) and faster_rcnn_R_50_C4 (backbone.stem.* /
+backbone.res{2,3,4}.* without `bottom_up`, roi_heads.res5.*). A backbone-only checkpoint loaded into a C4 model is renamed to those names
+(c4_names).
 
 Nothing here reads from the network: paths are local files. The result is a flat {d2 name: fp32 tensor} dict, ready for
 `model.load_state_dict` (host/modeling.py) or, after `weights.fold_frozen_bn`, for `OpensetRCNNEngine`."""
@@ -169,6 +171,21 @@ def load_checkpoint(path: str) -> CheckpointState:
     return CheckpointState(out, "d2")
 
 
+def c4_names(state: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """A backbone-only checkpoint's names (backbone.bottom_up.*: what the MSRA and torchvision converters above produce) as a C4 model
+    owns them ([d2] build_resnet_backbone + Res5ROIHeads): stem and res2..res4 directly under `backbone.`, res5 under `roi_heads.`."""
+    out = {}
+    for k, v in state.items():
+        m = re.fullmatch(r"backbone\.bottom_up\.(stem|res[2-5])\.(.+)", k)
+        if not m:
+            out[k] = v
+        elif m.group(1) == "res5":
+            out["roi_heads.res5." + m.group(2)] = v
+        else:
+            out[f"backbone.{m.group(1)}.{m.group(2)}"] = v
+    return CheckpointState(out, state.origin) if isinstance(state, CheckpointState) else out
+
+
 def load_into(model: torch.nn.Module, state: Dict[str, torch.Tensor], strict: bool = False) -> Tuple[List[str], List[str]]:
     """[d2] Checkpointer semantics: load matching names, report (missing, unexpected); shape mismatches raise. A backbone-only
     checkpoint (MSRA R-50) leaves FPN / RPN / RoI-head parameters at their initial values, as in the reference's training
@@ -178,6 +195,8 @@ def load_into(model: torch.nn.Module, state: Dict[str, torch.Tensor], strict: bo
         log.warning("loading a torchvision ResNet checkpoint into a model with MODEL.RESNETS.STRIDE_IN_1X1 True: torchvision puts "
                     "the stride in the 3x3 convolution; set STRIDE_IN_1X1 False (detectron2's convert-torchvision-to-d2 recipe)")
     own = model.state_dict()
+    if "backbone.stem.conv1.weight" in own and "backbone.bottom_up.stem.conv1.weight" in state:
+        state = c4_names(state)  # (a backbone-only checkpoint into a C4 model: res5 is its RoI head's)
     for k, v in state.items():
         if k in own and tuple(own[k].shape) != tuple(v.shape):
             raise ValueError(f"shape mismatch for '{k}': checkpoint {tuple(v.shape)} vs model {tuple(own[k].shape)}")

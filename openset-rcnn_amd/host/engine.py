@@ -313,14 +313,21 @@ class OpensetRCNNEngine:
         return o2.view(om.shape[0], om.shape[1], om.shape[2], cout)
 
     def _bottleneck(self, x, pre: str, first: bool, stride: int = 1, save: Optional[list] = None, chain: Optional[bool] = None,
-                    deform: bool = False):
+                    deform: bool = False, row_segs=None):
         """One [d2] BottleneckBlock (conv1 1x1 -> conv2 3x3 -> conv3 1x1 + shortcut, ReLU after each). res2's blocks run as one
         fused launch when the engine allows it (the intermediates never reach HBM); everything else as separate launches.
         save (a list: the training forward): the block keeps what its backward reads -- no fused res2 launch (its intermediates
         never reach memory), the chained launch also stores conv2's output -- and appends the record of it (_stages adds the
         block's place in its stage). chain: the caller's switch for the chained launch in place of chain_res3. deform: the block's
-        conv2 is deformable (_deform_conv2) -- neither the fused res2 launch nor the chained one applies; inference only."""
+        conv2 is deformable (_deform_conv2) -- neither the fused res2 launch nor the chained one applies; inference only.
+        row_segs = {rows per image: _conv's row_seg}: x's images are padded lists (res5 on pooled RoIs: engine_c4.py), and every
+        convolution of the block gets the entry for its own output size, h x w rows per image. The caller forms the entries once per
+        pass; a size it did not provide is a KeyError, not a layer that quietly computes every row."""
         w = self.w
+
+        def seg(h_, w_):
+            return None if row_segs is None else row_segs[h_ * w_]
+        down = lambda v, s: (v - 1) // s + 1  # noqa: E731  (a 1x1 with pad 0 or a 3x3 with pad 1 at stride s)
         if deform and save is not None:
             raise NotImplementedError(DEFORM_TRAINING_MESSAGE)
         if not deform and save is None and self.fuse_res2 and stride == 1 and w[pre + ".conv1.w"].shape[0] == 64:
@@ -338,12 +345,14 @@ class OpensetRCNNEngine:
                 return y
         s1, s2 = (stride, 1) if self.cfg["stride_in_1x1"] else (1, stride)  # the block's stride: in conv1 (MSRA) or in conv2 (torchvision): o1 at x's size
         # (the shortcut + conv1 launch needs both 1x1 layers at one stride)
-        pair = self._shortcut_conv1_one_launch(x, pre, stride) if first and self.fuse_levels and s1 == stride else None
+        pair = self._shortcut_conv1_one_launch(x, pre, stride) if first and self.fuse_levels and s1 == stride and row_segs is None else None
+        h1, w1 = down(x.shape[1], s1), down(x.shape[2], s1)
+        ho, wo = down(x.shape[1], stride), down(x.shape[2], stride)
         if pair is not None:
             sc, o1 = pair
         else:
-            sc = self._conv(x, pre + ".shortcut", stride) if first else x
-            o1 = self._conv(x, pre + ".conv1", s1, relu=True)
+            sc = self._conv(x, pre + ".shortcut", stride, row_seg=seg(ho, wo)) if first else x
+            o1 = self._conv(x, pre + ".conv1", s1, relu=True, row_seg=seg(h1, w1))
         y = o2 = None
         # res3: conv2 -> conv3 + shortcut as ONE launch (with save it also stores conv2's output for the backward), bit-identical to the two
         if deform:
@@ -361,8 +370,8 @@ class OpensetRCNNEngine:
                 y, o2 = r if save is not None else (r, None)
         if y is None:
             if o2 is None:
-                o2 = self._conv(o1, pre + ".conv2", s2, 1, relu=True)
-            y = self._conv(o2, pre + ".conv3", relu=True, residual=sc, res_mode=1)
+                o2 = self._conv(o1, pre + ".conv2", s2, 1, relu=True, row_seg=seg(ho, wo))
+            y = self._conv(o2, pre + ".conv3", relu=True, residual=sc, res_mode=1, row_seg=seg(ho, wo))
         if save is not None:
             save.append(dict(pre=pre, x=x, o1=o1, o2=o2, y=y, stride=stride, s1=s1, s2=s2, first=first))
         return y

@@ -26,6 +26,7 @@ from torch import nn
 from . import ops, parallel
 from .config import CfgNode
 from .engine import DEFAULT_CFG, OpensetRCNNEngine, check_deform_options, refuse_deform_training
+from .engine_c4 import C4_FEATURE, C4_STRIDE, TRAINING_MESSAGE as C4_TRAINING_MESSAGE, C4RCNNEngine
 from .engine_cascade import CascadeRCNNEngine, check_cascade_options
 from .engine_panoptic import PanopticFPNEngine, check_sem_seg_options, training_message as panoptic_training_message
 from .engine_retinanet import RETINA_PYRAMID, TRAINING_MESSAGE as RETINANET_TRAINING_MESSAGE, RetinaNetEngine, check_retina_anchors
@@ -292,6 +293,91 @@ def build_resnet_fpn_backbone(cfg: CfgNode, input_shape=None):
     return ResNetFPN(cfg)
 
 
+C4_BACKBONE, C4_ROI_HEADS = "build_resnet_backbone", "Res5ROIHeads"
+
+
+def check_c4_options(cfg: CfgNode) -> None:
+    """What a C4 model (BACKBONE.NAME "build_resnet_backbone" with ROI_HEADS.NAME "Res5ROIHeads") takes; a ValueError names the key.
+    The two names come together: the head runs res5 on res4's RoIs, and no other head reads a single stride-16 map here."""
+    m = cfg.MODEL
+    if (m.BACKBONE.NAME == C4_BACKBONE) != (m.ROI_HEADS.NAME == C4_ROI_HEADS):
+        raise ValueError(f"MODEL.BACKBONE.NAME {m.BACKBONE.NAME!r} with MODEL.ROI_HEADS.NAME {m.ROI_HEADS.NAME!r}: \"{C4_ROI_HEADS}\" runs on "
+                         f"\"{C4_BACKBONE}\" (one stride-16 map, res5 as the RoI head) and on nothing else; the FPN backbones take "
+                         "StandardROIHeads / CascadeROIHeads / OpensetROIHeads")
+    if m.BACKBONE.NAME != C4_BACKBONE:
+        return
+    if list(m.RESNETS.OUT_FEATURES) != [C4_FEATURE]:
+        raise ValueError(f"MODEL.RESNETS.OUT_FEATURES {list(m.RESNETS.OUT_FEATURES)!r}: {C4_BACKBONE} is built for [\"{C4_FEATURE}\"] "
+                         "(Base-RCNN-C4.yaml); res5 is the RoI head's")
+    if int(m.RESNETS.RES5_DILATION) != 1:
+        raise ValueError(f"MODEL.RESNETS.RES5_DILATION {m.RESNETS.RES5_DILATION}: 1 only -- DC5 needs a dilated 3x3 convolution, which has no kernel")
+    on = check_deform_options(m.RESNETS.DEFORM_ON_PER_STAGE, m.RESNETS.DEFORM_MODULATED, m.RESNETS.DEFORM_NUM_GROUPS)
+    if on[3]:
+        raise ValueError("MODEL.RESNETS.DEFORM_ON_PER_STAGE[3]: res5 is the RoI head of a C4 model and is not deformable ([d2] asserts the same)")
+    if m.MASK_ON:
+        raise ValueError(f"MODEL.MASK_ON with {C4_ROI_HEADS}: the fused mask tail takes at most 448 input channels, res5's RoI features have 2048")
+    if m.KEYPOINT_ON:
+        raise ValueError(f"MODEL.KEYPOINT_ON with {C4_ROI_HEADS}: the keypoint branch is built for StandardROIHeads")
+    if cfg.TEST.AUG.ENABLED:
+        raise ValueError(f"TEST.AUG: test-time augmentation is implemented for StandardROIHeads only, not {C4_ROI_HEADS}")
+    if list(m.RPN.IN_FEATURES) != [C4_FEATURE] or list(m.ROI_HEADS.IN_FEATURES) != [C4_FEATURE]:
+        raise ValueError(f"MODEL.RPN.IN_FEATURES {list(m.RPN.IN_FEATURES)!r} / MODEL.ROI_HEADS.IN_FEATURES {list(m.ROI_HEADS.IN_FEATURES)!r}: "
+                         f"[\"{C4_FEATURE}\"] with {C4_BACKBONE}")
+    if len(m.ANCHOR_GENERATOR.SIZES) != 1:
+        raise ValueError(f"MODEL.ANCHOR_GENERATOR.SIZES {m.ANCHOR_GENERATOR.SIZES!r}: one list (one level) with {C4_BACKBONE}")
+    k = int(m.RPN.PRE_NMS_TOPK_TEST)
+    if not 1 <= k <= ops.RPN_SELECT_WIDE_MAXK:
+        raise ValueError(f"MODEL.RPN.PRE_NMS_TOPK_TEST {k}: 1 .. {ops.RPN_SELECT_WIDE_MAXK} per level on the HIP path")
+
+
+def c4_engine_cfg_from(cfg: CfgNode) -> dict:
+    """engine_cfg_from for a C4 model: every anchor size of the one level, and the one pooler scale."""
+    e = engine_cfg_from(cfg)
+    e.update(anchor_sizes=(tuple(float(z) for z in cfg.MODEL.ANCHOR_GENERATOR.SIZES[0]),), pooler_scales=(1.0 / C4_STRIDE,))
+    return e
+
+
+class ResNetC4(_EngineOwner):
+    """[d2] build_resnet_backbone for R-50 with OUT_FEATURES ["res4"] (Base-RCNN-C4.yaml): stem and res2..res4 under [d2]'s names
+    backbone.stem.* / backbone.res{2,3,4}.* (no `bottom_up`); forward(x) takes the normalised, padded (N,3,H,W) fp32 batch and returns
+    {"res4": (N,1024,H/16,W/16)}."""
+    _prefix = "backbone."
+    _engine_cls = C4RCNNEngine
+
+    def __init__(self, cfg: CfgNode):
+        super().__init__()
+        assert cfg.MODEL.RESNETS.DEPTH == 50, "only R-50 is on the hot path (VOC-COCO / GraspNet yaml: DEPTH 50)"
+        assert cfg.MODEL.RESNETS.NORM == "FrozenBN", "only FrozenBN is on the hot path"
+        check_c4_options(cfg)
+        deform = deform_options_from(cfg)
+        off = ops.deform_offset_channels(deform["deform_num_groups"], deform["deform_modulated"])
+        self.stem = _Stem()
+        cin = 64
+        for si, (nb, mid) in enumerate(zip(R50_BLOCKS[:3], R50_MID[:3])):
+            blocks = []
+            for b in range(nb):
+                blocks.append(_Bottleneck(cin, mid, mid * 4, b == 0, off if deform["deform_on_per_stage"][si] else 0))
+                cin = mid * 4
+            setattr(self, f"res{si + 2}", nn.Sequential(*blocks))
+        self._eng_cfg = {"stride_in_1x1": bool(cfg.MODEL.RESNETS.STRIDE_IN_1X1), **deform}  # (a stand-alone backbone's engine)
+        self._out_features = [C4_FEATURE]
+        self.size_divisibility = 32  # ([d2] pads a C4 batch to its largest image only; the trunk's kernels take multiples of 32)
+
+    def output_shape(self) -> Dict[str, ShapeSpec]:
+        return {C4_FEATURE: ShapeSpec(channels=1024, stride=C4_STRIDE)}
+
+    def forward(self, x: torch.Tensor) -> Dict[str, torch.Tensor]:
+        n, _, h, w = x.shape
+        assert h % 32 == 0 and w % 32 == 0, "pad the batch to a multiple of 32 (ImageList.from_tensors(..., 32))"
+        feats = self.engine()._backbone(x.float().contiguous(), h, w, normalized=True)
+        return {k: v.permute(0, 3, 1, 2) for k, v in feats.items()}  # logical NCHW, channels_last memory
+
+
+@BACKBONE_REGISTRY.register()
+def build_resnet_backbone(cfg: CfgNode, input_shape=None):
+    return ResNetC4(cfg)
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # CF-RPN
 # ---------------------------------------------------------------------------------------------------------------
@@ -418,7 +504,7 @@ class StandardRPNHead(_EngineOwner):
         super().__init__()
         in_channels = input_shape[0].channels
         assert len(set(s.channels for s in input_shape)) == 1, "Each level must have the same channel!"
-        assert list(cfg.MODEL.RPN.CONV_DIMS) == [-1] and in_channels == 256
+        assert list(cfg.MODEL.RPN.CONV_DIMS) == [-1] and in_channels in (256, 1024)  # (an FPN level, or res4 of a C4 backbone)
         self.num_anchors = len(cfg.MODEL.ANCHOR_GENERATOR.ASPECT_RATIOS[0]) * len(cfg.MODEL.ANCHOR_GENERATOR.SIZES[0])
         self.conv = _Conv3x3ReLU(in_channels, in_channels)
         self.objectness_logits = nn.Conv2d(in_channels, self.num_anchors, kernel_size=1)
@@ -433,7 +519,7 @@ class StandardRPNHead(_EngineOwner):
         for x in features:
             n, _, h, w = x.shape
             t = ops.conv2d(_to_nhwc(x, eng.dtype), eng.w["proposal_generator.rpn_head.conv.w"], eng.w["proposal_generator.rpn_head.conv.b"], 1, 1, True,
-                           out_dtype=torch.float32).view(-1, 256)
+                           out_dtype=torch.float32).view(-1, self.conv.weight.shape[0])
             logits.append(ops.gemm_f32(t, eng.rpn_wo, eng.rpn_bo).view(n, h, w, -1).permute(0, 3, 1, 2))
             deltas.append(ops.gemm_f32(t, eng.rpn_wd, eng.rpn_bd).view(n, h, w, -1).permute(0, 3, 1, 2))
         return logits, deltas
@@ -454,6 +540,9 @@ class RPN(nn.Module):
         shapes = [input_shape[f] for f in self.in_features]
         self.rpn_head = RPN_HEAD_REGISTRY.get(cfg.MODEL.RPN.HEAD_NAME)(cfg, shapes)
         self.rpn_head._eng_cfg = engine_cfg_from(cfg)
+        if cfg.MODEL.BACKBONE.NAME == C4_BACKBONE:  # one level with every size: the C4 engine's anchors and its wide select
+            self.rpn_head._eng_cfg = c4_engine_cfg_from(cfg)
+            self.rpn_head._engine_cls = C4RCNNEngine
         check_std_supported(self.rpn_head._eng_cfg)  # (an unsupported loss type is refused when the model is built)
         self.sampler_generator = torch.Generator().manual_seed(max(int(cfg.SEED), 0))  # uniform keys replacing torch.randperm (H6)
 
@@ -463,6 +552,8 @@ class RPN(nn.Module):
         dev = feats[self.in_features[0]].device
         hw = torch.tensor(images.image_sizes, dtype=torch.int32, device=dev)
         losses = {}
+        if self.training and isinstance(eng, C4RCNNEngine):
+            raise NotImplementedError(C4_TRAINING_MESSAGE)
         if self.training:
             assert gt_instances is not None, "RPN requires gt_instances in training!"
             c, n = eng.cfg, len(gt_instances)
@@ -960,6 +1051,46 @@ class CascadeROIHeads(StandardROIHeads):
         self.num_cascade_stages = stages
 
 
+@ROI_HEADS_REGISTRY.register()
+class Res5ROIHeads(_EngineOwner):
+    """[d2] Res5ROIHeads (Base-RCNN-C4.yaml), box branch, inference: ROIPooler(14x14, ROIAlignV2) on res4 -> res5's three bottlenecks per
+    RoI -> the spatial mean -> FastRCNNOutputLayers.inference. Parameters under [d2]'s names roi_heads.res5.{0,1,2}.* and
+    roi_heads.box_predictor.{cls_score,bbox_pred}.*, so faster_rcnn_R_50_C4 checkpoints load. forward(images, features, proposals) ->
+    (list[Instances{pred_boxes, scores, pred_classes}], {}). Not a StandardROIHeads: no mask or keypoint branch, no given boxes, no
+    test-time augmentation. Training raises NotImplementedError naming the head."""
+    _prefix = "roi_heads."
+    _engine_cls = C4RCNNEngine
+
+    def __init__(self, cfg: CfgNode, input_shape: Dict[str, ShapeSpec], class_id=None):
+        super().__init__()
+        check_c4_options(cfg)
+        self.in_features = self.box_in_features = list(cfg.MODEL.ROI_HEADS.IN_FEATURES)
+        if C4_FEATURE not in input_shape:
+            raise ValueError(f"MODEL.ROI_HEADS.NAME \"{C4_ROI_HEADS}\" on a backbone without \"{C4_FEATURE}\" ({sorted(input_shape)}): it needs "
+                             f"MODEL.BACKBONE.NAME \"{C4_BACKBONE}\"")
+        self.mask_on = self.keypoint_on = False
+        cin, mid, cout = input_shape[C4_FEATURE].channels, R50_MID[3], R50_MID[3] * 4
+        self.res5 = nn.Sequential(*[_Bottleneck(cin if b == 0 else cout, mid, cout, b == 0) for b in range(R50_BLOCKS[3])])
+        self.box_predictor = FastRCNNOutputLayers(cfg, ShapeSpec(channels=cout))
+        self._eng_cfg = c4_engine_cfg_from(cfg)
+        res = self._eng_cfg["pooler_resolution"]
+        if isinstance(res, bool) or not isinstance(res, int) or not 1 <= res <= ops.MAX_POOLED_FWD:
+            raise ValueError(f"MODEL.ROI_BOX_HEAD.POOLER_RESOLUTION {res!r}: an integer 1 .. {ops.MAX_POOLED_FWD}")
+
+    def forward(self, images: ImageList, features: Dict[str, torch.Tensor], proposals: List[Instances], targets=None):
+        del images
+        if self.training:
+            raise NotImplementedError(C4_TRAINING_MESSAGE)
+        eng = self.engine()
+        n = len(proposals)
+        boxes, scores, bidx, counts, cap = OpensetROIHeads._pack_proposals(proposals)
+        sel = dict(boxes=boxes, scores=scores, batch_idx=bidx.view(-1), counts=counts, cap=cap)
+        hw = torch.tensor([p.image_size for p in proposals], dtype=torch.int32, device=boxes.device)
+        feats = {k: _to_nhwc(features[k], eng.dtype) for k in self.in_features}
+        res = OpensetRCNNEngine.to_instances(eng._roi_heads(feats, sel, hw), n, eng.output_fields())
+        return [_std_instances(p.image_size, r) for r, p in zip(res, proposals)], {}
+
+
 def _std_instances(image_size, r: dict) -> Instances:
     """Instances of one image from OpensetRCNNEngine.to_instances' dict; pred_masks (k, 1, M, M) probabilities when the engine has a
     mask head ([d2] mask_rcnn_inference), pred_keypoints (k, K, 3) {x, y, score} and pred_keypoint_heatmaps (k, K, 4P, 4P) when it has a
@@ -1012,6 +1143,7 @@ class GeneralizedRCNN(_EngineOwner):
 
     def __init__(self, cfg: CfgNode, class_id: Optional[torch.Tensor] = None):
         super().__init__()
+        check_c4_options(cfg)  # (a C4 backbone and Res5ROIHeads come together: ValueError naming both keys)
         self.backbone = BACKBONE_REGISTRY.get(cfg.MODEL.BACKBONE.NAME)(cfg)
         shapes = self.backbone.output_shape()
         self.proposal_generator = PROPOSAL_GENERATOR_REGISTRY.get(cfg.MODEL.PROPOSAL_GENERATOR.NAME)(cfg, shapes)
@@ -1021,8 +1153,11 @@ class GeneralizedRCNN(_EngineOwner):
         self._eng_cfg = engine_cfg_from(cfg)
         self._freeze_at = freeze_at_of(cfg)  # the trainer's (a negative value is refused here, when the model is built)
         self._class_map = class_id
-        self._engine_cls = self.roi_heads._engine_cls if isinstance(self.roi_heads, StandardROIHeads) else OpensetRCNNEngine
-        if issubclass(self._engine_cls, StandardRCNNEngine):
+        self._engine_cls = self.roi_heads._engine_cls if isinstance(self.roi_heads, (StandardROIHeads, Res5ROIHeads)) else OpensetRCNNEngine
+        self._c4 = isinstance(self.roi_heads, Res5ROIHeads)
+        if self._c4:
+            self._eng_cfg = dict(self.roi_heads._eng_cfg)
+        elif issubclass(self._engine_cls, StandardRCNNEngine):
             self._eng_cfg["pooler_scales"] = self.roi_heads._eng_cfg["pooler_scales"]
         self._trainer = None
         self._hook: Optional[torch.Tensor] = None
@@ -1053,6 +1188,7 @@ class GeneralizedRCNN(_EngineOwner):
         buffer (`solver.build_optimizer(cfg, model).step()` then all-reduces and applies it)."""
         if not self.training:
             return self.inference(batched_inputs)
+        self._refuse_c4_training()
         self._refuse_keypoint_training()
         trainer = self.trainer()
         tensors = self._train_tensors(batched_inputs, self.sampler_generator)
@@ -1100,6 +1236,7 @@ class GeneralizedRCNN(_EngineOwner):
         from .train import OpensetRCNNTrainer
         from .train_cascade import CascadeRCNNTrainer
         from .train_std import StandardRCNNTrainer
+        self._refuse_c4_training()  # (NotImplementedError naming MODEL.ROI_HEADS.NAME "Res5ROIHeads")
         refuse_deform_training(self._eng_cfg)  # (NotImplementedError naming MODEL.RESNETS.DEFORM_ON_PER_STAGE)
         self._refuse_keypoint_training()
         if self._mask_training() is False:
@@ -1186,6 +1323,10 @@ class GeneralizedRCNN(_EngineOwner):
         out = (batch, hw, hp, wp, gt.to(dev), gcls.to(dev), gcnt.to(dev), keys)
         return out if planes is None else out + (planes.to(dev),)  # (a ninth tensor only when the mask branch trains)
 
+    def _refuse_c4_training(self) -> None:
+        if getattr(self, "_c4", False):
+            raise NotImplementedError(C4_TRAINING_MESSAGE)
+
     def _refuse_keypoint_training(self) -> None:
         if getattr(self.roi_heads, "keypoint_on", False):
             raise NotImplementedError(KEYPOINT_LOSS_MESSAGE)
@@ -1207,6 +1348,7 @@ class GeneralizedRCNN(_EngineOwner):
         only: loss_rpn_loc, loss_rpn_ctr, loss_box_reg, loss_iou, loss_dml, loss_cls. Each input dict carries "image" and
         "instances" (gt_boxes: Boxes, gt_classes); a ragged batch is padded to its largest image. `generator` seeds the
         uniform keys that replace torch.randperm in the two samplers."""
+        self._refuse_c4_training()
         refuse_deform_training(self._eng_cfg)
         self._refuse_keypoint_training()
         if self._mask_training() is False:

@@ -900,6 +900,40 @@ def _rpn_select_ex(lv, cell_anchors, ctr, deltas, n, image_hw, pre_nms_topk, min
     return dict(boxes=boxes, scores=scores, src_index=src, batch_idx=bidx, level=level, counts=counts, status_flags=flags, cap=cap)
 
 
+def rpn_select_wide(lv: RpnLevels, cell_anchors: torch.Tensor, ctr: torch.Tensor, deltas: torch.Tensor, n: int,
+                    image_hw: torch.Tensor, pre_nms_topk: int, min_box_size: float = 0.0, b2b_weights: Optional[Sequence[float]] = None):
+    """rpn_select with pre_nms_topk up to RPN_SELECT_WIDE_MAXK per level (osr_rpn_select_wide: the single-level C4 RPN keeps 6000).
+    Same arguments, same dict; `level` is returned with b2b_weights as there. For pre_nms_topk <= RPN_SELECT_MAXK the outputs are
+    bit-identical to rpn_select's."""
+    lib = _lib.load()
+    _need(cell_anchors, torch.float32, "cell_anchors"); _need(ctr, torch.float32, "scores"); _need(deltas, torch.float32, "deltas")
+    _need(image_hw, torch.int32, "image_hw")
+    cap = lib.osr_rpn_select_wide_capacity(C.byref(lv), pre_nms_topk)
+    if cap < 0:
+        check(cap, "osr_rpn_select_wide_capacity")
+    wsb = lib.osr_rpn_select_wide_workspace_bytes(C.byref(lv), n, pre_nms_topk)
+    dev = ctr.device
+    ws = torch.empty((wsb,), dtype=torch.uint8, device=dev)
+    boxes = torch.empty((n, cap, 4), dtype=torch.float32, device=dev)
+    scores = torch.empty((n, cap), dtype=torch.float32, device=dev)
+    src = torch.empty((n, cap), dtype=torch.int32, device=dev)
+    level = torch.empty((n, cap), dtype=torch.int32, device=dev) if b2b_weights is not None else None
+    bidx = torch.empty((n * cap,), dtype=torch.int32, device=dev)
+    counts = torch.empty((n,), dtype=torch.int32, device=dev)
+    flags = torch.zeros((1,), dtype=torch.int32, device=dev)
+    rw = (C.c_float * 4)(*[float(v) for v in b2b_weights]) if b2b_weights is not None else None
+    check(lib.osr_rpn_select_wide(C.byref(lv), _p(cell_anchors), _p(ctr), _p(deltas), n, _p(image_hw), pre_nms_topk, float(min_box_size),
+                                  0 if b2b_weights is None else 1, rw, _p(boxes), _p(scores), _p(src), _p(bidx), _p(level), _p(counts), _p(flags),
+                                  _p(ws), wsb, _stream()), "osr_rpn_select_wide")
+    out = dict(boxes=boxes, scores=scores, src_index=src, batch_idx=bidx, counts=counts, status_flags=flags, cap=cap)
+    if level is not None:
+        out["level"] = level
+    return out
+
+
+RPN_SELECT_MAXK, RPN_SELECT_WIDE_MAXK = _lib.RPN_SELECT_MAXK, _lib.RPN_SELECT_WIDE_MAXK
+
+
 def retinanet_logit_thresh(score_thresh: float) -> float:
     """log(t / (1 - t)) in double, rounded once to fp32 (include/osr.h osr_retinanet_select: the candidates are `logit > this`)."""
     t = float(score_thresh)
@@ -1090,12 +1124,14 @@ def _roi_options(aligned, sampling_ratio):
 def roi_align(feats: List[torch.Tensor], scales: Sequence[float], boxes: torch.Tensor, batch_idx: torch.Tensor,
               pooled: int = 7, out_dtype: Optional[torch.dtype] = None, canonical_level: int = 4, canonical_size: int = 224,
               min_level: int = 2, order: Optional[torch.Tensor] = None, fill_padding: bool = True, aligned: bool = True,
-              sampling_ratio: int = 0) -> torch.Tensor:
+              sampling_ratio: int = 0, bin_stride: int = 1) -> torch.Tensor:
     """feats: NHWC per level; boxes (m,4) fp32; batch_idx (m) int32. Returns (m, pooled, pooled, c), pooled 1 .. MAX_POOLED_FWD. order: processing order, (m,)
     int32 or (m + 1,) as roi_locality_order returns it (None: that order when ROI_LOCALITY_ORDER, else list order); the result
     does not depend on it. fill_padding=False: the rows of padding entries (batch index -1) are left unwritten instead of zeroed.
     aligned / sampling_ratio: torchvision roi_align's (include/osr.h osr_roi_options); the defaults are POOLER_TYPE "ROIAlignV2" with
-    the adaptive grid, aligned=False is "ROIAlign", sampling_ratio=S > 0 a fixed S x S grid per bin."""
+    the adaptive grid, aligned=False is "ROIAlign", sampling_ratio=S > 0 a fixed S x S grid per bin.
+    bin_stride=2 (pooled 8 .. MAX_POOLED_FWD): only the bins at even positions are pooled, into (m, q, q, c) with q = ceil(pooled / 2),
+    each bit-identical to the full grid's (osr_roi_align_fwd_strided: what a stride-2 1 x 1 convolution reads of the grid)."""
     lib = _lib.load()
     opt = _roi_options(aligned, sampling_ratio)
     _need(boxes, torch.float32, "boxes"); _need(batch_idx, torch.int32, "batch_idx")
@@ -1110,6 +1146,15 @@ def roi_align(feats: List[torch.Tensor], scales: Sequence[float], boxes: torch.T
         if order.numel() == m + 1:
             nvalid = C.c_void_p(order.data_ptr() + 4 * m)
     out_dtype = out_dtype or feats[0].dtype
+    if bin_stride != 1:
+        if isinstance(bin_stride, bool) or not isinstance(bin_stride, int) or bin_stride < 1:
+            raise ValueError(f"RoIAlign: bin_stride must be a positive integer, got {bin_stride!r}")
+        q = -(-pooled // bin_stride)
+        out = torch.empty((m, q, q, py.c), dtype=out_dtype, device=boxes.device)
+        check(lib.osr_roi_align_fwd_strided(C.byref(py), _DT[feats[0].dtype], feats[0].shape[0], _p(boxes), _p(batch_idx), m, pooled, bin_stride,
+                                            canonical_level, canonical_size, min_level, _p(order), nvalid, 0 if fill_padding else 1, opt,
+                                            _p(out), _DT[out_dtype], _stream()), "osr_roi_align_fwd_strided")
+        return out
     out = torch.empty((m, pooled, pooled, py.c), dtype=out_dtype, device=boxes.device)
     check(lib.osr_roi_align_fwd_ordered_opt(C.byref(py), _DT[feats[0].dtype], feats[0].shape[0], _p(boxes), _p(batch_idx), m, pooled,
                                             canonical_level, canonical_size, min_level, _p(order), nvalid, 0 if fill_padding else 1, opt,
@@ -1294,6 +1339,22 @@ def mask_upsample_predict(x: torch.Tensor, w_packed: torch.Tensor, bias: torch.T
     check(lib.osr_mask_upsample_predict(_p(x), _DT[x.dtype], r, s, cin, cmid, _p(w_packed), _p(bias), _p(pred_w), _p(pred_b), k, _p(classes),
                                         _p(rows_valid), int(seg_rows), _p(probs), _stream()), "osr_mask_upsample_predict")
     return probs
+
+
+def avgpool_rows(x: torch.Tensor, rows_valid: Optional[torch.Tensor] = None, seg_rows: int = 0) -> torch.Tensor:
+    """[d2] Res5ROIHeads' box_features.mean(dim=[2, 3]) on channels-last rows (include/osr.h osr_avgpool_rows). x (r, s, c) or
+    (r, h, w, c); returns (r, c) fp32 = the fp32 sum over the positions in ascending order / their number. rows_valid (segments) int32
+    with seg_rows RoIs per segment: the RoIs beyond a segment's count come out as zeros."""
+    lib = _lib.load()
+    _need(x, name="x")
+    if x.dim() not in (3, 4):
+        raise OsrError(f"avgpool_rows: x {tuple(x.shape)} is not (r, s, c) or (r, h, w, c)")
+    r, c = x.shape[0], x.shape[-1]
+    s = x.shape[1] if x.dim() == 3 else x.shape[1] * x.shape[2]
+    _rows_valid_arg(rows_valid, seg_rows, r, "avgpool_rows")
+    out = torch.empty((r, c), dtype=torch.float32, device=x.device)
+    check(lib.osr_avgpool_rows(_p(x), _DT[x.dtype], r, s, c, _p(rows_valid), int(seg_rows), _p(out), _stream()), "osr_avgpool_rows")
+    return out
 
 
 def _rows_valid_arg(rows_valid, seg_rows, r, name):

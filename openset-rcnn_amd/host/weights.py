@@ -248,6 +248,32 @@ def random_standard_params(seed: int = 0, num_classes: int = 80, num_anchors: in
     return p
 
 
+def random_c4_params(seed: int = 0, num_classes: int = 80, num_anchors: int = 15, cls_agnostic: bool = False) -> Dict[str, torch.Tensor]:
+    """Seeded synthetic parameters for [d2] faster_rcnn_R_50_C4 under its names: random_params' BN-folded trunk with stem and res2..res4
+    under backbone.* (no `bottom_up`) and res5 under roi_heads.res5.*, a StandardRPNHead on res4's 1024 channels (conv 1024 -> 1024,
+    objectness_logits (A), anchor_deltas (4A)) and FastRCNNOutputLayers on res5's 2048 means, scaled so that logits and deltas spread."""
+    p = {}
+    for k, v in random_params(seed).items():
+        if k.startswith("backbone.bottom_up.res5."):
+            p["roi_heads.res5." + k[len("backbone.bottom_up.res5."):]] = v
+        elif k.startswith("backbone.bottom_up."):
+            p["backbone." + k[len("backbone.bottom_up."):]] = v
+    g = torch.Generator().manual_seed(seed + 4000)
+    rpn = "proposal_generator.rpn_head."
+    p[rpn + "conv.weight"] = torch.randn(1024, 1024, 3, 3, generator=g) * 0.01
+    p[rpn + "conv.bias"] = torch.zeros(1024)
+    p[rpn + "objectness_logits.weight"] = torch.randn(num_anchors, 1024, 1, 1, generator=g) * 0.25
+    p[rpn + "objectness_logits.bias"] = torch.zeros(num_anchors)
+    p[rpn + "anchor_deltas.weight"] = torch.randn(num_anchors * 4, 1024, 1, 1, generator=g) * 0.05
+    p[rpn + "anchor_deltas.bias"] = torch.zeros(num_anchors * 4)
+    rows = 4 if cls_agnostic else 4 * num_classes
+    p["roi_heads.box_predictor.cls_score.weight"] = torch.randn(num_classes + 1, 2048, generator=g) * 0.1
+    p["roi_heads.box_predictor.cls_score.bias"] = torch.zeros(num_classes + 1)
+    p["roi_heads.box_predictor.bbox_pred.weight"] = torch.randn(rows, 2048, generator=g) * 0.02
+    p["roi_heads.box_predictor.bbox_pred.bias"] = torch.zeros(rows)
+    return p
+
+
 def random_cascade_params(seed: int = 0, stages: int = 3, num_classes: int = 80, num_anchors: int = 3, fc_dim: int = 1024) -> Dict[str, torch.Tensor]:
     """random_standard_params with [d2] CascadeROIHeads' box stages: roi_heads.box_head.{s}.* and roi_heads.box_predictor.{s}.* for
     s < stages (class-agnostic bbox_pred). Stage 0 carries random_standard_params(seed)'s box head and output layers, stage s > 0
