@@ -1017,6 +1017,41 @@ osr_status osr_coco_match(int32_t task, const float* boxes, const float* scores,
                           int32_t num_thrs, const double* area_rng, int32_t num_areas, int32_t max_det, uint32_t* flags, int32_t* rank,
                           int32_t* match, double* sim, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * Class-agnostic box-proposal recall (AR@limit per area range), csrc/osr_proposal_recall.hip: what the reference's evaluator
+ * computes per image before it sums, for a batch of images, every area range and every proposal limit in ONE launch.
+ * host/proposal_evaluation.py's evaluate_box_proposals states the same rules as a torch-CPU loop and the tests hold the two against
+ * each other bit for bit. No host sync, no floating-point atomics, capturable, repeats are bit-identical. Every argument is validated
+ * before anything is launched (no GPU needed for a refusal); n == 0 is OSR_OK without a launch.
+ *
+ * Device inputs, all finite: boxes (n, cap, 4) fp32 xyxy, logits (n, cap) fp32, counts (n) int32 (clamped to 0 .. cap; rows past
+ * counts[i] hold anything and do not count). The batch's NON-CROWD ground truth in annotation order: gt_boxes (num_gt, 4) fp32 xyxy,
+ * gt_area (num_gt) fp32 (the annotation's area), seg_off (n + 1) int32: image i owns entries seg_off[i] .. seg_off[i + 1].
+ * max_gt_per_image: the largest segment, which the host knows since it built the table (a longer one is cut there).
+ * Host arrays: area_ranges (A, 2) fp32 {lo, hi}, limits (L) int32 >= 1, thresholds (T) fp32, used bit for bit as given.
+ *
+ *   - An image with counts[i] == 0, or with no non-crowd ground truth, adds nothing. That includes num_pos, since the reference skips
+ *     the image before it counts. All its gt_overlap entries are -1.
+ *   - Otherwise rank the proposals by logit, descending. Equal logits keep row order, so the sort is stable (-0 == +0).
+ *   - For area range a, the valid ground truths are those with lo <= area <= hi in fp32, both ends inclusive. An area of exactly 1024
+ *     is therefore both small and medium. num_pos[i, a] is their number. An invalid ground truth has gt_overlap -1.
+ *   - For limit l, the live proposals are the first min(counts[i], limit) ranks. The area filter comes before the limit.
+ *   - Then run min(live proposals, valid ground truths) rounds. Among live pairs take the largest osr_pairwise_iou (csrc/osr_boxes.h,
+ *     fp32, no FMA contraction). Ties go to the lowest ground-truth index in annotation order, then to the lowest rank. Record that IoU
+ *     at the chosen ground truth, then retire that ground truth and that proposal. A zero IoU is a legitimate choice. Ground truths
+ *     never chosen keep 0.
+ *   - hits[i, a, l, t] is the number of valid ground truths with gt_overlap >= thresholds[t], compared in fp32.
+ *
+ * Outputs: hits (n, A, L, T) int32 and num_pos (n, A) int32, written in full; gt_overlap (A, L, num_gt) fp32 or NULL, written at the
+ * entries the segments cover.
+ * Limits, OSR_ERR_UNSUPPORTED with nothing launched beyond them: cap <= 2048, max_gt_per_image <= 1024. A in 1 .. 8, L in 1 .. 8,
+ * T in 1 .. 16, limits >= 1, or OSR_ERR_INVALID_ARG.
+ * --------------------------------------------------------------------------------------------------------- */
+osr_status osr_proposal_recall(const float* boxes, const float* logits, const int32_t* counts, int32_t n, int32_t cap, const float* gt_boxes,
+                               const float* gt_area, const int32_t* seg_off, int32_t num_gt, int32_t max_gt_per_image,
+                               const float* area_ranges, int32_t num_areas, const int32_t* limits, int32_t num_limits,
+                               const float* thresholds, int32_t num_thrs, int32_t* hits, int32_t* num_pos, float* gt_overlap, void* stream);
+
 /* =========================================================================================================
  * Training step, forward half: targets and losses. Gradients are not
  * produced by this library yet; every function below is a forward kernel whose outputs equal the reference's

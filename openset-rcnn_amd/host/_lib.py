@@ -111,6 +111,9 @@ COCO_BBOX, COCO_KEYPOINTS = 0, 1
 COCO_MAX_CAP, COCO_MAX_DET, COCO_MAX_THRS, COCO_MAX_AREAS, COCO_MAX_KPTS, COCO_MAX_GROUP = 1024, 128, 16, 8, 32, 4096  # csrc/osr_coco_eval.hip CM_MAX_*
 
 
+PROPOSAL_MAX_CAP, PROPOSAL_MAX_GT, PROPOSAL_MAX_AREAS, PROPOSAL_MAX_LIMITS, PROPOSAL_MAX_THRS = 2048, 1024, 8, 8, 16  # csrc/osr_proposal_recall.hip PR_MAX_*
+
+
 class Pyramid(C.Structure):
     _fields_ = [
         ("num_levels", C.c_int32), ("c", C.c_int32),
@@ -186,6 +189,8 @@ PROTOTYPES = {
     # COCO box / keypoint matching (csrc/osr_coco_eval.hip)
     "osr_coco_match_workspace_bytes": (I64, [I32, I32, I32]),
     "osr_coco_match": (I32, [I32, P, P, P, P, P, I32, I32, I32, I32, P, P, P, P, P, P, I32, I32, P, I32, P, I32, I32, P, P, P, P, P, I64, P]),
+    # box-proposal recall (csrc/osr_proposal_recall.hip)
+    "osr_proposal_recall": (I32, [P, P, P, I32, I32, P, P, P, I32, I32, P, I32, P, I32, P, I32, P, P, P, P]),
     "osr_fastrcnn_candidates": (I32, [P, P, I32, I32, P, P, I32, I32, P, P, F32, P, P, P, P, P, P]),
     "osr_cascade_refine": (I32, [P, P, P, I32, I32, P, P, I32, P, P, P, I32, I32, F32, P, P, P, P, P, P, P]),
     "osr_cascade_candidates": (I32, [P, I32, P, I32, P, P, I32, I32, P, P, F32, P, P, P, P, P, P]),

@@ -11,7 +11,10 @@ v0.6 (coco_evaluation.py), and the rules are spelled out in include/osr.h (osr_c
     flags with vectorised numpy: per category one stable argsort of -score over the image-ordered detections with rank < maxDets,
     then cumulative sums over the thresholds. Both paths end in the same `precision_recall`, so they return equal figures.
 
-Not built: `segm` (polygon rasterisation and RLE), box-proposal AR, LVIS, a device accumulate."""
+Outputs that carry "proposals" (a ProposalNetwork's) are scored by host/proposal_evaluation.py: class-agnostic AR@100 / AR@1000 per
+area range, matched on the device by ops.proposal_recall, reported as "box_proposals" ahead of the tasks.
+
+Not built: `segm` (polygon rasterisation and RLE), LVIS, a device accumulate."""
 from __future__ import annotations
 
 import json
@@ -26,6 +29,7 @@ import torch
 from . import parallel
 from .datasets import MetadataCatalog
 from .os_coco_evaluation import box_iou_xywh
+from .proposal_evaluation import ProposalRecall
 
 logger = logging.getLogger(__name__)
 
@@ -334,9 +338,11 @@ class _GroundTruthTables:
         order = np.argsort(key, kind="mergesort")
         anns = [anns[i] for i in order]
         self.key = key[order]
+        self.json_pos = order  # where the annotation stands in the JSON: an image's annotation order (proposal recall reads it)
         self.box = np.array([a["bbox"] for a in anns], dtype=np.float64).reshape(-1, 4)
         self.area = np.array([a["area"] if "area" in a else a["bbox"][2] * a["bbox"][3] for a in anns], dtype=np.float64)
         crowd = np.array([int(a.get("iscrowd", 0)) for a in anns], dtype=np.uint8)
+        self.crowd = crowd
         nokp = np.array([a.get("num_keypoints", 0) == 0 for a in anns], dtype=bool)
         self.flags = {"bbox": (crowd | (crowd << 1)).astype(np.uint8), "keypoints": (crowd | ((crowd.astype(bool) | nokp).astype(np.uint8) << 1)).astype(np.uint8)}
         self.ann_ids = [a.get("id") for a in anns]
@@ -386,6 +392,9 @@ class COCOEvaluator:
     predictions carry: bbox, and keypoints when they have pred_keypoints) or a config node (bbox, keypoints with MODEL.KEYPOINT_ON;
     with MODEL.MASK_ON one warning that `segm` is not built, and the rest is scored). Asking for "segm" by name raises.
 
+    Outputs with "proposals" (with or without "instances") add "box_proposals": {AR@100, ARs@100, ARm@100, ARl@100, AR@1000, ...}, first
+    in the result, and <output_dir>/box_proposals.pkl.
+
     evaluate() returns {"bbox": {AP, AP50, AP75, APs, APm, APl, "AP-<name>" per class when there are several}, "keypoints": {AP, AP50,
     AP75, APm, APl}}, x100, NaN where COCOeval says -1, and writes detectron2's coco_instances_results.json into output_dir."""
 
@@ -419,9 +428,12 @@ class COCOEvaluator:
         self.class_names = [c["name"] for c in cats]
         id_map = getattr(meta, "thing_dataset_id_to_contiguous_id", None) or {c["id"]: i for i, c in enumerate(cats)}
         self.reverse_id_map = {v: k for k, v in id_map.items()}
+        self.proposals = ProposalRecall(self.tables)
         self.reset()
 
     def reset(self) -> None:
+        self.proposals.reset()
+        self._saw_instances = False
         self._cpu_records: List[dict] = []
         self._chunks: List[dict] = []      # per device batch: tensors that stay on the device
         self._image_ids: List = []         # of the device batches, in order
@@ -442,9 +454,14 @@ class COCOEvaluator:
         raise ValueError(f"COCOEvaluator: {num_keypoints} keypoints and no TEST.KEYPOINT_OKS_SIGMAS (only the 17 COCO keypoints have built-in sigmas)")
 
     def process(self, inputs: Sequence[dict], outputs: Sequence[dict]) -> None:
+        if outputs and "proposals" in outputs[0]:
+            self.proposals.process(inputs, outputs, keep=self.output_dir is not None)
+            if "instances" not in outputs[0]:
+                return
         insts = [o["instances"] for o in outputs]
         if not insts:
             return
+        self._saw_instances = True
         has_kp = insts[0].has("pred_keypoints")
         tasks = self._tasks_for(has_kp)
         if "keypoints" in tasks:
@@ -612,9 +629,22 @@ class COCOEvaluator:
             if self.tasks is None:
                 self.tasks = ("bbox", "keypoints") if records and "keypoints" in records[0] else ("bbox",)
             return self._score_records(records, img_ids)
-        gathered = parallel.gather_to_rank0({"device": self._fetch(), "cpu": self._cpu_records})
+        gathered = parallel.gather_to_rank0({"device": self._fetch(), "cpu": self._cpu_records, "instances": self._saw_instances,
+                                             "proposals": self.proposals.state(keep=self.output_dir is not None)})
         if gathered is None:
             return None
+        states = [g["proposals"] for g in gathered]
+        box_proposals = self.proposals.results(states)
+        if box_proposals is None:
+            return self._evaluate_instances(gathered, img_ids)
+        if self.output_dir:
+            self.proposals.write(states, self.output_dir)
+        out = {"box_proposals": box_proposals}  # (first, as in the reference)
+        if any(g["instances"] for g in gathered):
+            out.update(self._evaluate_instances(gathered, img_ids))
+        return out
+
+    def _evaluate_instances(self, gathered, img_ids) -> dict:
         parts = [g["device"] for g in gathered if g["device"] is not None]
         records = [r for q in parts for r in self._records_from(q)] + [r for g in gathered for r in g["cpu"]]
         if self.output_dir:

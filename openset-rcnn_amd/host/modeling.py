@@ -1405,6 +1405,92 @@ class GeneralizedRCNN(_EngineOwner):
 
 
 # ---------------------------------------------------------------------------------------------------------------
+# ProposalNetwork
+# ---------------------------------------------------------------------------------------------------------------
+PROPOSAL_NETWORK_KEY = 'MODEL.META_ARCHITECTURE "ProposalNetwork"'
+PROPOSAL_NETWORK_TRAINING_MESSAGE = (f'{PROPOSAL_NETWORK_KEY} runs at inference only on the HIP path: the trainers are built around the RoI heads\' '
+                                     'samplers and losses. Train the GeneralizedRCNN of the same backbone and proposal generator, and load its '
+                                     'checkpoint here (the roi_heads.* keys are reported as unexpected)')
+
+
+@META_ARCH_REGISTRY.register()
+class ProposalNetwork(_EngineOwner):
+    """[d2] ProposalNetwork: backbone + proposal generator, no RoI heads, under detectron2's parameter names (backbone.*,
+    proposal_generator.*). model(list[dict{image,height,width}]) -> list[{"proposals": Instances(proposal_boxes, objectness_logits)}]
+    in eval mode: the engine's backbone and RPN stage with the test-time top-k values, then [d2] detector_postprocess for proposals on
+    the device (scale to height / width, clip, drop empty boxes). PROPOSAL_GENERATOR.NAME "RPN" on the FPN or the C4 backbone, or
+    "ClsFreeRPN" (kernel_dtype float16 / bfloat16 / float32). No RoI-head weight exists, so none is packed."""
+    _prefix = ""
+
+    def __init__(self, cfg: CfgNode, class_id: Optional[torch.Tensor] = None):
+        super().__init__()
+        for on, key in ((cfg.MODEL.MASK_ON, "MODEL.MASK_ON"), (cfg.MODEL.KEYPOINT_ON, "MODEL.KEYPOINT_ON"), (cfg.TEST.AUG.ENABLED, "TEST.AUG")):
+            if on:
+                raise ValueError(f"{key} with {PROPOSAL_NETWORK_KEY}: a proposal network has no RoI heads, so no mask or keypoint branch and no "
+                                 "detections to augment")
+        self.backbone = BACKBONE_REGISTRY.get(cfg.MODEL.BACKBONE.NAME)(cfg)  # (a C4 backbone checks its own keys: PRE_NMS_TOPK_TEST <= 8192)
+        self.proposal_generator = PROPOSAL_GENERATOR_REGISTRY.get(cfg.MODEL.PROPOSAL_GENERATOR.NAME)(cfg, self.backbone.output_shape())
+        self.register_buffer("pixel_mean", torch.tensor(cfg.MODEL.PIXEL_MEAN).view(-1, 1, 1), False)
+        self.register_buffer("pixel_std", torch.tensor(cfg.MODEL.PIXEL_STD).view(-1, 1, 1), False)
+        head = self.proposal_generator.rpn_head
+        self._eng_cfg = dict(head._eng_cfg)  # the proposal generator's own engine: the stock RPN's, the C4 RPN's or the CF-RPN's
+        self._engine_cls = head._engine_cls
+
+    @property
+    def device(self):
+        return self.pixel_mean.device
+
+    _stack_images = GeneralizedRCNN._stack_images
+
+    def engine(self) -> OpensetRCNNEngine:
+        eng = super().engine()
+        for child in (self.backbone, self.proposal_generator.rpn_head):
+            child._shared = eng  # one packed copy of the weights for the whole model
+        return eng
+
+    def refresh(self):
+        super().refresh()
+        for child in (self.backbone, self.proposal_generator.rpn_head):
+            child._shared = None
+            child.refresh()
+
+    def forward(self, batched_inputs: List[dict]):
+        if self.training:
+            raise NotImplementedError(PROPOSAL_NETWORK_TRAINING_MESSAGE)
+        return self.inference(batched_inputs)
+
+    def make_trainer(self, *a, **k):
+        raise NotImplementedError(PROPOSAL_NETWORK_TRAINING_MESSAGE)
+
+    def trainer(self):
+        raise NotImplementedError(PROPOSAL_NETWORK_TRAINING_MESSAGE)
+
+    def losses_forward(self, *a, **k):
+        raise NotImplementedError(PROPOSAL_NETWORK_TRAINING_MESSAGE)
+
+    @torch.no_grad()
+    def inference(self, batched_inputs: List[dict], do_postprocess: bool = True):
+        """[d2] ProposalNetwork.forward. do_postprocess=False: the proposals as the RPN stage leaves them, in the model input's
+        coordinates. One D2H copy (the counts): the list-of-Instances form needs the lengths on the host."""
+        eng = self.engine()
+        batch, sizes = self._stack_images([x["image"] for x in batched_inputs])
+        d = eng.cfg["size_divisibility"]
+        hp, wp = (int(batch.shape[-2]) + d - 1) // d * d, (int(batch.shape[-1]) + d - 1) // d * d
+        image_hw = torch.tensor(sizes, dtype=torch.int32).to(self.device, non_blocking=True)
+        sel = eng._rpn(eng._backbone(batch, hp, wp), image_hw)
+        n, cap = len(sizes), int(sel["cap"])
+        boxes, logits, counts = sel["boxes"].view(n, cap, 4), sel["scores"].view(n, cap), sel["counts"]
+        outs = sizes
+        if do_postprocess:
+            outs = [(int(inp.get("height", s[0])), int(inp.get("width", s[1]))) for inp, s in zip(batched_inputs, sizes)]
+            scale = torch.tensor([[ow / s[1], oh / s[0]] for (oh, ow), s in zip(outs, sizes)], dtype=torch.float32, device=self.device)
+            boxes, logits, _, counts = ops.detector_postprocess(boxes.contiguous(), logits.contiguous(), torch.zeros((n, cap), dtype=torch.int64, device=self.device),
+                                                                counts, scale, torch.tensor(outs, dtype=torch.int32, device=self.device))
+        host = counts.cpu().tolist()
+        return [{"proposals": Instances(o, proposal_boxes=Boxes(boxes[i, :host[i]]), objectness_logits=logits[i, :host[i]])} for i, o in enumerate(outs)]
+
+
+# ---------------------------------------------------------------------------------------------------------------
 # RetinaNet
 # ---------------------------------------------------------------------------------------------------------------
 class LastLevelP6P7(nn.Module):

@@ -1821,6 +1821,42 @@ def coco_match(boxes: torch.Tensor, scores: torch.Tensor, classes: torch.Tensor,
     return flags, rank, match, (sim if want_sim else None)
 
 
+# ---- box-proposal recall (csrc/osr_proposal_recall.hip; host/proposal_evaluation.py) -------------------------------------------------
+def proposal_recall(boxes: torch.Tensor, logits: torch.Tensor, counts: torch.Tensor, gt_boxes: torch.Tensor, gt_area: torch.Tensor,
+                    seg_off: torch.Tensor, max_gt_per_image: int, area_ranges: torch.Tensor, limits: Sequence[int], thresholds: torch.Tensor,
+                    want_overlaps: bool = False):
+    """A batch's proposals matched to its non-crowd ground truth in one launch (include/osr.h osr_proposal_recall, which states every
+    rule). boxes (n, cap, 4) fp32 xyxy, logits (n, cap) fp32, counts (n) int32; gt_boxes (NG, 4) / gt_area (NG) fp32, seg_off (n + 1)
+    int32. area_ranges (A, 2) and thresholds (T) are fp32 CPU tensors whose bits the kernel compares with; limits a host sequence.
+    -> (hits (n, A, L, T) int32, num_pos (n, A) int32, gt_overlap (A, L, NG) fp32 or None)."""
+    lib = _lib.load()
+    _need(boxes, torch.float32, "boxes"); _need(logits, torch.float32, "logits"); _need(counts, torch.int32, "counts")
+    _need(gt_boxes, torch.float32, "gt_boxes"); _need(gt_area, torch.float32, "gt_area"); _need(seg_off, torch.int32, "seg_off")
+    if boxes.dim() != 3 or boxes.shape[2] != 4:
+        raise OsrError(f"proposal_recall: boxes {tuple(boxes.shape)} must be (n, cap, 4)")
+    n, cap = int(boxes.shape[0]), int(boxes.shape[1])
+    ng = int(gt_area.numel())
+    if tuple(logits.shape) != (n, cap) or counts.numel() != n or seg_off.numel() != n + 1 or tuple(gt_boxes.shape) != (ng, 4):
+        raise OsrError(f"proposal_recall: logits {tuple(logits.shape)} must be {(n, cap)}, counts ({n}), seg_off ({n + 1}) got {seg_off.numel()}, "
+                       f"gt_boxes {tuple(gt_boxes.shape)} ({ng}, 4)")
+    for t, name in ((area_ranges, "area_ranges"), (thresholds, "thresholds")):
+        if t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous():
+            raise OsrError(f"proposal_recall: {name} must be a contiguous float32 CPU tensor")
+    if area_ranges.dim() != 2 or area_ranges.shape[1] != 2 or thresholds.dim() != 1:
+        raise OsrError(f"proposal_recall: area_ranges {tuple(area_ranges.shape)} must be (A, 2), thresholds {tuple(thresholds.shape)} (T)")
+    lim = [int(v) for v in limits]
+    a, l, t = int(area_ranges.shape[0]), len(lim), int(thresholds.numel())
+    dev = boxes.device
+    hits = torch.empty((n, a, l, t), dtype=torch.int32, device=dev)
+    num_pos = torch.empty((n, a), dtype=torch.int32, device=dev)
+    ov = torch.full((a, l, ng), -1.0, dtype=torch.float32, device=dev) if want_overlaps else None
+    check(lib.osr_proposal_recall(_p(boxes) if cap else None, _p(logits) if cap else None, _p(counts), n, cap, _p(gt_boxes) if ng else None,
+                                  _p(gt_area) if ng else None, _p(seg_off), ng, int(max_gt_per_image), C.c_void_p(area_ranges.data_ptr()), a,
+                                  (C.c_int32 * max(l, 1))(*lim), l, C.c_void_p(thresholds.data_ptr()), t, _p(hits), _p(num_pos), _p(ov), _stream()),
+          "osr_proposal_recall")
+    return hits, num_pos, ov
+
+
 # ---- test-time augmentation glue (csrc/osr_tta.hip; host/tta.py) ---------------------------------------------------------------
 def _tta_lists(boxes, counts, sizes, name):
     _need(boxes, torch.float32, "boxes"); _need(counts, torch.int32, "counts"); _need(sizes, torch.int32, "sizes")

@@ -334,12 +334,23 @@ class OpensetCOCOEvaluator:
         self.reverse_id_map = contiguous_to_dataset_id
         self.max_dets = list(max_dets_per_image)
         self.output_dir = output_dir
+        from .coco_evaluation import _GroundTruthTables  # (that module imports this one)
+        from .proposal_evaluation import ProposalRecall
+        self.proposals = ProposalRecall(_GroundTruthTables(gt_json))
         self.reset()
 
     def reset(self):
         self._predictions: List[dict] = []
+        self._saw_instances = False
+        self.proposals.reset()
 
     def process(self, inputs, outputs):
+        """outputs carry "instances", "proposals" (a ProposalNetwork's: class-agnostic AR, host/proposal_evaluation.py) or both."""
+        if outputs and "proposals" in outputs[0]:
+            self.proposals.process(inputs, outputs, keep=self.output_dir is not None)
+            if "instances" not in outputs[0]:
+                return
+        self._saw_instances = self._saw_instances or len(outputs) > 0
         for inp, out in zip(inputs, outputs):
             self._predictions += instances_to_coco_json(out["instances"], inp["image_id"], self.reverse_id_map)
 
@@ -358,14 +369,28 @@ class OpensetCOCOEvaluator:
             with open(os.path.join(self.output_dir, self.RESULTS_FILE)) as f:
                 dets = json.load(f)
         else:
-            gathered = parallel.gather_to_rank0(self._predictions)
+            keep = self.output_dir is not None
+            gathered = parallel.gather_to_rank0({"dets": self._predictions, "instances": self._saw_instances, "proposals": self.proposals.state(keep=keep)})
             if gathered is None:
                 return None
-            dets = [d for part in gathered for d in part]
-            if self.output_dir:
-                os.makedirs(self.output_dir, exist_ok=True)
-                with open(os.path.join(self.output_dir, self.RESULTS_FILE), "w") as f:
-                    json.dump(dets, f)
+            dets = [d for part in gathered for d in part["dets"]]
+            states = [part["proposals"] for part in gathered]
+            box_proposals = self.proposals.results(states)
+            if box_proposals is not None:
+                if self.output_dir:
+                    self.proposals.write(states, self.output_dir)
+                res = {"box_proposals": box_proposals}  # (first, as in the reference)
+                if any(part["instances"] for part in gathered):
+                    res.update(self._score(dets, img_ids, write=True))
+                return res
+            return self._score(dets, img_ids, write=True)
+        return self._score(dets, img_ids, write=False)
+
+    def _score(self, dets, img_ids, write: bool):
+        if write and self.output_dir:
+            os.makedirs(self.output_dir, exist_ok=True)
+            with open(os.path.join(self.output_dir, self.RESULTS_FILE), "w") as f:
+                json.dump(dets, f)
         if not dets:
             return {"bbox": {m: float("nan") for m in METRICS}}
         ev = OpensetCOCOEval(copy.deepcopy(self.gt), dets, self.known_ids, self.max_dets, img_ids)

@@ -139,7 +139,8 @@ def do_test(cfg, args, model, D, iteration: int = 0):
         results[name] = res
         if res is not None:
             logger.info("Evaluation results for %s:", name)
-            multi = isinstance(res, dict) and "bbox" in res and "keypoints" in res  # COCOEvaluator with both tasks: one line each
+            # COCOEvaluator with both tasks, or proposals beside (or without) detections: one line each, box_proposals first
+            multi = isinstance(res, dict) and (("bbox" in res and "keypoints" in res) or "box_proposals" in res)
             flat = res if multi else res.get("bbox", res) if isinstance(res, dict) else res
             if flat and all(isinstance(v, dict) for v in flat.values()):  # one line per task (sem_seg, panoptic_seg)
                 for task, figures in flat.items():
