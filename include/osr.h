@@ -1018,6 +1018,72 @@ osr_status osr_coco_match(int32_t task, const float* boxes, const float* scores,
                           int32_t* match, double* sim, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * Open-set COCO matching (known and unknown AP / AR, wilderness impact, A-OSE): the per-image half of OpensetCOCOEval.evaluate,
+ * csrc/osr_os_coco_eval.hip. The rules below restate host/os_coco_evaluation.py (itself a restatement of the reference's
+ * os_cocoeval.py:242-555), and THIS TEXT is the contract; the numpy class states the same rules as literal sequential loops and the
+ * tests hold the two against each other bit for bit.
+ *
+ * osr_os_coco_match: ONE launch scores n images for every class slot, every area range and every IoU threshold; each slot's
+ * detection list is matched against up to THREE ground-truth sets of its image. No host sync, no atomics, capturable, repeats are
+ * bit-identical. Every argument is validated before anything is launched (no GPU needed for a refusal); n == 0 or cap == 0 is
+ * OSR_OK without a launch.
+ *
+ * Detections, the engines' padded lists (need not be sorted): boxes (n, cap, 4) fp32 xyxy, scores (n, cap) fp32, classes (n, cap)
+ * int64, counts (n) int32 (clamped to 0 .. cap).
+ * Class slots: class_slot (L) int32, built by the host, maps a class VALUE v to a slot: 0 .. K - 1 the known categories in ascending
+ * dataset id, K the unknown class (prediction value 1000, with or without a contiguous-id map), -1 dropped. A value outside [0, L)
+ * and an entry outside -1 .. K are dropped as well.
+ * Ground truth, built by the host from the JSON for the batch's images, one table with per-image offsets: gt_img_off (n + 1) int32,
+ * image i owns entries gt_img_off[i] .. gt_img_off[i + 1]; WITHIN an image the entries are sorted by (slot ascending, then annotation
+ * order). gt_box (NG, 4) fp64 xywh; gt_area (NG) fp64 (the JSON's area, else w * h); gt_slot (NG) int32: the known slot or K (any
+ * other value belongs to no set); gt_pos (NG) int32: the entry's position in the JSON's annotation order within its image (distinct
+ * within an image); gt_crowd (NG) uint8, bit 0 iscrowd (ignore = iscrowd). max_gt_per_image: the largest image, which the host knows
+ * since it built the table (a longer one is cut there).
+ * Host arrays: iou_thrs (T) fp64, passed as the doubles np.linspace(.5, .95, 10) gives and never recomputed; area_rng (A, 2) fp64
+ * {lo, hi}; max_det.
+ *
+ * Per (image i, slot c):
+ *   - the detection list is the rows r < counts[i] whose class maps to c, by descending score, equal scores the lower row first
+ *     (mergesort's stable order; scores compare by their order-preserving bit key, -0 == +0), cut to max_det. rank (n, cap) int32
+ *     is the row's position in that list, -1 for rows >= counts[i], dropped classes and rows beyond max_det;
+ *   - detection geometry, as instances_to_coco_json followed by loadRes: the four fp32 corners are widened to fp64 FIRST, then
+ *     w = x1 - x0, h = y1 - y0 and area = w * h in fp64. (osr_coco_match subtracts in fp32 and widens afterwards: the two differ
+ *     in the last bits for corners off a coarse grid, each as its own evaluator's records do);
+ *   - similarity, fp64 maskUtils.iou on xywh exactly as box_iou_xywh: iw = max(min(dx + dw, gx + gw) - max(dx, gx), 0), ih likewise,
+ *     inter = iw * ih, union = (dw * dh + gw * gh) - inter, or dw * dh for a crowd ground truth; inter / union, 0 where the union
+ *     is not positive;
+ *   - the sets. A known slot c < K: S0 the ground truths of slot c in annotation order; S1 those of the OTHER known slots in
+ *     annotation order across the slots (position = gt_pos); S2 the unknown ones in annotation order. The unknown slot K: S0 the
+ *     unknown ground truths in annotation order; S1 ALL known ones ordered by (slot ascending, then annotation order), i.e. in table
+ *     order, which is NOT a known slot's S1 order; no S2. With the table sorted as above, a set's order is the table's except for a
+ *     known slot's S1;
+ *   - the matching rule per set is pycocotools' as osr_coco_match states it. In area range a a ground truth is ignored when it is
+ *     crowd or its area is outside [lo, hi]. Per threshold t the detections are matched in list order, thr = min(t, 1 - 1e-10). A
+ *     ground truth is available unless an earlier detection of this (set, t, a) took it, or it is crowd. Among the available, not
+ *     ignored ground truths of the set with similarity >= thr the detection takes the largest similarity, equal similarities going
+ *     to the HIGHEST position in the set's order; if there is none, the same rule among the available ignored ones; else it stays
+ *     unmatched;
+ *   - a matched detection is ignored iff its ground truth is ignored at a; an unmatched one iff its own area is outside [lo, hi],
+ *     decided separately for each set.
+ *
+ * Outputs (all written in full by the call): rank; flags (n, cap, A, 3) uint32, word s belongs to set s: bit t = matched at
+ * threshold t, bit 16 + t = ignored at threshold t; a word is 0 where rank is -1, and word 2 is 0 for the unknown slot; match
+ * (n, cap, A, 3, T) int32 or NULL: the matched ground truth's index into gt_*, else -1.
+ * workspace: osr_os_coco_match_workspace_bytes(cap, NG) = cap * NG * 8 bytes for the similarities (image i's rows x ground truths
+ * from gt_img_off[i] * cap doubles on); OSR_ERR_WORKSPACE when it is smaller.
+ *
+ * Limits, OSR_ERR_UNSUPPORTED with nothing launched beyond them: cap <= 1024, max_det <= 128, T <= 16, A <= 8, max_gt_per_image <=
+ * 4096, n * (K + 1) < 2^31 - 1. L >= 1, K >= 0. A NaN score orders by its bit pattern; NaN similarities match nothing.
+ * --------------------------------------------------------------------------------------------------------- */
+int64_t osr_os_coco_match_workspace_bytes(int32_t cap, int32_t num_gt);
+osr_status osr_os_coco_match(const float* boxes, const float* scores, const int64_t* classes, const int32_t* counts, int32_t n, int32_t cap,
+                             const int32_t* class_slot, int32_t num_class_values, int32_t num_known, const int32_t* gt_img_off,
+                             const double* gt_box, const double* gt_area, const int32_t* gt_slot, const int32_t* gt_pos,
+                             const uint8_t* gt_crowd, int32_t num_gt, int32_t max_gt_per_image, const double* iou_thrs, int32_t num_thrs,
+                             const double* area_rng, int32_t num_areas, int32_t max_det, uint32_t* flags, int32_t* rank, int32_t* match,
+                             void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Class-agnostic box-proposal recall (AR@limit per area range), csrc/osr_proposal_recall.hip: what the reference's evaluator
  * computes per image before it sums, for a batch of images, every area range and every proposal limit in ONE launch.
  * host/proposal_evaluation.py's evaluate_box_proposals states the same rules as a torch-CPU loop and the tests hold the two against

@@ -109,6 +109,8 @@ CONF_LABELS, CONF_VALUES = 0, 1
 PQ_MAX_GT, PQ_MAX_PRED = 1023, 2047  # csrc/osr_seg_eval.hip PP_MAX_G / PP_MAX_P
 COCO_BBOX, COCO_KEYPOINTS = 0, 1
 COCO_MAX_CAP, COCO_MAX_DET, COCO_MAX_THRS, COCO_MAX_AREAS, COCO_MAX_KPTS, COCO_MAX_GROUP = 1024, 128, 16, 8, 32, 4096  # csrc/osr_coco_eval.hip CM_MAX_*
+OS_COCO_MAX_CAP, OS_COCO_MAX_DET, OS_COCO_MAX_THRS, OS_COCO_MAX_AREAS, OS_COCO_MAX_GT = 1024, 128, 16, 8, 4096  # csrc/osr_os_coco_eval.hip OM_MAX_*
+OS_COCO_SETS = 3  # flag words per (detection, area range): own slot, other known, unknown
 
 
 PROPOSAL_MAX_CAP, PROPOSAL_MAX_GT, PROPOSAL_MAX_AREAS, PROPOSAL_MAX_LIMITS, PROPOSAL_MAX_THRS = 2048, 1024, 8, 8, 16  # csrc/osr_proposal_recall.hip PR_MAX_*
@@ -189,6 +191,9 @@ PROTOTYPES = {
     # COCO box / keypoint matching (csrc/osr_coco_eval.hip)
     "osr_coco_match_workspace_bytes": (I64, [I32, I32, I32]),
     "osr_coco_match": (I32, [I32, P, P, P, P, P, I32, I32, I32, I32, P, P, P, P, P, P, I32, I32, P, I32, P, I32, I32, P, P, P, P, P, I64, P]),
+    # open-set COCO matching (csrc/osr_os_coco_eval.hip)
+    "osr_os_coco_match_workspace_bytes": (I64, [I32, I32]),
+    "osr_os_coco_match": (I32, [P, P, P, P, I32, I32, P, I32, I32, P, P, P, P, P, P, I32, I32, P, I32, P, I32, I32, P, P, P, P, I64, P]),
     # box-proposal recall (csrc/osr_proposal_recall.hip)
     "osr_proposal_recall": (I32, [P, P, P, I32, I32, P, P, P, I32, I32, P, I32, P, I32, P, I32, P, P, P, P]),
     "osr_fastrcnn_candidates": (I32, [P, P, I32, I32, P, P, I32, I32, P, P, F32, P, P, P, P, P, P]),

@@ -1821,6 +1821,47 @@ def coco_match(boxes: torch.Tensor, scores: torch.Tensor, classes: torch.Tensor,
     return flags, rank, match, (sim if want_sim else None)
 
 
+# ---- open-set COCO matching (csrc/osr_os_coco_eval.hip; host/os_coco_evaluation.py) ------------------------------------------------------
+def os_coco_match(boxes: torch.Tensor, scores: torch.Tensor, classes: torch.Tensor, counts: torch.Tensor, class_slot: torch.Tensor, num_known: int,
+                  gt_img_off: torch.Tensor, gt_box: torch.Tensor, gt_area: torch.Tensor, gt_slot: torch.Tensor, gt_pos: torch.Tensor,
+                  gt_crowd: torch.Tensor, max_gt_per_image: int, iou_thrs: Sequence[float], area_rng: Sequence[Sequence[float]], max_det: int,
+                  want_match: bool = False):
+    """A batch of images scored against its open-set ground truth in one launch (include/osr.h osr_os_coco_match, which states every
+    rule). boxes (n, cap, 4) fp32 xyxy, scores (n, cap) fp32, classes (n, cap) int64, counts (n) int32; class_slot (L) int32: class
+    value -> slot 0 .. num_known (the last one unknown) or -1; gt_img_off (n + 1) int32, gt_box (NG, 4) / gt_area (NG) float64,
+    gt_slot / gt_pos (NG) int32, gt_crowd (NG) uint8, each image's entries sorted by (slot, annotation order); iou_thrs and area_rng
+    are host sequences of doubles.
+    -> (flags (n, cap, A, 3) int32 holding the uint32 words, rank (n, cap) int32, match (n, cap, A, 3, T) int32 or None)."""
+    lib = _lib.load()
+    _need(boxes, torch.float32, "boxes"); _need(scores, torch.float32, "scores"); _need(classes, torch.int64, "classes"); _need(counts, torch.int32, "counts")
+    _need(class_slot, torch.int32, "class_slot"); _need(gt_img_off, torch.int32, "gt_img_off"); _need(gt_box, torch.float64, "gt_box")
+    _need(gt_area, torch.float64, "gt_area"); _need(gt_slot, torch.int32, "gt_slot"); _need(gt_pos, torch.int32, "gt_pos"); _need(gt_crowd, torch.uint8, "gt_crowd")
+    if boxes.dim() != 3 or boxes.shape[2] != 4:
+        raise OsrError(f"os_coco_match: boxes {tuple(boxes.shape)} must be (n, cap, 4)")
+    n, cap = int(boxes.shape[0]), int(boxes.shape[1])
+    ng, nl = int(gt_area.numel()), int(class_slot.numel())
+    if tuple(scores.shape) != (n, cap) or tuple(classes.shape) != (n, cap) or counts.numel() != n or gt_img_off.numel() != n + 1 or \
+            tuple(gt_box.shape) != (ng, 4) or gt_slot.numel() != ng or gt_pos.numel() != ng or gt_crowd.numel() != ng or nl < 1:
+        raise OsrError(f"os_coco_match: scores {tuple(scores.shape)} / classes {tuple(classes.shape)} must be {(n, cap)}, counts ({n}), gt_img_off "
+                       f"({n + 1}) got {gt_img_off.numel()}, gt_box {tuple(gt_box.shape)} ({ng}, 4), gt_slot / gt_pos / gt_crowd ({ng}), class_slot "
+                       f"({nl}) at least one entry")
+    thrs = [float(v) for v in iou_thrs]
+    rng = [float(v) for r in area_rng for v in r]
+    t, a = len(thrs), len(rng) // 2
+    dev = boxes.device
+    flags = torch.empty((n, cap, a, _lib.OS_COCO_SETS), dtype=torch.int32, device=dev)
+    rank = torch.empty((n, cap), dtype=torch.int32, device=dev)
+    match = torch.empty((n, cap, a, _lib.OS_COCO_SETS, t), dtype=torch.int32, device=dev) if want_match else None
+    ws_bytes = int(lib.osr_os_coco_match_workspace_bytes(cap, ng))
+    ws = torch.empty((max(ws_bytes, 0) // 8,), dtype=torch.float64, device=dev)
+    check(lib.osr_os_coco_match(_p(boxes), _p(scores), _p(classes), _p(counts), n, cap, _p(class_slot), nl, int(num_known), _p(gt_img_off),
+                                _p(gt_box) if ng else None, _p(gt_area) if ng else None, _p(gt_slot) if ng else None, _p(gt_pos) if ng else None,
+                                _p(gt_crowd) if ng else None, ng, int(max_gt_per_image), (C.c_double * t)(*thrs), t, (C.c_double * (2 * a))(*rng), a,
+                                int(max_det), _p(flags), _p(rank), _p(match), _p(ws) if ws_bytes > 0 else None, max(ws_bytes, 0), _stream()),
+          "osr_os_coco_match")
+    return flags, rank, match
+
+
 # ---- box-proposal recall (csrc/osr_proposal_recall.hip; host/proposal_evaluation.py) -------------------------------------------------
 def proposal_recall(boxes: torch.Tensor, logits: torch.Tensor, counts: torch.Tensor, gt_boxes: torch.Tensor, gt_area: torch.Tensor,
                     seg_off: torch.Tensor, max_gt_per_image: int, area_ranges: torch.Tensor, limits: Sequence[int], thresholds: torch.Tensor,

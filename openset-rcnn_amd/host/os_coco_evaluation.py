@@ -16,11 +16,17 @@ os_coco_evaluation.py:336-440:
     detections matched to known GT, and closed-set TP+FP / open-set FP at each recall threshold (wilderness impact);
   * summary (:789-972): 30 numbers -- known AP / AP50 / AP75 / APs / APm / APl, AR@10/20/30/50/100, ARs / ARm / ARl, WI at
     recall 0.8 and IoU 0.5, A-OSE at IoU 0.5, then the same 14 AP/AR numbers for the unknown class.
+
+`OpensetCOCOEval` is the specification. For device `Instances` the per-image half runs on the device instead (include/osr.h
+osr_os_coco_match, which restates the matching rules; csrc/osr_os_coco_eval.hip): `OpensetCOCOEvaluator.process` launches it once per
+batch and keeps detections, ranks and flags there; `evaluate` fetches them in one copy and `accumulate_from_flags` fills eval_kdt /
+eval_unkdt through the same `_fill_known` / `_fill_unknown` / `_pr` as `accumulate()`, so both paths return equal figures.
 """
 from __future__ import annotations
 
 import copy
 import json
+import logging
 import os
 from collections import defaultdict
 from typing import Dict, List, Optional, Sequence
@@ -28,6 +34,8 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 
 from . import parallel
+
+logger = logging.getLogger(__name__)
 
 UNKNOWN_CAT = 1000
 
@@ -175,24 +183,62 @@ class OpensetCOCOEval:
         R = len(self.rec_thrs)
         nd = len(tp)
         rc = tp / npig
-        pr = (tp / (fp + tp + np.spacing(1))).tolist()
-        q, ss = [0.0] * R, [0.0] * R
-        for i in range(nd - 1, 0, -1):
-            if pr[i] > pr[i - 1]:
-                pr[i - 1] = pr[i]
+        pr = tp / (fp + tp + np.spacing(1))
+        pr = np.maximum.accumulate(pr[::-1])[::-1]  # the envelope: the running maximum from the right
+        q, ss = np.zeros(R), np.zeros(R)
         inds = np.searchsorted(rc, self.rec_thrs, side="left")
-        for ri, pi in enumerate(inds):
-            if pi >= nd:
-                break
-            q[ri] = pr[pi]
-            ss[ri] = scores_sorted[pi]
-        return rc, np.array(q), np.array(ss), inds
+        ok = inds < nd  # (rc does not decrease, so neither does inds: nothing is filled past the first miss)
+        q[ok], ss[ok] = pr[inds[ok]], np.asarray(scores_sorted, dtype=np.float64)[inds[ok]]
+        return rc, q, ss, inds
+
+    def _empty_known(self) -> dict:
+        T, R, K, A, M = len(self.iou_thrs), len(self.rec_thrs), len(self.cat_ids), len(self.area_rng), len(self.max_dets)
+        return dict(precision=-np.ones((T, R, K, A, M)), recall=-np.ones((T, K, A, M)), scores=-np.ones((T, R, K, A, M)), ok_det_as_known=np.zeros((T, K, A, M)),
+                    unk_det_as_known=np.zeros((T, K, A, M)), tp_plus_fp_cs=np.zeros((T, R, K, A, M)), fp_os=np.zeros((T, R, K, A, M)))
+
+    def _empty_unknown(self) -> dict:
+        T, R, A, M = len(self.iou_thrs), len(self.rec_thrs), len(self.area_rng), len(self.max_dets)
+        return dict(precision=-np.ones((T, R, A, M)), recall=-np.ones((T, A, M)), scores=-np.ones((T, R, A, M)), k_det_as_unk=np.zeros((T, A, M)))
+
+    def _fill_known(self, out, k, a, m, scs, m_k, ig_k, m_ok, ig_ok, m_u, ig_u, npig):
+        """One (category, area range, maxDets) of eval_kdt from the (T, N) matched / ignored arrays of its three matchings, the
+        detections already in descending-score order. Shared by accumulate() and accumulate_from_flags()."""
+        tps = np.logical_and(m_k, np.logical_not(ig_k))
+        fps = np.logical_and(np.logical_not(m_k), np.logical_not(ig_k))
+        okfps = np.logical_and(m_ok, np.logical_not(ig_ok))
+        ufps = np.logical_and(m_u, np.logical_not(ig_u))
+        tp_sum, fp_sum = np.cumsum(tps, axis=1).astype(float), np.cumsum(fps, axis=1).astype(float)
+        ufp_sum = np.cumsum(ufps, axis=1).astype(float)
+        for t in range(len(self.iou_thrs)):
+            tp, fp, ufp = tp_sum[t], fp_sum[t], ufp_sum[t]
+            if len(ufp):
+                out["unk_det_as_known"][t, k, a, m] = ufp[-1]
+            out["ok_det_as_known"][t, k, a, m] = float(np.sum(okfps[t]))
+            rc, q, ss, pinds = self._pr(tp, fp, npig, scs)
+            out["recall"][t, k, a, m] = rc[-1] if len(tp) else 0
+            out["precision"][t, :, k, a, m], out["scores"][t, :, k, a, m] = q, ss
+            n = len(tp)
+            if n:
+                pi = np.where(pinds == n, pinds - 1, pinds)
+                out["tp_plus_fp_cs"][t, :, k, a, m] = (tp + fp)[pi]
+                out["fp_os"][t, :, k, a, m] = ufp[pi]
+
+    def _fill_unknown(self, out, a, m, scs, m_k, ig_k, m_u, ig_u, npig):
+        """One (area range, maxDets) of eval_unkdt, as _fill_known."""
+        tps = np.logical_and(m_u, np.logical_not(ig_u))
+        fps = np.logical_and(np.logical_not(m_u), np.logical_not(ig_u))
+        kfps = np.logical_and(m_k, np.logical_not(ig_k))
+        tp_sum, fp_sum, kfp_sum = np.cumsum(tps, axis=1).astype(float), np.cumsum(fps, axis=1).astype(float), np.cumsum(kfps, axis=1).astype(float)
+        for t in range(len(self.iou_thrs)):
+            if kfp_sum.shape[1]:
+                out["k_det_as_unk"][t, a, m] = kfp_sum[t][-1]
+            rc, q, ss, _ = self._pr(tp_sum[t], fp_sum[t], npig, scs)
+            out["recall"][t, a, m] = rc[-1] if len(tp_sum[t]) else 0
+            out["precision"][t, :, a, m], out["scores"][t, :, a, m] = q, ss
 
     def accumulate(self):
-        T, R, K, A, M = len(self.iou_thrs), len(self.rec_thrs), len(self.cat_ids), len(self.area_rng), len(self.max_dets)
-        precision, recall, scores = -np.ones((T, R, K, A, M)), -np.ones((T, K, A, M)), -np.ones((T, R, K, A, M))
-        ok_as_k, unk_as_k = np.zeros((T, K, A, M)), np.zeros((T, K, A, M))
-        fp_os, tp_plus_fp_cs = np.zeros((T, R, K, A, M)), np.zeros((T, R, K, A, M))
+        K, A = len(self.cat_ids), len(self.area_rng)
+        known, unknown = self._empty_known(), self._empty_unknown()
         I = len(self.img_ids)
         for k in range(K):
             for a in range(A):
@@ -206,31 +252,8 @@ class OpensetCOCOEval:
                     npig = int(np.count_nonzero(np.concatenate([e["gt_ig"] for e in E]) == 0))
                     if npig == 0:
                         continue
-                    tps = np.logical_and(m_k, np.logical_not(ig_k))
-                    fps = np.logical_and(np.logical_not(m_k), np.logical_not(ig_k))
-                    okfps = np.logical_and(m_ok, np.logical_not(ig_ok))
-                    ufps = np.logical_and(m_u, np.logical_not(ig_u))
-                    tp_sum, fp_sum = np.cumsum(tps, axis=1).astype(float), np.cumsum(fps, axis=1).astype(float)
-                    ufp_sum = np.cumsum(ufps, axis=1).astype(float)
-                    for t in range(T):
-                        tp, fp, ufp = tp_sum[t], fp_sum[t], ufp_sum[t]
-                        if len(ufp):
-                            unk_as_k[t, k, a, m] = ufp[-1]
-                        ok_as_k[t, k, a, m] = float(np.sum(okfps[t]))
-                        rc, q, ss, pinds = self._pr(tp, fp, npig, scs)
-                        recall[t, k, a, m] = rc[-1] if len(tp) else 0
-                        precision[t, :, k, a, m], scores[t, :, k, a, m] = q, ss
-                        n = len(tp)
-                        if n:
-                            tp_fp = tp + fp
-                            for ri, pi in enumerate(pinds):
-                                pi = pi - 1 if pi == n else pi
-                                tp_plus_fp_cs[t, ri, k, a, m] = tp_fp[pi]
-                                fp_os[t, ri, k, a, m] = ufp[pi]
-        self.eval_kdt = dict(precision=precision, recall=recall, scores=scores, ok_det_as_known=ok_as_k, unk_det_as_known=unk_as_k,
-                             tp_plus_fp_cs=tp_plus_fp_cs, fp_os=fp_os)
-        precision, recall, scores = -np.ones((T, R, A, M)), -np.ones((T, A, M)), -np.ones((T, R, A, M))
-        k_as_unk = np.zeros((T, A, M))
+                    self._fill_known(known, k, a, m, scs, m_k, ig_k, m_ok, ig_ok, m_u, ig_u, npig)
+        self.eval_kdt = known
         for a in range(A):
             E = [e for e in self.eval_imgs_unkdt[a * I:(a + 1) * I] if e is not None]
             if not E:
@@ -244,17 +267,42 @@ class OpensetCOCOEval:
                 npig = int(np.count_nonzero(np.concatenate([e["gt_ig"] for e in E]) == 0))
                 if npig == 0:
                     continue
-                tps = np.logical_and(m_u, np.logical_not(ig_u))
-                fps = np.logical_and(np.logical_not(m_u), np.logical_not(ig_u))
-                kfps = np.logical_and(m_k, np.logical_not(ig_k))
-                tp_sum, fp_sum, kfp_sum = np.cumsum(tps, axis=1).astype(float), np.cumsum(fps, axis=1).astype(float), np.cumsum(kfps, axis=1).astype(float)
-                for t in range(T):
-                    if kfp_sum.shape[1]:
-                        k_as_unk[t, a, m] = kfp_sum[t][-1]
-                    rc, q, ss, _ = self._pr(tp_sum[t], fp_sum[t], npig, scs)
-                    recall[t, a, m] = rc[-1] if len(tp_sum[t]) else 0
-                    precision[t, :, a, m], scores[t, :, a, m] = q, ss
-        self.eval_unkdt = dict(precision=precision, recall=recall, scores=scores, k_det_as_unk=k_as_unk)
+                self._fill_unknown(unknown, a, m, scs, m_k, ig_k, m_u, ig_u, npig)
+        self.eval_unkdt = unknown
+
+    def accumulate_from_flags(self, image: np.ndarray, slot: np.ndarray, rank: np.ndarray, score: np.ndarray, flags: np.ndarray, npig: np.ndarray):
+        """accumulate() from osr_os_coco_match's outputs instead of evaluate()'s per-image results. One entry per detection row:
+        image = the row's image as an index into self.img_ids (-1: not among them), slot = 0 .. K - 1 known / K unknown / -1, rank
+        and flags (N, A, 3) uint32 as the kernel writes them, score fp32 or fp64; npig (K + 1, A) = the ground truths that are not
+        ignored, per slot and area range, over ALL of self.img_ids (processed or not). The lists are put together as accumulate()
+        does: images in sorted id order, each image's list in rank order, then a mergesort by descending score."""
+        T, K, A = len(self.iou_thrs), len(self.cat_ids), len(self.area_rng)
+        score = np.asarray(score).astype(np.float64)
+        flags = np.asarray(flags).view(np.uint32).reshape(len(score), A, 3)
+        listed = (rank >= 0) & (image >= 0)
+        shifts = np.arange(T, dtype=np.uint32)[:, None]
+
+        def bits(sub, a, s):
+            w = flags[sub, a, s][None, :]
+            return ((w >> shifts) & 1).astype(bool), ((w >> (shifts + 16)) & 1).astype(bool)
+
+        known, unknown = self._empty_known(), self._empty_unknown()
+        for k in range(K + 1):
+            sel = np.nonzero(listed & (slot == k))[0]
+            sel = sel[np.lexsort((rank[sel], image[sel]))]
+            for m, max_det in enumerate(self.max_dets):
+                sub = sel[rank[sel] < max_det]
+                sub = sub[np.argsort(-score[sub], kind="mergesort")]
+                for a in range(A):
+                    if npig[k, a] == 0:
+                        continue
+                    (m0, i0), (m1, i1) = bits(sub, a, 0), bits(sub, a, 1)
+                    if k < K:
+                        m2, i2 = bits(sub, a, 2)
+                        self._fill_known(known, k, a, m, score[sub], m0, i0, m1, i1, m2, i2, int(npig[k, a]))
+                    else:
+                        self._fill_unknown(unknown, a, m, score[sub], m1, i1, m0, i0, int(npig[k, a]))
+        self.eval_kdt, self.eval_unkdt = known, unknown
 
     # ---- summary ------------------------------------------------------------------------------------------
     def summarize(self) -> np.ndarray:
@@ -319,9 +367,122 @@ def instances_to_coco_json(instances, img_id, reverse_id_map: Optional[Dict[int,
     return out
 
 
+def records_from_arrays(image_ids: Sequence, boxes: np.ndarray, scores: np.ndarray, classes: np.ndarray, reverse_id_map: Optional[Dict[int, int]]) -> List[dict]:
+    """instances_to_coco_json on rows fetched from the device: boxes (N, 4) fp32 xyxy widened to fp64 before the differences, the
+    records equal to what the host path builds from the same Instances."""
+    b = np.asarray(boxes, dtype=np.float32).reshape(-1, 4).astype(np.float64)
+    xywh = np.stack([b[:, 0], b[:, 1], b[:, 2] - b[:, 0], b[:, 3] - b[:, 1]], axis=1).tolist()
+    scores, classes = np.asarray(scores, dtype=np.float32).tolist(), np.asarray(classes).tolist()
+    out = []
+    for img, bb, s, c in zip(image_ids, xywh, scores, classes):
+        c = int(c)
+        if reverse_id_map is not None and c != UNKNOWN_CAT:
+            c = reverse_id_map[c]
+        out.append(dict(image_id=img, category_id=c, bbox=bb, score=float(s)))
+    return out
+
+
+class OpensetGroundTruthTables:
+    """The JSON's annotations as flat arrays sorted by (image, slot, annotation order): what osr_os_coco_match reads (include/osr.h).
+    slot: the category's position among the sorted known ids, K for every other category (the unknown class); pos: the
+    annotation's position in the JSON's order within its image."""
+
+    def __init__(self, gt: dict, known_ids: Sequence[int]):
+        self.known_ids = sorted(int(c) for c in known_ids)
+        K = self.num_known = len(self.known_ids)
+        slot_of = {c: k for k, c in enumerate(self.known_ids)}
+        anns = gt["annotations"]
+        self.img_ids = sorted({im["id"] for im in gt["images"]} | {a["image_id"] for a in anns})
+        self.img_pos = {v: i for i, v in enumerate(self.img_ids)}
+        I, N = len(self.img_ids), len(anns)
+        img = np.array([self.img_pos[a["image_id"]] for a in anns], dtype=np.int64)
+        slot = np.array([slot_of.get(a["category_id"], K) for a in anns], dtype=np.int64)
+        by_img = np.argsort(img, kind="mergesort")
+        first = np.searchsorted(img[by_img], np.arange(I + 1), side="left")
+        pos = np.zeros(N, dtype=np.int64)
+        pos[by_img] = np.arange(N) - first[img[by_img]]
+        order = np.lexsort((pos, slot, img))
+        self.img, self.slot, self.pos = img[order], slot[order].astype(np.int32), pos[order].astype(np.int32)
+        self.box = np.array([anns[i]["bbox"] for i in order], dtype=np.float64).reshape(-1, 4)
+        self.area = np.array([anns[i]["area"] if "area" in anns[i] else anns[i]["bbox"][2] * anns[i]["bbox"][3] for i in order], dtype=np.float64)
+        self.crowd = np.array([int(anns[i].get("iscrowd", 0)) for i in order], dtype=np.uint8)
+        self.start = first  # an image's annotations: start[i] .. start[i + 1]
+        self.ids_nonzero = all(a.get("id", 0) != 0 for a in anns)  # the numpy class reads "matched" as "matched id != 0"
+
+    def batch(self, image_ids: Sequence):
+        """-> (rows: indices into the flat arrays, image by image; img_off (n + 1) int32; the largest image)."""
+        rows, per_image = [], []
+        for img in image_ids:
+            p = self.img_pos.get(img)
+            r = np.arange(self.start[p], self.start[p + 1]) if p is not None else np.zeros(0, dtype=np.int64)
+            rows.append(r)
+            per_image.append(len(r))
+        rows = np.concatenate(rows) if rows else np.zeros(0, dtype=np.int64)
+        return rows, np.concatenate(([0], np.cumsum(per_image))).astype(np.int32), max(per_image, default=0)
+
+    def npig(self, area_rng, img_ids: Sequence) -> np.ndarray:
+        """(K + 1, A): the ground truths that are not ignored, per slot, over the given images."""
+        chosen = np.zeros(len(self.img_ids), dtype=bool)
+        chosen[[self.img_pos[i] for i in img_ids if i in self.img_pos]] = True
+        keep = chosen[self.img] & (self.crowd == 0)
+        out = np.zeros((self.num_known + 1, len(area_rng)), dtype=np.int64)
+        for a, (lo, hi) in enumerate(area_rng):
+            out[:, a] = np.bincount(self.slot[keep & ~((self.area < lo) | (self.area > hi))], minlength=self.num_known + 1)
+        return out
+
+    def class_slots(self, reverse_id_map: Optional[Dict[int, int]]) -> Optional[np.ndarray]:
+        """class value -> slot (include/osr.h: class_slot), or None when the values do not fit a table."""
+        K = self.num_known
+        slot_of = {c: k for k, c in enumerate(self.known_ids)}
+        values = {int(c): slot_of[d] for c, d in reverse_id_map.items() if d in slot_of} if reverse_id_map is not None else dict(slot_of)
+        if any(v < 0 for v in values) or max(values, default=0) >= 1 << 20:
+            return None
+        table = -np.ones(max(max(values, default=0), UNKNOWN_CAT) + 1, dtype=np.int32)
+        for v, k in values.items():
+            table[v] = k
+        table[UNKNOWN_CAT] = K  # (1000 is the unknown class before anything else, as in instances_to_coco_json)
+        return table
+
+
+def _align8(n: int) -> int:
+    return (n + 7) // 8 * 8
+
+
+class _Detections:
+    """Every rank's detections in processing order: ("host", records) and ("device", the arrays of one fetched chunk)."""
+
+    def __init__(self, segments: List[tuple], host_reason: Optional[str]):
+        self.segments, self.host_reason = segments, host_reason
+
+    def __len__(self) -> int:
+        return sum(len(seg) if kind == "host" else len(seg["scores"]) for kind, seg in self.segments)
+
+    def has_device(self) -> bool:
+        return any(kind == "device" for kind, _ in self.segments)
+
+    def device_only(self) -> bool:
+        """Whether the kernel's flags cover everything: device chunks only, each image in one of them, once."""
+        ids = [i for kind, seg in self.segments if kind == "device" for i in seg["image_ids"]]
+        return self.has_device() and self.host_reason is None and all(kind == "device" for kind, _ in self.segments) and len(set(ids)) == len(ids)
+
+    def records(self, reverse_id_map) -> List[dict]:
+        out: List[dict] = []
+        for kind, seg in self.segments:
+            out += seg if kind == "host" else records_from_arrays([seg["image_ids"][i] for i in seg["image"]], seg["boxes"], seg["scores"], seg["classes"],
+                                                                  reverse_id_map)
+        return out
+
+
 class OpensetCOCOEvaluator:
     """DatasetEvaluator-shaped wrapper (os_coco_evaluation.py:31-300): reset / process / evaluate on a COCO-format ground-truth
-    json; known_names select the known categories, everything else is "unknown"."""
+    json; known_names select the known categories, everything else is "unknown".
+
+    Device `Instances` (fp32 boxes and scores) are matched on the device: `process` pads the batch into the engines' list form,
+    uploads the batch's ground-truth table in ONE buffer and calls ops.os_coco_match once; detections, ranks and flags stay in device
+    buffers. `evaluate` fetches them in ONE copy, gathers on rank 0 and accumulates from the flags (OpensetCOCOEval.
+    accumulate_from_flags, which shares its arithmetic with accumulate()). CPU `Instances`, `resume=True`, a batch beyond a kernel
+    limit and a JSON with a zero or missing annotation id go through the numpy OpensetCOCOEval on the (rebuilt) records, as does a
+    run that mixes the two kinds of input."""
 
     def __init__(self, gt_json, known_names: Sequence[str], contiguous_to_dataset_id: Optional[Dict[int, int]] = None,
                  max_dets_per_image: Sequence[int] = (10, 20, 30, 50, 100), output_dir: Optional[str] = None):
@@ -337,10 +498,15 @@ class OpensetCOCOEvaluator:
         from .coco_evaluation import _GroundTruthTables  # (that module imports this one)
         from .proposal_evaluation import ProposalRecall
         self.proposals = ProposalRecall(_GroundTruthTables(gt_json))
+        self._tables: Optional[OpensetGroundTruthTables] = None  # built with the first device batch
+        self._class_slot = None                                   # (host table or None, its device copy or None)
         self.reset()
 
     def reset(self):
-        self._predictions: List[dict] = []
+        self._predictions: List[dict] = []   # the host path's records
+        self._chunks: List[dict] = []        # per device batch: tensors that stay on the device
+        self._segments: List[tuple] = []     # processing order: ("host", first record, last + 1) / ("device", chunk index)
+        self._host_reason: Optional[str] = None
         self._saw_instances = False
         self.proposals.reset()
 
@@ -351,8 +517,97 @@ class OpensetCOCOEvaluator:
             if "instances" not in outputs[0]:
                 return
         self._saw_instances = self._saw_instances or len(outputs) > 0
-        for inp, out in zip(inputs, outputs):
-            self._predictions += instances_to_coco_json(out["instances"], inp["image_id"], self.reverse_id_map)
+        insts = [out["instances"] for out in outputs]
+        if insts and insts[0].pred_boxes.tensor.is_cuda:
+            reason = self._process_device([inp["image_id"] for inp in inputs], insts)
+            if reason is None:
+                return
+            if self._host_reason is None:  # one line, not one per batch
+                logger.warning("OpensetCOCOEvaluator: device predictions take the host path and the numpy OpensetCOCOEval scores everything (%s)", reason)
+                self._host_reason = reason
+        first = len(self._predictions)
+        for inp, inst in zip(inputs, insts):
+            self._predictions += instances_to_coco_json(inst, inp["image_id"], self.reverse_id_map)
+        self._segments.append(("host", first, len(self._predictions)))
+
+    def _process_device(self, image_ids, insts) -> Optional[str]:
+        """The batch through ops.os_coco_match; -> None, or why this batch has to take the host path instead."""
+        import torch
+        from . import ops
+        L = ops._lib
+        if self._tables is None:
+            self._tables = OpensetGroundTruthTables(self.gt, self.known_ids)
+            table = self._tables.class_slots(self.reverse_id_map)
+            self._class_slot = (table, None)
+        tb = self._tables
+        if not tb.ids_nonzero:
+            return "an annotation without a non-zero id (the numpy class reads a match as a non-zero ground-truth id)"
+        if self._class_slot[0] is None:
+            return "class values that fit no slot table"
+        max_det = sorted(self.max_dets)[-1]
+        lens = [len(i) for i in insts]
+        cap = max(max(lens), 1)
+        if cap > L.OS_COCO_MAX_CAP or max_det > L.OS_COCO_MAX_DET:
+            return f"{cap} detections in one image / maxDets {max_det}: osr_os_coco_match takes at most {L.OS_COCO_MAX_CAP} / {L.OS_COCO_MAX_DET}"
+        if any(i.pred_boxes.tensor.dtype != torch.float32 or i.scores.dtype != torch.float32 for i in insts):
+            return "boxes or scores that are not float32"
+        rows, img_off, max_img = tb.batch(image_ids)
+        if max_img > L.OS_COCO_MAX_GT:
+            return f"{max_img} ground truths in one image: osr_os_coco_match takes at most {L.OS_COCO_MAX_GT}"
+        dev = insts[0].pred_boxes.tensor.device
+        if self._class_slot[1] is None or self._class_slot[1].device != dev:
+            self._class_slot = (self._class_slot[0], torch.from_numpy(self._class_slot[0]).to(dev))
+        n = len(insts)
+        boxes = torch.zeros((n, cap, 4), dtype=torch.float32, device=dev)
+        scores = torch.zeros((n, cap), dtype=torch.float32, device=dev)
+        classes = torch.full((n, cap), -1, dtype=torch.int64, device=dev)
+        for i, inst in enumerate(insts):
+            m = lens[i]
+            if m:
+                boxes[i, :m], scores[i, :m], classes[i, :m] = inst.pred_boxes.tensor.detach(), inst.scores.detach(), inst.pred_classes.detach().to(torch.int64)
+        # the batch's table, one buffer, one copy: float64 sections first, then int32, then bytes
+        ng = len(rows)
+        parts = [np.ascontiguousarray(a, dtype=np.float64).view(np.uint8) for a in (tb.box[rows].reshape(-1), tb.area[rows])] + \
+                [np.ascontiguousarray(a, dtype=np.int32).view(np.uint8) for a in (img_off, np.asarray(lens), tb.slot[rows], tb.pos[rows])] + [tb.crowd[rows]]
+        sizes = [p.size for p in parts]
+        buf = np.zeros(sum(_align8(s) for s in sizes), dtype=np.uint8)
+        offs, o = [], 0
+        for p, s in zip(parts, sizes):
+            buf[o:o + s] = p
+            offs.append(o)
+            o += _align8(s)
+        dbuf = torch.from_numpy(buf).to(dev, non_blocking=True)
+        view = lambda j, dt: dbuf[offs[j]:offs[j] + sizes[j]].view(dt)  # noqa: E731
+        area_rng = [[0 ** 2, 1e5 ** 2], [0 ** 2, 32 ** 2], [32 ** 2, 96 ** 2], [96 ** 2, 1e5 ** 2]]  # OpensetCOCOEval's, like its thresholds
+        iou_thrs = np.linspace(.5, 0.95, int(np.round((0.95 - .5) / .05)) + 1, endpoint=True)
+        d_counts = view(3, torch.int32)
+        flags, rank, _ = ops.os_coco_match(boxes, scores, classes, d_counts, self._class_slot[1], tb.num_known, view(2, torch.int32),
+                                           view(0, torch.float64).view(ng, 4), view(1, torch.float64), view(4, torch.int32), view(5, torch.int32),
+                                           view(6, torch.uint8), max_img, iou_thrs, area_rng, max_det)
+        self._chunks.append(dict(n=n, cap=cap, image_ids=list(image_ids), boxes=boxes, scores=scores, classes=classes, counts=d_counts, flags=flags, rank=rank))
+        self._segments.append(("device", len(self._chunks) - 1))
+        return None
+
+    def _fetch(self) -> List[dict]:
+        """Every device buffer in ONE copy -> per chunk the flat host arrays over the rows that exist."""
+        import torch
+        if not self._chunks:
+            return []
+        fields = (("boxes", np.float32), ("scores", np.float32), ("classes", np.int64), ("counts", np.int32), ("flags", np.uint32), ("rank", np.int32))
+        host = torch.cat([c[f].reshape(-1).view(torch.uint8) for c in self._chunks for f, _ in fields]).cpu().numpy()  # the one copy
+        out, o = [], 0
+        for c in self._chunks:
+            n, cap = c["n"], c["cap"]
+            got = {}
+            for f, dt in fields:
+                nbytes = c[f].numel() * c[f].element_size()
+                got[f] = host[o:o + nbytes].view(dt)
+                o += nbytes
+            exists = (np.arange(cap)[None, :] < got["counts"][:, None]).reshape(-1)
+            out.append(dict(image_ids=c["image_ids"], image=np.repeat(np.arange(n), cap)[exists], boxes=got["boxes"].reshape(-1, 4)[exists],
+                            scores=got["scores"][exists], classes=got["classes"][exists], rank=got["rank"][exists],
+                            flags=got["flags"].reshape(n * cap, -1)[exists]))
+        return out
 
     RESULTS_FILE = "coco_instances_results.json"
 
@@ -370,10 +625,13 @@ class OpensetCOCOEvaluator:
                 dets = json.load(f)
         else:
             keep = self.output_dir is not None
-            gathered = parallel.gather_to_rank0({"dets": self._predictions, "instances": self._saw_instances, "proposals": self.proposals.state(keep=keep)})
+            fetched = self._fetch()
+            segments = [("host", self._predictions[s[1]:s[2]]) if s[0] == "host" else ("device", fetched[s[1]]) for s in self._segments]
+            gathered = parallel.gather_to_rank0({"segments": segments, "host_reason": self._host_reason, "instances": self._saw_instances,
+                                                 "proposals": self.proposals.state(keep=keep)})
             if gathered is None:
                 return None
-            dets = [d for part in gathered for d in part["dets"]]
+            dets = _Detections([s for part in gathered for s in part["segments"]], next((part["host_reason"] for part in gathered if part["host_reason"]), None))
             states = [part["proposals"] for part in gathered]
             box_proposals = self.proposals.results(states)
             if box_proposals is not None:
@@ -386,16 +644,53 @@ class OpensetCOCOEvaluator:
             return self._score(dets, img_ids, write=True)
         return self._score(dets, img_ids, write=False)
 
+    def _get_tables(self) -> OpensetGroundTruthTables:
+        if self._tables is None:
+            self._tables = OpensetGroundTruthTables(self.gt, self.known_ids)
+            self._class_slot = (self._tables.class_slots(self.reverse_id_map), None)
+        return self._tables
+
+    def _accumulate_device(self, dets: "_Detections", img_ids) -> OpensetCOCOEval:
+        """The figures from the kernel's flags: no per-image matching on the host."""
+        ev = OpensetCOCOEval(dict(images=self.gt["images"], annotations=[]), [], self.known_ids, self.max_dets, img_ids)
+        tb, parts = self._get_tables(), [seg for _, seg in dets.segments]
+        table = self._class_slot[0]
+        index = {img: i for i, img in enumerate(ev.img_ids)}
+        image = np.concatenate([np.array([index.get(i, -1) for i in q["image_ids"]], dtype=np.int64)[q["image"]] for q in parts])
+        classes = np.concatenate([q["classes"] for q in parts])
+        inside = (classes >= 0) & (classes < len(table))
+        slot = np.where(inside, table[np.where(inside, classes, 0)], -1)
+        if self.reverse_id_map is not None:
+            bad = classes[(classes != UNKNOWN_CAT) & ~np.isin(classes, np.array(list(self.reverse_id_map), dtype=np.int64))]
+            if bad.size:
+                raise KeyError(int(bad[0]))  # (what instances_to_coco_json raises for a class outside the map)
+        ev.accumulate_from_flags(image, slot, np.concatenate([q["rank"] for q in parts]), np.concatenate([q["scores"] for q in parts]),
+                                 np.concatenate([q["flags"] for q in parts]), tb.npig(ev.area_rng, ev.img_ids))
+        return ev
+
     def _score(self, dets, img_ids, write: bool):
+        """dets: the records (a list, `resume`) or the gathered segments (_Detections)."""
+        device = isinstance(dets, _Detections) and dets.device_only()
+        if isinstance(dets, _Detections):
+            if not device and dets.has_device() and dets.host_reason is None:  # (a host_reason was logged when it arose)
+                logger.warning("OpensetCOCOEvaluator: the whole evaluation goes through the numpy OpensetCOCOEval (CPU and device predictions are mixed, or "
+                               "an image was processed twice)")
+            records = dets.records(self.reverse_id_map) if not device or (write and self.output_dir) else None
+            count = len(dets)
+        else:
+            records, count = dets, len(dets)
         if write and self.output_dir:
             os.makedirs(self.output_dir, exist_ok=True)
             with open(os.path.join(self.output_dir, self.RESULTS_FILE), "w") as f:
-                json.dump(dets, f)
-        if not dets:
+                json.dump(records, f)
+        if not count:
             return {"bbox": {m: float("nan") for m in METRICS}}
-        ev = OpensetCOCOEval(copy.deepcopy(self.gt), dets, self.known_ids, self.max_dets, img_ids)
-        ev.evaluate()
-        ev.accumulate()
+        if device:
+            ev = self._accumulate_device(dets, img_ids)
+        else:
+            ev = OpensetCOCOEval(copy.deepcopy(self.gt), records, self.known_ids, self.max_dets, img_ids)
+            ev.evaluate()
+            ev.accumulate()
         if self.output_dir:
             for tag, e in (("known", ev.eval_kdt), ("unknown", ev.eval_unkdt)):
                 np.save(os.path.join(self.output_dir, f"{tag}_precision_bbox.npy"), e["precision"])
