@@ -1084,6 +1084,59 @@ osr_status osr_os_coco_match(const float* boxes, const float* scores, const int6
                              void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * Open-set PASCAL-VOC matching (AP@K, AP@U, wilderness impact, A-OSE): the per-detection half of voc_eval for every class,
+ * csrc/osr_voc_eval.hip. The rules below restate host/evaluation.py (PascalVOCDetectionEvaluator.process and voc_eval, themselves a
+ * restatement of the reference's pascal_voc_evaluation.py:53-70 and :264-379), and THIS TEXT is the contract; voc_match_reference
+ * states the same rules as a literal numpy loop and the tests hold the two against each other bit for bit.
+ *
+ * osr_voc_match: ONE launch scores the n images of a batch against their ground truth for every class. No host sync, no atomics
+ * across workgroups, capturable, repeats are bit-identical. Every argument is validated before anything is launched (no GPU needed
+ * for a refusal); n == 0 or cap == 0 is OSR_OK without a launch (and nothing is written).
+ *
+ * Detections, the engines' padded lists (need not be sorted): boxes (n, cap, 4) fp32 xyxy, scores (n, cap) fp32, classes (n, cap)
+ * int64, counts (n) int32 (clamped to 0 .. cap), image_index (n) int32: the row's image in the ground-truth table.
+ * Ground truth, built ONCE by the host for the whole dataset: gt_img_off (num_images + 1) int32, image m owns entries
+ * gt_img_off[m] .. gt_img_off[m + 1] in annotation order; gt_box (NG, 4) fp64, the XML's integers (finite); gt_cls (NG) int32, an
+ * index into the evaluator's class names: a known index, or C - 1 for "unknown" exactly as parse_voc_xml renames (any other value
+ * belongs to no class); gt_difficult (NG) uint8, non-zero = difficult. max_gt_per_image: the largest image, which the host knows
+ * since it built the table (a longer one is cut there). ovthresh: a double, used as given. C = the number of class names.
+ *
+ * Per detection row r of batch row i:
+ *   - the row is VALID when r < counts[i], 0 <= class < C and 0 <= image_index[i] < num_images;
+ *   - record geometry, what the evaluator's text record holds: x0' = fp32(x0 + 1.0f) and y0' likewise IN FP32 (the evaluator adds a
+ *     Python int to an np.float32); each of x0', y0', x1, y1 then becomes t = rint((double)v * 10.0) and the record's value t / 10.0;
+ *     the score becomes k = rint((double)s * 1000.0) and conf = k / 1000.0. This IS the "{:.1f}" / "{:.3f}" text round trip: the
+ *     products are exact in fp64 for any fp32 input, rint is half-even like the formatting, and the division is correctly rounded
+ *     like float("...");
+ *   - a valid row is NON-FINITE when its score or a coordinate is not finite, |s * 1000| >= 2^31 or a |v * 10| >= 2^63 (k and t have
+ *     to fit milli and deci). It gets the valid and the non-finite bit and nothing else (milli 0, deci 0, match -1), belongs to no
+ *     list, and status becomes 1; the host then abandons the device result;
+ *   - the list of (image, class c) is its valid finite rows by descending k, equal k going to the lower row first (the stable
+ *     order; the ROUNDED score orders, not the raw one);
+ *   - overlap, fp64 with the inclusive + 1 convention exactly as _overlaps: iw = max(min(gx1, bx1) - max(gx0, bx0) + 1, 0), ih
+ *     likewise, inter = iw * ih, union = (bx1 - bx0 + 1) * (by1 - by0 + 1) + (gx1 - gx0 + 1) * (gy1 - gy0 + 1) - inter, ov = inter /
+ *     union, with b the record's values. A union of zero gives a NaN or an infinite ov, which count as numpy counts them: NaN is the
+ *     maximum of np.argmax and np.max and is not > ovthresh;
+ *   - matching: the detections of a list meet, in list order, the image's ground truths with gt_cls == c in annotation order; jmax
+ *     is the FIRST maximum of ov. If ov[jmax] > ovthresh (strictly): a difficult ground truth gives neither tp nor fp; a ground
+ *     truth no earlier detection of the list has taken gives tp and is taken; a taken one gives fp. Otherwise, and with no ground
+ *     truth of the class, fp;
+ *   - unknown overlap, for every class except C - 1: is_unk is set when the maximum of ov over the image's ground truths with
+ *     gt_cls == C - 1 is > ovthresh, independent of the matching; difficult ones count.
+ *
+ * Outputs (all written in full by the call): flags (n, cap) uint8: bit 0 valid, bit 1 tp, bit 2 fp, bit 3 is_unk, bit 4 non-finite;
+ * 0 for rows that are not valid. milli (n, cap) int32: k, 0 for rows in no list. match (n, cap) int32 or NULL: jmax as an index into
+ * gt_* where ov[jmax] > ovthresh (tp, fp on a taken one, or difficult), else -1. deci (n, cap, 4) int64 or NULL: the four t, 0 for
+ * rows in no list. status (1) int32: 1 when a non-finite row was met, else 0.
+ *
+ * Limits, OSR_ERR_UNSUPPORTED with nothing launched beyond them: cap <= 1024, max_gt_per_image <= 4096, C >= 1, n * C < 2^31.
+ * --------------------------------------------------------------------------------------------------------- */
+osr_status osr_voc_match(const float* boxes, const float* scores, const int64_t* classes, const int32_t* counts, const int32_t* image_index,
+                         int32_t n, int32_t cap, int32_t num_classes, const int32_t* gt_img_off, int32_t num_images, const double* gt_box,
+                         const int32_t* gt_cls, const uint8_t* gt_difficult, int32_t num_gt, int32_t max_gt_per_image, double ovthresh,
+                         uint8_t* flags, int32_t* milli, int32_t* match, int64_t* deci, int32_t* status, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Class-agnostic box-proposal recall (AR@limit per area range), csrc/osr_proposal_recall.hip: what the reference's evaluator
  * computes per image before it sums, for a batch of images, every area range and every proposal limit in ONE launch.
  * host/proposal_evaluation.py's evaluate_box_proposals states the same rules as a torch-CPU loop and the tests hold the two against

@@ -111,6 +111,7 @@ COCO_BBOX, COCO_KEYPOINTS = 0, 1
 COCO_MAX_CAP, COCO_MAX_DET, COCO_MAX_THRS, COCO_MAX_AREAS, COCO_MAX_KPTS, COCO_MAX_GROUP = 1024, 128, 16, 8, 32, 4096  # csrc/osr_coco_eval.hip CM_MAX_*
 OS_COCO_MAX_CAP, OS_COCO_MAX_DET, OS_COCO_MAX_THRS, OS_COCO_MAX_AREAS, OS_COCO_MAX_GT = 1024, 128, 16, 8, 4096  # csrc/osr_os_coco_eval.hip OM_MAX_*
 OS_COCO_SETS = 3  # flag words per (detection, area range): own slot, other known, unknown
+VOC_MAX_CAP, VOC_MAX_GT = 1024, 4096  # csrc/osr_voc_eval.hip VM_MAX_* (the flag bits: host/evaluation.py VOC_*)
 
 
 PROPOSAL_MAX_CAP, PROPOSAL_MAX_GT, PROPOSAL_MAX_AREAS, PROPOSAL_MAX_LIMITS, PROPOSAL_MAX_THRS = 2048, 1024, 8, 8, 16  # csrc/osr_proposal_recall.hip PR_MAX_*
@@ -194,6 +195,8 @@ PROTOTYPES = {
     # open-set COCO matching (csrc/osr_os_coco_eval.hip)
     "osr_os_coco_match_workspace_bytes": (I64, [I32, I32]),
     "osr_os_coco_match": (I32, [P, P, P, P, I32, I32, P, I32, I32, P, P, P, P, P, P, I32, I32, P, I32, P, I32, I32, P, P, P, P, I64, P]),
+    # open-set VOC matching (csrc/osr_voc_eval.hip)
+    "osr_voc_match": (I32, [P, P, P, P, P, I32, I32, I32, P, I32, P, P, P, I32, I32, C.c_double, P, P, P, P, P, P]),
     # box-proposal recall (csrc/osr_proposal_recall.hip)
     "osr_proposal_recall": (I32, [P, P, P, I32, I32, P, P, P, I32, I32, P, I32, P, I32, P, I32, P, P, P, P]),
     "osr_fastrcnn_candidates": (I32, [P, P, I32, I32, P, P, I32, I32, P, P, F32, P, P, P, P, P, P]),

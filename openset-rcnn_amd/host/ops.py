@@ -1862,6 +1862,39 @@ def os_coco_match(boxes: torch.Tensor, scores: torch.Tensor, classes: torch.Tens
     return flags, rank, match
 
 
+# ---- open-set VOC matching (csrc/osr_voc_eval.hip; host/evaluation.py) ------------------------------------------------------------------
+def voc_match(boxes: torch.Tensor, scores: torch.Tensor, classes: torch.Tensor, counts: torch.Tensor, image_index: torch.Tensor, num_classes: int,
+              gt_img_off: torch.Tensor, gt_box: torch.Tensor, gt_cls: torch.Tensor, gt_difficult: torch.Tensor, max_gt_per_image: int,
+              ovthresh: float = 0.5, want_match: bool = False, want_deci: bool = False):
+    """A batch of images scored against the dataset's VOC ground truth for every class in one launch (include/osr.h osr_voc_match,
+    which states every rule). boxes (n, cap, 4) fp32 xyxy, scores (n, cap) fp32, classes (n, cap) int64, counts (n) / image_index (n)
+    int32; gt_img_off (num_images + 1) int32, gt_box (NG, 4) float64, gt_cls (NG) int32, gt_difficult (NG) uint8.
+    -> (flags (n, cap) uint8, milli (n, cap) int32, match (n, cap) int32 or None, deci (n, cap, 4) int64 or None, status (1) int32)."""
+    lib = _lib.load()
+    _need(boxes, torch.float32, "boxes"); _need(scores, torch.float32, "scores"); _need(classes, torch.int64, "classes"); _need(counts, torch.int32, "counts")
+    _need(image_index, torch.int32, "image_index"); _need(gt_img_off, torch.int32, "gt_img_off"); _need(gt_box, torch.float64, "gt_box")
+    _need(gt_cls, torch.int32, "gt_cls"); _need(gt_difficult, torch.uint8, "gt_difficult")
+    if boxes.dim() != 3 or boxes.shape[2] != 4:
+        raise OsrError(f"voc_match: boxes {tuple(boxes.shape)} must be (n, cap, 4)")
+    n, cap = int(boxes.shape[0]), int(boxes.shape[1])
+    ng, num_images = int(gt_cls.numel()), int(gt_img_off.numel()) - 1
+    if tuple(scores.shape) != (n, cap) or tuple(classes.shape) != (n, cap) or counts.numel() != n or image_index.numel() != n or num_images < 0 or \
+            tuple(gt_box.shape) != (ng, 4) or gt_difficult.numel() != ng:
+        raise OsrError(f"voc_match: scores {tuple(scores.shape)} / classes {tuple(classes.shape)} must be {(n, cap)}, counts / image_index ({n}), "
+                       f"gt_img_off at least one entry, gt_box {tuple(gt_box.shape)} ({ng}, 4), gt_difficult ({ng})")
+    dev = boxes.device
+    launched = n > 0 and cap > 0  # (else the call writes nothing)
+    flags = torch.empty((n, cap), dtype=torch.uint8, device=dev)
+    milli = torch.empty((n, cap), dtype=torch.int32, device=dev)
+    match = torch.empty((n, cap), dtype=torch.int32, device=dev) if want_match else None
+    deci = torch.empty((n, cap, 4), dtype=torch.int64, device=dev) if want_deci else None
+    status = torch.empty((1,), dtype=torch.int32, device=dev) if launched else torch.zeros((1,), dtype=torch.int32, device=dev)
+    check(lib.osr_voc_match(_p(boxes), _p(scores), _p(classes), _p(counts), _p(image_index), n, cap, int(num_classes), _p(gt_img_off), num_images,
+                            _p(gt_box) if ng else None, _p(gt_cls) if ng else None, _p(gt_difficult) if ng else None, ng, int(max_gt_per_image),
+                            float(ovthresh), _p(flags), _p(milli), _p(match), _p(deci), _p(status), _stream()), "osr_voc_match")
+    return flags, milli, match, deci, status
+
+
 # ---- box-proposal recall (csrc/osr_proposal_recall.hip; host/proposal_evaluation.py) -------------------------------------------------
 def proposal_recall(boxes: torch.Tensor, logits: torch.Tensor, counts: torch.Tensor, gt_boxes: torch.Tensor, gt_area: torch.Tensor,
                     seg_off: torch.Tensor, max_gt_per_image: int, area_ranges: torch.Tensor, limits: Sequence[int], thresholds: torch.Tensor,
