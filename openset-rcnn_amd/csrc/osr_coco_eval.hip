@@ -3,33 +3,21 @@
 // the bbox similarities round like numpy's, so the flags equal the numpy specification's bit for bit.
 //
 // The grid is fixed: one workgroup of 1024 threads (16 waves) per (image, category); a group without a detection of its class
-// has nothing to write and leaves after the scan. Inside a group:
-//   A. the rows of the group's class are compacted in row order (a block scan over the <= 1024 rows), and each gets its rank by
-//      counting the members that precede it: higher score key, or the same key and a lower row (mergesort's stable order);
+// has nothing to write and leaves after the scan. Inside a group (osr_eval_match.h holds the shared steps A, D and E):
+//   A. the rows of the group's class are compacted in row order and ranked by score key, stably;
 //   B. per ranked detection its area, per ground truth one uint16 in LDS: bit a = "ignored in area range a", bit 8 = crowd;
 //   C. the M x G similarity matrix, one thread per pair, into the caller's matrix (global memory: 128 x 4096 doubles fit no LDS);
 //   D. the T x A greedy passes are independent, so the waves take them in turn (40 passes for bbox: 16 waves need three turns).
-//      A pass walks its <= 128 detections in rank order; per detection the lanes stride over the ground truths (lane l owns j = l, l + 64, ..: its "matched" bits are ONE 64-bit
-//      register, G <= 4096), keep the best available candidate among the not-ignored and among the ignored ones, and one wave
-//      reduction picks the winner (larger similarity; equal: the higher position, the loop's `<`). The pass leaves two bits per
-//      detection in LDS;
+//      There are no sets and a tie goes to the higher position, the loop's `<`;
 //   E. the bits of the T passes of an area range are packed into the flag words.
 // No atomics anywhere and every address has one writer: repeats are bit-identical. rank, flags and match are preset by memsets on
 // the same stream, so rows outside every list read -1 / 0 / -1.
-#include "osr_common.h"
+#include "osr_eval_match.h"
 
-#define CM_THREADS 1024
-#define CM_WAVES (CM_THREADS / 64)
-#define CM_MAX_CAP 1024
-#define CM_MAX_DET 128
-#define CM_MAX_T 16
-#define CM_MAX_A 8
 #define CM_MAX_KP 32
-#define CM_MAX_G 4096
 
 struct CmParams {
-    double thr[CM_MAX_T];       // min(t, 1 - 1e-10), formed on the host in fp64
-    double rng[CM_MAX_A * 2];
+    EmTables tb;
     int n, cap, K, Kp, T, A, max_det, mcap, task, num_gt, max_group;
 };
 
@@ -64,62 +52,46 @@ __device__ __forceinline__ double cm_oks(const float* __restrict__ dk, const dou
     return sum / (double)(k1 > 0 ? k1 : Kp);
 }
 
-// the larger similarity wins, equal similarities go to the higher position; j < 0: no candidate
-__device__ __forceinline__ void cm_wave_best(double& s, int& j) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) {
-        const double os = __shfl_xor(s, d, 64);
-        const int oj = __shfl_xor(j, d, 64);
-        if (oj >= 0 && (j < 0 || os > s || (os == s && oj > j))) s = os, j = oj;
-    }
-}
-
-__global__ __launch_bounds__(CM_THREADS) void cm_match_kernel(CmParams P, const float* __restrict__ boxes, const float* __restrict__ scores,
+__global__ __launch_bounds__(EM_THREADS) void cm_match_kernel(CmParams P, const float* __restrict__ boxes, const float* __restrict__ scores,
                                                              const int64_t* __restrict__ classes, const int32_t* __restrict__ counts,
                                                              const float* __restrict__ keypoints, const int32_t* __restrict__ gt_seg_off,
                                                              const double* __restrict__ gt_box, const double* __restrict__ gt_area,
                                                              const uint8_t* __restrict__ gt_flags, const double* __restrict__ gt_kpts,
                                                              const double* __restrict__ sigmas, uint32_t* __restrict__ flags, int32_t* __restrict__ rank,
                                                              int32_t* __restrict__ match, double* __restrict__ simm) {
-    __shared__ int c_row[CM_MAX_CAP];
-    __shared__ uint32_t c_key[CM_MAX_CAP];
-    __shared__ int d_row[CM_MAX_DET];
-    __shared__ double d_area[CM_MAX_DET];
-    __shared__ uint16_t g_meta[CM_MAX_G];
-    __shared__ uint8_t res[CM_MAX_T * CM_MAX_A][CM_MAX_DET];
+    __shared__ int c_row[EM_MAX_CAP];
+    __shared__ uint32_t c_key[EM_MAX_CAP];
+    __shared__ int d_row[EM_MAX_DET];
+    __shared__ double d_area[EM_MAX_DET];
+    __shared__ uint16_t g_meta[EM_MAX_G];
+    __shared__ uint8_t res[EM_MAX_T * EM_MAX_A][64];
     __shared__ int scan[17];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int i = blockIdx.x / P.K, c = blockIdx.x % P.K;
     const int cnt = min(max(counts[i], 0), P.cap);
-    int g0 = gt_seg_off[blockIdx.x], G = gt_seg_off[blockIdx.x + 1] - g0;
-    g0 = min(max(g0, 0), P.num_gt);
-    G = min(max(G, 0), min(P.num_gt - g0, P.max_group));
+    const int64_t row0 = (int64_t)i * P.cap;
+    int g0, G;
+    em_segment(gt_seg_off, blockIdx.x, P.num_gt, P.max_group, &g0, &G);
     // A. the class's rows, then their ranks
-    int D = 0;
-    for (int base = 0; base < cnt; base += CM_THREADS) {  // (cnt is uniform: the scans' barriers are too)
-        const int r = base + tid;
-        const bool mine = r < cnt && classes[(int64_t)i * P.cap + r] == (int64_t)c;
-        int total;
-        const int pos = osr_block_excl_scan(mine ? 1 : 0, scan, &total);
-        if (mine) c_row[D + pos] = r, c_key[D + pos] = osr_float_key(scores[(int64_t)i * P.cap + r]);
-        D += total;
-    }
+    const int D = em_compact(cnt, scan, c_row, c_key, [&](int r, uint32_t* key) {
+        if (classes[row0 + r] != (int64_t)c) return false;
+        *key = osr_float_key(scores[row0 + r]);
+        return true;
+    });
     if (D == 0) return;  // nothing to write: no row of this image carries the class (uniform)
     __syncthreads();
     const int M = min(D, P.max_det);
-    for (int m = tid; m < D; m += CM_THREADS) {
-        const uint32_t key = c_key[m];
-        int before = 0;
-        for (int o = 0; o < D; ++o) before += (c_key[o] > key) || (c_key[o] == key && o < m);
+    for (int m = tid; m < D; m += EM_THREADS) {
+        const int before = em_stable_before(c_key, D, m);
         if (before < M) {
             d_row[before] = c_row[m];
-            rank[(int64_t)i * P.cap + c_row[m]] = before;
+            rank[row0 + c_row[m]] = before;
         }
     }
     __syncthreads();
     // B. detection areas, ground-truth marks
-    for (int d = tid; d < M; d += CM_THREADS) {
-        const int64_t row = (int64_t)i * P.cap + d_row[d];
+    for (int d = tid; d < M; d += EM_THREADS) {
+        const int64_t row = row0 + d_row[d];
         if (P.task == OSR_COCO_BBOX) {
             const float* b = boxes + row * 4;
             d_area[d] = (double)(b[2] - b[0]) * (double)(b[3] - b[1]);
@@ -134,18 +106,15 @@ __global__ __launch_bounds__(CM_THREADS) void cm_match_kernel(CmParams P, const 
             d_area[d] = (xb - xa) * (yb - ya);
         }
     }
-    for (int j = tid; j < G; j += CM_THREADS) {
+    for (int j = tid; j < G; j += EM_THREADS) {
         const int f = gt_flags[g0 + j];
-        const double ga = gt_area[g0 + j];
-        int m = (f & 1) << 8;
-        for (int a = 0; a < P.A; ++a) m |= ((f & 2) || ga < P.rng[a * 2] || ga > P.rng[a * 2 + 1]) ? 1 << a : 0;
-        g_meta[j] = (uint16_t)m;
+        g_meta[j] = (uint16_t)((f & 1 ? EM_CROWD : 0) | em_ignored_bits(f & 2, gt_area[g0 + j], P.tb.rng, P.A));
     }
     // C. similarities: row d of the group's M x G block, which starts at g0 * mcap
     double* S = simm + (int64_t)g0 * P.mcap;
-    for (int64_t p = tid; p < (int64_t)M * G; p += CM_THREADS) {
+    for (int64_t p = tid; p < (int64_t)M * G; p += EM_THREADS) {
         const int d = (int)(p / G), j = (int)(p % G);
-        const int64_t row = (int64_t)i * P.cap + d_row[d];
+        const int64_t row = row0 + d_row[d];
         const double v = P.task == OSR_COCO_BBOX ? cm_bbox_sim(boxes + row * 4, gt_box + (int64_t)(g0 + j) * 4, gt_flags[g0 + j] & 1)
                                        : cm_oks(keypoints + row * P.Kp * 3, gt_kpts + (int64_t)(g0 + j) * P.Kp * 3, gt_box + (int64_t)(g0 + j) * 4,
                                                 gt_area[g0 + j], sigmas, P.Kp);
@@ -154,55 +123,17 @@ __global__ __launch_bounds__(CM_THREADS) void cm_match_kernel(CmParams P, const 
     __threadfence_block();
     __syncthreads();
     // D. the passes
-    const int steps = (G + 63) >> 6;
-    for (int pass = wave; pass < P.A * P.T; pass += CM_WAVES) {
+    for (int pass = wave; pass < P.A * P.T; pass += EM_WAVES) {
         const int a = pass / P.T, t = pass % P.T;
-        const double thr = P.thr[t], lo = P.rng[a * 2], hi = P.rng[a * 2 + 1];
-        unsigned long long taken = 0;  // bit q: ground truth q * 64 + lane is matched in this pass
-        for (int d = 0; d < M; ++d) {
-            double sn = 0.0, si = 0.0;
-            int jn = -1, ji = -1;
-            for (int q = 0; q < steps; ++q) {
-                const int j = (q << 6) + lane;
-                if (j >= G) break;
-                const int m = g_meta[j];
-                if (((taken >> q) & 1) && !(m & 0x100)) continue;
-                const double s = S[(int64_t)d * G + j];
-                if (!(s >= thr)) continue;
-                if ((m >> a) & 1) {
-                    if (ji < 0 || s >= si) si = s, ji = j;
-                } else {
-                    if (jn < 0 || s >= sn) sn = s, jn = j;
-                }
-            }
-            cm_wave_best(sn, jn);
-            if (jn < 0) {
-                cm_wave_best(si, ji);
-                jn = ji;
-            }
-            int out;
-            if (jn >= 0) {
-                if ((jn & 63) == lane) taken |= 1ull << (jn >> 6);
-                out = 1 | (((g_meta[jn] >> a) & 1) << 1);
-            } else {
-                out = (d_area[d] < lo || d_area[d] > hi) ? 2 : 0;
-            }
-            if (lane == 0) {
-                res[pass][d] = (uint8_t)out;
-                if (match && jn >= 0) match[(((int64_t)i * P.cap + d_row[d]) * P.A + a) * P.T + t] = g0 + jn;
-            }
-        }
+        res[pass][lane] = (uint8_t)em_greedy_pass<false>(
+            g_meta, G, -1, P.tb.thr[t], a, P.tb.rng[a * 2], P.tb.rng[a * 2 + 1], d_area, d_row, M, [&](int d) { return S + (int64_t)d * G; },
+            [](int j) { return j; }, match ? match + (row0 * P.A + a) * P.T + t : nullptr, (int64_t)P.A * P.T, g0);
     }
     __syncthreads();
     // E. the flag words
-    for (int p = tid; p < M * P.A; p += CM_THREADS) {
+    for (int p = tid; p < M * P.A; p += EM_THREADS) {
         const int d = p / P.A, a = p % P.A;
-        uint32_t w = 0;
-        for (int t = 0; t < P.T; ++t) {
-            const uint32_t b = res[a * P.T + t][d];
-            w |= (b & 1u) << t | ((b >> 1) & 1u) << (16 + t);
-        }
-        flags[((int64_t)i * P.cap + d_row[d]) * P.A + a] = w;
+        flags[(row0 + d_row[d]) * P.A + a] = em_flag_word(res, a * P.T, P.T, d);
     }
 }
 
@@ -222,12 +153,12 @@ extern "C" osr_status osr_coco_match(int32_t task, const float* boxes, const flo
     OSR_REQUIRE(n >= 0 && cap >= 0 && num_categories >= 1 && num_gt >= 0 && max_gt_per_group >= 0 && max_det >= 1 && num_thrs >= 1 && num_areas >= 1,
                 OSR_ERR_INVALID_ARG, "osr_coco_match: n %d, cap %d, categories %d, num_gt %d, max_gt_per_group %d, max_det %d, thresholds %d, area ranges %d", n, cap,
                 num_categories, num_gt, max_gt_per_group, max_det, num_thrs, num_areas);
-    OSR_REQUIRE(cap <= CM_MAX_CAP, OSR_ERR_UNSUPPORTED, "osr_coco_match: cap %d, at most %d rows per image", cap, CM_MAX_CAP);
-    OSR_REQUIRE(max_det <= CM_MAX_DET, OSR_ERR_UNSUPPORTED, "osr_coco_match: max_det %d, at most %d", max_det, CM_MAX_DET);
-    OSR_REQUIRE(num_thrs <= CM_MAX_T, OSR_ERR_UNSUPPORTED, "osr_coco_match: %d thresholds, at most %d", num_thrs, CM_MAX_T);
-    OSR_REQUIRE(num_areas <= CM_MAX_A, OSR_ERR_UNSUPPORTED, "osr_coco_match: %d area ranges, at most %d", num_areas, CM_MAX_A);
-    OSR_REQUIRE(max_gt_per_group <= CM_MAX_G, OSR_ERR_UNSUPPORTED, "osr_coco_match: %d ground truths in one (image, category), at most %d", max_gt_per_group,
-                CM_MAX_G);
+    OSR_REQUIRE(cap <= EM_MAX_CAP, OSR_ERR_UNSUPPORTED, "osr_coco_match: cap %d, at most %d rows per image", cap, EM_MAX_CAP);
+    OSR_REQUIRE(max_det <= EM_MAX_DET, OSR_ERR_UNSUPPORTED, "osr_coco_match: max_det %d, at most %d", max_det, EM_MAX_DET);
+    OSR_REQUIRE(num_thrs <= EM_MAX_T, OSR_ERR_UNSUPPORTED, "osr_coco_match: %d thresholds, at most %d", num_thrs, EM_MAX_T);
+    OSR_REQUIRE(num_areas <= EM_MAX_A, OSR_ERR_UNSUPPORTED, "osr_coco_match: %d area ranges, at most %d", num_areas, EM_MAX_A);
+    OSR_REQUIRE(max_gt_per_group <= EM_MAX_G, OSR_ERR_UNSUPPORTED, "osr_coco_match: %d ground truths in one (image, category), at most %d", max_gt_per_group,
+                EM_MAX_G);
     OSR_REQUIRE(!kp || (num_keypoints >= 1 && num_keypoints <= CM_MAX_KP), kp && num_keypoints > CM_MAX_KP ? OSR_ERR_UNSUPPORTED : OSR_ERR_INVALID_ARG,
                 "osr_coco_match: %d keypoints, 1 .. %d", num_keypoints, CM_MAX_KP);
     OSR_REQUIRE((int64_t)n * num_categories < (1LL << 31) - 1, OSR_ERR_INVALID_ARG, "osr_coco_match: %d images x %d categories", n, num_categories);
@@ -247,18 +178,16 @@ extern "C" osr_status osr_coco_match(int32_t task, const float* boxes, const flo
                     ((uintptr_t)match & 3) == 0 && ((uintptr_t)simm & 7) == 0,
                 OSR_ERR_INVALID_ARG, "osr_coco_match: misaligned pointer");
     CmParams P;
-    for (int t = 0; t < CM_MAX_T; ++t) P.thr[t] = t < num_thrs ? (iou_thrs[t] < 1 - 1e-10 ? iou_thrs[t] : 1 - 1e-10) : 2.0;
-    for (int a = 0; a < CM_MAX_A * 2; ++a) P.rng[a] = a < num_areas * 2 ? area_rng[a] : 0.0;
+    em_fill_tables(&P.tb, iou_thrs, num_thrs, area_rng, num_areas);
     P.n = n, P.cap = cap, P.K = num_categories, P.Kp = kp ? num_keypoints : 0, P.T = num_thrs, P.A = num_areas, P.max_det = max_det;
     P.mcap = cap < max_det ? cap : max_det, P.task = task, P.num_gt = num_gt, P.max_group = max_gt_per_group;
     hipStream_t st = (hipStream_t)stream;
     const int64_t rows = (int64_t)n * cap;
-    if (hipMemsetAsync(flags, 0, (size_t)rows * num_areas * 4, st) != hipSuccess || hipMemsetAsync(rank, 0xff, (size_t)rows * 4, st) != hipSuccess ||
-        (match && hipMemsetAsync(match, 0xff, (size_t)rows * num_areas * num_thrs * 4, st) != hipSuccess)) {
+    if (!em_preset(flags, rows * num_areas, rank, rows, match, rows * num_areas * num_thrs, st)) {
         osr_set_error("osr_coco_match: hipMemsetAsync failed");
         return OSR_ERR_LAUNCH;
     }
-    hipLaunchKernelGGL(cm_match_kernel, dim3(n * num_categories), dim3(CM_THREADS), 0, st, P, boxes, scores, classes, counts, keypoints, gt_seg_off, gt_box,
+    hipLaunchKernelGGL(cm_match_kernel, dim3(n * num_categories), dim3(EM_THREADS), 0, st, P, boxes, scores, classes, counts, keypoints, gt_seg_off, gt_box,
                        gt_area, gt_flags, gt_kpts, sigmas, flags, rank, match, simm);
     OSR_CHECK_LAUNCH("osr_coco_match");
     return OSR_OK;

@@ -7,9 +7,9 @@
 // one of them with its own tie order, and the detection geometry is formed from corners widened to fp64 first.
 //
 // The grid is fixed: one workgroup of 1024 threads (16 waves) per (image, slot), slots 0 .. K with K the unknown one; a group
-// without a detection of its slot has nothing to write and leaves after the scan. Inside a group:
-//   A. the rows of the group's slot are compacted in row order (a block scan over the <= 1024 rows), and each gets its rank by
-//      counting the members that precede it: higher score key, or the same key and a lower row (mergesort's stable order);
+// without a detection of its slot has nothing to write and leaves after the scan. Inside a group (osr_eval_match.h holds the shared
+// steps A, D and E):
+//   A. the rows of the group's slot are compacted in row order and ranked by score key, stably;
 //   B. per ranked detection its area, per ground truth of the IMAGE one uint16 in LDS: bit a = "ignored in area range a", bit 8 =
 //      crowd, bits 9-10 = the set it belongs to for this slot (3: none);
 //   C. the M x G similarity matrix, one thread per pair, into the workspace (global memory: 128 x 4096 doubles fit no LDS). A row of
@@ -17,27 +17,16 @@
 //      detection x ground-truth pair of an image is computed once. (Keeping a small matrix in LDS instead was measured on the
 //      GraspNet-shaped set and changed nothing: 0.877 against 0.884 ms per batch.)
 //   D. the sets x A x T greedy passes are independent chains, so the waves take them in turn (120 passes for a known slot: 16 waves
-//      need eight turns). A pass walks its <= 128 detections in rank order; per detection the lanes stride over the image's ground
-//      truths (lane l owns j = l, l + 64, ..: its "taken" bits are ONE 64-bit register, G <= 4096), skip those outside the pass's set,
-//      keep the best available candidate among the not-ignored and among the ignored ones, and one wave reduction picks the winner
-//      (larger similarity; equal: the higher position in the set's order). The pass leaves two bits per detection in LDS;
+//      need eight turns). A pass skips the ground truths outside its set, and a tie goes to the higher position in the set's order;
 //   E. the bits of the T passes of a (set, area range) are packed into the flag words.
 // No atomics anywhere and every address has one writer: repeats are bit-identical. rank, flags and match are preset by memsets on
 // the same stream, so rows outside every list read -1 / 0 / -1.
-#include "osr_common.h"
+#include "osr_eval_match.h"
 
-#define OM_THREADS 1024
-#define OM_WAVES (OM_THREADS / 64)
-#define OM_MAX_CAP 1024
-#define OM_MAX_DET 128
-#define OM_MAX_T 16
-#define OM_MAX_A 8
-#define OM_MAX_G 4096
 #define OM_SETS 3
 
 struct OmParams {
-    double thr[OM_MAX_T];       // min(t, 1 - 1e-10), formed on the host in fp64
-    double rng[OM_MAX_A * 2];
+    EmTables tb;
     int n, cap, K, L, T, A, max_det, num_gt, max_img;
 };
 
@@ -51,144 +40,83 @@ __device__ __forceinline__ double om_bbox_sim(const float* __restrict__ b, const
     return uni > 0.0 ? inter / fmax(uni, 1e-300) : 0.0;
 }
 
-// the larger similarity wins, equal similarities go to the higher key (the position in the set's order); j < 0: no candidate
-__device__ __forceinline__ void om_wave_best(double& s, int& k, int& j) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) {
-        const double os = __shfl_xor(s, d, 64);
-        const int ok = __shfl_xor(k, d, 64), oj = __shfl_xor(j, d, 64);
-        if (oj >= 0 && (j < 0 || os > s || (os == s && (ok > k || (ok == k && oj > j))))) s = os, k = ok, j = oj;
-    }
-}
-
-__global__ __launch_bounds__(OM_THREADS) void om_match_kernel(OmParams P, const float* __restrict__ boxes, const float* __restrict__ scores,
+// (8 waves per SIMD: two groups share a CU. Stated, not left to the register allocator, which otherwise spreads over 105 scalar registers.)
+__global__ __launch_bounds__(EM_THREADS, 8) void om_match_kernel(OmParams P, const float* __restrict__ boxes, const float* __restrict__ scores,
                                                              const int64_t* __restrict__ classes, const int32_t* __restrict__ counts,
                                                              const int32_t* __restrict__ class_slot, const int32_t* __restrict__ gt_img_off,
                                                              const double* __restrict__ gt_box, const double* __restrict__ gt_area,
                                                              const int32_t* __restrict__ gt_slot, const int32_t* __restrict__ gt_pos,
                                                              const uint8_t* __restrict__ gt_crowd, uint32_t* __restrict__ flags,
                                                              int32_t* __restrict__ rank, int32_t* __restrict__ match, double* __restrict__ simm) {
-    __shared__ int c_row[OM_MAX_CAP];
-    __shared__ uint32_t c_key[OM_MAX_CAP];
-    __shared__ int d_row[OM_MAX_DET];
-    __shared__ double d_area[OM_MAX_DET];
-    __shared__ uint16_t g_meta[OM_MAX_G];
-    __shared__ uint8_t res[OM_SETS * OM_MAX_A * OM_MAX_T][64];  // [pass][lane]: bits 0-1 detection `lane`, bits 2-3 detection 64 + `lane`
+    __shared__ int c_row[EM_MAX_CAP];
+    __shared__ uint32_t c_key[EM_MAX_CAP];
+    __shared__ int d_row[EM_MAX_DET];
+    __shared__ double d_area[EM_MAX_DET];
+    __shared__ uint16_t g_meta[EM_MAX_G];
+    __shared__ uint8_t res[OM_SETS * EM_MAX_A * EM_MAX_T][64];
     __shared__ int scan[17];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int slots = P.K + 1;
     const int i = blockIdx.x / slots, c = blockIdx.x % slots;
     const int cnt = min(max(counts[i], 0), P.cap);
-    int g0 = gt_img_off[i], G = gt_img_off[i + 1] - g0;
-    g0 = min(max(g0, 0), P.num_gt);
-    G = min(max(G, 0), min(P.num_gt - g0, P.max_img));
+    const int64_t row0 = (int64_t)i * P.cap;
+    int g0, G;
+    em_segment(gt_img_off, i, P.num_gt, P.max_img, &g0, &G);
     // A. the slot's rows, then their ranks
-    int D = 0;
-    for (int base = 0; base < cnt; base += OM_THREADS) {  // (cnt is uniform: the scans' barriers are too)
-        const int r = base + tid;
-        bool mine = false;
-        if (r < cnt) {
-            const int64_t v = classes[(int64_t)i * P.cap + r];
-            mine = v >= 0 && v < (int64_t)P.L && class_slot[v] == c;  // (c is in 0 .. K, so a slot outside -1 .. K is dropped as well)
-        }
-        int total;
-        const int pos = osr_block_excl_scan(mine ? 1 : 0, scan, &total);
-        if (mine) c_row[D + pos] = r, c_key[D + pos] = osr_float_key(scores[(int64_t)i * P.cap + r]);
-        D += total;
-    }
+    const int D = em_compact(cnt, scan, c_row, c_key, [&](int r, uint32_t* key) {
+        const int64_t v = classes[row0 + r];
+        if (!(v >= 0 && v < (int64_t)P.L && class_slot[v] == c)) return false;  // (c is in 0 .. K, so a slot outside -1 .. K is dropped as well)
+        *key = osr_float_key(scores[row0 + r]);
+        return true;
+    });
     if (D == 0) return;  // nothing to write: no row of this image carries the slot (uniform)
     __syncthreads();
     const int M = min(D, P.max_det);
-    for (int m = tid; m < D; m += OM_THREADS) {
-        const uint32_t key = c_key[m];
-        int before = 0;
-        for (int o = 0; o < D; ++o) before += (c_key[o] > key) || (c_key[o] == key && o < m);
+    for (int m = tid; m < D; m += EM_THREADS) {
+        const int before = em_stable_before(c_key, D, m);
         if (before < M) {
             d_row[before] = c_row[m];
-            rank[(int64_t)i * P.cap + c_row[m]] = before;
+            rank[row0 + c_row[m]] = before;
         }
     }
     __syncthreads();
     // B. detection areas, ground-truth marks
     const bool unknown = c == P.K;
-    for (int d = tid; d < M; d += OM_THREADS) {
-        const float* b = boxes + ((int64_t)i * P.cap + d_row[d]) * 4;
+    for (int d = tid; d < M; d += EM_THREADS) {
+        const float* b = boxes + (row0 + d_row[d]) * 4;
         d_area[d] = ((double)b[2] - (double)b[0]) * ((double)b[3] - (double)b[1]);
     }
-    for (int j = tid; j < G; j += OM_THREADS) {
+    for (int j = tid; j < G; j += EM_THREADS) {
         const int crowd = gt_crowd[g0 + j] & 1, gs = gt_slot[g0 + j];
-        const double ga = gt_area[g0 + j];
         int set = 3;
         if (gs == P.K) set = unknown ? 0 : 2;
         else if (gs >= 0 && gs < P.K) set = unknown ? 1 : (gs == c ? 0 : 1);
-        int m = crowd << 8 | set << 9;
-        for (int a = 0; a < P.A; ++a) m |= (crowd || ga < P.rng[a * 2] || ga > P.rng[a * 2 + 1]) ? 1 << a : 0;
-        g_meta[j] = (uint16_t)m;
+        g_meta[j] = (uint16_t)((crowd ? EM_CROWD : 0) | set << EM_SET_SHIFT | em_ignored_bits(crowd, gt_area[g0 + j], P.tb.rng, P.A));
     }
     // C. similarities: row r of the image's cap x G block, which starts at g0 * cap
     double* S = simm + (int64_t)g0 * P.cap;
-    for (int64_t p = tid; p < (int64_t)M * G; p += OM_THREADS) {
+    for (int64_t p = tid; p < (int64_t)M * G; p += EM_THREADS) {
         const int d = (int)(p / G), j = (int)(p % G);
         const int r = d_row[d];
-        S[(int64_t)r * G + j] = om_bbox_sim(boxes + ((int64_t)i * P.cap + r) * 4, gt_box + (int64_t)(g0 + j) * 4, gt_crowd[g0 + j] & 1);
+        S[(int64_t)r * G + j] = om_bbox_sim(boxes + (row0 + r) * 4, gt_box + (int64_t)(g0 + j) * 4, gt_crowd[g0 + j] & 1);
     }
     __threadfence_block();
     __syncthreads();
     // D. the passes
-    const int steps = (G + 63) >> 6, sets = unknown ? 2 : 3;
-    for (int pass = wave; pass < sets * P.A * P.T; pass += OM_WAVES) {
+    const int sets = unknown ? 2 : 3;
+    for (int pass = wave; pass < sets * P.A * P.T; pass += EM_WAVES) {
         const int s = pass / (P.A * P.T), a = pass / P.T % P.A, t = pass % P.T;
-        const double thr = P.thr[t], lo = P.rng[a * 2], hi = P.rng[a * 2 + 1];
         const bool by_pos = !unknown && s == 1;  // a known slot's other-known set stands in annotation order ACROSS the slots
-        unsigned long long taken = 0;  // bit q: ground truth q * 64 + lane is matched in this pass
-        uint32_t acc = 0;
-        for (int d = 0; d < M; ++d) {
-            const double* Sd = S + (int64_t)d_row[d] * G;
-            double sn = 0.0, si = 0.0;
-            int jn = -1, ji = -1, kn = -1, ki = -1;
-            for (int q = 0; q < steps; ++q) {
-                const int j = (q << 6) + lane;
-                if (j >= G) break;
-                const int m = g_meta[j];
-                if (((m >> 9) & 3) != s) continue;
-                if (((taken >> q) & 1) && !(m & 0x100)) continue;
-                const double sv = Sd[j];
-                if (!(sv >= thr)) continue;
-                const int key = by_pos ? gt_pos[g0 + j] : j;
-                if ((m >> a) & 1) {
-                    if (ji < 0 || sv > si || (sv == si && key > ki)) si = sv, ji = j, ki = key;
-                } else {
-                    if (jn < 0 || sv > sn || (sv == sn && key > kn)) sn = sv, jn = j, kn = key;
-                }
-            }
-            om_wave_best(sn, kn, jn);
-            if (jn < 0) {
-                om_wave_best(si, ki, ji);
-                jn = ji;
-            }
-            uint32_t out;
-            if (jn >= 0) {
-                if ((jn & 63) == lane) taken |= 1ull << (jn >> 6);
-                out = 1u | (uint32_t)((g_meta[jn] >> a) & 1) << 1;
-            } else {
-                out = (d_area[d] < lo || d_area[d] > hi) ? 2u : 0u;
-            }
-            if ((d & 63) == lane) acc |= out << ((d >> 6) * 2);
-            if (lane == 0 && match && jn >= 0)
-                match[((((int64_t)i * P.cap + d_row[d]) * P.A + a) * OM_SETS + s) * P.T + t] = g0 + jn;
-        }
-        res[pass][lane] = (uint8_t)acc;
+        res[pass][lane] = (uint8_t)em_greedy_pass<true>(
+            g_meta, G, s, P.tb.thr[t], a, P.tb.rng[a * 2], P.tb.rng[a * 2 + 1], d_area, d_row, M, [&](int d) { return S + (int64_t)d_row[d] * G; },
+            [&](int j) { return by_pos ? gt_pos[g0 + j] : j; }, match ? match + ((row0 * P.A + a) * OM_SETS + s) * P.T + t : nullptr,
+            (int64_t)P.A * OM_SETS * P.T, g0);
     }
     __syncthreads();
     // E. the flag words
-    for (int p = tid; p < M * P.A * sets; p += OM_THREADS) {
+    for (int p = tid; p < M * P.A * sets; p += EM_THREADS) {
         const int d = p / (P.A * sets), a = p / sets % P.A, s = p % sets;
-        uint32_t w = 0;
-        for (int t = 0; t < P.T; ++t) {
-            const uint32_t b = res[(s * P.A + a) * P.T + t][d & 63] >> ((d >> 6) * 2);
-            w |= (b & 1u) << t | ((b >> 1) & 1u) << (16 + t);
-        }
-        flags[(((int64_t)i * P.cap + d_row[d]) * P.A + a) * OM_SETS + s] = w;
+        flags[((row0 + d_row[d]) * P.A + a) * OM_SETS + s] = em_flag_word(res, (s * P.A + a) * P.T, P.T, d);
     }
 }
 
@@ -208,11 +136,11 @@ extern "C" osr_status osr_os_coco_match(const float* boxes, const float* scores,
                 OSR_ERR_INVALID_ARG,
                 "osr_os_coco_match: n %d, cap %d, class values %d, known slots %d, num_gt %d, max_gt_per_image %d, max_det %d, thresholds %d, area ranges %d", n,
                 cap, num_class_values, num_known, num_gt, max_gt_per_image, max_det, num_thrs, num_areas);
-    OSR_REQUIRE(cap <= OM_MAX_CAP, OSR_ERR_UNSUPPORTED, "osr_os_coco_match: cap %d, at most %d rows per image", cap, OM_MAX_CAP);
-    OSR_REQUIRE(max_det <= OM_MAX_DET, OSR_ERR_UNSUPPORTED, "osr_os_coco_match: max_det %d, at most %d", max_det, OM_MAX_DET);
-    OSR_REQUIRE(num_thrs <= OM_MAX_T, OSR_ERR_UNSUPPORTED, "osr_os_coco_match: %d thresholds, at most %d", num_thrs, OM_MAX_T);
-    OSR_REQUIRE(num_areas <= OM_MAX_A, OSR_ERR_UNSUPPORTED, "osr_os_coco_match: %d area ranges, at most %d", num_areas, OM_MAX_A);
-    OSR_REQUIRE(max_gt_per_image <= OM_MAX_G, OSR_ERR_UNSUPPORTED, "osr_os_coco_match: %d ground truths in one image, at most %d", max_gt_per_image, OM_MAX_G);
+    OSR_REQUIRE(cap <= EM_MAX_CAP, OSR_ERR_UNSUPPORTED, "osr_os_coco_match: cap %d, at most %d rows per image", cap, EM_MAX_CAP);
+    OSR_REQUIRE(max_det <= EM_MAX_DET, OSR_ERR_UNSUPPORTED, "osr_os_coco_match: max_det %d, at most %d", max_det, EM_MAX_DET);
+    OSR_REQUIRE(num_thrs <= EM_MAX_T, OSR_ERR_UNSUPPORTED, "osr_os_coco_match: %d thresholds, at most %d", num_thrs, EM_MAX_T);
+    OSR_REQUIRE(num_areas <= EM_MAX_A, OSR_ERR_UNSUPPORTED, "osr_os_coco_match: %d area ranges, at most %d", num_areas, EM_MAX_A);
+    OSR_REQUIRE(max_gt_per_image <= EM_MAX_G, OSR_ERR_UNSUPPORTED, "osr_os_coco_match: %d ground truths in one image, at most %d", max_gt_per_image, EM_MAX_G);
     OSR_REQUIRE((int64_t)n * ((int64_t)num_known + 1) < (1LL << 31) - 1, OSR_ERR_UNSUPPORTED, "osr_os_coco_match: %d images x %lld slots is no grid", n,
                 (long long)num_known + 1);
     OSR_REQUIRE(iou_thrs && area_rng, OSR_ERR_INVALID_ARG, "osr_os_coco_match: null pointer (thresholds / area ranges)");
@@ -228,18 +156,16 @@ extern "C" osr_status osr_os_coco_match(const float* boxes, const float* scores,
                     ((uintptr_t)match & 3) == 0 && ((uintptr_t)workspace & 7) == 0,
                 OSR_ERR_INVALID_ARG, "osr_os_coco_match: misaligned pointer");
     OmParams P;
-    for (int t = 0; t < OM_MAX_T; ++t) P.thr[t] = t < num_thrs ? (iou_thrs[t] < 1 - 1e-10 ? iou_thrs[t] : 1 - 1e-10) : 2.0;
-    for (int a = 0; a < OM_MAX_A * 2; ++a) P.rng[a] = a < num_areas * 2 ? area_rng[a] : 0.0;
+    em_fill_tables(&P.tb, iou_thrs, num_thrs, area_rng, num_areas);
     P.n = n, P.cap = cap, P.K = num_known, P.L = num_class_values, P.T = num_thrs, P.A = num_areas, P.max_det = max_det;
     P.num_gt = num_gt, P.max_img = max_gt_per_image;
     hipStream_t st = (hipStream_t)stream;
     const int64_t words = (int64_t)n * cap * num_areas * OM_SETS;
-    if (hipMemsetAsync(flags, 0, (size_t)words * 4, st) != hipSuccess || hipMemsetAsync(rank, 0xff, (size_t)n * cap * 4, st) != hipSuccess ||
-        (match && hipMemsetAsync(match, 0xff, (size_t)words * num_thrs * 4, st) != hipSuccess)) {
+    if (!em_preset(flags, words, rank, (int64_t)n * cap, match, words * num_thrs, st)) {
         osr_set_error("osr_os_coco_match: hipMemsetAsync failed");
         return OSR_ERR_LAUNCH;
     }
-    hipLaunchKernelGGL(om_match_kernel, dim3(n * (num_known + 1)), dim3(OM_THREADS), 0, st, P, boxes, scores, classes, counts, class_slot, gt_img_off, gt_box,
+    hipLaunchKernelGGL(om_match_kernel, dim3(n * (num_known + 1)), dim3(EM_THREADS), 0, st, P, boxes, scores, classes, counts, class_slot, gt_img_off, gt_box,
                        gt_area, gt_slot, gt_pos, gt_crowd, flags, rank, match, (double*)workspace);
     OSR_CHECK_LAUNCH("osr_os_coco_match");
     return OSR_OK;

@@ -16,6 +16,7 @@
 //   E. per threshold the ground truths at or above it are counted with wave ballots.
 // Every output address has one writer and the only atomics are integer adds in LDS: repeats are bit-identical.
 #include "osr_boxes.h"
+#include "osr_eval_match.h"  // (the clamped segment read only: the limits here are PR_*)
 #include "osr_select.h"
 
 #define PR_THREADS 1024
@@ -75,9 +76,8 @@ __global__ __launch_bounds__(PR_THREADS) void pr_recall_kernel(PrParams P, const
     const int al = blockIdx.x % (P.A * P.L), i = blockIdx.x / (P.A * P.L);
     const int a = al / P.L, l = al % P.L;
     const int cnt = min(max(counts[i], 0), P.cap);
-    int g0 = seg_off[i], G = seg_off[i + 1] - g0;
-    g0 = min(max(g0, 0), P.num_gt);
-    G = min(max(G, 0), min(P.num_gt - g0, P.max_gt));
+    int g0, G;
+    em_segment(seg_off, i, P.num_gt, P.max_gt, &g0, &G);
     int32_t* my_hits = hits + ((int64_t)(i * P.A + a) * P.L + l) * P.T;
     float* my_ov = gt_overlap ? gt_overlap + (int64_t)(a * P.L + l) * P.num_gt + g0 : nullptr;
     // A. the area range's ground truths

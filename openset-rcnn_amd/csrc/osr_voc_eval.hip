@@ -6,9 +6,8 @@
 // nothing to write and leaves after the scan. What makes VOC's greedy matching parallel: a detection's ground truth is the argmax
 // over ALL ground truths of its class, taken or not, so only "was it taken before me" depends on the other detections, and that is
 // "am I the first in list order among the detections that chose it". Inside a group:
-//   A. the rows of the group's class are compacted in row order (a block scan over the <= 1024 rows) with their rounded scores;
-//      non-finite rows are marked and left out; each member gets its rank by counting the members that precede it: higher rounded
-//      score, or the same one and a lower row (the stable order);
+//   A. the rows of the group's class are compacted in row order with their rounded scores and ranked by them, stably
+//      (osr_eval_match.h); non-finite rows are marked and left out;
 //   B. one wave per detection: the lanes stride over the image's ground truths, keep the best overlap among those of the class (NaN
 //      first, then the larger, equal ones to the lower index: np.argmax) and whether an "unknown" one overlaps, one wave reduction;
 //      lane 0 notes the chosen ground truth and, unless it is difficult, lowers that ground truth's "first rank" in LDS (an integer
@@ -17,13 +16,8 @@
 // The group of class 0 also writes the rows that belong to no list (past counts, class outside 0 .. C - 1, image outside the table),
 // so every output element has exactly ONE writer and repeats are bit-identical; `status` is preset by a memset on the same stream
 // and every group that meets a non-finite row stores the same 1.
-#include "osr_common.h"
+#include "osr_eval_match.h"
 #include <limits.h>
-
-#define VM_THREADS 1024
-#define VM_WAVES (VM_THREADS / 64)
-#define VM_MAX_CAP 1024
-#define VM_MAX_G 4096
 
 #define VM_VALID 1
 #define VM_TP 2
@@ -67,19 +61,19 @@ __device__ __forceinline__ bool vm_before(double a, int ja, double b, int jb) {
     return ja < jb;
 }
 
-__global__ __launch_bounds__(VM_THREADS) void vm_match_kernel(VmParams P, const float* __restrict__ boxes, const float* __restrict__ scores,
+__global__ __launch_bounds__(EM_THREADS) void vm_match_kernel(VmParams P, const float* __restrict__ boxes, const float* __restrict__ scores,
                                                              const int64_t* __restrict__ classes, const int32_t* __restrict__ counts,
                                                              const int32_t* __restrict__ image_index, const int32_t* __restrict__ gt_img_off,
                                                              const double* __restrict__ gt_box, const int32_t* __restrict__ gt_cls,
                                                              const uint8_t* __restrict__ gt_difficult, uint8_t* __restrict__ flags,
                                                              int32_t* __restrict__ milli, int32_t* __restrict__ match, int64_t* __restrict__ deci,
                                                              int32_t* __restrict__ status) {
-    __shared__ int c_row[VM_MAX_CAP];
-    __shared__ int c_k[VM_MAX_CAP];
-    __shared__ int c_rank[VM_MAX_CAP];
-    __shared__ int c_j[VM_MAX_CAP];
-    __shared__ uint8_t c_unk[VM_MAX_CAP];
-    __shared__ int g_first[VM_MAX_G];  // per ground truth of the image: the lowest rank among the detections that chose it
+    __shared__ int c_row[EM_MAX_CAP];
+    __shared__ int c_k[EM_MAX_CAP];
+    __shared__ int c_rank[EM_MAX_CAP];
+    __shared__ int c_j[EM_MAX_CAP];
+    __shared__ uint8_t c_unk[EM_MAX_CAP];
+    __shared__ int g_first[EM_MAX_G];  // per ground truth of the image: the lowest rank among the detections that chose it
     __shared__ int scan[17];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int i = blockIdx.x / P.C, c = blockIdx.x % P.C;
@@ -88,7 +82,7 @@ __global__ __launch_bounds__(VM_THREADS) void vm_match_kernel(VmParams P, const 
     const int cnt = min(max(counts[i], 0), P.cap);
     const int64_t row0 = (int64_t)i * P.cap;
     if (c == 0) {  // the rows of no list
-        for (int r = tid; r < P.cap; r += VM_THREADS) {
+        for (int r = tid; r < P.cap; r += EM_THREADS) {
             bool listed = img_ok && r < cnt;
             if (listed) {
                 const int64_t v = classes[row0 + r];
@@ -105,47 +99,33 @@ __global__ __launch_bounds__(VM_THREADS) void vm_match_kernel(VmParams P, const 
         }
     }
     if (!img_ok) return;  // (uniform)
-    int g0 = gt_img_off[img], G = gt_img_off[img + 1] - g0;
-    g0 = min(max(g0, 0), P.num_gt);
-    G = min(max(G, 0), min(P.num_gt - g0, P.max_img));
+    int g0, G;
+    em_segment(gt_img_off, img, P.num_gt, P.max_img, &g0, &G);
     // A. the class's finite rows and their rounded scores, then their ranks
-    int D = 0;
-    for (int base = 0; base < cnt; base += VM_THREADS) {  // (cnt is uniform: the scans' barriers are too)
-        const int r = base + tid;
-        bool mine = false;
-        int kk = 0;
-        if (r < cnt && classes[row0 + r] == (int64_t)c) {
-            double t[4], k;
-            if (vm_record(boxes + (row0 + r) * 4, scores[row0 + r], t, &k)) {
-                mine = true, kk = (int)k;
-            } else {
-                flags[row0 + r] = VM_VALID | VM_NONFINITE, milli[row0 + r] = 0;
-                if (match) match[row0 + r] = -1;
-                if (deci) {
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) deci[(row0 + r) * 4 + q] = 0;
-                }
-                status[0] = 1;  // (every writer stores the same word)
-            }
+    const int D = em_compact(cnt, scan, c_row, c_k, [&](int r, int* key) {
+        if (classes[row0 + r] != (int64_t)c) return false;
+        double t[4], k;
+        if (vm_record(boxes + (row0 + r) * 4, scores[row0 + r], t, &k)) {
+            *key = (int)k;
+            return true;
         }
-        int total;
-        const int pos = osr_block_excl_scan(mine ? 1 : 0, scan, &total);
-        if (mine) c_row[D + pos] = r, c_k[D + pos] = kk;
-        D += total;
-    }
+        flags[row0 + r] = VM_VALID | VM_NONFINITE, milli[row0 + r] = 0;
+        if (match) match[row0 + r] = -1;
+        if (deci) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) deci[(row0 + r) * 4 + q] = 0;
+        }
+        status[0] = 1;  // (every writer stores the same word)
+        return false;
+    });
     if (D == 0) return;  // nothing more to write: no finite row of this image carries the class (uniform)
     __syncthreads();
-    for (int m = tid; m < D; m += VM_THREADS) {
-        const int key = c_k[m];
-        int before = 0;
-        for (int o = 0; o < D; ++o) before += (c_k[o] > key) || (c_k[o] == key && o < m);
-        c_rank[m] = before;
-    }
-    for (int j = tid; j < G; j += VM_THREADS) g_first[j] = INT_MAX;
+    for (int m = tid; m < D; m += EM_THREADS) c_rank[m] = em_stable_before(c_k, D, m);
+    for (int j = tid; j < G; j += EM_THREADS) g_first[j] = INT_MAX;
     __syncthreads();
     // B. per detection the first maximum among the class's ground truths and the overlap with an unknown one
     const int unknown = P.C - 1;
-    for (int m = wave; m < D; m += VM_WAVES) {
+    for (int m = wave; m < D; m += EM_WAVES) {
         const int r = c_row[m];
         double t[4], k, bb[4];
         vm_record(boxes + (row0 + r) * 4, scores[row0 + r], t, &k);
@@ -181,7 +161,7 @@ __global__ __launch_bounds__(VM_THREADS) void vm_match_kernel(VmParams P, const 
     }
     __syncthreads();
     // C. the flag bytes
-    for (int m = tid; m < D; m += VM_THREADS) {
+    for (int m = tid; m < D; m += EM_THREADS) {
         const int r = c_row[m], j = c_j[m];
         int f = VM_VALID | (c_unk[m] ? VM_UNK : 0);
         if (j < 0) f |= VM_FP;
@@ -204,8 +184,8 @@ extern "C" osr_status osr_voc_match(const float* boxes, const float* scores, con
                                     uint8_t* flags, int32_t* milli, int32_t* match, int64_t* deci, int32_t* status, void* stream) {
     OSR_REQUIRE(n >= 0 && cap >= 0 && num_images >= 0 && num_gt >= 0 && max_gt_per_image >= 0, OSR_ERR_INVALID_ARG,
                 "osr_voc_match: n %d, cap %d, num_images %d, num_gt %d, max_gt_per_image %d", n, cap, num_images, num_gt, max_gt_per_image);
-    OSR_REQUIRE(cap <= VM_MAX_CAP, OSR_ERR_UNSUPPORTED, "osr_voc_match: cap %d, at most %d rows per image", cap, VM_MAX_CAP);
-    OSR_REQUIRE(max_gt_per_image <= VM_MAX_G, OSR_ERR_UNSUPPORTED, "osr_voc_match: %d ground truths in one image, at most %d", max_gt_per_image, VM_MAX_G);
+    OSR_REQUIRE(cap <= EM_MAX_CAP, OSR_ERR_UNSUPPORTED, "osr_voc_match: cap %d, at most %d rows per image", cap, EM_MAX_CAP);
+    OSR_REQUIRE(max_gt_per_image <= EM_MAX_G, OSR_ERR_UNSUPPORTED, "osr_voc_match: %d ground truths in one image, at most %d", max_gt_per_image, EM_MAX_G);
     OSR_REQUIRE(num_classes >= 1, OSR_ERR_UNSUPPORTED, "osr_voc_match: %d class names, at least 1 (\"unknown\")", num_classes);
     OSR_REQUIRE((int64_t)n * (int64_t)num_classes < (1LL << 31), OSR_ERR_UNSUPPORTED, "osr_voc_match: %d images x %d classes is no grid", n, num_classes);
     if (n == 0 || cap == 0) return OSR_OK;
@@ -223,7 +203,7 @@ extern "C" osr_status osr_voc_match(const float* boxes, const float* scores, con
         osr_set_error("osr_voc_match: hipMemsetAsync failed");
         return OSR_ERR_LAUNCH;
     }
-    hipLaunchKernelGGL(vm_match_kernel, dim3(n * num_classes), dim3(VM_THREADS), 0, st, P, boxes, scores, classes, counts, image_index, gt_img_off, gt_box,
+    hipLaunchKernelGGL(vm_match_kernel, dim3(n * num_classes), dim3(EM_THREADS), 0, st, P, boxes, scores, classes, counts, image_index, gt_img_off, gt_box,
                        gt_cls, gt_difficult, flags, milli, match, deci, status);
     OSR_CHECK_LAUNCH("osr_voc_match");
     return OSR_OK;

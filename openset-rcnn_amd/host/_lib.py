@@ -108,10 +108,10 @@ PANOPTIC_MAX_STUFF = 255       # labels 1 .. 255
 CONF_LABELS, CONF_VALUES = 0, 1
 PQ_MAX_GT, PQ_MAX_PRED = 1023, 2047  # csrc/osr_seg_eval.hip PP_MAX_G / PP_MAX_P
 COCO_BBOX, COCO_KEYPOINTS = 0, 1
-COCO_MAX_CAP, COCO_MAX_DET, COCO_MAX_THRS, COCO_MAX_AREAS, COCO_MAX_KPTS, COCO_MAX_GROUP = 1024, 128, 16, 8, 32, 4096  # csrc/osr_coco_eval.hip CM_MAX_*
-OS_COCO_MAX_CAP, OS_COCO_MAX_DET, OS_COCO_MAX_THRS, OS_COCO_MAX_AREAS, OS_COCO_MAX_GT = 1024, 128, 16, 8, 4096  # csrc/osr_os_coco_eval.hip OM_MAX_*
+COCO_MAX_CAP, COCO_MAX_DET, COCO_MAX_THRS, COCO_MAX_AREAS, COCO_MAX_KPTS, COCO_MAX_GROUP = 1024, 128, 16, 8, 32, 4096  # csrc/osr_eval_match.h EM_MAX_*, csrc/osr_coco_eval.hip CM_MAX_KP
+OS_COCO_MAX_CAP, OS_COCO_MAX_DET, OS_COCO_MAX_THRS, OS_COCO_MAX_AREAS, OS_COCO_MAX_GT = 1024, 128, 16, 8, 4096  # csrc/osr_eval_match.h EM_MAX_*
 OS_COCO_SETS = 3  # flag words per (detection, area range): own slot, other known, unknown
-VOC_MAX_CAP, VOC_MAX_GT = 1024, 4096  # csrc/osr_voc_eval.hip VM_MAX_* (the flag bits: host/evaluation.py VOC_*)
+VOC_MAX_CAP, VOC_MAX_GT = 1024, 4096  # csrc/osr_eval_match.h EM_MAX_CAP / EM_MAX_G (the flag bits: host/evaluation.py VOC_*)
 
 
 PROPOSAL_MAX_CAP, PROPOSAL_MAX_GT, PROPOSAL_MAX_AREAS, PROPOSAL_MAX_LIMITS, PROPOSAL_MAX_THRS = 2048, 1024, 8, 8, 16  # csrc/osr_proposal_recall.hip PR_MAX_*

@@ -29,6 +29,7 @@ import torch
 from . import parallel
 from .datasets import MetadataCatalog
 from .os_coco_evaluation import box_iou_xywh
+from .eval_buffers import fetch_chunks, upload_sections
 from .proposal_evaluation import ProposalRecall
 
 logger = logging.getLogger(__name__)
@@ -383,10 +384,6 @@ class _GroundTruthTables:
         return out
 
 
-def _align8(n: int) -> int:
-    return (n + 7) // 8 * 8
-
-
 class COCOEvaluator:
     """[d2] COCOEvaluator for the tasks "bbox" and "keypoints". `tasks`: a tuple of task names, None (taken from what the first
     predictions carry: bbox, and keypoints when they have pred_keypoints) or a config node (bbox, keypoints with MODEL.KEYPOINT_ON;
@@ -496,7 +493,7 @@ class COCOEvaluator:
                 boxes[i, :m], scores[i, :m], classes[i, :m] = inst.pred_boxes.tensor.to(torch.float32), inst.scores.to(torch.float32), inst.pred_classes.to(torch.int64)
                 if kp_task:
                     kpts[i, :m] = inst.pred_keypoints.to(torch.float32)
-        # the batch's tables, one buffer, one copy: float64 sections first, then int32, then bytes
+        # the batch's tables, one buffer, one copy
         tb = self.tables
         rows, seg_off, max_group = tb.batch(image_ids)
         if max_group > ops._lib.COCO_MAX_GROUP:
@@ -504,29 +501,17 @@ class COCOEvaluator:
         ng = len(rows)
         if kp_task and ng and tb.num_kpts != kpn:
             raise ValueError(f"COCOEvaluator: the predictions have {kpn} keypoints, the ground truth of {self.dataset_name} {tb.num_kpts}")
-        f64 = [tb.box[rows].reshape(-1), tb.area[rows]]
+        sections = [tb.box[rows], tb.area[rows], np.asarray(seg_off, dtype=np.int32), np.asarray(lens, dtype=np.int32)]  # (the tables are float64 / uint8)
         if kp_task:
-            f64 += [tb.kpts[rows].reshape(-1) if ng else np.zeros(0), self.sigmas_for(kpn)]
-        i32 = [seg_off, np.asarray(lens, dtype=np.int32)]
-        u8 = [tb.flags[t][rows] for t in tasks]
-        parts = [np.ascontiguousarray(a, dtype=np.float64).view(np.uint8) for a in f64] + [np.ascontiguousarray(a, dtype=np.int32).view(np.uint8) for a in i32]
-        sizes = [p.size for p in parts] + [a.size for a in u8]
-        buf = np.zeros(sum(_align8(s) for s in sizes), dtype=np.uint8)
-        offs, o = [], 0
-        for a, s in zip(parts + u8, sizes):
-            buf[o:o + s] = a
-            offs.append(o)
-            o += _align8(s)
-        dbuf = torch.from_numpy(buf).to(dev, non_blocking=True)
-        view = lambda j, dt: dbuf[offs[j]:offs[j] + sizes[j]].view(dt)  # noqa: E731
-        gt_box, gt_area = view(0, torch.float64).view(ng, 4), view(1, torch.float64)
-        nf = len(f64)
-        gt_kpts, sig = (view(2, torch.float64).view(ng, kpn, 3), view(3, torch.float64)) if kp_task else (None, None)
-        d_seg, d_counts = view(nf, torch.int32), view(nf + 1, torch.int32)
+            sections += [tb.kpts[rows] if ng else np.zeros((0, kpn, 3)), self.sigmas_for(kpn)]
+        views = upload_sections(sections + [tb.flags[t][rows] for t in tasks], dev)
+        gt_box, gt_area, d_seg, d_counts = views[:4]
+        gt_kpts, sig = views[4:6] if kp_task else (None, None)
+        gt_flags = views[len(sections):]
         chunk = dict(n=n, cap=cap, kpn=kpn, boxes=boxes, scores=scores, classes=classes, counts=d_counts, kpts=kpts)
         for ti, task in enumerate(tasks):
             p = Params(task, self.max_dets[task])
-            flags, rank, _, _ = ops.coco_match(boxes, scores, classes, d_counts, K, d_seg, gt_box, gt_area, view(nf + 2 + ti, torch.uint8), max_group, p.iou_thrs,
+            flags, rank, _, _ = ops.coco_match(boxes, scores, classes, d_counts, K, d_seg, gt_box, gt_area, gt_flags[ti], max_group, p.iou_thrs,
                                                p.area_rng, p.max_dets[-1], keypoints=kpts if task == "keypoints" else None,
                                                gt_kpts=gt_kpts if task == "keypoints" else None, sigmas=sig if task == "keypoints" else None)
             chunk["flags_" + task], chunk["rank_" + task] = flags, rank
@@ -538,19 +523,12 @@ class COCOEvaluator:
         """Every device buffer in ONE copy -> flat host arrays over the rows that exist, in processing order."""
         if not self._chunks:
             return None
-        fields = ["boxes", "scores", "classes", "counts"] + (["kpts"] if self._chunks[0]["kpts"] is not None else []) + \
-                 [f + t for t in self.tasks for f in ("flags_", "rank_")]
-        tensors = [c[f].reshape(-1).view(torch.uint8) for c in self._chunks for f in fields]
-        host = torch.cat(tensors).cpu().numpy()  # the one copy
-        dtypes = {"boxes": np.float32, "scores": np.float32, "classes": np.int64, "counts": np.int32, "kpts": np.float32}
-        out, o, img0 = defaultdict(list), 0, 0
-        for c in self._chunks:
+        fields = [("boxes", np.float32), ("scores", np.float32), ("classes", np.int64), ("counts", np.int32)] + \
+                 ([("kpts", np.float32)] if self._chunks[0]["kpts"] is not None else []) + \
+                 [(f + t, dt) for t in self.tasks for f, dt in (("flags_", np.uint32), ("rank_", np.int32))]
+        out, img0 = defaultdict(list), 0
+        for c, got in zip(self._chunks, fetch_chunks(self._chunks, fields)):
             n, cap = c["n"], c["cap"]
-            got = {}
-            for f in fields:
-                nbytes = c[f].numel() * c[f].element_size()
-                got[f] = host[o:o + nbytes].view(np.uint32 if f.startswith("flags_") else np.int32 if f.startswith("rank_") else dtypes[f])
-                o += nbytes
             exists = (np.arange(cap)[None, :] < got["counts"][:, None]).reshape(-1)
             out["image"].append(np.repeat(np.arange(img0, img0 + n), cap)[exists])
             out["boxes"].append(got["boxes"].reshape(-1, 4)[exists])

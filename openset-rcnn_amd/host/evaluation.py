@@ -342,6 +342,7 @@ class PascalVOCDetectionEvaluator:
         pred_classes only; copies nothing to the host and does not synchronise."""
         import torch
         from . import ops
+        from .eval_buffers import upload_sections
         L = ops._lib
         tb, reason = self._table()
         if tb is None:
@@ -363,19 +364,13 @@ class PascalVOCDetectionEvaluator:
                 return f"image_id {im!r} was processed twice"
             batch_ids.add(im)
             index.append(tb.index[im])
-        if self._dev_table is None or self._dev_table[0] != dev:  # the dataset's table, one buffer, one copy: float64 first, then int32, then bytes
-            hb = [np.ascontiguousarray(a).view(np.uint8).reshape(-1) for a in (tb.box, tb.img_off, tb.cls, tb.difficult)]
-            sizes = [h.size for h in hb]
-            d = torch.from_numpy(np.concatenate(hb)).to(dev, non_blocking=True)
-            o = np.concatenate(([0], np.cumsum(sizes)))
-            self._dev_table = (dev, d[o[0]:o[1]].view(torch.float64).view(-1, 4), d[o[1]:o[2]].view(torch.int32), d[o[2]:o[3]].view(torch.int32), d[o[3]:o[4]])
+        if self._dev_table is None or self._dev_table[0] != dev:  # the dataset's table, one buffer, one copy
+            self._dev_table = (dev, *upload_sections([tb.box, tb.img_off, tb.cls, tb.difficult], dev))
         _, gt_box, gt_off, gt_cls, gt_difficult = self._dev_table
         n, total = len(parts), sum(lens)
         cap = max((max(lens) + 7) // 8 * 8, 8)
         dest = np.concatenate([i * cap + np.arange(m, dtype=np.int64) for i, m in enumerate(lens)])  # where each detection goes in the padded lists
-        hb = np.concatenate([dest.view(np.uint8), np.asarray(lens, dtype=np.int32).view(np.uint8), np.asarray(index, dtype=np.int32).view(np.uint8)])
-        d = torch.from_numpy(hb).to(dev, non_blocking=True)
-        d_dest, d_counts, d_index = d[:8 * total].view(torch.int64), d[8 * total:8 * total + 4 * n].view(torch.int32), d[8 * total + 4 * n:].view(torch.int32)
+        d_dest, d_counts, d_index = upload_sections([dest, np.asarray(lens, dtype=np.int32), np.asarray(index, dtype=np.int32)], dev)
         boxes = torch.zeros((n, cap, 4), dtype=torch.float32, device=dev)
         scores = torch.zeros((n, cap), dtype=torch.float32, device=dev)
         classes = torch.full((n, cap), -1, dtype=torch.int64, device=dev)
@@ -395,21 +390,13 @@ class PascalVOCDetectionEvaluator:
     def _host_segments(self) -> List[tuple]:
         """The segments with every device chunk replaced by flat host arrays over the rows that exist, in arrival order (image row, then
         detection row). All chunks not fetched before come over in ONE copy."""
-        import torch
+        from .eval_buffers import fetch_chunks
         todo = [c for kind, c in self._segments if kind == "device" and "host" not in c]
-        if todo:
-            host = torch.cat([c[f].reshape(-1).view(torch.uint8) for c in todo for f, _ in self._FIELDS]).cpu().numpy()  # the one copy
-            o = 0
-            for c in todo:
-                got = {}
-                for f, dt in self._FIELDS:
-                    nbytes = c[f].numel() * c[f].element_size()
-                    got[f] = host[o:o + nbytes].view(dt)
-                    o += nbytes
-                exists = (np.arange(c["cap"])[None, :] < np.asarray(c["lens"])[:, None]).reshape(-1)
-                c["host"] = dict(image_ids=c["image_ids"], image=np.repeat(np.arange(c["n"]), c["cap"])[exists], boxes=got["boxes"].reshape(-1, 4)[exists],
-                                 scores=got["scores"][exists], classes=got["classes"][exists], flags=got["flags"][exists], milli=got["milli"][exists],
-                                 status=int(got["status"][0]))
+        for c, got in zip(todo, fetch_chunks(todo, self._FIELDS)):
+            exists = (np.arange(c["cap"])[None, :] < np.asarray(c["lens"])[:, None]).reshape(-1)
+            c["host"] = dict(image_ids=c["image_ids"], image=np.repeat(np.arange(c["n"]), c["cap"])[exists], boxes=got["boxes"].reshape(-1, 4)[exists],
+                             scores=got["scores"][exists], classes=got["classes"][exists], flags=got["flags"][exists], milli=got["milli"][exists],
+                             status=int(got["status"][0]))
         return [(kind, c["host"] if kind == "device" else c) for kind, c in self._segments]
 
     @staticmethod

@@ -444,10 +444,6 @@ class OpensetGroundTruthTables:
         return table
 
 
-def _align8(n: int) -> int:
-    return (n + 7) // 8 * 8
-
-
 class _Detections:
     """Every rank's detections in processing order: ("host", records) and ("device", the arrays of one fetched chunk)."""
 
@@ -534,6 +530,7 @@ class OpensetCOCOEvaluator:
         """The batch through ops.os_coco_match; -> None, or why this batch has to take the host path instead."""
         import torch
         from . import ops
+        from .eval_buffers import upload_sections
         L = ops._lib
         if self._tables is None:
             self._tables = OpensetGroundTruthTables(self.gt, self.known_ids)
@@ -565,44 +562,25 @@ class OpensetCOCOEvaluator:
             m = lens[i]
             if m:
                 boxes[i, :m], scores[i, :m], classes[i, :m] = inst.pred_boxes.tensor.detach(), inst.scores.detach(), inst.pred_classes.detach().to(torch.int64)
-        # the batch's table, one buffer, one copy: float64 sections first, then int32, then bytes
-        ng = len(rows)
-        parts = [np.ascontiguousarray(a, dtype=np.float64).view(np.uint8) for a in (tb.box[rows].reshape(-1), tb.area[rows])] + \
-                [np.ascontiguousarray(a, dtype=np.int32).view(np.uint8) for a in (img_off, np.asarray(lens), tb.slot[rows], tb.pos[rows])] + [tb.crowd[rows]]
-        sizes = [p.size for p in parts]
-        buf = np.zeros(sum(_align8(s) for s in sizes), dtype=np.uint8)
-        offs, o = [], 0
-        for p, s in zip(parts, sizes):
-            buf[o:o + s] = p
-            offs.append(o)
-            o += _align8(s)
-        dbuf = torch.from_numpy(buf).to(dev, non_blocking=True)
-        view = lambda j, dt: dbuf[offs[j]:offs[j] + sizes[j]].view(dt)  # noqa: E731
+        # the batch's table, one buffer, one copy
+        i32 = lambda a: np.asarray(a, dtype=np.int32)  # noqa: E731
+        gt_box, gt_area, d_off, d_counts, gt_slot, gt_pos, gt_crowd = upload_sections(
+            [tb.box[rows], tb.area[rows], i32(img_off), i32(lens), tb.slot[rows], tb.pos[rows], tb.crowd[rows]], dev)
         area_rng = [[0 ** 2, 1e5 ** 2], [0 ** 2, 32 ** 2], [32 ** 2, 96 ** 2], [96 ** 2, 1e5 ** 2]]  # OpensetCOCOEval's, like its thresholds
         iou_thrs = np.linspace(.5, 0.95, int(np.round((0.95 - .5) / .05)) + 1, endpoint=True)
-        d_counts = view(3, torch.int32)
-        flags, rank, _ = ops.os_coco_match(boxes, scores, classes, d_counts, self._class_slot[1], tb.num_known, view(2, torch.int32),
-                                           view(0, torch.float64).view(ng, 4), view(1, torch.float64), view(4, torch.int32), view(5, torch.int32),
-                                           view(6, torch.uint8), max_img, iou_thrs, area_rng, max_det)
+        flags, rank, _ = ops.os_coco_match(boxes, scores, classes, d_counts, self._class_slot[1], tb.num_known, d_off, gt_box, gt_area, gt_slot, gt_pos, gt_crowd,
+                                           max_img, iou_thrs, area_rng, max_det)
         self._chunks.append(dict(n=n, cap=cap, image_ids=list(image_ids), boxes=boxes, scores=scores, classes=classes, counts=d_counts, flags=flags, rank=rank))
         self._segments.append(("device", len(self._chunks) - 1))
         return None
 
     def _fetch(self) -> List[dict]:
         """Every device buffer in ONE copy -> per chunk the flat host arrays over the rows that exist."""
-        import torch
-        if not self._chunks:
-            return []
+        from .eval_buffers import fetch_chunks
         fields = (("boxes", np.float32), ("scores", np.float32), ("classes", np.int64), ("counts", np.int32), ("flags", np.uint32), ("rank", np.int32))
-        host = torch.cat([c[f].reshape(-1).view(torch.uint8) for c in self._chunks for f, _ in fields]).cpu().numpy()  # the one copy
-        out, o = [], 0
-        for c in self._chunks:
+        out = []
+        for c, got in zip(self._chunks, fetch_chunks(self._chunks, fields)):
             n, cap = c["n"], c["cap"]
-            got = {}
-            for f, dt in fields:
-                nbytes = c[f].numel() * c[f].element_size()
-                got[f] = host[o:o + nbytes].view(dt)
-                o += nbytes
             exists = (np.arange(cap)[None, :] < got["counts"][:, None]).reshape(-1)
             out.append(dict(image_ids=c["image_ids"], image=np.repeat(np.arange(n), cap)[exists], boxes=got["boxes"].reshape(-1, 4)[exists],
                             scores=got["scores"][exists], classes=got["classes"][exists], rank=got["rank"][exists],

@@ -18,6 +18,8 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
+from .eval_buffers import upload_sections
+
 # name -> [lo, hi] of the annotation's area, both ends inclusive; the first four are what the evaluators report
 AREA_RANGES = {"all": (0 ** 2, 1e5 ** 2), "small": (0 ** 2, 32 ** 2), "medium": (32 ** 2, 96 ** 2), "large": (96 ** 2, 1e5 ** 2),
                "96-128": (96 ** 2, 128 ** 2), "128-256": (128 ** 2, 256 ** 2), "256-512": (256 ** 2, 512 ** 2), "512-inf": (512 ** 2, 1e5 ** 2)}
@@ -190,15 +192,10 @@ class ProposalRecall:
         for i, p in enumerate(props):
             if lens[i]:
                 boxes[i, :lens[i]], logits[i, :lens[i]] = p.proposal_boxes.tensor.to(torch.float32), p.objectness_logits.to(torch.float32)
-        # the batch's tables, one buffer of 4-byte words, one copy: boxes, areas, segment offsets, counts
-        ng = sum(per_image)
+        # the batch's tables, one buffer, one copy
         seg_off = np.concatenate(([0], np.cumsum(per_image))).astype(np.int32)
-        parts = [np.concatenate([b for b, _ in gts]).reshape(-1).view(np.int32), np.concatenate([a for _, a in gts]).view(np.int32), seg_off,
-                 np.asarray(lens, dtype=np.int32)]
-        dbuf = torch.from_numpy(np.concatenate(parts)).to(dev, non_blocking=True)
-        o1, o2, o3 = ng * 4, ng * 5, ng * 5 + n + 1
-        gt_boxes, gt_area = dbuf[:o1].view(torch.float32).view(ng, 4), dbuf[o1:o2].view(torch.float32)
-        d_seg, d_counts = dbuf[o2:o3], dbuf[o3:]
+        gt_boxes, gt_area, d_seg, d_counts = upload_sections(
+            [np.concatenate([b for b, _ in gts]).reshape(-1, 4), np.concatenate([a for _, a in gts]), seg_off, np.asarray(lens, dtype=np.int32)], dev)
         hits, num_pos, _ = ops.proposal_recall(boxes, logits, d_counts, gt_boxes, gt_area, d_seg, max(per_image), self.area_ranges, self.limits,
                                                self.thresholds)
         sums = (hits.sum(dim=0, dtype=torch.int64), num_pos.sum(dim=0, dtype=torch.int64))

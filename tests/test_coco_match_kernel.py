@@ -72,6 +72,21 @@ def test_bbox_flags_rank_and_match_equal_the_numpy_cocoeval(osr, bbox_ref):
 
 
 @pytest.mark.gpu
+def test_bbox_at_max_det_128_fills_the_second_half_of_the_result_byte(osr, bbox_ref):
+    """The same arrays with max_det = 128, the kernel's limit: the 130 detections of class 0 are ranked up to 127, so the detections
+    64 .. 127 of a pass (bits 2-3 of a lane's result byte) are all in use."""
+    gt, boxes, scores, classes, counts = bbox_ref[:5]
+    flags, rank, match, _, _, _ = reference_outputs(osr, gt, IMAGE_IDS, boxes, scores, classes, counts, "bbox", 128)
+    # conditions on the input
+    assert rank[0].max() == 127 and (rank[0, :155][classes[0, :155] == 0] == -1).sum() == 2
+    assert ((flags[0] & 0xffff).any(axis=1) & (rank[0] >= 100)).any()  # a detection beyond rank 99 is matched
+    f, r, m, _ = device_match(osr, DEV, gt, IMAGE_IDS, boxes, scores, classes, counts, "bbox", 128)
+    assert np.array_equal(r, rank)
+    assert np.array_equal(f, flags)
+    assert np.array_equal(m, match)
+
+
+@pytest.mark.gpu
 def test_repeats_are_bit_identical_and_no_image_launches_nothing(osr, bbox_ref):
     gt, boxes, scores, classes, counts = bbox_ref[:5]
     a = device_match(osr, DEV, gt, IMAGE_IDS, boxes, scores, classes, counts, "bbox", 100)
