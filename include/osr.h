@@ -1084,6 +1084,70 @@ osr_status osr_os_coco_match(const float* boxes, const float* scores, const int6
                              void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * LVIS federated box AP: lvis-api's LVISResults cut, LVISEval._prepare's category filter and LVISEval.evaluate_img,
+ * csrc/osr_lvis_eval.hip. Neither lvis-api nor detectron2 is at hand: the rules are written from memory of lvis-api 0.5.x and
+ * detectron2 v0.6's LVISEvaluator, and THIS TEXT is the contract; host/lvis_evaluation.py's numpy LVISEval states the same rules as
+ * a literal sequential loop and the tests hold the two against each other bit for bit.
+ *
+ * osr_lvis_match: TWO launches (after the memsets that preset the outputs) score n images against their sparse ground truth: a
+ * first kernel cuts and groups each image's detections, a second matches every group for every area range and IoU threshold. The
+ * grid does not grow with the number of categories. No host sync, no atomics, capturable, repeats are bit-identical. Every argument
+ * is validated before anything is launched (no GPU needed for a refusal); n == 0 or cap == 0 is OSR_OK without a launch.
+ *
+ * Detections, the engines' padded lists (need not be sorted): boxes (n, cap, 4) fp32 xyxy, scores (n, cap) fp32, classes (n, cap)
+ * int64 contiguous ids, counts (n) int32 (clamped to 0 .. cap).
+ * Ground truth, built by the host from the JSON, sparse: an ENTRY is one evaluated (image, category): the image has a ground truth
+ * of the category (positive) or lists it in neg_category_ids. img_off (n + 1) int32: image i owns entries img_off[i] .. img_off[i + 1];
+ * ev_cat (NE) int32: the entry's contiguous category, STRICTLY ASCENDING within an image (the kernel looks a class up by binary
+ * search); ev_gt_off (NE + 1) int32: entry e owns ground truths ev_gt_off[e] .. ev_gt_off[e + 1], so the ground truths are stored in
+ * entry order, within an entry in the JSON's annotation order, and a negative entry owns none; ev_flags (NE) uint8: bit 0 = the
+ * category is in the image's not_exhaustive_category_ids. gt_box (NG, 4) fp64 xywh; gt_area (NG) fp64, the JSON's area; gt_flags
+ * (NG) uint8, bit 1 = the annotation's `ignore` field (bit 0, osr_coco_match's crowd bit, is not read: LVIS has no crowds).
+ * max_gt_per_group: the largest entry, which the host knows since it built the table (a longer one is cut there). Every offset is
+ * clamped to its table. Host arrays: iou_thrs (T) fp64, passed as the doubles np.linspace(.5, .95, 10) gives and never recomputed;
+ * area_rng (A, 2) fp64 {lo, hi}; max_dets (lvis-api's 300).
+ *
+ * Per image i:
+ *   - the cut (LVISResults): ALL rows r < counts[i], whatever their class, are ordered by descending score, equal scores the lower
+ *     row first (Python's stable sorted(reverse=True); scores compare by their order-preserving bit key, -0 == +0), and the first
+ *     max_dets are kept. The cut comes BEFORE the category filter;
+ *   - the category filter (_prepare): a kept row of class c is LISTED iff 0 <= c < K and the image has an entry of c. A row that is
+ *     not listed is neither a false positive nor ignored: it does not exist for the evaluation;
+ *   - a group is the listed rows of one entry in the order of the cut. There is no further cut per group. rank (n, cap) int32 is
+ *     the row's position in its group's list, -1 for rows >= counts[i], rows beyond the cut, classes outside [0, K) and categories
+ *     without an entry;
+ *   - detection geometry and similarity are osr_coco_match's for bbox with no crowd: x = x0, y = y0, w = x1 - x0 and h = y1 - y0 in
+ *     fp32, then widened to fp64, area = w * h in fp64; iw = max(min(dx + dw, gx + gw) - max(dx, gx), 0), ih likewise, inter = iw * ih,
+ *     union = (dw * dh + gw * gh) - inter, inter / union, 0 where the union is not positive;
+ *   - in area range a a ground truth is ignored when its ignore bit is set or its area is outside [lo, hi];
+ *   - per threshold t the detections of a group are matched in list order by the rule osr_coco_match states: thr = min(t, 1 - 1e-10);
+ *     a ground truth is available when no earlier detection of this (t, a) took it (there is no crowd re-use); among the available,
+ *     not ignored ones with similarity >= thr the largest similarity wins, equal similarities going to the HIGHEST position in the
+ *     group; if there is none, the same rule among the available ignored ones; else the detection stays unmatched. This equals
+ *     lvis-api's loop over the ground truths sorted ignored-last (stably) with its break;
+ *   - a matched detection is ignored iff its ground truth is ignored at a; an unmatched one iff its own area is outside [lo, hi] OR
+ *     its entry's not-exhaustive bit is set.
+ *
+ * Outputs (all written in full by the call): rank; flags (n, cap, A) uint32 in osr_coco_match's layout, bit t = matched at
+ * threshold t, bit 16 + t = ignored at threshold t, 0 where rank is -1; match (n, cap, A, T) int32 or NULL: the matched ground
+ * truth's index into gt_*, else -1. The similarity blocks go to `sim` when given, else to the head of `workspace`: min(cap,
+ * max_dets) * NG doubles, entry e with G ground truths from g0 = ev_gt_off[e] and M listed detections owns the doubles from
+ * g0 * min(cap, max_dets), [position in the group d][ground truth j] at d * G + j; what lies outside the blocks is not written.
+ * workspace is ALWAYS needed (the group tables the first kernel hands to the second stand behind the similarities):
+ * osr_lvis_match_workspace_bytes(n, cap, max_dets, NG) bytes, 8-byte aligned, OSR_ERR_WORKSPACE when it is smaller.
+ *
+ * Limits, OSR_ERR_UNSUPPORTED with nothing launched beyond them: cap <= 1024, max_dets <= 512, T <= 16, A <= 8, max_gt_per_group
+ * <= 4096. K >= 1 has no upper limit (nothing is sized by it). A NaN score orders by its bit pattern; NaN similarities match nothing.
+ * --------------------------------------------------------------------------------------------------------- */
+int64_t osr_lvis_match_workspace_bytes(int32_t n, int32_t cap, int32_t max_dets, int32_t num_gt);
+osr_status osr_lvis_match(const float* boxes, const float* scores, const int64_t* classes, const int32_t* counts, int32_t n, int32_t cap,
+                          int32_t num_categories, const int32_t* img_off, const int32_t* ev_cat, const int32_t* ev_gt_off,
+                          const uint8_t* ev_flags, int32_t num_entries, const double* gt_box, const double* gt_area, const uint8_t* gt_flags,
+                          int32_t num_gt, int32_t max_gt_per_group, const double* iou_thrs, int32_t num_thrs, const double* area_rng,
+                          int32_t num_areas, int32_t max_dets, uint32_t* flags, int32_t* rank, int32_t* match, double* sim, void* workspace,
+                          int64_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Open-set PASCAL-VOC matching (AP@K, AP@U, wilderness impact, A-OSE): the per-detection half of voc_eval for every class,
  * csrc/osr_voc_eval.hip. The rules below restate host/evaluation.py (PascalVOCDetectionEvaluator.process and voc_eval, themselves a
  * restatement of the reference's pascal_voc_evaluation.py:53-70 and :264-379), and THIS TEXT is the contract; voc_match_reference

@@ -38,6 +38,7 @@ SOURCES = {
     "osr_seg_eval.hip": [],
     "osr_coco_eval.hip": ["-ffp-contract=off"],  # (fp64 similarities that round like numpy's: the bbox flags are bit-exact)
     "osr_os_coco_eval.hip": ["-ffp-contract=off"],  # (the same for the open-set evaluator's three matchings)
+    "osr_lvis_eval.hip": ["-ffp-contract=off"],  # (the same for LVIS: osr_coco_eval.hip's similarities, cut and grouped per image)
     "osr_voc_eval.hip": ["-ffp-contract=off"],  # (the same for the open-set VOC evaluator: record rounding and overlaps in fp64)
     "osr_proposal_recall.hip": ["-ffp-contract=off"],  # (fp32 IoUs that round like torch's on the CPU: the chosen pairs and the hits are bit-exact)
     "osr_roi_align.hip": ["-ffp-contract=off"],

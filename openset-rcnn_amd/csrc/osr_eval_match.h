@@ -2,6 +2,8 @@
 // area-range table, one greedy pass of a wave and one packing of its results into the flag words. Users:
 //   osr_coco_eval.hip        cm_match_kernel   everything
 //   osr_os_coco_eval.hip     om_match_kernel   everything
+//   osr_lvis_eval.hip        lv_group_kernel   the compaction and the rank count (an image's rows, cut across its categories)
+//                            lv_match_kernel   the segment read, the tables, the greedy pass and the flag packer at 512 detections a group
 //   osr_voc_eval.hip         vm_match_kernel   the segment read, the compaction and the rank count
 //   osr_proposal_recall.hip  pr_recall_kernel  the segment read (its limits are its own PR_*: its LDS plan takes 2048 rows, 1024 ground truths)
 // Each of these is a place where a one-sided change would break bit-exactness against numpy: the stable tie order, the
@@ -11,6 +13,8 @@
 //   - what a group and its ground-truth sets are, the set bits of g_meta, and how the similarity matrix is indexed (by rank / by row);
 //   - VOC's argmax / first-rank scheme and proposal recall's rounds, which are other algorithms.
 #pragma once
+#include <type_traits>
+
 #include "osr_common.h"
 
 #define EM_THREADS 1024
@@ -101,13 +105,24 @@ __device__ __forceinline__ void em_wave_best(double& s, int& k, int& j) {
 // candidate among the not-ignored and among the ignored ones, and one wave reduction picks the winner. A crowd never retires; an
 // unmatched detection outside the area range is ignored. row(d): detection d's row of similarities; key_of(j): the tie key of ground
 // truth j (KEYED only); a match g0 + j goes to match0[d_row[d] * match_stride] (match0 null: nowhere). -> the lane's results, two bits
-// per detection (bit 0 matched, bit 1 ignored): bits 0-1 detection `lane`, bits 2-3 detection 64 + `lane`.
-static_assert(EM_MAX_DET <= 128, "a lane's result byte holds two detections");
+// per detection (bit 0 matched, bit 1 ignored): bits 0-1 detection `lane`, bits 2-3 detection 64 + `lane`, and so on.
+// MAX_DET is the most detections a group of the kernel lists. It sizes the word a lane's results are KEPT in (em_res_t: a byte holds
+// two detections, which is EM_MAX_DET = 128 and what the COCO and open-set kernels use; LVIS lists up to 512); the pass itself
+// gathers them in one 32-bit register whatever MAX_DET is.
+template <int MAX_DET>
+struct EmRes {
+    static_assert(MAX_DET >= 64 && MAX_DET <= 1024 && MAX_DET % 64 == 0, "a lane's results are at most one 32-bit register: 16 detections");
+    typedef std::conditional_t<MAX_DET <= 128, uint8_t, std::conditional_t<MAX_DET <= 512, uint16_t, uint32_t>> type;
+};
+template <int MAX_DET>
+using em_res_t = typename EmRes<MAX_DET>::type;
+static_assert(sizeof(em_res_t<EM_MAX_DET>) == 1, "a lane's result byte holds two detections");
 static_assert(EM_MAX_G <= 64 * 64, "a lane's matched bits are one 64-bit register");
 
-template <bool KEYED, class Row, class KeyOf>
+template <bool KEYED, int MAX_DET = EM_MAX_DET, class Row, class KeyOf>
 __device__ __forceinline__ uint32_t em_greedy_pass(const uint16_t* g_meta, int G, int set, double thr, int a, double lo, double hi, const double* d_area,
                                                    const int* d_row, int M, Row row, KeyOf key_of, int32_t* match0, int64_t match_stride, int g0) {
+    static_assert(sizeof(em_res_t<MAX_DET>) * 256 >= MAX_DET, "the caller's result word holds two bits for each of a lane's MAX_DET / 64 detections");
     const int lane = threadIdx.x & 63, steps = (G + 63) >> 6;
     unsigned long long taken = 0;  // bit q: ground truth q * 64 + lane is matched in this pass
     uint32_t acc = 0;
@@ -150,7 +165,8 @@ __device__ __forceinline__ uint32_t em_greedy_pass(const uint16_t* g_meta, int G
 }
 
 // the flag word of detection d from the T passes first_pass .. first_pass + T - 1 of res[pass][lane]: bit t matched, bit 16 + t ignored
-__device__ __forceinline__ uint32_t em_flag_word(const uint8_t (*res)[64], int first_pass, int T, int d) {
+template <int MAX_DET = EM_MAX_DET>
+__device__ __forceinline__ uint32_t em_flag_word(const em_res_t<MAX_DET> (*res)[64], int first_pass, int T, int d) {
     uint32_t w = 0;
     for (int t = 0; t < T; ++t) {
         const uint32_t b = res[first_pass + t][d & 63] >> ((d >> 6) * 2);

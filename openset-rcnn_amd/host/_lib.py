@@ -111,6 +111,7 @@ COCO_BBOX, COCO_KEYPOINTS = 0, 1
 COCO_MAX_CAP, COCO_MAX_DET, COCO_MAX_THRS, COCO_MAX_AREAS, COCO_MAX_KPTS, COCO_MAX_GROUP = 1024, 128, 16, 8, 32, 4096  # csrc/osr_eval_match.h EM_MAX_*, csrc/osr_coco_eval.hip CM_MAX_KP
 OS_COCO_MAX_CAP, OS_COCO_MAX_DET, OS_COCO_MAX_THRS, OS_COCO_MAX_AREAS, OS_COCO_MAX_GT = 1024, 128, 16, 8, 4096  # csrc/osr_eval_match.h EM_MAX_*
 OS_COCO_SETS = 3  # flag words per (detection, area range): own slot, other known, unknown
+LVIS_MAX_CAP, LVIS_MAX_DET, LVIS_MAX_THRS, LVIS_MAX_AREAS, LVIS_MAX_GROUP = 1024, 512, 16, 8, 4096  # csrc/osr_lvis_eval.hip LV_MAX_DET, csrc/osr_eval_match.h EM_MAX_*
 VOC_MAX_CAP, VOC_MAX_GT = 1024, 4096  # csrc/osr_eval_match.h EM_MAX_CAP / EM_MAX_G (the flag bits: host/evaluation.py VOC_*)
 
 
@@ -193,6 +194,8 @@ PROTOTYPES = {
     "osr_coco_match_workspace_bytes": (I64, [I32, I32, I32]),
     "osr_coco_match": (I32, [I32, P, P, P, P, P, I32, I32, I32, I32, P, P, P, P, P, P, I32, I32, P, I32, P, I32, I32, P, P, P, P, P, I64, P]),
     # open-set COCO matching (csrc/osr_os_coco_eval.hip)
+    "osr_lvis_match_workspace_bytes": (I64, [I32, I32, I32, I32]),
+    "osr_lvis_match": (I32, [P, P, P, P, I32, I32, I32, P, P, P, P, I32, P, P, P, I32, I32, P, I32, P, I32, I32, P, P, P, P, P, I64, P]),
     "osr_os_coco_match_workspace_bytes": (I64, [I32, I32]),
     "osr_os_coco_match": (I32, [P, P, P, P, I32, I32, P, I32, I32, P, P, P, P, P, P, I32, I32, P, I32, P, I32, I32, P, P, P, P, I64, P]),
     # open-set VOC matching (csrc/osr_voc_eval.hip)

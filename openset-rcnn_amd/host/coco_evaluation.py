@@ -14,7 +14,9 @@ v0.6 (coco_evaluation.py), and the rules are spelled out in include/osr.h (osr_c
 Outputs that carry "proposals" (a ProposalNetwork's) are scored by host/proposal_evaluation.py: class-agnostic AR@100 / AR@1000 per
 area range, matched on the device by ops.proposal_recall, reported as "box_proposals" ahead of the tasks.
 
-Not built: `segm` (polygon rasterisation and RLE), LVIS, a device accumulate."""
+LVIS names are scored by host/lvis_evaluation.py (federated box AP, matched on the device by ops.lvis_match).
+
+Not built: `segm` (polygon rasterisation and RLE), a device accumulate."""
 from __future__ import annotations
 
 import json

@@ -164,6 +164,58 @@ def register_builtin_coco(root: str) -> None:
                 register_coco_instances(name, {}, jf, os.path.join(coco, f"{split}2017"))
 
 
+def load_lvis_json(json_file: str, image_root: str, dataset_name: Optional[str] = None) -> List[dict]:
+    """[d2] load_lvis_json without lvis-api: one dict per image with file_name (the JSON's, else the last two path parts of coco_url:
+    LVIS v1 names its images "val2017/000000000139.jpg" that way), height, width, image_id, the image's not_exhaustive_category_ids
+    and neg_category_ids (dataset ids, as the JSON has them) and annotations [{bbox XYWH_ABS, category_id (contiguous, ascending
+    dataset id), segmentation (when the json has one, untouched)}]; records the category tables in the dataset's metadata."""
+    import json
+    with open(json_file) as f:
+        data = json.load(f)
+    cats = sorted(data["categories"], key=lambda c: c["id"])
+    id_map = {c["id"]: i for i, c in enumerate(cats)}
+    if dataset_name is not None:
+        meta = MetadataCatalog.get(dataset_name)
+        meta.thing_classes = [c["name"] for c in cats]
+        meta.thing_dataset_id_to_contiguous_id = id_map
+    by_img: Dict[int, List[dict]] = {}
+    for a in data["annotations"]:
+        by_img.setdefault(a["image_id"], []).append(a)
+    out = []
+    for im in sorted(data["images"], key=lambda r: r["id"]):
+        name = im["file_name"] if "file_name" in im else os.path.join(*im["coco_url"].split("/")[-2:])
+        rec = dict(file_name=os.path.join(image_root, name), height=im["height"], width=im["width"], image_id=im["id"],
+                   not_exhaustive_category_ids=list(im.get("not_exhaustive_category_ids", [])), neg_category_ids=list(im.get("neg_category_ids", [])),
+                   annotations=[])
+        for a in by_img.get(im["id"], []):
+            rec["annotations"].append(dict(bbox=list(a["bbox"]), bbox_mode="XYWH_ABS", category_id=id_map[a["category_id"]]))
+            if a.get("segmentation") is not None:
+                rec["annotations"][-1]["segmentation"] = a["segmentation"]
+        out.append(rec)
+    return out
+
+
+def register_lvis_instances(name: str, metadata: dict, json_file: str, image_root: str) -> None:
+    """[d2] register_lvis_instances. `lvis_json` tells get_evaluator that the name is scored with LVISEvaluator: metadata that merely
+    says evaluator_type "lvis" carries no such mark (and no JSON to score against)."""
+    DatasetCatalog.register(name, lambda: load_lvis_json(json_file, image_root, name))
+    meta = MetadataCatalog.get(name)
+    for k, v in dict(metadata).items():
+        setattr(meta, k, v)
+    meta.json_file, meta.image_root, meta.evaluator_type, meta.lvis_json = json_file, image_root, "lvis", True
+
+
+def register_builtin_lvis(root: str) -> None:
+    """lvis_v1_{train,val} and lvis_v0.5_{train,val} under detectron2's directory names, when their files exist: lvis/lvis_<version>_
+    <split>.json with the images under coco/ (the file names carry the split directory). thing_classes come from the JSON's
+    categories, ascending id, when the dataset is loaded or its evaluator built."""
+    for version in ("v1", "v0.5"):
+        for split in ("train", "val"):
+            jf = os.path.join(root, "lvis", f"lvis_{version}_{split}.json")
+            if os.path.isfile(jf):
+                register_lvis_instances(f"lvis_{version}_{split}", {}, jf, os.path.join(root, "coco"))
+
+
 def register_graspnet_os(root: str) -> None:
     for name, jf in GRASPNET_SPLITS.items():
         register_graspnet_instances(name, os.path.join(root, "graspnet_os", "annotations", jf), os.path.join(root, "graspnet_os", "images"))
@@ -265,7 +317,7 @@ def get_evaluator(cfg, dataset_name: str, output_folder=None):
     """train.py:57-78: "pascal_voc" -> open-set VOC evaluator, "coco" -> open-set COCO-style evaluator (GraspNet); [d2] train_net.py:
     "coco" on a register_coco_instances name (metadata closed_set) -> COCOEvaluator (box and keypoint AP; segm is not built),
     "sem_seg" -> SemSegEvaluator, "coco_panoptic_seg" -> SemSegEvaluator + COCOPanopticEvaluator (box AP is not wired into the
-    panoptic datasets)."""
+    panoptic datasets), "lvis" on a register_lvis_instances name (metadata lvis_json) -> LVISEvaluator (federated box AP)."""
     from .evaluation import PascalVOCDetectionEvaluator
     meta = MetadataCatalog.get(dataset_name)
     if getattr(meta, "evaluator_type", None) in ("sem_seg", "coco_panoptic_seg"):
@@ -278,6 +330,11 @@ def get_evaluator(cfg, dataset_name: str, output_folder=None):
         if cfg.MODEL.PANOPTIC_FPN.COMBINE.ENABLED:
             evaluators.append(COCOPanopticEvaluator(dataset_name, output_folder))
         return DatasetEvaluators(evaluators)
+    if getattr(meta, "evaluator_type", None) == "lvis" and getattr(meta, "lvis_json", False):
+        from .lvis_evaluation import LVISEvaluator
+        if not hasattr(meta, "thing_dataset_id_to_contiguous_id"):
+            DatasetCatalog[dataset_name]()  # loading the json fills the category tables
+        return LVISEvaluator(dataset_name, cfg, output_folder)
     if getattr(meta, "evaluator_type", None) == "coco" and getattr(meta, "closed_set", False):
         from .coco_evaluation import COCOEvaluator
         if not hasattr(meta, "thing_dataset_id_to_contiguous_id"):

@@ -1821,6 +1821,48 @@ def coco_match(boxes: torch.Tensor, scores: torch.Tensor, classes: torch.Tensor,
     return flags, rank, match, (sim if want_sim else None)
 
 
+# ---- LVIS federated box matching (csrc/osr_lvis_eval.hip; host/lvis_evaluation.py) ------------------------------------------------------
+def lvis_match(boxes: torch.Tensor, scores: torch.Tensor, classes: torch.Tensor, counts: torch.Tensor, num_categories: int, img_off: torch.Tensor,
+               ev_cat: torch.Tensor, ev_gt_off: torch.Tensor, ev_flags: torch.Tensor, gt_box: torch.Tensor, gt_area: torch.Tensor, gt_flags: torch.Tensor,
+               max_gt_per_group: int, iou_thrs: Sequence[float], area_rng: Sequence[Sequence[float]], max_dets: int, want_match: bool = False,
+               want_sim: bool = False):
+    """A batch of images cut, grouped and scored against its sparse LVIS ground truth in two launches (include/osr.h osr_lvis_match,
+    which states every rule). boxes (n, cap, 4) fp32 xyxy, scores (n, cap) fp32, classes (n, cap) int64, counts (n) int32; img_off
+    (n + 1) int32, per evaluated (image, category) entry ev_cat (NE) int32 ascending within an image, ev_gt_off (NE + 1) int32 and
+    ev_flags (NE) uint8 (bit 0 not exhaustive); gt_box (NG, 4) / gt_area (NG) float64, gt_flags (NG) uint8 (bit 1 ignore); iou_thrs
+    and area_rng are host sequences of doubles.
+    -> (flags (n, cap, A) int32 holding the uint32 words, rank (n, cap) int32, match (n, cap, A, T) int32 or None, sim (min(cap,
+    max_dets) * NG) float64 in the header's layout or None)."""
+    lib = _lib.load()
+    _need(boxes, torch.float32, "boxes"); _need(scores, torch.float32, "scores"); _need(classes, torch.int64, "classes"); _need(counts, torch.int32, "counts")
+    _need(img_off, torch.int32, "img_off"); _need(ev_cat, torch.int32, "ev_cat"); _need(ev_gt_off, torch.int32, "ev_gt_off"); _need(ev_flags, torch.uint8, "ev_flags")
+    _need(gt_box, torch.float64, "gt_box"); _need(gt_area, torch.float64, "gt_area"); _need(gt_flags, torch.uint8, "gt_flags")
+    if boxes.dim() != 3 or boxes.shape[2] != 4:
+        raise OsrError(f"lvis_match: boxes {tuple(boxes.shape)} must be (n, cap, 4)")
+    n, cap = int(boxes.shape[0]), int(boxes.shape[1])
+    ne, ng = int(ev_cat.numel()), int(gt_area.numel())
+    if tuple(scores.shape) != (n, cap) or tuple(classes.shape) != (n, cap) or counts.numel() != n or img_off.numel() != n + 1 or \
+            ev_gt_off.numel() != ne + 1 or ev_flags.numel() != ne or tuple(gt_box.shape) != (ng, 4) or gt_flags.numel() != ng:
+        raise OsrError(f"lvis_match: scores {tuple(scores.shape)} / classes {tuple(classes.shape)} must be {(n, cap)}, counts ({n}), img_off ({n + 1}) "
+                       f"got {img_off.numel()}, ev_gt_off ({ne + 1}) got {ev_gt_off.numel()}, ev_flags ({ne}), gt_box {tuple(gt_box.shape)} ({ng}, 4), "
+                       f"gt_flags ({ng})")
+    thrs = [float(v) for v in iou_thrs]
+    rng = [float(v) for r in area_rng for v in r]
+    t, a = len(thrs), len(rng) // 2
+    dev = boxes.device
+    flags = torch.empty((n, cap, a), dtype=torch.int32, device=dev)
+    rank = torch.empty((n, cap), dtype=torch.int32, device=dev)
+    match = torch.empty((n, cap, a, t), dtype=torch.int32, device=dev) if want_match else None
+    ws_bytes = max(int(lib.osr_lvis_match_workspace_bytes(n, cap, int(max_dets), ng)), 0)
+    ws = torch.empty((ws_bytes // 8,), dtype=torch.float64, device=dev)  # the similarities, then the group tables
+    sim = torch.empty((min(cap, max(int(max_dets), 0)) * ng,), dtype=torch.float64, device=dev) if want_sim else None
+    check(lib.osr_lvis_match(_p(boxes), _p(scores), _p(classes), _p(counts), n, cap, int(num_categories), _p(img_off), _p(ev_cat) if ne else None,
+                             _p(ev_gt_off), _p(ev_flags) if ne else None, ne, _p(gt_box) if ng else None, _p(gt_area) if ng else None,
+                             _p(gt_flags) if ng else None, ng, int(max_gt_per_group), (C.c_double * t)(*thrs), t, (C.c_double * (2 * a))(*rng), a,
+                             int(max_dets), _p(flags), _p(rank), _p(match), _p(sim), _p(ws) if ws_bytes else None, ws_bytes, _stream()), "osr_lvis_match")
+    return flags, rank, match, sim
+
+
 # ---- open-set COCO matching (csrc/osr_os_coco_eval.hip; host/os_coco_evaluation.py) ------------------------------------------------------
 def os_coco_match(boxes: torch.Tensor, scores: torch.Tensor, classes: torch.Tensor, counts: torch.Tensor, class_slot: torch.Tensor, num_known: int,
                   gt_img_off: torch.Tensor, gt_box: torch.Tensor, gt_area: torch.Tensor, gt_slot: torch.Tensor, gt_pos: torch.Tensor,

@@ -8,7 +8,8 @@ reports it for the first stage (os_coco_evaluation.py `_eval_box_proposals`; det
     proposals are kept and scored by the specification. Both paths end in `finish`, so they return equal figures, and the sums of
     several ranks add.
 
-Not built: re-reading stored proposals (MODEL.LOAD_PROPOSALS, --resume_test), LVIS."""
+Not built: re-reading stored proposals (MODEL.LOAD_PROPOSALS, --resume_test), LVIS proposal AR (host/lvis_evaluation.py scores LVIS
+detections and refuses outputs that carry only proposals)."""
 from __future__ import annotations
 
 import os

@@ -98,6 +98,7 @@ def register_datasets(cfg):
     D.register_builtin_pascal_voc(root)
     D.register_coco_panoptic(root)
     D.register_builtin_coco(root)
+    D.register_builtin_lvis(root)
     return D
 
 
